@@ -2,8 +2,15 @@
 """Headline benchmark: images/sec of the RAJNI token-pruning forward, ViT-B/16 @224, bf16,
 README 4-stage schedule, batch 256 per GPU (BASELINE.json configs[1]; configs[2] when --gpus 8).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line; it measures nothing else.
+`--full` adds every side measurement below (the pipelined region with its per-kernel roofline, the HBM-bound kernel
+timings, reference agreement, the opt-ins, the stock-PyTorch and CPU baselines, the other BASELINE configs).
+`--dump-outputs DIR` writes what the last timed step returned (rank 0): DIR/logits.npy (float32 [B, classes]; a fixed
+seeded sample of rows if it would pass 64 MB) and DIR/token_counts.npy (float64).  Weights and images are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 Without a launcher (`WORLD_SIZE` unset) and N > 1 this process never creates a GPU context or launches work: it counts
 the visible devices (exit 3 when fewer than N - there is no silent one-rank run), starts the N ranks as a fresh child
@@ -12,10 +19,10 @@ process through `torch.distributed.run`, relays rank 0's JSON line and exits wit
 A "step" is one forward of one 256-image synthetic batch per GPU, images already resident in HBM.
 `value` is the reference's metric exactly as rajni/eval.py:44-59,74 defines it: it comes out of
 `rajni_amd.evaluate_model` (per batch: sync -> model(images) -> sync, summed; SUM of images / MAX of seconds over
-the ranks), with every profiling hook off.  The K back-to-back forwards behind one sync (host enqueue hidden) are
-timed in a second region and reported as `pipelined_images_per_sec`; that second region is where the HIP-event
+the ranks), with every profiling hook off.  With --full the K back-to-back forwards behind one sync (host enqueue hidden)
+are timed in a second region and reported as `pipelined_images_per_sec`; that second region is where the HIP-event
 kernel timing behind `roofline` runs.
-One JSON line on stdout (rank 0).  Extra objects:
+One JSON line on stdout (rank 0).  Extra objects (--full only):
   roofline     - dominant kernel (the packed-token MFMA GEMM), timed live with HIP events on the
                  launch stream inside the timed region (rajni_profile_* hooks of the C ABI);
   cpu_baseline - the oracle's torch-CPU flavour (oracle/rajni_oracle_torch.py, a port of the reference algorithm
@@ -183,10 +190,17 @@ def parse_args(argv=None):
     ap.add_argument("--residual", default="fp32", choices=["fp32", "bf16"],
                     help="residual stream precision between blocks (RAJNIViTWrapper.set_residual_dtype): fp32 (default, the "
                          "build's accuracy choice) or bf16 (what the reference's own bf16 model keeps)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (pipelined region and roofline, HBM kernel timings, agreement, "
+                         "opt-ins, torch and CPU baselines, other configs); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--no-torch-baseline", action="store_true",
-                    help="skip every side measurement on the GPU (agreement, opt-ins, torch baselines, other configs): profiling runs")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip BASELINE configs[3] / configs[4] (other_configs)")
+                    help="with --full: skip every side measurement on the GPU (agreement, opt-ins, torch baselines, other "
+                         "configs): profiling runs")
+    ap.add_argument("--no-other-configs", action="store_true",
+                    help="with --full: skip BASELINE configs[3] / configs[4] (other_configs)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     return ap.parse_args(argv)
 
@@ -273,6 +287,23 @@ class ResidentLoader:
     def __iter__(self):
         for _ in range(self.n):
             yield self.images, self.labels
+
+
+DUMP_BYTES = 64 << 20
+
+
+def write_outputs(dirname, arrays):
+    """`--dump-outputs`: each array as DIR/<name>.npy, float64 kept, everything else float32 (bf16 logits widen exactly).
+    An array past its share of DUMP_BYTES keeps a fixed seeded sample of its rows (sorted), the same on every run."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], share // (a.nbytes // a.shape[0]), replace=False))
+            print(f"bench.py: {name}: {len(rows)} of {a.shape[0]} rows written (seeded sample)", file=sys.stderr)
+            a = a[rows]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def gemm_roofline(prof):
@@ -401,6 +432,8 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args, argv)
     return worker(args)
@@ -475,33 +508,46 @@ def worker(args):
     for _ in range(args.warmup):
         wrapped(images)
     barrier()
+    last = []      # --dump-outputs: the logits each timed step returns (the hook keeps the newest only)
+
+    def keep_last(mod, inp, out):
+        last[:] = [out]
+    hook = wrapped.register_forward_hook(keep_last) if args.dump_outputs else None
     w0 = time.perf_counter()
     value = metric_run(wrapped, images, labels, args.steps, dev)   # already the whole-job figure (all-reduced inside)
     barrier()
     wall = time.perf_counter() - w0
     per_rank = list(rajni_amd.evaluate_model.last_stats["per_rank"])   # every rank's own (images, seconds), same all-reduce
     counts = wrapped.get_last_stats()["token_counts"]
+    if hook is not None:
+        hook.remove()
+        if rank == 0:
+            write_outputs(args.dump_outputs, {"logits": last[0].float().cpu().numpy(),
+                                              "token_counts": np.asarray(counts, dtype=np.float64)})
 
-    # ---- second region: K back-to-back forwards behind one sync, HIP-event timing of the GEMM classes on
+    # ---- second region (--full): K back-to-back forwards behind one sync, HIP-event timing of the GEMM classes on
     # the packed-token GEMM classes: qkv/head, fc1, fc2 (K > N), proj (K <= N), and their fp8 x fp8 twins (13-15)
-    nat.profile_reset()
-    nat.profile_enable(GEMM_MASK)
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        wrapped(images)
-    barrier()
-    elapsed = time.perf_counter() - t0
-    nat.profile_enable(0)
+    elapsed, prof = None, {}
+    if args.full:
+        nat.profile_reset()
+        nat.profile_enable(GEMM_MASK)
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            wrapped(images)
+        barrier()
+        elapsed = time.perf_counter() - t0
+        nat.profile_enable(0)
+        prof = nat.profile_collect()
     if dist is not None:
-        t = torch.tensor([elapsed, wall], dtype=torch.float64, device=red_dev)
+        t = torch.tensor([elapsed or 0.0, wall], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, wall = (float(v) for v in t.tolist())
-    prof = nat.profile_collect()
+        e, wall = (float(v) for v in t.tolist())
+        elapsed = e if args.full else None
     # the HBM-bound part of the path (score -> top-k -> compact, the keep_idx gather fused into the attention
     # loads, LayerNorm): HIP-event timing of a few extra forwards
     hbm_prof = {}
-    if world == 1:
+    if world == 1 and args.full:
         nat.profile_reset()
         nat.profile_enable((1 << 4) | (1 << 5) | (1 << 6))
         for _ in range(5):
@@ -569,8 +615,8 @@ def worker(args):
            "timing": "rajni_amd.evaluate_model: sum over K batches of (sync -> forward -> sync), reference eval.py:51-59,74; "
                      "MAX over ranks; profiling hooks off",
            "wall_ms_per_step": round(wall / args.steps * 1e3, 3),
-           "pipelined_images_per_sec": round(world * B * args.steps / elapsed, 1),
-           "pipelined_ms_per_step": round(elapsed / args.steps * 1e3, 3),
+           **({"pipelined_images_per_sec": round(world * B * args.steps / elapsed, 1),
+               "pipelined_ms_per_step": round(elapsed / args.steps * 1e3, 3)} if args.full else {}),
            # every rank's own rate out of evaluate_model's one all-reduce: which rank set the node time, and the spread
            "per_rank_images_per_sec": {"list": [round(r, 1) for r in rates], "min": round(min(rates), 1),
                                        "max": round(max(rates), 1)},
@@ -588,11 +634,12 @@ def worker(args):
                       "collective": (f"{backend} all_reduce (SUM) of [correct,total,images] + one (images, seconds) slot per rank, "
                                      "once per run; node seconds = MAX over the slots" if world > 1 else None)},
            "model_tflops": round(value * fl_img / 1e12, 1),
-           "model_mfma_frac": round(value * fl_img / 1e12 / (peak_tflops * world), 4),
-           "roofline": roofline}
+           "model_mfma_frac": round(value * fl_img / 1e12 / (peak_tflops * world), 4)}
+    if args.full:
+        out["roofline"] = roofline
 
-    side = world == 1 and not args.no_torch_baseline   # (side measurements are skipped together: profiling runs - their
-    # forwards of other shapes would skew per-kernel averages)
+    # (side measurements are skipped together: profiling runs - their forwards of other shapes would skew per-kernel averages)
+    side = args.full and world == 1 and not args.no_torch_baseline
     vitb_workload = args.model == "vit_base_patch16_224" and not args.schedule
     if vitb_workload and side:   # for the opt-in formats it prices their numerics contract
         out["reference_agreement"] = reference_agreement(dev, weight_format=args.weight_format, residual=args.residual)
@@ -638,7 +685,7 @@ def worker(args):
             side_config(dev, "BASELINE.json configs[4]", "deit3_base_patch16_224", 512, README_SCHEDULE, "fp8_mfma", "fp32", ksteps),
             side_config(dev, "BASELINE.json configs[4], bf16 residual stream", "deit3_base_patch16_224", 512, README_SCHEDULE,
                         "fp8_mfma", "bf16", ksteps)]
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, schedule, args.cpu_seconds)
     print(json.dumps(out), flush=True)
     if dist is not None:

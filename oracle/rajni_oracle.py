@@ -9,7 +9,7 @@ Pinning: the reference holds no tests or golden vectors of its own (SURVEY.md se
 pinned by outputs of the reference itself, run in the authoring container on CPU:
 `tests/golden/make_golden.py` imports `/root/reference/rajni` and writes `tests/golden/*.npz`;
 `tests/test_oracle_golden.py` checks every function here against those fixtures, and
-`tests/test_oracle_vs_reference.py` checks it against the live import when `/root/reference` exists.
+`tests/test_oracle_vs_reference.py` checks it against more of them (other head dims, patch 14, LayerScale, odd ratios).
 Parity vs *real timm* for the patch-embed / unpruned-block / head code is unpinned (timm is not in
 the image); those parts follow timm's documented block semantics.
 

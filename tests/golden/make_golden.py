@@ -268,6 +268,51 @@ def agreement_case(ref, refw, name="base224_agree256", cfg_name="vit_base_patch1
           f"median top-2 margin {meta['median_top2_margin']:.4f}")
 
 
+def oracle_vs_reference_cases(ref, refw):
+    """The reference's outputs for tests/test_oracle_vs_reference.py: compute_importance, RAJNIViTWrapper.forward
+    (logits, token counts, keep_idx of every stage) and RAJNIAttention.forward on the inputs that file builds."""
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_oracle_vs_reference as t
+    out = {}
+    for B, N, H, D in t.IMPORTANCE_SHAPES:
+        out[f"imp.{B}-{N}-{H}-{D}"] = refw.compute_importance(torch.from_numpy(t.importance_inputs(B, N, H, D)), H).numpy()
+
+    orig = refw.RAJNIAttention.forward
+    for case in range(len(t.CASES)):
+        # the reference mutates the model it wraps (model.py:16-21): it gets its own copy
+        _, schedule, ref_model, images = t.forward_inputs(case)
+        trace = {}
+
+        def recording(self, x, prev_scores=None):
+            o, keep_idx, nxt = orig(self, x, prev_scores)
+            trace[self._blk] = keep_idx.numpy().copy()
+            return o, keep_idx, nxt
+
+        wrapped = ref.RAJNIViTWrapper(ref_model, {int(k): dict(v) for k, v in schedule.items()}).eval()
+        for i, blk in enumerate(wrapped.blocks):
+            if getattr(blk, "has_pruner", False):
+                blk.attn._blk = i
+        refw.RAJNIAttention.forward = recording
+        try:
+            with torch.no_grad():
+                out[f"fwd{case}.logits"] = wrapped(torch.from_numpy(images)).numpy()
+        finally:
+            refw.RAJNIAttention.forward = orig
+        out[f"fwd{case}.token_counts"] = np.asarray(wrapped.get_last_stats()["token_counts"], np.int64)
+        for i, idx in trace.items():
+            out[f"fwd{case}.blk{i}.keep_idx"] = idx
+
+    cfg, x, variants = t.attention_inputs()
+    for j, (update, prev) in enumerate(variants):
+        attn = refw.RAJNIAttention(ts.create_model(cfg, seed=9, std=0.1, bias_std=0.05).blocks[0].attn, 0.6, update)
+        with torch.no_grad():
+            o, idx, nxt = attn(torch.from_numpy(x), None if prev is None else torch.from_numpy(prev))
+        out[f"attn{j}.out"], out[f"attn{j}.keep_idx"], out[f"attn{j}.next_scores"] = o.numpy(), idx.numpy(), nxt.numpy()
+    np.savez_compressed(os.path.join(HERE, "oracle_vs_reference.npz"), **out)
+    print("oracle_vs_reference written:", len(out), "arrays")
+
+
 def main():
     torch.manual_seed(0)
     torch.set_num_threads(8)
@@ -293,6 +338,8 @@ def main():
         run_case(ref, refw, *c)
     if not only or "base224_agree256" in only:
         agreement_case(ref, refw)
+    if not only or "oracle_vs_reference" in only:
+        oracle_vs_reference_cases(ref, refw)
 
 
 if __name__ == "__main__":

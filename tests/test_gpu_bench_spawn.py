@@ -47,3 +47,43 @@ def test_bench_refuses_when_devices_are_missing():
     r = _run(["--gpus", str(n + 1), "--steps", "2"], {"RAJNI_BENCH_ONE_DEVICE": "0"})
     assert r.returncode == 3, (r.returncode, r.stderr[-500:])
     assert r.stdout.strip() == "" and f"needs {n + 1} visible" in r.stderr
+
+
+def test_plain_run_times_k_steps_and_dumps_the_last_one(tmp_path):
+    """`python bench.py --steps K --dump-outputs DIR`: the line reports K timed steps and only the headline (the side
+    measurements are `--full`'s); DIR holds the logits of the last timed step, which are the forward of the seeded
+    model on the seeded images."""
+    import importlib.util
+
+    import numpy as np
+    import torch
+
+    import rajni_amd
+    from rajni_amd import timm_shaped as ts
+
+    r = _run(["--steps", "3", "--warmup", "1", "--batch", "16", "--dump-outputs", str(tmp_path)], {})
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["unit"] == "images/sec" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert abs(d["ms_per_step"] - 16 / d["value"] * 1e3) < 1e-2
+    for k in ("roofline", "pipelined_images_per_sec", "hbm_kernels", "reference_agreement", "cpu_baseline",
+              "unpruned_torch_images_per_sec", "other_configs"):
+        assert k not in d, k
+    logits = np.load(tmp_path / "logits.npy")
+    assert logits.dtype == np.float32 and logits.shape == (16, 1000) and np.isfinite(logits).all()
+    assert np.load(tmp_path / "token_counts.npy").tolist() == d["config"]["token_counts"]
+
+    spec = importlib.util.spec_from_file_location("rajni_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    dev = torch.device("cuda", 0)
+    cfg = ts.CONFIGS["vit_base_patch16_224"]
+    wrapped = rajni_amd.RAJNIViTWrapper(ts.create_model(cfg, seed=0).to(torch.bfloat16).to(dev), bench.README_SCHEDULE).eval()
+    gen = torch.Generator(device=dev).manual_seed(1234)
+    images = torch.randn(16, 3, cfg.img_size, cfg.img_size, generator=gen, device=dev).to(torch.bfloat16)
+    want = wrapped(images).float().cpu().numpy()
+    scale = float(np.abs(want).max())
+    assert float(np.abs(logits - want).max()) <= 1e-2 * scale

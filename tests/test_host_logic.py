@@ -336,6 +336,28 @@ def test_bench_refuses_fewer_devices_than_ranks(monkeypatch, capsys):
         bench.main(["--gpus", "8"])
 
 
+def test_bench_options_and_output_dump(tmp_path, monkeypatch):
+    """A plain run measures the headline only (`--full` off by default); `--dump-outputs` writes float32 / float64 .npy
+    files and keeps a large array within 64 MB as the same seeded sample of rows on every call."""
+    bench = _load_bench()
+    a = bench.parse_args(["--steps", "7", "--dump-outputs", str(tmp_path / "d")])
+    assert a.steps == 7 and not a.full and a.dump_outputs == str(tmp_path / "d")
+    assert bench.parse_args(["--full"]).full
+    logits = torch.randn(4, 10).to(torch.bfloat16).float().numpy()
+    bench.write_outputs(str(tmp_path / "d"), {"logits": logits, "token_counts": np.array([197.0, 173.0])})
+    got = np.load(tmp_path / "d" / "logits.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, logits)
+    tc = np.load(tmp_path / "d" / "token_counts.npy")
+    assert tc.dtype == np.float64 and tc.tolist() == [197.0, 173.0]
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 10 * 4 * 100)          # room for 100 rows of 10 floats per array
+    big = np.arange(1000 * 10, dtype=np.float64).reshape(1000, 10).astype(np.float16)
+    for sub in ("s1", "s2"):
+        bench.write_outputs(str(tmp_path / sub), {"logits": big, "x": np.zeros(3)})
+    s1, s2 = np.load(tmp_path / "s1" / "logits.npy"), np.load(tmp_path / "s2" / "logits.npy")
+    assert s1.dtype == np.float32 and s1.shape == (100, 10) and np.array_equal(s1, s2)
+    assert (np.diff(s1[:, 0]) > 0).all() and np.isin(s1, big.astype(np.float32)).all()
+
+
 def test_fp8_row_quantiser_properties():
     """ops.quantize_rows_fp8 / pack_weight_fp8 (host side of the fp8-weight path): per-row
     scale maps the row maximum onto +-448, zero rows are harmless, RNE error bound, padded layout."""

@@ -1,12 +1,10 @@
-"""The oracles against the LIVE reference (authoring container only: skipped where /root/reference is absent,
-i.e. on the GPU box).  The committed fixtures in tests/golden/ pin the oracles on fixed seeds; this file re-runs the
-comparison on fresh random inputs every time, for shapes the fixtures do not hold (other head dims, patch 14, LayerScale,
-`update=False` stages, odd keep ratios).  The reference is imported read-only under an alias, exactly as
-tests/golden/make_golden.py does; nothing of it is copied.
+"""The oracles against the reference's own outputs for shapes the other fixtures in tests/golden/ do not hold (other head
+dims, patch 14, LayerScale, `update=False` stages, odd keep ratios).  The inputs are built from seeds by the functions
+below; what the reference computed from them (`tests/golden/make_golden.py::oracle_vs_reference_cases`, the reference
+imported read-only under an alias, nothing of it copied) is stored in tests/golden/oracle_vs_reference.npz, so the
+comparison runs anywhere.
 """
-import importlib.util
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -16,28 +14,27 @@ from oracle import rajni_oracle as orc
 from oracle import rajni_oracle_torch as ort
 from rajni_amd import timm_shaped as ts
 
-REF_DIR = "/root/reference/rajni"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_DIR), reason="the reference is only mounted in the authoring container")
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_vs_reference.npz")
 
 
 @pytest.fixture(scope="module")
 def ref():
-    sys.dont_write_bytecode = True
-    spec = importlib.util.spec_from_file_location("rajni_ref", os.path.join(REF_DIR, "__init__.py"),
-                                                  submodule_search_locations=[REF_DIR])
-    mod = importlib.util.module_from_spec(spec)
-    sys.modules["rajni_ref"] = mod
-    spec.loader.exec_module(mod)
-    import rajni_ref.wrapper as w
-    return mod, w
+    with np.load(FIXTURE) as f:
+        return dict(f)
 
 
-@pytest.mark.parametrize("B,N,H,D", [(2, 197, 12, 64), (3, 50, 4, 80), (1, 257, 16, 80), (2, 17, 2, 32), (2, 33, 3, 128), (4, 2, 1, 8)])
-def test_importance_on_fresh_inputs(ref, B, N, H, D):
-    _, w = ref
+IMPORTANCE_SHAPES = [(2, 197, 12, 64), (3, 50, 4, 80), (1, 257, 16, 80), (2, 17, 2, 32), (2, 33, 3, 128), (4, 2, 1, 8)]
+
+
+def importance_inputs(B, N, H, D):
     rng = np.random.default_rng(B * 1000 + N + D)
-    qkv = rng.standard_normal((B, N, 3 * H * D), dtype=np.float32) * rng.choice([0.3, 1.0, 3.0])
-    want = w.compute_importance(torch.from_numpy(qkv), H).numpy()          # importance.py:4-34
+    return rng.standard_normal((B, N, 3 * H * D), dtype=np.float32) * rng.choice([0.3, 1.0, 3.0])
+
+
+@pytest.mark.parametrize("B,N,H,D", IMPORTANCE_SHAPES)
+def test_importance_on_fresh_inputs(ref, B, N, H, D):
+    qkv = importance_inputs(B, N, H, D)
+    want = ref[f"imp.{B}-{N}-{H}-{D}"]                                     # importance.py:4-34
     np.testing.assert_allclose(orc.importance_scores(qkv, H), want, rtol=3e-5, atol=1e-8)
     np.testing.assert_allclose(ort.importance_scores(torch.from_numpy(qkv), H).numpy(), want, rtol=3e-5, atol=1e-8)
 
@@ -55,39 +52,26 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", range(len(CASES)))
-def test_forward_on_fresh_models(ref, case):
-    """RAJNIViTWrapper.forward of the reference on a freshly seeded timm-shaped model == both oracles: token counts
-    exactly; logits to fp32 round-off when the selections coincide (they do unless two scores tie in fp32)."""
-    mod, w = ref
+def forward_inputs(case):
+    """(cfg, schedule, model, images) of CASES[case]: a freshly seeded timm-shaped model and its images."""
     kw, schedule, batch = CASES[case]
     cfg = ts.ViTConfig(**kw)
     seed = 4242 + case
     model = ts.create_model(cfg, seed=seed, std=0.08, bias_std=0.02)
-    sd = ts.state_dict_numpy(model)
     images = np.random.default_rng(seed).standard_normal((batch, 3, cfg.img_size, cfg.img_size), dtype=np.float32)
+    return cfg, schedule, model, images
 
-    # the reference mutates the model it wraps (model.py:16-21): give it its own copy
-    ref_model = ts.create_model(cfg, seed=seed, std=0.08, bias_std=0.02)
-    trace = {}
-    orig = w.RAJNIAttention.forward
 
-    def recording(self, x, prev_scores=None):
-        out, keep_idx, nxt = orig(self, x, prev_scores)
-        trace[self._blk] = keep_idx.numpy().copy()
-        return out, keep_idx, nxt
-
-    wrapped = mod.RAJNIViTWrapper(ref_model, {int(k): dict(v) for k, v in schedule.items()}).eval()
-    for i, blk in enumerate(wrapped.blocks):
-        if getattr(blk, "has_pruner", False):
-            blk.attn._blk = i
-    w.RAJNIAttention.forward = recording
-    try:
-        with torch.no_grad():
-            want = wrapped(torch.from_numpy(images)).numpy()
-    finally:
-        w.RAJNIAttention.forward = orig
-    counts = wrapped.get_last_stats()["token_counts"]
+@pytest.mark.parametrize("case", range(len(CASES)))
+def test_forward_on_fresh_models(ref, case):
+    """RAJNIViTWrapper.forward of the reference on a freshly seeded timm-shaped model == both oracles: token counts
+    exactly; logits to fp32 round-off when the selections coincide (they do unless two scores tie in fp32)."""
+    cfg, schedule, model, images = forward_inputs(case)
+    sd = ts.state_dict_numpy(model)
+    want = ref[f"fwd{case}.logits"]
+    counts = ref[f"fwd{case}.token_counts"].tolist()
+    prefix = f"fwd{case}.blk"
+    trace = {int(k[len(prefix):-len(".keep_idx")]): v for k, v in ref.items() if k.startswith(prefix)}
 
     got, stats, tr = orc.vit_forward(sd, images, schedule, depth=cfg.depth, num_heads=cfg.num_heads, ln_eps=cfg.ln_eps,
                                      dtype=np.float64, return_trace=True)
@@ -105,20 +89,26 @@ def test_forward_on_fresh_models(ref, case):
     np.testing.assert_allclose(got_t.numpy(), want, rtol=0, atol=2e-4 * scale)
 
 
+ATTENTION_CFG = dict(img_size=64, embed_dim=128, depth=1, num_heads=2, num_classes=3)
+
+
+def attention_inputs():
+    """(cfg, x, [(update, prev_scores)]) of the RAJNIAttention contract cases; weights are create_model(cfg, seed=9, ...)."""
+    cfg = ts.ViTConfig(**ATTENTION_CFG)
+    x = np.random.default_rng(1).standard_normal((3, 17, 128), dtype=np.float32)
+    variants = [(True, None), (False, np.random.default_rng(2).random((3, 17), dtype=np.float32)), (False, None)]
+    return cfg, x, variants
+
+
 def test_rajni_attention_forward_contract(ref):
     """RAJNIAttention.forward(x, prev_scores) -> (out, keep_idx int64 ascending with CLS first, next_scores), with
     and without carried scores (attention.py:17-60) == oracle.rajni_attention on the same weights."""
-    _, w = ref
-    cfg = ts.ViTConfig(img_size=64, embed_dim=128, depth=1, num_heads=2, num_classes=3)
-    model = ts.create_model(cfg, seed=9, std=0.1, bias_std=0.05)
-    sd = ts.state_dict_numpy(model)
-    x = np.random.default_rng(1).standard_normal((3, 17, 128), dtype=np.float32)
-    for update, prev in ((True, None), (False, np.random.default_rng(2).random((3, 17), dtype=np.float32)), (False, None)):
-        attn = w.RAJNIAttention(ts.create_model(cfg, seed=9, std=0.1, bias_std=0.05).blocks[0].attn, 0.6, update)
-        with torch.no_grad():
-            out, idx, nxt = attn(torch.from_numpy(x), None if prev is None else torch.from_numpy(prev))
+    cfg, x, variants = attention_inputs()
+    sd = ts.state_dict_numpy(ts.create_model(cfg, seed=9, std=0.1, bias_std=0.05))
+    for j, (update, prev) in enumerate(variants):
+        out, idx, nxt = ref[f"attn{j}.out"], ref[f"attn{j}.keep_idx"], ref[f"attn{j}.next_scores"]
         o, i, n, _ = orc.rajni_attention(x, sd, "blocks.0.attn.", 2, 0.6, update, prev)
-        assert idx.dtype == torch.int64 and (idx[:, 0] == 0).all() and (idx[:, 1:] > idx[:, :-1]).all()
-        np.testing.assert_array_equal(i, idx.numpy())
-        np.testing.assert_allclose(o, out.numpy(), rtol=0, atol=2e-5)
-        np.testing.assert_allclose(n, nxt.numpy(), rtol=2e-5, atol=1e-8)
+        assert idx.dtype == np.int64 and (idx[:, 0] == 0).all() and (idx[:, 1:] > idx[:, :-1]).all()
+        np.testing.assert_array_equal(i, idx)
+        np.testing.assert_allclose(o, out, rtol=0, atol=2e-5)
+        np.testing.assert_allclose(n, nxt, rtol=2e-5, atol=1e-8)
