@@ -111,11 +111,13 @@ def test_keep_ratio_one_and_empty_schedule_equal_base():
     """keep_ratio=1.0 and an empty schedule are the unpruned network."""
     cfg = ts.CONFIGS["vit_micro_patch16_64"]
     imgs = torch.from_numpy(ts.bf16_round_np(np.random.default_rng(0).standard_normal((3, 3, 64, 64), dtype=np.float32))).to(DEV)
-    outs = []
+    outs, live = [], []
     for sched in ({}, {1: {"keep_ratio": 1.0}, 2: {"keep_ratio": 1.0, "update": False}}):
         m = ts.create_model(cfg, seed=5, std=0.08, bias_std=0.02, round_bf16=True)
         w = rajni_amd.RAJNIViTWrapper(m, sched).to(DEV).to(torch.bfloat16)
-        outs.append(w(imgs).float().cpu())
+        y = w(imgs)
+        live.append((w, y))      # the first wrapper and its device result stay alive: the second cannot inherit them
+        outs.append(y.float().cpu())
         assert w.get_last_stats()["token_counts"] == [17] * 4
     assert torch.equal(outs[0], outs[1])
     base = ts.create_model(cfg, seed=5, std=0.08, bias_std=0.02, round_bf16=True).to(DEV).to(torch.bfloat16)
@@ -386,8 +388,9 @@ def test_cls_only_last_block_is_skipped_when_the_last_block_prunes():
     model = ts.create_model(cfg, seed=2, std=0.08, bias_std=0.02, round_bf16=True)
     w = rajni_amd.RAJNIViTWrapper(model, {3: {"keep_ratio": 0.5}}).to(DEV).to(torch.bfloat16).eval()
     x = torch.randn(3, 3, 64, 64, device=DEV).to(torch.bfloat16)
-    a = w(x).float()
-    b = w.set_last_block_cls_only(True)(x).float()
+    ya = w(x)                    # kept alive until the second call has returned: it cannot inherit this block
+    yb = w.set_last_block_cls_only(True)(x)
+    a, b = ya.float(), yb.float()
     assert torch.equal(a, b) and w.get_last_trace()[3]["keep_idx"].shape[1] == orc.keep_count(0.5, 17) + 1
 
 

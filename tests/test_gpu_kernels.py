@@ -151,11 +151,15 @@ def test_linear_tile_order_blocks_do_not_change_results(nblk, tiling):
     x = torch.randn(M, K, device=DEV).to(torch.bfloat16)
     w = ops.pack_weight((torch.randn(N, K, device=DEV) * 0.1).to(torch.bfloat16))
     b = torch.randn(N, device=DEV)
+    # two separate, live output buffers prefilled with NaN: a launch that skipped tiles cannot inherit the other's values
+    ref = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=DEV)
+    got = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=DEV)
     nat.lib().rajni_debug_set_gemm_nblock_bytes(0)
     try:
-        ref = ops.linear(x, w, N, b, nat.EPI_BIAS_GELU).clone()
+        ops.linear(x, w, N, b, nat.EPI_BIAS_GELU, out=ref)
         nat.lib().rajni_debug_set_gemm_nblock_bytes(-nblk)
-        got = ops.linear(x, w, N, b, nat.EPI_BIAS_GELU)
+        ops.linear(x, w, N, b, nat.EPI_BIAS_GELU, out=got)
+        assert not torch.isnan(got).any()
         assert torch.equal(got, ref)
     finally:
         nat.lib().rajni_debug_set_gemm_nblock_bytes(1600 * 1024)
