@@ -9,8 +9,11 @@
  *   - every launch goes to the hipStream_t given (pass torch's current stream);
  *   - returns RAJNI_OK (0) or an error code; rajni_last_error() gives a host string (thread local);
  *   - `dtype` is the activation/weight element type of the model: RAJNI_BF16 (the fast path: bf16
- *     MFMA, fp32 accumulation) or RAJNI_F32 (accuracy path: every tensor fp32, v_mfma_f32_16x16x4_f32
- *     GEMMs, VALU attention; ~1/16 of the bf16 MFMA rate).
+ *     MFMA, fp32 accumulation), RAJNI_F16 (fp16 models: the same kernels, tilings and fusion on the f16
+ *     MFMA forms - same rate, 3 more mantissa bits; outputs rounded to nearest even, overflow to +-inf;
+ *     fp8 weights / activations need RAJNI_BF16 and return RAJNI_ERR_UNSUPPORTED with it) or RAJNI_F32
+ *     (accuracy path: every tensor fp32, v_mfma_f32_16x16x4_f32 GEMMs, VALU attention; ~1/16 of the
+ *     16-bit MFMA rate).
  *   - activations are row-major [B, N, C]; qkv is [B, N, 3*C] with the last axis laid out
  *     [3][H][D] (timm convention; importance.py:14, attention.py:46-47);
  *   - keep_idx is int32 on the device ([B, keep+1], slot 0 = CLS = 0, rest ascending); the Python
@@ -28,7 +31,7 @@ extern "C" {
 
 typedef void* rajni_stream_t; /* hipStream_t */
 
-enum { RAJNI_F32 = 0, RAJNI_BF16 = 1 };
+enum { RAJNI_F32 = 0, RAJNI_BF16 = 1, RAJNI_F16 = 2 };
 
 enum {
   RAJNI_OK = 0,
@@ -133,7 +136,7 @@ typedef struct {
   int M, N, K;
   int epilogue;
   int dtype;
-  int stream_f32;  /* RESID only: resid and y are the fp32 residual stream (1) instead of `dtype` (0) */
+  int stream_f32;  /* RESID only: resid and y are the fp32 residual stream (1) instead of `dtype` (0: a bf16 or fp16 stream) */
   /* fp8 weights (BASELINE config 5): when non-NULL, `w` holds fp8 e4m3 (OCP "fn": no inf, max 448) bytes
    * [N(pad256),K], ldw in bytes and a multiple of 16, and w_scale[n] (fp32 [N]) is the dequantisation
    * scale of row n: y = epi(x (q*s)^T) with bf16 x and fp32 accumulation.  dtype must be RAJNI_BF16. */
@@ -209,7 +212,9 @@ typedef struct {
                                                   reference's op graph */
   int resid_bf16;                              /* 0 (default): the residual stream x is kept in fp32 between
                                                   blocks (2x closer to the fp32 reference than a bf16 stream, see
-                                                  DESIGN.md); 1: keep it in bf16 like the reference's bf16 model */
+                                                  DESIGN.md); 1: keep it in the model's 16-bit dtype (bf16 or fp16)
+                                                  like the reference's 16-bit model.  (The name predates fp16 models;
+                                                  ignored for RAJNI_F32) */
   int act_fp8;                                 /* 1 (opt-in, needs e4m3 block weights): norm1 / norm2 emit per-row
                                                   scaled e4m3 activations, QKV / FC1 / FC2 run on the fp8 matrix
                                                   pipe, FC1's GELU epilogue re-quantises the hidden activations

@@ -62,6 +62,8 @@ __device__ __forceinline__ bf16x8 tr_pair(const char* sv, int row, int col) {
   return __builtin_bit_cast(bf16x8, v);
 }
 
+// A: the 16-bit operand format of every kernel below (bf16_t or f16_t: the MFMA form and the rounding of P and O)
+template <typename A = bf16_t>
 __global__ void __launch_bounds__(AT_THREADS) attn_bf16_d64(const AttnArgs a) {
   __shared__ __attribute__((aligned(16))) char smem[AT_LDS];
   char* sk = smem;
@@ -130,7 +132,7 @@ __global__ void __launch_bounds__(AT_THREADS) attn_bf16_d64(const AttnArgs a) {
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
           const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sk + k_off(krow, 2 * ks + h));
-          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], s, 0, 0, 0);
+          s = mfma_32x32x16<A>(kf, qf[ks], s);
         }
         const int nvalid = np - c0 - kb * 32;  // keys of this sub-block that exist
         if (nvalid < 32) {
@@ -172,8 +174,8 @@ __global__ void __launch_bounds__(AT_THREADS) attn_bf16_d64(const AttnArgs a) {
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
           typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-          const u32x4 w = {pack2bf(p[8 * s2 + 0], p[8 * s2 + 1]), pack2bf(p[8 * s2 + 2], p[8 * s2 + 3]),
-                           pack2bf(p[8 * s2 + 4], p[8 * s2 + 5]), pack2bf(p[8 * s2 + 6], p[8 * s2 + 7])};
+          const u32x4 w = {pack2<A>(p[8 * s2 + 0], p[8 * s2 + 1]), pack2<A>(p[8 * s2 + 2], p[8 * s2 + 3]),
+                           pack2<A>(p[8 * s2 + 4], p[8 * s2 + 5]), pack2<A>(p[8 * s2 + 6], p[8 * s2 + 7])};
           pb[s2] = __builtin_bit_cast(bf16x8, w);
         }
         // ---- O^T += V^T P^T ; lane (d = l31 of the d-tile, half h) needs keys 16s+4h+{0..3} and +8
@@ -183,8 +185,8 @@ __global__ void __launch_bounds__(AT_THREADS) attn_bf16_d64(const AttnArgs a) {
           const int col = 16 * (g & 1) + 4 * (l15 & 3);
           const bf16x8 v0 = tr_pair(sv, key0, col);
           const bf16x8 v1 = tr_pair(sv, key0, 32 + col);
-          o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v0, pb[s2], o0, 0, 0, 0);
-          o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v1, pb[s2], o1, 0, 0, 0);
+          o0 = mfma_32x32x16<A>(v0, pb[s2], o0);
+          o1 = mfma_32x32x16<A>(v1, pb[s2], o1);
         }
       }
     }
@@ -200,10 +202,10 @@ __global__ void __launch_bounds__(AT_THREADS) attn_bf16_d64(const AttnArgs a) {
     for (int t = 0; t < 4; ++t) {
       // registers 4t..4t+3 of a d-tile are d = 8t + 4h + {0..3}
       uint2 w0, w1;
-      w0.x = pack2bf(o0[4 * t] * inv, o0[4 * t + 1] * inv);
-      w0.y = pack2bf(o0[4 * t + 2] * inv, o0[4 * t + 3] * inv);
-      w1.x = pack2bf(o1[4 * t] * inv, o1[4 * t + 1] * inv);
-      w1.y = pack2bf(o1[4 * t + 2] * inv, o1[4 * t + 3] * inv);
+      w0.x = pack2<A>(o0[4 * t] * inv, o0[4 * t + 1] * inv);
+      w0.y = pack2<A>(o0[4 * t + 2] * inv, o0[4 * t + 3] * inv);
+      w1.x = pack2<A>(o1[4 * t] * inv, o1[4 * t + 1] * inv);
+      w1.y = pack2<A>(o1[4 * t + 2] * inv, o1[4 * t + 3] * inv);
       *reinterpret_cast<uint2*>(op + 8 * t) = w0;
       *reinterpret_cast<uint2*>(op + 32 + 8 * t) = w1;
     }
@@ -232,7 +234,7 @@ constexpr bool stage_o(int nsub) { return (RAJNI_ATTN_STAGE_MASK >> (nsub - 1)) 
 // layout a lane owns 8 bytes of 8 different rows per instruction: 32 partial cache lines each, which backed
 // up the vector-memory queue - the NEXT item's prefetch then stalled at issue (tools/attn_stamps.py:
 // prefetch issue 2.5k + stores 1.7k of 11k cycles per item).
-template <int NSUB, bool O8 = false>
+template <typename A, int NSUB, bool O8 = false>
 __device__ __forceinline__ void attn_tile_compute(const char* sk, const char* sv, const bf16x8 (&qf)[4],
                                                   const AttnArgs& a, int b, int head, int qbase, int lane,
                                                   char* so = nullptr) {
@@ -248,7 +250,7 @@ __device__ __forceinline__ void attn_tile_compute(const char* sk, const char* sv
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sk + k_off(krow, 2 * ks + h));
-      s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], s[kb], 0, 0, 0);
+      s[kb] = mfma_32x32x16<A>(kf, qf[ks], s[kb]);
     }
   }
 #ifdef RAJNI_ATTN_STAMPS
@@ -290,8 +292,8 @@ __device__ __forceinline__ void attn_tile_compute(const char* sk, const char* sv
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
       typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-      const u32x4 w = {pack2bf(p[8 * s2 + 0], p[8 * s2 + 1]), pack2bf(p[8 * s2 + 2], p[8 * s2 + 3]),
-                       pack2bf(p[8 * s2 + 4], p[8 * s2 + 5]), pack2bf(p[8 * s2 + 6], p[8 * s2 + 7])};
+      const u32x4 w = {pack2<A>(p[8 * s2 + 0], p[8 * s2 + 1]), pack2<A>(p[8 * s2 + 2], p[8 * s2 + 3]),
+                       pack2<A>(p[8 * s2 + 4], p[8 * s2 + 5]), pack2<A>(p[8 * s2 + 6], p[8 * s2 + 7])};
       pb[s2] = __builtin_bit_cast(bf16x8, w);
     }
 #pragma unroll
@@ -300,8 +302,8 @@ __device__ __forceinline__ void attn_tile_compute(const char* sk, const char* sv
       const int col = 16 * (g & 1) + 4 * (l15 & 3);
       const bf16x8 v0 = tr_pair(sv, key0, col);
       const bf16x8 v1 = tr_pair(sv, key0, 32 + col);
-      o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v0, pb[s2], o0, 0, 0, 0);
-      o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v1, pb[s2], o1, 0, 0, 0);
+      o0 = mfma_32x32x16<A>(v0, pb[s2], o0);
+      o1 = mfma_32x32x16<A>(v1, pb[s2], o1);
     }
   }
 #ifdef RAJNI_ATTN_STAMPS
@@ -354,10 +356,10 @@ __device__ __forceinline__ void attn_tile_compute(const char* sk, const char* sv
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       uint2 w0, w1;
-      w0.x = pack2bf(o0[4 * t] * inv, o0[4 * t + 1] * inv);
-      w0.y = pack2bf(o0[4 * t + 2] * inv, o0[4 * t + 3] * inv);
-      w1.x = pack2bf(o1[4 * t] * inv, o1[4 * t + 1] * inv);
-      w1.y = pack2bf(o1[4 * t + 2] * inv, o1[4 * t + 3] * inv);
+      w0.x = pack2<A>(o0[4 * t] * inv, o0[4 * t + 1] * inv);
+      w0.y = pack2<A>(o0[4 * t + 2] * inv, o0[4 * t + 3] * inv);
+      w1.x = pack2<A>(o1[4 * t] * inv, o1[4 * t + 1] * inv);
+      w1.y = pack2<A>(o1[4 * t + 2] * inv, o1[4 * t + 3] * inv);
       *reinterpret_cast<uint2*>(wr + ((t ^ key) << 4)) = w0;          // d = 8t + 4h .. +3
       *reinterpret_cast<uint2*>(wr + (((4 + t) ^ key) << 4)) = w1;    // d = 32 + 8t + 4h .. +3
     }
@@ -377,17 +379,17 @@ __device__ __forceinline__ void attn_tile_compute(const char* sk, const char* sv
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       uint2 w0, w1;
-      w0.x = pack2bf(o0[4 * t] * inv, o0[4 * t + 1] * inv);
-      w0.y = pack2bf(o0[4 * t + 2] * inv, o0[4 * t + 3] * inv);
-      w1.x = pack2bf(o1[4 * t] * inv, o1[4 * t + 1] * inv);
-      w1.y = pack2bf(o1[4 * t + 2] * inv, o1[4 * t + 3] * inv);
+      w0.x = pack2<A>(o0[4 * t] * inv, o0[4 * t + 1] * inv);
+      w0.y = pack2<A>(o0[4 * t + 2] * inv, o0[4 * t + 3] * inv);
+      w1.x = pack2<A>(o1[4 * t] * inv, o1[4 * t + 1] * inv);
+      w1.y = pack2<A>(o1[4 * t + 2] * inv, o1[4 * t + 3] * inv);
       *reinterpret_cast<uint2*>(op + 8 * t) = w0;
       *reinterpret_cast<uint2*>(op + 32 + 8 * t) = w1;
     }
   }
 }
 
-template <int NSUB>
+template <int NSUB, typename A = bf16_t>
 __global__ void __launch_bounds__(ATF_THREADS, 2) attn_bf16_d64_full(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int ROWS = NSUB * 32;
@@ -433,7 +435,7 @@ __global__ void __launch_bounds__(ATF_THREADS, 2) attn_bf16_d64_full(const AttnA
   }
   __syncthreads();
   if (!active) return;
-  attn_tile_compute<NSUB>(sk, sv, qf, a, b, head, qbase, lane);
+  attn_tile_compute<A, NSUB>(sk, sv, qf, a, b, head, qbase, lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -459,7 +461,7 @@ __device__ __forceinline__ void dma16(const char* base, unsigned off, char* dst)
 
 // G: rows are gathered through keep_idx (a.idx != NULL) - a template flag, so that the per-item prefetch
 // carries no pointer tests (they were 10 scalar branches per item).
-template <int NSUB, bool G, bool O8 = false>
+template <int NSUB, bool G, bool O8 = false, typename A = bf16_t>
 __global__ void __launch_bounds__(ATF_THREADS, 2) attn_bf16_d64_stream(const AttnArgs a, int n_items) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int ROWS = NSUB * 32, BUF = ROWS * 256, NP8 = ROWS / 8;   // pieces (8 rows) per operand
@@ -577,7 +579,7 @@ __global__ void __launch_bounds__(ATF_THREADS, 2) attn_bf16_d64_stream(const Att
 #endif
     if (active) {
       const int b = cb, head = chead;
-      attn_tile_compute<NSUB, O8>(smem + buf * BUF, smem + buf * BUF + ROWS * 128, qf, a, b, head, qbase, lane,
+      attn_tile_compute<A, NSUB, O8>(smem + buf * BUF, smem + buf * BUF + ROWS * 128, qf, a, b, head, qbase, lane,
                                   STAGE_O ? smem + 2 * BUF + (qbase >> 5) * STAGE_BYTES : nullptr);
     }
 #ifdef RAJNI_ATTN_STAMPS
@@ -694,7 +696,7 @@ constexpr int AG_VSTRIDE = 68;    // bf16 per V^T row (64 keys + 4)
 constexpr int AG_QROWS = 128;     // query rows per workgroup: 4 waves x 2 blocks of 16
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 
-template <int NW, int NB>   // waves per workgroup, blocks of 16 query rows per wave
+template <int NW, int NB, typename A = bf16_t>   // waves per workgroup, blocks of 16 query rows per wave
 __global__ void __launch_bounds__(NW * 64, 2) attn_bf16_dgen(const AttnArgs a, int D) {
   constexpr int NT = NW * 64, QROWS = NW * NB * 16, KI = 1024 / NT;   // K staging items per thread (<= 1024 per chunk)
   __shared__ __attribute__((aligned(16))) bf16_t sk[64 * AG_KSTRIDE];
@@ -806,7 +808,7 @@ __global__ void __launch_bounds__(NW * 64, 2) attn_bf16_dgen(const AttnArgs a, i
         if (kd < ND) {
           const s16x4_t ka = *reinterpret_cast<const s16x4_t*>(sk + (16 * kb + r) * AG_KSTRIDE + 16 * kd + 4 * g);
 #pragma unroll
-          for (int u = 0; u < NB; ++u) st[u][kb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ka, qf[u][kd], st[u][kb], 0, 0, 0);
+          for (int u = 0; u < NB; ++u) st[u][kb] = mfma_16x16x16<A>(ka, qf[u][kd], st[u][kb]);
         }
 #pragma unroll
       for (int u = 0; u < NB; ++u)
@@ -836,7 +838,7 @@ __global__ void __launch_bounds__(NW * 64, 2) attn_bf16_dgen(const AttnArgs a, i
           pv[j] = __builtin_amdgcn_exp2f(st[u][kb][j] - m_new);
           psum += pv[j];
         }
-        pf[u][kb] = __builtin_bit_cast(s16x4_t, make_uint2(pack2bf(pv[0], pv[1]), pack2bf(pv[2], pv[3])));
+        pf[u][kb] = __builtin_bit_cast(s16x4_t, make_uint2(pack2<A>(pv[0], pv[1]), pack2<A>(pv[2], pv[3])));
       }
       l_part[u] = fmaf(l_part[u], alpha[u], psum);
     }
@@ -849,7 +851,7 @@ __global__ void __launch_bounds__(NW * 64, 2) attn_bf16_dgen(const AttnArgs a, i
         for (int kb = 0; kb < 4; ++kb) {
           const s16x4_t va = *reinterpret_cast<const s16x4_t*>(svt + (16 * db + r) * AG_VSTRIDE + 16 * kb + 4 * g);
 #pragma unroll
-          for (int u = 0; u < NB; ++u) o[u][db] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(va, pf[u][kb], o[u][db], 0, 0, 0);
+          for (int u = 0; u < NB; ++u) o[u][db] = mfma_16x16x16<A>(va, pf[u][kb], o[u][db]);
         }
       }
   }
@@ -865,7 +867,7 @@ __global__ void __launch_bounds__(NW * 64, 2) attn_bf16_dgen(const AttnArgs a, i
         const int d0 = 16 * db + 4 * g;
         if (db < ND && d0 < D)
           *reinterpret_cast<uint2*>(op + d0) =
-              make_uint2(pack2bf(o[u][db][0] * inv, o[u][db][1] * inv), pack2bf(o[u][db][2] * inv, o[u][db][3] * inv));
+              make_uint2(pack2<A>(o[u][db][0] * inv, o[u][db][1] * inv), pack2<A>(o[u][db][2] * inv, o[u][db][3] * inv));
       }
     }
   }
@@ -969,19 +971,19 @@ int launch_full_o8(const AttnArgs& a, int B, hipStream_t s) {   // e4m3 output: 
   return RAJNI_OK;
 }
 
-template <int NSUB>
+template <int NSUB, typename A>
 int launch_full(const AttnArgs& a, int B, hipStream_t s) {
   if (g_force_attn == 2) {
     constexpr int lds = NSUB * 32 * 128 * 2;
-    hipLaunchKernelGGL(attn_bf16_d64_full<NSUB>, dim3(a.H, B), dim3(ATF_THREADS), lds, s, a);
+    hipLaunchKernelGGL((attn_bf16_d64_full<NSUB, A>), dim3(a.H, B), dim3(ATF_THREADS), lds, s, a);
     return RAJNI_OK;
   }
   constexpr int lds = NSUB * 32 * 256 * 2 + (stage_o(NSUB) ? 8 * 4096 : 0);   // two K+V buffers (+ output staging)
   static bool attr_by_device[RAJNI_MAX_DEVICES] = {};
   bool& attr = attr_by_device[rajni_current_device()];
   if (!attr && lds > 64 * 1024) {
-    for (const void* fn : {reinterpret_cast<const void*>(&attn_bf16_d64_stream<NSUB, false>),
-                           reinterpret_cast<const void*>(&attn_bf16_d64_stream<NSUB, true>)}) {
+    for (const void* fn : {reinterpret_cast<const void*>(&attn_bf16_d64_stream<NSUB, false, false, A>),
+                           reinterpret_cast<const void*>(&attn_bf16_d64_stream<NSUB, true, false, A>)}) {
       hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
       if (e != hipSuccess) { rajni_set_error("hipFuncSetAttribute(attn): %s", hipGetErrorString(e)); return RAJNI_ERR_LAUNCH; }
     }
@@ -992,9 +994,9 @@ int launch_full(const AttnArgs& a, int B, hipStream_t s) {
   const int cus = rajni_num_cus();
   const int grid = items < cus * per_cu ? items : cus * per_cu;
   if (a.idx != nullptr)
-    hipLaunchKernelGGL((attn_bf16_d64_stream<NSUB, true>), dim3(grid), dim3(ATF_THREADS), lds, s, a, items);
+    hipLaunchKernelGGL((attn_bf16_d64_stream<NSUB, true, false, A>), dim3(grid), dim3(ATF_THREADS), lds, s, a, items);
   else
-    hipLaunchKernelGGL((attn_bf16_d64_stream<NSUB, false>), dim3(grid), dim3(ATF_THREADS), lds, s, a, items);
+    hipLaunchKernelGGL((attn_bf16_d64_stream<NSUB, false, false, A>), dim3(grid), dim3(ATF_THREADS), lds, s, a, items);
   return RAJNI_OK;
 }
 
@@ -1061,9 +1063,45 @@ int launch_attention_cls(const void* qkv, void* out, int B, int N, int H, int D,
   ProfScope prof(KC_ATTENTION, s, 4.0 * B * H * (double)N * D, 2.0 * B * (double)N * H * D * (dtype == RAJNI_F32 ? 4.0 : 2.0));
   if (dtype == RAJNI_F32)
     hipLaunchKernelGGL(attn_cls_kernel<float>, dim3(H, B), dim3(64), lds, s, (const float*)qkv, (float*)out, N, H, D, c, 0.f);
+  else if (dtype == RAJNI_F16)
+    hipLaunchKernelGGL(attn_cls_kernel<f16_t>, dim3(H, B), dim3(64), lds, s, (const f16_t*)qkv, (f16_t*)out, N, H, D, c, 0.f);
   else
     hipLaunchKernelGGL(attn_cls_kernel<bf16_t>, dim3(H, B), dim3(64), lds, s, (const bf16_t*)qkv, (bf16_t*)out, N, H, D, c, q_scale);
   RAJNI_CHECK_LAUNCH("attn_cls_kernel");
+  return RAJNI_OK;
+}
+
+// the 16-bit formats (A = bf16_t or f16_t): the same kernel choice for the same shape
+template <typename A>
+int launch_attention16(const AttnArgs& a, int B, int np, int H, int D, hipStream_t s) {
+  const int nsub = (np + 31) / 32;
+  if (D != 64) {
+    #ifndef RAJNI_ATTN_DGEN_NW
+#define RAJNI_ATTN_DGEN_NW 4
+#endif
+#ifndef RAJNI_ATTN_DGEN_NB
+#define RAJNI_ATTN_DGEN_NB 2
+#endif
+    constexpr int qrows = RAJNI_ATTN_DGEN_NW * RAJNI_ATTN_DGEN_NB * 16;
+    hipLaunchKernelGGL((attn_bf16_dgen<RAJNI_ATTN_DGEN_NW, RAJNI_ATTN_DGEN_NB, A>), dim3((np + qrows - 1) / qrows, H, B),
+                       dim3(RAJNI_ATTN_DGEN_NW * 64), 0, s, a, D);
+  } else if (nsub <= 8 && g_force_attn != 1) {
+    int rc = RAJNI_OK;
+    switch (nsub) {
+      case 1: rc = launch_full<1, A>(a, B, s); break;
+      case 2: rc = launch_full<2, A>(a, B, s); break;
+      case 3: rc = launch_full<3, A>(a, B, s); break;
+      case 4: rc = launch_full<4, A>(a, B, s); break;
+      case 5: rc = launch_full<5, A>(a, B, s); break;
+      case 6: rc = launch_full<6, A>(a, B, s); break;
+      case 7: rc = launch_full<7, A>(a, B, s); break;
+      default: rc = launch_full<8, A>(a, B, s); break;
+    }
+    if (rc != RAJNI_OK) return rc;
+  } else {
+    hipLaunchKernelGGL(attn_bf16_d64<A>, dim3((np + AT_QROWS - 1) / AT_QROWS, H, B), dim3(AT_THREADS), 0,
+                       s, a);
+  }
   return RAJNI_OK;
 }
 
@@ -1089,7 +1127,7 @@ int launch_attention(const void* qkv, const int32_t* keep_idx, void* out, int B,
     RAJNI_CHECK_LAUNCH("attn_f32");
     return RAJNI_OK;
   }
-  RAJNI_REQUIRE(dtype == RAJNI_BF16, RAJNI_ERR_INVALID, "rajni_attention: bad dtype %d", dtype);
+  RAJNI_REQUIRE(dtype == RAJNI_BF16 || dtype == RAJNI_F16, RAJNI_ERR_INVALID, "rajni_attention: bad dtype %d", dtype);
   AttnArgs a{};
   a.qkv = (const bf16_t*)qkv; a.idx = keep_idx; a.out = (bf16_t*)out;
   a.n_src = n_src; a.np = np; a.H = H;
@@ -1098,34 +1136,8 @@ int launch_attention(const void* qkv, const int32_t* keep_idx, void* out, int B,
   const double flops = 4.0 * B * H * (double)np * np * D;
   const double bytes = 2.0 * B * (double)np * H * D * 4.0;
   ProfScope prof(KC_ATTENTION, s, flops, bytes);
-  const int nsub = (np + 31) / 32;
-  if (D != 64) {
-    #ifndef RAJNI_ATTN_DGEN_NW
-#define RAJNI_ATTN_DGEN_NW 4
-#endif
-#ifndef RAJNI_ATTN_DGEN_NB
-#define RAJNI_ATTN_DGEN_NB 2
-#endif
-    constexpr int qrows = RAJNI_ATTN_DGEN_NW * RAJNI_ATTN_DGEN_NB * 16;
-    hipLaunchKernelGGL((attn_bf16_dgen<RAJNI_ATTN_DGEN_NW, RAJNI_ATTN_DGEN_NB>), dim3((np + qrows - 1) / qrows, H, B),
-                       dim3(RAJNI_ATTN_DGEN_NW * 64), 0, s, a, D);
-  } else if (nsub <= 8 && g_force_attn != 1) {
-    int rc = RAJNI_OK;
-    switch (nsub) {
-      case 1: rc = launch_full<1>(a, B, s); break;
-      case 2: rc = launch_full<2>(a, B, s); break;
-      case 3: rc = launch_full<3>(a, B, s); break;
-      case 4: rc = launch_full<4>(a, B, s); break;
-      case 5: rc = launch_full<5>(a, B, s); break;
-      case 6: rc = launch_full<6>(a, B, s); break;
-      case 7: rc = launch_full<7>(a, B, s); break;
-      default: rc = launch_full<8>(a, B, s); break;
-    }
-    if (rc != RAJNI_OK) return rc;
-  } else {
-    hipLaunchKernelGGL(attn_bf16_d64, dim3((np + AT_QROWS - 1) / AT_QROWS, H, B), dim3(AT_THREADS), 0,
-                       s, a);
-  }
+  const int rc = dtype == RAJNI_F16 ? launch_attention16<f16_t>(a, B, np, H, D, s) : launch_attention16<bf16_t>(a, B, np, H, D, s);
+  if (rc != RAJNI_OK) return rc;
   RAJNI_CHECK_LAUNCH("attn_bf16_d64");
   return RAJNI_OK;
 }

@@ -97,8 +97,9 @@ int rajni_device_check(void) {
   return RAJNI_OK;
 }
 
-#define NEED_DTYPE(name)                                                                     \
-  RAJNI_REQUIRE(dtype == RAJNI_BF16 || dtype == RAJNI_F32, RAJNI_ERR_INVALID, name ": bad dtype %d", dtype)
+#define NEED_DTYPE(name)                                                                                     \
+  RAJNI_REQUIRE(dtype == RAJNI_BF16 || dtype == RAJNI_F32 || dtype == RAJNI_F16, RAJNI_ERR_INVALID, name ": bad dtype %d", \
+                dtype)
 
 int rajni_importance(const void* qkv, void* scores_out, int B, int N, int H, int D, float eps,
                      int dtype, rajni_stream_t stream) {
@@ -129,8 +130,8 @@ int rajni_score_select(const void* qkv, int B, int N, int H, int D, float eps, i
 
 int rajni_gather_rows(const void* src, const int32_t* idx, void* dst, int B, int n_src, int n_dst,
                       int row_elems, int dtype, rajni_stream_t stream) {
-  RAJNI_REQUIRE(dtype == RAJNI_BF16 || dtype == RAJNI_F32, RAJNI_ERR_INVALID, "rajni_gather_rows: bad dtype");
-  const int es = dtype == RAJNI_BF16 ? 2 : 4;
+  NEED_DTYPE("rajni_gather_rows");
+  const int es = dtype == RAJNI_F32 ? 4 : 2;   // a byte copy: bf16 and fp16 rows alike
   return launch_gather_rows(src, idx, dst, B, n_src, n_dst, row_elems * es, (hipStream_t)stream);
 }
 

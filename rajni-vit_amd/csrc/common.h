@@ -40,10 +40,72 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
   return v;
 }
 
-// 8 consecutive elements of the activation dtype (bf16_t or float) <-> 8 floats
+// ---- fp16 models: raw fp16 storage as a DISTINCT C++ type (bf16_t is unsigned short, so a second unsigned-short
+// typedef would silently pick the bf16 specialisations below).  Conversions round to nearest even
+// (v_cvt_f16_f32 / v_cvt_pk_f16_f32; never the round-toward-zero pkrtz form), overflow goes to +-inf as in torch.
+typedef _Float16 f16_t;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
+__device__ __forceinline__ float h2f(f16_t h) { return (float)h; }
+__device__ __forceinline__ f16_t f2h(float f) { return (_Float16)f; }
+__device__ __forceinline__ unsigned pack2h(float lo, float hi) {
+  f16x2 v = {(_Float16)lo, (_Float16)hi};
+  return __builtin_bit_cast(unsigned, v);
+}
+__device__ __forceinline__ float h_lo(unsigned u) { return (float)__builtin_bit_cast(f16x2, u)[0]; }
+__device__ __forceinline__ float h_hi(unsigned u) { return (float)__builtin_bit_cast(f16x2, u)[1]; }
+
+// the 16-bit activation formats (A = bf16_t or f16_t) behind one set of names: two values per 32-bit word,
+// 8 per 16-byte chunk
+template <typename A> __device__ __forceinline__ unsigned pack2(float lo, float hi);
+template <> __device__ __forceinline__ unsigned pack2<bf16_t>(float lo, float hi) { return pack2bf(lo, hi); }
+template <> __device__ __forceinline__ unsigned pack2<f16_t>(float lo, float hi) { return pack2h(lo, hi); }
+template <typename A> __device__ __forceinline__ float lo16(unsigned u);
+template <> __device__ __forceinline__ float lo16<bf16_t>(unsigned u) { return bf_lo(u); }
+template <> __device__ __forceinline__ float lo16<f16_t>(unsigned u) { return h_lo(u); }
+template <typename A> __device__ __forceinline__ float hi16(unsigned u);
+template <> __device__ __forceinline__ float hi16<bf16_t>(unsigned u) { return bf_hi(u); }
+template <> __device__ __forceinline__ float hi16<f16_t>(unsigned u) { return h_hi(u); }
+template <typename A> __device__ __forceinline__ void unpack8(const uint4& v, float* f) {
+  f[0] = lo16<A>(v.x); f[1] = hi16<A>(v.x); f[2] = lo16<A>(v.y); f[3] = hi16<A>(v.y);
+  f[4] = lo16<A>(v.z); f[5] = hi16<A>(v.z); f[6] = lo16<A>(v.w); f[7] = hi16<A>(v.w);
+}
+template <typename A> __device__ __forceinline__ uint4 pack8(const float* f) {
+  uint4 v;
+  v.x = pack2<A>(f[0], f[1]); v.y = pack2<A>(f[2], f[3]);
+  v.z = pack2<A>(f[4], f[5]); v.w = pack2<A>(f[6], f[7]);
+  return v;
+}
+// The MFMA forms the kernels issue, by operand format.  Fragments travel as bf16 vectors in both formats (the
+// same LDS reads and registers; hipcc's waitcnt insertion treats differently typed LDS reads differently, see
+// gemm.hip) and are reinterpreted for the f16 instruction - same shapes, same cycles (v_mfma_f32_*_f16).
+template <typename A> __device__ __forceinline__ f32x4 mfma_16x16x32(const bf16x8& a, const bf16x8& b, const f32x4& c) {
+  if constexpr (__is_same(A, f16_t))
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+template <typename A> __device__ __forceinline__ f32x16 mfma_32x32x16(const bf16x8& a, const bf16x8& b, const f32x16& c) {
+  if constexpr (__is_same(A, f16_t))
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+template <typename A> __device__ __forceinline__ f32x4 mfma_16x16x16(const s16x4& a, const s16x4& b, const f32x4& c) {
+  if constexpr (__is_same(A, f16_t))
+    return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4, a), __builtin_bit_cast(f16x4, b), c, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0);
+}
+
+// 8 consecutive elements of the activation dtype (bf16_t, f16_t or float) <-> 8 floats
 template <typename T> __device__ __forceinline__ void load8(const T* p, float* f);
 template <> __device__ __forceinline__ void load8<bf16_t>(const bf16_t* p, float* f) {
   unpack8(*reinterpret_cast<const uint4*>(p), f);
+}
+template <> __device__ __forceinline__ void load8<f16_t>(const f16_t* p, float* f) {
+  unpack8<f16_t>(*reinterpret_cast<const uint4*>(p), f);
 }
 template <> __device__ __forceinline__ void load8<float>(const float* p, float* f) {
   const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
@@ -53,6 +115,9 @@ template <typename T> __device__ __forceinline__ void store8(T* p, const float* 
 template <> __device__ __forceinline__ void store8<bf16_t>(bf16_t* p, const float* f) {
   *reinterpret_cast<uint4*>(p) = pack8(f);
 }
+template <> __device__ __forceinline__ void store8<f16_t>(f16_t* p, const float* f) {
+  *reinterpret_cast<uint4*>(p) = pack8<f16_t>(f);
+}
 template <> __device__ __forceinline__ void store8<float>(float* p, const float* f) {
   reinterpret_cast<float4*>(p)[0] = make_float4(f[0], f[1], f[2], f[3]);
   reinterpret_cast<float4*>(p)[1] = make_float4(f[4], f[5], f[6], f[7]);
@@ -60,10 +125,13 @@ template <> __device__ __forceinline__ void store8<float>(float* p, const float*
 // value as the activation dtype would hold it, and scalar load/store
 template <typename T> __device__ __forceinline__ float round_to(float v);
 template <> __device__ __forceinline__ float round_to<bf16_t>(float v) { return bf2f(f2bf(v)); }
+template <> __device__ __forceinline__ float round_to<f16_t>(float v) { return h2f(f2h(v)); }
 template <> __device__ __forceinline__ float round_to<float>(float v) { return v; }
 __device__ __forceinline__ float ld1(const bf16_t* p) { return bf2f(*p); }
+__device__ __forceinline__ float ld1(const f16_t* p) { return h2f(*p); }
 __device__ __forceinline__ float ld1(const float* p) { return *p; }
 __device__ __forceinline__ void st1(bf16_t* p, float v) { *p = f2bf(v); }
+__device__ __forceinline__ void st1(f16_t* p, float v) { *p = f2h(v); }
 __device__ __forceinline__ void st1(float* p, float v) { *p = v; }
 
 __device__ __forceinline__ float wave_sum(float v) {

@@ -52,7 +52,8 @@ __global__ void carry_scores_kernel(const T* scores, const int* idx, T* out, int
 }
 
 int check_plan(const rajni_vit_plan& p) {
-  RAJNI_REQUIRE(p.dtype == RAJNI_BF16 || p.dtype == RAJNI_F32, RAJNI_ERR_INVALID, "rajni_vit_forward: bad dtype %d", p.dtype);
+  RAJNI_REQUIRE(p.dtype == RAJNI_BF16 || p.dtype == RAJNI_F32 || p.dtype == RAJNI_F16, RAJNI_ERR_INVALID,
+                "rajni_vit_forward: bad dtype %d", p.dtype);
   RAJNI_REQUIRE(p.B > 0 && p.depth > 0 && p.blocks != nullptr, RAJNI_ERR_INVALID, "rajni_vit_forward: bad plan");
   RAJNI_REQUIRE(p.C == p.H * p.D && p.D >= 8 && p.D <= 128 && p.D % 8 == 0, RAJNI_ERR_UNSUPPORTED,
                 "rajni_vit_forward: need C == H*D and a head dim that is a multiple of 8 up to 128 (C=%d H=%d D=%d)", p.C, p.H, p.D);
@@ -60,6 +61,13 @@ int check_plan(const rajni_vit_plan& p) {
                 "rajni_vit_forward: C and hidden must be multiples of 64");
   RAJNI_REQUIRE(p.patch_w && p.cls_token && p.pos_embed && p.norm_w && p.norm_b && p.head_w,
                 RAJNI_ERR_INVALID, "rajni_vit_forward: null weight pointer");
+  if (p.dtype == RAJNI_F16) {
+    bool w8 = false;
+    for (int i = 0; i < p.depth; ++i)
+      w8 = w8 || p.blocks[i].qkv_s || p.blocks[i].proj_s || p.blocks[i].fc1_s || p.blocks[i].fc2_s;
+    RAJNI_REQUIRE(!w8 && !p.act_fp8, RAJNI_ERR_UNSUPPORTED,
+                  "rajni_vit_forward: fp8 weights or activations need a bf16 model (dtype fp16 given)");
+  }
   if (p.act_fp8) {
     RAJNI_REQUIRE(p.dtype == RAJNI_BF16, RAJNI_ERR_UNSUPPORTED, "rajni_vit_forward: act_fp8 needs a bf16 model");
     RAJNI_REQUIRE(p.C % 256 == 0 && p.hidden % 256 == 0 && p.C >= 512, RAJNI_ERR_UNSUPPORTED,
@@ -95,7 +103,7 @@ extern "C" int rajni_vit_forward(const rajni_vit_plan* plan, const void* images,
   int N = gw * gw + 1;
 
   const int dt = p.dtype;
-  const int sf32 = (dt == RAJNI_BF16 && !p.resid_bf16) ? 1 : 0;  // bf16 model with an fp32 residual stream
+  const int sf32 = (dt != RAJNI_F32 && !p.resid_bf16) ? 1 : 0;  // 16-bit model with an fp32 residual stream
   rc = launch_patch_embed(images, p.patch_w, p.patch_b, p.cls_token, p.pos_embed, p.pos_has_cls,
                           w.xa, sf32, B, p.in_chans, p.img_size, p.patch_size, C, dt, w.cols, w.cols_bytes, s);
   if (rc != RAJNI_OK) return rc;
@@ -177,7 +185,7 @@ extern "C" int rajni_vit_forward(const rajni_vit_plan* plan, const void* images,
         if (dt == RAJNI_F32)
           hipLaunchKernelGGL(carry_scores_kernel<float>, dim3((n + 255) / 256), dim3(256), 0, s,
                              (const float*)full, blk.forced_keep_idx, (float*)blk.next_scores, B, N, Np);
-        else
+        else   // (a 16-bit copy: serves fp16 scores too)
           hipLaunchKernelGGL(carry_scores_kernel<bf16_t>, dim3((n + 255) / 256), dim3(256), 0, s,
                              (const bf16_t*)full, blk.forced_keep_idx, (bf16_t*)blk.next_scores, B, N, Np);
         RAJNI_CHECK_LAUNCH("carry_scores_kernel");

@@ -106,49 +106,49 @@ __device__ __forceinline__ void gelu_pk4(f32x2& a, f32x2& b) {
   a = ya; b = yb;
 }
 
-// load / store 16 consecutive stream elements (bf16 or fp32) as floats
-template <bool F32>
+// load / store 16 consecutive stream elements (the 16-bit activation format A, or fp32) as floats
+template <bool F32, typename A>
 __device__ __forceinline__ void load16(const void* base, long off, float* f) {
   if (F32) {
     const float4* q = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(base) + off);
 #pragma unroll
     for (int i = 0; i < 4; ++i) { const float4 t = q[i]; f[4*i] = t.x; f[4*i+1] = t.y; f[4*i+2] = t.z; f[4*i+3] = t.w; }
   } else {
-    const bf16_t* q = reinterpret_cast<const bf16_t*>(base) + off;
-    unpack8(*reinterpret_cast<const uint4*>(q), f);
-    unpack8(*reinterpret_cast<const uint4*>(q + 8), f + 8);
+    const A* q = reinterpret_cast<const A*>(base) + off;
+    unpack8<A>(*reinterpret_cast<const uint4*>(q), f);
+    unpack8<A>(*reinterpret_cast<const uint4*>(q + 8), f + 8);
   }
 }
-template <bool F32>
+template <bool F32, typename A>
 __device__ __forceinline__ void load8s(const void* base, long off, float* f) {   // 8 stream elements
   if (F32) load8<float>(reinterpret_cast<const float*>(base) + off, f);
-  else load8<bf16_t>(reinterpret_cast<const bf16_t*>(base) + off, f);
+  else load8<A>(reinterpret_cast<const A*>(base) + off, f);
 }
-template <bool F32>
+template <bool F32, typename A>
 __device__ __forceinline__ void store8s(void* base, long off, const float* v) {
   if (F32) store8<float>(reinterpret_cast<float*>(base) + off, v);
-  else store8<bf16_t>(reinterpret_cast<bf16_t*>(base) + off, v);
+  else store8<A>(reinterpret_cast<A*>(base) + off, v);
 }
-template <bool F32>
+template <bool F32, typename A>
 __device__ __forceinline__ float load1(const void* base, long off) {
-  return F32 ? reinterpret_cast<const float*>(base)[off] : bf2f(reinterpret_cast<const bf16_t*>(base)[off]);
+  return F32 ? reinterpret_cast<const float*>(base)[off] : ld1(reinterpret_cast<const A*>(base) + off);
 }
-template <bool F32>
+template <bool F32, typename A>
 __device__ __forceinline__ void store16(void* base, long off, const float* v) {
   if (F32) {
     float4* q = reinterpret_cast<float4*>(reinterpret_cast<float*>(base) + off);
 #pragma unroll
     for (int i = 0; i < 4; ++i) q[i] = make_float4(v[4*i], v[4*i+1], v[4*i+2], v[4*i+3]);
   } else {
-    bf16_t* q = reinterpret_cast<bf16_t*>(base) + off;
-    *reinterpret_cast<uint4*>(q) = pack8(v);
-    *reinterpret_cast<uint4*>(q + 8) = pack8(v + 8);
+    A* q = reinterpret_cast<A*>(base) + off;
+    *reinterpret_cast<uint4*>(q) = pack8<A>(v);
+    *reinterpret_cast<uint4*>(q + 8) = pack8<A>(v + 8);
   }
 }
-template <bool F32>
+template <bool F32, typename A>
 __device__ __forceinline__ void store1(void* base, long off, float v) {
   if (F32) reinterpret_cast<float*>(base)[off] = v;
-  else reinterpret_cast<bf16_t*>(base)[off] = f2bf(v);
+  else st1(reinterpret_cast<A*>(base) + off, v);
 }
 
 // FC1's hidden activations (the largest tensor of a block: written once, read once by FC2) are stored NON-TEMPORAL:
@@ -170,7 +170,7 @@ __device__ __forceinline__ void store_u4(void* ptr, const uint4& v) {
 // SF32: the residual-stream tensors this launch touches (R and Y of RESID, Y of PATCH) are fp32.
 // v[0..7] are columns nbA..nbA+7 and v[8..15] columns nbB..nbB+7 of output row m (nbB = nbA + 32: the
 // sector mapping MAP_SEC below).
-template <int EPI, bool SF32>
+template <int EPI, bool SF32, typename A>
 __device__ __forceinline__ void epilogue_row(const GemmParams& p, int m, int nbA, int nbB, float* v, const float* gam) {
   long orow = m;
   const bool full = nbB + 8 <= p.N;   // both halves inside N (nbA < nbB)
@@ -190,45 +190,45 @@ __device__ __forceinline__ void epilogue_row(const GemmParams& p, int m, int nbA
     const long rbase = rrow * p.ldr;
     if (full) {
       float rf[16];
-      load8s<SF32>(p.R, rbase + nbA, rf);
-      load8s<SF32>(p.R, rbase + nbB, rf + 8);
+      load8s<SF32, A>(p.R, rbase + nbA, rf);
+      load8s<SF32, A>(p.R, rbase + nbB, rf + 8);
 #pragma unroll
       for (int j = 0; j < 16; ++j) v[j] = fmaf(gam[j], v[j], rf[j]);
     } else {
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
         const int n = (j < 8 ? nbA : nbB - 8) + j;
-        if (n < p.N) v[j] = fmaf(gam[j], v[j], load1<SF32>(p.R, rbase + n));
+        if (n < p.N) v[j] = fmaf(gam[j], v[j], load1<SF32, A>(p.R, rbase + n));
       }
     }
   } else if (EPI == EPI_PATCH) {
     const int b = m / p.npatch, pp = m - b * p.npatch;
     orow = (long)b * (p.npatch + 1) + 1 + pp;
-    const bf16_t* pr = reinterpret_cast<const bf16_t*>(p.pos) + (long)(pp + p.pos_off) * p.ldc;
+    const A* pr = reinterpret_cast<const A*>(p.pos) + (long)(pp + p.pos_off) * p.ldc;
     if (full) {
       float pf[16];
-      unpack8(*reinterpret_cast<const uint4*>(pr + nbA), pf);
-      unpack8(*reinterpret_cast<const uint4*>(pr + nbB), pf + 8);
+      unpack8<A>(*reinterpret_cast<const uint4*>(pr + nbA), pf);
+      unpack8<A>(*reinterpret_cast<const uint4*>(pr + nbB), pf + 8);
 #pragma unroll
       for (int j = 0; j < 16; ++j) v[j] += pf[j];
     } else {
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
         const int n = (j < 8 ? nbA : nbB - 8) + j;
-        if (n < p.N) v[j] += bf2f(pr[n]);
+        if (n < p.N) v[j] += ld1(pr + n);
       }
     }
   }
   constexpr bool OUT32 = SF32 && (EPI == EPI_RESID || EPI == EPI_PATCH);
   const long ybase = orow * p.ldc;
   if (full) {
-    store8s<OUT32>(p.Y, ybase + nbA, v);
-    store8s<OUT32>(p.Y, ybase + nbB, v + 8);
+    store8s<OUT32, A>(p.Y, ybase + nbA, v);
+    store8s<OUT32, A>(p.Y, ybase + nbB, v + 8);
   } else {
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       const int n = (j < 8 ? nbA : nbB - 8) + j;
-      if (n < p.N) store1<OUT32>(p.Y, ybase + n, v[j]);
+      if (n < p.N) store1<OUT32, A>(p.Y, ybase + n, v[j]);
     }
   }
 }
@@ -303,7 +303,7 @@ __device__ __forceinline__ bf16x8 w_frag_bf16(const bf16x8& f) { return f; }
 __device__ __forceinline__ bf16x8 w_frag_bf16(const fp8x8_raw& f) { return fp8x8_to_bf16(__builtin_bit_cast(uint2, f)); }
 
 // natural-order epilogue of one output row (fp32 stream): v = accumulators + bias on entry
-template <int EPI>
+template <int EPI, typename A>
 __device__ __forceinline__ void epilogue_row_nat(const GemmParams& p, int m, int n0w, int g, float* v, const float* gam) {
   long orow = m, rrow = m;
   int pp = 0;
@@ -317,7 +317,7 @@ __device__ __forceinline__ void epilogue_row_nat(const GemmParams& p, int m, int
     orow = (long)b * (p.npatch + 1) + 1 + pp;
   }
   const float* R = reinterpret_cast<const float*>(p.R);
-  const bf16_t* P = reinterpret_cast<const bf16_t*>(p.pos);
+  const A* P = reinterpret_cast<const A*>(p.pos);
   float* Y = reinterpret_cast<float*>(p.Y);
 #pragma unroll
   for (int ni = 0; ni < 4; ++ni) {
@@ -330,7 +330,7 @@ __device__ __forceinline__ void epilogue_row_nat(const GemmParams& p, int m, int
         vv[2] = fmaf(gam[4 * ni + 2], vv[2], r.z); vv[3] = fmaf(gam[4 * ni + 3], vv[3], r.w);
       } else {
         const uint2 q = *reinterpret_cast<const uint2*>(P + (long)(pp + p.pos_off) * p.ldc + c);
-        vv[0] += bf_lo(q.x); vv[1] += bf_hi(q.x); vv[2] += bf_lo(q.y); vv[3] += bf_hi(q.y);
+        vv[0] += lo16<A>(q.x); vv[1] += hi16<A>(q.x); vv[2] += lo16<A>(q.y); vv[3] += hi16<A>(q.y);
       }
       *reinterpret_cast<float4*>(Y + orow * p.ldc + c) = make_float4(vv[0], vv[1], vv[2], vv[3]);
     } else {
@@ -339,7 +339,7 @@ __device__ __forceinline__ void epilogue_row_nat(const GemmParams& p, int m, int
         if (c + e < p.N) {
           float o = vv[e];
           if (EPI == EPI_RESID) o = fmaf(gam[4 * ni + e], o, R[rrow * p.ldr + c + e]);
-          else o += bf2f(P[(long)(pp + p.pos_off) * p.ldc + c + e]);
+          else o += ld1(P + (long)(pp + p.pos_off) * p.ldc + c + e);
           Y[orow * p.ldc + c + e] = o;
           vv[e] = o;
         }
@@ -429,8 +429,9 @@ __device__ __forceinline__ void prefetch_resid(const GemmParams& p, ResidPrefetc
   }
 }
 
-// shared tail of every bf16 tiling: bias/gamma for this lane's columns, then one row per m-tile
-template <int EPI, bool SF32, int MI, bool W8 = false>
+// shared tail of every 16-bit tiling: bias/gamma for this lane's columns, then one row per m-tile (A: bf16_t or f16_t,
+// the format of the 16-bit outputs and of the residual stream when it is not fp32)
+template <typename A, int EPI, bool SF32, int MI, bool W8 = false>
 __device__ __forceinline__ void epilogue_tile(const GemmParams& p, f32x4 (&acc)[4][MI], int m_base, int n0w,
                                               int l15, int g, ResidPrefetch<MI>& pre, int m_lo = 0,
                                               bool interior = false, char* scratch = nullptr) {
@@ -564,7 +565,7 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, f32x4 (&acc)[
         load8<float>(p.wscale + cb, ws + 8);
       }
       __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): see the note in the general path
-      bf16_t* Y = reinterpret_cast<bf16_t*>(p.Y);
+      A* Y = reinterpret_cast<A*>(p.Y);
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) {
         float v[16];
@@ -589,8 +590,8 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, f32x4 (&acc)[
           asm volatile("" : "+v"(lane));
           const int rr = lane >> 3, cc = lane & 7;
           const int key = l15 & 7;
-          *reinterpret_cast<bf16x8*>(scratch + l15 * 128 + ((g ^ key) << 4)) = __builtin_bit_cast(bf16x8, pack8(v));
-          *reinterpret_cast<bf16x8*>(scratch + l15 * 128 + (((4 + g) ^ key) << 4)) = __builtin_bit_cast(bf16x8, pack8(v + 8));
+          *reinterpret_cast<bf16x8*>(scratch + l15 * 128 + ((g ^ key) << 4)) = __builtin_bit_cast(bf16x8, pack8<A>(v));
+          *reinterpret_cast<bf16x8*>(scratch + l15 * 128 + (((4 + g) ^ key) << 4)) = __builtin_bit_cast(bf16x8, pack8<A>(v + 8));
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
           __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -601,9 +602,9 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, f32x4 (&acc)[
           }
           __builtin_amdgcn_wave_barrier();
         } else {
-          bf16_t* row = Y + (long)(m_base + mi * 16 + l15) * p.ldc;
-          store_u4<RAJNI_FC1_NT && EPI == EPI_GELU>(row + ca, pack8(v));
-          store_u4<RAJNI_FC1_NT && EPI == EPI_GELU>(row + cb, pack8(v + 8));
+          A* row = Y + (long)(m_base + mi * 16 + l15) * p.ldc;
+          store_u4<RAJNI_FC1_NT && EPI == EPI_GELU>(row + ca, pack8<A>(v));
+          store_u4<RAJNI_FC1_NT && EPI == EPI_GELU>(row + cb, pack8<A>(v + 8));
         }
       }
       return;
@@ -661,8 +662,8 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, f32x4 (&acc)[
     for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
       for (int rg = 0; rg < 4; ++rg) v[ni * 4 + rg] = sb(acc[ni][mi][rg], ni * 4 + rg);
-    if (NAT) epilogue_row_nat<EPI>(p, m, n0w, g, v, gam);
-    else epilogue_row<EPI, SF32>(p, m, n0w + 8 * g, n0w + 32 + 8 * g, v, gam);
+    if (NAT) epilogue_row_nat<EPI, A>(p, m, n0w, g, v, gam);
+    else epilogue_row<EPI, SF32, A>(p, m, n0w + 8 * g, n0w + 32 + 8 * g, v, gam);
   }
 }
 // XCD-aware tile id: blocks b and b+8 share an XCD; give each XCD a contiguous range of tiles
@@ -765,7 +766,7 @@ template <int N> __device__ __forceinline__ void wait_step() {   // lgkmcnt(0) +
 // Eight waves of (MI*16) x 64 outputs each.
 // TAG does nothing in the body: residual launches with K <= N (the attention projection, bound by its fp32-stream
 // epilogue) run an instantiation of their own so that profilers list them apart from fc2, like bench.py's classes.
-template <int EPI, int ALOAD, bool SF32, int WM, int WN, int MI, int NS, bool W8 = false, int TAG = 0>
+template <int EPI, int ALOAD, bool SF32, int WM, int WN, int MI, int NS, bool W8 = false, int TAG = 0, typename A = bf16_t>
 __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_bf16_tn_stream(const GemmParams p) {
   using C = Cfg<WN, NS, W8, WM * WN>;
   constexpr int NI = 4;                        // 16-column n-tiles per wave
@@ -912,7 +913,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_bf16_tn_stream(const Gem
     for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni)
-        acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv[ni], xc[mi], acc[ni][mi], 0, 0, 0);
+        acc[ni][mi] = mfma_16x16x32<A>(wv[ni], xc[mi], acc[ni][mi]);
       if constexpr (READ) {
         xn[mi] = *reinterpret_cast<const bf16x8*>(sb + xo[rks] + mi * 2048);
 #pragma unroll
@@ -1006,7 +1007,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_bf16_tn_stream(const Gem
 #endif
 
     // ---- epilogue (the next tile's first loads are in flight)
-    epilogue_tile<EPI, SF32, MI, W8>(p, acc, m0 + wm * (MI * 16), n0 + wn * 64, l15, g, pre, m_lo, inter,
+    epilogue_tile<A, EPI, SF32, MI, W8>(p, acc, m0 + wm * (MI * 16), n0 + wn * 64, l15, g, pre, m_lo, inter,
                                      (ROWMAJOR || ROWMAJOR_WIDE || TSTORE) ? smem + C::LDS_BYTES + wave * 2048 : nullptr);
 #ifdef RAJNI_GEMM_STAMPS
     if (p.stamps != nullptr && wave == 0) {
@@ -1038,7 +1039,7 @@ constexpr int LDS_BYTES = 2 * STAGE_BYTES;     // double buffered: 64 KiB
 __device__ __forceinline__ int key_x(int row) { return (row >> 1) & 7; }
 __device__ __forceinline__ int key_w(int row) { return ((row >> 4) & 3) * 2 + ((row >> 1) & 1); }
 
-template <int EPI, int ALOAD, bool SF32, bool W8 = false>
+template <int EPI, int ALOAD, bool SF32, bool W8 = false, typename A = bf16_t>
 __global__ void __launch_bounds__(256, 2) gemm_bf16_tn_128x128(const GemmParams p) {
   constexpr int MAP = col_map(EPI, SF32);      // W-row permutation = which output columns a lane owns
   constexpr int PW = W8 ? 2 : 4;               // W pieces per wave per K step (fp8 tile is 8 KiB)
@@ -1127,11 +1128,11 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_tn_128x128(const GemmParams 
       for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi)
-          acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ni], xf[mi], acc[ni][mi], 0, 0, 0);
+          acc[ni][mi] = mfma_16x16x32<A>(wf[ni], xf[mi], acc[ni][mi]);
     }
   }
 
-  epilogue_tile<EPI, SF32, 4, W8>(p, acc, m0 + wm * 64, n0 + wn * 64, l15, g, pre);
+  epilogue_tile<A, EPI, SF32, 4, W8>(p, acc, m0 + wm * 64, n0 + wn * 64, l15, g, pre);
 }
 }  // namespace small
 
@@ -1196,7 +1197,7 @@ __device__ __forceinline__ void epilogue_row_f32(const GemmParams& p, int m, int
   }
   const long yoff = orow * p.ldc + nb;
   if (nb + 16 <= p.N) {
-    store16<true>(p.Y, yoff, v);
+    store16<true, bf16_t>(p.Y, yoff, v);
   } else {
 #pragma unroll
     for (int j = 0; j < 16; ++j)
@@ -1325,7 +1326,7 @@ __global__ void cls_pos_kernel(const T* cls, const T* pos, int pos_has_cls, void
   const int b = i / C, c = i - b * C;
   float v = ld1(cls + c);
   if (pos_has_cls) v += ld1(pos + c);
-  store1<SF32>(x, (long)b * img_stride + c, v);
+  store1<SF32, T>(x, (long)b * img_stride + c, v);
 }
 
 // LDS stages of the wide tiling: 2 for bf16 weights (2 x 64 KiB); fp8 weights leave room for 3 (3 x 48 KiB)
@@ -1382,7 +1383,7 @@ inline int stream_grid(int total_tiles, int cus) { return total_tiles <= cus ? t
 // at 2 units and 8.878 / 8.838 at 0).  rajni_debug_set_resid_stagger(0) turns it off.
 int g_resid_stagger = 1;
 
-template <int EPI, int ALOAD, bool SF32, bool W8 = false>
+template <int EPI, int ALOAD, bool SF32, bool W8 = false, typename A = bf16_t>
 int launch_gemm(GemmParams p, int kclass, hipStream_t s) {
   p.stamps = rajni_g_stamps;
   p.stagger = g_resid_stagger;
@@ -1419,40 +1420,40 @@ int launch_gemm(GemmParams p, int kclass, hipStream_t s) {
     using C = wide::Cfg<4, RAJNI_W8_WIDE_NS_OR(W8), W8>;
     constexpr int NS = RAJNI_W8_WIDE_NS_OR(W8);
     constexpr int lds = C::LDS_BYTES + (((RAJNI_TSTORE && (EPI == EPI_BIAS || EPI == EPI_GELU)) || (nat_order(EPI, SF32) && EPI == EPI_RESID && !W8)) ? 8 * 2048 : 0);
-    if ((rc = set_lds_attr(&wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 2, 4, 8, NS, W8, 0>, lds, attr[1])) != RAJNI_OK) return rc;
+    if ((rc = set_lds_attr(&wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 2, 4, 8, NS, W8, 0, A>, lds, attr[1])) != RAJNI_OK) return rc;
     if constexpr (EPI == EPI_RESID)
-      if ((rc = set_lds_attr(&wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 2, 4, 8, NS, W8, 1>, lds, attr[3])) != RAJNI_OK) return rc;
+      if ((rc = set_lds_attr(&wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 2, 4, 8, NS, W8, 1, A>, lds, attr[3])) != RAJNI_OK) return rc;
     p.tiles_n = (p.N + 255) / 256;
     p.total_tiles = p.tiles_n * ((p.M + 255) / 256);
     p.nblk = n_block(p.tiles_n, (p.M + 255) / 256, 256, p.K, 2, cus);   // fp8 W: same blocks as bf16 (measured)
     const int grid = stream_grid(p.total_tiles, cus);
     if (EPI == EPI_RESID && kclass == KC_GEMM_RESID_SQ) {
       if constexpr (EPI == EPI_RESID)
-        hipLaunchKernelGGL((wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 2, 4, 8, NS, W8, 1>), dim3(grid), dim3(512), lds, s, p);
+        hipLaunchKernelGGL((wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 2, 4, 8, NS, W8, 1, A>), dim3(grid), dim3(512), lds, s, p);
     } else {
-      hipLaunchKernelGGL((wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 2, 4, 8, NS, W8, 0>), dim3(grid), dim3(512), lds, s, p);
+      hipLaunchKernelGGL((wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 2, 4, 8, NS, W8, 0, A>), dim3(grid), dim3(512), lds, s, p);
     }
   } else if (mode == 5) {
     using C = wide::Cfg<2, 3, W8>;
     // fp32-stream RESID: 2 KiB of LDS per wave behind the three stages for the epilogue's transpose (144 + 16 = 160 KiB)
     constexpr int lds = C::LDS_BYTES + (((nat_order(EPI, SF32) && EPI == EPI_RESID) || (RAJNI_TSTORE && (EPI == EPI_BIAS || EPI == EPI_GELU))) ? 8 * 2048 : 0);
-    if ((rc = set_lds_attr(&wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 4, 2, 4, 3, W8, 0>, lds, attr[2])) != RAJNI_OK) return rc;
+    if ((rc = set_lds_attr(&wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 4, 2, 4, 3, W8, 0, A>, lds, attr[2])) != RAJNI_OK) return rc;
     if constexpr (EPI == EPI_RESID)
-      if ((rc = set_lds_attr(&wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 4, 2, 4, 3, W8, 1>, lds, attr[4])) != RAJNI_OK) return rc;
+      if ((rc = set_lds_attr(&wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 4, 2, 4, 3, W8, 1, A>, lds, attr[4])) != RAJNI_OK) return rc;
     p.total_tiles = t256;
     p.nblk = n_block(p.tiles_n, (p.M + 255) / 256, 128, p.K, 2, cus);
     const int grid = stream_grid(p.total_tiles, cus);
     if (EPI == EPI_RESID && kclass == KC_GEMM_RESID_SQ) {
       if constexpr (EPI == EPI_RESID)
-        hipLaunchKernelGGL((wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 4, 2, 4, 3, W8, 1>), dim3(grid), dim3(512), lds, s, p);
+        hipLaunchKernelGGL((wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 4, 2, 4, 3, W8, 1, A>), dim3(grid), dim3(512), lds, s, p);
     } else {
-      hipLaunchKernelGGL((wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 4, 2, 4, 3, W8, 0>), dim3(grid), dim3(512), lds, s, p);
+      hipLaunchKernelGGL((wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 4, 2, 4, 3, W8, 0, A>), dim3(grid), dim3(512), lds, s, p);
     }
   } else {
     constexpr int lds = small::LDS_BYTES;
-    if ((rc = set_lds_attr(&small::gemm_bf16_tn_128x128<EPI, ALOAD, SF32, W8>, lds, attr[0])) != RAJNI_OK) return rc;
+    if ((rc = set_lds_attr(&small::gemm_bf16_tn_128x128<EPI, ALOAD, SF32, W8, A>, lds, attr[0])) != RAJNI_OK) return rc;
     p.total_tiles = t128;
-    hipLaunchKernelGGL((small::gemm_bf16_tn_128x128<EPI, ALOAD, SF32, W8>), dim3(t128), dim3(256), lds, s, p);
+    hipLaunchKernelGGL((small::gemm_bf16_tn_128x128<EPI, ALOAD, SF32, W8, A>), dim3(t128), dim3(256), lds, s, p);
   }
   RAJNI_CHECK_LAUNCH("gemm_bf16_tn");
   return RAJNI_OK;
@@ -1534,8 +1535,28 @@ extern "C" void rajni_debug_set_gemm_nblock_bytes(int bytes) { g_nblk_bytes = by
 // diagnostic builds (-DRAJNI_GEMM_STAMPS): device buffer of 4 x u64 per workgroup, or NULL
 extern "C" void rajni_debug_set_gemm_stamps(void* buf) { rajni_g_stamps = (unsigned long long*)buf; }
 
+// the 16-bit plans (bf16 or fp16 operands, A): same tilings, same shape-driven choice, the format's MFMA and conversions
+template <typename A>
+static int launch_linear16(const GemmParams& p, const rajni_linear_args& a, hipStream_t s) {
+  switch (a.epilogue) {
+    case RAJNI_EPI_BIAS: return launch_gemm<EPI_BIAS, ALOAD_PLAIN, false, false, A>(p, KC_GEMM_BIAS, s);
+    case RAJNI_EPI_BIAS_GELU: return launch_gemm<EPI_GELU, ALOAD_PLAIN, false, false, A>(p, KC_GEMM_GELU, s);
+    case RAJNI_EPI_BIAS_RESID:
+      RAJNI_REQUIRE(a.resid != nullptr && a.ldr % 8 == 0, RAJNI_ERR_INVALID,
+                    "rajni_linear: RESID epilogue needs resid and ldr %% 8 == 0");
+      return a.stream_f32 ? launch_gemm<EPI_RESID, ALOAD_PLAIN, true, false, A>(p, a.K <= a.N ? KC_GEMM_RESID_SQ : KC_GEMM_RESID, s)
+                          : launch_gemm<EPI_RESID, ALOAD_PLAIN, false, false, A>(p, a.K <= a.N ? KC_GEMM_RESID_SQ : KC_GEMM_RESID, s);
+    default:
+      rajni_set_error("rajni_linear: unknown epilogue %d", a.epilogue);
+      return RAJNI_ERR_INVALID;
+  }
+}
+
 int launch_linear(const rajni_linear_args& a, hipStream_t s) {
-  RAJNI_REQUIRE(a.dtype == RAJNI_BF16 || a.dtype == RAJNI_F32, RAJNI_ERR_INVALID, "rajni_linear: bad dtype %d", a.dtype);
+  RAJNI_REQUIRE(a.dtype == RAJNI_BF16 || a.dtype == RAJNI_F32 || a.dtype == RAJNI_F16, RAJNI_ERR_INVALID,
+                "rajni_linear: bad dtype %d", a.dtype);
+  RAJNI_REQUIRE(a.dtype != RAJNI_F16 || (a.w_scale == nullptr && a.x_scale == nullptr), RAJNI_ERR_UNSUPPORTED,
+                "rajni_linear: fp8 weights or activations need a bf16 model (dtype fp16 given)");
   RAJNI_REQUIRE(a.x && a.w && a.y, RAJNI_ERR_INVALID, "rajni_linear: null pointer");
   RAJNI_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0 && a.K % 64 == 0, RAJNI_ERR_INVALID,
                 "rajni_linear: M,N>0 and K %% 64 == 0 required (M=%d N=%d K=%d)", a.M, a.N, a.K);
@@ -1606,18 +1627,7 @@ int launch_linear(const rajni_linear_args& a, hipStream_t s) {
         return RAJNI_ERR_INVALID;
     }
   }
-  switch (a.epilogue) {
-    case RAJNI_EPI_BIAS: return launch_gemm<EPI_BIAS, ALOAD_PLAIN, false>(p, KC_GEMM_BIAS, s);
-    case RAJNI_EPI_BIAS_GELU: return launch_gemm<EPI_GELU, ALOAD_PLAIN, false>(p, KC_GEMM_GELU, s);
-    case RAJNI_EPI_BIAS_RESID:
-      RAJNI_REQUIRE(a.resid != nullptr && a.ldr % 8 == 0, RAJNI_ERR_INVALID,
-                    "rajni_linear: RESID epilogue needs resid and ldr %% 8 == 0");
-      return a.stream_f32 ? launch_gemm<EPI_RESID, ALOAD_PLAIN, true>(p, a.K <= a.N ? KC_GEMM_RESID_SQ : KC_GEMM_RESID, s)
-                          : launch_gemm<EPI_RESID, ALOAD_PLAIN, false>(p, a.K <= a.N ? KC_GEMM_RESID_SQ : KC_GEMM_RESID, s);
-    default:
-      rajni_set_error("rajni_linear: unknown epilogue %d", a.epilogue);
-      return RAJNI_ERR_INVALID;
-  }
+  return a.dtype == RAJNI_F16 ? launch_linear16<f16_t>(p, a, s) : launch_linear16<bf16_t>(p, a, s);
 }
 
 // the fused im2col loader reads 16-byte runs of a patch row with shifts: power-of-two patches of >= 8 pixels
@@ -1667,7 +1677,8 @@ int launch_patch_embed(const void* images, const void* w, const float* bias, con
   RAJNI_REQUIRE(P >= 1 && S % P == 0 && B > 0 && Cin > 0, RAJNI_ERR_INVALID,
                 "rajni_patch_embed: the patch size must divide the image (P=%d S=%d)", P, S);
   RAJNI_REQUIRE(C % 8 == 0, RAJNI_ERR_UNSUPPORTED, "rajni_patch_embed: C %% 8 == 0 required");
-  RAJNI_REQUIRE(dtype == RAJNI_BF16 || dtype == RAJNI_F32, RAJNI_ERR_INVALID, "rajni_patch_embed: bad dtype %d", dtype);
+  RAJNI_REQUIRE(dtype == RAJNI_BF16 || dtype == RAJNI_F32 || dtype == RAJNI_F16, RAJNI_ERR_INVALID,
+                "rajni_patch_embed: bad dtype %d", dtype);
   const int K = Cin * P * P, kpad = (K + 63) / 64 * 64;
   const int gw = S / P, npatch = gw * gw;
   GemmParams p{};
@@ -1684,6 +1695,9 @@ int launch_patch_embed(const void* images, const void* w, const float* bias, con
     p.X = images; p.lda = 0;
     p.cin = Cin; p.S = S; p.log2ps = log2ps;
     if (dtype == RAJNI_F32) rc = f32::launch<EPI_PATCH, ALOAD_PATCH>(p, KC_GEMM_PATCH, s);
+    else if (dtype == RAJNI_F16)
+      rc = out_f32 ? launch_gemm<EPI_PATCH, ALOAD_PATCH, true, false, f16_t>(p, KC_GEMM_PATCH, s)
+                   : launch_gemm<EPI_PATCH, ALOAD_PATCH, false, false, f16_t>(p, KC_GEMM_PATCH, s);
     else rc = out_f32 ? launch_gemm<EPI_PATCH, ALOAD_PATCH, true>(p, KC_GEMM_PATCH, s)
                       : launch_gemm<EPI_PATCH, ALOAD_PATCH, false>(p, KC_GEMM_PATCH, s);
   } else {
@@ -1696,12 +1710,15 @@ int launch_patch_embed(const void* images, const void* w, const float* bias, con
       const dim3 grid((unsigned)((total8 + 255) / 256)), block(256);
       if (dtype == RAJNI_F32)
         hipLaunchKernelGGL(im2col_kernel<float>, grid, block, 0, s, (const float*)images, (float*)ws, Cin, S, P, gw, kpad, total8);
-      else
+      else   // a byte copy: the bf16 instantiation serves fp16 images too
         hipLaunchKernelGGL(im2col_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)images, (bf16_t*)ws, Cin, S, P, gw, kpad, total8);
       RAJNI_CHECK_LAUNCH("im2col_kernel");
     }
     p.X = ws; p.lda = kpad;
     if (dtype == RAJNI_F32) rc = f32::launch<EPI_PATCH, ALOAD_PLAIN>(p, KC_GEMM_PATCH, s);
+    else if (dtype == RAJNI_F16)
+      rc = out_f32 ? launch_gemm<EPI_PATCH, ALOAD_PLAIN, true, false, f16_t>(p, KC_GEMM_PATCH, s)
+                   : launch_gemm<EPI_PATCH, ALOAD_PLAIN, false, false, f16_t>(p, KC_GEMM_PATCH, s);
     else rc = out_f32 ? launch_gemm<EPI_PATCH, ALOAD_PLAIN, true>(p, KC_GEMM_PATCH, s)
                       : launch_gemm<EPI_PATCH, ALOAD_PLAIN, false>(p, KC_GEMM_PATCH, s);
   }
@@ -1713,6 +1730,12 @@ int launch_patch_embed(const void* images, const void* w, const float* bias, con
     const long stride = (long)(npatch + 1) * C;
     if (dtype == RAJNI_F32)
       hipLaunchKernelGGL((cls_pos_kernel<true, float>), grid, block, 0, s, (const float*)cls, (const float*)pos,
+                         pos_has_cls, x, stride, B, C);
+    else if (dtype == RAJNI_F16 && out_f32)
+      hipLaunchKernelGGL((cls_pos_kernel<true, f16_t>), grid, block, 0, s, (const f16_t*)cls, (const f16_t*)pos,
+                         pos_has_cls, x, stride, B, C);
+    else if (dtype == RAJNI_F16)
+      hipLaunchKernelGGL((cls_pos_kernel<false, f16_t>), grid, block, 0, s, (const f16_t*)cls, (const f16_t*)pos,
                          pos_has_cls, x, stride, B, C);
     else if (out_f32)
       hipLaunchKernelGGL((cls_pos_kernel<true, bf16_t>), grid, block, 0, s, (const bf16_t*)cls, (const bf16_t*)pos,

@@ -335,7 +335,7 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_stream(const GemmParams p) 
         pre.valid = inter;
         scratch = smem + LDS_BYTES + wave * 2048;     // host: 16 KiB more dynamic LDS for these instantiations
       }
-      epilogue_tile<EPI, SF32, MI, true>(p, acc, m_base, n0w, l15, g, pre, 0, inter, scratch);
+      epilogue_tile<bf16_t, EPI, SF32, MI, true>(p, acc, m_base, n0w, l15, g, pre, 0, inter, scratch);
     }
     __builtin_amdgcn_sched_barrier(0);    // keep the fragment reads below the epilogue (hoisted, they cost it 64 VGPRs)
 #ifdef RAJNI_GEMM_STAMPS

@@ -65,9 +65,9 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const TX* __restrict__ x
 // R rows per wave (fp32 rows in, bf16 out, C <= 1024): R times the loads in flight per wave.  The one-row kernel keeps 3 KB per wave in
 // flight at 8 waves per SIMD - Little's law put that short of the HBM rate: LayerNorm was a latency-bound kernel, not a bandwidth-bound one
 // (two rows, still 64 VGPRs = 8 waves: 772 -> 715 us per forward; the e4m3-output kernel, with four wave reductions per row, loses with two).
-template <int NC, int R>
+template <int NC, int R, typename TY = bf16_t>
 __global__ void __launch_bounds__(256) layernorm_rows_kernel(const float* __restrict__ x, long xs, const float* __restrict__ w,
-                                                             const float* __restrict__ b, bf16_t* __restrict__ y, int rows, int C, float eps) {
+                                                             const float* __restrict__ b, TY* __restrict__ y, int rows, int C, float eps) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int r0 = (blockIdx.x * 4 + wave) * R;
   if (r0 >= rows) return;
@@ -124,7 +124,7 @@ __global__ void __launch_bounds__(256) layernorm_rows_kernel(const float* __rest
         float o[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = fmaf((v[r][i][j] - mean[r]) * rstd[r], wv[j], bv[j]);
-        if (r0 + r < rows) store8<bf16_t>(y + (long)(r0 + r) * C + c * 8, o);
+        if (r0 + r < rows) store8<TY>(y + (long)(r0 + r) * C + c * 8, o);
       }
     }
   }
@@ -365,6 +365,9 @@ __global__ void __launch_bounds__(256) gather_rows_kernel(const uint4* __restric
 
 }  // namespace
 
+static int launch_layernorm_f16(const void* x, long xs, const float* w, const float* b, void* y, int rows,
+                                int C, float eps, int x_f32, hipStream_t s);
+
 int launch_layernorm(const void* x, long xs, const float* w, const float* b, void* y, int rows,
                      int C, float eps, int x_f32, int dtype, hipStream_t s) {
   RAJNI_REQUIRE(x && w && b && y, RAJNI_ERR_INVALID, "rajni_layernorm: null pointer");
@@ -373,6 +376,7 @@ int launch_layernorm(const void* x, long xs, const float* w, const float* b, voi
   const bool f32io = dtype == RAJNI_F32;
   ProfScope prof(KC_LAYERNORM, s, 8.0 * rows * C, (f32io ? 8.0 : (x_f32 ? 6.0 : 4.0)) * rows * C);
   const dim3 grid((rows + 3) / 4), block(256);
+  if (dtype == RAJNI_F16) return launch_layernorm_f16(x, xs, w, b, y, rows, C, eps, x_f32, s);
   if (f32io)
     hipLaunchKernelGGL((layernorm_kernel<float, float>), grid, block, 0, s, (const float*)x, xs, w, b, (float*)y, rows, C, eps);
   else if (x_f32 && RAJNI_LN_ROWS > 1 && C <= 1024 && rows >= 4096)
@@ -382,6 +386,20 @@ int launch_layernorm(const void* x, long xs, const float* w, const float* b, voi
     hipLaunchKernelGGL((layernorm_kernel<float, bf16_t>), grid, block, 0, s, (const float*)x, xs, w, b, (bf16_t*)y, rows, C, eps);
   else
     hipLaunchKernelGGL((layernorm_kernel<bf16_t, bf16_t>), grid, block, 0, s, (const bf16_t*)x, xs, w, b, (bf16_t*)y, rows, C, eps);
+  RAJNI_CHECK_LAUNCH("layernorm_kernel");
+  return RAJNI_OK;
+}
+// fp16 models: the same kernels and the same choice, fp16 output (and input when the stream is fp16)
+static int launch_layernorm_f16(const void* x, long xs, const float* w, const float* b, void* y, int rows,
+                                int C, float eps, int x_f32, hipStream_t s) {
+  const dim3 grid((rows + 3) / 4), block(256);
+  if (x_f32 && RAJNI_LN_ROWS > 1 && C <= 1024 && rows >= 4096)
+    hipLaunchKernelGGL((layernorm_rows_kernel<2, RAJNI_LN_ROWS, f16_t>), dim3((rows + 4 * RAJNI_LN_ROWS - 1) / (4 * RAJNI_LN_ROWS)), block, 0, s,
+                       (const float*)x, xs, w, b, (f16_t*)y, rows, C, eps);
+  else if (x_f32)
+    hipLaunchKernelGGL((layernorm_kernel<float, f16_t>), grid, block, 0, s, (const float*)x, xs, w, b, (f16_t*)y, rows, C, eps);
+  else
+    hipLaunchKernelGGL((layernorm_kernel<f16_t, f16_t>), grid, block, 0, s, (const f16_t*)x, xs, w, b, (f16_t*)y, rows, C, eps);
   RAJNI_CHECK_LAUNCH("layernorm_kernel");
   return RAJNI_OK;
 }

@@ -31,7 +31,7 @@ constexpr int SS_PART = 512;
 #define RAJNI_SS_VUM 6
 #endif
 
-struct ScoreArgs {          // T = activation dtype (bf16_t or float)
+struct ScoreArgs {          // T = activation dtype (bf16_t, f16_t or float)
   const void* qkv;          // T [B,N,3C] or null (select-only)
   const void* scores_in;    // T [B,N] (select-only)
   int N, H, D;
@@ -372,8 +372,9 @@ __global__ void __launch_bounds__(SS_THREADS) score_select_kernel(const ScoreArg
   const int per_iter = SS_THREADS / tpt, sl = tid & (tpt - 1);
   // The count loop is VALU bound (N^2 compares over 4 SIMDs: stamps put it at 14k of the kernel's 88k cycles at 197
   // tokens, 95k of 297k at 577, when a compare was ~8 instructions: two range tests, >, ==, index test, or / and / add).
-  // 16-bit scores (the bf16 path): ONE unsigned compare per pair on a packed key
+  // 16-bit scores (bf16 and fp16): ONE unsigned compare per pair on a packed key
   //     key32[j] = sortable16(score_j) << 16 | (0xFFFF - j)        (NaN = +inf, -0 = +0; N <= 65535)
+  // (sortable16 of the score's own 16-bit pattern: for bf16 that is the upper half of the fp32 pattern, for fp16 not)
   // "j beats i" (larger score, or equal score and lower index - the defined tie rule) <=> key32[j] > key32[i], and the
   // CLS slot and the padding hold 0 (below every real key), so slices need no range tests: v_cmp + add-with-carry.
   // fp32 scores keep the float compare (the accuracy path).
@@ -388,10 +389,19 @@ __global__ void __launch_bounds__(SS_THREADS) score_select_kernel(const ScoreArg
       const int n = off < cps * 4 ? slw * cps * 4 + off : N;     // token of word w (padding words: none)
       unsigned k = 0;
       if (n >= 1 && n < N) {
-        unsigned u = __float_as_uint(rank_key(sc[n]));
-        u = (u == 0x80000000u) ? 0u : u;                            // -0 ranks as +0
-        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);             // monotone float -> unsigned
-        k = (u & 0xFFFF0000u) | (unsigned)(0xFFFF - n);
+        if constexpr (__is_same(T, f16_t)) {
+          // fp16 scores: the upper half of the fp32 pattern would merge fp16 values that differ below bf16 precision,
+          // so the key is built from the fp16 pattern itself (exact: sc holds fp16 values; NaN -> +inf first)
+          unsigned u = __builtin_bit_cast(unsigned short, f2h(rank_key(sc[n])));
+          u = (u == 0x8000u) ? 0u : u;                              // -0 ranks as +0
+          u = (u & 0x8000u) ? (~u & 0xFFFFu) : (u | 0x8000u);       // monotone half -> unsigned
+          k = (u << 16) | (unsigned)(0xFFFF - n);
+        } else {   // bf16 scores: the upper half of the fp32 pattern is the bf16 pattern
+          unsigned u = __float_as_uint(rank_key(sc[n]));
+          u = (u == 0x80000000u) ? 0u : u;                            // -0 ranks as +0
+          u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);             // monotone float -> unsigned
+          k = (u & 0xFFFF0000u) | (unsigned)(0xFFFF - n);
+        }
       }
       keys32[w] = k;
     }
@@ -478,7 +488,7 @@ extern "C" void rajni_debug_force_score_two_pass(int on) { g_ss_force_two_pass =
 int launch_score_select(const void* qkv, const void* scores_in, int B, int N, int H, int D,
                         float eps, int keep, void* scores_out, int32_t* keep_idx,
                         void* next_scores, int dtype, hipStream_t s) {
-  RAJNI_REQUIRE(dtype == RAJNI_BF16 || dtype == RAJNI_F32, RAJNI_ERR_INVALID, "score/select: bad dtype %d", dtype);
+  RAJNI_REQUIRE(dtype == RAJNI_BF16 || dtype == RAJNI_F32 || dtype == RAJNI_F16, RAJNI_ERR_INVALID, "score/select: bad dtype %d", dtype);
   RAJNI_REQUIRE(B > 0 && N >= 2, RAJNI_ERR_INVALID, "score/select: need B > 0 and N >= 2 (B=%d N=%d)", B, N);
   RAJNI_REQUIRE(keep >= 0 && keep <= N - 1, RAJNI_ERR_INVALID,
                 "score/select: keep=%d out of range for N=%d (keep_ratio must be <= 1)", keep, N);
@@ -505,7 +515,10 @@ int launch_score_select(const void* qkv, const void* scores_in, int B, int N, in
                 "score/select: N=%d H=%d D=%d needs %zu B of LDS (> 160 KiB)", N, H, D, lds);
   const bool f32 = dtype == RAJNI_F32;
   typedef void (*kern_t)(const ScoreArgs);
-  const kern_t kern = qkv ? (merged ? (f32 ? &score_select_kernel<true, float, true> : &score_select_kernel<true, bf16_t, true>)
+  const kern_t kern = dtype == RAJNI_F16
+      ? (qkv ? (merged ? &score_select_kernel<true, f16_t, true> : &score_select_kernel<true, f16_t, false>)
+             : &score_select_kernel<false, f16_t, false>)
+      : qkv ? (merged ? (f32 ? &score_select_kernel<true, float, true> : &score_select_kernel<true, bf16_t, true>)
                                     : (f32 ? &score_select_kernel<true, float, false> : &score_select_kernel<true, bf16_t, false>))
                           : (f32 ? &score_select_kernel<false, float, false> : &score_select_kernel<false, bf16_t, false>);
   if (lds > 64 * 1024) {

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RAJNI_HIP_LIB") or os.path.join(_HERE, "lib", "librajni_hip.so")
 
-RAJNI_F32, RAJNI_BF16 = 0, 1
+RAJNI_F32, RAJNI_BF16, RAJNI_F16 = 0, 1, 2
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID = 0, 1, 2
 NUM_KCLASS = 17
 
@@ -164,6 +164,8 @@ def device_guard(device):
 def dtype_code(dt: torch.dtype) -> int:
     if dt == torch.bfloat16:
         return RAJNI_BF16
+    if dt == torch.float16:
+        return RAJNI_F16
     if dt == torch.float32:
         return RAJNI_F32
     raise NotImplementedError(f"rajni_amd: dtype {dt} is not supported (bfloat16 is the built compute type)")

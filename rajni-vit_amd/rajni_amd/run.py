@@ -40,15 +40,16 @@ def get_args(argv=None):
     p.add_argument("--max_batches", type=int, default=None)
     p.add_argument("--compare_base", action="store_true")
     p.add_argument("--synthetic", action="store_true", help="seeded randn batches generated on the device")
-    p.add_argument("--dtype", type=str, default="bfloat16", choices=["bfloat16", "float32"])
+    p.add_argument("--dtype", type=str, default="bfloat16", choices=["bfloat16", "float16", "float32"])
     p.add_argument("--weights", type=str, default=None, help="local timm-format state dict (.safetensors / .pt)")
     p.add_argument("--pretrained", action="store_true", help="timm pretrained weights (needs timm + network)")
     p.add_argument("--seed", type=int, default=0)
     # build-specific opt-ins (none of them exists in the reference CLI; defaults = the reference-faithful path)
     p.add_argument("--weight_format", type=str, default="model", choices=["model", "fp8", "fp8_mfma"],
                    help="RAJNIViTWrapper.set_weight_format: e4m3 block weights (fp8) / plus e4m3 activations on the fp8 matrix pipe (fp8_mfma)")
-    p.add_argument("--residual", type=str, default="float32", choices=["float32", "bfloat16"],
-                   help="residual stream precision between blocks (RAJNIViTWrapper.set_residual_dtype)")
+    p.add_argument("--residual", type=str, default="float32", choices=["float32", "bfloat16", "float16"],
+                   help="residual stream precision between blocks (RAJNIViTWrapper.set_residual_dtype; "
+                        "a 16-bit stream must match --dtype)")
     return p.parse_args(argv)
 
 
@@ -184,8 +185,8 @@ def main(argv=None):
     model = RAJNIViTWrapper(base2.to(dtype), schedule).to(device).eval()
     if args.weight_format != "model":
         model.set_weight_format(args.weight_format)
-    if args.residual == "bfloat16":
-        model.set_residual_dtype(torch.bfloat16)
+    if args.residual != "float32":
+        model.set_residual_dtype(getattr(torch, args.residual))
     say("Evaluating RAJNI model (HIP path)...")
     acc, thr = evaluate_model(model, loader, device=device, max_batches=args.max_batches, warmup=args.warmup)
     say(f"RAJNI accuracy: {acc:.2f}%  throughput: {thr:.1f} img/s")

@@ -71,8 +71,10 @@ class RAJNIViTWrapper(nn.Module):
         self._forced: Dict[int, torch.Tensor] = {}
         self._trace_scores = False
         # residual stream precision between blocks: fp32 (default; see DESIGN.md "numerics") or the
-        # model dtype like the reference's bf16 model (`set_residual_dtype(torch.bfloat16)`)
-        self._resid_bf16 = False
+        # model's 16-bit dtype like the reference's bf16 / fp16 model (`set_residual_dtype(torch.bfloat16)` or
+        # `(torch.float16)`; it must match the model dtype at forward)
+        self._resid_bf16 = False   # 16-bit stream (rajni_vit_plan.resid_bf16)
+        self._resid_dtype = torch.float32
         # storage format of the four big Linear weights of every block: "model" = the model dtype,
         # "fp8" = e4m3 bytes + per-row fp32 scale (`set_weight_format("fp8")`, bf16 models only)
         self._weight_format = "model"
@@ -108,9 +110,10 @@ class RAJNIViTWrapper(nn.Module):
         self._plans = {}
 
     def set_residual_dtype(self, dtype):
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("residual stream dtype must be torch.float32 or torch.bfloat16")
-        self._resid_bf16 = dtype == torch.bfloat16
+        if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError("residual stream dtype must be torch.float32, torch.bfloat16 or torch.float16")
+        self._resid_bf16 = dtype != torch.float32
+        self._resid_dtype = dtype
         self._drop_plans()
         return self
 
@@ -413,6 +416,9 @@ class RAJNIViTWrapper(nn.Module):
         if x.dim() != 4 or x.shape[-1] != x.shape[-2]:
             raise ValueError(f"expected images [B, C, S, S], got {tuple(x.shape)}")
         dtype = self.m.cls_token.dtype
+        if self._resid_bf16 and dtype in (torch.bfloat16, torch.float16) and self._resid_dtype != dtype:
+            raise ValueError(f"a {self._resid_dtype} residual stream needs a {self._resid_dtype} model (the model is {dtype}); "
+                             f"the 16-bit stream is kept in the model dtype")
         if self.m.cls_token.device != x.device:
             raise nat.NativeError(f"model is on {self.m.cls_token.device} but images are on {x.device}")
         if x.dtype != dtype:

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Compile csrc/gemm.hip for gfx950 (device pass only, ~15 s, no GPU needed) and check two properties of
-the persistent GEMM kernels that cost 10-15 % each when they break:
+the persistent GEMM kernels (bf16 and fp16 operand instantiations alike) that cost 10-15 % each when they break
+(DESIGN.md section 4):
   * no `s_waitcnt vmcnt(0)` and no scratch access inside the inner K loop (either one drains the LDS-DMA
     queue in every K step);
   * no register spills inside that loop, and at most 64 bytes per lane outside it, in the instantiations the dispatcher
@@ -25,6 +26,12 @@ def kernel_id(mangled):
         m = re.search(r"gemm_f8_tn_(?:stream|wide)I(.*?)EEv", mangled)
         return ("f8",) + tuple(int(x[2:]) for x in re.findall(r"L[ib]\d+", m.group(1)))
     return tuple(int(x[2:]) for x in re.findall(r"L[ib]\d+", m.group(1)))
+
+
+def operand_format(mangled):
+    """16-bit operand format of a gemm_bf16_tn_stream instantiation (its last template argument: unsigned short = the raw
+    bf16 bits, _Float16 = fp16 models); the fp8 x fp8 kernels have none"""
+    return "f16" if "DF16_" in mangled else ("f8" if "gemm_f8_" in mangled else "bf16")
 
 
 def dispatched(k):
@@ -56,7 +63,7 @@ def scan(asm_path):
         m = re.search(r"; ScratchSize: (\d+)", line)
         if m:
             spills = int(m.group(1))
-            rows.append((kernel_id(name), drains, scratch, spills))
+            rows.append((kernel_id(name), drains, scratch, spills, operand_format(name)))
             name = None
     return rows
 
@@ -68,14 +75,14 @@ def main():
         subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         rows = scan(out)
     bad = 0
-    for k, drains, scratch, spills in sorted(rows, key=lambda r: tuple(map(str, r[0]))):
+    for k, drains, scratch, spills, fmt in sorted(rows, key=lambda r: (tuple(map(str, r[0])), r[4])):
         prod = dispatched(k)
         # spills outside the K loop: up to SPILL_BYTES_OUTSIDE_LOOP per lane are tolerated (the 256 x 256 RESID instantiation -
         # 128 accumulators - keeps 36 bytes of its EDGE-tile epilogue's operands in scratch: a handful of scratch accesses
         # per tile, none in the K loop); anything inside the loop is a violation
         ok = (drains == 0 and scratch == 0 and spills <= SPILL_BYTES_OUTSIDE_LOOP) or not prod
         bad += not ok
-        print(f"stream<{','.join(map(str, k))}>  in-loop vmcnt(0): {drains}  in-loop scratch: {scratch}  "
+        print(f"stream<{','.join(map(str, k))}> {fmt:4s}  in-loop vmcnt(0): {drains}  in-loop scratch: {scratch}  "
               f"scratch bytes/lane: {spills}  {'dispatched' if prod else 'test hook only'}  {'ok' if ok else 'VIOLATION'}")
     if not rows:
         print("no persistent GEMM kernels found in the ISA")
