@@ -56,38 +56,33 @@ struct GemmParams {
                                 // first tile (see g_resid_stagger); 0 = off
 };
 
-// exact-erf GELU (timm nn.GELU()) for the bf16 path, two values per instruction (v_pk_*_f32, no
-// transcendentals):  gelu(x) = x*(0.5 + h(x)),  h(x) = 0.5*erf(x/sqrt2) ~= xc*P(xc^2),
-// xc = clamp(x, +-3*sqrt2), P = degree-8 least-squares fit on Chebyshev nodes (coefficients from
-// tools/fit_gelu.py).  |gelu error| <= 4.3e-5 absolute - 1/50 of a bf16 ulp at |y| ~ 1 - measured
-// against fp64 erf over [-8, 8].  The FC1 epilogue is VALU bound: the previous exp+rcp form
+// exact-erf GELU (timm nn.GELU()) for the 16-bit paths, two values per instruction (v_pk_*_f32, no
+// transcendentals):  gelu(x) = xl*(0.5 + h(x)),  h(x) = 0.5*erf(x/sqrt2) ~= xc*P(xc^2),
+// xc = clamp(x, +-3*sqrt2), xl = max(x, -3*sqrt2), P = degree-8 least-squares fit on Chebyshev nodes (coefficients from
+// tools/fit_gelu.py).  |gelu error| <= 4.24e-5 absolute - 1/50 of a bf16 ulp at |y| ~ 1 - against fp64 erf over [-8, 8]
+// (tools/fit_gelu.py, this evaluation order; the maximum sits at the clamp point), and <= 1.21e-5 for every x below the
+// clamp: the final multiplier is xl, not x, so the residual 0.5 + h(-X0) = 2.8e-6 is never scaled by a large |x| (with x
+// itself the tail read -4.2e-5 at x = -15 and -2.8e-2 at x = -1e4, pre-activations a 16-bit model can produce).  Above the
+// clamp the same residual is a RELATIVE error of 2.8e-6, far inside a 16-bit output's rounding.  For x >= -X0 the result is
+// bit for bit what the unclamped multiplier gave.  Cost: the clamp is v_max_f32 + v_min_f32 where it was one v_med3_f32
+// (+1 of ~9 VALU issues per element; 0.5 % of the ViT-B forward).  Two forms that keep the count were
+// measured and not taken: a lower clamp at -4.24506521, where this evaluation order gives h = -0.5 exactly on the device (the
+// tail is then exactly 0, but the error between the two clamp points rises to 4.98e-5 and the constant depends on the
+// instruction sequence), and x * clamp(0.5 + x P(x^2), 0, 1) without an argument clamp (fewer instructions than before and
+// exact tails, but other fp32 bits for every x: two selection-sensitive fp8 forward tests then miss their bars).
+// tests/test_gpu_numerics.py holds the 16-bit epilogues to 5e-5 + one output rounding on a chosen grid.
+// The FC1 epilogue is VALU bound: the previous exp+rcp form
 // (Abramowitz-Stegun 7.1.26) cost ~20k cycles per 256x256 tile, a third of the tile's time.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 gelu_pk(f32x2 x) {
-  const float X0 = 4.24264069f;
-  f32x2 xc = __builtin_elementwise_min(__builtin_elementwise_max(x, f32x2{-X0, -X0}), f32x2{X0, X0});
-  const f32x2 u = xc * xc;
-  f32x2 q = f32x2{5.405088552e-11f, 5.405088552e-11f};
-  q = q * u + f32x2{-5.202485173e-09f, -5.202485173e-09f};
-  q = q * u + f32x2{2.215015442e-07f, 2.215015442e-07f};
-  q = q * u + f32x2{-5.557312053e-06f, -5.557312053e-06f};
-  q = q * u + f32x2{9.274613401e-05f, 9.274613401e-05f};
-  q = q * u + f32x2{-1.104852507e-03f, -1.104852507e-03f};
-  q = q * u + f32x2{9.805144109e-03f, 9.805144109e-03f};
-  q = q * u + f32x2{-6.633033261e-02f, -6.633033261e-02f};
-  q = q * u + f32x2{3.988969665e-01f, 3.988969665e-01f};
-  const f32x2 h = xc * q;
-  return x * h + x * f32x2{0.5f, 0.5f};
-}
-// the same for two pairs at once, the two Horner chains interleaved statement by statement: a packed fp32 op that reads the
+// two pairs at once, the two Horner chains interleaved statement by statement: a packed fp32 op that reads the
 // result of the one issued right before it costs a wait state (hipcc pads with s_nop 0: the single-chain form had one
 // behind almost every v_pk_fma_f32 - ~600 per tile and wave, a quarter on top of the epilogue's VALU time); two
-// independent chains fill each other's slots.  Same operations per element: bit-identical results.
+// independent chains fill each other's slots.
 __device__ __forceinline__ void gelu_pk4(f32x2& a, f32x2& b) {
   const float X0 = 4.24264069f;
   const f32x2 lo = f32x2{-X0, -X0}, hi = f32x2{X0, X0};
-  const f32x2 ac = __builtin_elementwise_min(__builtin_elementwise_max(a, lo), hi);
-  const f32x2 bc = __builtin_elementwise_min(__builtin_elementwise_max(b, lo), hi);
+  const f32x2 al = __builtin_elementwise_max(a, lo), bl = __builtin_elementwise_max(b, lo);
+  const f32x2 ac = __builtin_elementwise_min(al, hi), bc = __builtin_elementwise_min(bl, hi);
   const f32x2 ua = ac * ac, ub = bc * bc;
   f32x2 qa = f32x2{5.405088552e-11f, 5.405088552e-11f}, qb = qa;
 #define RAJNI_GELU_STEP(c) { const f32x2 k = f32x2{c, c}; qa = qa * ua + k; qb = qb * ub + k; }
@@ -102,7 +97,7 @@ __device__ __forceinline__ void gelu_pk4(f32x2& a, f32x2& b) {
 #undef RAJNI_GELU_STEP
   const f32x2 ha = ac * qa, hb = bc * qb;
   const f32x2 half = f32x2{0.5f, 0.5f};
-  const f32x2 ya = a * ha + a * half, yb = b * hb + b * half;
+  const f32x2 ya = al * ha + al * half, yb = bl * hb + bl * half;
   a = ya; b = yb;
 }
 

@@ -3,8 +3,9 @@ the CPU oracle on the same seeded inputs.  GPU box only (`-m gpu`).
 
 Tolerances: integer/index results are bit exact.  bf16 results are compared with the fp64 oracle
 evaluated on the same bf16-representable inputs; the only legitimate difference is fp32
-accumulation order plus ONE bf16 rounding of the output (rel 2^-9 = 0.2 %), so `rtol=1e-2` of the
-tensor's scale is the bar BASELINE.json states for bf16.
+accumulation order plus ONE bf16 rounding of the output (unit roundoff 2^-8 = 0.39 % of the element), so
+`rtol=1e-2` of the tensor's scale is the bar BASELINE.json states for bf16.  That one global scale does not
+see wrong SMALL values: tests/test_gpu_numerics.py holds the same kernels to per-element budgets on stress inputs.
 """
 import json
 import os

@@ -12,11 +12,34 @@ a, *_ = np.linalg.lstsq(V * w[:, None], f * w, rcond=None)
 c = [0.5 / np.sqrt(2) * a[i] / 2 ** i for i in range(n)]
 print("X0 =", zmax * np.sqrt(2))
 print(", ".join("%.9ef" % v for v in c))
-x = np.linspace(-8, 8, 400001).astype(np.float32)
-xc = np.clip(x, -np.float32(zmax * np.sqrt(2)), np.float32(zmax * np.sqrt(2)))
-acc = np.full_like(x, np.float32(c[-1]))
-for v in c[-2::-1]:
-    acc = acc * (xc * xc) + np.float32(v)
-g = x * (xc * acc) + np.float32(0.5) * x
-ref = 0.5 * x.astype(np.float64) * (1 + erf(x.astype(np.float64) / np.sqrt(2)))
-print("max |gelu err| (fp32 Horner) = %.3e" % np.abs(g - ref).max())
+# the kernel's own evaluation order in fp32 (gelu_pk): fused multiply-adds, and the LOWER-clamped x as the final multiplier
+# (with the unclamped x the residual 0.5 + h(-X0) = 2.8e-6 would scale with |x|: -2.8e-2 at x = -1e4)
+f32 = np.float32
+X0 = f32(zmax * np.sqrt(2))
+
+
+def fma(a, b, k):
+    return (a.astype(np.float64) * b.astype(np.float64) + np.float64(k)).astype(f32)
+
+
+def gelu_pk(x):
+    xl = np.maximum(x.astype(f32), -X0)
+    xc = np.minimum(xl, X0)
+    u = xc * xc
+    acc = np.full_like(xl, f32(c[-1]))
+    for v in c[-2::-1]:
+        acc = fma(acc, u, f32(v))
+    return fma(xl, xc * acc, xl * f32(0.5))
+
+
+def gelu64(x):
+    x = x.astype(np.float64)
+    return 0.5 * x * (1 + erf(x / np.sqrt(2)))
+
+
+x = np.linspace(-8, 8, 400001).astype(f32)
+x = np.concatenate([x, [np.nextafter(X0, f32(0)), X0, np.nextafter(X0, f32(9))]]).astype(f32)
+x = np.concatenate([x, -x])
+print("max |gelu err| on [-8, 8] (fp32 fma Horner) = %.3e" % np.abs(gelu_pk(x) - gelu64(x)).max())
+t = -(2.0 ** np.arange(3, 17)).astype(f32)
+print("max |gelu err| for x = -2^3 .. -2^16        = %.3e" % np.abs(gelu_pk(t) - gelu64(t)).max())
