@@ -230,6 +230,59 @@ size_t rajni_vit_workspace_bytes(const rajni_vit_plan* plan);
 int rajni_vit_forward(const rajni_vit_plan* plan, const void* images, void* logits,
                       rajni_stream_t stream);
 
+/* ---- timm VisionTransformer options the reference drops (deviation B4) ----
+ * The reference wrapper reads none of attn.q_norm / attn.k_norm, norm_pre, global_pool and fc_norm (model.py:34-37,
+ * 65-66, attention.py:8-12 take a fixed attribute set), so it mis-computes every model that has one.  The semantics
+ * below are timm's (timm/models/vision_transformer.py: Attention.forward, VisionTransformer.forward_features, .pool,
+ * .forward_head).  All statistics are fp32 and two-pass, every sum has one fixed order: the same input gives the same
+ * bits.  LayerNorm weights are fp32 and required, biases fp32 or NULL (= 0). */
+
+/* q = q_norm(q); k = k_norm(k)   (timm Attention.forward: `q, k = self.q_norm(q), self.k_norm(k)`, both
+ * nn.LayerNorm(D), one module for all heads), IN PLACE on the q and k thirds of qkv [rows, 3*H*D]; the v third is
+ * neither read nor written.  Score+select, attention and the fp8 attention output read the buffer afterwards, so the
+ * importance scores are the CLS row of the attention the block performs.  D % 8 == 0, 8 <= D <= 128 (D = 64: a group
+ * is one 128-byte line of 8 lanes; other head dims share a general form). */
+int rajni_qk_norm(void* qkv, const float* q_w, const float* q_b, const float* k_w, const float* k_b, int rows, int H,
+                  int D, float eps, int dtype, rajni_stream_t stream);
+
+/* x = norm_pre(x)   (timm forward_features: `x = self.norm_pre(x)` after _pos_embed), IN PLACE on the residual stream
+ * x [rows, C]: fp32 when x_f32 != 0 (or dtype is RAJNI_F32), else `dtype`.  C % 8 == 0, C <= 2048. */
+int rajni_layernorm_stream(void* x, const float* w, const float* b, int rows, int C, float eps, int dtype, int x_f32,
+                           rajni_stream_t stream);
+
+/* out[b] = fc_norm(pool(norm(x[b])))   (timm forward_features' `x = self.norm(x)`, then .pool and forward_head's
+ * `x = self.fc_norm(x)`): x [B,N,C] is the residual stream (fp32 when x_f32 != 0, else `dtype`), out [B,C] `dtype` - the
+ * row the head GEMM reads.  pool = RAJNI_POOL_TOKEN: x[:, 0]; RAJNI_POOL_AVG: the mean of x[:, 1:], i.e. of the patch
+ * tokens that SURVIVED pruning (what timm computes on whatever token set reaches the head), summed in a fixed order
+ * in fp32.  norm_w == NULL / fc_w == NULL: that norm is nn.Identity.  C % 8 == 0, C <= 2048. */
+enum { RAJNI_POOL_TOKEN = 0, RAJNI_POOL_AVG = 1 };
+int rajni_pool_norm(const void* x, int B, int N, int C, int pool, const float* norm_w, const float* norm_b,
+                    float norm_eps, const float* fc_w, const float* fc_b, float fc_eps, void* out, int dtype, int x_f32,
+                    rajni_stream_t stream);
+
+/* The extension record of the whole forward: everything a plan cannot say, beside it (so the plan's layout and
+ * RAJNI_ABI_VERSION stay what they are).  An all-zero record is the plain forward. */
+typedef struct {
+  const float* q_norm_w; const float* q_norm_b;   /* [D], [D] or NULL */
+  const float* k_norm_w; const float* k_norm_b;
+} rajni_qk_affine;
+
+typedef struct {
+  const rajni_qk_affine* qk_norm;   /* host array [depth] (every block, pruned or not), or NULL: no q/k-norm */
+  float qk_eps;
+  const float* norm_pre_w; const float* norm_pre_b; float norm_pre_eps;   /* norm_pre_w == NULL: no norm_pre */
+  int norm_absent;                  /* 1: base_model.norm is nn.Identity (plan.norm_w / norm_b are not read) */
+  int pool;                         /* RAJNI_POOL_TOKEN (0) or RAJNI_POOL_AVG; AVG with plan.cls_only_last_block is
+                                       RAJNI_ERR_INVALID: that opt-in never forms the rows to be averaged */
+  const float* fc_norm_w; const float* fc_norm_b; float fc_norm_eps;      /* fc_norm_w == NULL: no fc_norm */
+} rajni_vit_ext;
+
+/* rajni_vit_forward with the options of `ext` (NULL or all zero: exactly the launches of rajni_vit_forward).
+ * norm_pre runs after patch embed + CLS + pos-embed, q/k-norm after every block's QKV GEMM, and the tail is
+ * norm -> pool -> fc_norm -> head.  No workspace beyond rajni_vit_workspace_bytes(). */
+int rajni_vit_forward_ext(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const void* images, void* logits,
+                          rajni_stream_t stream);
+
 /* ---- measurement hooks (bench.py roofline): HIP-event timing per kernel class on the launch
  * stream.  mask bit i enables class i; classes listed by rajni_profile_class_name(). ---- */
 enum { RAJNI_NUM_KCLASS = 17 };

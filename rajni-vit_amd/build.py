@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "rajni_amd", "lib")
 OUT = os.path.join(OUT_DIR, "librajni_hip.so")
-SOURCES = ["capi.hip", "gemm.hip", "rowops.hip", "score_select.hip", "attention.hip", "forward.hip"]
+SOURCES = ["capi.hip", "gemm.hip", "rowops.hip", "score_select.hip", "attention.hip", "variants.hip", "forward.hip"]
 
 
 def needs_build():

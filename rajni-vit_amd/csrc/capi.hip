@@ -159,6 +159,25 @@ int rajni_layernorm_fp8(const void* x, long x_row_stride, const float* w, const 
                               x_f32, (hipStream_t)stream);
 }
 
+int rajni_qk_norm(void* qkv, const float* q_w, const float* q_b, const float* k_w, const float* k_b, int rows, int H,
+                  int D, float eps, int dtype, rajni_stream_t stream) {
+  NEED_DTYPE("rajni_qk_norm");
+  return launch_qk_norm(qkv, q_w, q_b, k_w, k_b, rows, H, D, eps, dtype, (hipStream_t)stream);
+}
+
+int rajni_layernorm_stream(void* x, const float* w, const float* b, int rows, int C, float eps, int dtype, int x_f32,
+                           rajni_stream_t stream) {
+  NEED_DTYPE("rajni_layernorm_stream");
+  return launch_layernorm_stream(x, w, b, rows, C, eps, x_f32, dtype, (hipStream_t)stream);
+}
+
+int rajni_pool_norm(const void* x, int B, int N, int C, int pool, const float* norm_w, const float* norm_b,
+                    float norm_eps, const float* fc_w, const float* fc_b, float fc_eps, void* out, int dtype, int x_f32,
+                    rajni_stream_t stream) {
+  NEED_DTYPE("rajni_pool_norm");
+  return launch_pool_norm(x, B, N, C, pool, norm_w, norm_b, norm_eps, fc_w, fc_b, fc_eps, out, x_f32, dtype, (hipStream_t)stream);
+}
+
 int rajni_linear(const rajni_linear_args* args, rajni_stream_t stream) {
   RAJNI_REQUIRE(args != nullptr, RAJNI_ERR_INVALID, "rajni_linear: null args");
   return launch_linear(*args, (hipStream_t)stream);

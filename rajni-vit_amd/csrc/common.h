@@ -209,3 +209,9 @@ int launch_score_select(const void* qkv, const void* scores_in, int B, int N, in
                         void* next_scores, int dtype, hipStream_t s);
 int launch_gather_rows(const void* src, const int32_t* idx, void* dst, int B, int n_src, int n_dst,
                        int row_bytes, hipStream_t s);
+// variants.hip: the timm options of rajni_vit_ext (b pointers may be NULL = no bias; nw / fw NULL = that norm is absent)
+int launch_qk_norm(void* qkv, const float* qw, const float* qb, const float* kw, const float* kb, int rows, int H, int D,
+                   float eps, int dtype, hipStream_t s);
+int launch_layernorm_stream(void* x, const float* w, const float* b, int rows, int C, float eps, int x_f32, int dtype, hipStream_t s);
+int launch_pool_norm(const void* x, int B, int N, int C, int pool, const float* nw, const float* nb, float neps,
+                     const float* fw, const float* fb, float feps, void* out, int x_f32, int dtype, hipStream_t s);

@@ -51,7 +51,7 @@ __global__ void carry_scores_kernel(const T* scores, const int* idx, T* out, int
   out[i] = scores[(long)b * N + idx[i]];
 }
 
-int check_plan(const rajni_vit_plan& p) {
+int check_plan(const rajni_vit_plan& p, bool norm_absent) {
   RAJNI_REQUIRE(p.dtype == RAJNI_BF16 || p.dtype == RAJNI_F32 || p.dtype == RAJNI_F16, RAJNI_ERR_INVALID,
                 "rajni_vit_forward: bad dtype %d", p.dtype);
   RAJNI_REQUIRE(p.B > 0 && p.depth > 0 && p.blocks != nullptr, RAJNI_ERR_INVALID, "rajni_vit_forward: bad plan");
@@ -59,7 +59,7 @@ int check_plan(const rajni_vit_plan& p) {
                 "rajni_vit_forward: need C == H*D and a head dim that is a multiple of 8 up to 128 (C=%d H=%d D=%d)", p.C, p.H, p.D);
   RAJNI_REQUIRE(p.C % 64 == 0 && p.hidden % 64 == 0, RAJNI_ERR_UNSUPPORTED,
                 "rajni_vit_forward: C and hidden must be multiples of 64");
-  RAJNI_REQUIRE(p.patch_w && p.cls_token && p.pos_embed && p.norm_w && p.norm_b && p.head_w,
+  RAJNI_REQUIRE(p.patch_w && p.cls_token && p.pos_embed && p.head_w && (norm_absent || (p.norm_w && p.norm_b)),
                 RAJNI_ERR_INVALID, "rajni_vit_forward: null weight pointer");
   if (p.dtype == RAJNI_F16) {
     bool w8 = false;
@@ -79,6 +79,21 @@ int check_plan(const rajni_vit_plan& p) {
   return RAJNI_OK;
 }
 
+int check_ext(const rajni_vit_plan& p, const rajni_vit_ext& e) {
+  RAJNI_REQUIRE(e.pool == RAJNI_POOL_TOKEN || e.pool == RAJNI_POOL_AVG, RAJNI_ERR_UNSUPPORTED,
+                "rajni_vit_forward_ext: pool must be RAJNI_POOL_TOKEN or RAJNI_POOL_AVG (%d)", e.pool);
+  RAJNI_REQUIRE(!(e.pool == RAJNI_POOL_AVG && p.cls_only_last_block), RAJNI_ERR_INVALID,
+                "rajni_vit_forward_ext: 'avg' pooling with cls_only_last_block - that opt-in never forms the rows to be averaged");
+  if (e.qk_norm)
+    for (int i = 0; i < p.depth; ++i)
+      RAJNI_REQUIRE(e.qk_norm[i].q_norm_w && e.qk_norm[i].k_norm_w, RAJNI_ERR_INVALID,
+                    "rajni_vit_forward_ext: q/k-norm weights missing (block %d)", i);
+  return RAJNI_OK;
+}
+
+// the whole forward; ext == nullptr (rajni_vit_forward) and an all-zero record enqueue the same launches
+int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const void* images, void* logits, hipStream_t s);
+
 }  // namespace
 
 extern "C" size_t rajni_vit_workspace_bytes(const rajni_vit_plan* plan) {
@@ -90,11 +105,26 @@ extern "C" size_t rajni_vit_workspace_bytes(const rajni_vit_plan* plan) {
 
 extern "C" int rajni_vit_forward(const rajni_vit_plan* plan, const void* images, void* logits,
                                  rajni_stream_t stream) {
+  return vit_forward(plan, nullptr, images, logits, (hipStream_t)stream);
+}
+
+extern "C" int rajni_vit_forward_ext(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const void* images, void* logits,
+                                     rajni_stream_t stream) {
+  return vit_forward(plan, ext, images, logits, (hipStream_t)stream);
+}
+
+namespace {
+
+int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const void* images, void* logits, hipStream_t s) {
   RAJNI_REQUIRE(plan && images && logits, RAJNI_ERR_INVALID, "rajni_vit_forward: null pointer");
   const rajni_vit_plan& p = *plan;
-  int rc = check_plan(p);
+  int rc = check_plan(p, ext != nullptr && ext->norm_absent != 0);
   if (rc != RAJNI_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
+  if (ext) {
+    rc = check_ext(p, *ext);
+    if (rc != RAJNI_OK) return rc;
+  }
+  const rajni_qk_affine* qkn = ext ? ext->qk_norm : nullptr;
   const Workspace w = carve(p);
   RAJNI_REQUIRE(p.workspace != nullptr && p.workspace_bytes >= w.total, RAJNI_ERR_INVALID,
                 "rajni_vit_forward: workspace too small (%zu < %zu)", p.workspace_bytes, w.total);
@@ -107,6 +137,10 @@ extern "C" int rajni_vit_forward(const rajni_vit_plan* plan, const void* images,
   rc = launch_patch_embed(images, p.patch_w, p.patch_b, p.cls_token, p.pos_embed, p.pos_has_cls,
                           w.xa, sf32, B, p.in_chans, p.img_size, p.patch_size, C, dt, w.cols, w.cols_bytes, s);
   if (rc != RAJNI_OK) return rc;
+  if (ext && ext->norm_pre_w) {   // timm forward_features: x = norm_pre(x), written back into the stream
+    rc = launch_layernorm_stream(w.xa, ext->norm_pre_w, ext->norm_pre_b, B * N, C, ext->norm_pre_eps, sf32, dt, s);
+    if (rc != RAJNI_OK) return rc;
+  }
 
   char* cur = w.xa;
   char* oth = w.xb;
@@ -127,6 +161,10 @@ extern "C" int rajni_vit_forward(const rajni_vit_plan* plan, const void* images,
     g.y = w.qkv; g.ldc = 3 * C; g.M = M; g.N = 3 * C; g.K = C; g.epilogue = RAJNI_EPI_BIAS;
     rc = launch_linear(g, s);
     if (rc != RAJNI_OK) return rc;
+    if (qkn) {   // timm Attention.forward: q, k = q_norm(q), k_norm(k) - in place, so everything below reads normalised q and k
+      rc = launch_qk_norm(w.qkv, qkn[i].q_norm_w, qkn[i].q_norm_b, qkn[i].k_norm_w, qkn[i].k_norm_b, M, p.H, p.D, ext->qk_eps, dt, s);
+      if (rc != RAJNI_OK) return rc;
+    }
 
     if (p.cls_only_last_block && i == p.depth - 1 && blk.keep == 0 && N > 1) {
       // ---- last block, not a pruning stage, caller opted in: only x[:, 0] reaches the head (model.py:65-66),
@@ -255,7 +293,12 @@ extern "C" int rajni_vit_forward(const rajni_vit_plan* plan, const void* images,
   }
 
   // ---- final norm on the CLS rows only (LN is per token; model.py:65-66) + head
-  rc = launch_layernorm(cur, (long)N * C, p.norm_w, p.norm_b, w.clsn, B, C, p.ln_eps, sf32, dt, s);
+  // (with a pooled head, fc_norm or no norm: norm on every row that is pooled -> pool -> fc_norm, one kernel)
+  if (ext && (ext->pool != RAJNI_POOL_TOKEN || ext->fc_norm_w || ext->norm_absent))
+    rc = launch_pool_norm(cur, B, N, C, ext->pool, ext->norm_absent ? nullptr : p.norm_w, p.norm_b, p.ln_eps,
+                          ext->fc_norm_w, ext->fc_norm_b, ext->fc_norm_eps, w.clsn, sf32, dt, s);
+  else
+    rc = launch_layernorm(cur, (long)N * C, p.norm_w, p.norm_b, w.clsn, B, C, p.ln_eps, sf32, dt, s);
   if (rc != RAJNI_OK) return rc;
   rajni_linear_args g{};
   g.dtype = dt;
@@ -266,3 +309,5 @@ extern "C" int rajni_vit_forward(const rajni_vit_plan* plan, const void* images,
   g.y = logits; g.ldc = ld; g.M = B; g.N = p.num_classes; g.K = C; g.epilogue = RAJNI_EPI_BIAS;
   return launch_linear(g, s);
 }
+
+}  // namespace

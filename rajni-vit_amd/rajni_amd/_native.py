@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("RAJNI_HIP_LIB") or os.path.join(_HERE, "lib", "libraj
 RAJNI_F32, RAJNI_BF16, RAJNI_F16 = 0, 1, 2
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID = 0, 1, 2
 NUM_KCLASS = 17
+POOL_TOKEN, POOL_AVG = 0, 1
 
 c_void_p, c_int, c_long, c_float, c_size_t = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
 
@@ -61,6 +62,18 @@ class VitPlan(C.Structure):
                 ("resid_bf16", c_int), ("act_fp8", c_int)]
 
 
+class QkAffine(C.Structure):
+    _fields_ = [("q_norm_w", c_void_p), ("q_norm_b", c_void_p), ("k_norm_w", c_void_p), ("k_norm_b", c_void_p)]
+
+
+class VitExt(C.Structure):
+    """rajni_vit_ext: the timm options beside the plan (q/k-norm, norm_pre, pooled head, fc_norm); all zero = none"""
+    _fields_ = [("qk_norm", C.POINTER(QkAffine)), ("qk_eps", c_float),
+                ("norm_pre_w", c_void_p), ("norm_pre_b", c_void_p), ("norm_pre_eps", c_float),
+                ("norm_absent", c_int), ("pool", c_int),
+                ("fc_norm_w", c_void_p), ("fc_norm_b", c_void_p), ("fc_norm_eps", c_float)]
+
+
 _SIGS = {
     "rajni_abi_version": (c_int, []),
     "rajni_last_error": (C.c_char_p, []),
@@ -79,6 +92,10 @@ _SIGS = {
     "rajni_layernorm_fp8": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                     c_int, c_int, c_float, c_int, c_void_p]),
     "rajni_linear": (c_int, [C.POINTER(LinearArgs), c_void_p]),
+    "rajni_qk_norm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "rajni_layernorm_stream": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_int, c_void_p]),
+    "rajni_pool_norm": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_float,
+                                c_void_p, c_int, c_int, c_void_p]),
     "rajni_debug_force_gemm_tiling": (None, [c_int]),
     "rajni_debug_force_f8_tiling": (None, [c_int]),
     "rajni_debug_set_resid_stagger": (None, [c_int]),
@@ -91,6 +108,7 @@ _SIGS = {
                                   c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "rajni_vit_workspace_bytes": (c_size_t, [C.POINTER(VitPlan)]),
     "rajni_vit_forward": (c_int, [C.POINTER(VitPlan), c_void_p, c_void_p, c_void_p]),
+    "rajni_vit_forward_ext": (c_int, [C.POINTER(VitPlan), C.POINTER(VitExt), c_void_p, c_void_p, c_void_p]),
     "rajni_profile_enable": (None, [C.c_uint]),
     "rajni_profile_class_name": (C.c_char_p, [c_int]),
     "rajni_profile_collect": (c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.POINTER(C.c_double),

@@ -231,6 +231,63 @@ def layernorm_fp8(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float,
     return (q, scale) if hs is None else (q, scale, hs)
 
 
+def qk_norm(qkv: torch.Tensor, num_heads: int, q_w: torch.Tensor, q_b: Optional[torch.Tensor], k_w: torch.Tensor,
+            k_b: Optional[torch.Tensor], eps: float) -> torch.Tensor:
+    """timm's `q, k = q_norm(q), k_norm(k)`: LayerNorm over the head dim of the q and k thirds of qkv [..., 3C], IN PLACE
+    (v is not touched); q_w / k_w fp32 [D], biases fp32 [D] or None.  Returns qkv."""
+    nat.require_device(qkv, "qkv")
+    if not qkv.is_contiguous():
+        raise ValueError("qk_norm works in place: qkv must be contiguous")
+    threeC = qkv.shape[-1]
+    rows = qkv.numel() // threeC
+    D = threeC // 3 // num_heads
+    for v in (q_w, q_b, k_w, k_b):
+        if v is not None and (v.dtype != torch.float32 or v.numel() != D or not v.is_contiguous()):
+            raise ValueError(f"qk_norm: weights and biases must be contiguous fp32 [{D}]")
+    with nat.device_guard(qkv.device):
+        nat.check(nat.lib().rajni_qk_norm(qkv.data_ptr(), q_w.data_ptr(), nat.ptr(q_b), k_w.data_ptr(), nat.ptr(k_b), rows,
+                                          num_heads, D, float(eps), _dt(qkv), nat.stream_ptr(qkv.device)), "rajni_qk_norm")
+    return qkv
+
+
+def layernorm_stream(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], eps: float,
+                     model_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """timm's `x = norm_pre(x)`: LayerNorm over the last axis written back IN PLACE into the residual stream x (fp32, or the
+    model's 16-bit type).  `model_dtype` is the model's dtype when x is its fp32 stream (default: x's own).  Returns x."""
+    nat.require_device(x, "x")
+    if not x.is_contiguous():
+        raise ValueError("layernorm_stream works in place: x must be contiguous")
+    Cc = x.shape[-1]
+    dt = nat.dtype_code(model_dtype if model_dtype is not None else x.dtype)
+    x_f32 = int(x.dtype == torch.float32 and dt != nat.RAJNI_F32)
+    if not x_f32 and nat.dtype_code(x.dtype) != dt:
+        raise ValueError("layernorm_stream: x must be fp32 or the model dtype")
+    with nat.device_guard(x.device):
+        nat.check(nat.lib().rajni_layernorm_stream(x.data_ptr(), w.data_ptr(), nat.ptr(b), x.numel() // Cc, Cc, float(eps), dt,
+                                                   x_f32, nat.stream_ptr(x.device)), "rajni_layernorm_stream")
+    return x
+
+
+def pool_norm(x: torch.Tensor, pool: str = "token", norm=None, fc_norm=None, out_dtype=torch.bfloat16) -> torch.Tensor:
+    """timm's head input: fc_norm(pool(norm(x))) for x [B, N, C] (`out_dtype`, or fp32 = the fp32 residual stream) -> [B, C]
+    in `out_dtype`.  pool: "token" (x[:, 0]) or "avg" (mean of x[:, 1:]); norm / fc_norm: (w, b or None, eps) or None."""
+    nat.require_device(x, "x")
+    if pool not in ("token", "avg"):
+        raise NotImplementedError(f"pool_norm: pool '{pool}' is not supported ('token' or 'avg')")
+    x = x.contiguous()
+    B, N, Cc = x.shape
+    x_f32 = int(x.dtype == torch.float32 and out_dtype != torch.float32)
+    nw, nb, ne = norm if norm is not None else (None, None, 0.0)
+    fw, fb, fe = fc_norm if fc_norm is not None else (None, None, 0.0)
+    out = torch.empty((B, Cc), dtype=out_dtype, device=x.device)
+    with nat.device_guard(x.device):
+        nat.check(nat.lib().rajni_pool_norm(x.data_ptr(), B, N, Cc, nat.POOL_AVG if pool == "avg" else nat.POOL_TOKEN,
+                                            nat.ptr(nw), nat.ptr(nb), float(ne), nat.ptr(fw), nat.ptr(fb), float(fe),
+                                            out.data_ptr(), nat.dtype_code(out_dtype), x_f32, nat.stream_ptr(x.device)),
+                  "rajni_pool_norm")
+    return out
+
+
 def linear(x: torch.Tensor, w_packed: torch.Tensor, n_out: int, bias: Optional[torch.Tensor] = None,
            epilogue: int = nat.EPI_BIAS, gamma: Optional[torch.Tensor] = None,
            resid: Optional[torch.Tensor] = None, r_idx: Optional[torch.Tensor] = None,

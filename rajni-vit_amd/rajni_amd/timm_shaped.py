@@ -44,6 +44,16 @@ class ViTConfig:
     layer_scale: Optional[float] = None   # DeiT-3 style LayerScale init value
     no_embed_class: bool = False          # DeiT-3: pos_embed has no CLS row
     ln_eps: float = 1e-6
+    # timm VisionTransformer options (defaults = none of them: the modules and the synthetic weight stream of every
+    # config above this line are unchanged)
+    qk_norm: bool = False                 # LayerNorm(head_dim) on q and k in every block
+    pre_norm: bool = False                # norm_pre after the pos-embed (CLIP-derived ViTs)
+    global_pool: str = "token"            # 'token' (x[:, 0]) or 'avg' (mean of x[:, 1:])
+    fc_norm: Optional[bool] = None        # None = timm's default: an fc_norm (and no final norm) iff global_pool == 'avg'
+
+    @property
+    def use_fc_norm(self) -> bool:
+        return self.global_pool == "avg" if self.fc_norm is None else bool(self.fc_norm)
 
     @property
     def num_patches(self) -> int:
@@ -86,6 +96,23 @@ CONFIGS: Dict[str, ViTConfig] = {
     # the same with head dim 80 (ViT-H's), for the general-head-dim kernels (not a timm name)
     "vit_micro_d80_patch16_64": ViTConfig(img_size=64, embed_dim=320, depth=4, num_heads=4,
                                           num_classes=10),
+    # ---- timm options beyond plain ViT / DeiT ----
+    # CLIP-derived ViT-B/16 (timm `vit_base_patch16_clip_224`: pre_norm, LayerNorm eps 1e-5, exact GELU, token head; the
+    # `_quickgelu_` variants are a different activation and stay refused)
+    "vit_base_patch16_clip_224": ViTConfig(embed_dim=768, depth=12, num_heads=12, pre_norm=True, ln_eps=1e-5),
+    # ViT-B/16 with q/k LayerNorm (timm `vit_base_patch16_224(qk_norm=True)`; not a checkpoint name)
+    "vit_base_patch16_qknorm_224": ViTConfig(embed_dim=768, depth=12, num_heads=12, qk_norm=True),
+    # micro models, one option each and all together (not timm names)
+    "vit_micro_qknorm_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, num_classes=10, qk_norm=True),
+    "vit_micro_prenorm_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, num_classes=10, pre_norm=True),
+    "vit_micro_gap_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, num_classes=10, global_pool="avg"),
+    "vit_micro_fcnorm_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, num_classes=10, fc_norm=True),
+    "vit_micro_all_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, num_classes=10, qk_norm=True,
+                                          pre_norm=True, global_pool="avg"),
+    # q/k-norm on the fp8-capable micro model, and on head dim 80 (a 10-lane group of the general q/k-norm form)
+    "vit_micro512_qknorm_patch16_64": ViTConfig(img_size=64, embed_dim=512, depth=4, num_heads=8, num_classes=10, qk_norm=True),
+    "vit_micro_d80_qknorm_patch16_64": ViTConfig(img_size=64, embed_dim=320, depth=4, num_heads=4, num_classes=10,
+                                                 qk_norm=True, global_pool="avg"),
 }
 
 
@@ -103,14 +130,14 @@ class PatchEmbed(nn.Module):
 
 
 class Attention(nn.Module):
-    def __init__(self, dim: int, num_heads: int):
+    def __init__(self, dim: int, num_heads: int, qk_norm: bool = False, ln_eps: float = 1e-6):
         super().__init__()
         self.num_heads = num_heads
         self.head_dim = dim // num_heads
         self.scale = self.head_dim ** -0.5
         self.qkv = nn.Linear(dim, dim * 3, bias=True)
-        self.q_norm = nn.Identity()
-        self.k_norm = nn.Identity()
+        self.q_norm = nn.LayerNorm(self.head_dim, eps=ln_eps) if qk_norm else nn.Identity()
+        self.k_norm = nn.LayerNorm(self.head_dim, eps=ln_eps) if qk_norm else nn.Identity()
         self.attn_drop = nn.Dropout(0.0)
         self.proj = nn.Linear(dim, dim)
         self.proj_drop = nn.Dropout(0.0)
@@ -119,6 +146,7 @@ class Attention(nn.Module):
         B, N, C = x.shape
         qkv = self.qkv(x).reshape(B, N, 3, self.num_heads, self.head_dim).permute(2, 0, 3, 1, 4)
         q, k, v = qkv.unbind(0)
+        q, k = self.q_norm(q), self.k_norm(k)
         x = F.scaled_dot_product_attention(q, k, v)
         return self.proj_drop(self.proj(x.transpose(1, 2).reshape(B, N, C)))
 
@@ -151,7 +179,7 @@ class Block(nn.Module):
         super().__init__()
         C = cfg.embed_dim
         self.norm1 = nn.LayerNorm(C, eps=cfg.ln_eps)
-        self.attn = Attention(C, cfg.num_heads)
+        self.attn = Attention(C, cfg.num_heads, cfg.qk_norm, cfg.ln_eps)
         self.ls1 = LayerScale(C, cfg.layer_scale) if cfg.layer_scale else nn.Identity()
         self.drop_path1 = nn.Identity()
         self.norm2 = nn.LayerNorm(C, eps=cfg.ln_eps)
@@ -180,9 +208,14 @@ class VisionTransformer(nn.Module):
         n_pos = cfg.num_patches if cfg.no_embed_class else cfg.num_patches + 1
         self.pos_embed = nn.Parameter(torch.zeros(1, n_pos, cfg.embed_dim))
         self.pos_drop = nn.Dropout(0.0)
+        if cfg.global_pool not in ("token", "avg"):
+            raise ValueError(f"global_pool must be 'token' or 'avg', got {cfg.global_pool!r}")
+        self.global_pool = cfg.global_pool
+        self.norm_pre = nn.LayerNorm(cfg.embed_dim, eps=cfg.ln_eps) if cfg.pre_norm else nn.Identity()
         self.blocks = nn.Sequential(*[Block(cfg) for _ in range(cfg.depth)])
-        self.norm = nn.LayerNorm(cfg.embed_dim, eps=cfg.ln_eps)
-        self.fc_norm = nn.Identity()
+        # timm: the final norm moves behind the pooling (fc_norm) when fc_norm is in use
+        self.norm = nn.Identity() if cfg.use_fc_norm else nn.LayerNorm(cfg.embed_dim, eps=cfg.ln_eps)
+        self.fc_norm = nn.LayerNorm(cfg.embed_dim, eps=cfg.ln_eps) if cfg.use_fc_norm else nn.Identity()
         self.head_drop = nn.Dropout(0.0)
         self.head = nn.Linear(cfg.embed_dim, cfg.num_classes)
 
@@ -196,12 +229,14 @@ class VisionTransformer(nn.Module):
 
     def forward_features(self, x):
         x = self._pos_embed(self.patch_embed(x))
+        x = self.norm_pre(x)
         x = self.blocks(x)
         return self.norm(x)
 
     def forward(self, x):
         x = self.forward_features(x)
-        return self.head(self.head_drop(self.fc_norm(x[:, 0])))
+        x = x[:, self.num_prefix_tokens:].mean(dim=1) if self.global_pool == "avg" else x[:, 0]
+        return self.head(self.head_drop(self.fc_norm(x)))
 
 
 # ----------------------------------------------------------------------------------------------
@@ -248,10 +283,25 @@ def synth_state_dict(cfg: ViTConfig, seed: int = 0, std: float = 0.02,
             # so the LayerScale multiply is observable in parity tests.
             sd[p + "ls1.gamma"] = (np.float32(cfg.layer_scale) + np.abs(nrm(C, s=0.5))).astype(np.float32)
             sd[p + "ls2.gamma"] = (np.float32(cfg.layer_scale) + np.abs(nrm(C, s=0.5))).astype(np.float32)
-    sd["norm.weight"] = (1.0 + nrm(C, s=bias_std)).astype(np.float32)
-    sd["norm.bias"] = nrm(C, s=bias_std) if bias_std else np.zeros(C, np.float32)
+    if not cfg.use_fc_norm:
+        sd["norm.weight"] = (1.0 + nrm(C, s=bias_std)).astype(np.float32)
+        sd["norm.bias"] = nrm(C, s=bias_std) if bias_std else np.zeros(C, np.float32)
     sd["head.weight"] = nrm(cfg.num_classes, C)
     sd["head.bias"] = nrm(cfg.num_classes, s=bias_std) if bias_std else np.zeros(cfg.num_classes, np.float32)
+
+    # the timm options' tensors are drawn AFTER everything above, so a config without them keeps its stream
+    def ln(prefix, n):
+        sd[prefix + ".weight"] = (1.0 + nrm(n, s=bias_std)).astype(np.float32)
+        sd[prefix + ".bias"] = nrm(n, s=bias_std) if bias_std else np.zeros(n, np.float32)
+
+    if cfg.pre_norm:
+        ln("norm_pre", C)
+    if cfg.qk_norm:
+        for i in range(cfg.depth):
+            ln(f"blocks.{i}.attn.q_norm", cfg.head_dim)
+            ln(f"blocks.{i}.attn.k_norm", cfg.head_dim)
+    if cfg.use_fc_norm:
+        ln("fc_norm", C)
     return sd
 
 

@@ -18,6 +18,27 @@ from .. import _native as nat
 from .. import ops
 
 
+def qk_norm_modules(attn: nn.Module, where: str = "RAJNIAttention"):
+    """(q_norm, k_norm) of a timm Attention when it normalises q and k (timm `qk_norm=True`: two affine nn.LayerNorm over
+    the head dim with one eps), None when it does not (no attribute, None or nn.Identity).  Anything else - RMSNorm, a
+    non-affine norm, one of the two missing, differing eps - is refused: the reference silently drops it."""
+    mods = [getattr(attn, name, None) for name in ("q_norm", "k_norm")]
+    plain = [m is None or isinstance(m, nn.Identity) for m in mods]
+    if all(plain):
+        return None
+    for name, mod, off in zip(("q_norm", "k_norm"), mods, plain):
+        if off or not isinstance(mod, nn.LayerNorm) or mod.weight is None:
+            raise NotImplementedError(
+                f"{where}: attn.{name} is {type(mod).__name__}; only an affine nn.LayerNorm on both q and k is supported "
+                "(the reference silently drops it, SURVEY Q5) - refusing instead of computing something different")
+    q, k = mods
+    if tuple(q.normalized_shape) != tuple(k.normalized_shape) or len(q.normalized_shape) != 1:
+        raise NotImplementedError(f"{where}: attn.q_norm / attn.k_norm must normalise the head dim alone")
+    if float(q.eps) != float(k.eps):
+        raise NotImplementedError(f"{where}: attn.q_norm and attn.k_norm have different eps ({q.eps} / {k.eps})")
+    return q, k
+
+
 class RAJNIAttention(nn.Module):
     def __init__(self, attn: nn.Module, keep_ratio: float, update: bool):
         super().__init__()
@@ -27,12 +48,11 @@ class RAJNIAttention(nn.Module):
         self.qkv = attn.qkv
         self.proj = attn.proj
         self.proj_drop = attn.proj_drop
-        for extra in ("q_norm", "k_norm"):
-            mod = getattr(attn, extra, None)
-            if mod is not None and not isinstance(mod, nn.Identity):
-                raise NotImplementedError(
-                    f"RAJNIAttention: attn.{extra} is {type(mod).__name__}; the reference silently drops "
-                    "it (SURVEY Q5) - refusing instead of computing something different")
+        # timm qk_norm=True: LayerNorm over the head dim of q and k (ops.qk_norm); the modules stay attributes, so the
+        # parameter set and the state-dict names are the timm Attention's
+        qk = qk_norm_modules(attn)
+        self.q_norm = qk[0] if qk else getattr(attn, "q_norm", None) or nn.Identity()
+        self.k_norm = qk[1] if qk else getattr(attn, "k_norm", None) or nn.Identity()
         self.keep_ratio = keep_ratio
         self.update = update
         self._packed = None
@@ -41,6 +61,9 @@ class RAJNIAttention(nn.Module):
     # ---- weights in the layout the kernels want (rebuilt when parameters change) -------------
     def _weights(self, device, dtype):
         params = [self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias]
+        qk = qk_norm_modules(self)
+        if qk:
+            params += [qk[0].weight, qk[0].bias, qk[1].weight, qk[1].bias]
         key = (str(device), dtype) + tuple((p.data_ptr(), p._version) for p in params if p is not None)
         if self._packed_key != key:
             self._packed = dict(
@@ -48,6 +71,10 @@ class RAJNIAttention(nn.Module):
                 qkv_b=ops.pack_vec(self.qkv.bias, dtype, device),
                 proj_w=ops.pack_weight(self.proj.weight, dtype, device),
                 proj_b=ops.pack_vec(self.proj.bias, dtype, device))
+            if qk:
+                self._packed.update(qk_eps=float(qk[0].eps),
+                                    q_w=ops.pack_vec(qk[0].weight, dtype, device), q_b=ops.pack_vec(qk[0].bias, dtype, device),
+                                    k_w=ops.pack_vec(qk[1].weight, dtype, device), k_b=ops.pack_vec(qk[1].bias, dtype, device))
             self._packed_key = key
         return self._packed
 
@@ -59,6 +86,8 @@ class RAJNIAttention(nn.Module):
         B, N, Cc = x.shape
         w = self._weights(x.device, x.dtype)
         qkv = ops.linear(x, w["qkv_w"], 3 * Cc, w["qkv_b"], nat.EPI_BIAS)            # attention.py:21-22
+        if "q_w" in w:                                                                # timm: q, k = q_norm(q), k_norm(k)
+            ops.qk_norm(qkv, self.num_heads, w["q_w"], w["q_b"], w["k_w"], w["k_b"], w["qk_eps"])
         keep = ops.keep_count(self.keep_ratio, N)                                     # attention.py:31-32
         if self.update or prev_scores is None:                                        # attention.py:25-28
             _, keep_idx, next_scores = ops.score_select(qkv, self.num_heads, keep, want_scores=False)

@@ -5,7 +5,8 @@ Kept from the reference: constructor signature, in-place surgery on the base mod
 blocks get a `RAJNIAttention`, every block gets `has_pruner`; model.py:12-23), parameter sharing,
 `forward(images) -> logits`, `get_last_stats() -> {"token_counts": [...]}` (None before the first
 forward).  Deliberate fixes: schedule keys are normalised to int (B1: a JSON-loaded
-schedule prunes), and a `no_embed_class` pos-embed works (B3).
+schedule prunes), a `no_embed_class` pos-embed works (B3), and timm's `qk_norm`, `pre_norm`, `global_pool='avg'`
+and `fc_norm` options are computed as timm computes them instead of being dropped (B4).
 
 Not kept: the Python per-block loop.  `forward` builds (once per batch shape) a `rajni_vit_plan`
 - packed weights, workspace, per-stage index buffers - and calls `rajni_vit_forward`, which enqueues
@@ -21,7 +22,7 @@ import torch.nn as nn
 
 from .. import _native as nat
 from .. import ops
-from .attention import RAJNIAttention
+from .attention import RAJNIAttention, qk_norm_modules
 
 
 def normalise_schedule(schedule) -> Dict[int, Dict]:
@@ -158,6 +159,9 @@ class RAJNIViTWrapper(nn.Module):
         tokens, proj / MLP on B rows.  The logits are the same function of the input (the reference's head reads
         x[:, 0] only); the other rows of the last block are never formed.  Off by default: the default forward
         executes the reference's op graph row for row."""
+        if on and self._pool_kind() == "avg":
+            raise ValueError("set_last_block_cls_only: the model pools with global_pool='avg'; the CLS-only last block never "
+                             "forms the rows to be averaged")
         if bool(on) != self._cls_only_last:
             self._cls_only_last = bool(on)
             self._drop_plans()
@@ -178,6 +182,18 @@ class RAJNIViTWrapper(nn.Module):
         return self
 
     # ------------------------------------------------------------------------------------------
+    def _pool_kind(self) -> str:
+        """'token' or 'avg': `base_model.global_pool` when the attribute exists, else 'token'."""
+        pool = getattr(self.m, "global_pool", "token")
+        if pool not in ("token", "avg"):
+            raise NotImplementedError(f"RAJNIViTWrapper: global_pool={pool!r} is not supported ('token' or 'avg')")
+        return pool
+
+    def check_supported(self) -> Dict:
+        """Raise NotImplementedError if the base model has a feature the native forward does not compute (host only, no
+        device needed; `forward` runs the same check).  Returns the model description."""
+        return self._describe()
+
     def _describe(self):
         m = self.m
         pe = m.patch_embed.proj
@@ -205,14 +221,40 @@ class RAJNIViTWrapper(nn.Module):
             mlp_norm = getattr(blk.mlp, "norm", None)
             if mlp_norm is not None and not isinstance(mlp_norm, nn.Identity):
                 raise NotImplementedError(f"block {i}: mlp.norm is not supported")
-            for extra in ("q_norm", "k_norm"):
-                mod = getattr(blk.attn, extra, None)
-                if mod is not None and not isinstance(mod, nn.Identity):
-                    raise NotImplementedError(f"block {i}: attn.{extra} is not supported (SURVEY Q5)")
+            qk = qk_norm_modules(blk.attn, f"block {i}")
+            if i == 0:
+                desc["qk_norm"] = qk is not None
+                desc["qk_eps"] = float(qk[0].eps) if qk else 0.0
+            if (qk is not None) != desc["qk_norm"] or (qk and float(qk[0].eps) != desc["qk_eps"]):
+                raise NotImplementedError(f"block {i}: attn.q_norm / attn.k_norm differ between blocks (presence or eps)")
+            if qk and tuple(qk[0].normalized_shape) != (desc["D"],):
+                raise NotImplementedError(f"block {i}: attn.q_norm must be nn.LayerNorm over the head dim {desc['D']}")
             if blk.attn.num_heads != heads or float(blk.attn.scale) != desc["scale"]:
                 raise NotImplementedError(f"block {i}: heads/scale differ between blocks")
-        if not isinstance(m.norm, nn.LayerNorm) or float(m.norm.eps) != desc["ln_eps"]:
+        # timm's head: norm -> pool -> fc_norm -> head, `norm` and `fc_norm` each an affine LayerNorm or Identity
+        desc["pool"] = self._pool_kind()
+        if getattr(m, "attn_pool", None) is not None:
+            raise NotImplementedError("RAJNIViTWrapper: attn_pool (global_pool='map') is not supported")
+        if getattr(m, "num_prefix_tokens", 1) != 1 or getattr(m, "reg_token", None) is not None:
+            raise NotImplementedError(f"RAJNIViTWrapper: {getattr(m, 'num_prefix_tokens', 1)} prefix tokens (register / distillation "
+                                      "tokens) are not supported: exactly one class token")
+        fc_norm = getattr(m, "fc_norm", None)
+        desc["fc_norm"] = fc_norm is not None and not isinstance(fc_norm, nn.Identity)
+        desc["norm"] = not isinstance(m.norm, nn.Identity)
+        if desc["norm"] and (not isinstance(m.norm, nn.LayerNorm) or m.norm.weight is None or float(m.norm.eps) != desc["ln_eps"]):
             raise NotImplementedError("RAJNIViTWrapper: base_model.norm must be nn.LayerNorm with the blocks' eps")
+        if not desc["norm"] and not desc["fc_norm"]:
+            raise NotImplementedError("RAJNIViTWrapper: base_model.norm must be nn.LayerNorm with the blocks' eps "
+                                      "(nn.Identity only together with an fc_norm)")
+        norm_pre = getattr(m, "norm_pre", None)
+        desc["norm_pre"] = norm_pre is not None and not isinstance(norm_pre, nn.Identity)
+        for name, mod, on in (("fc_norm", fc_norm, desc["fc_norm"]), ("norm_pre", norm_pre, desc["norm_pre"])):
+            if on and (not isinstance(mod, nn.LayerNorm) or mod.weight is None or tuple(mod.normalized_shape) != (Cdim,)):
+                raise NotImplementedError(f"RAJNIViTWrapper: base_model.{name} must be an affine nn.LayerNorm over the embed dim")
+        if desc["pool"] == "avg" and self._cls_only_last:
+            raise ValueError("global_pool='avg' with set_last_block_cls_only(True): that opt-in never forms the rows to be averaged")
+        # plans that need none of these keep calling rajni_vit_forward
+        desc["ext"] = desc["qk_norm"] or desc["norm_pre"] or desc["fc_norm"] or not desc["norm"] or desc["pool"] != "token"
         return desc
 
     def _all_params(self):
@@ -254,7 +296,7 @@ class RAJNIViTWrapper(nn.Module):
         # the sync -> forward -> sync metric); `_weights_key` is just the epoch of the last re-pack
         sig = [p.data_ptr() for p in params]
         sig += [p._version for p in params]
-        cfg_key = (device, dtype, self._weight_format)
+        cfg_key = (device, dtype, self._weight_format, getattr(self.m, "global_pool", "token"))
         if self._weights is not None and self._weights_sig == sig and self._weights_cfg == cfg_key:
             return self._weights
         key = (getattr(self, "_weights_epoch", 0) + 1)
@@ -274,7 +316,13 @@ class RAJNIViTWrapper(nn.Module):
         W["patch_b"] = pv(m.patch_embed.proj.bias) if m.patch_embed.proj.bias is not None else zeros(desc["C"])
         W["cls"] = m.cls_token.detach().to(device=device, dtype=dtype).reshape(-1).contiguous()
         W["pos"] = m.pos_embed.detach().to(device=device, dtype=dtype).reshape(-1, desc["C"]).contiguous()
-        W["norm_w"], W["norm_b"] = pv(m.norm.weight), pv(m.norm.bias)
+        W["norm_w"], W["norm_b"] = (pv(m.norm.weight), pv(m.norm.bias)) if desc["norm"] else (None, None)
+        if desc["norm"] and W["norm_b"] is None:
+            W["norm_b"] = zeros(desc["C"])
+        for name in ("norm_pre", "fc_norm"):      # rajni_vit_ext (a missing bias stays None = 0)
+            mod = getattr(m, name, None) if desc[name] else None
+            W[name + "_w"], W[name + "_b"] = (pv(mod.weight), pv(mod.bias)) if mod is not None else (None, None)
+            W[name + "_eps"] = float(mod.eps) if mod is not None else 0.0
         W["head_w"] = pw(m.head.weight)
         W["head_b"] = pv(m.head.bias) if m.head.bias is not None else zeros(desc["num_classes"])
         blocks = []
@@ -312,6 +360,9 @@ class RAJNIViTWrapper(nn.Module):
                 ls1=g1, norm2_w=pv(blk.norm2.weight), norm2_b=pv(blk.norm2.bias),
                 fc1_w=fc1_w, fc1_s=fc1_s, fc1_b=fc1_b,
                 fc2_w=fc2_w, fc2_s=fc2_s, fc2_b=pv(blk.mlp.fc2.bias), ls2=g2))
+            if desc["qk_norm"]:
+                q, k = qk_norm_modules(a)
+                blocks[-1].update(q_norm_w=pv(q.weight), q_norm_b=pv(q.bias), k_norm_w=pv(k.weight), k_norm_b=pv(k.bias))
             if self._weight_format == "fp8_mfma":
                 # constants of the hidden-activation bound (rajni_layernorm_fp8): largest row norm of the DEQUANTISED
                 # fc1 weight and largest |bias| as the kernels hold it
@@ -392,7 +443,7 @@ class RAJNIViTWrapper(nn.Module):
         plan.patch_w, plan.patch_b = W["patch_w"].data_ptr(), W["patch_b"].data_ptr()
         plan.cls_token, plan.pos_embed = W["cls"].data_ptr(), W["pos"].data_ptr()
         plan.blocks = blocks
-        plan.norm_w, plan.norm_b = W["norm_w"].data_ptr(), W["norm_b"].data_ptr()
+        plan.norm_w, plan.norm_b = nat.ptr(W["norm_w"]), nat.ptr(W["norm_b"])
         plan.head_w, plan.head_b = W["head_w"].data_ptr(), W["head_b"].data_ptr()
         tc = (C.c_int32 * d["depth"])()
         plan.token_counts = tc
@@ -403,7 +454,23 @@ class RAJNIViTWrapper(nn.Module):
         nbytes = nat.lib().rajni_vit_workspace_bytes(C.byref(plan))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
         plan.workspace, plan.workspace_bytes = ws.data_ptr(), nbytes
-        self._plan = (key, plan, (blocks, tc, ws, W), bufs, counts)   # W: a stale optimistic launch keeps its weights alive
+        ext = qk = None
+        if d["ext"]:        # the options beside the plan (rajni_vit_ext); None: the plain rajni_vit_forward
+            if d["pool"] == "avg" and self._cls_only_last:
+                raise ValueError("global_pool='avg' with set_last_block_cls_only(True): that opt-in never forms the rows to be averaged")
+            ext = nat.VitExt()
+            if d["qk_norm"]:
+                qk = (nat.QkAffine * d["depth"])()
+                for i, bw in enumerate(W["blocks"]):
+                    for name in ("q_norm_w", "q_norm_b", "k_norm_w", "k_norm_b"):
+                        setattr(qk[i], name, nat.ptr(bw[name]))
+                ext.qk_norm, ext.qk_eps = qk, d["qk_eps"]
+            ext.norm_pre_w, ext.norm_pre_b, ext.norm_pre_eps = nat.ptr(W["norm_pre_w"]), nat.ptr(W["norm_pre_b"]), W["norm_pre_eps"]
+            ext.fc_norm_w, ext.fc_norm_b, ext.fc_norm_eps = nat.ptr(W["fc_norm_w"]), nat.ptr(W["fc_norm_b"]), W["fc_norm_eps"]
+            ext.norm_absent = int(not d["norm"])
+            ext.pool = nat.POOL_AVG if d["pool"] == "avg" else nat.POOL_TOKEN
+        # W: a stale optimistic launch keeps its weights alive
+        self._plan = (key, plan, (blocks, tc, ws, W, ext, qk), bufs, counts)
         if len(self._plans) >= 4:     # workspaces are large: keep only a few batch shapes alive
             self._plans.pop(next(iter(self._plans)))
         self._plans[key] = self._plan
@@ -429,8 +496,13 @@ class RAJNIViTWrapper(nn.Module):
             def launch(entry):
                 plan = entry[1]
                 out = torch.empty((B, plan.logits_ld), dtype=dtype, device=x.device)
-                nat.check(nat.lib().rajni_vit_forward(C.byref(plan), x.data_ptr(), out.data_ptr(),
-                                                      nat.stream_ptr(x.device)), "rajni_vit_forward")
+                ext = entry[2][4]
+                if ext is None:
+                    nat.check(nat.lib().rajni_vit_forward(C.byref(plan), x.data_ptr(), out.data_ptr(),
+                                                          nat.stream_ptr(x.device)), "rajni_vit_forward")
+                else:
+                    nat.check(nat.lib().rajni_vit_forward_ext(C.byref(plan), C.byref(ext), x.data_ptr(), out.data_ptr(),
+                                                              nat.stream_ptr(x.device)), "rajni_vit_forward_ext")
                 return out
             # Optimistic launch: with a plan of this batch shape at hand the kernels are enqueued FIRST and the check
             # that the base model's weights are still the packed ones (a walk over ~150 parameters, ~0.1 ms of Python)
