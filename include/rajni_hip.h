@@ -16,8 +16,8 @@
  *     16-bit MFMA rate).
  *   - activations are row-major [B, N, C]; qkv is [B, N, 3*C] with the last axis laid out
  *     [3][H][D] (timm convention; importance.py:14, attention.py:46-47);
- *   - keep_idx is int32 on the device ([B, keep+1], slot 0 = CLS = 0, rest ascending); the Python
- *     surface widens to int64 to match attention.py:38.
+ *   - keep_idx is int32 on the device ([B, keep+1], slot 0 = CLS = 0, rest ascending; [B, P+keep] with P prefix
+ *     tokens, see the *_prefix entry points); the Python surface widens to int64 to match attention.py:38.
  */
 #ifndef RAJNI_HIP_H
 #define RAJNI_HIP_H
@@ -282,6 +282,50 @@ typedef struct {
  * norm -> pool -> fc_norm -> head.  No workspace beyond rajni_vit_workspace_bytes(). */
 int rajni_vit_forward_ext(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const void* images, void* logits,
                           rajni_stream_t stream);
+
+/* ---- prefix tokens beyond CLS: timm's register tokens (`reg_tokens=R`, e.g. vit_*_patch14_reg4_dinov2) ----
+ * The reference knows one prefix token (it concatenates cls_token only and slices [:, 1:]); the semantics here are timm's
+ * VisionTransformer._pos_embed and .pool.  With P = 1 + R prefix tokens and n patches the token order is
+ * [cls, reg_0 .. reg_{R-1}, patch_0 .. patch_{n-1}]; pos_embed has n rows (added to the patch rows only, `pos_has_cls` = 0)
+ * or P + n rows in token order (added to every row, `pos_has_cls` != 0).  Importance is unchanged (CLS is the query, the
+ * softmax and the V statistics run over all N tokens, registers included).  Only patch tokens are ranked:
+ * keep = max(1, int(keep_ratio * (N - P))), keep_idx is [B, P+keep] with slots 0..P-1 = 0..P-1 and the rest ascending
+ * patch indices >= P, next_scores = scores gathered at keep_idx (prefix slots included).  'avg' pooling is the mean of
+ * rows P..N-1.  Every *_prefix entry point with num_prefix = 1 issues the launches of its namesake and gives the same bits.
+ * 1 <= num_prefix <= RAJNI_MAX_PREFIX. */
+#define RAJNI_MAX_PREFIX 32
+
+/* The prefix record of the whole forward: travels beside the plan and the ext record (their layouts stay what they are). */
+typedef struct {
+  int num_prefix;          /* P = 1 + number of register tokens; 0 or 1: CLS only (reg_token is not read) */
+  const void* reg_token;   /* [num_prefix-1, C] in the plan's dtype, 16-byte aligned; required when num_prefix > 1.
+                              plan.pos_embed then has (plan.pos_has_cls ? num_prefix : 0) + n rows */
+} rajni_vit_prefix;
+
+/* rajni_select_topk / rajni_score_select over scores [B,N] whose first num_prefix tokens are always kept and take no rank
+ * slot: 1 <= keep <= N - num_prefix, keep_idx and next_scores are [B, num_prefix+keep]. */
+int rajni_select_topk_prefix(const void* scores, int B, int N, int num_prefix, int keep, int32_t* keep_idx,
+                             void* next_scores, int dtype, rajni_stream_t stream);
+int rajni_score_select_prefix(const void* qkv, int B, int N, int H, int D, float eps, int num_prefix, int keep,
+                              void* scores_out, int32_t* keep_idx, void* next_scores, int dtype,
+                              rajni_stream_t stream);
+/* rajni_patch_embed writing x [B, num_prefix+(S/P)^2, C]: row 0 = cls, rows 1..num_prefix-1 = reg [num_prefix-1, C]
+ * (`dtype`; may be NULL when num_prefix = 1), then the patches; pos [(pos_has_cls ? num_prefix : 0)+(S/P)^2, C].
+ * cls, reg and pos must be 16-byte aligned when num_prefix > 1. */
+int rajni_patch_embed_prefix(const void* images, const void* w, const float* bias, const void* cls, const void* reg,
+                             int num_prefix, const void* pos, int pos_has_cls, void* x, int x_f32, int B, int Cin, int S,
+                             int P, int C, int dtype, void* workspace, size_t workspace_bytes, rajni_stream_t stream);
+/* rajni_pool_norm whose RAJNI_POOL_AVG is the mean of x[:, num_prefix:] (same fixed fp32 summation order). */
+int rajni_pool_norm_prefix(const void* x, int B, int N, int num_prefix, int C, int pool, const float* norm_w,
+                           const float* norm_b, float norm_eps, const float* fc_w, const float* fc_b, float fc_eps,
+                           void* out, int dtype, int x_f32, rajni_stream_t stream);
+/* The whole forward with prefix tokens: the stream starts with num_prefix + n tokens, rajni_block.keep counts kept PATCH
+ * tokens (keep <= N - num_prefix), rajni_block.keep_idx / next_scores / forced_keep_idx are [B, num_prefix+keep],
+ * token_counts count every token.  The fp8_mfma attention limit of 224 rows counts the prefix rows.  prefix == NULL, or
+ * num_prefix <= 1 with no reg_token: exactly the launches of rajni_vit_forward_ext, the same bits.  ext may be NULL. */
+size_t rajni_vit_workspace_bytes_prefix(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix);
+int rajni_vit_forward_ext_prefix(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
+                                 const void* images, void* logits, rajni_stream_t stream);
 
 /* ---- measurement hooks (bench.py roofline): HIP-event timing per kernel class on the launch
  * stream.  mask bit i enables class i; classes listed by rajni_profile_class_name(). ---- */

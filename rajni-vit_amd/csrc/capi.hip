@@ -128,6 +128,35 @@ int rajni_score_select(const void* qkv, int B, int N, int H, int D, float eps, i
                              (hipStream_t)stream);
 }
 
+int rajni_select_topk_prefix(const void* scores, int B, int N, int num_prefix, int keep, int32_t* keep_idx,
+                             void* next_scores, int dtype, rajni_stream_t stream) {
+  NEED_DTYPE("rajni_select_topk_prefix");
+  RAJNI_REQUIRE(scores && keep_idx, RAJNI_ERR_INVALID, "rajni_select_topk_prefix: null pointer");
+  RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
+                "rajni_select_topk_prefix: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
+  RAJNI_REQUIRE(B > 0 && N >= num_prefix + 1, RAJNI_ERR_INVALID,
+                "rajni_select_topk_prefix: need B > 0 and at least one patch token (B=%d N=%d num_prefix=%d)", B, N, num_prefix);
+  RAJNI_REQUIRE(keep >= 1 && keep <= N - num_prefix, RAJNI_ERR_INVALID,
+                "rajni_select_topk_prefix: keep must be 1..%d (%d)", N - num_prefix, keep);
+  return launch_score_select(nullptr, scores, B, N, 0, 0, 0.f, keep, nullptr, keep_idx, next_scores, dtype,
+                             (hipStream_t)stream, num_prefix);
+}
+
+int rajni_score_select_prefix(const void* qkv, int B, int N, int H, int D, float eps, int num_prefix, int keep,
+                              void* scores_out, int32_t* keep_idx, void* next_scores, int dtype,
+                              rajni_stream_t stream) {
+  NEED_DTYPE("rajni_score_select_prefix");
+  RAJNI_REQUIRE(qkv && keep_idx, RAJNI_ERR_INVALID, "rajni_score_select_prefix: null pointer");
+  RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
+                "rajni_score_select_prefix: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
+  RAJNI_REQUIRE(B > 0 && N >= num_prefix + 1, RAJNI_ERR_INVALID,
+                "rajni_score_select_prefix: need B > 0 and at least one patch token (B=%d N=%d num_prefix=%d)", B, N, num_prefix);
+  RAJNI_REQUIRE(keep >= 1 && keep <= N - num_prefix, RAJNI_ERR_INVALID,
+                "rajni_score_select_prefix: keep must be 1..%d (%d)", N - num_prefix, keep);
+  return launch_score_select(qkv, nullptr, B, N, H, D, eps, keep, scores_out, keep_idx, next_scores, dtype,
+                             (hipStream_t)stream, num_prefix);
+}
+
 int rajni_gather_rows(const void* src, const int32_t* idx, void* dst, int B, int n_src, int n_dst,
                       int row_elems, int dtype, rajni_stream_t stream) {
   NEED_DTYPE("rajni_gather_rows");
@@ -178,6 +207,19 @@ int rajni_pool_norm(const void* x, int B, int N, int C, int pool, const float* n
   return launch_pool_norm(x, B, N, C, pool, norm_w, norm_b, norm_eps, fc_w, fc_b, fc_eps, out, x_f32, dtype, (hipStream_t)stream);
 }
 
+int rajni_pool_norm_prefix(const void* x, int B, int N, int num_prefix, int C, int pool, const float* norm_w,
+                           const float* norm_b, float norm_eps, const float* fc_w, const float* fc_b, float fc_eps,
+                           void* out, int dtype, int x_f32, rajni_stream_t stream) {
+  NEED_DTYPE("rajni_pool_norm_prefix");
+  RAJNI_REQUIRE(x && out, RAJNI_ERR_INVALID, "rajni_pool_norm_prefix: null pointer");
+  RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
+                "rajni_pool_norm_prefix: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
+  RAJNI_REQUIRE(pool != RAJNI_POOL_AVG || N >= num_prefix + 1, RAJNI_ERR_INVALID,
+                "rajni_pool_norm_prefix: 'avg' needs at least one patch token (N=%d num_prefix=%d)", N, num_prefix);
+  return launch_pool_norm(x, B, N, C, pool, norm_w, norm_b, norm_eps, fc_w, fc_b, fc_eps, out, x_f32, dtype,
+                          (hipStream_t)stream, num_prefix);
+}
+
 int rajni_linear(const rajni_linear_args* args, rajni_stream_t stream) {
   RAJNI_REQUIRE(args != nullptr, RAJNI_ERR_INVALID, "rajni_linear: null args");
   return launch_linear(*args, (hipStream_t)stream);
@@ -189,6 +231,20 @@ int rajni_patch_embed(const void* images, const void* w, const float* bias, cons
   NEED_DTYPE("rajni_patch_embed");
   return launch_patch_embed(images, w, bias, cls, pos, pos_has_cls, x, x_f32, B, Cin, S, P, C, dtype,
                             workspace, workspace_bytes, (hipStream_t)stream);
+}
+int rajni_patch_embed_prefix(const void* images, const void* w, const float* bias, const void* cls, const void* reg,
+                             int num_prefix, const void* pos, int pos_has_cls, void* x, int x_f32, int B, int Cin, int S,
+                             int P, int C, int dtype, void* workspace, size_t workspace_bytes, rajni_stream_t stream) {
+  NEED_DTYPE("rajni_patch_embed_prefix");
+  RAJNI_REQUIRE(images && w && cls && pos && x, RAJNI_ERR_INVALID, "rajni_patch_embed_prefix: null pointer");
+  RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
+                "rajni_patch_embed_prefix: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
+  RAJNI_REQUIRE(num_prefix == 1 || reg != nullptr, RAJNI_ERR_INVALID,
+                "rajni_patch_embed_prefix: %d prefix tokens but reg is null", num_prefix);
+  RAJNI_REQUIRE(num_prefix == 1 || ((uintptr_t)cls % 16 == 0 && (uintptr_t)reg % 16 == 0 && (uintptr_t)pos % 16 == 0),
+                RAJNI_ERR_INVALID, "rajni_patch_embed_prefix: cls, reg and pos must be 16-byte aligned");
+  return launch_patch_embed(images, w, bias, cls, pos, pos_has_cls, x, x_f32, B, Cin, S, P, C, dtype,
+                            workspace, workspace_bytes, (hipStream_t)stream, num_prefix, num_prefix > 1 ? reg : nullptr);
 }
 size_t rajni_patch_embed_workspace_bytes(int B, int Cin, int S, int P, int dtype) {
   return patch_embed_workspace_bytes(B, Cin, S, P, dtype);

@@ -192,7 +192,8 @@ extern unsigned long long* rajni_g_stamps;
 int launch_linear(const rajni_linear_args& a, hipStream_t s);
 int launch_patch_embed(const void* images, const void* w, const float* bias, const void* cls,
                        const void* pos, int pos_has_cls, void* x, int out_f32, int B, int Cin, int S,
-                       int P, int C, int dtype, void* ws, size_t ws_bytes, hipStream_t s);
+                       int P, int C, int dtype, void* ws, size_t ws_bytes, hipStream_t s,
+                       int num_prefix = 1, const void* reg = nullptr);   // reg: [num_prefix-1, C] register tokens behind CLS
 size_t patch_embed_workspace_bytes(int B, int Cin, int S, int P, int dtype);   // 0: im2col fused into the GEMM loads
 int launch_layernorm(const void* x, long xs, const float* w, const float* b, void* y, int rows,
                      int C, float eps, int x_f32, int dtype, hipStream_t s);
@@ -206,7 +207,7 @@ int launch_attention_cls(const void* qkv, void* out, int B, int N, int H, int D,
                          hipStream_t s, float q_scale = 0.f);   // q_scale > 0: the row passes through rajni_attention_fp8's e4m3 rounding
 int launch_score_select(const void* qkv, const void* scores_in, int B, int N, int H, int D,
                         float eps, int keep, void* scores_out, int32_t* keep_idx,
-                        void* next_scores, int dtype, hipStream_t s);
+                        void* next_scores, int dtype, hipStream_t s, int num_prefix = 1);
 int launch_gather_rows(const void* src, const int32_t* idx, void* dst, int B, int n_src, int n_dst,
                        int row_bytes, hipStream_t s);
 // variants.hip: the timm options of rajni_vit_ext (b pointers may be NULL = no bias; nw / fw NULL = that norm is absent)
@@ -214,4 +215,5 @@ int launch_qk_norm(void* qkv, const float* qw, const float* qb, const float* kw,
                    float eps, int dtype, hipStream_t s);
 int launch_layernorm_stream(void* x, const float* w, const float* b, int rows, int C, float eps, int x_f32, int dtype, hipStream_t s);
 int launch_pool_norm(const void* x, int B, int N, int C, int pool, const float* nw, const float* nb, float neps,
-                     const float* fw, const float* fb, float feps, void* out, int x_f32, int dtype, hipStream_t s);
+                     const float* fw, const float* fb, float feps, void* out, int x_f32, int dtype, hipStream_t s,
+                     int num_prefix = 1);

@@ -21,8 +21,8 @@ struct Workspace {
   size_t total, cols_bytes;
 };
 
-Workspace carve(const rajni_vit_plan& p) {
-  const size_t gw = p.img_size / p.patch_size, n0 = gw * gw + 1;
+Workspace carve(const rajni_vit_plan& p, int P) {
+  const size_t gw = p.img_size / p.patch_size, n0 = gw * gw + P;
   const size_t rows = (size_t)p.B * n0, es = p.dtype == RAJNI_F32 ? 4 : 2, xs = (p.dtype == RAJNI_F32 || !p.resid_bf16) ? 4 : 2;
   Workspace w{};
   size_t off = 0;
@@ -91,8 +91,24 @@ int check_ext(const rajni_vit_plan& p, const rajni_vit_ext& e) {
   return RAJNI_OK;
 }
 
-// the whole forward; ext == nullptr (rajni_vit_forward) and an all-zero record enqueue the same launches
-int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const void* images, void* logits, hipStream_t s);
+// P of a prefix record: NULL, 0 and 1 all mean CLS only
+inline int prefix_count(const rajni_vit_prefix* pre) { return (pre && pre->num_prefix > 1) ? pre->num_prefix : 1; }
+
+int check_prefix(const rajni_vit_prefix* pre, const char* who) {
+  if (!pre) return RAJNI_OK;
+  RAJNI_REQUIRE(pre->num_prefix >= 0 && pre->num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
+                "%s: num_prefix must be 0..%d (%d)", who, RAJNI_MAX_PREFIX, pre->num_prefix);
+  RAJNI_REQUIRE(pre->num_prefix <= 1 || pre->reg_token != nullptr, RAJNI_ERR_INVALID,
+                "%s: %d prefix tokens but reg_token is null", who, pre->num_prefix);
+  RAJNI_REQUIRE(pre->num_prefix > 1 || pre->reg_token == nullptr, RAJNI_ERR_INVALID,
+                "%s: reg_token given but num_prefix is %d", who, pre->num_prefix);
+  return RAJNI_OK;
+}
+
+// the whole forward; ext == nullptr (rajni_vit_forward) and an all-zero record enqueue the same launches, and so does
+// pre == nullptr (or a record with one prefix token) next to any ext
+int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre, const void* images,
+                void* logits, hipStream_t s);
 
 }  // namespace
 
@@ -100,22 +116,38 @@ extern "C" size_t rajni_vit_workspace_bytes(const rajni_vit_plan* plan) {
   if (!plan || plan->patch_size <= 0) return 0;
   rajni_vit_plan tmp = *plan;
   tmp.workspace = nullptr;
-  return carve(tmp).total;
+  return carve(tmp, 1).total;
+}
+
+extern "C" size_t rajni_vit_workspace_bytes_prefix(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix) {
+  if (!plan || plan->patch_size <= 0) return 0;
+  if (check_prefix(prefix, "rajni_vit_workspace_bytes_prefix") != RAJNI_OK) return 0;
+  rajni_vit_plan tmp = *plan;
+  tmp.workspace = nullptr;
+  return carve(tmp, prefix_count(prefix)).total;
 }
 
 extern "C" int rajni_vit_forward(const rajni_vit_plan* plan, const void* images, void* logits,
                                  rajni_stream_t stream) {
-  return vit_forward(plan, nullptr, images, logits, (hipStream_t)stream);
+  return vit_forward(plan, nullptr, nullptr, images, logits, (hipStream_t)stream);
 }
 
 extern "C" int rajni_vit_forward_ext(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const void* images, void* logits,
                                      rajni_stream_t stream) {
-  return vit_forward(plan, ext, images, logits, (hipStream_t)stream);
+  return vit_forward(plan, ext, nullptr, images, logits, (hipStream_t)stream);
+}
+
+extern "C" int rajni_vit_forward_ext_prefix(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
+                                            const void* images, void* logits, rajni_stream_t stream) {
+  const int rc = check_prefix(prefix, "rajni_vit_forward_ext_prefix");
+  if (rc != RAJNI_OK) return rc;
+  return vit_forward(plan, ext, prefix, images, logits, (hipStream_t)stream);
 }
 
 namespace {
 
-int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const void* images, void* logits, hipStream_t s) {
+int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre, const void* images,
+                void* logits, hipStream_t s) {
   RAJNI_REQUIRE(plan && images && logits, RAJNI_ERR_INVALID, "rajni_vit_forward: null pointer");
   const rajni_vit_plan& p = *plan;
   int rc = check_plan(p, ext != nullptr && ext->norm_absent != 0);
@@ -125,17 +157,19 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const void
     if (rc != RAJNI_OK) return rc;
   }
   const rajni_qk_affine* qkn = ext ? ext->qk_norm : nullptr;
-  const Workspace w = carve(p);
+  const int P = prefix_count(pre);   // prefix tokens: CLS + registers, never pruned
+  const Workspace w = carve(p, P);
   RAJNI_REQUIRE(p.workspace != nullptr && p.workspace_bytes >= w.total, RAJNI_ERR_INVALID,
                 "rajni_vit_forward: workspace too small (%zu < %zu)", p.workspace_bytes, w.total);
   const int B = p.B, C = p.C;
   const int gw = p.img_size / p.patch_size;
-  int N = gw * gw + 1;
+  int N = gw * gw + P;
 
   const int dt = p.dtype;
   const int sf32 = (dt != RAJNI_F32 && !p.resid_bf16) ? 1 : 0;  // 16-bit model with an fp32 residual stream
   rc = launch_patch_embed(images, p.patch_w, p.patch_b, p.cls_token, p.pos_embed, p.pos_has_cls,
-                          w.xa, sf32, B, p.in_chans, p.img_size, p.patch_size, C, dt, w.cols, w.cols_bytes, s);
+                          w.xa, sf32, B, p.in_chans, p.img_size, p.patch_size, C, dt, w.cols, w.cols_bytes, s,
+                          P, P > 1 ? pre->reg_token : nullptr);
   if (rc != RAJNI_OK) return rc;
   if (ext && ext->norm_pre_w) {   // timm forward_features: x = norm_pre(x), written back into the stream
     rc = launch_layernorm_stream(w.xa, ext->norm_pre_w, ext->norm_pre_b, B * N, C, ext->norm_pre_eps, sf32, dt, s);
@@ -207,9 +241,9 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const void
     int Np = N;
     const int32_t* idx = nullptr;
     if (blk.keep > 0) {  // scheduled block (model.py:50)
-      RAJNI_REQUIRE(blk.keep <= N - 1, RAJNI_ERR_INVALID, "block %d: keep=%d but only %d patch tokens", i, blk.keep, N - 1);
+      RAJNI_REQUIRE(blk.keep <= N - P, RAJNI_ERR_INVALID, "block %d: keep=%d but only %d patch tokens", i, blk.keep, N - P);
       RAJNI_REQUIRE(blk.keep_idx && blk.next_scores, RAJNI_ERR_INVALID, "block %d: keep_idx/next_scores buffers missing", i);
-      Np = blk.keep + 1;
+      Np = blk.keep + P;
       const bool recompute = blk.update || carried == nullptr;  // attention.py:25
       if (blk.forced_keep_idx) {
         const void* full = carried;
@@ -231,10 +265,10 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const void
       } else {
         if (recompute)
           rc = launch_score_select(w.qkv, nullptr, B, N, p.H, p.D, 1e-6f, blk.keep, blk.scores,
-                                   blk.keep_idx, blk.next_scores, dt, s);
+                                   blk.keep_idx, blk.next_scores, dt, s, P);
         else
           rc = launch_score_select(nullptr, carried, B, N, 0, 0, 0.f, blk.keep, nullptr,
-                                   blk.keep_idx, blk.next_scores, dt, s);
+                                   blk.keep_idx, blk.next_scores, dt, s, P);
         if (rc != RAJNI_OK) return rc;
         idx = blk.keep_idx;
       }
@@ -296,7 +330,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const void
   // (with a pooled head, fc_norm or no norm: norm on every row that is pooled -> pool -> fc_norm, one kernel)
   if (ext && (ext->pool != RAJNI_POOL_TOKEN || ext->fc_norm_w || ext->norm_absent))
     rc = launch_pool_norm(cur, B, N, C, ext->pool, ext->norm_absent ? nullptr : p.norm_w, p.norm_b, p.ln_eps,
-                          ext->fc_norm_w, ext->fc_norm_b, ext->fc_norm_eps, w.clsn, sf32, dt, s);
+                          ext->fc_norm_w, ext->fc_norm_b, ext->fc_norm_eps, w.clsn, sf32, dt, s, P);
   else
     rc = launch_layernorm(cur, (long)N * C, p.norm_w, p.norm_b, w.clsn, B, C, p.ln_eps, sf32, dt, s);
   if (rc != RAJNI_OK) return rc;

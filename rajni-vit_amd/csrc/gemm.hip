@@ -50,6 +50,7 @@ struct GemmParams {
   int nblk;                     // persistent tilings: column tiles per N block of the tile order (tile_mn)
   // patch-embed A loader / epilogue
   int cin, S, log2ps, gw, npatch;
+  int nprefix;                  // prefix rows per image ahead of the patch rows: CLS + register tokens (>= 1)
   const void* pos; int pos_off; // pos-embed rows, activation dtype
   unsigned long long* stamps;   // diagnostic builds only (RAJNI_GEMM_STAMPS): 4 s_memtime values per block
   int stagger;                  // residual launches: every other workgroup of an XCD sleeps stagger x 8k cycles before its
@@ -198,7 +199,7 @@ __device__ __forceinline__ void epilogue_row(const GemmParams& p, int m, int nbA
     }
   } else if (EPI == EPI_PATCH) {
     const int b = m / p.npatch, pp = m - b * p.npatch;
-    orow = (long)b * (p.npatch + 1) + 1 + pp;
+    orow = (long)b * (p.npatch + p.nprefix) + p.nprefix + pp;
     const A* pr = reinterpret_cast<const A*>(p.pos) + (long)(pp + p.pos_off) * p.ldc;
     if (full) {
       float pf[16];
@@ -309,7 +310,7 @@ __device__ __forceinline__ void epilogue_row_nat(const GemmParams& p, int m, int
   if (EPI == EPI_PATCH) {
     const int b = m / p.npatch;
     pp = m - b * p.npatch;
-    orow = (long)b * (p.npatch + 1) + 1 + pp;
+    orow = (long)b * (p.npatch + p.nprefix) + p.nprefix + pp;
   }
   const float* R = reinterpret_cast<const float*>(p.R);
   const A* P = reinterpret_cast<const A*>(p.pos);
@@ -1184,7 +1185,7 @@ __device__ __forceinline__ void epilogue_row_f32(const GemmParams& p, int m, int
       if (nb + j < p.N) v[j] = fmaf(gam[j], v[j], reinterpret_cast<const float*>(p.R)[roff + j]);
   } else if (EPI == EPI_PATCH) {
     const int b = m / p.npatch, pp = m - b * p.npatch;
-    orow = (long)b * (p.npatch + 1) + 1 + pp;
+    orow = (long)b * (p.npatch + p.nprefix) + p.nprefix + pp;
     const float* pr = reinterpret_cast<const float*>(p.pos) + (long)(pp + p.pos_off) * p.ldc + nb;
 #pragma unroll
     for (int j = 0; j < 16; ++j)
@@ -1322,6 +1323,30 @@ __global__ void cls_pos_kernel(const T* cls, const T* pos, int pos_has_cls, void
   float v = ld1(cls + c);
   if (pos_has_cls) v += ld1(pos + c);
   store1<SF32, T>(x, (long)b * img_stride + c, v);
+}
+
+// x[b,r,:] = prefix[r] + pos[r] for the P prefix rows of image b (row 0 = cls, rows 1..P-1 = the register tokens; the
+// prefix row alone when pos has no prefix rows).  One thread = 8 consecutive channels: one 16-byte store into a 16-bit
+// stream, two into the fp32 one, a wave a run of whole lines.  (P = 1 keeps cls_pos_kernel: the same launches as ever.)
+template <bool SF32, typename T>
+__global__ void __launch_bounds__(256) prefix_pos_kernel(const T* cls, const T* reg, const T* pos, int pos_has_prefix, void* x,
+                                                         long img_stride, int B, int P, int C) {
+  const int c8 = C >> 3;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * P * c8) return;
+  const int br = i / c8, c = (i - br * c8) * 8;
+  const int b = br / P, r = br - b * P;
+  float v[8];
+  load8<T>((r == 0 ? cls : reg + (long)(r - 1) * C) + c, v);
+  if (pos_has_prefix) {
+    float pf[8];
+    load8<T>(pos + (long)r * C + c, pf);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] += pf[j];
+  }
+  const long off = (long)b * img_stride + (long)r * C + c;
+  if constexpr (SF32) store8<float>(reinterpret_cast<float*>(x) + off, v);
+  else store8<T>(reinterpret_cast<T*>(x) + off, v);
 }
 
 // LDS stages of the wide tiling: 2 for bf16 weights (2 x 64 KiB); fp8 weights leave room for 3 (3 x 48 KiB)
@@ -1667,8 +1692,13 @@ __global__ void __launch_bounds__(256) im2col_kernel(const T* img, T* cols, int 
 
 int launch_patch_embed(const void* images, const void* w, const float* bias, const void* cls,
                        const void* pos, int pos_has_cls, void* x, int out_f32, int B, int Cin, int S,
-                       int P, int C, int dtype, void* ws, size_t ws_bytes, hipStream_t s) {
+                       int P, int C, int dtype, void* ws, size_t ws_bytes, hipStream_t s, int num_prefix, const void* reg) {
   RAJNI_REQUIRE(images && w && cls && pos && x, RAJNI_ERR_INVALID, "rajni_patch_embed: null pointer");
+  RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
+                "rajni_patch_embed: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
+  RAJNI_REQUIRE(num_prefix == 1 || reg != nullptr, RAJNI_ERR_INVALID, "rajni_patch_embed: %d prefix tokens but reg_token is null", num_prefix);
+  RAJNI_REQUIRE(num_prefix == 1 || ((uintptr_t)cls % 16 == 0 && (uintptr_t)reg % 16 == 0 && (uintptr_t)pos % 16 == 0),
+                RAJNI_ERR_INVALID, "rajni_patch_embed: cls, reg_token and pos must be 16-byte aligned");
   RAJNI_REQUIRE(P >= 1 && S % P == 0 && B > 0 && Cin > 0, RAJNI_ERR_INVALID,
                 "rajni_patch_embed: the patch size must divide the image (P=%d S=%d)", P, S);
   RAJNI_REQUIRE(C % 8 == 0, RAJNI_ERR_UNSUPPORTED, "rajni_patch_embed: C %% 8 == 0 required");
@@ -1682,7 +1712,8 @@ int launch_patch_embed(const void* images, const void* w, const float* bias, con
   p.Y = x; p.ldc = C;
   p.M = B * npatch; p.N = C; p.K = kpad;
   p.gw = gw; p.npatch = npatch;
-  p.pos = pos; p.pos_off = pos_has_cls ? 1 : 0;
+  p.pos = pos; p.pos_off = pos_has_cls ? num_prefix : 0;
+  p.nprefix = num_prefix;
   int rc;
   if (patch_fused(Cin, S, P)) {
     int log2ps = 0;
@@ -1718,7 +1749,22 @@ int launch_patch_embed(const void* images, const void* w, const float* bias, con
                       : launch_gemm<EPI_PATCH, ALOAD_PLAIN, false>(p, KC_GEMM_PATCH, s);
   }
   if (rc != RAJNI_OK) return rc;
-  {
+  if (num_prefix > 1) {
+    ProfScope prof(KC_CLS_POS, s, 0.0, 6.0 * B * num_prefix * C);
+    const int n = B * num_prefix * (C / 8);
+    const dim3 grid((n + 255) / 256), block(256);
+    const long stride = (long)(npatch + num_prefix) * C;
+#define RAJNI_PREFIX_POS(SF, T)                                                                                        \
+  hipLaunchKernelGGL((prefix_pos_kernel<SF, T>), grid, block, 0, s, (const T*)cls, (const T*)reg, (const T*)pos, pos_has_cls, x, \
+                     stride, B, num_prefix, C)
+    if (dtype == RAJNI_F32) RAJNI_PREFIX_POS(true, float);
+    else if (dtype == RAJNI_F16 && out_f32) RAJNI_PREFIX_POS(true, f16_t);
+    else if (dtype == RAJNI_F16) RAJNI_PREFIX_POS(false, f16_t);
+    else if (out_f32) RAJNI_PREFIX_POS(true, bf16_t);
+    else RAJNI_PREFIX_POS(false, bf16_t);
+#undef RAJNI_PREFIX_POS
+    RAJNI_CHECK_LAUNCH("prefix_pos_kernel");
+  } else {
     ProfScope prof(KC_CLS_POS, s, 0.0, 6.0 * B * C);
     const int n = B * C;
     const dim3 grid((n + 255) / 256), block(256);

@@ -37,9 +37,10 @@ struct ScoreArgs {          // T = activation dtype (bf16_t, f16_t or float)
   int N, H, D;
   float eps;
   int keep;                 // 0: scores only
+  int P;                    // prefix tokens (CLS + registers): rows 0..P-1 are always kept and never ranked
   void* scores_out;         // T [B,N] or null
-  int* keep_idx;            // [B,keep+1]
-  void* next_scores;        // T [B,keep+1] or null
+  int* keep_idx;            // [B,P+keep]
+  void* next_scores;        // T [B,P+keep] or null
   unsigned long long* stamps;   // diagnostic builds (-DRAJNI_SS_STAMPS): 16 x u64 s_memtime per workgroup, or null
 };
 #ifdef RAJNI_SS_STAMPS
@@ -49,6 +50,25 @@ struct ScoreArgs {          // T = activation dtype (bf16_t, f16_t or float)
 #endif
 
 __device__ __forceinline__ float rank_key(float s) { return (s != s) ? INFINITY : s; }
+
+// lanes that share one token's rank count, by the number of ranked (patch) tokens
+__host__ __device__ inline int ss_tpt(int npatch) {
+  return npatch * 8 <= SS_THREADS ? 8 : npatch * 4 <= SS_THREADS ? 4 : npatch * 2 <= SS_THREADS ? 2 : 1;
+}
+// words of the packed-key image of N tokens (P of them prefix): tpt slices of `cstride` 16-byte chunks.  It lives in the
+// logits' region, which is smaller than this for a handful of tokens (N = 2, H = 1, D = 8: 20 words against 32), so the
+// kernel and ss_lds_bytes both size the region to hold it.
+__host__ __device__ inline int ss_key_words(int N, int P) {
+  const int tpt = ss_tpt(N - P);
+  const int chunks = (N + 3) >> 2, cps = (chunks + tpt - 1) / tpt;
+  return (cps | 1) * tpt * 4;
+}
+__host__ __device__ inline int ss_region_words(int N, int H, int D, int P, bool merged) {
+  const int lg = (H * N + 3) & ~3;
+  const int r = merged ? lg + N * D : (((H * N > N * D) ? H * N : N * D) + 3) & ~3;
+  const int kw = ss_key_words(N, P);
+  return r > kw ? r : kw;
+}
 
 // sum over an aligned group of `width` (4, 8 or 16) consecutive lanes, every lane gets the total; DPP adds in
 // a fixed tree (bitwise reproducible): xor 1, xor 2, mirror within 8, mirror within 16
@@ -73,7 +93,7 @@ __global__ void __launch_bounds__(SS_THREADS) score_select_kernel(const ScoreArg
   const int b = blockIdx.x;
   const int N = a.N, H = a.H, D = a.D, C = H * D;
   const int lg_sz = (H * N + 3) & ~3;
-  const int region_sz = MERGED ? lg_sz + N * D : (((H * N > N * D) ? H * N : N * D) + 3) & ~3;
+  const int region_sz = ss_region_words(N, H, D, a.P, MERGED);
   float* qcls = sm;                    // [C]
   float* region = qcls + C;            // logits [H][N]  (then / followed by)  vbar [N][D]
   float* vbar = MERGED ? region + lg_sz : region;
@@ -360,15 +380,15 @@ __global__ void __launch_bounds__(SS_THREADS) score_select_kernel(const ScoreArg
   SS_STAMP(5);
   if (a.keep <= 0) return;
 
-  // ---- rank patch tokens 1..N-1, keep rank < keep, compact in ascending index order
+  // ---- rank patch tokens P..N-1, keep rank < keep, compact in ascending index order behind the P prefix slots
   //      (attention.py:34-39: topk -> sort -> +1 -> prepend CLS; attention.py:58: carried scores)
-  const int keep = a.keep;
-  int* kout = a.keep_idx + (long)b * (keep + 1);
-  T* nout = a.next_scores ? reinterpret_cast<T*>(a.next_scores) + (long)b * (keep + 1) : nullptr;
+  const int keep = a.keep, P = a.P;
+  int* kout = a.keep_idx + (long)b * (keep + P);
+  T* nout = a.next_scores ? reinterpret_cast<T*>(a.next_scores) + (long)b * (keep + P) : nullptr;
   int running = 0;
   // tpt = 1, 2, 4 or 8 lanes share a token's rank count (each a slice of the j range, summed by shuffles): with
   // 197 tokens one lane per token left 60 % of the workgroup idle through a 196-step loop
-  const int tpt = (N - 1) * 8 <= SS_THREADS ? 8 : (N - 1) * 4 <= SS_THREADS ? 4 : (N - 1) * 2 <= SS_THREADS ? 2 : 1;
+  const int tpt = ss_tpt(N - P);
   const int per_iter = SS_THREADS / tpt, sl = tid & (tpt - 1);
   // The count loop is VALU bound (N^2 compares over 4 SIMDs: stamps put it at 14k of the kernel's 88k cycles at 197
   // tokens, 95k of 297k at 577, when a compare was ~8 instructions: two range tests, >, ==, index test, or / and / add).
@@ -376,11 +396,11 @@ __global__ void __launch_bounds__(SS_THREADS) score_select_kernel(const ScoreArg
   //     key32[j] = sortable16(score_j) << 16 | (0xFFFF - j)        (NaN = +inf, -0 = +0; N <= 65535)
   // (sortable16 of the score's own 16-bit pattern: for bf16 that is the upper half of the fp32 pattern, for fp16 not)
   // "j beats i" (larger score, or equal score and lower index - the defined tie rule) <=> key32[j] > key32[i], and the
-  // CLS slot and the padding hold 0 (below every real key), so slices need no range tests: v_cmp + add-with-carry.
+  // prefix slots and the padding hold 0 (below every real key), so slices need no range tests: v_cmp + add-with-carry.
   // fp32 scores keep the float compare (the accuracy path).
   constexpr bool PACKED = sizeof(T) == 2;
   float* keys = acls;                                         // fp32 path: ranking keys (NaN = +inf), A_cls is dead
-  unsigned* keys32 = reinterpret_cast<unsigned*>(region);     // packed path: the logits' region is dead (>= N + 4 * tpt + 4 words)
+  unsigned* keys32 = reinterpret_cast<unsigned*>(region);     // packed path: the logits' region is dead (>= ss_key_words(N, P) words)
   const int chunks = (N + 3) >> 2, cps = (chunks + tpt - 1) / tpt;   // 16-byte chunks of keys; per slice
   const int cstride = cps | 1;     // slices an ODD number of chunks apart: the tpt broadcast reads of a step hit distinct banks
   if constexpr (PACKED) {
@@ -388,7 +408,7 @@ __global__ void __launch_bounds__(SS_THREADS) score_select_kernel(const ScoreArg
       const int slw = w / (cstride * 4), off = w - slw * cstride * 4;
       const int n = off < cps * 4 ? slw * cps * 4 + off : N;     // token of word w (padding words: none)
       unsigned k = 0;
-      if (n >= 1 && n < N) {
+      if (n >= P && n < N) {
         if constexpr (__is_same(T, f16_t)) {
           // fp16 scores: the upper half of the fp32 pattern would merge fp16 values that differ below bf16 precision,
           // so the key is built from the fp16 pattern itself (exact: sc holds fp16 values; NaN -> +inf first)
@@ -410,8 +430,8 @@ __global__ void __launch_bounds__(SS_THREADS) score_select_kernel(const ScoreArg
   }
   __syncthreads();
   SS_STAMP(7);
-  const int slice = (N - 1 + tpt - 1) / tpt;
-  for (int base_i = 1; base_i < N; base_i += per_iter) {
+  const int slice = (N - P + tpt - 1) / tpt;
+  for (int base_i = P; base_i < N; base_i += per_iter) {
     const int i = base_i + tid / tpt;
     const bool valid = i < N;
     float si = 0.f;
@@ -429,7 +449,7 @@ __global__ void __launch_bounds__(SS_THREADS) score_select_kernel(const ScoreArg
         }
       } else {
         const float ki = keys[i];
-        const int j0 = 1 + sl * slice, j1 = j0 + slice < N ? j0 + slice : N;
+        const int j0 = P + sl * slice, j1 = j0 + slice < N ? j0 + slice : N;
         // j beats i when its key is larger, or equal with a lower index (the defined tie rule)
         auto beats = [&](float kj, int j) { return (j >= j0 && j < j1 && (kj > ki || (kj == ki && j < i))) ? 1 : 0; };
 #pragma unroll 4
@@ -457,24 +477,23 @@ __global__ void __launch_bounds__(SS_THREADS) score_select_kernel(const ScoreArg
     }
     if (kept) {
       const int pos = running + prefix + __popcll(bal & ((1ull << lane) - 1ull));
-      kout[1 + pos] = i;
-      if (nout) st1(nout + 1 + pos, si);
+      kout[P + pos] = i;
+      if (nout) st1(nout + P + pos, si);
     }
     running += total;
     __syncthreads();
     SS_STAMP(10);
   }
-  if (tid == 0) {
-    kout[0] = 0;
-    if (nout) st1(nout, sc[0]);
+  if (tid < P) {   // the prefix slots: CLS and the register tokens, in place
+    kout[tid] = tid;
+    if (nout) st1(nout + tid, sc[tid]);
   }
   SS_STAMP(6);
 }
 
-size_t ss_lds_bytes(int N, int H, int D, bool merged) {
+size_t ss_lds_bytes(int N, int H, int D, int P, bool merged) {
   const size_t C = (size_t)H * D;
-  const size_t region = merged ? (size_t)((H * N + 3) & ~3) + (size_t)N * D
-                               : (size_t)((((H * N > N * D) ? H * N : N * D) + 3) & ~3);
+  const size_t region = (size_t)ss_region_words(N, H, D, P, merged);
   return (C + region + 2 * (size_t)N + 2 * (size_t)H + SS_PART + D + 16 + SS_THREADS / 64) * sizeof(float);
 }
 
@@ -487,14 +506,15 @@ extern "C" void rajni_debug_force_score_two_pass(int on) { g_ss_force_two_pass =
 // qkv != null: compute scores (and select when keep > 0); qkv == null: select from scores_in.
 int launch_score_select(const void* qkv, const void* scores_in, int B, int N, int H, int D,
                         float eps, int keep, void* scores_out, int32_t* keep_idx,
-                        void* next_scores, int dtype, hipStream_t s) {
+                        void* next_scores, int dtype, hipStream_t s, int P) {
   RAJNI_REQUIRE(dtype == RAJNI_BF16 || dtype == RAJNI_F32 || dtype == RAJNI_F16, RAJNI_ERR_INVALID, "score/select: bad dtype %d", dtype);
-  RAJNI_REQUIRE(B > 0 && N >= 2, RAJNI_ERR_INVALID, "score/select: need B > 0 and N >= 2 (B=%d N=%d)", B, N);
-  RAJNI_REQUIRE(keep >= 0 && keep <= N - 1, RAJNI_ERR_INVALID,
-                "score/select: keep=%d out of range for N=%d (keep_ratio must be <= 1)", keep, N);
+  RAJNI_REQUIRE(P >= 1 && P <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID, "score/select: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, P);
+  RAJNI_REQUIRE(B > 0 && N >= P + 1, RAJNI_ERR_INVALID, "score/select: need B > 0 and N >= %d (B=%d N=%d)", P + 1, B, N);
+  RAJNI_REQUIRE(keep >= 0 && keep <= N - P, RAJNI_ERR_INVALID,
+                "score/select: keep=%d out of range for N=%d with %d prefix tokens (keep_ratio must be <= 1)", keep, N, P);
   RAJNI_REQUIRE(keep == 0 || keep_idx != nullptr, RAJNI_ERR_INVALID, "score/select: keep_idx is null");
   ScoreArgs a{};
-  a.N = N; a.keep = keep; a.eps = eps;
+  a.N = N; a.keep = keep; a.eps = eps; a.P = P;
   a.scores_out = scores_out; a.keep_idx = keep_idx; a.next_scores = next_scores;
   a.stamps = rajni_g_stamps;
   size_t lds;
@@ -504,12 +524,12 @@ int launch_score_select(const void* qkv, const void* scores_in, int B, int N, in
                   "importance: head dim %d not supported (multiples of 8 up to 128)", D);
     RAJNI_REQUIRE(H > 0, RAJNI_ERR_INVALID, "importance: H must be positive");
     a.qkv = qkv; a.H = H; a.D = D;
-    merged = ss_lds_bytes(N, H, D, true) <= 160 * 1024 && g_ss_force_two_pass == 0;   // else vbar reuses the logits' region
-    lds = ss_lds_bytes(N, H, D, merged);
+    merged = ss_lds_bytes(N, H, D, P, true) <= 160 * 1024 && g_ss_force_two_pass == 0;   // else vbar reuses the logits' region
+    lds = ss_lds_bytes(N, H, D, P, merged);
   } else {
     RAJNI_REQUIRE(scores_in != nullptr, RAJNI_ERR_INVALID, "select: scores is null");
     a.scores_in = scores_in; a.H = 1; a.D = 32;
-    lds = ss_lds_bytes(N, 1, 32, false);
+    lds = ss_lds_bytes(N, 1, 32, P, false);
   }
   RAJNI_REQUIRE(lds <= 160 * 1024, RAJNI_ERR_UNSUPPORTED,
                 "score/select: N=%d H=%d D=%d needs %zu B of LDS (> 160 KiB)", N, H, D, lds);

@@ -159,7 +159,8 @@ __global__ void __launch_bounds__(256) layernorm_stream_kernel(T* x, const float
 
 // One workgroup of 8 waves per image.  out[img] = fc_norm(mean_{r0 <= r < r1} norm(x[img, r])), either norm optional.
 // Summation order (fixed): wave k adds its rows r0 + k, r0 + k + 8, ... in ascending order; then s_k += s_{k+4} (k < 4);
-// then ((s_0 + s_1) + s_2) + s_3.  'token' pooling is r0 = 0, r1 = 1: one row, the sums are that row.
+// then ((s_0 + s_1) + s_2) + s_3.  'token' pooling is r0 = 0, r1 = 1: one row, the sums are that row; 'avg' is r0 = the number
+// of prefix tokens (CLS + registers), r1 = N.
 constexpr int POOL_WAVES = 8;
 template <typename TX, typename TY>
 __global__ void __launch_bounds__(64 * POOL_WAVES) pool_norm_kernel(const TX* __restrict__ x, int N, int C, int r0, int r1,
@@ -300,14 +301,17 @@ int launch_layernorm_stream(void* x, const float* w, const float* b, int rows, i
 }
 
 int launch_pool_norm(const void* x, int B, int N, int C, int pool, const float* nw, const float* nb, float neps,
-                     const float* fw, const float* fb, float feps, void* out, int x_f32, int dtype, hipStream_t s) {
+                     const float* fw, const float* fb, float feps, void* out, int x_f32, int dtype, hipStream_t s, int num_prefix) {
   RAJNI_REQUIRE(x && out, RAJNI_ERR_INVALID, "rajni_pool_norm: null pointer");
+  RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
+                "rajni_pool_norm: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
   RAJNI_REQUIRE(pool == RAJNI_POOL_TOKEN || pool == RAJNI_POOL_AVG, RAJNI_ERR_UNSUPPORTED,
                 "rajni_pool_norm: pool must be RAJNI_POOL_TOKEN or RAJNI_POOL_AVG (%d)", pool);
   RAJNI_REQUIRE(B > 0 && N > 0 && C > 0 && C % 8 == 0 && C <= 64 * 8 * LS_MAX_CHUNKS, RAJNI_ERR_UNSUPPORTED,
                 "rajni_pool_norm: need C %% 8 == 0, C <= 2048 (C=%d)", C);
-  RAJNI_REQUIRE(pool == RAJNI_POOL_TOKEN || N >= 2, RAJNI_ERR_INVALID, "rajni_pool_norm: 'avg' needs at least one patch token (N=%d)", N);
-  const int r0 = pool == RAJNI_POOL_AVG ? 1 : 0, r1 = pool == RAJNI_POOL_AVG ? N : 1;
+  RAJNI_REQUIRE(pool == RAJNI_POOL_TOKEN || N >= num_prefix + 1, RAJNI_ERR_INVALID,
+                "rajni_pool_norm: 'avg' needs at least one patch token (N=%d, %d prefix tokens)", N, num_prefix);
+  const int r0 = pool == RAJNI_POOL_AVG ? num_prefix : 0, r1 = pool == RAJNI_POOL_AVG ? N : 1;
   const bool f32 = dtype == RAJNI_F32 || x_f32;
   ProfScope prof(KC_LAYERNORM, s, 8.0 * B * (r1 - r0) * C, (f32 ? 4.0 : 2.0) * B * (r1 - r0) * C);
   if (f32) launch_pool_norm_t<float>(x, B, N, C, r0, r1, nw, nb, neps, fw, fb, feps, out, dtype, s);

@@ -74,6 +74,13 @@ class VitExt(C.Structure):
                 ("fc_norm_w", c_void_p), ("fc_norm_b", c_void_p), ("fc_norm_eps", c_float)]
 
 
+class VitPrefix(C.Structure):
+    """rajni_vit_prefix: prefix tokens beyond CLS (timm register tokens), beside the plan and the ext record"""
+    _fields_ = [("num_prefix", c_int), ("reg_token", c_void_p)]
+
+
+MAX_PREFIX = 32     # RAJNI_MAX_PREFIX
+
 _SIGS = {
     "rajni_abi_version": (c_int, []),
     "rajni_last_error": (C.c_char_p, []),
@@ -109,6 +116,16 @@ _SIGS = {
     "rajni_vit_workspace_bytes": (c_size_t, [C.POINTER(VitPlan)]),
     "rajni_vit_forward": (c_int, [C.POINTER(VitPlan), c_void_p, c_void_p, c_void_p]),
     "rajni_vit_forward_ext": (c_int, [C.POINTER(VitPlan), C.POINTER(VitExt), c_void_p, c_void_p, c_void_p]),
+    "rajni_select_topk_prefix": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "rajni_score_select_prefix": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_int, c_void_p]),
+    "rajni_patch_embed_prefix": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                         c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "rajni_pool_norm_prefix": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p,
+                                       c_void_p, c_float, c_void_p, c_int, c_int, c_void_p]),
+    "rajni_vit_workspace_bytes_prefix": (c_size_t, [C.POINTER(VitPlan), C.POINTER(VitPrefix)]),
+    "rajni_vit_forward_ext_prefix": (c_int, [C.POINTER(VitPlan), C.POINTER(VitExt), C.POINTER(VitPrefix), c_void_p, c_void_p,
+                                             c_void_p]),
     "rajni_profile_enable": (None, [C.c_uint]),
     "rajni_profile_class_name": (C.c_char_p, [c_int]),
     "rajni_profile_collect": (c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.POINTER(C.c_double),

@@ -12,10 +12,11 @@ import torch
 from . import _native as nat
 
 
-def keep_count(keep_ratio: float, n_tokens: int) -> int:
+def keep_count(keep_ratio: float, n_tokens: int, num_prefix: int = 1) -> int:
     """`keep = max(1, int(keep_ratio * (N - 1)))` - Python-double semantics of the reference
-    (rajni/wrapper/attention.py:31-32); data independent."""
-    return max(1, int(keep_ratio * (n_tokens - 1)))
+    (rajni/wrapper/attention.py:31-32); data independent.  With `num_prefix` = P prefix tokens (CLS + register tokens)
+    only the N - P patch tokens are ranked: max(1, int(keep_ratio * (N - P)))."""
+    return max(1, int(keep_ratio * (n_tokens - num_prefix)))
 
 
 def _dt(t: torch.Tensor) -> int:
@@ -93,30 +94,46 @@ def importance(qkv: torch.Tensor, num_heads: int, eps: float = 1e-6) -> torch.Te
     return out
 
 
-def select_topk(scores: torch.Tensor, keep: int) -> Tuple[torch.Tensor, torch.Tensor]:
+def select_topk(scores: torch.Tensor, keep: int, num_prefix: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """scores [B, N] -> (keep_idx int32 [B, P+keep], next_scores [B, P+keep]); the first P = `num_prefix` tokens are always
+    kept (slots 0..P-1) and take no rank slot."""
     nat.require_device(scores, "scores")
     scores = scores.contiguous()
     B, N = scores.shape
-    idx = torch.empty((B, keep + 1), dtype=torch.int32, device=scores.device)
-    nxt = torch.empty((B, keep + 1), dtype=scores.dtype, device=scores.device)
+    P = int(num_prefix)
+    idx = torch.empty((B, keep + P), dtype=torch.int32, device=scores.device)
+    nxt = torch.empty((B, keep + P), dtype=scores.dtype, device=scores.device)
     with nat.device_guard(scores.device):
-        nat.check(nat.lib().rajni_select_topk(scores.data_ptr(), B, N, keep, idx.data_ptr(), nxt.data_ptr(),
-                                              _dt(scores), nat.stream_ptr(scores.device)), "rajni_select_topk")
+        if P == 1:
+            nat.check(nat.lib().rajni_select_topk(scores.data_ptr(), B, N, keep, idx.data_ptr(), nxt.data_ptr(),
+                                                  _dt(scores), nat.stream_ptr(scores.device)), "rajni_select_topk")
+        else:
+            nat.check(nat.lib().rajni_select_topk_prefix(scores.data_ptr(), B, N, P, keep, idx.data_ptr(), nxt.data_ptr(),
+                                                         _dt(scores), nat.stream_ptr(scores.device)), "rajni_select_topk_prefix")
     return idx, nxt
 
 
-def score_select(qkv: torch.Tensor, num_heads: int, keep: int, eps: float = 1e-6, want_scores: bool = True):
+def score_select(qkv: torch.Tensor, num_heads: int, keep: int, eps: float = 1e-6, want_scores: bool = True,
+                 num_prefix: int = 1):
+    """qkv [B, N, 3C] -> (scores [B, N] or None, keep_idx int32 [B, P+keep], next_scores [B, P+keep]), P = `num_prefix`
+    as in select_topk (the scores themselves do not depend on P)."""
     nat.require_device(qkv, "qkv")
     qkv = qkv.contiguous()
     B, N, threeC = qkv.shape
     D = threeC // 3 // num_heads
+    P = int(num_prefix)
     scores = torch.empty((B, N), dtype=qkv.dtype, device=qkv.device) if want_scores else None
-    idx = torch.empty((B, keep + 1), dtype=torch.int32, device=qkv.device)
-    nxt = torch.empty((B, keep + 1), dtype=qkv.dtype, device=qkv.device)
+    idx = torch.empty((B, keep + P), dtype=torch.int32, device=qkv.device)
+    nxt = torch.empty((B, keep + P), dtype=qkv.dtype, device=qkv.device)
     with nat.device_guard(qkv.device):
-        nat.check(nat.lib().rajni_score_select(qkv.data_ptr(), B, N, num_heads, D, eps, keep, nat.ptr(scores),
-                                               idx.data_ptr(), nxt.data_ptr(), _dt(qkv),
-                                               nat.stream_ptr(qkv.device)), "rajni_score_select")
+        if P == 1:
+            nat.check(nat.lib().rajni_score_select(qkv.data_ptr(), B, N, num_heads, D, eps, keep, nat.ptr(scores),
+                                                   idx.data_ptr(), nxt.data_ptr(), _dt(qkv),
+                                                   nat.stream_ptr(qkv.device)), "rajni_score_select")
+        else:
+            nat.check(nat.lib().rajni_score_select_prefix(qkv.data_ptr(), B, N, num_heads, D, eps, P, keep, nat.ptr(scores),
+                                                          idx.data_ptr(), nxt.data_ptr(), _dt(qkv),
+                                                          nat.stream_ptr(qkv.device)), "rajni_score_select_prefix")
     return scores, idx, nxt
 
 
@@ -268,9 +285,10 @@ def layernorm_stream(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]
     return x
 
 
-def pool_norm(x: torch.Tensor, pool: str = "token", norm=None, fc_norm=None, out_dtype=torch.bfloat16) -> torch.Tensor:
+def pool_norm(x: torch.Tensor, pool: str = "token", norm=None, fc_norm=None, out_dtype=torch.bfloat16,
+              num_prefix: int = 1) -> torch.Tensor:
     """timm's head input: fc_norm(pool(norm(x))) for x [B, N, C] (`out_dtype`, or fp32 = the fp32 residual stream) -> [B, C]
-    in `out_dtype`.  pool: "token" (x[:, 0]) or "avg" (mean of x[:, 1:]); norm / fc_norm: (w, b or None, eps) or None."""
+    in `out_dtype`.  pool: "token" (x[:, 0]) or "avg" (mean of x[:, num_prefix:]); norm / fc_norm: (w, b or None, eps) or None."""
     nat.require_device(x, "x")
     if pool not in ("token", "avg"):
         raise NotImplementedError(f"pool_norm: pool '{pool}' is not supported ('token' or 'avg')")
@@ -280,11 +298,18 @@ def pool_norm(x: torch.Tensor, pool: str = "token", norm=None, fc_norm=None, out
     nw, nb, ne = norm if norm is not None else (None, None, 0.0)
     fw, fb, fe = fc_norm if fc_norm is not None else (None, None, 0.0)
     out = torch.empty((B, Cc), dtype=out_dtype, device=x.device)
+    pk = nat.POOL_AVG if pool == "avg" else nat.POOL_TOKEN
     with nat.device_guard(x.device):
-        nat.check(nat.lib().rajni_pool_norm(x.data_ptr(), B, N, Cc, nat.POOL_AVG if pool == "avg" else nat.POOL_TOKEN,
-                                            nat.ptr(nw), nat.ptr(nb), float(ne), nat.ptr(fw), nat.ptr(fb), float(fe),
-                                            out.data_ptr(), nat.dtype_code(out_dtype), x_f32, nat.stream_ptr(x.device)),
-                  "rajni_pool_norm")
+        if int(num_prefix) == 1:
+            nat.check(nat.lib().rajni_pool_norm(x.data_ptr(), B, N, Cc, pk,
+                                                nat.ptr(nw), nat.ptr(nb), float(ne), nat.ptr(fw), nat.ptr(fb), float(fe),
+                                                out.data_ptr(), nat.dtype_code(out_dtype), x_f32, nat.stream_ptr(x.device)),
+                      "rajni_pool_norm")
+        else:
+            nat.check(nat.lib().rajni_pool_norm_prefix(x.data_ptr(), B, N, int(num_prefix), Cc, pk,
+                                                       nat.ptr(nw), nat.ptr(nb), float(ne), nat.ptr(fw), nat.ptr(fb), float(fe),
+                                                       out.data_ptr(), nat.dtype_code(out_dtype), x_f32,
+                                                       nat.stream_ptr(x.device)), "rajni_pool_norm_prefix")
     return out
 
 
@@ -334,11 +359,18 @@ def linear(x: torch.Tensor, w_packed: torch.Tensor, n_out: int, bias: Optional[t
 
 def patch_embed(images: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, cls: torch.Tensor,
                 pos: torch.Tensor, pos_has_cls: bool, patch: int, embed_dim: int,
-                out_f32: bool = False) -> torch.Tensor:
+                out_f32: bool = False, reg: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """images [B, Cin, S, S] -> x [B, P + (S/patch)^2, C]: CLS, the R = P - 1 register tokens `reg` ([R, C] in the images'
+    dtype, None = no registers), then the patches; `pos` has (P if pos_has_cls else 0) + (S/patch)^2 rows."""
     nat.require_device(images, "images")
     images = images.contiguous()
     B, Cin, S, _ = images.shape
-    n = (S // patch) ** 2 + 1
+    if reg is not None:
+        if reg.dim() != 2 or reg.shape[1] != embed_dim or reg.shape[0] < 1 or reg.dtype != images.dtype:
+            raise ValueError(f"patch_embed: reg must be [R, {embed_dim}] in the images' dtype, got {tuple(reg.shape)} {reg.dtype}")
+        reg = reg.contiguous()
+    P = 1 + (reg.shape[0] if reg is not None else 0)
+    n = (S // patch) ** 2 + P
     x = torch.empty((B, n, embed_dim), dtype=torch.float32 if out_f32 else images.dtype, device=images.device)
     kpad = (Cin * patch * patch + 63) // 64 * 64
     if w_packed.shape[1] != kpad:
@@ -346,8 +378,14 @@ def patch_embed(images: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor
     nbytes = nat.lib().rajni_patch_embed_workspace_bytes(B, Cin, S, patch, _dt(images))   # 0: im2col fused into the loads
     ws = torch.empty(nbytes, dtype=torch.uint8, device=images.device) if nbytes else None
     with nat.device_guard(images.device):
-        nat.check(nat.lib().rajni_patch_embed(images.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), cls.data_ptr(),
-                                              pos.data_ptr(), int(pos_has_cls), x.data_ptr(), int(out_f32), B, Cin, S, patch,
-                                              embed_dim, _dt(images), nat.ptr(ws), nbytes, nat.stream_ptr(images.device)),
-                  "rajni_patch_embed")
+        if reg is None:
+            nat.check(nat.lib().rajni_patch_embed(images.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), cls.data_ptr(),
+                                                  pos.data_ptr(), int(pos_has_cls), x.data_ptr(), int(out_f32), B, Cin, S, patch,
+                                                  embed_dim, _dt(images), nat.ptr(ws), nbytes, nat.stream_ptr(images.device)),
+                      "rajni_patch_embed")
+        else:
+            nat.check(nat.lib().rajni_patch_embed_prefix(images.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), cls.data_ptr(),
+                                                         reg.data_ptr(), P, pos.data_ptr(), int(pos_has_cls), x.data_ptr(),
+                                                         int(out_f32), B, Cin, S, patch, embed_dim, _dt(images), nat.ptr(ws),
+                                                         nbytes, nat.stream_ptr(images.device)), "rajni_patch_embed_prefix")
     return x

@@ -6,6 +6,8 @@ timm is not installed in the build/bench images, and the reference wrapper
 
   base : .patch_embed(x)->[B,N-1,C]  .cls_token [1,1,C]  .pos_embed [1,N,C]
          .pos_drop  .blocks  .norm  .head
+         (+ timm's optional .reg_token [1,R,C] / .num_prefix_tokens = 1 + R: register tokens behind the
+          class token, which the reference does not handle and RAJNIViTWrapper does)
   block: .norm1 .attn .norm2 .mlp  (+ optional .ls1 .ls2 .drop_path1 .drop_path2), blk(x)
   attn : .num_heads .scale .qkv (Linear C->3C laid out [3][H][D]) .proj .proj_drop
 
@@ -50,6 +52,11 @@ class ViTConfig:
     pre_norm: bool = False                # norm_pre after the pos-embed (CLIP-derived ViTs)
     global_pool: str = "token"            # 'token' (x[:, 0]) or 'avg' (mean of x[:, 1:])
     fc_norm: Optional[bool] = None        # None = timm's default: an fc_norm (and no final norm) iff global_pool == 'avg'
+    reg_tokens: int = 0                   # register tokens behind the class token (timm reg_tokens; DINOv2 "reg4": 4)
+
+    @property
+    def num_prefix_tokens(self) -> int:
+        return 1 + self.reg_tokens
 
     @property
     def use_fc_norm(self) -> bool:
@@ -113,6 +120,22 @@ CONFIGS: Dict[str, ViTConfig] = {
     "vit_micro512_qknorm_patch16_64": ViTConfig(img_size=64, embed_dim=512, depth=4, num_heads=8, num_classes=10, qk_norm=True),
     "vit_micro_d80_qknorm_patch16_64": ViTConfig(img_size=64, embed_dim=320, depth=4, num_heads=4, num_classes=10,
                                                  qk_norm=True, global_pool="avg"),
+    # ---- register tokens (timm reg_tokens=R: token order [cls, reg_0 .. reg_{R-1}, patches]) ----
+    # class token + 4 registers, a pos-embed with a row for every prefix token (not timm names)
+    "vit_micro_reg4_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, num_classes=10, reg_tokens=4),
+    # the same with no_embed_class (pos-embed on the patch rows only) and LayerScale: the DINOv2 / DeiT-3 layout
+    "deit3_micro_reg4_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, num_classes=10,
+                                             layer_scale=1e-6, no_embed_class=True, reg_tokens=4),
+    # one register, patch 14 (materialised patch columns), 'avg' pool over the patch rows behind both prefix tokens
+    "vit_micro_reg1_gap_patch14_56": ViTConfig(img_size=56, patch_size=14, embed_dim=128, depth=4, num_heads=2, num_classes=10,
+                                               global_pool="avg", reg_tokens=1),
+    # registers on the fp8-capable micro model
+    "vit_micro512_reg4_patch16_64": ViTConfig(img_size=64, embed_dim=512, depth=4, num_heads=8, num_classes=10, reg_tokens=4),
+    # timm `vit_small_patch14_reg4_dinov2` dimensions (DINOv2 ViT-S/14 with 4 registers: no_embed_class, LayerScale) at
+    # img_size 224 = 261 tokens.  The pretrained size 518 gives 1374 tokens, more than the score/select kernel's LDS holds
+    # today (it refuses with an LDS error): out of scope here - run the checkpoint at 224 with an interpolated pos-embed.
+    "vit_small_patch14_reg4_dinov2": ViTConfig(img_size=224, patch_size=14, embed_dim=384, depth=12, num_heads=6,
+                                               layer_scale=1e-5, no_embed_class=True, reg_tokens=4),
 }
 
 
@@ -201,11 +224,13 @@ class VisionTransformer(nn.Module):
         self.cfg = cfg
         self.num_classes = cfg.num_classes
         self.embed_dim = cfg.embed_dim
-        self.num_prefix_tokens = 1
+        self.num_prefix_tokens = cfg.num_prefix_tokens
+        self.num_reg_tokens = cfg.reg_tokens
         self.no_embed_class = cfg.no_embed_class
         self.patch_embed = PatchEmbed(cfg)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, cfg.embed_dim))
-        n_pos = cfg.num_patches if cfg.no_embed_class else cfg.num_patches + 1
+        self.reg_token = nn.Parameter(torch.zeros(1, cfg.reg_tokens, cfg.embed_dim)) if cfg.reg_tokens else None
+        n_pos = cfg.num_patches if cfg.no_embed_class else cfg.num_patches + cfg.num_prefix_tokens
         self.pos_embed = nn.Parameter(torch.zeros(1, n_pos, cfg.embed_dim))
         self.pos_drop = nn.Dropout(0.0)
         if cfg.global_pool not in ("token", "avg"):
@@ -220,11 +245,14 @@ class VisionTransformer(nn.Module):
         self.head = nn.Linear(cfg.embed_dim, cfg.num_classes)
 
     def _pos_embed(self, x):
-        cls = self.cls_token.expand(x.shape[0], -1, -1)
+        # timm: prefix tokens [cls, reg...] in front; the pos-embed covers them unless no_embed_class
+        prefix = [self.cls_token.expand(x.shape[0], -1, -1)]
+        if self.reg_token is not None:
+            prefix.append(self.reg_token.expand(x.shape[0], -1, -1))
         if self.no_embed_class:
-            x = torch.cat([cls, x + self.pos_embed], dim=1)
+            x = torch.cat(prefix + [x + self.pos_embed], dim=1)
         else:
-            x = torch.cat([cls, x], dim=1) + self.pos_embed
+            x = torch.cat(prefix + [x], dim=1) + self.pos_embed
         return self.pos_drop(x)
 
     def forward_features(self, x):
@@ -260,7 +288,7 @@ def synth_state_dict(cfg: ViTConfig, seed: int = 0, std: float = 0.02,
 
     sd: Dict[str, np.ndarray] = {}
     sd["cls_token"] = nrm(1, 1, C)
-    n_pos = cfg.num_patches if cfg.no_embed_class else cfg.num_patches + 1
+    n_pos = cfg.num_patches if cfg.no_embed_class else cfg.num_patches + cfg.num_prefix_tokens
     sd["pos_embed"] = nrm(1, n_pos, C)
     fan_in = cfg.in_chans * P * P
     sd["patch_embed.proj.weight"] = nrm(C, cfg.in_chans, P, P, s=1.0 / math.sqrt(fan_in))
@@ -302,6 +330,8 @@ def synth_state_dict(cfg: ViTConfig, seed: int = 0, std: float = 0.02,
             ln(f"blocks.{i}.attn.k_norm", cfg.head_dim)
     if cfg.use_fc_norm:
         ln("fc_norm", C)
+    if cfg.reg_tokens:      # after every other draw: only pos_embed's row count differs from the register-free config
+        sd["reg_token"] = nrm(1, cfg.reg_tokens, C)
     return sd
 
 

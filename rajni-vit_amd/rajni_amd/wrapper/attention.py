@@ -55,6 +55,9 @@ class RAJNIAttention(nn.Module):
         self.k_norm = qk[1] if qk else getattr(attn, "k_norm", None) or nn.Identity()
         self.keep_ratio = keep_ratio
         self.update = update
+        # prefix tokens at the front of x (CLS + timm register tokens): always kept, never ranked.  RAJNIViTWrapper sets it
+        # from the base model; 1 = the reference's single class token
+        self.num_prefix_tokens = 1
         self._packed = None
         self._packed_key = None
 
@@ -81,18 +84,19 @@ class RAJNIAttention(nn.Module):
     @torch.no_grad()
     def forward(self, x: torch.Tensor, prev_scores: Optional[torch.Tensor] = None):
         """x: [B, N, C] (already normed).  Returns out [B, Np, C], keep_idx [B, Np] int64,
-        next_scores [B, Np]."""
+        next_scores [B, Np]; Np = num_prefix_tokens + keep."""
         nat.require_device(x, "x")
         B, N, Cc = x.shape
         w = self._weights(x.device, x.dtype)
         qkv = ops.linear(x, w["qkv_w"], 3 * Cc, w["qkv_b"], nat.EPI_BIAS)            # attention.py:21-22
         if "q_w" in w:                                                                # timm: q, k = q_norm(q), k_norm(k)
             ops.qk_norm(qkv, self.num_heads, w["q_w"], w["q_b"], w["k_w"], w["k_b"], w["qk_eps"])
-        keep = ops.keep_count(self.keep_ratio, N)                                     # attention.py:31-32
+        P = int(getattr(self, "num_prefix_tokens", 1))
+        keep = ops.keep_count(self.keep_ratio, N, P)                                  # attention.py:31-32
         if self.update or prev_scores is None:                                        # attention.py:25-28
-            _, keep_idx, next_scores = ops.score_select(qkv, self.num_heads, keep, want_scores=False)
+            _, keep_idx, next_scores = ops.score_select(qkv, self.num_heads, keep, want_scores=False, num_prefix=P)
         else:
-            keep_idx, next_scores = ops.select_topk(prev_scores.to(x.dtype), keep)    # attention.py:34-39,58
+            keep_idx, next_scores = ops.select_topk(prev_scores.to(x.dtype), keep, num_prefix=P)   # attention.py:34-39,58
         out = ops.attention(qkv, keep_idx, self.num_heads, self.scale)                # attention.py:42-54
         out = ops.linear(out, w["proj_w"], Cc, w["proj_b"], nat.EPI_BIAS)             # attention.py:55
         if isinstance(self.proj_drop, nn.Dropout) and self.proj_drop.p > 0 and self.training:

@@ -6,7 +6,8 @@ blocks get a `RAJNIAttention`, every block gets `has_pruner`; model.py:12-23), p
 `forward(images) -> logits`, `get_last_stats() -> {"token_counts": [...]}` (None before the first
 forward).  Deliberate fixes: schedule keys are normalised to int (B1: a JSON-loaded
 schedule prunes), a `no_embed_class` pos-embed works (B3), and timm's `qk_norm`, `pre_norm`, `global_pool='avg'`
-and `fc_norm` options are computed as timm computes them instead of being dropped (B4).
+and `fc_norm` options are computed as timm computes them instead of being dropped (B4), and so are
+timm's register tokens (`reg_tokens=R`: `reg_token` [1, R, C] behind the class token, never pruned, never ranked).
 
 Not kept: the Python per-block loop.  `forward` builds (once per batch shape) a `rajni_vit_plan`
 - packed weights, workspace, per-stage index buffers - and calls `rajni_vit_forward`, which enqueues
@@ -34,14 +35,40 @@ def normalise_schedule(schedule) -> Dict[int, Dict]:
     return out
 
 
-def plan_token_counts(n0: int, depth: int, schedule: Dict[int, Dict]) -> List[int]:
-    """Tokens at the entry of every block (model.py:43) - a pure function of (N0, depth, schedule)."""
+def plan_token_counts(n0: int, depth: int, schedule: Dict[int, Dict], num_prefix: int = 1) -> List[int]:
+    """Tokens at the entry of every block (model.py:43) - a pure function of (N0, depth, schedule, prefix tokens); every
+    count includes the `num_prefix` prefix tokens, which are never dropped."""
     counts, n = [], n0
     for i in range(depth):
         counts.append(n)
         if i in schedule:
-            n = ops.keep_count(schedule[i]["keep_ratio"], n) + 1
+            n = ops.keep_count(schedule[i]["keep_ratio"], n, num_prefix) + num_prefix
     return counts
+
+
+def model_num_prefix(m: nn.Module) -> int:
+    """P = 1 + R prefix tokens the base model's PARAMETERS supply: `cls_token` and `reg_token` [1, R, C] (timm reg_tokens=R).
+    Raises NotImplementedError for what the native forward does not compute (no class token, distillation token, a
+    malformed or oversized register set, a declared `num_prefix_tokens` that disagrees)."""
+    cls = getattr(m, "cls_token", None)
+    if cls is None:
+        raise NotImplementedError("RAJNIViTWrapper: the model has no cls_token (class_token=False): the class token is the "
+                                  "importance query and is required")
+    if getattr(m, "dist_token", None) is not None or getattr(m, "head_dist", None) is not None:
+        raise NotImplementedError("RAJNIViTWrapper: distillation token / head_dist (DeiT distilled) are not supported")
+    reg = getattr(m, "reg_token", None)
+    P = 1
+    if reg is not None:
+        if reg.dim() != 3 or reg.shape[0] != 1 or reg.shape[1] < 1 or reg.shape[2] != cls.shape[-1]:
+            raise NotImplementedError(f"RAJNIViTWrapper: reg_token must be [1, R, {cls.shape[-1]}] with R >= 1, got {tuple(reg.shape)}")
+        P = 1 + int(reg.shape[1])
+    declared = getattr(m, "num_prefix_tokens", P)
+    if declared != P:
+        raise NotImplementedError(f"RAJNIViTWrapper: the model declares {declared} prefix tokens but its parameters supply {P} "
+                                  "(cls_token + reg_token); distillation or other prefix tokens are not supported")
+    if P > nat.MAX_PREFIX:
+        raise NotImplementedError(f"RAJNIViTWrapper: {P} prefix tokens; at most {nat.MAX_PREFIX} are supported")
+    return P
 
 
 class RAJNIViTWrapper(nn.Module):
@@ -51,6 +78,10 @@ class RAJNIViTWrapper(nn.Module):
         self.blocks = base_model.blocks
         self.pruning_schedule = normalise_schedule(pruning_schedule)
 
+        try:                       # block-level use of RAJNIAttention keeps the registers too; check_supported() reports problems
+            prefix = model_num_prefix(base_model)
+        except NotImplementedError:
+            prefix = 1
         for i, blk in enumerate(self.blocks):
             if i in self.pruning_schedule:
                 cfg = self.pruning_schedule[i]
@@ -58,6 +89,7 @@ class RAJNIViTWrapper(nn.Module):
                     blk.attn = RAJNIAttention(blk.attn, keep_ratio=cfg["keep_ratio"], update=cfg["update"])
                 else:  # re-wrapping an already wrapped base
                     blk.attn.keep_ratio, blk.attn.update = cfg["keep_ratio"], cfg["update"]
+                blk.attn.num_prefix_tokens = prefix
                 blk.has_pruner = True
             else:
                 blk.has_pruner = False
@@ -87,8 +119,8 @@ class RAJNIViTWrapper(nn.Module):
         return self._last_stats
 
     def get_last_trace(self) -> Dict[int, Dict[str, torch.Tensor]]:
-        """Per scheduled block: keep_idx [B,Np] int64, next_scores [B,Np] and (if enabled with
-        `trace_scores(True)`) the full scores [B,N] the stage ranked.  Test/diagnostic surface."""
+        """Per scheduled block: keep_idx [B,Np] int64, next_scores [B,Np] (Np = prefix tokens + keep) and (if enabled
+        with `trace_scores(True)`) the full scores [B,N] the stage ranked.  Test/diagnostic surface."""
         if self._plan is None:
             return {}
         out = {}
@@ -174,7 +206,8 @@ class RAJNIViTWrapper(nn.Module):
 
     def force_keep_idx(self, forced: Optional[Dict[int, torch.Tensor]]):
         """Test hook for selection-conditional parity: use the given keep_idx
-        ([B, keep+1], CLS first, ascending) in the listed blocks instead of the device selection."""
+        ([B, P+keep]: the P prefix tokens 0..P-1 first - P = 1, the class token, without register tokens - then
+        ascending patch indices) in the listed blocks instead of the device selection."""
         self._forced = {}
         for k, v in (forced or {}).items():
             self._forced[int(k)] = v.to(torch.int32).contiguous()
@@ -196,6 +229,7 @@ class RAJNIViTWrapper(nn.Module):
 
     def _describe(self):
         m = self.m
+        num_prefix = model_num_prefix(m)
         pe = m.patch_embed.proj
         if not isinstance(pe, nn.Conv2d) or pe.kernel_size != pe.stride or pe.kernel_size[0] != pe.kernel_size[1]:
             raise NotImplementedError("RAJNIViTWrapper: patch_embed.proj must be a square Conv2d with stride == kernel")
@@ -235,9 +269,12 @@ class RAJNIViTWrapper(nn.Module):
         desc["pool"] = self._pool_kind()
         if getattr(m, "attn_pool", None) is not None:
             raise NotImplementedError("RAJNIViTWrapper: attn_pool (global_pool='map') is not supported")
-        if getattr(m, "num_prefix_tokens", 1) != 1 or getattr(m, "reg_token", None) is not None:
-            raise NotImplementedError(f"RAJNIViTWrapper: {getattr(m, 'num_prefix_tokens', 1)} prefix tokens (register / distillation "
-                                      "tokens) are not supported: exactly one class token")
+        # prefix tokens: the class token plus timm's register tokens (never pruned, never ranked; 'avg' pools behind them)
+        desc["num_prefix"] = num_prefix
+        n_patches = getattr(m.patch_embed, "num_patches", None)
+        if num_prefix > 1 and isinstance(n_patches, int) and m.pos_embed.shape[-2] not in (n_patches, n_patches + num_prefix):
+            raise NotImplementedError(f"RAJNIViTWrapper: pos_embed has {m.pos_embed.shape[-2]} rows; with {num_prefix} prefix tokens "
+                                      f"and {n_patches} patches it must have {n_patches} (no_embed_class) or {n_patches + num_prefix}")
         fc_norm = getattr(m, "fc_norm", None)
         desc["fc_norm"] = fc_norm is not None and not isinstance(fc_norm, nn.Identity)
         desc["norm"] = not isinstance(m.norm, nn.Identity)
@@ -315,6 +352,8 @@ class RAJNIViTWrapper(nn.Module):
         W["patch_w"] = ops.pack_weight(m.patch_embed.proj.weight, dtype, device, k_multiple=64)
         W["patch_b"] = pv(m.patch_embed.proj.bias) if m.patch_embed.proj.bias is not None else zeros(desc["C"])
         W["cls"] = m.cls_token.detach().to(device=device, dtype=dtype).reshape(-1).contiguous()
+        W["reg"] = (m.reg_token.detach().to(device=device, dtype=dtype).reshape(-1, desc["C"]).contiguous()
+                    if desc["num_prefix"] > 1 else None)
         W["pos"] = m.pos_embed.detach().to(device=device, dtype=dtype).reshape(-1, desc["C"]).contiguous()
         W["norm_w"], W["norm_b"] = (pv(m.norm.weight), pv(m.norm.bias)) if desc["norm"] else (None, None)
         if desc["norm"] and W["norm_b"] is None:
@@ -383,8 +422,9 @@ class RAJNIViTWrapper(nn.Module):
     def _build_plan(self, B: int, S: int, device, dtype):
         W = self._pack_weights(device, dtype)
         d = W["desc"]
+        P = d["num_prefix"]
         key = (B, S, device, dtype, self._weights_key, tuple(sorted(self._forced)), self._trace_scores, self._resid_bf16,
-               self._cls_only_last)
+               self._cls_only_last, P)
         if self._plan is not None and self._plan[0] == key:
             return self._plan
         if key in self._plans:
@@ -392,15 +432,15 @@ class RAJNIViTWrapper(nn.Module):
             return self._plan
         if S % d["patch"] != 0:
             raise ValueError(f"image size {S} is not a multiple of the patch size {d['patch']}")
-        n0 = (S // d["patch"]) ** 2 + 1
+        n0 = (S // d["patch"]) ** 2 + P
         pos_rows = W["pos"].shape[0]
-        if pos_rows >= n0:
-            pos_has_cls = 1      # reference: x + pos_embed[:, :N]  (model.py:37)
-        elif pos_rows == n0 - 1:
-            pos_has_cls = 0      # timm no_embed_class
+        if pos_rows == n0 or (P == 1 and pos_rows > n0):
+            pos_has_cls = 1      # reference: x + pos_embed[:, :N]  (model.py:37); timm: a row for every prefix token too
+        elif pos_rows == n0 - P:
+            pos_has_cls = 0      # timm no_embed_class: the prefix rows get no pos-embed
         else:
-            raise ValueError(f"pos_embed has {pos_rows} rows but the input yields {n0} tokens")
-        counts = plan_token_counts(n0, d["depth"], self.pruning_schedule)
+            raise ValueError(f"pos_embed has {pos_rows} rows but the input yields {n0} tokens ({P} of them prefix tokens)")
+        counts = plan_token_counts(n0, d["depth"], self.pruning_schedule, P)
 
         blocks = (nat.Block * d["depth"])()
         bufs: Dict[int, Dict[str, Optional[torch.Tensor]]] = {}
@@ -415,11 +455,11 @@ class RAJNIViTWrapper(nn.Module):
             if i in self.pruning_schedule:
                 cfg = self.pruning_schedule[i]
                 N = counts[i]
-                keep = ops.keep_count(cfg["keep_ratio"], N)
-                if keep > N - 1:
+                keep = ops.keep_count(cfg["keep_ratio"], N, P)
+                if keep > N - P:
                     raise ValueError(f"block {i}: keep_ratio {cfg['keep_ratio']} > 1 selects more tokens than exist")
-                kb = dict(keep_idx=torch.empty((B, keep + 1), dtype=torch.int32, device=device),
-                          next_scores=torch.empty((B, keep + 1), dtype=dtype, device=device),
+                kb = dict(keep_idx=torch.empty((B, keep + P), dtype=torch.int32, device=device),
+                          next_scores=torch.empty((B, keep + P), dtype=dtype, device=device),
                           scores=torch.empty((B, N), dtype=dtype, device=device) if self._trace_scores else None)
                 bufs[i] = kb
                 cb.keep, cb.update = keep, int(cfg["update"])
@@ -427,8 +467,10 @@ class RAJNIViTWrapper(nn.Module):
                     nat.ptr(kb["scores"])
                 if i in self._forced:
                     f = self._forced[i].to(device)
-                    if tuple(f.shape) != (B, keep + 1):
-                        raise ValueError(f"forced keep_idx for block {i} has shape {tuple(f.shape)}, want {(B, keep + 1)}")
+                    if tuple(f.shape) != (B, keep + P):
+                        raise ValueError(f"forced keep_idx for block {i} has shape {tuple(f.shape)}, want {(B, keep + P)}")
+                    if P > 1 and not bool((f[:, :P].cpu() == torch.arange(P, dtype=torch.int32)).all()):
+                        raise ValueError(f"forced keep_idx for block {i}: slots 0..{P - 1} must hold the prefix tokens 0..{P - 1}")
                     self._forced[i] = f
                     cb.forced_keep_idx = f.data_ptr()
             else:
@@ -451,7 +493,12 @@ class RAJNIViTWrapper(nn.Module):
         plan.resid_bf16 = int(self._resid_bf16)
         plan.cls_only_last_block = int(self._cls_only_last)
         plan.act_fp8 = int(self._weight_format == "fp8_mfma")
-        nbytes = nat.lib().rajni_vit_workspace_bytes(C.byref(plan))
+        pre = None
+        if P > 1:           # the prefix record beside the plan (rajni_vit_prefix); None: CLS only, the entry points as ever
+            pre = nat.VitPrefix()
+            pre.num_prefix, pre.reg_token = P, W["reg"].data_ptr()
+        nbytes = (nat.lib().rajni_vit_workspace_bytes(C.byref(plan)) if pre is None
+                  else nat.lib().rajni_vit_workspace_bytes_prefix(C.byref(plan), C.byref(pre)))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
         plan.workspace, plan.workspace_bytes = ws.data_ptr(), nbytes
         ext = qk = None
@@ -470,7 +517,7 @@ class RAJNIViTWrapper(nn.Module):
             ext.norm_absent = int(not d["norm"])
             ext.pool = nat.POOL_AVG if d["pool"] == "avg" else nat.POOL_TOKEN
         # W: a stale optimistic launch keeps its weights alive
-        self._plan = (key, plan, (blocks, tc, ws, W, ext, qk), bufs, counts)
+        self._plan = (key, plan, (blocks, tc, ws, W, ext, qk, pre), bufs, counts)
         if len(self._plans) >= 4:     # workspaces are large: keep only a few batch shapes alive
             self._plans.pop(next(iter(self._plans)))
         self._plans[key] = self._plan
@@ -496,8 +543,12 @@ class RAJNIViTWrapper(nn.Module):
             def launch(entry):
                 plan = entry[1]
                 out = torch.empty((B, plan.logits_ld), dtype=dtype, device=x.device)
-                ext = entry[2][4]
-                if ext is None:
+                ext, pre = entry[2][4], entry[2][6]
+                if pre is not None:
+                    nat.check(nat.lib().rajni_vit_forward_ext_prefix(C.byref(plan), C.byref(ext) if ext is not None else None,
+                                                                     C.byref(pre), x.data_ptr(), out.data_ptr(),
+                                                                     nat.stream_ptr(x.device)), "rajni_vit_forward_ext_prefix")
+                elif ext is None:
                     nat.check(nat.lib().rajni_vit_forward(C.byref(plan), x.data_ptr(), out.data_ptr(),
                                                           nat.stream_ptr(x.device)), "rajni_vit_forward")
                 else:
