@@ -327,6 +327,25 @@ size_t rajni_vit_workspace_bytes_prefix(const rajni_vit_plan* plan, const rajni_
 int rajni_vit_forward_ext_prefix(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
                                  const void* images, void* logits, rajni_stream_t stream);
 
+/* ---- importance scores beyond one workgroup's LDS (high-resolution inputs) ----
+ * rajni_importance / rajni_score_select[_prefix] run one workgroup per image with the logits [H][N] and the head-mean
+ * values [N][D] in LDS, and refuse (RAJNI_ERR_UNSUPPORTED) what 160 KiB cannot hold: about 600 tokens at head dim 64, 475
+ * at 80, 300 at 128.  Larger shapes are scored by a tile kernel (grid: 32-token tiles x B) and a one-workgroup-per-image
+ * finish kernel that pass fp32 logits, head-mean values and per-tile partial sums through caller-provided scratch - two
+ * launches, no host synchronisation, capturable.  All sums are fixed trees in tile order: an image's scores do not depend
+ * on B or on its place in the batch.  They meet the same error budget as the single-workgroup kernel's but are not bit-equal
+ * to them (the summation orders differ).  The tiled path takes N <= 16416 (16384 patch tokens + RAJNI_MAX_PREFIX), every supported head dim and dtype.
+ *
+ * rajni_score_select_workspace_bytes: host only; 0 for every shape the single-workgroup kernel holds (and for shapes no
+ * path takes: those are refused by the call itself).
+ * rajni_score_select_ws: rajni_score_select_prefix with that scratch (256-byte aligned; may be NULL when the size is 0, and
+ * then the call IS rajni_score_select_prefix / rajni_importance: same kernel, same bits).  keep == 0 computes scores only
+ * (scores_out required; keep_idx / next_scores may be NULL); with keep >= 1 scores_out may be NULL. */
+size_t rajni_score_select_workspace_bytes(int B, int N, int H, int D, int dtype);
+int rajni_score_select_ws(const void* qkv, int B, int N, int H, int D, float eps, int num_prefix, int keep,
+                          void* scores_out, int32_t* keep_idx, void* next_scores, int dtype, void* workspace,
+                          size_t workspace_bytes, rajni_stream_t stream);
+
 /* ---- measurement hooks (bench.py roofline): HIP-event timing per kernel class on the launch
  * stream.  mask bit i enables class i; classes listed by rajni_profile_class_name(). ---- */
 enum { RAJNI_NUM_KCLASS = 17 };

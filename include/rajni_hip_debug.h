@@ -33,6 +33,11 @@ void rajni_debug_set_gemm_nblock_bytes(int bytes);
  * needs) even when the one-pass layout fits; 0 = default.  Scores are bit-identical either way (tested). */
 void rajni_debug_force_score_two_pass(int on);
 
+/* score+select: 1 = rajni_score_select_workspace_bytes asks for scratch and rajni_score_select_ws (and the whole forward)
+ * takes the tiled kernels for EVERY shape, also those one workgroup holds; 0 = default.  Entry points without scratch are
+ * not affected. */
+void rajni_debug_force_score_tiled(int on);
+
 /* diagnostic builds (-DRAJNI_GEMM_STAMPS / -DRAJNI_ATTN_STAMPS / -DRAJNI_SS_STAMPS) only: device buffer receiving
  * 4 x uint64 s_memtime stamps per workgroup; NULL disables */
 void rajni_debug_set_gemm_stamps(void* buf);

@@ -157,6 +157,30 @@ int rajni_score_select_prefix(const void* qkv, int B, int N, int H, int D, float
                              (hipStream_t)stream, num_prefix);
 }
 
+int rajni_score_select_ws(const void* qkv, int B, int N, int H, int D, float eps, int num_prefix, int keep,
+                          void* scores_out, int32_t* keep_idx, void* next_scores, int dtype, void* workspace,
+                          size_t workspace_bytes, rajni_stream_t stream) {
+  NEED_DTYPE("rajni_score_select_ws");
+  RAJNI_REQUIRE(qkv != nullptr, RAJNI_ERR_INVALID, "rajni_score_select_ws: qkv is null");
+  RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
+                "rajni_score_select_ws: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
+  RAJNI_REQUIRE(B > 0 && N >= num_prefix + 1, RAJNI_ERR_INVALID,
+                "rajni_score_select_ws: need B > 0 and at least one patch token (B=%d N=%d num_prefix=%d)", B, N, num_prefix);
+  RAJNI_REQUIRE(keep >= 0 && keep <= N - num_prefix, RAJNI_ERR_INVALID,
+                "rajni_score_select_ws: keep must be 0 (scores only) or 1..%d (%d)", N - num_prefix, keep);
+  RAJNI_REQUIRE(keep == 0 || keep_idx != nullptr, RAJNI_ERR_INVALID, "rajni_score_select_ws: keep_idx is null with keep=%d", keep);
+  RAJNI_REQUIRE(keep > 0 || scores_out != nullptr, RAJNI_ERR_INVALID, "rajni_score_select_ws: scores_out is null with keep=0");
+  const size_t need = rajni_score_select_workspace_bytes(B, N, H, D, dtype);
+  RAJNI_REQUIRE(need == 0 || workspace != nullptr, RAJNI_ERR_INVALID,
+                "rajni_score_select_ws: workspace is null but N=%d H=%d D=%d needs %zu B (rajni_score_select_workspace_bytes)", N, H, D, need);
+  RAJNI_REQUIRE(workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, RAJNI_ERR_INVALID,
+                "rajni_score_select_ws: workspace must be 256-byte aligned");
+  RAJNI_REQUIRE(workspace_bytes >= need, RAJNI_ERR_INVALID,
+                "rajni_score_select_ws: workspace_bytes=%zu but N=%d H=%d D=%d needs %zu B", workspace_bytes, N, H, D, need);
+  return launch_score_select(qkv, nullptr, B, N, H, D, eps, keep, scores_out, keep_idx, next_scores, dtype,
+                             (hipStream_t)stream, num_prefix, need ? workspace : nullptr, need ? workspace_bytes : 0);
+}
+
 int rajni_gather_rows(const void* src, const int32_t* idx, void* dst, int B, int n_src, int n_dst,
                       int row_elems, int dtype, rajni_stream_t stream) {
   NEED_DTYPE("rajni_gather_rows");

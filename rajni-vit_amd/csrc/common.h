@@ -208,6 +208,11 @@ int launch_attention_cls(const void* qkv, void* out, int B, int N, int H, int D,
 int launch_score_select(const void* qkv, const void* scores_in, int B, int N, int H, int D,
                         float eps, int keep, void* scores_out, int32_t* keep_idx,
                         void* next_scores, int dtype, hipStream_t s, int num_prefix = 1);
+// ... with scratch of rajni_score_select_workspace_bytes(B, N, H, D, dtype) bytes (256-byte aligned; may be null when that
+// is 0): shapes beyond one workgroup's LDS are scored by the tiled kernels through it
+int launch_score_select(const void* qkv, const void* scores_in, int B, int N, int H, int D,
+                        float eps, int keep, void* scores_out, int32_t* keep_idx,
+                        void* next_scores, int dtype, hipStream_t s, int num_prefix, void* ws, size_t ws_bytes);
 int launch_gather_rows(const void* src, const int32_t* idx, void* dst, int B, int n_src, int n_dst,
                        int row_bytes, hipStream_t s);
 // variants.hip: the timm options of rajni_vit_ext (b pointers may be NULL = no bias; nw / fw NULL = that norm is absent)

@@ -17,6 +17,7 @@ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct Workspace {
   char *xa, *xb, *xn, *qkv, *att, *hid, *clsn, *scf, *cols;
+  char* sst; size_t sst_bytes;   // scratch of the tiled score kernels: zero bytes wherever one workgroup holds (n0, H, D)
   float *xs, *hs;          // act_fp8 plans: per-row scales of the e4m3 LayerNorm output / MLP hidden activations
   size_t total, cols_bytes;
 };
@@ -34,9 +35,12 @@ Workspace carve(const rajni_vit_plan& p, int P) {
   w.cols_bytes = patch_embed_workspace_bytes(p.B, p.in_chans, p.img_size, p.patch_size, p.dtype);   // 0 when fused
   const size_t ocols = take(w.cols_bytes);
   const size_t oxs = take(p.act_fp8 ? rows * sizeof(float) : 0), ohs = take(p.act_fp8 ? rows * sizeof(float) : 0);
+  w.sst_bytes = rajni_score_select_workspace_bytes(p.B, (int)n0, p.H, p.D, p.dtype);
+  const size_t osst = take(w.sst_bytes);
   char* base = (char*)p.workspace;
   w.xa = base + oxa; w.xb = base + oxb; w.xn = base + oxn; w.qkv = base + oqkv; w.att = base + oatt;
   w.hid = base + ohid; w.clsn = base + ocls; w.scf = base + oscf; w.cols = base + ocols;
+  w.sst = w.sst_bytes ? base + osst : nullptr;
   w.xs = reinterpret_cast<float*>(base + oxs); w.hs = reinterpret_cast<float*>(base + ohs);
   w.total = off;
   return w;
@@ -249,7 +253,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
         const void* full = carried;
         if (recompute) {
           void* dst = blk.scores ? blk.scores : (void*)w.scf;
-          rc = launch_score_select(w.qkv, nullptr, B, N, p.H, p.D, 1e-6f, 0, dst, nullptr, nullptr, dt, s);
+          rc = launch_score_select(w.qkv, nullptr, B, N, p.H, p.D, 1e-6f, 0, dst, nullptr, nullptr, dt, s, 1, w.sst, w.sst_bytes);
           if (rc != RAJNI_OK) return rc;
           full = dst;
         }
@@ -265,7 +269,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
       } else {
         if (recompute)
           rc = launch_score_select(w.qkv, nullptr, B, N, p.H, p.D, 1e-6f, blk.keep, blk.scores,
-                                   blk.keep_idx, blk.next_scores, dt, s, P);
+                                   blk.keep_idx, blk.next_scores, dt, s, P, w.sst, w.sst_bytes);
         else
           rc = launch_score_select(nullptr, carried, B, N, 0, 0, 0.f, blk.keep, nullptr,
                                    blk.keep_idx, blk.next_scores, dt, s, P);

@@ -83,6 +83,124 @@ __device__ __forceinline__ float group_sum(float v, int width) {
   return v;
 }
 
+// The selection tail both kernels share: rank the patch tokens of image b by the scores in `sc` [N] (already rounded to T)
+// and compact the kept ones.  `keys` (fp32 scores: N floats, read 16 bytes at a time, so up to 3 floats past N must be
+// readable) and `keys32` (16-bit scores: ss_key_words(N, P) words, 16-byte aligned) are LDS the caller no longer needs;
+// `wcount` holds SS_THREADS / 64 ints.  Called by all SS_THREADS threads of the workgroup, after a barrier behind `sc`.
+template <typename T>
+__device__ __forceinline__ void select_tail(const ScoreArgs& a, int b, float* sc, float* keys, unsigned* keys32, int* wcount) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int N = a.N;
+
+  // ---- rank patch tokens P..N-1, keep rank < keep, compact in ascending index order behind the P prefix slots
+  //      (attention.py:34-39: topk -> sort -> +1 -> prepend CLS; attention.py:58: carried scores)
+  const int keep = a.keep, P = a.P;
+  int* kout = a.keep_idx + (long)b * (keep + P);
+  T* nout = a.next_scores ? reinterpret_cast<T*>(a.next_scores) + (long)b * (keep + P) : nullptr;
+  int running = 0;
+  // tpt = 1, 2, 4 or 8 lanes share a token's rank count (each a slice of the j range, summed by shuffles): with
+  // 197 tokens one lane per token left 60 % of the workgroup idle through a 196-step loop
+  const int tpt = ss_tpt(N - P);
+  const int per_iter = SS_THREADS / tpt, sl = tid & (tpt - 1);
+  // The count loop is VALU bound (N^2 compares over 4 SIMDs: stamps put it at 14k of the kernel's 88k cycles at 197
+  // tokens, 95k of 297k at 577, when a compare was ~8 instructions: two range tests, >, ==, index test, or / and / add).
+  // 16-bit scores (bf16 and fp16): ONE unsigned compare per pair on a packed key
+  //     key32[j] = sortable16(score_j) << 16 | (0xFFFF - j)        (NaN = +inf, -0 = +0; N <= 65535)
+  // (sortable16 of the score's own 16-bit pattern: for bf16 that is the upper half of the fp32 pattern, for fp16 not)
+  // "j beats i" (larger score, or equal score and lower index - the defined tie rule) <=> key32[j] > key32[i], and the
+  // prefix slots and the padding hold 0 (below every real key), so slices need no range tests: v_cmp + add-with-carry.
+  // fp32 scores keep the float compare (the accuracy path).
+  constexpr bool PACKED = sizeof(T) == 2;
+  const int chunks = (N + 3) >> 2, cps = (chunks + tpt - 1) / tpt;   // 16-byte chunks of keys; per slice
+  const int cstride = cps | 1;     // slices an ODD number of chunks apart: the tpt broadcast reads of a step hit distinct banks
+  if constexpr (PACKED) {
+    for (int w = tid; w < cstride * tpt * 4; w += SS_THREADS) {
+      const int slw = w / (cstride * 4), off = w - slw * cstride * 4;
+      const int n = off < cps * 4 ? slw * cps * 4 + off : N;     // token of word w (padding words: none)
+      unsigned k = 0;
+      if (n >= P && n < N) {
+        if constexpr (__is_same(T, f16_t)) {
+          // fp16 scores: the upper half of the fp32 pattern would merge fp16 values that differ below bf16 precision,
+          // so the key is built from the fp16 pattern itself (exact: sc holds fp16 values; NaN -> +inf first)
+          unsigned u = __builtin_bit_cast(unsigned short, f2h(rank_key(sc[n])));
+          u = (u == 0x8000u) ? 0u : u;                              // -0 ranks as +0
+          u = (u & 0x8000u) ? (~u & 0xFFFFu) : (u | 0x8000u);       // monotone half -> unsigned
+          k = (u << 16) | (unsigned)(0xFFFF - n);
+        } else {   // bf16 scores: the upper half of the fp32 pattern is the bf16 pattern
+          unsigned u = __float_as_uint(rank_key(sc[n]));
+          u = (u == 0x80000000u) ? 0u : u;                            // -0 ranks as +0
+          u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);             // monotone float -> unsigned
+          k = (u & 0xFFFF0000u) | (unsigned)(0xFFFF - n);
+        }
+      }
+      keys32[w] = k;
+    }
+  } else {
+    for (int n = tid; n < N; n += SS_THREADS) keys[n] = rank_key(sc[n]);
+  }
+  __syncthreads();
+  SS_STAMP(7);
+  const int slice = (N - P + tpt - 1) / tpt;
+  for (int base_i = P; base_i < N; base_i += per_iter) {
+    const int i = base_i + tid / tpt;
+    const bool valid = i < N;
+    float si = 0.f;
+    int rank = 0;
+    if (valid) {
+      si = sc[i];
+      if constexpr (PACKED) {
+        const int si_ = i / (cps * 4);                                  // slice and word that hold token i's key
+        const unsigned ki = keys32[si_ * cstride * 4 + (i - si_ * cps * 4)];
+        const uint4* kp = reinterpret_cast<const uint4*>(keys32) + sl * cstride;
+#pragma unroll 4
+        for (int c = 0; c < cps; ++c) {
+          const uint4 k4 = kp[c];
+          rank += (k4.x > ki) + (k4.y > ki) + (k4.z > ki) + (k4.w > ki);
+        }
+      } else {
+        const float ki = keys[i];
+        const int j0 = P + sl * slice, j1 = j0 + slice < N ? j0 + slice : N;
+        // j beats i when its key is larger, or equal with a lower index (the defined tie rule)
+        auto beats = [&](float kj, int j) { return (j >= j0 && j < j1 && (kj > ki || (kj == ki && j < i))) ? 1 : 0; };
+#pragma unroll 4
+        for (int j = j0 & ~3; j < j1; j += 4) {    // aligned 16-byte reads; entries outside [j0, j1) are masked
+          const float4 k4 = *reinterpret_cast<const float4*>(keys + j);   // may run 3 floats into `sc`: masked
+          rank += beats(k4.x, j) + beats(k4.y, j + 1) + beats(k4.z, j + 2) + beats(k4.w, j + 3);
+        }
+      }
+    }
+    SS_STAMP(8);
+    if (tpt >= 2) rank += __shfl_xor(rank, 1, 64);
+    if (tpt >= 4) rank += __shfl_xor(rank, 2, 64);
+    if (tpt >= 8) rank += __shfl_xor(rank, 4, 64);
+    const bool kept = valid && sl == 0 && rank < keep;
+    const unsigned long long bal = __ballot(kept);
+    if (lane == 0) wcount[wave] = __popcll(bal);
+    __syncthreads();
+    SS_STAMP(9);
+    int prefix = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < SS_THREADS / 64; ++w) {
+      const int cnt = wcount[w];
+      prefix += (w < wave) ? cnt : 0;
+      total += cnt;
+    }
+    if (kept) {
+      const int pos = running + prefix + __popcll(bal & ((1ull << lane) - 1ull));
+      kout[P + pos] = i;
+      if (nout) st1(nout + P + pos, si);
+    }
+    running += total;
+    __syncthreads();
+    SS_STAMP(10);
+  }
+  if (tid < P) {   // the prefix slots: CLS and the register tokens, in place
+    kout[tid] = tid;
+    if (nout) st1(nout + tid, sc[tid]);
+  }
+  SS_STAMP(6);
+}
+
 // MERGED: logits and vbar have LDS regions of their own and K and V rows are read in ONE pass (a token's K and V
 // thirds are 3072 contiguous bytes of its 4608-byte qkv row, and no V load has to wait for the softmax statistics);
 // otherwise (N = 577 with 16 heads: 185 KiB would be needed) vbar reuses the logits' region after the statistics.
@@ -379,116 +497,8 @@ __global__ void __launch_bounds__(SS_THREADS) score_select_kernel(const ScoreArg
 
   SS_STAMP(5);
   if (a.keep <= 0) return;
-
-  // ---- rank patch tokens P..N-1, keep rank < keep, compact in ascending index order behind the P prefix slots
-  //      (attention.py:34-39: topk -> sort -> +1 -> prepend CLS; attention.py:58: carried scores)
-  const int keep = a.keep, P = a.P;
-  int* kout = a.keep_idx + (long)b * (keep + P);
-  T* nout = a.next_scores ? reinterpret_cast<T*>(a.next_scores) + (long)b * (keep + P) : nullptr;
-  int running = 0;
-  // tpt = 1, 2, 4 or 8 lanes share a token's rank count (each a slice of the j range, summed by shuffles): with
-  // 197 tokens one lane per token left 60 % of the workgroup idle through a 196-step loop
-  const int tpt = ss_tpt(N - P);
-  const int per_iter = SS_THREADS / tpt, sl = tid & (tpt - 1);
-  // The count loop is VALU bound (N^2 compares over 4 SIMDs: stamps put it at 14k of the kernel's 88k cycles at 197
-  // tokens, 95k of 297k at 577, when a compare was ~8 instructions: two range tests, >, ==, index test, or / and / add).
-  // 16-bit scores (bf16 and fp16): ONE unsigned compare per pair on a packed key
-  //     key32[j] = sortable16(score_j) << 16 | (0xFFFF - j)        (NaN = +inf, -0 = +0; N <= 65535)
-  // (sortable16 of the score's own 16-bit pattern: for bf16 that is the upper half of the fp32 pattern, for fp16 not)
-  // "j beats i" (larger score, or equal score and lower index - the defined tie rule) <=> key32[j] > key32[i], and the
-  // prefix slots and the padding hold 0 (below every real key), so slices need no range tests: v_cmp + add-with-carry.
-  // fp32 scores keep the float compare (the accuracy path).
-  constexpr bool PACKED = sizeof(T) == 2;
-  float* keys = acls;                                         // fp32 path: ranking keys (NaN = +inf), A_cls is dead
-  unsigned* keys32 = reinterpret_cast<unsigned*>(region);     // packed path: the logits' region is dead (>= ss_key_words(N, P) words)
-  const int chunks = (N + 3) >> 2, cps = (chunks + tpt - 1) / tpt;   // 16-byte chunks of keys; per slice
-  const int cstride = cps | 1;     // slices an ODD number of chunks apart: the tpt broadcast reads of a step hit distinct banks
-  if constexpr (PACKED) {
-    for (int w = tid; w < cstride * tpt * 4; w += SS_THREADS) {
-      const int slw = w / (cstride * 4), off = w - slw * cstride * 4;
-      const int n = off < cps * 4 ? slw * cps * 4 + off : N;     // token of word w (padding words: none)
-      unsigned k = 0;
-      if (n >= P && n < N) {
-        if constexpr (__is_same(T, f16_t)) {
-          // fp16 scores: the upper half of the fp32 pattern would merge fp16 values that differ below bf16 precision,
-          // so the key is built from the fp16 pattern itself (exact: sc holds fp16 values; NaN -> +inf first)
-          unsigned u = __builtin_bit_cast(unsigned short, f2h(rank_key(sc[n])));
-          u = (u == 0x8000u) ? 0u : u;                              // -0 ranks as +0
-          u = (u & 0x8000u) ? (~u & 0xFFFFu) : (u | 0x8000u);       // monotone half -> unsigned
-          k = (u << 16) | (unsigned)(0xFFFF - n);
-        } else {   // bf16 scores: the upper half of the fp32 pattern is the bf16 pattern
-          unsigned u = __float_as_uint(rank_key(sc[n]));
-          u = (u == 0x80000000u) ? 0u : u;                            // -0 ranks as +0
-          u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);             // monotone float -> unsigned
-          k = (u & 0xFFFF0000u) | (unsigned)(0xFFFF - n);
-        }
-      }
-      keys32[w] = k;
-    }
-  } else {
-    for (int n = tid; n < N; n += SS_THREADS) keys[n] = rank_key(sc[n]);
-  }
-  __syncthreads();
-  SS_STAMP(7);
-  const int slice = (N - P + tpt - 1) / tpt;
-  for (int base_i = P; base_i < N; base_i += per_iter) {
-    const int i = base_i + tid / tpt;
-    const bool valid = i < N;
-    float si = 0.f;
-    int rank = 0;
-    if (valid) {
-      si = sc[i];
-      if constexpr (PACKED) {
-        const int si_ = i / (cps * 4);                                  // slice and word that hold token i's key
-        const unsigned ki = keys32[si_ * cstride * 4 + (i - si_ * cps * 4)];
-        const uint4* kp = reinterpret_cast<const uint4*>(keys32) + sl * cstride;
-#pragma unroll 4
-        for (int c = 0; c < cps; ++c) {
-          const uint4 k4 = kp[c];
-          rank += (k4.x > ki) + (k4.y > ki) + (k4.z > ki) + (k4.w > ki);
-        }
-      } else {
-        const float ki = keys[i];
-        const int j0 = P + sl * slice, j1 = j0 + slice < N ? j0 + slice : N;
-        // j beats i when its key is larger, or equal with a lower index (the defined tie rule)
-        auto beats = [&](float kj, int j) { return (j >= j0 && j < j1 && (kj > ki || (kj == ki && j < i))) ? 1 : 0; };
-#pragma unroll 4
-        for (int j = j0 & ~3; j < j1; j += 4) {    // aligned 16-byte reads; entries outside [j0, j1) are masked
-          const float4 k4 = *reinterpret_cast<const float4*>(keys + j);   // may run 3 floats into `sc`: masked
-          rank += beats(k4.x, j) + beats(k4.y, j + 1) + beats(k4.z, j + 2) + beats(k4.w, j + 3);
-        }
-      }
-    }
-    SS_STAMP(8);
-    if (tpt >= 2) rank += __shfl_xor(rank, 1, 64);
-    if (tpt >= 4) rank += __shfl_xor(rank, 2, 64);
-    if (tpt >= 8) rank += __shfl_xor(rank, 4, 64);
-    const bool kept = valid && sl == 0 && rank < keep;
-    const unsigned long long bal = __ballot(kept);
-    if (lane == 0) wcount[wave] = __popcll(bal);
-    __syncthreads();
-    SS_STAMP(9);
-    int prefix = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < SS_THREADS / 64; ++w) {
-      const int cnt = wcount[w];
-      prefix += (w < wave) ? cnt : 0;
-      total += cnt;
-    }
-    if (kept) {
-      const int pos = running + prefix + __popcll(bal & ((1ull << lane) - 1ull));
-      kout[P + pos] = i;
-      if (nout) st1(nout + P + pos, si);
-    }
-    running += total;
-    __syncthreads();
-    SS_STAMP(10);
-  }
-  if (tid < P) {   // the prefix slots: CLS and the register tokens, in place
-    kout[tid] = tid;
-    if (nout) st1(nout + tid, sc[tid]);
-  }
-  SS_STAMP(6);
+  // A_cls and the logits' region are dead: they hold the ranking keys (fp32 / packed 16-bit; the region has >= ss_key_words(N, P) words)
+  select_tail<T>(a, b, sc, acls, reinterpret_cast<unsigned*>(region), wcount);
 }
 
 size_t ss_lds_bytes(int N, int H, int D, int P, bool merged) {
@@ -497,16 +507,365 @@ size_t ss_lds_bytes(int N, int H, int D, int P, bool merged) {
   return (C + region + 2 * (size_t)N + 2 * (size_t)H + SS_PART + D + 16 + SS_THREADS / 64) * sizeof(float);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The TILED form: shapes whose [H][N] logits and [N][D] head-mean values do not fit one workgroup's LDS.
+//   score_tile_kernel    grid (token tiles, B): a workgroup owns ST_TILE consecutive tokens, reads the CLS query row and its
+//                        tokens' K and V thirds once (16-byte loads) and writes, to the caller's scratch: fp32 logits
+//                        [B][H][N], fp32 vbar [B][N][D], the tile's column sums of vbar [B][tiles][D] and the tile's
+//                        per-head softmax statistics (max, sum exp) [B][tiles][H][2].
+//   score_finish_kernel  one workgroup per image: joins the tiles' statistics and column sums in tile order, computes
+//                        A_cls, the norms (vbar read back from the scratch: L2 resident), mu / std and the scores, then
+//                        runs select_tail.  Its LDS holds O(N) words - never [N][D].
+// Every sum is a fixed tree over a fixed order that depends on (N, H, D) alone: the same image gives the same bits at any
+// batch size and batch position.  The sums are not the single-workgroup kernel's, so the two paths agree within the
+// budget of the numerics tests and not bit for bit.
+constexpr int ST_TILE = 32;       // tokens per workgroup: a constant (never a function of B or the CU count: the sum order hangs on it)
+constexpr int ST_THREADS = 256;   // 32 tokens x 8 lanes per 64-wide head row; 4 waves at ~88 VGPRs: 5 workgroups per CU, so a CU overlaps tiles
+constexpr int ST_KU = 4;          // K chunks in flight per lane
+constexpr int ST_MAX_N = 16384 + RAJNI_MAX_PREFIX;   // cap of the tiled path: 2048 px at patch 16 with any prefix count (the finish kernel's LDS would hold ~19.8k tokens; the packed key 65535)
+
+struct TiledArgs {
+  int tiles;
+  float* logits;    // [B][H][N]
+  float* vbar;      // [B][N][D]
+  float* colsum;    // [B][tiles][D]
+  float* stats;     // [B][tiles][H][2]: max, sum of exp(l - max) over the tile's tokens
+};
+
+template <typename T>
+__global__ void __launch_bounds__(ST_THREADS) score_tile_kernel(const ScoreArgs a, const TiledArgs t) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tile = blockIdx.x, b = blockIdx.y;
+  const int N = a.N, H = a.H, D = a.D, C = H * D;
+  const int t0 = tile * ST_TILE, tn = N - t0 < ST_TILE ? N - t0 : ST_TILE;   // this tile's tokens: t0 .. t0 + tn - 1
+  float* qcls = sm;                 // [C]
+  float* lt = qcls + C;             // logits of the tile [H][ST_TILE]
+  float* vt = lt + H * ST_TILE;     // vbar of the tile [ST_TILE][D]
+  const T* base = reinterpret_cast<const T*>(a.qkv) + (size_t)b * N * 3 * C;
+  const T* tbase = base + (size_t)t0 * 3 * C;
+  const int LP = D >> 3;
+  const bool pow2 = LP == 4 || LP == 8 || LP == 16;     // as in score_select_kernel: DPP group sums, else the plain forms
+  const int sub = tid % LP, grp = tid / LP, ngrp = ST_THREADS / LP;
+
+  for (int c = tid; c < (C >> 3); c += ST_THREADS) {
+    float f[8];
+    load8<T>(base + c * 8, f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) qcls[c * 8 + j] = f[j];
+  }
+  __syncthreads();
+
+  // ---- logits of the tile's tokens (the lane mappings of score_select_kernel, over tn tokens instead of N)
+  const float inv_sqrt_d = 1.0f / sqrtf((float)D);
+  const float inv_h = 1.0f / (float)H;
+  const int CP = C >> 3;
+  if (!pow2) {
+    for (int item = tid; item < tn * H; item += ST_THREADS) {
+      const int n = item / H, h = item - n * H;
+      const T* kp = tbase + (size_t)n * 3 * C + C + h * D;
+      float dot = 0.f;
+      for (int c = 0; c < LP; ++c) {
+        float kf[8];
+        load8<T>(kp + c * 8, kf);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dot = fmaf(kf[j], qcls[h * D + c * 8 + j], dot);
+      }
+      lt[h * ST_TILE + n] = dot * inv_sqrt_d;
+    }
+  } else {
+    const int dn = ST_THREADS / CP, dc = ST_THREADS - dn * CP;   // item index += ST_THREADS
+    int n = tid / CP, c = tid - n * CP;
+    while (n < tn) {
+      float kf[ST_KU][8];
+      int nn[ST_KU], cc[ST_KU];
+#pragma unroll
+      for (int u = 0; u < ST_KU; ++u) {
+        nn[u] = n; cc[u] = c;
+        if (n < tn) load8<T>(tbase + (size_t)n * 3 * C + C + c * 8, kf[u]);
+        n += dn; c += dc;
+        if (c >= CP) { c -= CP; ++n; }
+      }
+#pragma unroll
+      for (int u = 0; u < ST_KU; ++u)
+        if (nn[u] < tn) {
+          const float4 q0 = *reinterpret_cast<const float4*>(qcls + cc[u] * 8);
+          const float4 q1 = *reinterpret_cast<const float4*>(qcls + cc[u] * 8 + 4);
+          float dot = kf[u][0] * q0.x;
+          dot = fmaf(kf[u][1], q0.y, dot); dot = fmaf(kf[u][2], q0.z, dot); dot = fmaf(kf[u][3], q0.w, dot);
+          dot = fmaf(kf[u][4], q1.x, dot); dot = fmaf(kf[u][5], q1.y, dot); dot = fmaf(kf[u][6], q1.z, dot);
+          dot = fmaf(kf[u][7], q1.w, dot);
+          dot = group_sum(dot, LP);     // the LP lanes of a head row are one aligned group with one token: all in or all out
+          if ((cc[u] & (LP - 1)) == 0) lt[(cc[u] / LP) * ST_TILE + nn[u]] = dot * inv_sqrt_d;
+        }
+    }
+  }
+  // ---- vbar of the tile's tokens: thread (token, 16-byte slice of the head dim), heads summed in head order
+  for (int n = grp < ngrp ? grp : tn; n < tn; n += ngrp) {
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const T* vp = tbase + (size_t)n * 3 * C + 2 * C + sub * 8;
+    for (int h0 = 0; h0 < H; h0 += 8) {
+      float vf[8][8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (h0 + u < H) load8<T>(vp + (h0 + u) * D, vf[u]);
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (h0 + u < H) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) acc[j] += vf[u][j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] *= inv_h;
+    float* dst = vt + n * D + sub * 8;
+    reinterpret_cast<float4*>(dst)[0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    reinterpret_cast<float4*>(dst)[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
+    store8<float>(t.vbar + ((size_t)b * N + t0 + n) * D + sub * 8, acc);
+  }
+  __syncthreads();
+
+  // ---- the tile's softmax statistics per head (one token per lane: ST_TILE <= 64), its logits, its column sums
+  for (int h = wave; h < H; h += ST_THREADS / 64) {
+    const float l = lane < tn ? lt[h * ST_TILE + lane] : -INFINITY;
+    const float mx = wave_max(l);
+    const float se = wave_sum(lane < tn ? __expf(l - mx) : 0.f);
+    if (lane == 0)
+      *reinterpret_cast<float2*>(t.stats + (((size_t)b * t.tiles + tile) * H + h) * 2) = make_float2(mx, se);
+  }
+  for (int i = tid; i < H * ST_TILE; i += ST_THREADS) {
+    const int h = i / ST_TILE, j = i - h * ST_TILE;
+    if (j < tn) t.logits[((size_t)b * H + h) * N + t0 + j] = lt[i];
+  }
+  if (tid < D) {   // four chains (token j mod 4), joined in a fixed tree
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    for (int j = 0; j < tn; j += 4) {
+      s0 += vt[j * D + tid];
+      if (j + 1 < tn) s1 += vt[(j + 1) * D + tid];
+      if (j + 2 < tn) s2 += vt[(j + 2) * D + tid];
+      if (j + 3 < tn) s3 += vt[(j + 3) * D + tid];
+    }
+    t.colsum[((size_t)b * t.tiles + tile) * D + tid] = (s0 + s1) + (s2 + s3);
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(SS_THREADS) score_finish_kernel(const ScoreArgs a, const TiledArgs t) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int b = blockIdx.x;
+  const int N = a.N, H = a.H, D = a.D, tiles = t.tiles;
+  const int kw = ss_key_words(N, a.P), n4 = (N + 3) & ~3;
+  float* acls = sm;                           // [N], then the ranking keys (max(N, key words) words)
+  float* sc = acls + (kw > n4 ? kw : n4);     // vnorm [N] then scores [N]
+  float* hstat = sc + N;                      // [2H]
+  float* part = hstat + 2 * H;                // [SS_THREADS]
+  float* mean = part + SS_THREADS;            // [D]
+  float* misc = mean + D;                     // [16]
+  int* wcount = reinterpret_cast<int*>(misc + 16);   // [SS_THREADS / 64]
+  const float* logits = t.logits + (size_t)b * H * N;
+  const float* vbar = t.vbar + (size_t)b * N * D;
+  const int LP = D >> 3;
+  const bool pow2 = LP == 4 || LP == 8 || LP == 16;
+  const int sub = tid % LP, grp = tid / LP, ngrp = SS_THREADS / LP;
+
+  // ---- per-head softmax statistics over all N tokens from the tiles': max of the maxima, sum of the rescaled sums
+  //      (lane l takes tiles l, l + 64, ... in tile order, then the wave's fixed tree)
+  for (int h = wave; h < H; h += SS_THREADS / 64) {
+    const float* st = t.stats + ((size_t)b * tiles * H + h) * 2;
+    float mx = -INFINITY;
+    for (int i = lane; i < tiles; i += 64) mx = fmaxf(mx, st[(size_t)i * H * 2]);
+    mx = wave_max(mx);
+    float se = 0.f;
+    for (int i = lane; i < tiles; i += 64) se += st[(size_t)i * H * 2 + 1] * __expf(st[(size_t)i * H * 2] - mx);
+    se = wave_sum(se);
+    if (lane == 0) { hstat[h] = mx; hstat[H + h] = se; }
+  }
+  // ---- token mean of vbar from the tiles' column sums: partial sums over tiles prt, prt + nparts, ..., joined in order
+  {
+    const int d = tid % D, prt = tid / D, nparts = SS_THREADS / D;
+    if (prt < nparts) {
+      float s = 0.f;
+      for (int i = prt; i < tiles; i += nparts) s += t.colsum[((size_t)b * tiles + i) * D + d];
+      part[prt * D + d] = s;
+    }
+    __syncthreads();
+    if (tid < D) {
+      float s = 0.f;
+      for (int q = 0; q < nparts; ++q) s += part[q * D + tid];
+      mean[tid] = s / (float)N;
+    }
+    __syncthreads();
+  }
+  // ---- A_cls[n] = mean_h softmax_h[n]: four lanes per token as in score_select_kernel
+  for (int n0 = 0; n0 < N; n0 += SS_THREADS / 4) {
+    const int n = n0 + (tid >> 2), q = tid & 3;
+    float s = 0.f;
+    if (n < N)
+      for (int h = q; h < H; h += 4) s += __expf(logits[(size_t)h * N + n] - hstat[h]) / hstat[H + h];
+    s = dpp_add<0xB1>(s);
+    s = dpp_add<0x4E>(s);
+    if (n < N && q == 0) acls[n] = s / (float)H;
+  }
+  // ---- ||vbar[n] - mean||_2
+  if (!pow2) {
+    for (int n = tid; n < N; n += SS_THREADS) {
+      float ss = 0.f;
+      for (int d = 0; d < D; d += 8) {
+        float v[8];
+        load8<float>(vbar + (size_t)n * D + d, v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float dlt = v[j] - mean[d + j];
+          ss = fmaf(dlt, dlt, ss);
+        }
+      }
+      sc[n] = sqrtf(ss);
+    }
+  } else {
+    const int rounds = (N + ngrp - 1) / ngrp;     // whole groups step together: the DPP adds need every lane of a group
+    for (int r = 0; r < rounds; ++r) {
+      const int n = r * ngrp + grp;
+      float ss = 0.f;
+      if (n < N) {
+        float v[8];
+        load8<float>(vbar + (size_t)n * D + sub * 8, v);
+        const float* mp = mean + sub * 8;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float dlt = v[j] - mp[j];
+          ss = fmaf(dlt, dlt, ss);
+        }
+      }
+      ss = group_sum(ss, LP);
+      if (n < N && sub == 0) sc[n] = sqrtf(ss);
+    }
+  }
+  __syncthreads();
+  // ---- mu, unbiased std + eps over tokens
+  if (wave == 0) {
+    float s = 0.f;
+    for (int n = lane; n < N; n += 64) s += sc[n];
+    const float mu = wave_sum(s) / (float)N;
+    float ss = 0.f;
+    for (int n = lane; n < N; n += 64) {
+      const float dlt = sc[n] - mu;
+      ss = fmaf(dlt, dlt, ss);
+    }
+    ss = wave_sum(ss);
+    if (lane == 0) {
+      misc[0] = mu;
+      misc[1] = sqrtf(ss / (float)(N - 1)) + a.eps;
+    }
+  }
+  __syncthreads();
+  {
+    const float mu = misc[0], sd = misc[1];
+    for (int n = tid; n < N; n += SS_THREADS) {
+      const float z = (sc[n] - mu) / sd;
+      const float sig = 1.0f / (1.0f + __expf(-z));
+      const float sv = round_to<T>(acls[n] * sig);
+      if (a.scores_out != nullptr) st1(reinterpret_cast<T*>(a.scores_out) + (size_t)b * N + n, sv);
+      sc[n] = sv;
+    }
+  }
+  __syncthreads();
+  if (a.keep <= 0) return;
+  select_tail<T>(a, b, sc, acls, reinterpret_cast<unsigned*>(acls), wcount);   // A_cls is dead: its words hold the keys
+}
+
+size_t st_tile_lds_bytes(int H, int D) { return ((size_t)H * D + (size_t)H * ST_TILE + (size_t)ST_TILE * D) * sizeof(float); }
+size_t st_finish_lds_bytes(int N, int H, int D, int P) {
+  const size_t kw = (size_t)ss_key_words(N, P), n4 = ((size_t)N + 3) & ~(size_t)3;
+  return ((kw > n4 ? kw : n4) + (size_t)N + 2 * (size_t)H + SS_THREADS + D + 16 + SS_THREADS / 64) * sizeof(float);
+}
+inline size_t st_align256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct TiledLayout { int tiles; size_t logits, vbar, colsum, stats, total; };   // byte offsets of the scratch regions
+TiledLayout st_layout(int B, int N, int H, int D) {
+  TiledLayout l{};
+  l.tiles = (N + ST_TILE - 1) / ST_TILE;
+  size_t off = 0;
+  auto take = [&](size_t floats) { const size_t o = off; off += st_align256(floats * sizeof(float)); return o; };
+  l.logits = take((size_t)B * H * N);
+  l.vbar = take((size_t)B * N * D);
+  l.colsum = take((size_t)B * l.tiles * D);
+  l.stats = take((size_t)B * l.tiles * H * 2);
+  l.total = off;
+  return l;
+}
+
+int g_ss_force_tiled = 0;      // test hook: 1 = the tiled path wherever scratch is passed, even when one workgroup holds the shape
+
+inline bool ss_shape_ok(int B, int N, int H, int D) { return B > 0 && N >= 2 && H > 0 && D >= 8 && D <= 128 && D % 8 == 0; }
+// the single-workgroup layout cannot hold the shape (P = 1: the prefix count only matters for a handful of tokens)
+inline bool ss_needs_tiles(int N, int H, int D) { return ss_lds_bytes(N, H, D, 1, false) > 160 * 1024; }
+
 int g_ss_force_two_pass = 0;   // test hook (rajni_hip_debug.h): 1 = the two-pass layout even when the merged one fits
 
 }  // namespace
 
 extern "C" void rajni_debug_force_score_two_pass(int on) { g_ss_force_two_pass = on; }
+extern "C" void rajni_debug_force_score_tiled(int on) { g_ss_force_tiled = on; }
+
+// Scratch bytes rajni_score_select_ws needs: 0 wherever one workgroup holds the shape (and for shapes no path takes)
+extern "C" size_t rajni_score_select_workspace_bytes(int B, int N, int H, int D, int dtype) {
+  if (!(dtype == RAJNI_BF16 || dtype == RAJNI_F32 || dtype == RAJNI_F16) || !ss_shape_ok(B, N, H, D) || N > ST_MAX_N) return 0;
+  if (!ss_needs_tiles(N, H, D) && g_ss_force_tiled == 0) return 0;
+  return st_layout(B, N, H, D).total;
+}
+
+namespace {
+// the tiled path: tile kernel + finish kernel, nothing else on the stream
+int launch_score_tiled(ScoreArgs a, int B, int dtype, void* ws, size_t ws_bytes, hipStream_t s) {
+  const int N = a.N, H = a.H, D = a.D;
+  RAJNI_REQUIRE(N <= ST_MAX_N, RAJNI_ERR_UNSUPPORTED,
+                "score/select: N=%d is beyond the tiled path's cap of %d tokens (one workgroup's LDS holds far fewer at H=%d D=%d)",
+                N, ST_MAX_N, H, D);
+  const size_t tl = st_tile_lds_bytes(H, D), fl = st_finish_lds_bytes(N, H, D, a.P);
+  RAJNI_REQUIRE(tl <= 64 * 1024 && fl <= 160 * 1024, RAJNI_ERR_UNSUPPORTED,
+                "score/select: N=%d H=%d D=%d needs %zu B (tile) / %zu B (finish) of LDS (caps: 64 KiB, 160 KiB; N <= %d)",
+                N, H, D, tl, fl, ST_MAX_N);
+  const TiledLayout l = st_layout(B, N, H, D);
+  RAJNI_REQUIRE(ws != nullptr && ws_bytes >= l.total, RAJNI_ERR_INVALID,
+                "score/select: the tiled path needs %zu B of scratch (rajni_score_select_workspace_bytes), got %zu", l.total, ws_bytes);
+  RAJNI_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, RAJNI_ERR_INVALID, "score/select: scratch must be 256-byte aligned");
+  char* base = static_cast<char*>(ws);
+  TiledArgs t{};
+  t.tiles = l.tiles;
+  t.logits = reinterpret_cast<float*>(base + l.logits); t.vbar = reinterpret_cast<float*>(base + l.vbar);
+  t.colsum = reinterpret_cast<float*>(base + l.colsum); t.stats = reinterpret_cast<float*>(base + l.stats);
+  typedef void (*kern_t)(const ScoreArgs, const TiledArgs);
+  const kern_t tile = dtype == RAJNI_F16 ? &score_tile_kernel<f16_t> : dtype == RAJNI_F32 ? &score_tile_kernel<float> : &score_tile_kernel<bf16_t>;
+  const kern_t fin = dtype == RAJNI_F16 ? &score_finish_kernel<f16_t> : dtype == RAJNI_F32 ? &score_finish_kernel<float> : &score_finish_kernel<bf16_t>;
+  if (fl > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fin), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fl);
+    if (e != hipSuccess) {
+      rajni_set_error("hipFuncSetAttribute(score_finish, %zu): %s", fl, hipGetErrorString(e));
+      return RAJNI_ERR_LAUNCH;
+    }
+  }
+  // algorithmic bytes: the K and V thirds and the CLS query row once, the scratch written once and read once, the scores
+  const double es = dtype == RAJNI_F32 ? 4.0 : 2.0;
+  const double bytes = (2.0 * N * H * D + H * D) * es * B + 2.0 * (double)l.total + 4.0 * N * B;
+  ProfScope prof(a.keep > 0 ? KC_SCORE_SELECT : KC_IMPORTANCE, s, 0.0, bytes);
+  hipLaunchKernelGGL(tile, dim3(l.tiles, B), dim3(ST_THREADS), tl, s, a, t);
+  RAJNI_CHECK_LAUNCH("score_tile_kernel");
+  hipLaunchKernelGGL(fin, dim3(B), dim3(SS_THREADS), fl, s, a, t);
+  RAJNI_CHECK_LAUNCH("score_finish_kernel");
+  return RAJNI_OK;
+}
+}  // namespace
+
+int launch_score_select(const void* qkv, const void* scores_in, int B, int N, int H, int D,
+                        float eps, int keep, void* scores_out, int32_t* keep_idx,
+                        void* next_scores, int dtype, hipStream_t s, int P) {
+  return launch_score_select(qkv, scores_in, B, N, H, D, eps, keep, scores_out, keep_idx, next_scores, dtype, s, P, nullptr, 0);
+}
 
 // qkv != null: compute scores (and select when keep > 0); qkv == null: select from scores_in.
 int launch_score_select(const void* qkv, const void* scores_in, int B, int N, int H, int D,
                         float eps, int keep, void* scores_out, int32_t* keep_idx,
-                        void* next_scores, int dtype, hipStream_t s, int P) {
+                        void* next_scores, int dtype, hipStream_t s, int P, void* ws, size_t ws_bytes) {
   RAJNI_REQUIRE(dtype == RAJNI_BF16 || dtype == RAJNI_F32 || dtype == RAJNI_F16, RAJNI_ERR_INVALID, "score/select: bad dtype %d", dtype);
   RAJNI_REQUIRE(P >= 1 && P <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID, "score/select: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, P);
   RAJNI_REQUIRE(B > 0 && N >= P + 1, RAJNI_ERR_INVALID, "score/select: need B > 0 and N >= %d (B=%d N=%d)", P + 1, B, N);
@@ -524,6 +883,8 @@ int launch_score_select(const void* qkv, const void* scores_in, int B, int N, in
                   "importance: head dim %d not supported (multiples of 8 up to 128)", D);
     RAJNI_REQUIRE(H > 0, RAJNI_ERR_INVALID, "importance: H must be positive");
     a.qkv = qkv; a.H = H; a.D = D;
+    // a shape one workgroup holds takes the kernel it always took; scratch serves the others (and any shape under the test hook)
+    if (ws != nullptr && (ss_needs_tiles(N, H, D) || g_ss_force_tiled != 0)) return launch_score_tiled(a, B, dtype, ws, ws_bytes, s);
     merged = ss_lds_bytes(N, H, D, P, true) <= 160 * 1024 && g_ss_force_two_pass == 0;   // else vbar reuses the logits' region
     lds = ss_lds_bytes(N, H, D, P, merged);
   } else {
@@ -531,8 +892,12 @@ int launch_score_select(const void* qkv, const void* scores_in, int B, int N, in
     a.scores_in = scores_in; a.H = 1; a.D = 32;
     lds = ss_lds_bytes(N, 1, 32, P, false);
   }
+  RAJNI_REQUIRE(lds <= 160 * 1024 || qkv == nullptr || N <= ST_MAX_N, RAJNI_ERR_UNSUPPORTED,
+                "score/select: N=%d H=%d D=%d needs %zu B of LDS (> 160 KiB), and the tiled path (rajni_score_select_ws) is capped at N <= %d",
+                N, H, D, lds, ST_MAX_N);
   RAJNI_REQUIRE(lds <= 160 * 1024, RAJNI_ERR_UNSUPPORTED,
-                "score/select: N=%d H=%d D=%d needs %zu B of LDS (> 160 KiB)", N, H, D, lds);
+                "score/select: N=%d H=%d D=%d needs %zu B of LDS (> 160 KiB)%s", N, H, D, lds,
+                qkv != nullptr ? "; rajni_score_select_ws scores such shapes through caller-provided scratch" : "");
   const bool f32 = dtype == RAJNI_F32;
   typedef void (*kern_t)(const ScoreArgs);
   const kern_t kern = dtype == RAJNI_F16

@@ -80,6 +80,8 @@ class VitPrefix(C.Structure):
 
 
 MAX_PREFIX = 32     # RAJNI_MAX_PREFIX
+SCORE_TILE_TOKENS = 32      # ST_TILE of csrc/score_select.hip: tokens per workgroup of the tiled score kernels
+SCORE_TILED_MAX_TOKENS = 16384 + MAX_PREFIX   # ST_MAX_N: the tiled path's cap
 
 _SIGS = {
     "rajni_abi_version": (c_int, []),
@@ -109,6 +111,7 @@ _SIGS = {
     "rajni_debug_set_gemm_nblock_bytes": (None, [c_int]),
     "rajni_debug_force_attention": (None, [c_int]),
     "rajni_debug_force_score_two_pass": (None, [c_int]),
+    "rajni_debug_force_score_tiled": (None, [c_int]),
     "rajni_debug_set_gemm_stamps": (None, [c_void_p]),
     "rajni_patch_embed_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "rajni_patch_embed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
@@ -119,6 +122,9 @@ _SIGS = {
     "rajni_select_topk_prefix": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "rajni_score_select_prefix": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p,
                                           c_void_p, c_int, c_void_p]),
+    "rajni_score_select_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "rajni_score_select_ws": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "rajni_patch_embed_prefix": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                          c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "rajni_pool_norm_prefix": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p,

@@ -82,15 +82,27 @@ def pack_vec(v: Optional[torch.Tensor], like_dtype=torch.bfloat16, device=None) 
     return v.detach().to(like_dtype).to(torch.float32).to(device if device is not None else v.device).contiguous()
 
 
+def _score_scratch(qkv: torch.Tensor, B: int, N: int, H: int, D: int) -> Optional[torch.Tensor]:
+    """scratch of the tiled score kernels (rajni_score_select_ws), None for every shape one workgroup's LDS holds"""
+    nbytes = nat.lib().rajni_score_select_workspace_bytes(B, N, H, D, _dt(qkv))
+    return torch.empty(nbytes, dtype=torch.uint8, device=qkv.device) if nbytes else None
+
+
 def importance(qkv: torch.Tensor, num_heads: int, eps: float = 1e-6) -> torch.Tensor:
     nat.require_device(qkv, "qkv")
     qkv = qkv.contiguous()
     B, N, threeC = qkv.shape
     D = threeC // 3 // num_heads
     out = torch.empty((B, N), dtype=qkv.dtype, device=qkv.device)
+    ws = _score_scratch(qkv, B, N, num_heads, D)
     with nat.device_guard(qkv.device):
-        nat.check(nat.lib().rajni_importance(qkv.data_ptr(), out.data_ptr(), B, N, num_heads, D, eps, _dt(qkv),
-                                             nat.stream_ptr(qkv.device)), "rajni_importance")
+        if ws is None:
+            nat.check(nat.lib().rajni_importance(qkv.data_ptr(), out.data_ptr(), B, N, num_heads, D, eps, _dt(qkv),
+                                                 nat.stream_ptr(qkv.device)), "rajni_importance")
+        else:       # more tokens than one workgroup's LDS holds: the tiled kernels, through scratch
+            nat.check(nat.lib().rajni_score_select_ws(qkv.data_ptr(), B, N, num_heads, D, eps, 1, 0, out.data_ptr(), None, None,
+                                                      _dt(qkv), ws.data_ptr(), ws.numel(), nat.stream_ptr(qkv.device)),
+                      "rajni_score_select_ws")
     return out
 
 
@@ -125,8 +137,13 @@ def score_select(qkv: torch.Tensor, num_heads: int, keep: int, eps: float = 1e-6
     scores = torch.empty((B, N), dtype=qkv.dtype, device=qkv.device) if want_scores else None
     idx = torch.empty((B, keep + P), dtype=torch.int32, device=qkv.device)
     nxt = torch.empty((B, keep + P), dtype=qkv.dtype, device=qkv.device)
+    ws = _score_scratch(qkv, B, N, num_heads, D)
     with nat.device_guard(qkv.device):
-        if P == 1:
+        if ws is not None:      # more tokens than one workgroup's LDS holds: the tiled kernels, through scratch
+            nat.check(nat.lib().rajni_score_select_ws(qkv.data_ptr(), B, N, num_heads, D, eps, P, keep, nat.ptr(scores),
+                                                      idx.data_ptr(), nxt.data_ptr(), _dt(qkv), ws.data_ptr(), ws.numel(),
+                                                      nat.stream_ptr(qkv.device)), "rajni_score_select_ws")
+        elif P == 1:
             nat.check(nat.lib().rajni_score_select(qkv.data_ptr(), B, N, num_heads, D, eps, keep, nat.ptr(scores),
                                                    idx.data_ptr(), nxt.data_ptr(), _dt(qkv),
                                                    nat.stream_ptr(qkv.device)), "rajni_score_select")

@@ -132,10 +132,18 @@ CONFIGS: Dict[str, ViTConfig] = {
     # registers on the fp8-capable micro model
     "vit_micro512_reg4_patch16_64": ViTConfig(img_size=64, embed_dim=512, depth=4, num_heads=8, num_classes=10, reg_tokens=4),
     # timm `vit_small_patch14_reg4_dinov2` dimensions (DINOv2 ViT-S/14 with 4 registers: no_embed_class, LayerScale) at
-    # img_size 224 = 261 tokens.  The pretrained size 518 gives 1374 tokens, more than the score/select kernel's LDS holds
-    # today (it refuses with an LDS error): out of scope here - run the checkpoint at 224 with an interpolated pos-embed.
+    # img_size 224 = 261 tokens, and at the pretrained size 518 = 1374 tokens: more than one workgroup's LDS holds, scored by
+    # the tiled score kernels (up to 16416 tokens, every head dim and dtype)
     "vit_small_patch14_reg4_dinov2": ViTConfig(img_size=224, patch_size=14, embed_dim=384, depth=12, num_heads=6,
                                                layer_scale=1e-5, no_embed_class=True, reg_tokens=4),
+    "vit_small_patch14_reg4_dinov2_518": ViTConfig(img_size=518, patch_size=14, embed_dim=384, depth=12, num_heads=6,
+                                                   layer_scale=1e-5, no_embed_class=True, reg_tokens=4),
+    # ---- more tokens than one workgroup's LDS holds (the tiled score kernels) at micro cost (not timm names) ----
+    # 400 px at patch 16: 626 tokens x 2 heads of 64 = 42 056 LDS words in the single-workgroup layout, 40 960 available
+    "vit_micro_patch16_400": ViTConfig(img_size=400, embed_dim=128, depth=4, num_heads=2, num_classes=10),
+    # the same with 4 registers in the DINOv2 / DeiT-3 layout (630 tokens)
+    "vit_micro_reg4_patch16_400": ViTConfig(img_size=400, embed_dim=128, depth=4, num_heads=2, num_classes=10,
+                                            layer_scale=1e-6, no_embed_class=True, reg_tokens=4),
 }
 
 
