@@ -49,6 +49,26 @@ enum {
                               model.py:59 (mlp.fc2, ls2, add)                                       */
 };
 
+/* ---- addressing limits ----
+ * Tensors may be of any size the device holds: every kernel forms row, image and workspace offsets in 64 bits, so buffers of
+ * 2^31 elements / 2^32 bytes and more are supported (qkv of a 2048 px batch, the MLP hidden buffer of a large batch), and
+ * rajni_vit_workspace_bytes() may exceed 2^32.  Counts are 32-bit ints: B, rows, M, N, K, n_src each stay below 2^31.
+ * Where a kernel keeps a 32-bit offset on purpose (registers), the host routes around it or refuses the call:
+ *   - rajni_linear, RAJNI_EPI_BIAS_RESID with an fp32 stream on the 256 x 128 tiling: the residual rows are addressed with
+ *     32-bit element offsets.  A residual operand that spans 2^31 elements or more (resid rows x ldr, gathered: the rows of
+ *     all source images) is sent to the 128 x 128 tiling instead, under the forced tiling hook too.  Same bits, slower.
+ *   - rajni_attention (16-bit, head dim 64, np <= 256: the persistent kernel) and rajni_attention_fp8: rows are addressed
+ *     inside ONE image with a 32-bit byte offset; the image base is 64-bit.  n_src * 3 * H * 64 * 2 bytes must stay below
+ *     2^32, else RAJNI_ERR_UNSUPPORTED (16416 tokens, the score path's cap, fit with up to 340 heads).
+ *   - rajni_qk_norm: (token, head) groups are counted in 32 bits: rows * 2 * H < RAJNI_QK_NORM_MAX_GROUPS, else
+ *     RAJNI_ERR_UNSUPPORTED.  Split the rows over several calls (the op is row-wise).
+ *   - rajni_attention and the tiled score path (rajni_score_select_ws with scratch) put the image index on a grid axis:
+ *     B <= RAJNI_MAX_GRID_YZ (rajni_attention: H too), else RAJNI_ERR_UNSUPPORTED.  Split the batch (images are independent).
+ *     rajni_vit_forward (and its _ext / _prefix forms) checks plan->B against the same limit with the rest of the plan.
+ * All of these refusals happen before anything is launched. */
+#define RAJNI_MAX_GRID_YZ 65535
+#define RAJNI_QK_NORM_MAX_GROUPS ((1LL << 31) - 1024)
+
 #define RAJNI_ABI_VERSION 8 /* bumped whenever a struct or an entry point changes; checked by the ctypes binding */
 int rajni_abi_version(void); /* == RAJNI_ABI_VERSION of the header the library was built from */
 const char* rajni_last_error(void);

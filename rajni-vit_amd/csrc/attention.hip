@@ -1105,8 +1105,20 @@ int launch_attention16(const AttnArgs& a, int B, int np, int H, int D, hipStream
   return RAJNI_OK;
 }
 
+// attn_bf16_d64_stream (the persistent kernel: head dim 64, 16-bit operands, up to 256 kept tokens) addresses a row inside its
+// image as (unsigned)row * row_bytes; every other attention kernel forms (long)row * C3
+static inline bool image_bytes_ok(int n_src, int H) { return (size_t)n_src * 3 * (size_t)H * 64 * 2 <= 0xFFFFFFFFul; }
+
 int launch_attention(const void* qkv, const int32_t* keep_idx, void* out, int B, int n_src, int np,
                      int H, int D, float scale, int dtype, hipStream_t s) {
+  // (the grid limit before the pointers: a refused shape is refused whatever else the call holds)
+  RAJNI_REQUIRE(H <= RAJNI_MAX_GRID_YZ && B <= RAJNI_MAX_GRID_YZ, RAJNI_ERR_UNSUPPORTED,
+                "rajni_attention: B=%d H=%d - one launch takes at most %d images and %d heads (grid y / z)", B, H,
+                RAJNI_MAX_GRID_YZ, RAJNI_MAX_GRID_YZ);
+  const bool persistent = D == 64 && dtype != RAJNI_F32 && (np + 31) / 32 <= 8 && g_force_attn == 0;
+  RAJNI_REQUIRE(!persistent || image_bytes_ok(n_src, H), RAJNI_ERR_UNSUPPORTED,
+                "rajni_attention: one image of qkv is n_src=%d x 3*H*64 x 2 bytes - with up to 256 kept tokens the limit is 2^32 - 1 "
+                "bytes per image", n_src);
   RAJNI_REQUIRE(qkv && out, RAJNI_ERR_INVALID, "rajni_attention: null pointer");
   RAJNI_REQUIRE(D >= 8 && D <= 128 && D % 8 == 0, RAJNI_ERR_UNSUPPORTED,
                 "rajni_attention: head dim %d not supported (multiples of 8 up to 128)", D);
@@ -1114,7 +1126,6 @@ int launch_attention(const void* qkv, const int32_t* keep_idx, void* out, int B,
                 "rajni_attention: bad shape B=%d H=%d np=%d n_src=%d", B, H, np, n_src);
   RAJNI_REQUIRE(keep_idx != nullptr || np == n_src, RAJNI_ERR_INVALID,
                 "rajni_attention: identity selection needs np == n_src");
-  RAJNI_REQUIRE(H <= 65535 && B <= 65535, RAJNI_ERR_UNSUPPORTED, "rajni_attention: grid too large");
   if (dtype == RAJNI_F32) {
     AttnArgsF32 f{};
     f.qkv = (const float*)qkv; f.idx = keep_idx; f.out = (float*)out;
@@ -1146,6 +1157,11 @@ int launch_attention(const void* qkv, const int32_t* keep_idx, void* out, int B,
 // LDS to spare for the output staging)
 int launch_attention_fp8(const void* qkv, const int32_t* keep_idx, void* out_q, float out_scale, float* row_scale,
                          int B, int n_src, int np, int H, int D, float scale, hipStream_t s) {
+  RAJNI_REQUIRE(H <= RAJNI_MAX_GRID_YZ && B <= RAJNI_MAX_GRID_YZ, RAJNI_ERR_UNSUPPORTED,
+                "rajni_attention_fp8: B=%d H=%d - one launch takes at most %d images and %d heads", B, H, RAJNI_MAX_GRID_YZ,
+                RAJNI_MAX_GRID_YZ);
+  RAJNI_REQUIRE(image_bytes_ok(n_src, H), RAJNI_ERR_UNSUPPORTED,
+                "rajni_attention_fp8: one image of qkv is n_src=%d x 3*H*64 x 2 bytes - the limit is 2^32 - 1 bytes per image", n_src);
   RAJNI_REQUIRE(qkv && out_q && row_scale, RAJNI_ERR_INVALID, "rajni_attention_fp8: null pointer");
   RAJNI_REQUIRE(D == 64 && np <= 224, RAJNI_ERR_UNSUPPORTED,
                 "rajni_attention_fp8: head dim 64 and at most 224 tokens (D=%d np=%d)", D, np);

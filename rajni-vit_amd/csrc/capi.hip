@@ -161,6 +161,10 @@ int rajni_score_select_ws(const void* qkv, int B, int N, int H, int D, float eps
                           void* scores_out, int32_t* keep_idx, void* next_scores, int dtype, void* workspace,
                           size_t workspace_bytes, rajni_stream_t stream) {
   NEED_DTYPE("rajni_score_select_ws");
+  // (the grid limit of the tiled path before the pointers: a refused shape is refused whatever else the call holds)
+  RAJNI_REQUIRE(B <= RAJNI_MAX_GRID_YZ || rajni_score_select_workspace_bytes(B, N, H, D, dtype) == 0, RAJNI_ERR_UNSUPPORTED,
+                "rajni_score_select_ws: B=%d - one launch of the tiled path takes at most %d images (grid: token tiles x images)",
+                B, RAJNI_MAX_GRID_YZ);
   RAJNI_REQUIRE(qkv != nullptr, RAJNI_ERR_INVALID, "rajni_score_select_ws: qkv is null");
   RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
                 "rajni_score_select_ws: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);

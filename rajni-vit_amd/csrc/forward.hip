@@ -59,6 +59,10 @@ int check_plan(const rajni_vit_plan& p, bool norm_absent) {
   RAJNI_REQUIRE(p.dtype == RAJNI_BF16 || p.dtype == RAJNI_F32 || p.dtype == RAJNI_F16, RAJNI_ERR_INVALID,
                 "rajni_vit_forward: bad dtype %d", p.dtype);
   RAJNI_REQUIRE(p.B > 0 && p.depth > 0 && p.blocks != nullptr, RAJNI_ERR_INVALID, "rajni_vit_forward: bad plan");
+  // every block's attention puts the image index on a grid axis: refuse here, not in the middle of the forward
+  RAJNI_REQUIRE(p.B <= RAJNI_MAX_GRID_YZ, RAJNI_ERR_UNSUPPORTED,
+                "rajni_vit_forward: B=%d - one forward takes at most %d images (split the batch: images are independent)", p.B,
+                RAJNI_MAX_GRID_YZ);
   RAJNI_REQUIRE(p.C == p.H * p.D && p.D >= 8 && p.D <= 128 && p.D % 8 == 0, RAJNI_ERR_UNSUPPORTED,
                 "rajni_vit_forward: need C == H*D and a head dim that is a multiple of 8 up to 128 (C=%d H=%d D=%d)", p.C, p.H, p.D);
   RAJNI_REQUIRE(p.C % 64 == 0 && p.hidden % 64 == 0, RAJNI_ERR_UNSUPPORTED,

@@ -818,6 +818,9 @@ namespace {
 // the tiled path: tile kernel + finish kernel, nothing else on the stream
 int launch_score_tiled(ScoreArgs a, int B, int dtype, void* ws, size_t ws_bytes, hipStream_t s) {
   const int N = a.N, H = a.H, D = a.D;
+  RAJNI_REQUIRE(B <= RAJNI_MAX_GRID_YZ, RAJNI_ERR_UNSUPPORTED,
+                "score/select: B=%d - one launch of the tiled path takes at most %d images (grid: token tiles x images)", B,
+                RAJNI_MAX_GRID_YZ);
   RAJNI_REQUIRE(N <= ST_MAX_N, RAJNI_ERR_UNSUPPORTED,
                 "score/select: N=%d is beyond the tiled path's cap of %d tokens (one workgroup's LDS holds far fewer at H=%d D=%d)",
                 N, ST_MAX_N, H, D);

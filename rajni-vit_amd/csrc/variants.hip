@@ -270,12 +270,15 @@ void launch_pool_norm_t(const void* x, int B, int N, int C, int r0, int r1, cons
 
 int launch_qk_norm(void* qkv, const float* qw, const float* qb, const float* kw, const float* kb, int rows, int H, int D,
                    float eps, int dtype, hipStream_t s) {
-  RAJNI_REQUIRE(qkv && qw && kw, RAJNI_ERR_INVALID, "rajni_qk_norm: null pointer");
+  // (shape limits before the pointers: a refused shape is refused whatever else the call holds)
   RAJNI_REQUIRE(rows > 0 && H > 0, RAJNI_ERR_INVALID, "rajni_qk_norm: bad shape (rows=%d H=%d)", rows, H);
   RAJNI_REQUIRE(D >= 8 && D <= 128 && D % 8 == 0, RAJNI_ERR_UNSUPPORTED,
                 "rajni_qk_norm: need a head dim that is a multiple of 8 up to 128 (D=%d)", D);
-  RAJNI_REQUIRE((long)rows * 2 * H < (1L << 31) - 1024, RAJNI_ERR_UNSUPPORTED, "rajni_qk_norm: too many (token, head) groups (%ld)",
-                (long)rows * 2 * H);
+  // the kernel indexes (token, head) groups with 32-bit ints and rounds the count up to whole workgroups
+  RAJNI_REQUIRE((long)rows * 2 * H < RAJNI_QK_NORM_MAX_GROUPS, RAJNI_ERR_UNSUPPORTED,
+                "rajni_qk_norm: %ld (token, head) groups (rows * 2 * H) - the limit is %ld", (long)rows * 2 * H,
+                (long)RAJNI_QK_NORM_MAX_GROUPS - 1);
+  RAJNI_REQUIRE(qkv && qw && kw, RAJNI_ERR_INVALID, "rajni_qk_norm: null pointer");
   const int groups = rows * 2 * H;
   const double es = dtype == RAJNI_F32 ? 4.0 : 2.0;
   ProfScope prof(KC_LAYERNORM, s, 8.0 * groups * D, 2.0 * es * groups * (double)D);
