@@ -5,6 +5,8 @@
 #ifndef RAJNI_HIP_DEBUG_H
 #define RAJNI_HIP_DEBUG_H
 
+#include "rajni_hip.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -22,12 +24,30 @@ void rajni_debug_force_gemm_tiling(int mode);
 void rajni_debug_force_f8_tiling(int mode);
 
 /* every other workgroup of an XCD sleeps `units` x 8192 cycles before its first tile of a residual-epilogue GEMM, so
- * that the two halves of the chip do not burst in the same instant; default 2 (+0.5-0.8 % on the forward), 0 = off */
+ * that the two halves of the chip do not burst in the same instant; default 1 (best in the forward by 0.1-0.3 %), 0 = off */
 void rajni_debug_set_resid_stagger(int units);
 
 /* W bytes one N block of the persistent tile order may occupy (default 1600 KiB); 0 = the plain column-fastest
  * order; -k = blocks of k column tiles regardless of size.  Results are bit-identical for every value (tested). */
 void rajni_debug_set_gemm_nblock_bytes(int bytes);
+
+/* Dry run of a linear call: the same argument checks, format / epilogue resolution and tiling choice, for a device of
+ * `cus` compute units (no device needed), and no launch.  Returns the code the call itself would return before launching and
+ * sets the same last-error text; on RAJNI_OK `*out` holds what would be launched.  The pointers in `args` are checked
+ * (null, alignment) and never followed. */
+enum { RAJNI_TILING_SMALL = 1,       /* 128x128x64, one workgroup per tile */
+       RAJNI_TILING_F32 = 2,         /* 128x128x32 on fp32 operands */
+       RAJNI_TILING_WIDE = 4,        /* 256x256x64 persistent */
+       RAJNI_TILING_MID = 5,         /* 256x128x64 persistent, 3 stages */
+       RAJNI_TILING_F8_STREAM = 8,   /* fp8 x fp8 256x128x128 persistent */
+       RAJNI_TILING_F8_WIDE = 9 };   /* fp8 x fp8 256x256x128 persistent */
+typedef struct rajni_linear_plan {
+  int tiling;                       /* RAJNI_TILING_* */
+  int tiles_n, total_tiles, nblk;   /* column tiles, tiles, column tiles per N block of the tile order (0: plain order) */
+  int grid;                         /* workgroups */
+  int lds_bytes;                    /* dynamic LDS per workgroup: stages + epilogue scratch */
+} rajni_linear_plan;
+int rajni_debug_linear_plan(const rajni_linear_args* args, int cus, rajni_linear_plan* out);
 
 /* score+select: 1 = read K and V in two passes with vbar reusing the logits' LDS region (what N = 577 x 16 heads
  * needs) even when the one-pass layout fits; 0 = default.  Scores are bit-identical either way (tested). */

@@ -15,7 +15,7 @@
 //   * workgroup -> tile mapping: every XCD gets a contiguous range of tile ids; ids run (N block of
 //     ~1.5 MiB of W, row tile, column in block), see tile_mn.
 //
-// Tilings (chosen per launch, see launch_gemm):
+// Tilings (chosen per launch, see choose_gemm):
 //   wide  256 x 256 x 64, 8 waves, 2 LDS stages, persistent stream  - wide outputs (qkv, fc1)
 //   mid   256 x 128 x 64, 8 waves, 3 LDS stages, persistent stream  - N = 768-class outputs (proj, fc2)
 //   small 128 x 128 x 64, 4 waves, 2 stages, 2 workgroups per CU    - M < 1024 (head, tiny batches)
@@ -250,6 +250,32 @@ constexpr bool nat_order(int epi, bool sf32) { return sf32 && (epi == EPI_RESID 
 enum { MAP_NAT = 1, MAP_SEC = 2, MAP_F8 = 3 };
 constexpr int col_map(int epi, bool sf32) { return epi == EPI_GELU8 ? MAP_F8 : nat_order(epi, sf32) ? MAP_NAT : MAP_SEC; }
 
+// ---- epilogue scratch: LDS per wave behind the stages, through which an epilogue transposes its wave's block into whole
+// 128-byte lines.  This is the ONE statement of which instantiation has how much: the kernels form their scratch pointer
+// from it (non-null exactly when it is non-zero) and the host sizes the dynamic LDS with it (lds_bytes of each family).
+#ifndef RAJNI_TSTORE
+#define RAJNI_TSTORE 1      // bf16 outputs (BIAS, GELU) of the stream tilings leave as whole lines too
+#endif
+#ifndef RAJNI_F8W_LINES
+#define RAJNI_F8W_LINES 1   // ... and the bf16 output of the fp8 x fp8 256 x 256 kernel (gemm_f8.h)
+#endif
+constexpr bool resid_nat(int epi, bool sf32) { return nat_order(epi, sf32) && epi == EPI_RESID; }
+// fp32-stream RESID of gemm_bf16_tn_stream (mi = row groups per wave: 4 on 256 x 128, 8 on 256 x 256):
+//   ROWMAJOR       256 x 128, both weight formats: residual rows prefetched in full lines (prefetch_resid_rowmajor)
+//   ROWMAJOR_WIDE  256 x 256: loads in the epilogue, group by group; bf16 weights only (with the fp8-weight scale on top the
+//                  instantiation spills - it keeps the accumulator-layout epilogue)
+constexpr bool epi_rowmajor(int epi, bool sf32, int mi) { return resid_nat(epi, sf32) && mi <= 4; }
+constexpr bool epi_rowmajor_wide(int epi, bool sf32, int mi, bool w8) { return resid_nat(epi, sf32) && mi > 4 && !w8; }
+constexpr bool epi_tstore(int epi) { return RAJNI_TSTORE && (epi == EPI_BIAS || epi == EPI_GELU); }
+constexpr int stream_scratch_bytes(int epi, bool sf32, int mi, bool w8) {   // wide::gemm_bf16_tn_stream
+  return (epi_rowmajor(epi, sf32, mi) || epi_rowmajor_wide(epi, sf32, mi, w8) || epi_tstore(epi)) ? 2048 : 0;
+}
+constexpr int f8_scratch_bytes(int epi, bool sf32) {   // f8::gemm_f8_tn_stream: fp32-stream RESID and bf16 outputs
+  return (resid_nat(epi, sf32) || epi == EPI_BIAS) ? 2048 : 0;
+}
+constexpr int f8w_scratch_bytes(int epi) { return (epi == EPI_BIAS && RAJNI_F8W_LINES) ? 4096 : 0; }   // f8w::gemm_f8_tn_wide
+constexpr int LDS_MAX_BYTES = 160 * 1024;   // per workgroup on gfx950
+
 template <int MAP>
 __device__ __forceinline__ int out_col(int n0w, int g, int j) {
   const int ni = j >> 2, rg = j & 3;
@@ -423,6 +449,19 @@ __device__ __forceinline__ void prefetch_resid(const GemmParams& p, ResidPrefetc
       pre.valid = true;
     }
   }
+}
+
+// Vector stores per wave that epilogue_tile issues for an INTERIOR tile of mi row groups (16 rows x 64 columns each), by
+// path.  The stream kernels let their first counted wait of a tile leave that many stores outstanding (NSTORE there), so
+// the count of every path an instantiation can take has to stay at or above what tile_stores returns.
+constexpr int stores_acc_layout(bool nat, int mi) { return (nat ? 4 : 2) * mi; }   // per row: 4 float4 (natural order) or 2 x 8 16-bit values
+constexpr int stores_rowmajor(int mi) { return 2 * 2 * mi; }   // ROWMAJOR, ROWMAJOR_WIDE: per row group 2 column halves x 2 x (8 rows x 128 bytes)
+constexpr int stores_tstore(int mi) { return 2 * mi; }         // TSTORE: per row group 2 x (8 rows x 128 bytes)
+constexpr int tile_stores(int epi, bool sf32, int mi, bool rowmajor, bool tstore) {   // the fewest over the instantiation's paths
+  int n = stores_acc_layout(nat_order(epi, sf32), mi);   // the path every instantiation has (no scratch, gathered rows)
+  if (rowmajor && stores_rowmajor(mi) < n) n = stores_rowmajor(mi);
+  if (tstore && stores_tstore(mi) < n) n = stores_tstore(mi);
+  return n;
 }
 
 // shared tail of every 16-bit tiling: bias/gamma for this lane's columns, then one row per m-tile (A: bf16_t or f16_t,
@@ -716,9 +755,6 @@ struct XSource {
 // every LDS read and DMA issue sits between MFMAs (sched_group_barrier pins the order).
 // =============================================================================================
 #define RAJNI_GEMM_NBLK_BYTES (1600 * 1024)
-#ifndef RAJNI_TSTORE
-#define RAJNI_TSTORE 1
-#endif
 namespace wide {
 constexpr int BM = 256, BK = 64;
 constexpr int X_BYTES = BM * BK * 2;            // 32 KiB
@@ -736,6 +772,9 @@ template <int WN_, int NS_, bool W8_ = false, int NW_ = 8> struct Cfg {   // WN_
   // W pieces 32 tile rows apart share their swizzle key (every map): one pointer per piece of the first 32 rows
   static constexpr int NPW = PW < (W8_ ? 2 : 4) ? PW : (W8_ ? 2 : 4);
 };
+// dynamic LDS of gemm_bf16_tn_stream<EPI, ., SF32, ., WN, MI, NS, W8>: the stages plus the eight waves' epilogue scratch
+template <int EPI, bool SF32, int WN, int MI, int NS, bool W8>
+constexpr int lds_bytes() { return Cfg<WN, NS, W8>::LDS_BYTES + 8 * stream_scratch_bytes(EPI, SF32, MI, W8); }
 
 // issue order of one half step: MI groups of {NI MFMAs, 1-2 fragment reads, DMA pieces}, reads and pieces spread
 // evenly over the groups (front-loading either was measured and is slower: the forward 9.03 -> 9.45 ms)
@@ -772,12 +811,12 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_bf16_tn_stream(const Gem
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // fp32-stream RESID launches of the 256 x 128 tiling: full-line residual loads / output stores through a 2 KiB per-wave
-  // LDS transpose behind the stages (host: RESID_SCRATCH_BYTES more dynamic LDS) - see prefetch_resid_rowmajor
-  // (bf16 weights: with the fp8-weight scale on top the instantiation spills - it keeps the accumulator-layout epilogue)
-  constexpr bool ROWMAJOR = nat_order(EPI, SF32) && EPI == EPI_RESID && MI <= 4;
-  constexpr bool TSTORE = RAJNI_TSTORE && (EPI == EPI_BIAS || EPI == EPI_GELU);   // bf16 outputs leave as whole lines too
-  constexpr bool ROWMAJOR_WIDE = nat_order(EPI, SF32) && EPI == EPI_RESID && MI > 4 && !W8;    // loads in the epilogue, group by group
+  // fp32-stream RESID launches (ROWMAJOR covers both weight formats on the 256 x 128 tiling; only ROWMAJOR_WIDE, on 256 x
+  // 256, excludes fp8 weights) and bf16 outputs: full-line loads / stores through a 2 KiB per-wave LDS transpose behind the
+  // stages - stream_scratch_bytes, which also sizes the host's dynamic LDS (lds_bytes); see prefetch_resid_rowmajor
+  constexpr bool ROWMAJOR = epi_rowmajor(EPI, SF32, MI);
+  constexpr int SCRATCH = stream_scratch_bytes(EPI, SF32, MI, W8);
+  static_assert(lds_bytes<EPI, SF32, WN, MI, NS, W8>() <= LDS_MAX_BYTES, "stages + epilogue scratch exceed the workgroup's LDS");
 
   // ---- staging: a piece = 1 KiB = 8 rows x 128 B; wave w stages X pieces 4w..4w+3, W pieces PW*w..
   //      (fp8 W: a piece = 16 rows x 64 B, lane -> row lane>>2, 16-byte unit lane&3)
@@ -956,7 +995,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_bf16_tn_stream(const Gem
   // vmcnt as well and retires vector-memory ops in order, so the first counted wait of a tile may leave
   // exactly the epilogue's stores outstanding instead of waiting for them to reach L2: an interior tile's
   // epilogue issues NSTORE stores per wave after the DMA of K step 1 (a lower bound is all that is needed).
-  constexpr int NSTORE_ALL = nat_order(EPI, SF32) ? 4 * MI : 2 * MI;
+  constexpr int NSTORE_ALL = tile_stores(EPI, SF32, MI, ROWMAJOR || epi_rowmajor_wide(EPI, SF32, MI, W8), epi_tstore(EPI));
   constexpr int NSTORE = NSTORE_ALL < 48 ? NSTORE_ALL : 48;   // vmcnt is a 6-bit counter
   bool prev_full = false;          // the previous tile of this workgroup was interior
 
@@ -1004,7 +1043,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_bf16_tn_stream(const Gem
 
     // ---- epilogue (the next tile's first loads are in flight)
     epilogue_tile<A, EPI, SF32, MI, W8>(p, acc, m0 + wm * (MI * 16), n0 + wn * 64, l15, g, pre, m_lo, inter,
-                                     (ROWMAJOR || ROWMAJOR_WIDE || TSTORE) ? smem + C::LDS_BYTES + wave * 2048 : nullptr);
+                                     SCRATCH > 0 ? smem + C::LDS_BYTES + wave * SCRATCH : nullptr);
 #ifdef RAJNI_GEMM_STAMPS
     if (p.stamps != nullptr && wave == 0) {
       const unsigned long long ts3 = __builtin_amdgcn_s_memtime();
@@ -1133,23 +1172,6 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_tn_128x128(const GemmParams 
 }  // namespace small
 
 #include "gemm_f8.h"   // namespace f8: the fp8 x fp8 persistent kernel (v_mfma_f32_16x16x128_f8f6f4)
-
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): `done` is the calling site's
-// per-device flag array (a process may drive several GPUs; one process per GPU is the deployment, but a model on
-// cuda:1 in a process whose first launch was on cuda:0 must not inherit that device's "done")
-template <typename K>
-int set_lds_attr(K kernel, int lds, bool (&done_by_device)[RAJNI_MAX_DEVICES]) {
-  bool& done = done_by_device[rajni_current_device()];
-  if (done) return RAJNI_OK;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) {
-    rajni_set_error("hipFuncSetAttribute(gemm): %s", hipGetErrorString(e));
-    return RAJNI_ERR_LAUNCH;
-  }
-  done = true;
-  return RAJNI_OK;
-}
 
 // =============================================================================================
 // fp32 model path: 128 x 128 x 32(fp32) tile - byte-for-byte the LDS geometry of the small bf16
@@ -1298,19 +1320,6 @@ __global__ void __launch_bounds__(256, 2) gemm_f32_tn_128x128(const GemmParams p
   }
 }
 
-template <int EPI, int ALOAD>
-int launch(GemmParams p, int kclass, hipStream_t s) {
-  static bool attr[RAJNI_MAX_DEVICES] = {};
-  p.tiles_n = (p.N + 127) / 128;
-  p.total_tiles = p.tiles_n * ((p.M + 127) / 128);
-  int rc = set_lds_attr(&gemm_f32_tn_128x128<EPI, ALOAD>, LDS_BYTES, attr);
-  if (rc != RAJNI_OK) return rc;
-  ProfScope prof(kclass, s, 2.0 * p.M * (double)p.N * p.K,
-                 4.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N));
-  hipLaunchKernelGGL((gemm_f32_tn_128x128<EPI, ALOAD>), dim3(p.total_tiles), dim3(256), LDS_BYTES, s, p);
-  RAJNI_CHECK_LAUNCH("gemm_f32_tn");
-  return RAJNI_OK;
-}
 }  // namespace f32
 
 // x[b,0,:] = cls + pos[0]  (or cls alone when pos has no CLS row)
@@ -1349,6 +1358,8 @@ __global__ void __launch_bounds__(256) prefix_pos_kernel(const T* cls, const T* 
   else store8<T>(reinterpret_cast<T*>(x) + off, v);
 }
 
+// ---- host side: choose a tiling (pure functions of the shape, the CU count, the instantiation's traits and the hooks),
+//      then launch it
 // LDS stages of the wide tiling: 2 for bf16 weights (2 x 64 KiB); fp8 weights leave room for 3 (3 x 48 KiB)
 #ifndef RAJNI_W8_WIDE_NS
 #define RAJNI_W8_WIDE_NS 2
@@ -1356,17 +1367,18 @@ __global__ void __launch_bounds__(256) prefix_pos_kernel(const T* cls, const T* 
 #define RAJNI_W8_WIDE_NS_OR(w8) ((w8) ? RAJNI_W8_WIDE_NS : 2)
 // test / tuning hooks (include/rajni_hip_debug.h): process-global, unsynchronised - not for concurrent use
 int g_force_tiling = 0;  // 0 auto, 1 small (128x128x64, 2 stages), 4 wide 256x256x64, 5 mid 256x128x64 (tests)
+int g_force_f8_tiling = 0;   // test hook: 0 by shape, 1 = 256 x 128 always, 2 = 256 x 256 wherever it exists
 int g_nblk_bytes = RAJNI_GEMM_NBLK_BYTES;   // W bytes of one N block (0 = plain order, < 0 = forced block size: tuning)
 
 // column tiles per N block of the persistent tile order (see tile_mn).  Measured on the ViT-B shapes
 // (tools/nblk_bench.py): blocks of ~1.5 MiB of W help once every block spans at least two rounds of tiles
 // (QKV at 197 tokens 179 -> 161 us, FC1 254 -> 239 us); with fewer rounds W is not re-read often enough
 // to pay for reading X once per block, and K = 3072 (fc2) never pays.
-inline int n_block(int tiles_n, int tiles_m, int bn, int K, int wbytes, int cus) {
-  if (g_nblk_bytes < 0) return -g_nblk_bytes < tiles_n ? -g_nblk_bytes : tiles_n;
-  if (g_nblk_bytes == 0) return tiles_n;
+inline int n_block(int tiles_n, int tiles_m, int bn, int K, int wbytes, int cus, int nblk_bytes) {
+  if (nblk_bytes < 0) return -nblk_bytes < tiles_n ? -nblk_bytes : tiles_n;
+  if (nblk_bytes == 0) return tiles_n;
   const long per_tile = (long)bn * K * wbytes;
-  const int fit = (int)(g_nblk_bytes / per_tile);
+  const int fit = (int)(nblk_bytes / per_tile);
   if (fit < 1 || fit >= tiles_n) return tiles_n;
   const int blocks = (tiles_n + fit - 1) / fit;
   const int rounds = tiles_n * tiles_m / cus;
@@ -1395,29 +1407,36 @@ inline bool wide_wins_on_rounds(int M, int N, int cus) {
 // the 20 GEMM shapes of the schedule.
 inline int stream_grid(int total_tiles, int cus) { return total_tiles <= cus ? total_tiles : cus; }
 
-// Every other workgroup of an XCD starts a residual-epilogue launch `units` x 8192 cycles late, so that the two halves of
-// the chip do not hit their prologue loads and epilogue bursts in the same instant.  Round 2 (tools/stagger_probe.py,
-// tools/ab_forward.py stagger): proj alone -4 % at 1 unit, fc2 alone flat; in the forward 2 units were best (+0.5-0.8 %).
-// Round 3, with the full-line epilogue: stand-alone proj now LOSES with any offset (84.4 us at 0, 88.5 at 1, 97.4 at 2 units;
-// four or eight phase groups worse still), in the forward 1 unit is best by 0.1-0.3 % (8.850 / 8.804 ms against 8.872 / 8.825
-// at 2 units and 8.878 / 8.838 at 0).  rajni_debug_set_resid_stagger(0) turns it off.
-int g_resid_stagger = 1;
+// what a choice needs to know of the instantiations behind a launch
+struct TileTraits {
+  int epi;
+  bool resid_nat;             // fp32-stream RESID: the 256 x 128 tiling's epilogue addresses the residual with 32-bit offsets
+  int lds_wide, lds_narrow;   // dynamic LDS of the 256 x 256 / 256 x 128 kernel (lds_wide = 0: there is no 256 x 256 kernel)
+};
+// tiles of bm x bn.  bm = 256: a persistent stream (grid <= cus) whose tile order runs in N blocks of W, wbytes per element;
+// otherwise one workgroup per tile in the plain order
+rajni_linear_plan make_plan(const GemmParams& p, int tiling, int bm, int bn, int lds, int cus = 0, int wbytes = 0, int nblk_bytes = 0) {
+  const int tiles_m = (p.M + bm - 1) / bm;
+  rajni_linear_plan c{};
+  c.tiling = tiling; c.lds_bytes = lds;
+  c.tiles_n = (p.N + bn - 1) / bn;
+  c.grid = c.total_tiles = c.tiles_n * tiles_m;
+  if (bm == 256) {
+    c.nblk = n_block(c.tiles_n, tiles_m, bn, p.K, wbytes, cus, nblk_bytes);
+    c.grid = stream_grid(c.total_tiles, cus);
+  }
+  return c;
+}
 
-template <int EPI, int ALOAD, bool SF32, bool W8 = false, typename A = bf16_t>
-int launch_gemm(GemmParams p, int kclass, hipStream_t s) {
-  p.stamps = rajni_g_stamps;
-  p.stagger = g_resid_stagger;
-  p.tiles_n = (p.N + 127) / 128;
-  const int t256 = p.tiles_n * ((p.M + 255) / 256), t128 = p.tiles_n * ((p.M + 127) / 128);
-  int mode = g_force_tiling;
-  const int cus = rajni_num_cus();
+// 16-bit activations (wide / mid / small); `force` = rajni_debug_force_gemm_tiling
+rajni_linear_plan choose_gemm(const GemmParams& p, const TileTraits& r, int cus, int force, int nblk_bytes) {
+  int mode = force;
   if ((mode == 4 || mode == 5) && p.M < 256) mode = 1;   // stream tiles may start at M - 256
   if (mode == 4 && p.K < 192) mode = 1;                   // the persistent streams need >= NS + 1 K steps
   if (mode == 5 && p.K < 256) mode = 1;
   // the 256 x 128 tiling's full-line residual epilogue addresses the residual tensor with 32-bit element offsets
-  constexpr bool RESID_NAT = nat_order(EPI, SF32) && EPI == EPI_RESID;
   const long resid_rows = p.ridx != nullptr ? (long)(p.M / p.r_np) * p.r_nsrc : (long)p.M;
-  const bool mid_ok = !RESID_NAT || resid_rows * p.ldr < (1L << 31);
+  const bool mid_ok = !r.resid_nat || resid_rows * p.ldr < (1L << 31);
   if (mode == 5 && !mid_ok) mode = 1;
   if (mode == 0) {
     // measured on ViT-B shapes (tools/gemm_bench.py, tools/proj_probe.py, profiles/):
@@ -1429,65 +1448,16 @@ int launch_gemm(GemmParams p, int kclass, hipStream_t s) {
     else if (p.M >= 1024 && p.K >= 256) mode = (p.K > p.N && p.K >= 1536 && wide_wins_on_rounds(p.M, p.N, cus)) ? 4 : (mid_ok ? 5 : 1);
     else mode = 1;
   }
-  static bool attr[5][RAJNI_MAX_DEVICES] = {};   // [0] small, [1] wide, [2] mid, [3] [4] their K<=N twins; per device
-  // algorithmic bytes: X + W + output (+ the residual rows read), fp32 where the residual stream is fp32
-  constexpr double ysz = (SF32 && (EPI == EPI_RESID || EPI == EPI_PATCH)) ? 4.0 : 2.0;
-  constexpr double rsz = EPI == EPI_RESID ? (SF32 ? 4.0 : 2.0) : 0.0;
-  ProfScope prof(kclass, s, 2.0 * p.M * (double)p.N * p.K,
-                 2.0 * (double)p.M * p.K + (ysz + rsz) * (double)p.M * p.N + (W8 ? 1.0 : 2.0) * (double)p.N * p.K);
-  int rc;
-  if (mode == 4) {
-    using C = wide::Cfg<4, RAJNI_W8_WIDE_NS_OR(W8), W8>;
-    constexpr int NS = RAJNI_W8_WIDE_NS_OR(W8);
-    constexpr int lds = C::LDS_BYTES + (((RAJNI_TSTORE && (EPI == EPI_BIAS || EPI == EPI_GELU)) || (nat_order(EPI, SF32) && EPI == EPI_RESID && !W8)) ? 8 * 2048 : 0);
-    if ((rc = set_lds_attr(&wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 2, 4, 8, NS, W8, 0, A>, lds, attr[1])) != RAJNI_OK) return rc;
-    if constexpr (EPI == EPI_RESID)
-      if ((rc = set_lds_attr(&wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 2, 4, 8, NS, W8, 1, A>, lds, attr[3])) != RAJNI_OK) return rc;
-    p.tiles_n = (p.N + 255) / 256;
-    p.total_tiles = p.tiles_n * ((p.M + 255) / 256);
-    p.nblk = n_block(p.tiles_n, (p.M + 255) / 256, 256, p.K, 2, cus);   // fp8 W: same blocks as bf16 (measured)
-    const int grid = stream_grid(p.total_tiles, cus);
-    if (EPI == EPI_RESID && kclass == KC_GEMM_RESID_SQ) {
-      if constexpr (EPI == EPI_RESID)
-        hipLaunchKernelGGL((wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 2, 4, 8, NS, W8, 1, A>), dim3(grid), dim3(512), lds, s, p);
-    } else {
-      hipLaunchKernelGGL((wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 2, 4, 8, NS, W8, 0, A>), dim3(grid), dim3(512), lds, s, p);
-    }
-  } else if (mode == 5) {
-    using C = wide::Cfg<2, 3, W8>;
-    // fp32-stream RESID: 2 KiB of LDS per wave behind the three stages for the epilogue's transpose (144 + 16 = 160 KiB)
-    constexpr int lds = C::LDS_BYTES + (((nat_order(EPI, SF32) && EPI == EPI_RESID) || (RAJNI_TSTORE && (EPI == EPI_BIAS || EPI == EPI_GELU))) ? 8 * 2048 : 0);
-    if ((rc = set_lds_attr(&wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 4, 2, 4, 3, W8, 0, A>, lds, attr[2])) != RAJNI_OK) return rc;
-    if constexpr (EPI == EPI_RESID)
-      if ((rc = set_lds_attr(&wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 4, 2, 4, 3, W8, 1, A>, lds, attr[4])) != RAJNI_OK) return rc;
-    p.total_tiles = t256;
-    p.nblk = n_block(p.tiles_n, (p.M + 255) / 256, 128, p.K, 2, cus);
-    const int grid = stream_grid(p.total_tiles, cus);
-    if (EPI == EPI_RESID && kclass == KC_GEMM_RESID_SQ) {
-      if constexpr (EPI == EPI_RESID)
-        hipLaunchKernelGGL((wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 4, 2, 4, 3, W8, 1, A>), dim3(grid), dim3(512), lds, s, p);
-    } else {
-      hipLaunchKernelGGL((wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, 4, 2, 4, 3, W8, 0, A>), dim3(grid), dim3(512), lds, s, p);
-    }
-  } else {
-    constexpr int lds = small::LDS_BYTES;
-    if ((rc = set_lds_attr(&small::gemm_bf16_tn_128x128<EPI, ALOAD, SF32, W8, A>, lds, attr[0])) != RAJNI_OK) return rc;
-    p.total_tiles = t128;
-    hipLaunchKernelGGL((small::gemm_bf16_tn_128x128<EPI, ALOAD, SF32, W8, A>), dim3(t128), dim3(256), lds, s, p);
-  }
-  RAJNI_CHECK_LAUNCH("gemm_bf16_tn");
-  return RAJNI_OK;
+  // W blocks of the tile order: fp8 W gets the same blocks as bf16 (measured), hence 2 bytes per element
+  if (mode == 4) return make_plan(p, RAJNI_TILING_WIDE, 256, 256, r.lds_wide, cus, 2, nblk_bytes);
+  if (mode == 5) return make_plan(p, RAJNI_TILING_MID, 256, 128, r.lds_narrow, cus, 2, nblk_bytes);
+  return make_plan(p, RAJNI_TILING_SMALL, 128, 128, small::LDS_BYTES);
 }
 
-int g_force_f8_tiling = 0;   // test hook: 0 by shape, 1 = 256 x 128 always, 2 = 256 x 256 wherever it exists
-
-// fp8 x fp8 launches (gemm_f8.h), persistent: 256 x 256 for wide outputs without a residual epilogue (QKV, FC1),
-// 256 x 128 otherwise (FC2, small problems)
-template <int EPI, bool SF32>
-int launch_gemm_f8(GemmParams p, int kclass, bool tag_sq, hipStream_t s) {
-  const int cus = rajni_num_cus();
-  p.stamps = rajni_g_stamps;
-  if constexpr (EPI == EPI_BIAS || EPI == EPI_GELU8) {
+// fp8 x fp8 (gemm_f8.h), persistent: 256 x 256 for wide outputs without a residual epilogue (QKV, FC1), 256 x 128
+// otherwise (FC2, small problems); `force` = rajni_debug_force_f8_tiling
+rajni_linear_plan choose_gemm_f8(const GemmParams& p, const TileTraits& r, int cus, int force, int nblk_bytes) {
+  if (r.lds_wide != 0) {   // EPI_BIAS, EPI_GELU8
     const bool wide_ok = p.K >= 384;
     // measured on ViT-B at batch 256 (K = 768: 6 K steps per tile, so per-tile costs weigh double against the bf16
     // tilings): FC1 + GELU -> e4m3 132 us on 256 x 256 vs 139 us on 256 x 128.  QKV -> bf16: 256 x 256 since its
@@ -1500,79 +1470,106 @@ int launch_gemm_f8(GemmParams p, int kclass, bool tag_sq, hipStream_t s) {
       const double frac = rounds - (long)rounds;
       return !(rounds < 8.0 && frac > 0.0 && frac < 0.2);
     };
-    const bool want = g_force_f8_tiling == 2 ||
-                      (g_force_f8_tiling == 0 && p.M >= 1024 && p.N >= 1536 && (EPI == EPI_GELU8 || (RAJNI_F8W_LINES && rounds_ok())));
-    if (wide_ok && want) {
-      p.tiles_n = (p.N + f8w::BN - 1) / f8w::BN;
-      const int tiles_m = (p.M + 255) / 256;
-      p.total_tiles = p.tiles_n * tiles_m;
-      p.nblk = n_block(p.tiles_n, tiles_m, f8w::BN, p.K, 1, cus);
-      static bool attrw[RAJNI_MAX_DEVICES] = {};
-      ProfScope prof(kclass, s, 2.0 * p.M * (double)p.N * p.K,
-                     (double)p.M * p.K + (EPI == EPI_GELU8 ? 1.0 : 2.0) * (double)p.M * p.N + (double)p.N * p.K);
-      int rc;
-      // bf16 output: 4 KiB of LDS per wave behind the two stages for the epilogue's whole-line transpose (128 + 32 = 160 KiB)
-      constexpr int ldsw = f8w::LDS_BYTES + ((EPI == EPI_BIAS && RAJNI_F8W_LINES) ? 8 * 4096 : 0);
-      if ((rc = set_lds_attr(&f8w::gemm_f8_tn_wide<EPI>, ldsw, attrw)) != RAJNI_OK) return rc;
-      hipLaunchKernelGGL((f8w::gemm_f8_tn_wide<EPI>), dim3(stream_grid(p.total_tiles, cus)), dim3(512), ldsw, s, p);
-      RAJNI_CHECK_LAUNCH("gemm_f8_tn_wide");
-      return RAJNI_OK;
-    }
+    const bool want = force == 2 ||
+                      (force == 0 && p.M >= 1024 && p.N >= 1536 && (r.epi == EPI_GELU8 || (RAJNI_F8W_LINES && rounds_ok())));
+    if (wide_ok && want) return make_plan(p, RAJNI_TILING_F8_WIDE, 256, f8w::BN, r.lds_wide, cus, 1, nblk_bytes);
   }
-  p.tiles_n = (p.N + f8::BN - 1) / f8::BN;
-  const int tiles_m = (p.M + 255) / 256;
-  p.total_tiles = p.tiles_n * tiles_m;
-  p.nblk = n_block(p.tiles_n, tiles_m, f8::BN, p.K, 1, cus);
-  static bool attr[2][RAJNI_MAX_DEVICES] = {};
-  constexpr double ysz = EPI == EPI_GELU8 ? 1.0 : (SF32 && EPI == EPI_RESID) ? 4.0 : 2.0;
-  constexpr double rsz = EPI == EPI_RESID ? (SF32 ? 4.0 : 2.0) : 0.0;
-  ProfScope prof(kclass, s, 2.0 * p.M * (double)p.N * p.K,
-                 (double)p.M * p.K + (ysz + rsz) * (double)p.M * p.N + (double)p.N * p.K);
-  int rc;
-  const int grid = stream_grid(p.total_tiles, cus);
-  // fp32-stream RESID and bf16 outputs: 2 KiB of LDS per wave behind the three stages for the epilogue's transpose (144 + 16 KiB)
-  constexpr int lds8 = f8::LDS_BYTES + (((nat_order(EPI, SF32) && EPI == EPI_RESID) || EPI == EPI_BIAS) ? 8 * 2048 : 0);
-  if (EPI == EPI_RESID && tag_sq) {
-    if constexpr (EPI == EPI_RESID) {
-      if ((rc = set_lds_attr(&f8::gemm_f8_tn_stream<EPI, SF32, 1>, lds8, attr[1])) != RAJNI_OK) return rc;
-      hipLaunchKernelGGL((f8::gemm_f8_tn_stream<EPI, SF32, 1>), dim3(grid), dim3(512), lds8, s, p);
+  return make_plan(p, RAJNI_TILING_F8_STREAM, 256, f8::BN, r.lds_narrow, cus, 1, nblk_bytes);
+}
+
+// Every other workgroup of an XCD starts a residual-epilogue launch `units` x 8192 cycles late, so that the two halves of
+// the chip do not hit their prologue loads and epilogue bursts in the same instant.  Round 2 (tools/stagger_probe.py,
+// tools/ab_forward.py stagger): proj alone -4 % at 1 unit, fc2 alone flat; in the forward 2 units were best (+0.5-0.8 %).
+// Round 3, with the full-line epilogue: stand-alone proj now LOSES with any offset (84.4 us at 0, 88.5 at 1, 97.4 at 2 units;
+// four or eight phase groups worse still), in the forward 1 unit is best by 0.1-0.3 % (8.850 / 8.804 ms against 8.872 / 8.825
+// at 2 units and 8.878 / 8.838 at 0).  rajni_debug_set_resid_stagger(0) turns it off.
+int g_resid_stagger = 1;
+
+// How a launch is asked for: its profile class, whether a residual launch has K <= N (the TAG = 1 twin, see
+// gemm_bf16_tn_stream), the stream - and, for rajni_debug_linear_plan, the CU count to plan for (0: the current device's)
+// and where the plan goes INSTEAD of a launch.
+struct LaunchCtl { int kclass; bool sq; hipStream_t s; int cus; rajni_linear_plan* plan_only; };
+inline int cus_of(const LaunchCtl& l) { return l.cus > 0 ? l.cus : rajni_num_cus(); }
+
+// Launch `Kernel` as planned - the one launch of every GEMM kernel.  hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per
+// (kernel, device): the flags belong to the kernel's own instantiation of this function, one per device (a process may
+// drive several GPUs; one process per GPU is the deployment, but a model on cuda:1 in a process whose first launch was on
+// cuda:0 must not inherit that device's "done").
+template <auto Kernel>
+int launch_planned(const rajni_linear_plan& c, int threads, GemmParams& p, const LaunchCtl& l, double bytes, const char* name) {
+  if (l.plan_only != nullptr) { *l.plan_only = c; return RAJNI_OK; }   // the dry run ends here, ahead of every HIP call
+  static bool done_by_device[RAJNI_MAX_DEVICES] = {};
+  bool& done = done_by_device[rajni_current_device()];
+  if (!done) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, c.lds_bytes);
+    if (e != hipSuccess) {
+      rajni_set_error("hipFuncSetAttribute(gemm): %s", hipGetErrorString(e));
+      return RAJNI_ERR_LAUNCH;
     }
-  } else {
-    if ((rc = set_lds_attr(&f8::gemm_f8_tn_stream<EPI, SF32, 0>, lds8, attr[0])) != RAJNI_OK) return rc;
-    hipLaunchKernelGGL((f8::gemm_f8_tn_stream<EPI, SF32, 0>), dim3(grid), dim3(512), lds8, s, p);
+    done = true;
   }
-  RAJNI_CHECK_LAUNCH("gemm_f8_tn");
+  p.tiles_n = c.tiles_n; p.total_tiles = c.total_tiles; p.nblk = c.nblk;
+  ProfScope prof(l.kclass, l.s, 2.0 * p.M * (double)p.N * p.K, bytes);
+  hipLaunchKernelGGL(Kernel, dim3(c.grid), dim3(threads), c.lds_bytes, l.s, p);
+  RAJNI_CHECK_LAUNCH(name);
   return RAJNI_OK;
 }
-
-}  // namespace
-
-extern "C" void rajni_debug_force_gemm_tiling(int mode) { g_force_tiling = mode; }
-extern "C" void rajni_debug_force_f8_tiling(int mode) { g_force_f8_tiling = mode; }
-extern "C" void rajni_debug_set_resid_stagger(int units) { g_resid_stagger = units; }
-
-extern "C" void rajni_debug_set_gemm_nblock_bytes(int bytes) { g_nblk_bytes = bytes; }
-// diagnostic builds (-DRAJNI_GEMM_STAMPS): device buffer of 4 x u64 per workgroup, or NULL
-extern "C" void rajni_debug_set_gemm_stamps(void* buf) { rajni_g_stamps = (unsigned long long*)buf; }
-
-// the 16-bit plans (bf16 or fp16 operands, A): same tilings, same shape-driven choice, the format's MFMA and conversions
-template <typename A>
-static int launch_linear16(const GemmParams& p, const rajni_linear_args& a, hipStream_t s) {
-  switch (a.epilogue) {
-    case RAJNI_EPI_BIAS: return launch_gemm<EPI_BIAS, ALOAD_PLAIN, false, false, A>(p, KC_GEMM_BIAS, s);
-    case RAJNI_EPI_BIAS_GELU: return launch_gemm<EPI_GELU, ALOAD_PLAIN, false, false, A>(p, KC_GEMM_GELU, s);
-    case RAJNI_EPI_BIAS_RESID:
-      RAJNI_REQUIRE(a.resid != nullptr && a.ldr % 8 == 0, RAJNI_ERR_INVALID,
-                    "rajni_linear: RESID epilogue needs resid and ldr %% 8 == 0");
-      return a.stream_f32 ? launch_gemm<EPI_RESID, ALOAD_PLAIN, true, false, A>(p, a.K <= a.N ? KC_GEMM_RESID_SQ : KC_GEMM_RESID, s)
-                          : launch_gemm<EPI_RESID, ALOAD_PLAIN, false, false, A>(p, a.K <= a.N ? KC_GEMM_RESID_SQ : KC_GEMM_RESID, s);
-    default:
-      rajni_set_error("rajni_linear: unknown epilogue %d", a.epilogue);
-      return RAJNI_ERR_INVALID;
-  }
+// algorithmic bytes: X + W + output (+ the residual rows read), each at its element size - fp32 where the residual stream is
+inline double gemm_bytes(const GemmParams& p, double xsz, double wsz, double ysz) {
+  return xsz * (double)p.M * p.K + ysz * (double)p.M * p.N + wsz * (double)p.N * p.K;
+}
+constexpr double out_bytes(int epi, bool sf32) {   // per output element of the 16-bit and fp8 x fp8 families
+  const double ysz = epi == EPI_GELU8 ? 1.0 : (sf32 && (epi == EPI_RESID || epi == EPI_PATCH)) ? 4.0 : 2.0;
+  return ysz + (epi == EPI_RESID ? (sf32 ? 4.0 : 2.0) : 0.0);
 }
 
-int launch_linear(const rajni_linear_args& a, hipStream_t s) {
+// 16-bit activations, A = bf16_t or f16_t (W8: fp8 weights on bf16)
+template <int EPI, int ALOAD, bool SF32, bool W8, typename A, int WM, int WN, int MI, int NS>
+int launch_stream(const rajni_linear_plan& c, GemmParams& p, const LaunchCtl& l, double bytes) {
+  if constexpr (EPI == EPI_RESID)
+    if (l.sq) return launch_planned<&wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, WM, WN, MI, NS, W8, 1, A>>(c, 512, p, l, bytes, "gemm_bf16_tn");
+  return launch_planned<&wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, WM, WN, MI, NS, W8, 0, A>>(c, 512, p, l, bytes, "gemm_bf16_tn");
+}
+template <int EPI, int ALOAD, bool SF32, bool W8 = false, typename A = bf16_t>
+int launch_gemm(GemmParams& p, const LaunchCtl& l) {
+  constexpr int NS = RAJNI_W8_WIDE_NS_OR(W8);
+  constexpr TileTraits T{EPI, resid_nat(EPI, SF32), wide::lds_bytes<EPI, SF32, 4, 8, NS, W8>(), wide::lds_bytes<EPI, SF32, 2, 4, 3, W8>()};
+  const rajni_linear_plan c = choose_gemm(p, T, cus_of(l), g_force_tiling, g_nblk_bytes);
+  p.stamps = rajni_g_stamps;
+  p.stagger = g_resid_stagger;
+  const double bytes = gemm_bytes(p, 2.0, W8 ? 1.0 : 2.0, out_bytes(EPI, SF32));
+  if (c.tiling == RAJNI_TILING_WIDE) return launch_stream<EPI, ALOAD, SF32, W8, A, 2, 4, 8, NS>(c, p, l, bytes);
+  if (c.tiling == RAJNI_TILING_MID) return launch_stream<EPI, ALOAD, SF32, W8, A, 4, 2, 4, 3>(c, p, l, bytes);
+  return launch_planned<&small::gemm_bf16_tn_128x128<EPI, ALOAD, SF32, W8, A>>(c, 256, p, l, bytes, "gemm_bf16_tn");
+}
+template <int EPI, bool SF32>
+int launch_gemm_f8(GemmParams& p, const LaunchCtl& l) {
+  constexpr bool HAS_WIDE = EPI == EPI_BIAS || EPI == EPI_GELU8;
+  constexpr TileTraits T{EPI, resid_nat(EPI, SF32), HAS_WIDE ? f8w::lds_bytes(EPI) : 0, f8::lds_bytes(EPI, SF32)};
+  const rajni_linear_plan c = choose_gemm_f8(p, T, cus_of(l), g_force_f8_tiling, g_nblk_bytes);
+  p.stamps = rajni_g_stamps;
+  const double bytes = gemm_bytes(p, 1.0, 1.0, out_bytes(EPI, SF32));
+  if constexpr (HAS_WIDE)
+    if (c.tiling == RAJNI_TILING_F8_WIDE) return launch_planned<&f8w::gemm_f8_tn_wide<EPI>>(c, 512, p, l, bytes, "gemm_f8_tn_wide");
+  if constexpr (EPI == EPI_RESID)
+    if (l.sq) return launch_planned<&f8::gemm_f8_tn_stream<EPI, SF32, 1>>(c, 512, p, l, bytes, "gemm_f8_tn");
+  return launch_planned<&f8::gemm_f8_tn_stream<EPI, SF32, 0>>(c, 512, p, l, bytes, "gemm_f8_tn");
+}
+template <int EPI, int ALOAD>
+int launch_gemm_f32(GemmParams& p, const LaunchCtl& l) {   // (as found: the residual rows a RESID launch reads are not counted)
+  return launch_planned<&f32::gemm_f32_tn_128x128<EPI, ALOAD>>(make_plan(p, RAJNI_TILING_F32, 128, 128, f32::LDS_BYTES), 256, p, l,
+                                                              gemm_bytes(p, 4.0, 4.0, 4.0), "gemm_f32_tn");
+}
+
+// rajni_linear and its dry run: the refusals, then the one table - format x epilogue (x fp32 residual stream for RESID)
+enum { FMT_F8F8, FMT_W8, FMT_F32, FMT_BF16, FMT_F16 };   // fp8 x fp8, fp8 weights on bf16, and the three plain dtypes
+template <bool W8, typename A>
+int linear16(int epi, bool sf32, GemmParams& p, const LaunchCtl& l) {
+  return epi == EPI_BIAS ? launch_gemm<EPI_BIAS, ALOAD_PLAIN, false, W8, A>(p, l)
+       : epi == EPI_GELU ? launch_gemm<EPI_GELU, ALOAD_PLAIN, false, W8, A>(p, l)
+       : sf32 ? launch_gemm<EPI_RESID, ALOAD_PLAIN, true, W8, A>(p, l) : launch_gemm<EPI_RESID, ALOAD_PLAIN, false, W8, A>(p, l);
+}
+int linear(const rajni_linear_args& a, LaunchCtl l) {
   RAJNI_REQUIRE(a.dtype == RAJNI_BF16 || a.dtype == RAJNI_F32 || a.dtype == RAJNI_F16, RAJNI_ERR_INVALID,
                 "rajni_linear: bad dtype %d", a.dtype);
   RAJNI_REQUIRE(a.dtype != RAJNI_F16 || (a.w_scale == nullptr && a.x_scale == nullptr), RAJNI_ERR_UNSUPPORTED,
@@ -1593,61 +1590,75 @@ int launch_linear(const rajni_linear_args& a, hipStream_t s) {
   p.Y = a.y; p.ldc = a.ldc;
   p.M = a.M; p.N = a.N; p.K = a.K;
   p.wscale = a.w_scale;
-  if (a.x_scale != nullptr) {   // fp8 e4m3 activations AND weights on the fp8 matrix pipe
+  const int fmt = a.x_scale != nullptr ? FMT_F8F8 : a.w_scale != nullptr ? FMT_W8
+                : a.dtype == RAJNI_F32 ? FMT_F32 : a.dtype == RAJNI_F16 ? FMT_F16 : FMT_BF16;
+  const bool f8 = fmt == FMT_F8F8;
+  if (f8) {   // fp8 e4m3 activations AND weights on the fp8 matrix pipe
     RAJNI_REQUIRE(a.w_scale != nullptr && a.dtype == RAJNI_BF16, RAJNI_ERR_INVALID,
                   "rajni_linear: fp8 activations (x_scale) need fp8 weights (w_scale) and dtype bf16");
     RAJNI_REQUIRE(a.K % 256 == 0 && a.K >= 512, RAJNI_ERR_UNSUPPORTED,
                   "rajni_linear: the fp8 x fp8 kernel needs K %% 256 == 0 and K >= 512 (K=%d)", a.K);
     RAJNI_REQUIRE(a.lda % 16 == 0 && a.ldw % 16 == 0, RAJNI_ERR_INVALID, "rajni_linear: fp8 operands need lda, ldw %% 16 == 0 (bytes)");
     p.xscale = a.x_scale; p.yscale = a.y_scale;
-    switch (a.epilogue) {
-      case RAJNI_EPI_BIAS:
-        RAJNI_REQUIRE(a.y_scale == nullptr, RAJNI_ERR_UNSUPPORTED, "rajni_linear: an fp8 output (y_scale) exists for the GELU epilogue only");
-        return launch_gemm_f8<EPI_BIAS, false>(p, KC_GEMM8_BIAS, false, s);
-      case RAJNI_EPI_BIAS_GELU:
-        RAJNI_REQUIRE(a.y_scale != nullptr && a.ldc % 16 == 0, RAJNI_ERR_UNSUPPORTED,
-                      "rajni_linear: the fp8 x fp8 GELU epilogue writes e4m3 (y_scale required, ldc %% 16 == 0 bytes)");
-        return launch_gemm_f8<EPI_GELU8, false>(p, KC_GEMM8_GELU, false, s);
-      case RAJNI_EPI_BIAS_RESID:
-        RAJNI_REQUIRE(a.resid != nullptr && a.ldr % 8 == 0 && a.y_scale == nullptr, RAJNI_ERR_INVALID,
-                      "rajni_linear: RESID epilogue needs resid, ldr %% 8 == 0 and no y_scale");
-        return a.stream_f32 ? launch_gemm_f8<EPI_RESID, true>(p, a.K <= a.N ? KC_GEMM8_RESID_SQ : KC_GEMM8_RESID, a.K <= a.N, s)
-                            : launch_gemm_f8<EPI_RESID, false>(p, a.K <= a.N ? KC_GEMM8_RESID_SQ : KC_GEMM8_RESID, a.K <= a.N, s);
-      default:
-        rajni_set_error("rajni_linear: unknown epilogue %d", a.epilogue);
-        return RAJNI_ERR_INVALID;
+  } else {
+    RAJNI_REQUIRE(a.y_scale == nullptr, RAJNI_ERR_INVALID, "rajni_linear: y_scale without x_scale");
+    if (fmt == FMT_W8) {   // fp8 e4m3 weights, bf16 activations
+      RAJNI_REQUIRE(a.dtype == RAJNI_BF16, RAJNI_ERR_UNSUPPORTED, "rajni_linear: fp8 weights need bf16 activations");
+      RAJNI_REQUIRE(a.ldw % 16 == 0, RAJNI_ERR_INVALID, "rajni_linear: fp8 weights need ldw %% 16 == 0");
     }
   }
-  RAJNI_REQUIRE(a.y_scale == nullptr, RAJNI_ERR_INVALID, "rajni_linear: y_scale without x_scale");
-  if (a.w_scale != nullptr) {   // fp8 e4m3 weights, bf16 activations
-    RAJNI_REQUIRE(a.dtype == RAJNI_BF16, RAJNI_ERR_UNSUPPORTED, "rajni_linear: fp8 weights need bf16 activations");
-    RAJNI_REQUIRE(a.ldw % 16 == 0, RAJNI_ERR_INVALID, "rajni_linear: fp8 weights need ldw %% 16 == 0");
-    switch (a.epilogue) {
-      case RAJNI_EPI_BIAS: return launch_gemm<EPI_BIAS, ALOAD_PLAIN, false, true>(p, KC_GEMM_BIAS, s);
-      case RAJNI_EPI_BIAS_GELU: return launch_gemm<EPI_GELU, ALOAD_PLAIN, false, true>(p, KC_GEMM_GELU, s);
-      case RAJNI_EPI_BIAS_RESID:
-        RAJNI_REQUIRE(a.resid != nullptr && a.ldr % 8 == 0, RAJNI_ERR_INVALID,
-                      "rajni_linear: RESID epilogue needs resid and ldr %% 8 == 0");
-        return a.stream_f32 ? launch_gemm<EPI_RESID, ALOAD_PLAIN, true, true>(p, a.K <= a.N ? KC_GEMM_RESID_SQ : KC_GEMM_RESID, s)
-                            : launch_gemm<EPI_RESID, ALOAD_PLAIN, false, true>(p, a.K <= a.N ? KC_GEMM_RESID_SQ : KC_GEMM_RESID, s);
-      default:
-        rajni_set_error("rajni_linear: unknown epilogue %d", a.epilogue);
-        return RAJNI_ERR_INVALID;
-    }
+  int epi;
+  switch (a.epilogue) {
+    case RAJNI_EPI_BIAS:
+      RAJNI_REQUIRE(!f8 || a.y_scale == nullptr, RAJNI_ERR_UNSUPPORTED, "rajni_linear: an fp8 output (y_scale) exists for the GELU epilogue only");
+      epi = EPI_BIAS; l.kclass = f8 ? KC_GEMM8_BIAS : KC_GEMM_BIAS;
+      break;
+    case RAJNI_EPI_BIAS_GELU:
+      RAJNI_REQUIRE(!f8 || (a.y_scale != nullptr && a.ldc % 16 == 0), RAJNI_ERR_UNSUPPORTED,
+                    "rajni_linear: the fp8 x fp8 GELU epilogue writes e4m3 (y_scale required, ldc %% 16 == 0 bytes)");
+      epi = f8 ? EPI_GELU8 : EPI_GELU; l.kclass = f8 ? KC_GEMM8_GELU : KC_GEMM_GELU;
+      break;
+    case RAJNI_EPI_BIAS_RESID:
+      // as found, not known to be intended: fp32 does not ask for ldr % 8; only fp8 x fp8 can meet a y_scale here and names it
+      if (f8) RAJNI_REQUIRE(a.resid != nullptr && a.ldr % 8 == 0 && a.y_scale == nullptr, RAJNI_ERR_INVALID,
+                            "rajni_linear: RESID epilogue needs resid, ldr %% 8 == 0 and no y_scale");
+      else if (fmt == FMT_F32) RAJNI_REQUIRE(a.resid != nullptr, RAJNI_ERR_INVALID, "rajni_linear: RESID epilogue needs resid");
+      else RAJNI_REQUIRE(a.resid != nullptr && a.ldr % 8 == 0, RAJNI_ERR_INVALID,
+                         "rajni_linear: RESID epilogue needs resid and ldr %% 8 == 0");
+      epi = EPI_RESID; l.sq = a.K <= a.N;   // K <= N (the attention projection): a profile class and a kernel twin of its own
+      l.kclass = f8 ? (l.sq ? KC_GEMM8_RESID_SQ : KC_GEMM8_RESID) : (l.sq ? KC_GEMM_RESID_SQ : KC_GEMM_RESID);
+      break;
+    default:
+      rajni_set_error("rajni_linear: unknown epilogue %d", a.epilogue);
+      return RAJNI_ERR_INVALID;
   }
-  if (a.dtype == RAJNI_F32) {
-    switch (a.epilogue) {
-      case RAJNI_EPI_BIAS: return f32::launch<EPI_BIAS, ALOAD_PLAIN>(p, KC_GEMM_BIAS, s);
-      case RAJNI_EPI_BIAS_GELU: return f32::launch<EPI_GELU, ALOAD_PLAIN>(p, KC_GEMM_GELU, s);
-      case RAJNI_EPI_BIAS_RESID:
-        RAJNI_REQUIRE(a.resid != nullptr, RAJNI_ERR_INVALID, "rajni_linear: RESID epilogue needs resid");
-        return f32::launch<EPI_RESID, ALOAD_PLAIN>(p, a.K <= a.N ? KC_GEMM_RESID_SQ : KC_GEMM_RESID, s);
-      default:
-        rajni_set_error("rajni_linear: unknown epilogue %d", a.epilogue);
-        return RAJNI_ERR_INVALID;
-    }
+  const bool sf32 = a.stream_f32 != 0;
+  switch (fmt) {
+    case FMT_F8F8: return epi == EPI_BIAS ? launch_gemm_f8<EPI_BIAS, false>(p, l) : epi == EPI_GELU8 ? launch_gemm_f8<EPI_GELU8, false>(p, l)
+                        : sf32 ? launch_gemm_f8<EPI_RESID, true>(p, l) : launch_gemm_f8<EPI_RESID, false>(p, l);
+    case FMT_F32: return epi == EPI_BIAS ? launch_gemm_f32<EPI_BIAS, ALOAD_PLAIN>(p, l) : epi == EPI_GELU ? launch_gemm_f32<EPI_GELU, ALOAD_PLAIN>(p, l)
+                       : launch_gemm_f32<EPI_RESID, ALOAD_PLAIN>(p, l);
+    case FMT_W8: return linear16<true, bf16_t>(epi, sf32, p, l);
+    case FMT_F16: return linear16<false, f16_t>(epi, sf32, p, l);
+    default: return linear16<false, bf16_t>(epi, sf32, p, l);
   }
-  return a.dtype == RAJNI_F16 ? launch_linear16<f16_t>(p, a, s) : launch_linear16<bf16_t>(p, a, s);
+}
+
+}  // namespace
+
+extern "C" void rajni_debug_force_gemm_tiling(int mode) { g_force_tiling = mode; }
+extern "C" void rajni_debug_force_f8_tiling(int mode) { g_force_f8_tiling = mode; }
+extern "C" void rajni_debug_set_resid_stagger(int units) { g_resid_stagger = units; }
+extern "C" void rajni_debug_set_gemm_nblock_bytes(int bytes) { g_nblk_bytes = bytes; }
+// diagnostic builds (-DRAJNI_GEMM_STAMPS): device buffer of 4 x u64 per workgroup, or NULL
+extern "C" void rajni_debug_set_gemm_stamps(void* buf) { rajni_g_stamps = (unsigned long long*)buf; }
+
+int launch_linear(const rajni_linear_args& a, hipStream_t s) { return linear(a, LaunchCtl{0, false, s, 0, nullptr}); }
+// rajni_linear up to, not including, its launch (launch_planned), planned for a device of `cus` CUs
+extern "C" int rajni_debug_linear_plan(const rajni_linear_args* args, int cus, rajni_linear_plan* out) {
+  RAJNI_REQUIRE(args != nullptr, RAJNI_ERR_INVALID, "rajni_linear: null args");
+  RAJNI_REQUIRE(out != nullptr && cus > 0, RAJNI_ERR_INVALID, "rajni_debug_linear_plan: needs out and cus > 0");
+  return linear(*args, LaunchCtl{0, false, nullptr, cus, out});
 }
 
 // the fused im2col loader reads 16-byte runs of a patch row with shifts: power-of-two patches of >= 8 pixels
@@ -1690,6 +1701,13 @@ __global__ void __launch_bounds__(256) im2col_kernel(const T* img, T* cols, int 
   for (int j = 0; j < 8; ++j) dst[j] = v[j];
 }
 
+// (dtype, out_f32) -> (the residual stream is fp32, the element type of images and parameters): f(bool constant, T{})
+template <typename F>
+static void with_stream_types(int dtype, int out_f32, F&& f) {
+  if (dtype == RAJNI_F32) f(std::true_type{}, float{});
+  else if (dtype == RAJNI_F16) out_f32 ? f(std::true_type{}, f16_t{}) : f(std::false_type{}, f16_t{});
+  else out_f32 ? f(std::true_type{}, bf16_t{}) : f(std::false_type{}, bf16_t{});
+}
 int launch_patch_embed(const void* images, const void* w, const float* bias, const void* cls,
                        const void* pos, int pos_has_cls, void* x, int out_f32, int B, int Cin, int S,
                        int P, int C, int dtype, void* ws, size_t ws_bytes, hipStream_t s, int num_prefix, const void* reg) {
@@ -1714,76 +1732,55 @@ int launch_patch_embed(const void* images, const void* w, const float* bias, con
   p.gw = gw; p.npatch = npatch;
   p.pos = pos; p.pos_off = pos_has_cls ? num_prefix : 0;
   p.nprefix = num_prefix;
-  int rc;
-  if (patch_fused(Cin, S, P)) {
+  const bool fused = patch_fused(Cin, S, P);
+  if (fused) {
     int log2ps = 0;
     while ((1 << log2ps) < P) ++log2ps;
     p.X = images; p.lda = 0;
     p.cin = Cin; p.S = S; p.log2ps = log2ps;
-    if (dtype == RAJNI_F32) rc = f32::launch<EPI_PATCH, ALOAD_PATCH>(p, KC_GEMM_PATCH, s);
-    else if (dtype == RAJNI_F16)
-      rc = out_f32 ? launch_gemm<EPI_PATCH, ALOAD_PATCH, true, false, f16_t>(p, KC_GEMM_PATCH, s)
-                   : launch_gemm<EPI_PATCH, ALOAD_PATCH, false, false, f16_t>(p, KC_GEMM_PATCH, s);
-    else rc = out_f32 ? launch_gemm<EPI_PATCH, ALOAD_PATCH, true>(p, KC_GEMM_PATCH, s)
-                      : launch_gemm<EPI_PATCH, ALOAD_PATCH, false>(p, KC_GEMM_PATCH, s);
   } else {
     const size_t need = patch_embed_workspace_bytes(B, Cin, S, P, dtype);
     RAJNI_REQUIRE(ws != nullptr && ws_bytes >= need && (uintptr_t)ws % 16 == 0, RAJNI_ERR_INVALID,
                   "rajni_patch_embed: patch size %d needs a %zu-byte, 16-byte aligned column workspace (got %zu)", P, need, ws_bytes);
-    {
-      ProfScope prof(KC_CLS_POS, s, 0.0, 2.0 * (double)need);
-      const long total8 = (long)B * npatch * (kpad / 8);
-      const dim3 grid((unsigned)((total8 + 255) / 256)), block(256);
-      if (dtype == RAJNI_F32)
-        hipLaunchKernelGGL(im2col_kernel<float>, grid, block, 0, s, (const float*)images, (float*)ws, Cin, S, P, gw, kpad, total8);
-      else   // a byte copy: the bf16 instantiation serves fp16 images too
-        hipLaunchKernelGGL(im2col_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)images, (bf16_t*)ws, Cin, S, P, gw, kpad, total8);
-      RAJNI_CHECK_LAUNCH("im2col_kernel");
-    }
+    ProfScope prof(KC_CLS_POS, s, 0.0, 2.0 * (double)need);
+    const long total8 = (long)B * npatch * (kpad / 8);
+    const dim3 grid((unsigned)((total8 + 255) / 256)), block(256);
+    if (dtype == RAJNI_F32)
+      hipLaunchKernelGGL(im2col_kernel<float>, grid, block, 0, s, (const float*)images, (float*)ws, Cin, S, P, gw, kpad, total8);
+    else   // a byte copy: the bf16 instantiation serves fp16 images too
+      hipLaunchKernelGGL(im2col_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)images, (bf16_t*)ws, Cin, S, P, gw, kpad, total8);
+    RAJNI_CHECK_LAUNCH("im2col_kernel");
     p.X = ws; p.lda = kpad;
-    if (dtype == RAJNI_F32) rc = f32::launch<EPI_PATCH, ALOAD_PLAIN>(p, KC_GEMM_PATCH, s);
-    else if (dtype == RAJNI_F16)
-      rc = out_f32 ? launch_gemm<EPI_PATCH, ALOAD_PLAIN, true, false, f16_t>(p, KC_GEMM_PATCH, s)
-                   : launch_gemm<EPI_PATCH, ALOAD_PLAIN, false, false, f16_t>(p, KC_GEMM_PATCH, s);
-    else rc = out_f32 ? launch_gemm<EPI_PATCH, ALOAD_PLAIN, true>(p, KC_GEMM_PATCH, s)
-                      : launch_gemm<EPI_PATCH, ALOAD_PLAIN, false>(p, KC_GEMM_PATCH, s);
   }
+  int rc = RAJNI_OK;
+  const LaunchCtl l{KC_GEMM_PATCH, false, s, 0, nullptr};
+  with_stream_types(dtype, out_f32, [&](auto sf32, auto t) {
+    using T = decltype(t);
+    constexpr bool SF32 = decltype(sf32)::value;
+    if constexpr (std::is_same<T, float>::value)
+      rc = fused ? launch_gemm_f32<EPI_PATCH, ALOAD_PATCH>(p, l) : launch_gemm_f32<EPI_PATCH, ALOAD_PLAIN>(p, l);
+    else
+      rc = fused ? launch_gemm<EPI_PATCH, ALOAD_PATCH, SF32, false, T>(p, l) : launch_gemm<EPI_PATCH, ALOAD_PLAIN, SF32, false, T>(p, l);
+  });
   if (rc != RAJNI_OK) return rc;
+  ProfScope prof(KC_CLS_POS, s, 0.0, 6.0 * B * num_prefix * C);
+  const long stride = (long)(npatch + num_prefix) * C;
+  const dim3 block(256);
   if (num_prefix > 1) {
-    ProfScope prof(KC_CLS_POS, s, 0.0, 6.0 * B * num_prefix * C);
-    const int n = B * num_prefix * (C / 8);
-    const dim3 grid((n + 255) / 256), block(256);
-    const long stride = (long)(npatch + num_prefix) * C;
-#define RAJNI_PREFIX_POS(SF, T)                                                                                        \
-  hipLaunchKernelGGL((prefix_pos_kernel<SF, T>), grid, block, 0, s, (const T*)cls, (const T*)reg, (const T*)pos, pos_has_cls, x, \
-                     stride, B, num_prefix, C)
-    if (dtype == RAJNI_F32) RAJNI_PREFIX_POS(true, float);
-    else if (dtype == RAJNI_F16 && out_f32) RAJNI_PREFIX_POS(true, f16_t);
-    else if (dtype == RAJNI_F16) RAJNI_PREFIX_POS(false, f16_t);
-    else if (out_f32) RAJNI_PREFIX_POS(true, bf16_t);
-    else RAJNI_PREFIX_POS(false, bf16_t);
-#undef RAJNI_PREFIX_POS
+    const dim3 grid((B * num_prefix * (C / 8) + 255) / 256);
+    with_stream_types(dtype, out_f32, [&](auto sf32, auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((prefix_pos_kernel<decltype(sf32)::value, T>), grid, block, 0, s, (const T*)cls, (const T*)reg, (const T*)pos,
+                         pos_has_cls, x, stride, B, num_prefix, C);
+    });
     RAJNI_CHECK_LAUNCH("prefix_pos_kernel");
   } else {
-    ProfScope prof(KC_CLS_POS, s, 0.0, 6.0 * B * C);
-    const int n = B * C;
-    const dim3 grid((n + 255) / 256), block(256);
-    const long stride = (long)(npatch + 1) * C;
-    if (dtype == RAJNI_F32)
-      hipLaunchKernelGGL((cls_pos_kernel<true, float>), grid, block, 0, s, (const float*)cls, (const float*)pos,
-                         pos_has_cls, x, stride, B, C);
-    else if (dtype == RAJNI_F16 && out_f32)
-      hipLaunchKernelGGL((cls_pos_kernel<true, f16_t>), grid, block, 0, s, (const f16_t*)cls, (const f16_t*)pos,
-                         pos_has_cls, x, stride, B, C);
-    else if (dtype == RAJNI_F16)
-      hipLaunchKernelGGL((cls_pos_kernel<false, f16_t>), grid, block, 0, s, (const f16_t*)cls, (const f16_t*)pos,
-                         pos_has_cls, x, stride, B, C);
-    else if (out_f32)
-      hipLaunchKernelGGL((cls_pos_kernel<true, bf16_t>), grid, block, 0, s, (const bf16_t*)cls, (const bf16_t*)pos,
-                         pos_has_cls, x, stride, B, C);
-    else
-      hipLaunchKernelGGL((cls_pos_kernel<false, bf16_t>), grid, block, 0, s, (const bf16_t*)cls, (const bf16_t*)pos,
-                         pos_has_cls, x, stride, B, C);
+    const dim3 grid((B * C + 255) / 256);
+    with_stream_types(dtype, out_f32, [&](auto sf32, auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((cls_pos_kernel<decltype(sf32)::value, T>), grid, block, 0, s, (const T*)cls, (const T*)pos, pos_has_cls, x,
+                         stride, B, C);
+    });
     RAJNI_CHECK_LAUNCH("cls_pos_kernel");
   }
   return RAJNI_OK;

@@ -30,6 +30,8 @@ constexpr int KB = 128;                           // bytes (= fp8 elements) of K
 constexpr int W_BYTES = BN * KB;                  // 16 KiB
 constexpr int STAGE_BYTES = X_BYTES + W_BYTES;    // 48 KiB
 constexpr int LDS_BYTES = NS * STAGE_BYTES;       // 144 KiB
+// dynamic LDS of gemm_f8_tn_stream<EPI, SF32>: the stages plus the eight waves' epilogue scratch (144 + 16 KiB)
+constexpr int lds_bytes(int epi, bool sf32) { return LDS_BYTES + 8 * f8_scratch_bytes(epi, sf32); }
 constexpr int XP = 4, PW = 2, PIECES = XP + PW;   // 1 KiB pieces per wave per K step
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -61,6 +63,8 @@ __device__ __forceinline__ unsigned pack4_e4m3(float a, float b, float c, float 
 template <int EPI, bool SF32, int TAG = 0>
 __global__ void __launch_bounds__(512, 2) gemm_f8_tn_stream(const GemmParams p) {
   constexpr int MAP = col_map(EPI, SF32);
+  constexpr int SCRATCH = f8_scratch_bytes(EPI, SF32);   // epilogue_tile's whole-line transposes (gemm.hip)
+  static_assert(lds_bytes(EPI, SF32) <= LDS_MAX_BYTES, "stages + epilogue scratch exceed the workgroup's LDS");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -161,7 +165,8 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_stream(const GemmParams p) 
   constexpr int WBASE = (NS - 2) * PIECES;
   // stores of the previous tile's epilogue may still be in flight at a tile's first counted wait (gfx9 counts stores
   // in vmcnt and retires vector-memory ops in order): a lower bound on their number keeps that wait from draining them
-  constexpr int NSTORE = EPI == EPI_GELU8 ? MI : (nat_order(EPI, SF32) ? 4 * MI : 2 * MI);
+  constexpr int STORES_GELU8 = MI;   // the GELU8 epilogue below: one 16-byte e4m3 store per row group
+  constexpr int NSTORE = EPI == EPI_GELU8 ? STORES_GELU8 : tile_stores(EPI, SF32, MI, resid_nat(EPI, SF32), EPI == EPI_BIAS);
   bool prev_full = false;
   point_at(tile);
 #pragma unroll
@@ -292,8 +297,6 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_stream(const GemmParams p) 
       // serialised load-wait-store)
       ResidPrefetch<MI> pre;
       pre.valid = false;
-      char* scratch = nullptr;
-      if constexpr (EPI == EPI_BIAS) scratch = smem + LDS_BYTES + wave * 2048;   // bf16 output (QKV) as whole lines: epilogue_tile
       if constexpr (nat_order(EPI, SF32) && EPI == EPI_RESID) {
         // loaded on EVERY path (addresses clamped into the tensor; edge tiles ignore the values): a conditional load
         // leaves `pre` half-defined and hipcc then keeps its registers reserved around the whole tile loop.
@@ -333,8 +336,9 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_stream(const GemmParams p) 
             }
         }
         pre.valid = inter;
-        scratch = smem + LDS_BYTES + wave * 2048;     // host: 16 KiB more dynamic LDS for these instantiations
       }
+      // bf16 output (QKV) as whole lines and the fp32-stream RESID transpose: epilogue_tile
+      char* scratch = SCRATCH > 0 ? smem + LDS_BYTES + wave * SCRATCH : nullptr;
       epilogue_tile<bf16_t, EPI, SF32, MI, true>(p, acc, m_base, n0w, l15, g, pre, 0, inter, scratch);
     }
     __builtin_amdgcn_sched_barrier(0);    // keep the fragment reads below the epilogue (hoisted, they cost it 64 VGPRs)
@@ -377,9 +381,6 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_stream(const GemmParams p) 
 //   half 2: 8 MFMAs(j, ks1)  ||  12 LDS reads of (j+1, ks0)  ||  8 DMA pieces of step j+2 into stage j
 // Epilogues: bias -> bf16 (QKV) and bias + GELU -> e4m3 (FC1).  Host contract: K % 128 == 0, K >= 384.
 // =============================================================================================
-#ifndef RAJNI_F8W_LINES
-#define RAJNI_F8W_LINES 1
-#endif
 namespace f8w {
 using f8::Frag;
 using f8::frag_bits;
@@ -391,6 +392,12 @@ constexpr int BM = 256, BN = 256, KB = 128, NS = 2;
 constexpr int X_BYTES = BM * KB, W_BYTES = BN * KB, STAGE_BYTES = X_BYTES + W_BYTES, LDS_BYTES = NS * STAGE_BYTES;
 constexpr int XP = 4, PW = 4, PIECES = XP + PW;
 constexpr int MT = 4, NT = 2;     // 32 x 32 tiles per wave: 128 rows x 64 columns
+// dynamic LDS of gemm_f8_tn_wide<EPI>: the stages plus the eight waves' epilogue scratch (128 + 32 = 160 KiB with it)
+constexpr int lds_bytes(int epi) { return LDS_BYTES + 8 * f8w_scratch_bytes(epi); }
+// vector stores per wave of an interior tile, by epilogue path (NSTORE below must not exceed what a path issues)
+constexpr int STORES_GELU8 = MT * NT;       // one 16-byte e4m3 store per 32 x 32 tile
+constexpr int STORES_ACC = 2 * MT * NT;     // bf16 from the accumulator layout: two 16-byte stores per 32 x 32 tile
+constexpr int STORES_LINES = 4 * MT;        // bf16 as whole lines: per 32-row group 4 x (8 rows x 128 bytes)
 // W tile row (of 32) read by A-row i, and the swizzle key of a W tile row: the 16 rows one ds_read_b128 lane group
 // touches ({0-3, 16-19, 4-7, 20-23} + 8 for the second group) must land in 16 distinct 16-byte slots of 256 bytes
 __device__ __forceinline__ int w_row32(int i) { return 16 * ((i >> 2) & 1) + (i & 3) + 4 * (i >> 3); }
@@ -409,6 +416,8 @@ __device__ __forceinline__ void sched_half() {
 template <int EPI>
 __global__ void __launch_bounds__(512, 2) gemm_f8_tn_wide(const GemmParams p) {
   static_assert(EPI == EPI_BIAS || EPI == EPI_GELU8, "wide fp8 tile: bias (bf16 out) or GELU (e4m3 out)");
+  constexpr int SCRATCH = f8w_scratch_bytes(EPI);
+  static_assert(lds_bytes(EPI) <= LDS_MAX_BYTES, "stages + epilogue scratch exceed the workgroup's LDS");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -508,7 +517,7 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_wide(const GemmParams p) {
       wa[i].hi = *reinterpret_cast<const bf16x8*>(sb + wo[0][1] + i * 32 * KB);
     }
   };
-  constexpr int NSTORE = EPI == EPI_GELU8 ? MT * NT : 2 * MT * NT;   // stores per wave of an interior tile's epilogue
+  constexpr int NSTORE = EPI == EPI_GELU8 ? STORES_GELU8 : (SCRATCH > 0 && STORES_LINES < STORES_ACC) ? STORES_LINES : STORES_ACC;
   bool prev_full = false;
   point_at(tile);
 #pragma unroll
@@ -582,14 +591,14 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_wide(const GemmParams p) {
       }
     }
     bool lines_done = false;
-    if constexpr (EPI == EPI_BIAS && RAJNI_F8W_LINES) {
+    if constexpr (SCRATCH > 0) {
       if (inter) {
         // interior tile, bf16 output as whole 128-byte lines: per 32-row group the wave's 32 x 64 block (two 16-byte pieces
         // per lane and column tile: chunks 4 ni + 2 h, + 1 of row r) goes through 4 KiB of LDS behind the stages - slot =
         // chunk ^ (row & 7), conflict free both ways - and leaves as 8 rows x 128 bytes per instruction.  Stored
         // straight from the accumulator layout an instruction touches 32 rows x 64 bytes (two lanes per row): half lines,
         // which a CU moves at a third of the rate (tools/pull_probe.hip) - the reason QKV used the 256 x 128 kernel.
-        char* scratch = smem + LDS_BYTES + wave * 4096;
+        char* scratch = smem + LDS_BYTES + wave * SCRATCH;
         int lane_v = lane;
         asm volatile("" : "+v"(lane_v));
         const int rr = lane_v >> 3, cc = lane_v & 7;

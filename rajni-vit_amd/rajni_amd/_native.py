@@ -35,6 +35,15 @@ class LinearArgs(C.Structure):
                 ("x_scale", c_void_p), ("y_scale", c_void_p)]
 
 
+class LinearPlan(C.Structure):
+    """rajni_linear_plan (include/rajni_hip_debug.h): what rajni_debug_linear_plan says a linear call would launch"""
+    _fields_ = [("tiling", c_int), ("tiles_n", c_int), ("total_tiles", c_int), ("nblk", c_int), ("grid", c_int),
+                ("lds_bytes", c_int)]
+
+
+TILING_SMALL, TILING_F32, TILING_WIDE, TILING_MID, TILING_F8_STREAM, TILING_F8_WIDE = 1, 2, 4, 5, 8, 9
+
+
 class Block(C.Structure):
     _fields_ = [("norm1_w", c_void_p), ("norm1_b", c_void_p),
                 ("qkv_w", c_void_p), ("qkv_b", c_void_p),
@@ -109,6 +118,7 @@ _SIGS = {
     "rajni_debug_force_f8_tiling": (None, [c_int]),
     "rajni_debug_set_resid_stagger": (None, [c_int]),
     "rajni_debug_set_gemm_nblock_bytes": (None, [c_int]),
+    "rajni_debug_linear_plan": (c_int, [C.POINTER(LinearArgs), c_int, C.POINTER(LinearPlan)]),
     "rajni_debug_force_attention": (None, [c_int]),
     "rajni_debug_force_score_two_pass": (None, [c_int]),
     "rajni_debug_force_score_tiled": (None, [c_int]),

@@ -40,7 +40,7 @@ def tiling(request):
 
 
 # NOTE: the dispatcher turns a forced 256x256 / 256x128 tiling into 128x128 where the persistent kernels cannot run
-# (M < 256, K < 192 resp. 256: launch_gemm in csrc/gemm.hip), and "auto" picks 128x128 below M = 1024.  Of GEMM_SHAPES only
+# (M < 256, K < 192 resp. 256: choose_gemm in csrc/gemm.hip), and "auto" picks 128x128 below M = 1024.  Of GEMM_SHAPES only
 # 394x2304x768 and 346x768x3072 (wide and mid) and 513x260x128 (neither: K = 128) reach the persistent kernels when forced;
 # for the other shapes the wide / mid ids repeat the 128x128 kernel.  The epilogue sweeps below choose their launch shape
 # by tiling so that the named kernel really runs.
@@ -209,7 +209,7 @@ def test_fp8_matrix_instruction_accumulation_as_recorded():
 
 def through_bias(bias32, dt, epilogue, tiling=0):
     """epi(0 W^T + bias) for a vector of fp32 biases: [rows, len(bias)] in the model type (all rows must agree).
-    A forced persistent tiling (4 = 256x256, 5 = 256x128) is only honoured from M >= 256 and K >= 256 on (launch_gemm), so
+    A forced persistent tiling (4 = 256x256, 5 = 256x128) is only honoured from M >= 256 and K >= 256 on (choose_gemm), so
     those launches use 261 rows (one full row tile and a ragged one: interior and guarded epilogue paths) and K = 256 of
     zeros; the 128x128 kernel gets 5 rows and K = 64."""
     n = len(bias32)

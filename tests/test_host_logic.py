@@ -74,6 +74,17 @@ def test_struct_layouts_match_header_sizes():
     plan.act_fp8 = 1        # two per-row scale vectors
     assert nat.lib().rajni_vit_workspace_bytes(C.byref(plan)) == want + 2 * a256(rows * 4)
     plan.act_fp8 = 0        # (the LAST int of the struct, ABI 8: the whole layout lines up)
+    # rajni_linear_plan (debug header): ints in the header's order, and the dry-run hook fills each where the mirror reads it
+    with open(os.path.join(ROOT, "include", "rajni_hip_debug.h")) as f:
+        body = re.search(r"typedef struct rajni_linear_plan \{(.*?)\} rajni_linear_plan;", f.read(), re.S).group(1)
+    names = re.findall(r"\b([a-z_]+)\s*[,;]", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+    assert names == [n for n, _ in nat.LinearPlan._fields_] and C.sizeof(nat.LinearPlan) == 4 * len(names)
+    a = nat.LinearArgs()
+    a.x, a.w, a.y = 0x1000, 0x2000, 0x3000        # checked (non-null, 16-byte aligned), never followed: nothing is launched
+    a.lda, a.ldw, a.ldc, a.M, a.N, a.K, a.epilogue, a.dtype = 512, 512, 192, 300, 192, 512, nat.EPI_BIAS, nat.RAJNI_BF16
+    out = nat.LinearPlan()
+    assert nat.lib().rajni_debug_linear_plan(C.byref(a), 256, C.byref(out)) == 0
+    assert (out.tiling, out.tiles_n, out.total_tiles, out.nblk, out.grid, out.lds_bytes) == (nat.TILING_SMALL, 2, 6, 0, 6, 64 * 1024)
 
 
 def test_no_cpu_fallback():

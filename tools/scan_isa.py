@@ -35,7 +35,7 @@ def operand_format(mangled):
 
 
 def dispatched(k):
-    """instantiations launch_gemm picks without a test hook: everything except the 256x256 tiling with the
+    """instantiations choose_gemm picks without a test hook: everything except the 256x256 tiling with the
     fused patch loader (a patch embed wider than 1536 channels has K = 3*14*14, not a multiple of 64)."""
     if k[0] == "f8":
         return True
