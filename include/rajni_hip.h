@@ -228,8 +228,9 @@ typedef struct {
                                                   CLS row only - attention with the CLS query over all tokens,
                                                   proj / MLP on B rows.  model.py:65-66 feeds only x[:, 0] to the
                                                   head, so the logits are the same function; the other rows of the
-                                                  last block are never formed.  0 (default): every row, like the
-                                                  reference's op graph */
+                                                  last block are never formed.  This opt-in's CLS attention is a kernel
+                                                  of its own (logits within a 16-bit ulp); 0 (default) computes the same
+                                                  rows with the all-rows kernels, bit for bit the all-rows logits */
   int resid_bf16;                              /* 0 (default): the residual stream x is kept in fp32 between
                                                   blocks (2x closer to the fp32 reference than a bf16 stream, see
                                                   DESIGN.md); 1: keep it in the model's 16-bit dtype (bf16 or fp16)

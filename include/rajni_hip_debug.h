@@ -15,6 +15,23 @@ extern "C" {
  * online-softmax kernel, 2 = one-shot full-row kernel (np <= 256) */
 void rajni_debug_force_attention(int mode);
 
+/* The attention of the boundary header limited to the query rows [0, nq), 1 <= nq <= np: same arguments, same kernel and
+ * instantiation as the all-rows call (chosen by np, D and dtype), but query tiles that hold none of the wanted rows are
+ * switched off or not launched.  A tile that straddles nq is computed and stored whole (32 rows with head dim 64 on 16-bit
+ * operands, 128 with other head dims, 64 on fp32), nothing past it is written; the rows written hold the bits the all-rows
+ * call writes (tested).  The forward uses nq = 1 in its last block. */
+int rajni_debug_attention_rows(const void* qkv, const int32_t* keep_idx, void* out, int B, int n_src, int np, int nq,
+                               int H, int D, float scale, int dtype, rajni_stream_t stream);
+
+/* Last block of the whole forward: 0 (default) = when only x[:, 0] is observable behind it (last block not a pruning stage,
+ * token-pooled head, no act_fp8, cls_only_last_block off) attention runs for the first query tile and proj / LN2 / FC1 / fc2
+ * on the B CLS rows - the all-rows kernels on fewer rows, logits bit for bit the same; 1 = every row of the last block is
+ * computed, the reference's op graph row for row.  Token counts, stats and traces are the same either way. */
+void rajni_debug_set_last_block_all_rows(int on);
+/* the eligibility test alone, on the host (ext / prefix may be NULL; no device pointer is followed): 1 when the forward of
+ * this plan computes its last block for the CLS rows only, 0 when for all rows */
+int rajni_debug_last_block_cls_rows(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix);
+
 /* GEMM tiling: 0 = by shape (default), 1 = 128x128x64 (4 waves), 4 = 256x256x64 persistent,
  * 5 = 256x128x64 3-stage persistent */
 void rajni_debug_force_gemm_tiling(int mode);

@@ -28,6 +28,7 @@ struct AttnArgs {
   const int* idx;   // [B,np] or null
   bf16_t* out;      // [B,np,H*64]
   int n_src, np, H;
+  int nq;           // query rows [0, nq) are wanted (np everywhere but the last block's CLS-row launch): the tiles that hold none are skipped
   float c;          // scale * log2(e)
   unsigned long long* stamps;   // diagnostic builds (-DRAJNI_ATTN_STAMPS) only
   // fp8 output (rajni_attention_fp8; the O8 instantiations): rows as e4m3_rne_sat(o * oinv) bytes [B,np,H*64], and the
@@ -76,7 +77,7 @@ __global__ void __launch_bounds__(AT_THREADS) attn_bf16_d64(const AttnArgs a) {
   const int* idx = a.idx ? a.idx + (long)b * np : nullptr;
 
   const int qbase = blockIdx.x * AT_QROWS + wave * 32;
-  const bool active = qbase < np;
+  const bool active = qbase < (a.nq < np ? a.nq : np);
 
   // ---- Q fragments straight from HBM (B operand: lane holds Q[q = l31][d = 16s + 8h .. +7])
   bf16x8 qf[4];
@@ -402,7 +403,7 @@ __global__ void __launch_bounds__(ATF_THREADS, 2) attn_bf16_d64_full(const AttnA
   const bf16_t* img = a.qkv + (long)b * a.n_src * C3;
   const int* idx = a.idx ? a.idx + (long)b * np : nullptr;
   const int qbase = wave * 32;
-  const bool active = qbase < np;
+  const bool active = qbase < (a.nq < np ? a.nq : np);
 
   // ---- Q fragments from HBM while K/V are staged
   bf16x8 qf[4];
@@ -473,7 +474,7 @@ __global__ void __launch_bounds__(ATF_THREADS, 2) attn_bf16_d64_stream(const Att
   const int l31 = lane & 31, h = lane >> 5;
   const int np = a.np, C = a.H * 64, C3 = 3 * C;
   const int qbase = wave * 32;
-  const bool active = qbase < np;
+  const bool active = qbase < (a.nq < np ? a.nq : np);
   const int r_in = lane >> 3, pos = lane & 7;
 
   // token (packed index) of the rows this lane stages, and of its query row
@@ -606,6 +607,7 @@ struct AttnArgsF32 {
   const float* qkv; const int* idx; float* out;
   int n_src, np, H;
   float c;
+  int nq;           // as in AttnArgs (the launch's grid.x covers nq rows)
 };
 
 __global__ void __launch_bounds__(256) attn_f32_d64(const AttnArgsF32 a) {
@@ -1074,7 +1076,7 @@ int launch_attention_cls(const void* qkv, void* out, int B, int N, int H, int D,
 // the 16-bit formats (A = bf16_t or f16_t): the same kernel choice for the same shape
 template <typename A>
 int launch_attention16(const AttnArgs& a, int B, int np, int H, int D, hipStream_t s) {
-  const int nsub = (np + 31) / 32;
+  const int nsub = (np + 31) / 32;   // the kernel is chosen by np alone: a launch limited to a.nq query rows runs the instantiation the all-rows one does
   if (D != 64) {
     #ifndef RAJNI_ATTN_DGEN_NW
 #define RAJNI_ATTN_DGEN_NW 4
@@ -1083,7 +1085,7 @@ int launch_attention16(const AttnArgs& a, int B, int np, int H, int D, hipStream
 #define RAJNI_ATTN_DGEN_NB 2
 #endif
     constexpr int qrows = RAJNI_ATTN_DGEN_NW * RAJNI_ATTN_DGEN_NB * 16;
-    hipLaunchKernelGGL((attn_bf16_dgen<RAJNI_ATTN_DGEN_NW, RAJNI_ATTN_DGEN_NB, A>), dim3((np + qrows - 1) / qrows, H, B),
+    hipLaunchKernelGGL((attn_bf16_dgen<RAJNI_ATTN_DGEN_NW, RAJNI_ATTN_DGEN_NB, A>), dim3((a.nq + qrows - 1) / qrows, H, B),
                        dim3(RAJNI_ATTN_DGEN_NW * 64), 0, s, a, D);
   } else if (nsub <= 8 && g_force_attn != 1) {
     int rc = RAJNI_OK;
@@ -1099,7 +1101,7 @@ int launch_attention16(const AttnArgs& a, int B, int np, int H, int D, hipStream
     }
     if (rc != RAJNI_OK) return rc;
   } else {
-    hipLaunchKernelGGL(attn_bf16_d64<A>, dim3((np + AT_QROWS - 1) / AT_QROWS, H, B), dim3(AT_THREADS), 0,
+    hipLaunchKernelGGL(attn_bf16_d64<A>, dim3((a.nq + AT_QROWS - 1) / AT_QROWS, H, B), dim3(AT_THREADS), 0,
                        s, a);
   }
   return RAJNI_OK;
@@ -1109,7 +1111,12 @@ int launch_attention16(const AttnArgs& a, int B, int np, int H, int D, hipStream
 // image as (unsigned)row * row_bytes; every other attention kernel forms (long)row * C3
 static inline bool image_bytes_ok(int n_src, int H) { return (size_t)n_src * 3 * (size_t)H * 64 * 2 <= 0xFFFFFFFFul; }
 
-int launch_attention(const void* qkv, const int32_t* keep_idx, void* out, int B, int n_src, int np,
+// nq: only query rows [0, nq) are wanted (nq == np: all of them).  Kernel and instantiation are chosen by np, D and dtype as
+// for all rows; the query tiles that hold none of the wanted rows are switched off (persistent / one-shot / chunked head-dim-64
+// kernels: their waves still stage K/V and take every barrier) or not launched (grid.x of the tiled kernels).  A query row's
+// output depends on its own Q and on all K/V, never on another query row, so the rows that are written hold the bits the
+// all-rows launch writes; a tile that straddles nq is written whole, nothing past it is touched.
+int launch_attention(const void* qkv, const int32_t* keep_idx, void* out, int B, int n_src, int np, int nq,
                      int H, int D, float scale, int dtype, hipStream_t s) {
   // (the grid limit before the pointers: a refused shape is refused whatever else the call holds)
   RAJNI_REQUIRE(H <= RAJNI_MAX_GRID_YZ && B <= RAJNI_MAX_GRID_YZ, RAJNI_ERR_UNSUPPORTED,
@@ -1126,12 +1133,15 @@ int launch_attention(const void* qkv, const int32_t* keep_idx, void* out, int B,
                 "rajni_attention: bad shape B=%d H=%d np=%d n_src=%d", B, H, np, n_src);
   RAJNI_REQUIRE(keep_idx != nullptr || np == n_src, RAJNI_ERR_INVALID,
                 "rajni_attention: identity selection needs np == n_src");
+  RAJNI_REQUIRE(nq >= 1 && nq <= np, RAJNI_ERR_INVALID, "rajni_attention: query-row limit nq=%d outside 1..np=%d", nq, np);
+  // K and V of all np rows are read; Q is read and the output written for the nq wanted rows
+  const double kv_q_o = 2.0 * np + 2.0 * nq;
   if (dtype == RAJNI_F32) {
     AttnArgsF32 f{};
     f.qkv = (const float*)qkv; f.idx = keep_idx; f.out = (float*)out;
-    f.n_src = n_src; f.np = np; f.H = H; f.c = scale * 1.4426950408889634f;
-    ProfScope prof(KC_ATTENTION, s, 4.0 * B * H * (double)np * np * D, 4.0 * B * (double)np * H * D * 4.0);
-    const dim3 grid((np + 63) / 64, H, B);
+    f.n_src = n_src; f.np = np; f.H = H; f.c = scale * 1.4426950408889634f; f.nq = nq;
+    ProfScope prof(KC_ATTENTION, s, 4.0 * B * H * (double)nq * np * D, 4.0 * B * kv_q_o * H * D);
+    const dim3 grid((nq + 63) / 64, H, B);
     if (D == 64) hipLaunchKernelGGL(attn_f32_d64, grid, dim3(256), 0, s, f);
     else if (D < 64) hipLaunchKernelGGL(attn_f32_dgen<16>, grid, dim3(256), 0, s, f, D);
     else hipLaunchKernelGGL(attn_f32_dgen<32>, grid, dim3(256), 0, s, f, D);
@@ -1141,11 +1151,11 @@ int launch_attention(const void* qkv, const int32_t* keep_idx, void* out, int B,
   RAJNI_REQUIRE(dtype == RAJNI_BF16 || dtype == RAJNI_F16, RAJNI_ERR_INVALID, "rajni_attention: bad dtype %d", dtype);
   AttnArgs a{};
   a.qkv = (const bf16_t*)qkv; a.idx = keep_idx; a.out = (bf16_t*)out;
-  a.n_src = n_src; a.np = np; a.H = H;
+  a.n_src = n_src; a.np = np; a.H = H; a.nq = nq;
   a.c = scale * 1.4426950408889634f;
   a.stamps = rajni_g_stamps;
-  const double flops = 4.0 * B * H * (double)np * np * D;
-  const double bytes = 2.0 * B * (double)np * H * D * 4.0;
+  const double flops = 4.0 * B * H * (double)nq * np * D;
+  const double bytes = 2.0 * B * kv_q_o * H * D;
   ProfScope prof(KC_ATTENTION, s, flops, bytes);
   const int rc = dtype == RAJNI_F16 ? launch_attention16<f16_t>(a, B, np, H, D, s) : launch_attention16<bf16_t>(a, B, np, H, D, s);
   if (rc != RAJNI_OK) return rc;
@@ -1172,7 +1182,7 @@ int launch_attention_fp8(const void* qkv, const int32_t* keep_idx, void* out_q, 
   RAJNI_REQUIRE(out_scale > 0.f && out_scale < INFINITY, RAJNI_ERR_INVALID, "rajni_attention_fp8: out_scale must be positive and finite");
   AttnArgs a{};
   a.qkv = (const bf16_t*)qkv; a.idx = keep_idx; a.out = nullptr;
-  a.n_src = n_src; a.np = np; a.H = H;
+  a.n_src = n_src; a.np = np; a.H = H; a.nq = np;
   a.c = scale * 1.4426950408889634f;
   a.stamps = nullptr;
   a.out8 = (unsigned char*)out_q; a.oscale = out_scale; a.oinv = 1.0f / out_scale; a.row_scale = row_scale;

@@ -195,7 +195,14 @@ int rajni_gather_rows(const void* src, const int32_t* idx, void* dst, int B, int
 int rajni_attention(const void* qkv, const int32_t* keep_idx, void* out, int B, int n_src, int np,
                     int H, int D, float scale, int dtype, rajni_stream_t stream) {
   NEED_DTYPE("rajni_attention");
-  return launch_attention(qkv, keep_idx, out, B, n_src, np, H, D, scale, dtype, (hipStream_t)stream);
+  return launch_attention(qkv, keep_idx, out, B, n_src, np, np, H, D, scale, dtype, (hipStream_t)stream);
+}
+
+// rajni_attention limited to the query rows [0, nq) (include/rajni_hip_debug.h)
+extern "C" int rajni_debug_attention_rows(const void* qkv, const int32_t* keep_idx, void* out, int B, int n_src, int np, int nq,
+                                          int H, int D, float scale, int dtype, rajni_stream_t stream) {
+  NEED_DTYPE("rajni_debug_attention_rows");
+  return launch_attention(qkv, keep_idx, out, B, n_src, np, nq, H, D, scale, dtype, (hipStream_t)stream);
 }
 
 extern "C" int rajni_attention_fp8(const void* qkv, const int32_t* keep_idx, void* out_q, float out_scale, float* row_scale,

@@ -199,8 +199,8 @@ int launch_layernorm(const void* x, long xs, const float* w, const float* b, voi
                      int C, float eps, int x_f32, int dtype, hipStream_t s);
 int launch_layernorm_fp8(const void* x, long xs, const float* w, const float* b, void* yq, float* yscale,
                          float* hscale, float wnorm, float bmax, int rows, int C, float eps, int x_f32, hipStream_t s);
-int launch_attention(const void* qkv, const int32_t* keep_idx, void* out, int B, int n_src, int np,
-                     int H, int D, float scale, int dtype, hipStream_t s);
+int launch_attention(const void* qkv, const int32_t* keep_idx, void* out, int B, int n_src, int np, int nq,
+                     int H, int D, float scale, int dtype, hipStream_t s);   // nq: query rows [0, nq) only (np = all)
 int launch_attention_fp8(const void* qkv, const int32_t* keep_idx, void* out_q, float out_scale, float* row_scale,
                          int B, int n_src, int np, int H, int D, float scale, hipStream_t s);
 int launch_attention_cls(const void* qkv, void* out, int B, int N, int H, int D, float scale, int dtype,

@@ -99,6 +99,50 @@ int check_ext(const rajni_vit_plan& p, const rajni_vit_ext& e) {
   return RAJNI_OK;
 }
 
+// test hook (rajni_debug_set_last_block_all_rows): 1 = the last block runs every row, the reference's op graph row for row
+int g_last_block_all_rows = 0;
+
+// The head reads x[:, 0] only (model.py:65-66), so past the last block's K and V nothing but the CLS row of each image is
+// observable.  When this holds for block i entering with N tokens, the block runs attention for the first query tile and
+// proj / LN2 / FC1 / fc2 on the B CLS rows - the kernels of the all-rows form on fewer rows, hence the same bits (a row
+// of an attention, LayerNorm or rajni_linear result does not depend on which other rows are in the launch).  Not for: a
+// last block that prunes (its selection is part of the trace), an avg-pooled head (reads every row), act_fp8 plans and
+// the cls_only_last_block opt-in (they keep the opt-in's own branch and numerics contract).
+inline bool last_block_cls_rows(const rajni_vit_plan& p, const rajni_vit_ext* ext, int i, int N) {
+  return i == p.depth - 1 && p.blocks[i].keep == 0 && N > 1 && (ext == nullptr || ext->pool == RAJNI_POOL_TOKEN) &&
+         !p.act_fp8 && !p.cls_only_last_block && !g_last_block_all_rows;
+}
+
+// the three B-row linears of such a block: proj reads the CLS rows of the attention output in place (row stride N * C)
+// and gathers the residual the same way; `x` / `y` are the stream before / after proj, both [B, C] from there on
+struct ClsRowLinears { rajni_linear_args proj, fc1, fc2; };
+ClsRowLinears cls_row_linears(const rajni_vit_plan& p, const rajni_block& blk, int N, const void* att, const void* x, void* y,
+                              void* xn, void* hid, int sf32) {
+  const int B = p.B, C = p.C;
+  ClsRowLinears l{};
+  rajni_linear_args& g = l.proj;
+  g.dtype = p.dtype;
+  g.x = att; g.lda = (long)N * C; g.w = blk.proj_w; g.ldw = C; g.bias = blk.proj_b; g.gamma = blk.ls1; g.w_scale = blk.proj_s;
+  g.resid = x; g.ldr = (long)N * C;
+  g.y = y; g.ldc = C; g.M = B; g.N = C; g.K = C; g.epilogue = RAJNI_EPI_BIAS_RESID; g.stream_f32 = sf32;
+  rajni_linear_args& f = l.fc1;
+  f.dtype = p.dtype;
+  f.x = xn; f.lda = C; f.w = blk.fc1_w; f.ldw = C; f.bias = blk.fc1_b; f.w_scale = blk.fc1_s;
+  f.y = hid; f.ldc = p.hidden; f.M = B; f.N = p.hidden; f.K = C; f.epilogue = RAJNI_EPI_BIAS_GELU;
+  rajni_linear_args& h = l.fc2;
+  h.dtype = p.dtype;
+  h.x = hid; h.lda = p.hidden; h.w = blk.fc2_w; h.ldw = p.hidden; h.bias = blk.fc2_b; h.gamma = blk.ls2; h.w_scale = blk.fc2_s;
+  h.resid = y; h.ldr = C; h.y = y; h.ldc = C; h.M = B; h.N = C; h.K = p.hidden;
+  h.epilogue = RAJNI_EPI_BIAS_RESID; h.stream_f32 = sf32;
+  return l;
+}
+// would rajni_linear take all three?  (the dry run: every refusal, no launch; 256 CUs - no refusal depends on the count)
+bool cls_row_linears_ok(const ClsRowLinears& l) {
+  rajni_linear_plan unused;
+  return rajni_debug_linear_plan(&l.proj, 256, &unused) == RAJNI_OK && rajni_debug_linear_plan(&l.fc1, 256, &unused) == RAJNI_OK &&
+         rajni_debug_linear_plan(&l.fc2, 256, &unused) == RAJNI_OK;
+}
+
 // P of a prefix record: NULL, 0 and 1 all mean CLS only
 inline int prefix_count(const rajni_vit_prefix* pre) { return (pre && pre->num_prefix > 1) ? pre->num_prefix : 1; }
 
@@ -150,6 +194,19 @@ extern "C" int rajni_vit_forward_ext_prefix(const rajni_vit_plan* plan, const ra
   const int rc = check_prefix(prefix, "rajni_vit_forward_ext_prefix");
   if (rc != RAJNI_OK) return rc;
   return vit_forward(plan, ext, prefix, images, logits, (hipStream_t)stream);
+}
+
+extern "C" void rajni_debug_set_last_block_all_rows(int on) { g_last_block_all_rows = on; }
+
+// 1 when the forward of this plan (with this ext / prefix record, either may be NULL) computes its last block for the CLS rows
+// only, 0 when for all rows: the eligibility test alone, on the host, nothing launched and no device pointer followed
+extern "C" int rajni_debug_last_block_cls_rows(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix) {
+  if (!plan || !plan->blocks || plan->depth <= 0 || plan->patch_size <= 0) return 0;
+  const int P = prefix_count(prefix), gw = plan->img_size / plan->patch_size;
+  int N = gw * gw + P;
+  for (int i = 0; i + 1 < plan->depth; ++i)
+    if (plan->blocks[i].keep > 0) N = plan->blocks[i].keep + P;
+  return last_block_cls_rows(*plan, ext, plan->depth - 1, N) ? 1 : 0;
 }
 
 namespace {
@@ -246,6 +303,26 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
       break;
     }
 
+    if (last_block_cls_rows(p, ext, i, N)) {
+      // ---- last block, nothing but x[:, 0] observable behind its K and V: the all-rows kernels on the rows the head reads
+      const ClsRowLinears l = cls_row_linears(p, blk, N, w.att, cur, oth, w.xn, w.hid, sf32);
+      if (cls_row_linears_ok(l)) {   // (a refused shape or stride: all rows below, as if this branch were not here)
+        rc = launch_attention(w.qkv, nullptr, w.att, B, N, N, 1, p.H, p.D, p.attn_scale, dt, s);   // CLS row of image b: row b * N
+        if (rc != RAJNI_OK) return rc;
+        rc = launch_linear(l.proj, s);
+        if (rc != RAJNI_OK) return rc;
+        { char* t = cur; cur = oth; oth = t; }
+        N = 1;                                          // the stream is now [B, 1, C]
+        rc = launch_layernorm(cur, C, blk.norm2_w, blk.norm2_b, w.xn, B, C, p.ln_eps, sf32, dt, s);
+        if (rc != RAJNI_OK) return rc;
+        rc = launch_linear(l.fc1, s);
+        if (rc != RAJNI_OK) return rc;
+        rc = launch_linear(l.fc2, s);
+        if (rc != RAJNI_OK) return rc;
+        break;
+      }
+    }
+
     int Np = N;
     const int32_t* idx = nullptr;
     if (blk.keep > 0) {  // scheduled block (model.py:50)
@@ -290,7 +367,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
     // wherever the persistent head-dim-64 kernel serves the launch (rajni_attention_fp8); proj then runs fp8 x fp8
     const bool att8 = p.act_fp8 && blk.attn_out_scale > 0.f && blk.proj_s != nullptr && p.D == 64 && Np <= 224;
     if (att8) rc = launch_attention_fp8(w.qkv, idx, w.att, blk.attn_out_scale, w.xs, B, N, Np, p.H, p.D, p.attn_scale, s);
-    else rc = launch_attention(w.qkv, idx, w.att, B, N, Np, p.H, p.D, p.attn_scale, dt, s);
+    else rc = launch_attention(w.qkv, idx, w.att, B, N, Np, Np, p.H, p.D, p.attn_scale, dt, s);
     if (rc != RAJNI_OK) return rc;
 
     // ---- proj + (gathered) residual + LayerScale (attention.py:55-56, model.py:55-58)

@@ -120,6 +120,10 @@ _SIGS = {
     "rajni_debug_set_gemm_nblock_bytes": (None, [c_int]),
     "rajni_debug_linear_plan": (c_int, [C.POINTER(LinearArgs), c_int, C.POINTER(LinearPlan)]),
     "rajni_debug_force_attention": (None, [c_int]),
+    "rajni_debug_attention_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                           c_int, c_void_p]),
+    "rajni_debug_set_last_block_all_rows": (None, [c_int]),
+    "rajni_debug_last_block_cls_rows": (c_int, [C.POINTER(VitPlan), C.POINTER(VitExt), C.POINTER(VitPrefix)]),
     "rajni_debug_force_score_two_pass": (None, [c_int]),
     "rajni_debug_force_score_tiled": (None, [c_int]),
     "rajni_debug_set_gemm_stamps": (None, [c_void_p]),
