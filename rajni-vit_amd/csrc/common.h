@@ -205,14 +205,12 @@ int launch_attention_fp8(const void* qkv, const int32_t* keep_idx, void* out_q, 
                          int B, int n_src, int np, int H, int D, float scale, hipStream_t s);
 int launch_attention_cls(const void* qkv, void* out, int B, int N, int H, int D, float scale, int dtype,
                          hipStream_t s, float q_scale = 0.f);   // q_scale > 0: the row passes through rajni_attention_fp8's e4m3 rounding
-int launch_score_select(const void* qkv, const void* scores_in, int B, int N, int H, int D,
-                        float eps, int keep, void* scores_out, int32_t* keep_idx,
-                        void* next_scores, int dtype, hipStream_t s, int num_prefix = 1);
-// ... with scratch of rajni_score_select_workspace_bytes(B, N, H, D, dtype) bytes (256-byte aligned; may be null when that
+// ws: scratch of rajni_score_select_workspace_bytes(B, N, H, D, dtype) bytes (256-byte aligned; may be null when that
 // is 0): shapes beyond one workgroup's LDS are scored by the tiled kernels through it
 int launch_score_select(const void* qkv, const void* scores_in, int B, int N, int H, int D,
                         float eps, int keep, void* scores_out, int32_t* keep_idx,
-                        void* next_scores, int dtype, hipStream_t s, int num_prefix, void* ws, size_t ws_bytes);
+                        void* next_scores, int dtype, hipStream_t s, int num_prefix = 1, void* ws = nullptr,
+                        size_t ws_bytes = 0);
 int launch_gather_rows(const void* src, const int32_t* idx, void* dst, int B, int n_src, int n_dst,
                        int row_bytes, hipStream_t s);
 // variants.hip: the timm options of rajni_vit_ext (b pointers may be NULL = no bias; nw / fw NULL = that norm is absent)

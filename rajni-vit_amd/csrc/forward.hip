@@ -1,14 +1,19 @@
 // Whole-forward orchestration: RAJNIViTWrapper.forward (reference model.py:30-69) as one host call
 // that enqueues every kernel on the caller's stream.  Token counts are data independent,
-// so all shapes are known up front: no allocation, no host sync, no device->host traffic inside.
+// so all shapes are known up front: no allocation, no host sync, no device->host traffic inside, and
+// every refusal that depends on the plan alone (check_plan, check_ext, check_schedule) comes before the first launch.
+//
+// Per block:  LN1 -> QKV GEMM (all N tokens) -> an attention form -> the tail (launch_tail):
+// proj GEMM whose epilogue gathers the residual row, applies LayerScale and adds -> LN2 -> FC1 GEMM + GELU ->
+// FC2 GEMM + LayerScale + residual (in place).  The attention form is one of
+//   [score+select] -> attention on the kept tokens (gather fused into its loads), all rows;
+//   the first query tile of that attention, tail on the B CLS rows (last block, the same bits: last_block_cls_rows);
+//   the CLS-query kernel, tail on the B CLS rows (last block, the cls_only_last_block opt-in);
+// and hands the tail an AttnRows record.  The reference's three gathers (qkv, scores, x) never exist as kernels here.
 //
 // With plan.act_fp8 (opt-in): LN1 / LN2 emit per-row-scaled e4m3 rows, QKV / FC1 / FC2 run on the fp8 matrix pipe
-// (gemm_f8.h) and FC1's GELU epilogue re-quantises the hidden activations; attention, proj, the residual stream,
-// patch embed and head are unchanged.
-// Per block:  LN1 -> QKV GEMM (all N tokens) -> [score+select] -> attention on kept tokens (gather
-// fused into its loads) -> proj GEMM whose epilogue gathers the residual row, applies LayerScale and
-// adds -> LN2 -> FC1 GEMM + GELU -> FC2 GEMM + LayerScale + residual (in place).
-// The reference's three gathers (qkv, scores, x) never exist as kernels here.
+// (gemm_f8.h) and FC1's GELU epilogue re-quantises the hidden activations; where attention emits e4m3 rows
+// (attn_emits_e4m3) proj runs there too.  The residual stream, patch embed and head are unchanged.
 #include "common.h"
 
 namespace {
@@ -113,34 +118,89 @@ inline bool last_block_cls_rows(const rajni_vit_plan& p, const rajni_vit_ext* ex
          !p.act_fp8 && !p.cls_only_last_block && !g_last_block_all_rows;
 }
 
-// the three B-row linears of such a block: proj reads the CLS rows of the attention output in place (row stride N * C)
-// and gathers the residual the same way; `x` / `y` are the stream before / after proj, both [B, C] from there on
-struct ClsRowLinears { rajni_linear_args proj, fc1, fc2; };
-ClsRowLinears cls_row_linears(const rajni_vit_plan& p, const rajni_block& blk, int N, const void* att, const void* x, void* y,
-                              void* xn, void* hid, int sf32) {
-  const int B = p.B, C = p.C;
-  ClsRowLinears l{};
-  rajni_linear_args& g = l.proj;
-  g.dtype = p.dtype;
-  g.x = att; g.lda = (long)N * C; g.w = blk.proj_w; g.ldw = C; g.bias = blk.proj_b; g.gamma = blk.ls1; g.w_scale = blk.proj_s;
-  g.resid = x; g.ldr = (long)N * C;
-  g.y = y; g.ldc = C; g.M = B; g.N = C; g.K = C; g.epilogue = RAJNI_EPI_BIAS_RESID; g.stream_f32 = sf32;
-  rajni_linear_args& f = l.fc1;
-  f.dtype = p.dtype;
-  f.x = xn; f.lda = C; f.w = blk.fc1_w; f.ldw = C; f.bias = blk.fc1_b; f.w_scale = blk.fc1_s;
-  f.y = hid; f.ldc = p.hidden; f.M = B; f.N = p.hidden; f.K = C; f.epilogue = RAJNI_EPI_BIAS_GELU;
-  rajni_linear_args& h = l.fc2;
-  h.dtype = p.dtype;
-  h.x = hid; h.lda = p.hidden; h.w = blk.fc2_w; h.ldw = p.hidden; h.bias = blk.fc2_b; h.gamma = blk.ls2; h.w_scale = blk.fc2_s;
-  h.resid = y; h.ldr = C; h.y = y; h.ldc = C; h.M = B; h.N = C; h.K = p.hidden;
-  h.epilogue = RAJNI_EPI_BIAS_RESID; h.stream_f32 = sf32;
-  return l;
+// what is fixed for one forward, for the builders and launchers below
+struct Fwd { const rajni_vit_plan& p; const Workspace& w; int sf32; hipStream_t s; };   // sf32: 16-bit model, fp32 residual stream
+
+// y[M, N] = epi(x[M, K] wt[N, K]^T + bias), every operand dense
+rajni_linear_args linear_args(int dtype, const void* x, const void* wt, const float* bias, const float* w_scale, void* y,
+                              int M, int N, int K, int epilogue) {
+  rajni_linear_args g{};
+  g.dtype = dtype;
+  g.x = x; g.lda = K; g.w = wt; g.ldw = K; g.bias = bias; g.w_scale = w_scale;
+  g.y = y; g.ldc = N; g.M = M; g.N = N; g.K = K; g.epilogue = epilogue;
+  return g;
+}
+
+// the rows a block's attention left in w.att for the tail, and the residual row of each
+struct AttnRows {
+  int M; long lda;                          // B * tokens rows of stride C, or the B CLS rows of stride C / N * C
+  const float* x_scale;                     // e4m3 rows (launch_attention_fp8 wrote them): their scale, else null
+  long ldr;                                 // residual: row stride in the stream before proj ...
+  const int32_t* idx; int np, nsrc;         // ... and the selection it is gathered by (null: row m)
+};
+
+// norm1 + qkv on ALL N tokens (model.py:51, attention.py:21-22)
+rajni_linear_args qkv_args(const Fwd& f, const rajni_block& blk, int M) {
+  rajni_linear_args g = linear_args(f.p.dtype, f.w.xn, blk.qkv_w, blk.qkv_b, blk.qkv_s, f.w.qkv, M, 3 * f.p.C, f.p.C, RAJNI_EPI_BIAS);
+  if (f.p.act_fp8) g.x_scale = f.w.xs;
+  return g;
+}
+// proj + (gathered) residual + LayerScale (attention.py:55-56, model.py:55-58): x -> y is the stream before / after
+rajni_linear_args proj_args(const Fwd& f, const rajni_block& blk, const AttnRows& r, const void* x, void* y) {
+  rajni_linear_args g = linear_args(f.p.dtype, f.w.att, blk.proj_w, blk.proj_b, blk.proj_s, y, r.M, f.p.C, f.p.C, RAJNI_EPI_BIAS_RESID);
+  g.lda = r.lda; g.x_scale = r.x_scale;
+  g.gamma = blk.ls1; g.resid = x; g.ldr = r.ldr; g.stream_f32 = f.sf32;
+  if (r.idx) { g.r_idx = r.idx; g.r_np = r.np; g.r_nsrc = r.nsrc; }
+  return g;
+}
+// MLP (model.py:59): fc1 + GELU; act_fp8: e4m3 in, e4m3 out (per-row scales)
+rajni_linear_args fc1_args(const Fwd& f, const rajni_block& blk, int M) {
+  rajni_linear_args g = linear_args(f.p.dtype, f.w.xn, blk.fc1_w, blk.fc1_b, blk.fc1_s, f.w.hid, M, f.p.hidden, f.p.C, RAJNI_EPI_BIAS_GELU);
+  if (f.p.act_fp8) { g.x_scale = f.w.xs; g.y_scale = f.w.hs; }
+  return g;
+}
+// fc2 + LayerScale + residual, in place on the stream y
+rajni_linear_args fc2_args(const Fwd& f, const rajni_block& blk, int M, void* y) {
+  rajni_linear_args g = linear_args(f.p.dtype, f.w.hid, blk.fc2_w, blk.fc2_b, blk.fc2_s, y, M, f.p.C, f.p.hidden, RAJNI_EPI_BIAS_RESID);
+  if (f.p.act_fp8) g.x_scale = f.w.hs;
+  g.gamma = blk.ls2; g.resid = y; g.ldr = f.p.C; g.stream_f32 = f.sf32;
+  return g;
+}
+
+// LayerNorm of `rows` stream rows into w.xn; act_fp8 plans: e4m3 rows + their scales into w.xs, and with hs the hidden
+// scale of the rows' MLP (norm2 only)
+int layernorm(const Fwd& f, const void* x, const float* g, const float* b, int rows, float* hs = nullptr, float wnorm = 0.f,
+              float bmax = 0.f) {
+  const rajni_vit_plan& p = f.p;
+  if (p.act_fp8) return launch_layernorm_fp8(x, p.C, g, b, f.w.xn, f.w.xs, hs, wnorm, bmax, rows, p.C, p.ln_eps, f.sf32, f.s);
+  return launch_layernorm(x, p.C, g, b, f.w.xn, rows, p.C, p.ln_eps, f.sf32, p.dtype, f.s);
+}
+
+// act_fp8 plans: this block's attention over np tokens emits e4m3 rows + their (one) scale into w.xs - norm1's row scales
+// there were consumed by QKV - wherever the persistent head-dim-64 kernel serves the launch (rajni_attention_fp8)
+inline bool attn_emits_e4m3(const rajni_vit_plan& p, const rajni_block& blk, int np) {
+  return p.act_fp8 && blk.attn_out_scale > 0.f && blk.proj_s != nullptr && p.D == 64 && np <= 224;
+}
+
+// everything of a block behind its attention: proj + residual -> LN2 -> fc1 + GELU -> fc2 + residual
+struct Tail { rajni_linear_args proj, fc1, fc2; };
+Tail tail_args(const Fwd& f, const rajni_block& blk, const AttnRows& r, const void* x, void* y) {
+  return Tail{proj_args(f, blk, r, x, y), fc1_args(f, blk, r.M), fc2_args(f, blk, r.M, y)};
 }
 // would rajni_linear take all three?  (the dry run: every refusal, no launch; 256 CUs - no refusal depends on the count)
-bool cls_row_linears_ok(const ClsRowLinears& l) {
+bool tail_ok(const Tail& t) {
   rajni_linear_plan unused;
-  return rajni_debug_linear_plan(&l.proj, 256, &unused) == RAJNI_OK && rajni_debug_linear_plan(&l.fc1, 256, &unused) == RAJNI_OK &&
-         rajni_debug_linear_plan(&l.fc2, 256, &unused) == RAJNI_OK;
+  return rajni_debug_linear_plan(&t.proj, 256, &unused) == RAJNI_OK && rajni_debug_linear_plan(&t.fc1, 256, &unused) == RAJNI_OK &&
+         rajni_debug_linear_plan(&t.fc2, 256, &unused) == RAJNI_OK;
+}
+int launch_tail(const Fwd& f, const rajni_block& blk, const Tail& t) {
+  int rc = launch_linear(t.proj, f.s);
+  if (rc != RAJNI_OK) return rc;
+  rc = layernorm(f, t.proj.y, blk.norm2_w, blk.norm2_b, t.proj.M, f.w.hs, blk.fc1_rownorm_max, blk.fc1_bias_absmax);
+  if (rc != RAJNI_OK) return rc;
+  rc = launch_linear(t.fc1, f.s);
+  if (rc != RAJNI_OK) return rc;
+  return launch_linear(t.fc2, f.s);
 }
 
 // P of a prefix record: NULL, 0 and 1 all mean CLS only
@@ -157,19 +217,39 @@ int check_prefix(const rajni_vit_prefix* pre, const char* who) {
   return RAJNI_OK;
 }
 
+// the token walk (model.py:43,50): a scheduled block leaves its kept patch tokens and the P prefix tokens ...
+inline int tokens_after(const rajni_block& blk, int N, int P) { return blk.keep > 0 ? blk.keep + P : N; }
+// ... so this many enter block i
+int tokens_entering(const rajni_vit_plan& p, int P, int i) {
+  const int gw = p.img_size / p.patch_size;
+  int N = gw * gw + P;
+  for (int j = 0; j < i; ++j) N = tokens_after(p.blocks[j], N, P);
+  return N;
+}
+
+inline int logits_stride(const rajni_vit_plan& p) { return p.logits_ld > 0 ? p.logits_ld : p.num_classes; }
+
+// the pruning schedule and the logits stride: what the block loop and the head rely on, refused before anything is launched
+int check_schedule(const rajni_vit_plan& p, int P) {
+  for (int i = 0; i < p.depth; ++i) {
+    const rajni_block& blk = p.blocks[i];
+    if (blk.keep <= 0) continue;
+    const int patches = tokens_entering(p, P, i) - P;
+    RAJNI_REQUIRE(blk.keep <= patches, RAJNI_ERR_INVALID, "block %d: keep=%d but only %d patch tokens", i, blk.keep, patches);
+    RAJNI_REQUIRE(blk.keep_idx && blk.next_scores, RAJNI_ERR_INVALID, "block %d: keep_idx/next_scores buffers missing", i);
+  }
+  const int ld = logits_stride(p);
+  RAJNI_REQUIRE(ld % 8 == 0 && ld >= p.num_classes, RAJNI_ERR_INVALID,
+                "rajni_vit_forward: logits row stride must be a multiple of 8 and >= num_classes (%d)", ld);
+  return RAJNI_OK;
+}
+
 // the whole forward; ext == nullptr (rajni_vit_forward) and an all-zero record enqueue the same launches, and so does
 // pre == nullptr (or a record with one prefix token) next to any ext
 int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre, const void* images,
                 void* logits, hipStream_t s);
 
 }  // namespace
-
-extern "C" size_t rajni_vit_workspace_bytes(const rajni_vit_plan* plan) {
-  if (!plan || plan->patch_size <= 0) return 0;
-  rajni_vit_plan tmp = *plan;
-  tmp.workspace = nullptr;
-  return carve(tmp, 1).total;
-}
 
 extern "C" size_t rajni_vit_workspace_bytes_prefix(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix) {
   if (!plan || plan->patch_size <= 0) return 0;
@@ -178,6 +258,8 @@ extern "C" size_t rajni_vit_workspace_bytes_prefix(const rajni_vit_plan* plan, c
   tmp.workspace = nullptr;
   return carve(tmp, prefix_count(prefix)).total;
 }
+
+extern "C" size_t rajni_vit_workspace_bytes(const rajni_vit_plan* plan) { return rajni_vit_workspace_bytes_prefix(plan, nullptr); }
 
 extern "C" int rajni_vit_forward(const rajni_vit_plan* plan, const void* images, void* logits,
                                  rajni_stream_t stream) {
@@ -202,11 +284,8 @@ extern "C" void rajni_debug_set_last_block_all_rows(int on) { g_last_block_all_r
 // only, 0 when for all rows: the eligibility test alone, on the host, nothing launched and no device pointer followed
 extern "C" int rajni_debug_last_block_cls_rows(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix) {
   if (!plan || !plan->blocks || plan->depth <= 0 || plan->patch_size <= 0) return 0;
-  const int P = prefix_count(prefix), gw = plan->img_size / plan->patch_size;
-  int N = gw * gw + P;
-  for (int i = 0; i + 1 < plan->depth; ++i)
-    if (plan->blocks[i].keep > 0) N = plan->blocks[i].keep + P;
-  return last_block_cls_rows(*plan, ext, plan->depth - 1, N) ? 1 : 0;
+  const int last = plan->depth - 1;
+  return last_block_cls_rows(*plan, ext, last, tokens_entering(*plan, prefix_count(prefix), last)) ? 1 : 0;
 }
 
 namespace {
@@ -223,21 +302,21 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
   }
   const rajni_qk_affine* qkn = ext ? ext->qk_norm : nullptr;
   const int P = prefix_count(pre);   // prefix tokens: CLS + registers, never pruned
+  rc = check_schedule(p, P);
+  if (rc != RAJNI_OK) return rc;
   const Workspace w = carve(p, P);
   RAJNI_REQUIRE(p.workspace != nullptr && p.workspace_bytes >= w.total, RAJNI_ERR_INVALID,
                 "rajni_vit_forward: workspace too small (%zu < %zu)", p.workspace_bytes, w.total);
-  const int B = p.B, C = p.C;
-  const int gw = p.img_size / p.patch_size;
-  int N = gw * gw + P;
+  const int B = p.B, C = p.C, dt = p.dtype;
+  const Fwd f{p, w, (dt != RAJNI_F32 && !p.resid_bf16) ? 1 : 0, s};
+  int N = tokens_entering(p, P, 0);
 
-  const int dt = p.dtype;
-  const int sf32 = (dt != RAJNI_F32 && !p.resid_bf16) ? 1 : 0;  // 16-bit model with an fp32 residual stream
   rc = launch_patch_embed(images, p.patch_w, p.patch_b, p.cls_token, p.pos_embed, p.pos_has_cls,
-                          w.xa, sf32, B, p.in_chans, p.img_size, p.patch_size, C, dt, w.cols, w.cols_bytes, s,
+                          w.xa, f.sf32, B, p.in_chans, p.img_size, p.patch_size, C, dt, w.cols, w.cols_bytes, s,
                           P, P > 1 ? pre->reg_token : nullptr);
   if (rc != RAJNI_OK) return rc;
   if (ext && ext->norm_pre_w) {   // timm forward_features: x = norm_pre(x), written back into the stream
-    rc = launch_layernorm_stream(w.xa, ext->norm_pre_w, ext->norm_pre_b, B * N, C, ext->norm_pre_eps, sf32, dt, s);
+    rc = launch_layernorm_stream(w.xa, ext->norm_pre_w, ext->norm_pre_b, B * N, C, ext->norm_pre_eps, f.sf32, dt, s);
     if (rc != RAJNI_OK) return rc;
   }
 
@@ -249,86 +328,44 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
     const rajni_block& blk = p.blocks[i];
     if (p.token_counts) p.token_counts[i] = N;  // model.py:43
     const int M = B * N;
-    // ---- norm1 + qkv on ALL N tokens (model.py:51, attention.py:21-22)
-    if (p.act_fp8) rc = launch_layernorm_fp8(cur, C, blk.norm1_w, blk.norm1_b, w.xn, w.xs, nullptr, 0.f, 0.f, M, C, p.ln_eps, sf32, s);
-    else rc = launch_layernorm(cur, C, blk.norm1_w, blk.norm1_b, w.xn, M, C, p.ln_eps, sf32, dt, s);
+    rc = layernorm(f, cur, blk.norm1_w, blk.norm1_b, M);
     if (rc != RAJNI_OK) return rc;
-    rajni_linear_args g{};
-    g.dtype = dt;
-    g.x = w.xn; g.lda = C; g.w = blk.qkv_w; g.ldw = C; g.bias = blk.qkv_b; g.w_scale = blk.qkv_s;
-    if (p.act_fp8) g.x_scale = w.xs;
-    g.y = w.qkv; g.ldc = 3 * C; g.M = M; g.N = 3 * C; g.K = C; g.epilogue = RAJNI_EPI_BIAS;
-    rc = launch_linear(g, s);
+    rc = launch_linear(qkv_args(f, blk, M), s);
     if (rc != RAJNI_OK) return rc;
     if (qkn) {   // timm Attention.forward: q, k = q_norm(q), k_norm(k) - in place, so everything below reads normalised q and k
       rc = launch_qk_norm(w.qkv, qkn[i].q_norm_w, qkn[i].q_norm_b, qkn[i].k_norm_w, qkn[i].k_norm_b, M, p.H, p.D, ext->qk_eps, dt, s);
       if (rc != RAJNI_OK) return rc;
     }
 
+    // ---- the two CLS forms of the last block: only x[:, 0] reaches the head (model.py:65-66), so the tail runs on the B CLS
+    //      rows - the residual row of image b is its CLS row, row b * N of `cur` - and leaves the stream [B, 1, C] in `oth`
+    const long cls_ld = (long)N * C;
     if (p.cls_only_last_block && i == p.depth - 1 && blk.keep == 0 && N > 1) {
-      // ---- last block, not a pruning stage, caller opted in: only x[:, 0] reaches the head (model.py:65-66),
-      //      so attention runs for the CLS query alone (over all N keys) and proj / MLP on the B CLS rows
+      // caller opted in: attention for the CLS query alone (over all N keys), a kernel of its own writing [B, C]
       // (an act_fp8 block whose all-rows form would emit e4m3 attention rows rounds the CLS row the same way)
-      const bool att8c = p.act_fp8 && blk.attn_out_scale > 0.f && blk.proj_s != nullptr && p.D == 64 && N <= 224;
-      rc = launch_attention_cls(w.qkv, w.att, B, N, p.H, p.D, p.attn_scale, dt, s, att8c ? blk.attn_out_scale : 0.f);
+      rc = launch_attention_cls(w.qkv, w.att, B, N, p.H, p.D, p.attn_scale, dt, s, attn_emits_e4m3(p, blk, N) ? blk.attn_out_scale : 0.f);
       if (rc != RAJNI_OK) return rc;
-      g = rajni_linear_args{};
-      g.dtype = dt;
-      g.x = w.att; g.lda = C; g.w = blk.proj_w; g.ldw = C; g.bias = blk.proj_b; g.gamma = blk.ls1; g.w_scale = blk.proj_s;
-      g.resid = cur; g.ldr = (long)N * C;            // residual row of image b = its CLS row
-      g.y = oth; g.ldc = C; g.M = B; g.N = C; g.K = C; g.epilogue = RAJNI_EPI_BIAS_RESID; g.stream_f32 = sf32;
-      rc = launch_linear(g, s);
+      rc = launch_tail(f, blk, tail_args(f, blk, AttnRows{B, C, nullptr, cls_ld, nullptr, 0, 0}, cur, oth));
       if (rc != RAJNI_OK) return rc;
-      { char* t = cur; cur = oth; oth = t; }
-      N = 1;                                          // the stream is now [B, 1, C]
-      if (p.act_fp8) rc = launch_layernorm_fp8(cur, C, blk.norm2_w, blk.norm2_b, w.xn, w.xs, w.hs, blk.fc1_rownorm_max,
-                                               blk.fc1_bias_absmax, B, C, p.ln_eps, sf32, s);
-      else rc = launch_layernorm(cur, C, blk.norm2_w, blk.norm2_b, w.xn, B, C, p.ln_eps, sf32, dt, s);
-      if (rc != RAJNI_OK) return rc;
-      g = rajni_linear_args{};
-      g.dtype = dt;
-      g.x = w.xn; g.lda = C; g.w = blk.fc1_w; g.ldw = C; g.bias = blk.fc1_b; g.w_scale = blk.fc1_s;
-      g.y = w.hid; g.ldc = p.hidden; g.M = B; g.N = p.hidden; g.K = C; g.epilogue = RAJNI_EPI_BIAS_GELU;
-      if (p.act_fp8) { g.x_scale = w.xs; g.y_scale = w.hs; }
-      rc = launch_linear(g, s);
-      if (rc != RAJNI_OK) return rc;
-      g = rajni_linear_args{};
-      g.dtype = dt;
-      g.x = w.hid; g.lda = p.hidden; g.w = blk.fc2_w; g.ldw = p.hidden; g.bias = blk.fc2_b; g.gamma = blk.ls2; g.w_scale = blk.fc2_s;
-      if (p.act_fp8) g.x_scale = w.hs;
-      g.resid = cur; g.ldr = C; g.y = cur; g.ldc = C; g.M = B; g.N = C; g.K = p.hidden;
-      g.epilogue = RAJNI_EPI_BIAS_RESID; g.stream_f32 = sf32;
-      rc = launch_linear(g, s);
-      if (rc != RAJNI_OK) return rc;
+      cur = oth; N = 1;
       break;
     }
-
     if (last_block_cls_rows(p, ext, i, N)) {
-      // ---- last block, nothing but x[:, 0] observable behind its K and V: the all-rows kernels on the rows the head reads
-      const ClsRowLinears l = cls_row_linears(p, blk, N, w.att, cur, oth, w.xn, w.hid, sf32);
-      if (cls_row_linears_ok(l)) {   // (a refused shape or stride: all rows below, as if this branch were not here)
-        rc = launch_attention(w.qkv, nullptr, w.att, B, N, N, 1, p.H, p.D, p.attn_scale, dt, s);   // CLS row of image b: row b * N
+      // the all-rows kernels on the rows the head reads: the first query tile, proj on its CLS rows in place (stride N * C)
+      const Tail t = tail_args(f, blk, AttnRows{B, cls_ld, nullptr, cls_ld, nullptr, 0, 0}, cur, oth);
+      if (tail_ok(t)) {   // (a refused shape or stride: all rows below, as if this branch were not here)
+        rc = launch_attention(w.qkv, nullptr, w.att, B, N, N, 1, p.H, p.D, p.attn_scale, dt, s);
         if (rc != RAJNI_OK) return rc;
-        rc = launch_linear(l.proj, s);
+        rc = launch_tail(f, blk, t);
         if (rc != RAJNI_OK) return rc;
-        { char* t = cur; cur = oth; oth = t; }
-        N = 1;                                          // the stream is now [B, 1, C]
-        rc = launch_layernorm(cur, C, blk.norm2_w, blk.norm2_b, w.xn, B, C, p.ln_eps, sf32, dt, s);
-        if (rc != RAJNI_OK) return rc;
-        rc = launch_linear(l.fc1, s);
-        if (rc != RAJNI_OK) return rc;
-        rc = launch_linear(l.fc2, s);
-        if (rc != RAJNI_OK) return rc;
+        cur = oth; N = 1;
         break;
       }
     }
 
-    int Np = N;
+    const int Np = tokens_after(blk, N, P);
     const int32_t* idx = nullptr;
     if (blk.keep > 0) {  // scheduled block (model.py:50)
-      RAJNI_REQUIRE(blk.keep <= N - P, RAJNI_ERR_INVALID, "block %d: keep=%d but only %d patch tokens", i, blk.keep, N - P);
-      RAJNI_REQUIRE(blk.keep_idx && blk.next_scores, RAJNI_ERR_INVALID, "block %d: keep_idx/next_scores buffers missing", i);
-      Np = blk.keep + P;
       const bool recompute = blk.update || carried == nullptr;  // attention.py:25
       if (blk.forced_keep_idx) {
         const void* full = carried;
@@ -363,70 +400,30 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
     }
 
     // ---- attention on the kept tokens, gather fused (attention.py:42-54)
-    // act_fp8 plans: e4m3 output rows + their (one) scale into w.xs - norm1's row scales there were consumed by QKV -
-    // wherever the persistent head-dim-64 kernel serves the launch (rajni_attention_fp8); proj then runs fp8 x fp8
-    const bool att8 = p.act_fp8 && blk.attn_out_scale > 0.f && blk.proj_s != nullptr && p.D == 64 && Np <= 224;
+    const bool att8 = attn_emits_e4m3(p, blk, Np);
     if (att8) rc = launch_attention_fp8(w.qkv, idx, w.att, blk.attn_out_scale, w.xs, B, N, Np, p.H, p.D, p.attn_scale, s);
     else rc = launch_attention(w.qkv, idx, w.att, B, N, Np, Np, p.H, p.D, p.attn_scale, dt, s);
     if (rc != RAJNI_OK) return rc;
-
-    // ---- proj + (gathered) residual + LayerScale (attention.py:55-56, model.py:55-58)
-    const int Mp = B * Np;
-    g = rajni_linear_args{};
-    g.dtype = dt;
-    g.x = w.att; g.lda = C; g.w = blk.proj_w; g.ldw = C; g.bias = blk.proj_b; g.gamma = blk.ls1; g.w_scale = blk.proj_s;
-    g.resid = cur; g.ldr = C; g.M = Mp; g.N = C; g.K = C; g.epilogue = RAJNI_EPI_BIAS_RESID; g.stream_f32 = sf32;
-    if (att8) g.x_scale = w.xs;
-    if (idx) {
-      g.r_idx = idx; g.r_np = Np; g.r_nsrc = N;
-      g.y = oth; g.ldc = C;
-      rc = launch_linear(g, s);
-      char* t = cur; cur = oth; oth = t;
-    } else {
-      g.y = cur; g.ldc = C;  // each element is read and written by the same lane: in place is safe
-      rc = launch_linear(g, s);
-    }
+    // a pruned block gathers its residual rows from `cur` into `oth`; an unpruned one runs proj in place (each element is
+    // read and written by the same lane: in place is safe)
+    char* y = idx ? oth : cur;
+    rc = launch_tail(f, blk, tail_args(f, blk, AttnRows{B * Np, C, att8 ? w.xs : nullptr, C, idx, Np, N}, cur, y));
     if (rc != RAJNI_OK) return rc;
+    if (idx) { oth = cur; cur = y; }
     N = Np;
-
-    // ---- MLP (model.py:59): norm2 -> fc1 + GELU -> fc2 + LayerScale + residual (in place)
-    if (p.act_fp8) rc = launch_layernorm_fp8(cur, C, blk.norm2_w, blk.norm2_b, w.xn, w.xs, w.hs, blk.fc1_rownorm_max,
-                                                  blk.fc1_bias_absmax, Mp, C, p.ln_eps, sf32, s);
-    else rc = launch_layernorm(cur, C, blk.norm2_w, blk.norm2_b, w.xn, Mp, C, p.ln_eps, sf32, dt, s);
-    if (rc != RAJNI_OK) return rc;
-    g = rajni_linear_args{};
-    g.dtype = dt;
-    g.x = w.xn; g.lda = C; g.w = blk.fc1_w; g.ldw = C; g.bias = blk.fc1_b; g.w_scale = blk.fc1_s;
-    g.y = w.hid; g.ldc = p.hidden; g.M = Mp; g.N = p.hidden; g.K = C; g.epilogue = RAJNI_EPI_BIAS_GELU;
-    if (p.act_fp8) { g.x_scale = w.xs; g.y_scale = w.hs; }   // e4m3 in, e4m3 out (per-row scales)
-    rc = launch_linear(g, s);
-    if (rc != RAJNI_OK) return rc;
-    g = rajni_linear_args{};
-    g.dtype = dt;
-    g.x = w.hid; g.lda = p.hidden; g.w = blk.fc2_w; g.ldw = p.hidden; g.bias = blk.fc2_b; g.gamma = blk.ls2; g.w_scale = blk.fc2_s;
-    if (p.act_fp8) g.x_scale = w.hs;
-    g.resid = cur; g.ldr = C; g.y = cur; g.ldc = C; g.M = Mp; g.N = C; g.K = p.hidden;
-    g.epilogue = RAJNI_EPI_BIAS_RESID; g.stream_f32 = sf32;
-    rc = launch_linear(g, s);
-    if (rc != RAJNI_OK) return rc;
   }
 
   // ---- final norm on the CLS rows only (LN is per token; model.py:65-66) + head
   // (with a pooled head, fc_norm or no norm: norm on every row that is pooled -> pool -> fc_norm, one kernel)
   if (ext && (ext->pool != RAJNI_POOL_TOKEN || ext->fc_norm_w || ext->norm_absent))
     rc = launch_pool_norm(cur, B, N, C, ext->pool, ext->norm_absent ? nullptr : p.norm_w, p.norm_b, p.ln_eps,
-                          ext->fc_norm_w, ext->fc_norm_b, ext->fc_norm_eps, w.clsn, sf32, dt, s, P);
+                          ext->fc_norm_w, ext->fc_norm_b, ext->fc_norm_eps, w.clsn, f.sf32, dt, s, P);
   else
-    rc = launch_layernorm(cur, (long)N * C, p.norm_w, p.norm_b, w.clsn, B, C, p.ln_eps, sf32, dt, s);
+    rc = launch_layernorm(cur, (long)N * C, p.norm_w, p.norm_b, w.clsn, B, C, p.ln_eps, f.sf32, dt, s);
   if (rc != RAJNI_OK) return rc;
-  rajni_linear_args g{};
-  g.dtype = dt;
-  g.x = w.clsn; g.lda = C; g.w = p.head_w; g.ldw = C; g.bias = p.head_b;
-  const int ld = p.logits_ld > 0 ? p.logits_ld : p.num_classes;
-  RAJNI_REQUIRE(ld % 8 == 0 && ld >= p.num_classes, RAJNI_ERR_INVALID,
-                "rajni_vit_forward: logits row stride must be a multiple of 8 and >= num_classes (%d)", ld);
-  g.y = logits; g.ldc = ld; g.M = B; g.N = p.num_classes; g.K = C; g.epilogue = RAJNI_EPI_BIAS;
-  return launch_linear(g, s);
+  rajni_linear_args head = linear_args(dt, w.clsn, p.head_w, p.head_b, nullptr, logits, B, p.num_classes, C, RAJNI_EPI_BIAS);
+  head.ldc = logits_stride(p);
+  return launch_linear(head, s);
 }
 
 }  // namespace

@@ -859,12 +859,6 @@ int launch_score_tiled(ScoreArgs a, int B, int dtype, void* ws, size_t ws_bytes,
 }
 }  // namespace
 
-int launch_score_select(const void* qkv, const void* scores_in, int B, int N, int H, int D,
-                        float eps, int keep, void* scores_out, int32_t* keep_idx,
-                        void* next_scores, int dtype, hipStream_t s, int P) {
-  return launch_score_select(qkv, scores_in, B, N, H, D, eps, keep, scores_out, keep_idx, next_scores, dtype, s, P, nullptr, 0);
-}
-
 // qkv != null: compute scores (and select when keep > 0); qkv == null: select from scores_in.
 int launch_score_select(const void* qkv, const void* scores_in, int B, int N, int H, int D,
                         float eps, int keep, void* scores_out, int32_t* keep_idx,
