@@ -48,6 +48,13 @@ void rajni_debug_set_resid_stagger(int units);
  * order; -k = blocks of k column tiles regardless of size.  Results are bit-identical for every value (tested). */
 void rajni_debug_set_gemm_nblock_bytes(int bytes);
 
+/* Persistent launches (the 256-row stream tilings of rajni_linear and rajni_patch_embed on 16-bit, fp8-weight and fp8 x fp8
+ * operands; the head-dim-64 attention kernel for up to 256 kept tokens, rajni_attention_fp8 and rajni_debug_attention_rows
+ * included) use at most `n` workgroups; 0 (default) = as many as the device takes.  ONLY the grid changes: tiling, tile and
+ * item order, N blocks and dynamic LDS stay, so each workgroup walks more tiles or items through its next-tile / next-item
+ * pipeline.  Results are bit-identical for every n (tested); rajni_debug_linear_plan reports the capped grid. */
+void rajni_debug_set_persistent_workgroups(int n);
+
 /* Dry run of a linear call: the same argument checks, format / epilogue resolution and tiling choice, for a device of
  * `cus` compute units (no device needed), and no launch.  Returns the code the call itself would return before launching and
  * sets the same last-error text; on RAJNI_OK `*out` holds what would be launched.  The pointers in `args` are checked

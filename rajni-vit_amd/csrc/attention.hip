@@ -965,7 +965,7 @@ int launch_full_o8(const AttnArgs& a, int B, hipStream_t s) {   // e4m3 output: 
   const int per_cu = (160 * 1024) / lds >= 2 ? 2 : 1;
   const int items = a.H * B;
   const int cus = rajni_num_cus();
-  const int grid = items < cus * per_cu ? items : cus * per_cu;
+  const int grid = rajni_persistent_grid(items < cus * per_cu ? items : cus * per_cu);
   if (a.idx != nullptr)
     hipLaunchKernelGGL((attn_bf16_d64_stream<NSUB, true, true>), dim3(grid), dim3(ATF_THREADS), lds, s, a, items);
   else
@@ -994,7 +994,7 @@ int launch_full(const AttnArgs& a, int B, hipStream_t s) {
   const int per_cu = (160 * 1024) / lds >= 2 ? 2 : 1;   // 512-thread workgroups resident per CU
   const int items = a.H * B;
   const int cus = rajni_num_cus();
-  const int grid = items < cus * per_cu ? items : cus * per_cu;
+  const int grid = rajni_persistent_grid(items < cus * per_cu ? items : cus * per_cu);
   if (a.idx != nullptr)
     hipLaunchKernelGGL((attn_bf16_d64_stream<NSUB, true, false, A>), dim3(grid), dim3(ATF_THREADS), lds, s, a, items);
   else

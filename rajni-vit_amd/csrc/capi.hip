@@ -31,6 +31,8 @@ const char* const kNames[RAJNI_NUM_KCLASS] = {
 }  // namespace
 
 unsigned long long* rajni_g_stamps = nullptr;
+int rajni_g_persistent_cap = 0;   // test hook: at most this many workgroups per persistent launch (0 = no cap)
+extern "C" void rajni_debug_set_persistent_workgroups(int n) { rajni_g_persistent_cap = n > 0 ? n : 0; }
 
 int rajni_current_device() {
   int dev = 0;

@@ -152,6 +152,10 @@ void rajni_set_error(const char* fmt, ...);
 #define RAJNI_MAX_DEVICES 32
 int rajni_current_device();
 int rajni_num_cus();
+// workgroups of a persistent launch that would take `grid`: the test hook rajni_debug_set_persistent_workgroups
+// (include/rajni_hip_debug.h) caps it; 0 (default) = as computed.  Only the grid changes - tiles, items and their order do not.
+extern int rajni_g_persistent_cap;
+inline int rajni_persistent_grid(int grid) { return rajni_g_persistent_cap > 0 && grid > rajni_g_persistent_cap ? rajni_g_persistent_cap : grid; }
 
 enum KClass {
   KC_GEMM_BIAS = 0, KC_GEMM_GELU = 1, KC_GEMM_RESID = 2, KC_GEMM_PATCH = 3, KC_ATTENTION = 4,

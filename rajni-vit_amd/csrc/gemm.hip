@@ -1405,7 +1405,7 @@ inline bool wide_wins_on_rounds(int M, int N, int cus) {
 // persistent grid: one workgroup per CU of the device the launch goes to (hipDeviceProp_t::multiProcessorCount;
 // 256 on MI355X).  A grid balanced to whole rounds, as hipBLASLt picks for fc2, was measured: 0.7 % slower over
 // the 20 GEMM shapes of the schedule.
-inline int stream_grid(int total_tiles, int cus) { return total_tiles <= cus ? total_tiles : cus; }
+inline int stream_grid(int total_tiles, int cus) { return rajni_persistent_grid(total_tiles <= cus ? total_tiles : cus); }
 
 // what a choice needs to know of the instantiations behind a launch
 struct TileTraits {

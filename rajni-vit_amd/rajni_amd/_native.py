@@ -118,6 +118,7 @@ _SIGS = {
     "rajni_debug_force_f8_tiling": (None, [c_int]),
     "rajni_debug_set_resid_stagger": (None, [c_int]),
     "rajni_debug_set_gemm_nblock_bytes": (None, [c_int]),
+    "rajni_debug_set_persistent_workgroups": (None, [c_int]),
     "rajni_debug_linear_plan": (c_int, [C.POINTER(LinearArgs), c_int, C.POINTER(LinearPlan)]),
     "rajni_debug_force_attention": (None, [c_int]),
     "rajni_debug_attention_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float,

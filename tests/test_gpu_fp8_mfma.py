@@ -17,19 +17,10 @@ from oracle import rajni_oracle as orc
 from rajni_amd import ops, timm_shaped as ts, _native as nat
 from rajni_amd.timm_shaped import bf16_round_np
 from helpers import load_case, case_images, pruned_blocks
+import numerics_fp8 as n8
+from numerics_fp8 import e4m3_bytes_to_f64
 
 DEV = "cuda"
-
-
-def e4m3_bytes_to_f64(q: torch.Tensor) -> np.ndarray:
-    return q.cpu().view(torch.float8_e4m3fn).to(torch.float32).numpy().astype(np.float64)
-
-
-def random_e4m3(rng, shape):
-    """uniform random e4m3 codes without the two NaN patterns (0x7F, 0xFF)"""
-    b = rng.integers(0, 256, size=shape, dtype=np.uint8)
-    b[(b & 0x7F) == 0x7F] = 0x38
-    return b
 
 
 @pytest.mark.parametrize("rows,Cc,x_f32", [(300, 768, True), (64, 512, False), (1000, 1024, True), (5, 256, True),
@@ -85,18 +76,8 @@ def test_attention_fp8_output_rule(B, N, Np, H, loose):
     xb = torch.from_numpy(qkv).to(DEV).to(torch.bfloat16)
     out, rs = ops.attention_fp8(xb, idx_t, H, 64 ** -0.5, scale)
     assert out.dtype == torch.uint8 and tuple(out.shape) == (B, Np, Cc)
-    assert (rs.cpu().numpy() == np.float32(scale)).all()
-    deq = e4m3_bytes_to_f64(out) * np.float64(np.float32(scale))
     ref = ops.attention(xb, idx_t, H, 64 ** -0.5).float().cpu().numpy().astype(np.float64)     # the bf16-output kernel: same products
-    # e4m3: half an ulp = 2^-4 relative in the normal range, scale * 2^-10 absolute below it; on top, what separates the two
-    # kernels' own roundings of the same fp32 value (bf16 output: 2^-9 relative)
-    bound = np.maximum(np.abs(ref) * 2.0 ** -4, scale * 2.0 ** -10) * 1.001 + np.abs(ref) * 2.0 ** -8 + 1e-6 * np.abs(want).max()
-    assert (np.abs(deq - ref) <= bound).all(), float((np.abs(deq - ref) - bound).max())
-    assert np.abs(deq - want).max() <= (2.0 ** -4 + 1.5e-2) * np.abs(want).max()
-    # byte for byte the stated rule applied to the bf16 kernel's output, except where that output sits within its own
-    # rounding of an e4m3 boundary
-    rule = orc.quantize_rows_e4m3(ref, np.float32(scale))
-    assert np.mean(rule != deq) < 0.08
+    n8.check_attention_fp8(out, rs, ref, want, scale)     # bounds and the byte rule: tests/numerics_fp8.py
 
 
 def test_attention_fp8_refuses_what_it_does_not_serve():
@@ -131,15 +112,7 @@ def test_attention_out_scale_is_a_bound_and_matches_the_oracle():
 
 
 def _f8_operands(rng, M, N, K):
-    xq, wq = random_e4m3(rng, (M, K)), random_e4m3(rng, (N, K))
-    # keep products tame: scales so that dequantised entries are O(1)
-    xs = (rng.uniform(0.5, 2.0, size=M) / 64.0).astype(np.float32)
-    ws = (rng.uniform(0.5, 2.0, size=N) / 64.0).astype(np.float32)
-    npad = (N + 255) // 256 * 256
-    wp = np.zeros((npad, K), np.uint8)
-    wp[:N] = wq
-    xd = e4m3_bytes_to_f64(torch.from_numpy(xq)) * xs[:, None]
-    wd = e4m3_bytes_to_f64(torch.from_numpy(wq)) * ws[:, None]
+    xq, xs, wp, ws, xd, wd = n8.f8_operands(rng, M, N, K)
     dev = lambda a: torch.from_numpy(a).to(DEV)
     return dev(xq), dev(xs), dev(wp), dev(ws), xd, wd
 
@@ -162,7 +135,7 @@ def test_linear_f8_bias(M, N, K, f8_tiling):
     assert y.dtype == torch.bfloat16
     want = xd @ wd.T + b
     got = y.float().cpu().numpy()[:, :N]
-    assert np.abs(got - want).max() <= 2.0 ** -8 * np.abs(want).max() + 1e-3
+    n8.check_bias(got, want)
 
 
 @pytest.mark.parametrize("M,N,K", [(256, 256, 512), (700, 3072, 768), (60, 1000, 1024), (1300, 520, 768), (2100, 3072, 768)])
@@ -172,16 +145,12 @@ def test_linear_f8_gelu_requant(M, N, K, f8_tiling):
     xq, xs, wp, ws, xd, wd = _f8_operands(rng, M, N, K)
     b = rng.standard_normal(N).astype(np.float32)
     pre = xd @ wd.T + b
-    h = orc.gelu(pre)
-    ys = (np.abs(pre).max(axis=1) * rng.uniform(1.0, 8.0, size=M) / 448.0).astype(np.float32)   # a bound, not the max
+    ys = n8.gelu8_row_scales(rng, pre)                       # a bound, not the max
     y = ops.linear(xq, wp, N, torch.from_numpy(b).to(DEV), nat.EPI_BIAS_GELU, w_scale=ws, x_scale=xs,
                    y_scale=torch.from_numpy(ys).to(DEV))
     assert y.dtype == torch.uint8
     deq = e4m3_bytes_to_f64(y)[:, :N] * ys[:, None].astype(np.float64)
-    bound = np.maximum(np.abs(h) * 2.0 ** -4, ys[:, None] * 2.0 ** -10) * 1.01 + 2e-4 * np.abs(h).max()
-    assert (np.abs(deq - h) <= bound).all()
-    want = orc.quantize_rows_e4m3(h, ys)
-    assert np.mean(want != deq) < 5e-3          # fp32 accumulation order + the 4e-5 GELU polynomial near boundaries
+    n8.check_gelu8(deq, pre, ys)
 
 
 @pytest.mark.parametrize("M,N,K,gather", [(512, 768, 3072, False), (700, 768, 1024, True), (90, 256, 512, False),
@@ -208,7 +177,7 @@ def test_linear_f8_resid_fp32_stream(M, N, K, gather):
     assert y.dtype == torch.float32
     want = gam * (xd @ wd.T + b) + r_rows
     got = y.cpu().numpy().reshape(M, -1)[:, :N]
-    assert np.abs(got - want).max() <= 1e-4 * np.abs(want).max()      # fp32 accumulation over K <= 3072 wide-range terms
+    n8.check_resid_f32(got, want)
 
 
 def _build_f8(cfg_name, sched, seed, std=0.06):

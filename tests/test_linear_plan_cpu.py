@@ -56,6 +56,7 @@ def hooks():
         lib.rajni_debug_force_gemm_tiling(force)
         lib.rajni_debug_force_f8_tiling(force_f8)
         lib.rajni_debug_set_gemm_nblock_bytes(nblk)
+        lib.rajni_debug_set_persistent_workgroups(0)
     yield set_hooks
     set_hooks()
 
