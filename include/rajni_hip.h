@@ -69,6 +69,50 @@ enum {
 #define RAJNI_MAX_GRID_YZ 65535
 #define RAJNI_QK_NORM_MAX_GROUPS ((1LL << 31) - 1024)
 
+/* ---- placement: minimum alignment of every pointer ----
+ * The kernels reach memory in 16-byte pieces wherever they can, so WHERE a buffer sits is part of the contract.  Minimum
+ * alignment in bytes of each pointer of each entry point ("elem" = one element of `dtype`: 2 bytes for bf16 / fp16, 4 for fp32):
+ *   - data tensors (activations, weights, qkv, images, the residual stream, outputs, e4m3 bytes, cls / reg / pos, the
+ *     patch-embed column workspace): 16.  Row strides keep their own rules and no others: lda / ldw / ldc / ldr,
+ *     x_row_stride and logits_ld are multiples of 8 elements (bytes % 16 for e4m3 operands), so every row starts on a
+ *     16-byte boundary and nothing more is assumed - not a 128-byte line, not a dense row.  (rajni_linear with
+ *     dtype RAJNI_F32 reads the residual row one element at a time and asks for no ldr rule.)
+ *   - fp32 per-column vectors (bias, gamma / LayerScale, LayerNorm and q/k-norm w and b, w_scale): 16 - every kernel
+ *     that takes one reads it as float4 somewhere (LayerNorm rows, the stream tilings' epilogues).
+ *   - arrays indexed per element: x_scale, y_scale, row_scale, hid_scale (fp32) and keep_idx / idx / r_idx (int32): 4;
+ *     score arrays (scores, scores_out, next_scores): elem.
+ *   - scratch of the tiled score path and rajni_vit_plan.workspace: 256 (the forward carves its workspace at 256-byte
+ *     offsets from the base, and the score scratch is one of the pieces).
+ * A pointer below its minimum is refused with RAJNI_ERR_INVALID and a message that names it, before anything is
+ * launched; a NULL optional pointer is aligned.  No kernel or tiling choice looks at an address or at a stride's
+ * residue: the same values at another legal placement give the same bits.  The table (one entry point per line, `name
+ * bytes`; the whole forward per struct):
+ *   rajni_importance: qkv 16, scores_out elem
+ *   rajni_select_topk: scores elem, keep_idx 4, next_scores elem
+ *   rajni_score_select: qkv 16, scores_out elem, keep_idx 4, next_scores elem
+ *   rajni_select_topk_prefix: scores elem, keep_idx 4, next_scores elem
+ *   rajni_score_select_prefix: qkv 16, scores_out elem, keep_idx 4, next_scores elem
+ *   rajni_score_select_ws: qkv 16, scores_out elem, keep_idx 4, next_scores elem, workspace 256
+ *   rajni_gather_rows: src 16, idx 4, dst 16
+ *   rajni_attention: qkv 16, keep_idx 4, out 16
+ *   rajni_attention_fp8: qkv 16, keep_idx 4, out_q 16, row_scale 4
+ *   rajni_layernorm: x 16, w 16, b 16, y 16
+ *   rajni_layernorm_fp8: x 16, w 16, b 16, y_q 16, y_scale 4, hid_scale 4
+ *   rajni_linear: x 16, w 16, y 16, resid 16, bias 16, gamma 16, w_scale 16, x_scale 4, y_scale 4, r_idx 4
+ *   rajni_patch_embed: images 16, w 16, bias 16, cls 16, pos 16, x 16, workspace 16
+ *   rajni_patch_embed_prefix: images 16, w 16, bias 16, cls 16, reg 16, pos 16, x 16, workspace 16
+ *   rajni_qk_norm: qkv 16, q_w 16, q_b 16, k_w 16, k_b 16
+ *   rajni_layernorm_stream: x 16, w 16, b 16
+ *   rajni_pool_norm: x 16, norm_w 16, norm_b 16, fc_w 16, fc_b 16, out 16
+ *   rajni_pool_norm_prefix: x 16, norm_w 16, norm_b 16, fc_w 16, fc_b 16, out 16
+ *   rajni_vit_forward: images 16, logits 16
+ *   rajni_vit_plan: patch_w 16, patch_b 16, cls_token 16, pos_embed 16, norm_w 16, norm_b 16, head_w 16, head_b 16, workspace 256
+ *   rajni_block: norm1_w 16, norm1_b 16, qkv_w 16, qkv_b 16, proj_w 16, proj_b 16, ls1 16, norm2_w 16, norm2_b 16, fc1_w 16, fc1_b 16, fc2_w 16, fc2_b 16, ls2 16, keep_idx 4, scores elem, next_scores elem, forced_keep_idx 4, qkv_s 16, proj_s 16, fc1_s 16, fc2_s 16
+ *   rajni_qk_affine: q_norm_w 16, q_norm_b 16, k_norm_w 16, k_norm_b 16
+ *   rajni_vit_ext: norm_pre_w 16, norm_pre_b 16, fc_norm_w 16, fc_norm_b 16
+ *   rajni_vit_prefix: reg_token 16
+ * (end of the placement table) */
+
 #define RAJNI_ABI_VERSION 8 /* bumped whenever a struct or an entry point changes; checked by the ctypes binding */
 int rajni_abi_version(void); /* == RAJNI_ABI_VERSION of the header the library was built from */
 const char* rajni_last_error(void);
@@ -332,7 +376,7 @@ int rajni_score_select_prefix(const void* qkv, int B, int N, int H, int D, float
                               rajni_stream_t stream);
 /* rajni_patch_embed writing x [B, num_prefix+(S/P)^2, C]: row 0 = cls, rows 1..num_prefix-1 = reg [num_prefix-1, C]
  * (`dtype`; may be NULL when num_prefix = 1), then the patches; pos [(pos_has_cls ? num_prefix : 0)+(S/P)^2, C].
- * cls, reg and pos must be 16-byte aligned when num_prefix > 1. */
+ * cls, reg and pos are 16-byte aligned like every data tensor (see "placement"). */
 int rajni_patch_embed_prefix(const void* images, const void* w, const float* bias, const void* cls, const void* reg,
                              int num_prefix, const void* pos, int pos_has_cls, void* x, int x_f32, int B, int Cin, int S,
                              int P, int C, int dtype, void* workspace, size_t workspace_bytes, rajni_stream_t stream);

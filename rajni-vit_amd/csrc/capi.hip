@@ -57,6 +57,13 @@ void rajni_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+int rajni_check_placement(const char* who, const PlacedPtr* ptrs, int n) {
+  for (int i = 0; i < n; ++i)
+    RAJNI_REQUIRE(reinterpret_cast<uintptr_t>(ptrs[i].p) % (uintptr_t)ptrs[i].align == 0, RAJNI_ERR_INVALID,
+                  "%s: %s must be %d-byte aligned", who, ptrs[i].name, ptrs[i].align);
+  return RAJNI_OK;
+}
+
 ProfScope::ProfScope(int kclass, hipStream_t stream, double flops, double bytes)
     : kc(kclass), s(stream), rec(nullptr) {
   if (!(g_prof_mask & (1u << kclass))) return;
@@ -106,6 +113,7 @@ int rajni_device_check(void) {
 int rajni_importance(const void* qkv, void* scores_out, int B, int N, int H, int D, float eps,
                      int dtype, rajni_stream_t stream) {
   NEED_DTYPE("rajni_importance");
+  RAJNI_REQUIRE_PLACED("rajni_importance", {"qkv", qkv, 16}, {"scores_out", scores_out, rajni_elem_bytes(dtype)});
   RAJNI_REQUIRE(qkv && scores_out, RAJNI_ERR_INVALID, "rajni_importance: null pointer");
   return launch_score_select(qkv, nullptr, B, N, H, D, eps, 0, scores_out, nullptr, nullptr, dtype,
                              (hipStream_t)stream);
@@ -114,6 +122,8 @@ int rajni_importance(const void* qkv, void* scores_out, int B, int N, int H, int
 int rajni_select_topk(const void* scores, int B, int N, int keep, int32_t* keep_idx,
                       void* next_scores, int dtype, rajni_stream_t stream) {
   NEED_DTYPE("rajni_select_topk");
+  RAJNI_REQUIRE_PLACED("rajni_select_topk", {"scores", scores, rajni_elem_bytes(dtype)}, {"keep_idx", keep_idx, 4},
+                       {"next_scores", next_scores, rajni_elem_bytes(dtype)});
   RAJNI_REQUIRE(scores && keep_idx, RAJNI_ERR_INVALID, "rajni_select_topk: null pointer");
   RAJNI_REQUIRE(keep >= 1, RAJNI_ERR_INVALID, "rajni_select_topk: keep must be >= 1");
   return launch_score_select(nullptr, scores, B, N, 0, 0, 0.f, keep, nullptr, keep_idx, next_scores, dtype,
@@ -124,6 +134,8 @@ int rajni_score_select(const void* qkv, int B, int N, int H, int D, float eps, i
                        void* scores_out, int32_t* keep_idx, void* next_scores, int dtype,
                        rajni_stream_t stream) {
   NEED_DTYPE("rajni_score_select");
+  RAJNI_REQUIRE_PLACED("rajni_score_select", {"qkv", qkv, 16}, {"scores_out", scores_out, rajni_elem_bytes(dtype)},
+                       {"keep_idx", keep_idx, 4}, {"next_scores", next_scores, rajni_elem_bytes(dtype)});
   RAJNI_REQUIRE(qkv && keep_idx, RAJNI_ERR_INVALID, "rajni_score_select: null pointer");
   RAJNI_REQUIRE(keep >= 1, RAJNI_ERR_INVALID, "rajni_score_select: keep must be >= 1");
   return launch_score_select(qkv, nullptr, B, N, H, D, eps, keep, scores_out, keep_idx, next_scores, dtype,
@@ -133,6 +145,8 @@ int rajni_score_select(const void* qkv, int B, int N, int H, int D, float eps, i
 int rajni_select_topk_prefix(const void* scores, int B, int N, int num_prefix, int keep, int32_t* keep_idx,
                              void* next_scores, int dtype, rajni_stream_t stream) {
   NEED_DTYPE("rajni_select_topk_prefix");
+  RAJNI_REQUIRE_PLACED("rajni_select_topk_prefix", {"scores", scores, rajni_elem_bytes(dtype)}, {"keep_idx", keep_idx, 4},
+                       {"next_scores", next_scores, rajni_elem_bytes(dtype)});
   RAJNI_REQUIRE(scores && keep_idx, RAJNI_ERR_INVALID, "rajni_select_topk_prefix: null pointer");
   RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
                 "rajni_select_topk_prefix: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
@@ -148,6 +162,8 @@ int rajni_score_select_prefix(const void* qkv, int B, int N, int H, int D, float
                               void* scores_out, int32_t* keep_idx, void* next_scores, int dtype,
                               rajni_stream_t stream) {
   NEED_DTYPE("rajni_score_select_prefix");
+  RAJNI_REQUIRE_PLACED("rajni_score_select_prefix", {"qkv", qkv, 16}, {"scores_out", scores_out, rajni_elem_bytes(dtype)},
+                       {"keep_idx", keep_idx, 4}, {"next_scores", next_scores, rajni_elem_bytes(dtype)});
   RAJNI_REQUIRE(qkv && keep_idx, RAJNI_ERR_INVALID, "rajni_score_select_prefix: null pointer");
   RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
                 "rajni_score_select_prefix: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
@@ -167,6 +183,8 @@ int rajni_score_select_ws(const void* qkv, int B, int N, int H, int D, float eps
   RAJNI_REQUIRE(B <= RAJNI_MAX_GRID_YZ || rajni_score_select_workspace_bytes(B, N, H, D, dtype) == 0, RAJNI_ERR_UNSUPPORTED,
                 "rajni_score_select_ws: B=%d - one launch of the tiled path takes at most %d images (grid: token tiles x images)",
                 B, RAJNI_MAX_GRID_YZ);
+  RAJNI_REQUIRE_PLACED("rajni_score_select_ws", {"qkv", qkv, 16}, {"scores_out", scores_out, rajni_elem_bytes(dtype)},
+                       {"keep_idx", keep_idx, 4}, {"next_scores", next_scores, rajni_elem_bytes(dtype)}, {"workspace", workspace, 256});
   RAJNI_REQUIRE(qkv != nullptr, RAJNI_ERR_INVALID, "rajni_score_select_ws: qkv is null");
   RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
                 "rajni_score_select_ws: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
@@ -179,8 +197,6 @@ int rajni_score_select_ws(const void* qkv, int B, int N, int H, int D, float eps
   const size_t need = rajni_score_select_workspace_bytes(B, N, H, D, dtype);
   RAJNI_REQUIRE(need == 0 || workspace != nullptr, RAJNI_ERR_INVALID,
                 "rajni_score_select_ws: workspace is null but N=%d H=%d D=%d needs %zu B (rajni_score_select_workspace_bytes)", N, H, D, need);
-  RAJNI_REQUIRE(workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, RAJNI_ERR_INVALID,
-                "rajni_score_select_ws: workspace must be 256-byte aligned");
   RAJNI_REQUIRE(workspace_bytes >= need, RAJNI_ERR_INVALID,
                 "rajni_score_select_ws: workspace_bytes=%zu but N=%d H=%d D=%d needs %zu B", workspace_bytes, N, H, D, need);
   return launch_score_select(qkv, nullptr, B, N, H, D, eps, keep, scores_out, keep_idx, next_scores, dtype,
@@ -190,6 +206,7 @@ int rajni_score_select_ws(const void* qkv, int B, int N, int H, int D, float eps
 int rajni_gather_rows(const void* src, const int32_t* idx, void* dst, int B, int n_src, int n_dst,
                       int row_elems, int dtype, rajni_stream_t stream) {
   NEED_DTYPE("rajni_gather_rows");
+  RAJNI_REQUIRE_PLACED("rajni_gather_rows", {"src", src, 16}, {"idx", idx, 4}, {"dst", dst, 16});
   const int es = dtype == RAJNI_F32 ? 4 : 2;   // a byte copy: bf16 and fp16 rows alike
   return launch_gather_rows(src, idx, dst, B, n_src, n_dst, row_elems * es, (hipStream_t)stream);
 }
@@ -197,6 +214,7 @@ int rajni_gather_rows(const void* src, const int32_t* idx, void* dst, int B, int
 int rajni_attention(const void* qkv, const int32_t* keep_idx, void* out, int B, int n_src, int np,
                     int H, int D, float scale, int dtype, rajni_stream_t stream) {
   NEED_DTYPE("rajni_attention");
+  RAJNI_REQUIRE_PLACED("rajni_attention", {"qkv", qkv, 16}, {"keep_idx", keep_idx, 4}, {"out", out, 16});
   return launch_attention(qkv, keep_idx, out, B, n_src, np, np, H, D, scale, dtype, (hipStream_t)stream);
 }
 
@@ -204,23 +222,28 @@ int rajni_attention(const void* qkv, const int32_t* keep_idx, void* out, int B, 
 extern "C" int rajni_debug_attention_rows(const void* qkv, const int32_t* keep_idx, void* out, int B, int n_src, int np, int nq,
                                           int H, int D, float scale, int dtype, rajni_stream_t stream) {
   NEED_DTYPE("rajni_debug_attention_rows");
+  RAJNI_REQUIRE_PLACED("rajni_attention", {"qkv", qkv, 16}, {"keep_idx", keep_idx, 4}, {"out", out, 16});
   return launch_attention(qkv, keep_idx, out, B, n_src, np, nq, H, D, scale, dtype, (hipStream_t)stream);
 }
 
 extern "C" int rajni_attention_fp8(const void* qkv, const int32_t* keep_idx, void* out_q, float out_scale, float* row_scale,
                                    int B, int n_src, int np, int H, int D, float scale, rajni_stream_t stream) {
+  RAJNI_REQUIRE_PLACED("rajni_attention_fp8", {"qkv", qkv, 16}, {"keep_idx", keep_idx, 4}, {"out_q", out_q, 16}, {"row_scale", row_scale, 4});
   return launch_attention_fp8(qkv, keep_idx, out_q, out_scale, row_scale, B, n_src, np, H, D, scale, (hipStream_t)stream);
 }
 
 int rajni_layernorm(const void* x, long x_row_stride, const float* w, const float* b, void* y,
                     int rows, int C, float eps, int dtype, int x_f32, rajni_stream_t stream) {
   NEED_DTYPE("rajni_layernorm");
+  RAJNI_REQUIRE_PLACED("rajni_layernorm", {"x", x, 16}, {"w", w, 16}, {"b", b, 16}, {"y", y, 16});
   return launch_layernorm(x, x_row_stride, w, b, y, rows, C, eps, x_f32, dtype, (hipStream_t)stream);
 }
 
 int rajni_layernorm_fp8(const void* x, long x_row_stride, const float* w, const float* b, void* y_q,
                         float* y_scale, float* hid_scale, float w1_rownorm_max, float b1_absmax,
                         int rows, int C, float eps, int x_f32, rajni_stream_t stream) {
+  RAJNI_REQUIRE_PLACED("rajni_layernorm_fp8", {"x", x, 16}, {"w", w, 16}, {"b", b, 16}, {"y_q", y_q, 16}, {"y_scale", y_scale, 4},
+                       {"hid_scale", hid_scale, 4});
   return launch_layernorm_fp8(x, x_row_stride, w, b, y_q, y_scale, hid_scale, w1_rownorm_max, b1_absmax, rows, C, eps,
                               x_f32, (hipStream_t)stream);
 }
@@ -228,12 +251,14 @@ int rajni_layernorm_fp8(const void* x, long x_row_stride, const float* w, const 
 int rajni_qk_norm(void* qkv, const float* q_w, const float* q_b, const float* k_w, const float* k_b, int rows, int H,
                   int D, float eps, int dtype, rajni_stream_t stream) {
   NEED_DTYPE("rajni_qk_norm");
+  RAJNI_REQUIRE_PLACED("rajni_qk_norm", {"qkv", qkv, 16}, {"q_w", q_w, 16}, {"q_b", q_b, 16}, {"k_w", k_w, 16}, {"k_b", k_b, 16});
   return launch_qk_norm(qkv, q_w, q_b, k_w, k_b, rows, H, D, eps, dtype, (hipStream_t)stream);
 }
 
 int rajni_layernorm_stream(void* x, const float* w, const float* b, int rows, int C, float eps, int dtype, int x_f32,
                            rajni_stream_t stream) {
   NEED_DTYPE("rajni_layernorm_stream");
+  RAJNI_REQUIRE_PLACED("rajni_layernorm_stream", {"x", x, 16}, {"w", w, 16}, {"b", b, 16});
   return launch_layernorm_stream(x, w, b, rows, C, eps, x_f32, dtype, (hipStream_t)stream);
 }
 
@@ -241,6 +266,8 @@ int rajni_pool_norm(const void* x, int B, int N, int C, int pool, const float* n
                     float norm_eps, const float* fc_w, const float* fc_b, float fc_eps, void* out, int dtype, int x_f32,
                     rajni_stream_t stream) {
   NEED_DTYPE("rajni_pool_norm");
+  RAJNI_REQUIRE_PLACED("rajni_pool_norm", {"x", x, 16}, {"norm_w", norm_w, 16}, {"norm_b", norm_b, 16}, {"fc_w", fc_w, 16},
+                       {"fc_b", fc_b, 16}, {"out", out, 16});
   return launch_pool_norm(x, B, N, C, pool, norm_w, norm_b, norm_eps, fc_w, fc_b, fc_eps, out, x_f32, dtype, (hipStream_t)stream);
 }
 
@@ -248,6 +275,8 @@ int rajni_pool_norm_prefix(const void* x, int B, int N, int num_prefix, int C, i
                            const float* norm_b, float norm_eps, const float* fc_w, const float* fc_b, float fc_eps,
                            void* out, int dtype, int x_f32, rajni_stream_t stream) {
   NEED_DTYPE("rajni_pool_norm_prefix");
+  RAJNI_REQUIRE_PLACED("rajni_pool_norm_prefix", {"x", x, 16}, {"norm_w", norm_w, 16}, {"norm_b", norm_b, 16}, {"fc_w", fc_w, 16},
+                       {"fc_b", fc_b, 16}, {"out", out, 16});
   RAJNI_REQUIRE(x && out, RAJNI_ERR_INVALID, "rajni_pool_norm_prefix: null pointer");
   RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
                 "rajni_pool_norm_prefix: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
@@ -266,6 +295,8 @@ int rajni_patch_embed(const void* images, const void* w, const float* bias, cons
                       const void* pos, int pos_has_cls, void* x, int x_f32, int B, int Cin, int S,
                       int P, int C, int dtype, void* workspace, size_t workspace_bytes, rajni_stream_t stream) {
   NEED_DTYPE("rajni_patch_embed");
+  RAJNI_REQUIRE_PLACED("rajni_patch_embed", {"images", images, 16}, {"w", w, 16}, {"bias", bias, 16}, {"cls", cls, 16}, {"pos", pos, 16},
+                       {"x", x, 16}, {"workspace", workspace, 16});
   return launch_patch_embed(images, w, bias, cls, pos, pos_has_cls, x, x_f32, B, Cin, S, P, C, dtype,
                             workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -273,13 +304,13 @@ int rajni_patch_embed_prefix(const void* images, const void* w, const float* bia
                              int num_prefix, const void* pos, int pos_has_cls, void* x, int x_f32, int B, int Cin, int S,
                              int P, int C, int dtype, void* workspace, size_t workspace_bytes, rajni_stream_t stream) {
   NEED_DTYPE("rajni_patch_embed_prefix");
+  RAJNI_REQUIRE_PLACED("rajni_patch_embed_prefix", {"images", images, 16}, {"w", w, 16}, {"bias", bias, 16}, {"cls", cls, 16},
+                       {"reg", reg, 16}, {"pos", pos, 16}, {"x", x, 16}, {"workspace", workspace, 16});
   RAJNI_REQUIRE(images && w && cls && pos && x, RAJNI_ERR_INVALID, "rajni_patch_embed_prefix: null pointer");
   RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
                 "rajni_patch_embed_prefix: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
   RAJNI_REQUIRE(num_prefix == 1 || reg != nullptr, RAJNI_ERR_INVALID,
                 "rajni_patch_embed_prefix: %d prefix tokens but reg is null", num_prefix);
-  RAJNI_REQUIRE(num_prefix == 1 || ((uintptr_t)cls % 16 == 0 && (uintptr_t)reg % 16 == 0 && (uintptr_t)pos % 16 == 0),
-                RAJNI_ERR_INVALID, "rajni_patch_embed_prefix: cls, reg and pos must be 16-byte aligned");
   return launch_patch_embed(images, w, bias, cls, pos, pos_has_cls, x, x_f32, B, Cin, S, P, C, dtype,
                             workspace, workspace_bytes, (hipStream_t)stream, num_prefix, num_prefix > 1 ? reg : nullptr);
 }

@@ -189,6 +189,19 @@ struct ProfScope {
     }                                        \
   } while (0)
 
+// The placement contract of include/rajni_hip.h ("placement"): each pointer of an entry point with the minimum alignment the
+// kernels behind it need.  The first pointer below its minimum is refused by name (RAJNI_ERR_INVALID); a null pointer passes
+// (the null checks name it).  Host-side integer tests only: every entry point runs them before its first HIP call.
+struct PlacedPtr { const char* name; const void* p; int align; };
+int rajni_check_placement(const char* who, const PlacedPtr* ptrs, int n);
+#define RAJNI_REQUIRE_PLACED(who, ...)                                                        \
+  do {                                                                                        \
+    const PlacedPtr placed__[] = {__VA_ARGS__};                                               \
+    const int rc__ = rajni_check_placement(who, placed__, (int)(sizeof(placed__) / sizeof(placed__[0]))); \
+    if (rc__ != RAJNI_OK) return rc__;                                                        \
+  } while (0)
+inline int rajni_elem_bytes(int dtype) { return dtype == RAJNI_F32 ? 4 : 2; }   // score arrays: element alignment
+
 // diagnostic builds only (-DRAJNI_GEMM_STAMPS / -DRAJNI_ATTN_STAMPS): device buffer for s_memtime stamps
 extern unsigned long long* rajni_g_stamps;
 

@@ -1,7 +1,7 @@
 // Whole-forward orchestration: RAJNIViTWrapper.forward (reference model.py:30-69) as one host call
 // that enqueues every kernel on the caller's stream.  Token counts are data independent,
 // so all shapes are known up front: no allocation, no host sync, no device->host traffic inside, and
-// every refusal that depends on the plan alone (check_plan, check_ext, check_schedule) comes before the first launch.
+// every refusal that depends on the plan alone (check_plan, check_placement, check_ext, check_schedule) comes before the first launch.
 //
 // Per block:  LN1 -> QKV GEMM (all N tokens) -> an attention form -> the tail (launch_tail):
 // proj GEMM whose epilogue gathers the residual row, applies LayerScale and adds -> LN2 -> FC1 GEMM + GELU ->
@@ -60,6 +60,27 @@ __global__ void carry_scores_kernel(const T* scores, const int* idx, T* out, int
   out[i] = scores[(long)b * N + idx[i]];
 }
 
+// the placement contract (include/rajni_hip.h) for everything a plan points to, with images and logits
+int check_placement(const rajni_vit_plan& p, const void* images, const void* logits) {
+  const char* who = "rajni_vit_forward";
+  const int eb = rajni_elem_bytes(p.dtype);
+  RAJNI_REQUIRE_PLACED(who, {"images", images, 16}, {"logits", logits, 16}, {"patch_w", p.patch_w, 16}, {"patch_b", p.patch_b, 16},
+                       {"cls_token", p.cls_token, 16}, {"pos_embed", p.pos_embed, 16}, {"norm_w", p.norm_w, 16}, {"norm_b", p.norm_b, 16},
+                       {"head_w", p.head_w, 16}, {"head_b", p.head_b, 16}, {"workspace", p.workspace, 256});
+  for (int i = 0; i < p.depth; ++i) {
+    const rajni_block& k = p.blocks[i];
+    char blk[48];
+    snprintf(blk, sizeof(blk), "%s: block %d", who, i);
+    RAJNI_REQUIRE_PLACED(blk, {"norm1_w", k.norm1_w, 16}, {"norm1_b", k.norm1_b, 16}, {"qkv_w", k.qkv_w, 16}, {"qkv_b", k.qkv_b, 16},
+                         {"proj_w", k.proj_w, 16}, {"proj_b", k.proj_b, 16}, {"ls1", k.ls1, 16}, {"norm2_w", k.norm2_w, 16},
+                         {"norm2_b", k.norm2_b, 16}, {"fc1_w", k.fc1_w, 16}, {"fc1_b", k.fc1_b, 16}, {"fc2_w", k.fc2_w, 16},
+                         {"fc2_b", k.fc2_b, 16}, {"ls2", k.ls2, 16}, {"keep_idx", k.keep_idx, 4}, {"scores", k.scores, eb},
+                         {"next_scores", k.next_scores, eb}, {"forced_keep_idx", k.forced_keep_idx, 4}, {"qkv_s", k.qkv_s, 16},
+                         {"proj_s", k.proj_s, 16}, {"fc1_s", k.fc1_s, 16}, {"fc2_s", k.fc2_s, 16});
+  }
+  return RAJNI_OK;
+}
+
 int check_plan(const rajni_vit_plan& p, bool norm_absent) {
   RAJNI_REQUIRE(p.dtype == RAJNI_BF16 || p.dtype == RAJNI_F32 || p.dtype == RAJNI_F16, RAJNI_ERR_INVALID,
                 "rajni_vit_forward: bad dtype %d", p.dtype);
@@ -101,6 +122,15 @@ int check_ext(const rajni_vit_plan& p, const rajni_vit_ext& e) {
     for (int i = 0; i < p.depth; ++i)
       RAJNI_REQUIRE(e.qk_norm[i].q_norm_w && e.qk_norm[i].k_norm_w, RAJNI_ERR_INVALID,
                     "rajni_vit_forward_ext: q/k-norm weights missing (block %d)", i);
+  if (e.qk_norm)
+    for (int i = 0; i < p.depth; ++i) {
+      char blk[56];
+      snprintf(blk, sizeof(blk), "rajni_vit_forward_ext: block %d", i);
+      RAJNI_REQUIRE_PLACED(blk, {"q_norm_w", e.qk_norm[i].q_norm_w, 16}, {"q_norm_b", e.qk_norm[i].q_norm_b, 16},
+                           {"k_norm_w", e.qk_norm[i].k_norm_w, 16}, {"k_norm_b", e.qk_norm[i].k_norm_b, 16});
+    }
+  RAJNI_REQUIRE_PLACED("rajni_vit_forward_ext", {"norm_pre_w", e.norm_pre_w, 16}, {"norm_pre_b", e.norm_pre_b, 16},
+                       {"fc_norm_w", e.fc_norm_w, 16}, {"fc_norm_b", e.fc_norm_b, 16});
   return RAJNI_OK;
 }
 
@@ -296,6 +326,9 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
   const rajni_vit_plan& p = *plan;
   int rc = check_plan(p, ext != nullptr && ext->norm_absent != 0);
   if (rc != RAJNI_OK) return rc;
+  rc = check_placement(p, images, logits);
+  if (rc != RAJNI_OK) return rc;
+  if (pre) RAJNI_REQUIRE_PLACED("rajni_vit_forward", {"reg_token", pre->reg_token, 16});
   if (ext) {
     rc = check_ext(p, *ext);
     if (rc != RAJNI_OK) return rc;

@@ -1579,8 +1579,15 @@ int linear(const rajni_linear_args& a, LaunchCtl l) {
                 "rajni_linear: M,N>0 and K %% 64 == 0 required (M=%d N=%d K=%d)", a.M, a.N, a.K);
   RAJNI_REQUIRE(a.lda % 8 == 0 && a.ldw % 8 == 0 && a.ldc % 8 == 0, RAJNI_ERR_INVALID,
                 "rajni_linear: leading dimensions must be multiples of 8 elements");
-  RAJNI_REQUIRE(((uintptr_t)a.x | (uintptr_t)a.w | (uintptr_t)a.y | (uintptr_t)a.resid) % 16 == 0,
-                RAJNI_ERR_INVALID, "rajni_linear: pointers must be 16-byte aligned");
+  {
+    const PlacedPtr data[] = {{"x", a.x, 16}, {"w", a.w, 16}, {"y", a.y, 16}, {"resid", a.resid, 16}};
+    for (const PlacedPtr& d : data)
+      RAJNI_REQUIRE((uintptr_t)d.p % 16 == 0, RAJNI_ERR_INVALID, "rajni_linear: pointers must be 16-byte aligned (%s)", d.name);
+  }
+  // the stream tilings read bias, gamma and w_scale 16 bytes at a time (gemm_tail, gemm_f8.h); the row scales and r_idx are
+  // read one element at a time
+  RAJNI_REQUIRE_PLACED("rajni_linear", {"bias", a.bias, 16}, {"gamma", a.gamma, 16}, {"w_scale", a.w_scale, 16}, {"x_scale", a.x_scale, 4},
+                       {"y_scale", a.y_scale, 4}, {"r_idx", a.r_idx, 4});
   GemmParams p{};
   p.X = a.x; p.lda = a.lda;
   p.W = a.w; p.ldw = a.ldw;
@@ -1619,7 +1626,9 @@ int linear(const rajni_linear_args& a, LaunchCtl l) {
       epi = f8 ? EPI_GELU8 : EPI_GELU; l.kclass = f8 ? KC_GEMM8_GELU : KC_GEMM_GELU;
       break;
     case RAJNI_EPI_BIAS_RESID:
-      // as found, not known to be intended: fp32 does not ask for ldr % 8; only fp8 x fp8 can meet a y_scale here and names it
+      // fp32 asks for no ldr rule: its epilogue (epilogue_row_f32) reads the residual row one element at a time, so any
+      // stride serves; the 16-bit and fp8 x fp8 epilogues read it 16 bytes at a time.  Only fp8 x fp8 can meet a y_scale
+      // here and names it
       if (f8) RAJNI_REQUIRE(a.resid != nullptr && a.ldr % 8 == 0 && a.y_scale == nullptr, RAJNI_ERR_INVALID,
                             "rajni_linear: RESID epilogue needs resid, ldr %% 8 == 0 and no y_scale");
       else if (fmt == FMT_F32) RAJNI_REQUIRE(a.resid != nullptr, RAJNI_ERR_INVALID, "rajni_linear: RESID epilogue needs resid");

@@ -82,6 +82,27 @@ def pack_vec(v: Optional[torch.Tensor], like_dtype=torch.bfloat16, device=None) 
     return v.detach().to(like_dtype).to(torch.float32).to(device if device is not None else v.device).contiguous()
 
 
+def _placed(t: Optional[torch.Tensor], name: str, align: int = 16, in_place: bool = False) -> Optional[torch.Tensor]:
+    """The placement contract of include/rajni_hip.h for one operand: `t` made contiguous with its data pointer a multiple
+    of `align` bytes (16: data tensors and fp32 per-column vectors; 4: row scales and index arrays).  A contiguous view
+    keeps its storage offset (`buf[1:].view(rows, C)`), so a read-only input below the contract is cloned into a fresh
+    allocation; an operand the kernel writes (`in_place`: qk_norm, layernorm_stream, a caller's `out`) cannot be moved
+    and raises ValueError.  An operand that meets the contract is returned as it is (the same object)."""
+    if t is None:
+        return None
+    if in_place:
+        if not t.is_contiguous():
+            raise ValueError(f"{name} is written in place: it must be contiguous")
+        if t.data_ptr() % align:
+            raise ValueError(f"{name} must be {align}-byte aligned (it is written in place and cannot be copied)")
+        return t
+    t = t.contiguous()
+    if t.data_ptr() % align:
+        t = t.clone(memory_format=torch.contiguous_format)
+        assert t.data_ptr() % align == 0, f"{name}: a fresh allocation is not {align}-byte aligned"
+    return t
+
+
 def _score_scratch(qkv: torch.Tensor, B: int, N: int, H: int, D: int) -> Optional[torch.Tensor]:
     """scratch of the tiled score kernels (rajni_score_select_ws), None for every shape one workgroup's LDS holds"""
     nbytes = nat.lib().rajni_score_select_workspace_bytes(B, N, H, D, _dt(qkv))
@@ -90,7 +111,7 @@ def _score_scratch(qkv: torch.Tensor, B: int, N: int, H: int, D: int) -> Optiona
 
 def importance(qkv: torch.Tensor, num_heads: int, eps: float = 1e-6) -> torch.Tensor:
     nat.require_device(qkv, "qkv")
-    qkv = qkv.contiguous()
+    qkv = _placed(qkv, "qkv")
     B, N, threeC = qkv.shape
     D = threeC // 3 // num_heads
     out = torch.empty((B, N), dtype=qkv.dtype, device=qkv.device)
@@ -110,7 +131,7 @@ def select_topk(scores: torch.Tensor, keep: int, num_prefix: int = 1) -> Tuple[t
     """scores [B, N] -> (keep_idx int32 [B, P+keep], next_scores [B, P+keep]); the first P = `num_prefix` tokens are always
     kept (slots 0..P-1) and take no rank slot."""
     nat.require_device(scores, "scores")
-    scores = scores.contiguous()
+    scores = _placed(scores, "scores", scores.element_size())
     B, N = scores.shape
     P = int(num_prefix)
     idx = torch.empty((B, keep + P), dtype=torch.int32, device=scores.device)
@@ -130,7 +151,7 @@ def score_select(qkv: torch.Tensor, num_heads: int, keep: int, eps: float = 1e-6
     """qkv [B, N, 3C] -> (scores [B, N] or None, keep_idx int32 [B, P+keep], next_scores [B, P+keep]), P = `num_prefix`
     as in select_topk (the scores themselves do not depend on P)."""
     nat.require_device(qkv, "qkv")
-    qkv = qkv.contiguous()
+    qkv = _placed(qkv, "qkv")
     B, N, threeC = qkv.shape
     D = threeC // 3 // num_heads
     P = int(num_prefix)
@@ -157,8 +178,8 @@ def score_select(qkv: torch.Tensor, num_heads: int, keep: int, eps: float = 1e-6
 def gather_rows(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """src [B, N, E], idx [B, K] int32 -> [B, K, E]"""
     nat.require_device(src, "src")
-    src = src.contiguous()
-    idx = idx.to(torch.int32).contiguous()
+    src = _placed(src, "src")
+    idx = _placed(idx.to(torch.int32), "idx", 4)
     B, N, E = src.shape
     K = idx.shape[1]
     out = torch.empty((B, K, E), dtype=src.dtype, device=src.device)
@@ -171,12 +192,12 @@ def gather_rows(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
 def attention(qkv: torch.Tensor, keep_idx: Optional[torch.Tensor], num_heads: int, scale: float) -> torch.Tensor:
     """qkv [B, N, 3C]; keep_idx [B, Np] int32 or None -> [B, Np, C]"""
     nat.require_device(qkv, "qkv")
-    qkv = qkv.contiguous()
+    qkv = _placed(qkv, "qkv")
     B, N, threeC = qkv.shape
     Cc = threeC // 3
     D = Cc // num_heads
     if keep_idx is not None:
-        keep_idx = keep_idx.to(torch.int32).contiguous()
+        keep_idx = _placed(keep_idx.to(torch.int32), "keep_idx", 4)
         Np = keep_idx.shape[1]
     else:
         Np = N
@@ -204,12 +225,12 @@ def attention_fp8(qkv: torch.Tensor, keep_idx: Optional[torch.Tensor], num_heads
     """attention with e4m3 output rows (opt-in fp8_mfma format): qkv bf16 [B, N, 3C], head dim 64, at most 224 kept tokens
     -> (bytes uint8 [B, Np, C] = e4m3_rne_sat(attn / out_scale), row scales fp32 [B * Np] = out_scale)"""
     nat.require_device(qkv, "qkv")
-    qkv = qkv.contiguous()
+    qkv = _placed(qkv, "qkv")
     B, N, threeC = qkv.shape
     Cc = threeC // 3
     D = Cc // num_heads
     if keep_idx is not None:
-        keep_idx = keep_idx.to(torch.int32).contiguous()
+        keep_idx = _placed(keep_idx.to(torch.int32), "keep_idx", 4)
         Np = keep_idx.shape[1]
     else:
         Np = N
@@ -227,7 +248,7 @@ def layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float, row
     """LayerNorm over the last axis; w, b fp32.  x may be `out_dtype` or fp32 (the fp32 residual
     stream); the result is `out_dtype`.  With rows/row_stride reads a strided subset of rows."""
     nat.require_device(x, "x")
-    x = x.contiguous()
+    x, w, b = _placed(x, "x"), _placed(w, "w"), _placed(b, "b")
     x_f32 = int(x.dtype == torch.float32 and out_dtype != torch.float32)
     Cc = x.shape[-1]
     if rows is None:
@@ -249,7 +270,7 @@ def layernorm_fp8(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float,
     returns (q uint8 [..., C] of e4m3 bytes, scale fp32 [rows]) and, with `hidden_bound = (max row norm of the
     dequantised fc1 weight, max |fc1 bias|)`, also the per-row scale of the MLP hidden activations."""
     nat.require_device(x, "x")
-    x = x.contiguous()
+    x, w, b = _placed(x, "x"), _placed(w, "w"), _placed(b, "b")
     if x.dtype not in (torch.float32, torch.bfloat16):
         raise NotImplementedError("layernorm_fp8: x must be fp32 (the residual stream) or bf16")
     Cc = x.shape[-1]
@@ -272,12 +293,14 @@ def qk_norm(qkv: torch.Tensor, num_heads: int, q_w: torch.Tensor, q_b: Optional[
     nat.require_device(qkv, "qkv")
     if not qkv.is_contiguous():
         raise ValueError("qk_norm works in place: qkv must be contiguous")
+    qkv = _placed(qkv, "qkv", in_place=True)
     threeC = qkv.shape[-1]
     rows = qkv.numel() // threeC
     D = threeC // 3 // num_heads
     for v in (q_w, q_b, k_w, k_b):
         if v is not None and (v.dtype != torch.float32 or v.numel() != D or not v.is_contiguous()):
             raise ValueError(f"qk_norm: weights and biases must be contiguous fp32 [{D}]")
+    q_w, q_b, k_w, k_b = _placed(q_w, "q_w"), _placed(q_b, "q_b"), _placed(k_w, "k_w"), _placed(k_b, "k_b")
     with nat.device_guard(qkv.device):
         nat.check(nat.lib().rajni_qk_norm(qkv.data_ptr(), q_w.data_ptr(), nat.ptr(q_b), k_w.data_ptr(), nat.ptr(k_b), rows,
                                           num_heads, D, float(eps), _dt(qkv), nat.stream_ptr(qkv.device)), "rajni_qk_norm")
@@ -291,6 +314,7 @@ def layernorm_stream(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]
     nat.require_device(x, "x")
     if not x.is_contiguous():
         raise ValueError("layernorm_stream works in place: x must be contiguous")
+    x, w, b = _placed(x, "x", in_place=True), _placed(w, "w"), _placed(b, "b")
     Cc = x.shape[-1]
     dt = nat.dtype_code(model_dtype if model_dtype is not None else x.dtype)
     x_f32 = int(x.dtype == torch.float32 and dt != nat.RAJNI_F32)
@@ -309,11 +333,12 @@ def pool_norm(x: torch.Tensor, pool: str = "token", norm=None, fc_norm=None, out
     nat.require_device(x, "x")
     if pool not in ("token", "avg"):
         raise NotImplementedError(f"pool_norm: pool '{pool}' is not supported ('token' or 'avg')")
-    x = x.contiguous()
+    x = _placed(x, "x")
     B, N, Cc = x.shape
     x_f32 = int(x.dtype == torch.float32 and out_dtype != torch.float32)
     nw, nb, ne = norm if norm is not None else (None, None, 0.0)
     fw, fb, fe = fc_norm if fc_norm is not None else (None, None, 0.0)
+    nw, nb, fw, fb = _placed(nw, "norm_w"), _placed(nb, "norm_b"), _placed(fw, "fc_w"), _placed(fb, "fc_b")
     out = torch.empty((B, Cc), dtype=out_dtype, device=x.device)
     pk = nat.POOL_AVG if pool == "avg" else nat.POOL_TOKEN
     with nat.device_guard(x.device):
@@ -342,7 +367,9 @@ def linear(x: torch.Tensor, w_packed: torch.Tensor, n_out: int, bias: Optional[t
     With `x_scale` (fp32 [M]) x is the uint8 e4m3 tensor of layernorm_fp8() and the product runs on the fp8 matrix
     pipe (w_scale required); with EPI_BIAS_GELU `y_scale` (fp32 [M]) is required and the result is uint8 e4m3."""
     nat.require_device(x, "x")
-    x = x.contiguous()
+    x, w_packed = _placed(x, "x"), _placed(w_packed, "w")
+    bias, gamma, w_scale = _placed(bias, "bias"), _placed(gamma, "gamma"), _placed(w_scale, "w_scale")
+    x_scale, y_scale = _placed(x_scale, "x_scale", 4), _placed(y_scale, "y_scale", 4)
     K = x.shape[-1]
     M = x.numel() // K
     f8 = x_scale is not None
@@ -352,7 +379,10 @@ def linear(x: torch.Tensor, w_packed: torch.Tensor, n_out: int, bias: Optional[t
     out8 = f8 and epilogue == nat.EPI_BIAS_GELU
     ld = (n_out + 15) // 16 * 16 if out8 else (n_out + 7) // 8 * 8
     stream_f32 = int(resid is not None and resid.dtype == torch.float32 and act_dtype != torch.float32)
-    if out is None:
+    if out is not None:
+        if out.data_ptr() % 16:
+            raise ValueError("y must be 16-byte aligned (a caller's `out` is written in place and cannot be copied)")
+    else:
         out = torch.empty((M, ld), dtype=torch.uint8 if out8 else (torch.float32 if stream_f32 else act_dtype), device=x.device)
     a = nat.LinearArgs()
     a.x, a.lda, a.w, a.ldw = x.data_ptr(), K, w_packed.data_ptr(), w_packed.shape[1]
@@ -363,10 +393,10 @@ def linear(x: torch.Tensor, w_packed: torch.Tensor, n_out: int, bias: Optional[t
     a.M, a.N, a.K, a.epilogue, a.dtype, a.stream_f32 = M, n_out, K, epilogue, nat.dtype_code(act_dtype), stream_f32
     a.x_scale, a.y_scale = nat.ptr(x_scale), nat.ptr(y_scale)
     if resid is not None:
-        resid = resid.contiguous()
+        resid = _placed(resid, "resid")
         a.resid, a.ldr = resid.data_ptr(), resid.shape[-1]
         if r_idx is not None:
-            r_idx = r_idx.to(torch.int32).contiguous()
+            r_idx = _placed(r_idx.to(torch.int32), "r_idx", 4)
             a.r_idx, a.r_np, a.r_nsrc = r_idx.data_ptr(), r_idx.shape[1], resid.shape[1]
     with nat.device_guard(x.device):
         nat.check(nat.lib().rajni_linear(C.byref(a), nat.stream_ptr(x.device)), "rajni_linear")
@@ -380,12 +410,13 @@ def patch_embed(images: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor
     """images [B, Cin, S, S] -> x [B, P + (S/patch)^2, C]: CLS, the R = P - 1 register tokens `reg` ([R, C] in the images'
     dtype, None = no registers), then the patches; `pos` has (P if pos_has_cls else 0) + (S/patch)^2 rows."""
     nat.require_device(images, "images")
-    images = images.contiguous()
+    images, w_packed, bias = _placed(images, "images"), _placed(w_packed, "w"), _placed(bias, "bias")
+    cls, pos = _placed(cls, "cls"), _placed(pos, "pos")
     B, Cin, S, _ = images.shape
     if reg is not None:
         if reg.dim() != 2 or reg.shape[1] != embed_dim or reg.shape[0] < 1 or reg.dtype != images.dtype:
             raise ValueError(f"patch_embed: reg must be [R, {embed_dim}] in the images' dtype, got {tuple(reg.shape)} {reg.dtype}")
-        reg = reg.contiguous()
+        reg = _placed(reg, "reg")
     P = 1 + (reg.shape[0] if reg is not None else 0)
     n = (S // patch) ** 2 + P
     x = torch.empty((B, n, embed_dim), dtype=torch.float32 if out_f32 else images.dtype, device=images.device)

@@ -39,10 +39,14 @@ class Guarded:
     """`shape` [..., cols] of `dtype` inside a poisoned arena on `device`.  Rows (every leading index, flattened) are
     `row_stride` elements apart (default: cols).  `fill_int32` replaces the 0xFF pattern by an int32 value (index
     arrays).  `after_rows` widens the guard after the view to that many rows (an input whose over-reads may reach
-    further than one row tile, like gathered residual rows).  `misalign` shifts the view off its 256-byte boundary: only the self-test uses it, to see it refused."""
+    further than one row tile, like gathered residual rows).  `misalign` starts the view that many bytes past a 256-byte
+    boundary and `align` is what the view's pointer must then be a multiple of: the default 256 refuses every `misalign`
+    (the self-test sees that), the placement tests ask for `align=16, misalign=16` and the like."""
 
     def __init__(self, shape: Sequence[int], dtype: torch.dtype, device="cpu", row_stride: Optional[int] = None,
-                 fill_int32: Optional[int] = None, after_rows: int = ROW_TILE, misalign: int = 0):
+                 fill_int32: Optional[int] = None, after_rows: int = ROW_TILE, misalign: int = 0, align: int = ALIGN):
+        self.align = int(align)
+        assert self.align > 0 and ALIGN % self.align == 0, f"align must divide {ALIGN} ({align})"
         self.shape = tuple(int(s) for s in shape)
         self.dtype = dtype
         self.esize = element_size(dtype)
@@ -72,7 +76,7 @@ class Guarded:
             raise ValueError("misalign must be a multiple of the element size")
         flat = self.arena[self.offset:self.offset + max(self.region, self.esize)]
         self.t = flat.view(dtype).as_strided(self.shape, strides)
-        assert_aligned(self.t, what=f"guarded {dtype} {self.shape}")
+        assert_aligned(self.t, self.align, what=f"guarded {dtype} {self.shape}")
 
     # ---- pointers ------------------------------------------------------------------------------
     def ptr(self) -> int:
@@ -127,9 +131,9 @@ class Guarded:
         return int((v.view(self.rows, self.cols, self.esize) == POISON).all(dim=-1).sum())
 
     def check(self, what: str = "", written: bool = True, gaps: bool = True) -> None:
-        """Assert the view is 256-byte aligned, both guards are intact, the row gaps are untouched (`gaps`) and every
+        """Assert the view is aligned as asked (256 bytes by default), both guards are intact, the row gaps are untouched (`gaps`) and every
         element was written (`written`: outputs)."""
-        assert_aligned(self.t, what=what)
+        assert_aligned(self.t, self.align, what=what)
         d = self.guard_damage()
         assert d is None, f"{what}: {d}"
         if gaps:

@@ -75,6 +75,31 @@ def test_misaligned_view_is_refused():
         g.check("shifted")
 
 
+def test_view_at_a_chosen_placement_is_accepted_and_still_guarded():
+    g = Guarded((4, 8), torch.float32, row_stride=16, align=16, misalign=16)
+    assert g.ptr() % ALIGN == 16 and g.ptr() % 16 == 0
+    g.t.zero_()
+    g.check("placed")
+    for before in (True, False):                      # one byte before the view, one byte after it
+        h = Guarded((4, 8), torch.float32, row_stride=16, align=16, misalign=16)
+        h.t.zero_()
+        h.arena[h.offset - 1 if before else h.end] = 0x00
+        with pytest.raises(AssertionError, match="guard (BEFORE|AFTER)"):
+            h.check("placed")
+    g.arena[g.offset + (2 * 16 + 9) * 4] = 0x12
+    with pytest.raises(AssertionError, match="row gap"):
+        g.check("placed gap")
+    i = Guarded((3, 5), torch.int32, fill_int32=7, align=4, misalign=4)
+    assert i.ptr() % ALIGN == 4 and (i.arena.view(torch.int32) == 7).all()
+    i.t.copy_(torch.arange(15, dtype=torch.int32).view(3, 5))
+    i.check("index", written=False)
+
+
+def test_placement_below_the_asked_alignment_is_refused():
+    with pytest.raises(AssertionError, match="8 bytes past a 16-byte boundary"):
+        Guarded((4, 8), torch.float32, align=16, misalign=8)
+
+
 def test_index_arena_holds_a_valid_index():
     g = Guarded((3, 5), torch.int32, fill_int32=7)
     assert (g.arena.view(torch.int32) == 7).all()
