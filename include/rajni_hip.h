@@ -44,9 +44,14 @@ enum {
 enum {
   RAJNI_EPI_BIAS = 0,      /* y = x W^T + b                                  attention.py:22 (qkv) */
   RAJNI_EPI_BIAS_GELU = 1, /* y = gelu_erf(x W^T + b)                        model.py:59 (mlp.fc1+act) */
-  RAJNI_EPI_BIAS_RESID = 2 /* y = resid[row or gathered row] + gamma*(x W^T + b)
+  RAJNI_EPI_BIAS_RESID = 2,/* y = resid[row or gathered row] + gamma*(x W^T + b)
                               attention.py:55 + model.py:55-58 (proj, gather x, ls1, add);
                               model.py:59 (mlp.fc2, ls2, add)                                       */
+  RAJNI_EPI_BIAS_QUICK_GELU = 16 /* y = quick_gelu(x W^T + b), quick_gelu(v) = v * sigmoid(1.702 v): the MLP activation of the
+                              OpenAI CLIP, MetaCLIP and DFN towers.  BIAS_GELU in every other respect (output type, tilings,
+                              profile class); bf16, fp16, fp32 and fp8 WEIGHTS.  With x_scale (fp8 x fp8) it is
+                              RAJNI_ERR_UNSUPPORTED: the re-quantising e4m3 epilogue exists for exact GELU only.
+                              Codes 3..15 and >= 17 are unknown.                                       */
 };
 
 /* ---- addressing limits ----
@@ -321,6 +326,7 @@ int rajni_layernorm_stream(void* x, const float* w, const float* b, int rows, in
  * tokens that SURVIVED pruning (what timm computes on whatever token set reaches the head), summed in a fixed order
  * in fp32.  norm_w == NULL / fc_w == NULL: that norm is nn.Identity.  C % 8 == 0, C <= 2048. */
 enum { RAJNI_POOL_TOKEN = 0, RAJNI_POOL_AVG = 1 };
+enum { RAJNI_MLP_GELU = 0, RAJNI_MLP_QUICK_GELU = 1 };   /* rajni_vit_ext.mlp_act */
 int rajni_pool_norm(const void* x, int B, int N, int C, int pool, const float* norm_w, const float* norm_b,
                     float norm_eps, const float* fc_w, const float* fc_b, float fc_eps, void* out, int dtype, int x_f32,
                     rajni_stream_t stream);
@@ -340,6 +346,13 @@ typedef struct {
   int pool;                         /* RAJNI_POOL_TOKEN (0) or RAJNI_POOL_AVG; AVG with plan.cls_only_last_block is
                                        RAJNI_ERR_INVALID: that opt-in never forms the rows to be averaged */
   const float* fc_norm_w; const float* fc_norm_b; float fc_norm_eps;      /* fc_norm_w == NULL: no fc_norm */
+  int mlp_act;                      /* RAJNI_MLP_GELU (0) or RAJNI_MLP_QUICK_GELU: the activation of every block's FC1.  It sits in
+                                       what were the four bytes of tail padding behind fc_norm_eps (offset 68 of 72: the record
+                                       is 8-byte aligned), so no field moves and the size stays; a caller built against the
+                                       record without it passes zeroed or ignored padding - callers zero the record, "an
+                                       all-zero record is the plain forward" - and gets exact GELU as before.  Hence
+                                       RAJNI_ABI_VERSION does not move.  Any other value is RAJNI_ERR_INVALID; QUICK_GELU with
+                                       plan.act_fp8 is RAJNI_ERR_UNSUPPORTED (see RAJNI_EPI_BIAS_QUICK_GELU) */
 } rajni_vit_ext;
 
 /* rajni_vit_forward with the options of `ext` (NULL or all zero: exactly the launches of rajni_vit_forward).

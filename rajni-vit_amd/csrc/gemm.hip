@@ -31,7 +31,11 @@
 namespace {
 
 enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_PATCH = 3,
-       EPI_GELU8 = 4 };   // fp8 x fp8 kernel only (gemm_f8.h): bias + GELU, output re-quantised to e4m3 with a per-row scale
+       EPI_GELU8 = 4,     // fp8 x fp8 kernel only (gemm_f8.h): bias + GELU, output re-quantised to e4m3 with a per-row scale
+       EPI_QGELU = 5 };   // bias + QuickGELU: EPI_GELU in everything but the function applied (see epi_act)
+// The activation epilogues of the 16-bit and fp32 kernels: a 16-bit (or fp32) output in the bias epilogue's column order and
+// store path, FC1's non-temporal hidden store, the profile class KC_GEMM_GELU.  Whatever asks "is this FC1's epilogue" asks here.
+constexpr bool epi_act(int epi) { return epi == EPI_GELU || epi == EPI_QGELU; }
 enum { ALOAD_PLAIN = 0, ALOAD_PATCH = 1 };
 
 struct GemmParams {
@@ -101,6 +105,22 @@ __device__ __forceinline__ void gelu_pk4(f32x2& a, f32x2& b) {
   const f32x2 ya = al * ha + al * half, yb = bl * hb + bl * half;
   a = ya; b = yb;
 }
+
+// QuickGELU (the OpenAI CLIP / MetaCLIP / DFN towers): x * sigmoid(1.702 x) = x * rcp(1 + exp2(-1.702 log2(e) x)), in fp32
+// on the accumulators with the hardware v_exp_f32 / v_rcp_f32 (1 ulp each): |error| <= 7e-7 on [-8, 8] against fp64, far
+// inside a 16-bit output's rounding.  The ends need no clamp: for large x the exponential underflows to 0 and the factor is
+// rcp(1) = 1; for large -x it overflows to +inf (so does the argument product itself beyond |x| ~ 1.4e38), 1 + inf = inf,
+// rcp(inf) = +0 and x * 0 = -0 for every finite x - no inf - inf, 0 * inf or inf / inf can form, so a finite pre-activation
+// never yields NaN or inf.  act(0) = 0 * rcp(2) = 0 exactly: the zero-padded hidden columns of odd MLP widths stay zero.
+// This is the plain form, and it is the cheaper epilogue of the two: measured on ViT-B FC1 launches 158 us against 170 us with
+// gelu_pk4 (the FC1 class -6.9 %, DESIGN.md section 4 (13), profiles/quickgelu_ab.txt) - two transcendentals and three plain
+// fp32 operations per element cost less than the clamped degree-8 packed polynomial.
+__device__ __forceinline__ float quick_gelu1(float x) {
+  return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.4554669595930157f * x));
+}
+// (The two sites that apply an activation - epilogue_row and the interior path of epilogue_tile - keep the GELU loop spelled
+//  out as it always was, with the QuickGELU loop beside it: routed through one shared helper, hipcc allocated the GELU
+//  kernels' registers differently, and every kernel that existed before QuickGELU is held to identical machine code.)
 
 // load / store 16 consecutive stream elements (the 16-bit activation format A, or fp32) as floats
 template <bool F32, typename A>
@@ -177,6 +197,9 @@ __device__ __forceinline__ void epilogue_row(const GemmParams& p, int m, int nbA
       gelu_pk4(a, b);
       v[j] = a[0]; v[j + 1] = a[1]; v[j + 2] = b[0]; v[j + 3] = b[1];
     }
+  } else if (EPI == EPI_QGELU) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = quick_gelu1(v[j]);
   } else if (EPI == EPI_RESID) {
     long rrow = m;
     if (p.ridx != nullptr) {
@@ -266,7 +289,7 @@ constexpr bool resid_nat(int epi, bool sf32) { return nat_order(epi, sf32) && ep
 //                  instantiation spills - it keeps the accumulator-layout epilogue)
 constexpr bool epi_rowmajor(int epi, bool sf32, int mi) { return resid_nat(epi, sf32) && mi <= 4; }
 constexpr bool epi_rowmajor_wide(int epi, bool sf32, int mi, bool w8) { return resid_nat(epi, sf32) && mi > 4 && !w8; }
-constexpr bool epi_tstore(int epi) { return RAJNI_TSTORE && (epi == EPI_BIAS || epi == EPI_GELU); }
+constexpr bool epi_tstore(int epi) { return RAJNI_TSTORE && (epi == EPI_BIAS || epi_act(epi)); }
 constexpr int stream_scratch_bytes(int epi, bool sf32, int mi, bool w8) {   // wide::gemm_bf16_tn_stream
   return (epi_rowmajor(epi, sf32, mi) || epi_rowmajor_wide(epi, sf32, mi, w8) || epi_tstore(epi)) ? 2048 : 0;
 }
@@ -582,7 +605,7 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, f32x4 (&acc)[
       return;
     }
   }
-  if constexpr (MAP == MAP_SEC && (EPI == EPI_BIAS || EPI == EPI_GELU)) {
+  if constexpr (MAP == MAP_SEC && (EPI == EPI_BIAS || epi_act(EPI))) {
     // interior tile of a bf16-output launch (QKV, FC1 - the bulk of all tiles): no row or column guard, the
     // lane's 2 x 8 columns of bias (and fp8 scale) as four 16-byte loads, two 16-byte stores per row.  The
     // guarded general path below costs ~3x the instructions in exec-mask branches alone.
@@ -616,6 +639,9 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, f32x4 (&acc)[
             gelu_pk4(a, b);
             v[j] = a[0]; v[j + 1] = a[1]; v[j + 2] = b[0]; v[j + 3] = b[1];
           }
+        } else if (EPI == EPI_QGELU) {
+#pragma unroll
+          for (int j = 0; j < 16; ++j) v[j] = quick_gelu1(v[j]);
         }
         if (scratch != nullptr) {
           // whole 128-byte lines: the wave's 16 x 64 bf16 block (one line per row) through its 2 KiB LDS scratch - written as
@@ -633,13 +659,13 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, f32x4 (&acc)[
           for (int j = 0; j < 2; ++j) {
             const int row = 8 * j + rr;
             const uint4 q = __builtin_bit_cast(uint4, *reinterpret_cast<const bf16x8*>(scratch + row * 128 + ((cc ^ (row & 7)) << 4)));
-            store_u4<RAJNI_FC1_NT && EPI == EPI_GELU>(Y + (long)(m_base + mi * 16 + row) * p.ldc + n0w + 8 * cc, q);
+            store_u4<RAJNI_FC1_NT && epi_act(EPI)>(Y + (long)(m_base + mi * 16 + row) * p.ldc + n0w + 8 * cc, q);
           }
           __builtin_amdgcn_wave_barrier();
         } else {
           A* row = Y + (long)(m_base + mi * 16 + l15) * p.ldc;
-          store_u4<RAJNI_FC1_NT && EPI == EPI_GELU>(row + ca, pack8<A>(v));
-          store_u4<RAJNI_FC1_NT && EPI == EPI_GELU>(row + cb, pack8<A>(v + 8));
+          store_u4<RAJNI_FC1_NT && epi_act(EPI)>(row + ca, pack8<A>(v));
+          store_u4<RAJNI_FC1_NT && epi_act(EPI)>(row + cb, pack8<A>(v + 8));
         }
       }
       return;
@@ -1195,6 +1221,9 @@ __device__ __forceinline__ void epilogue_row_f32(const GemmParams& p, int m, int
   if (EPI == EPI_GELU) {
 #pragma unroll
     for (int j = 0; j < 16; ++j) v[j] = 0.5f * v[j] * (1.0f + erff(v[j] * 0.70710678118654752f));
+  } else if (EPI == EPI_QGELU) {   // accurate expf and a true division; expf -> +inf for large -v: v / inf = -0, never NaN
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = v[j] / (1.0f + expf(-1.702f * v[j]));
   } else if (EPI == EPI_RESID) {
     long rrow = m;
     if (p.ridx != nullptr) {
@@ -1567,6 +1596,7 @@ template <bool W8, typename A>
 int linear16(int epi, bool sf32, GemmParams& p, const LaunchCtl& l) {
   return epi == EPI_BIAS ? launch_gemm<EPI_BIAS, ALOAD_PLAIN, false, W8, A>(p, l)
        : epi == EPI_GELU ? launch_gemm<EPI_GELU, ALOAD_PLAIN, false, W8, A>(p, l)
+       : epi == EPI_QGELU ? launch_gemm<EPI_QGELU, ALOAD_PLAIN, false, W8, A>(p, l)
        : sf32 ? launch_gemm<EPI_RESID, ALOAD_PLAIN, true, W8, A>(p, l) : launch_gemm<EPI_RESID, ALOAD_PLAIN, false, W8, A>(p, l);
 }
 int linear(const rajni_linear_args& a, LaunchCtl l) {
@@ -1625,6 +1655,12 @@ int linear(const rajni_linear_args& a, LaunchCtl l) {
                     "rajni_linear: the fp8 x fp8 GELU epilogue writes e4m3 (y_scale required, ldc %% 16 == 0 bytes)");
       epi = f8 ? EPI_GELU8 : EPI_GELU; l.kclass = f8 ? KC_GEMM8_GELU : KC_GEMM_GELU;
       break;
+    case RAJNI_EPI_BIAS_QUICK_GELU:
+      RAJNI_REQUIRE(!f8, RAJNI_ERR_UNSUPPORTED,
+                    "rajni_linear: the QuickGELU epilogue is unsupported with fp8 activations (x_scale): the fp8 x fp8 kernel's "
+                    "re-quantising epilogue exists for exact GELU only");
+      epi = EPI_QGELU; l.kclass = KC_GEMM_GELU;
+      break;
     case RAJNI_EPI_BIAS_RESID:
       // fp32 asks for no ldr rule: its epilogue (epilogue_row_f32) reads the residual row one element at a time, so any
       // stride serves; the 16-bit and fp8 x fp8 epilogues read it 16 bytes at a time.  Only fp8 x fp8 can meet a y_scale
@@ -1646,7 +1682,7 @@ int linear(const rajni_linear_args& a, LaunchCtl l) {
     case FMT_F8F8: return epi == EPI_BIAS ? launch_gemm_f8<EPI_BIAS, false>(p, l) : epi == EPI_GELU8 ? launch_gemm_f8<EPI_GELU8, false>(p, l)
                         : sf32 ? launch_gemm_f8<EPI_RESID, true>(p, l) : launch_gemm_f8<EPI_RESID, false>(p, l);
     case FMT_F32: return epi == EPI_BIAS ? launch_gemm_f32<EPI_BIAS, ALOAD_PLAIN>(p, l) : epi == EPI_GELU ? launch_gemm_f32<EPI_GELU, ALOAD_PLAIN>(p, l)
-                       : launch_gemm_f32<EPI_RESID, ALOAD_PLAIN>(p, l);
+                       : epi == EPI_QGELU ? launch_gemm_f32<EPI_QGELU, ALOAD_PLAIN>(p, l) : launch_gemm_f32<EPI_RESID, ALOAD_PLAIN>(p, l);
     case FMT_W8: return linear16<true, bf16_t>(epi, sf32, p, l);
     case FMT_F16: return linear16<false, f16_t>(epi, sf32, p, l);
     default: return linear16<false, bf16_t>(epi, sf32, p, l);

@@ -16,8 +16,10 @@ LIB_PATH = os.environ.get("RAJNI_HIP_LIB") or os.path.join(_HERE, "lib", "libraj
 
 RAJNI_F32, RAJNI_BF16, RAJNI_F16 = 0, 1, 2
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID = 0, 1, 2
+EPI_BIAS_QUICK_GELU = 16      # y = quick_gelu(x W^T + b); not with fp8 activations (x_scale)
 NUM_KCLASS = 17
 POOL_TOKEN, POOL_AVG = 0, 1
+MLP_GELU, MLP_QUICK_GELU = 0, 1      # rajni_vit_ext.mlp_act
 
 c_void_p, c_int, c_long, c_float, c_size_t = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
 
@@ -76,11 +78,13 @@ class QkAffine(C.Structure):
 
 
 class VitExt(C.Structure):
-    """rajni_vit_ext: the timm options beside the plan (q/k-norm, norm_pre, pooled head, fc_norm); all zero = none"""
+    """rajni_vit_ext: the timm options beside the plan (q/k-norm, norm_pre, pooled head, fc_norm, the MLP activation); all
+    zero = none.  `mlp_act` fills what was the record's tail padding: offset 68, size 72 as before."""
     _fields_ = [("qk_norm", C.POINTER(QkAffine)), ("qk_eps", c_float),
                 ("norm_pre_w", c_void_p), ("norm_pre_b", c_void_p), ("norm_pre_eps", c_float),
                 ("norm_absent", c_int), ("pool", c_int),
-                ("fc_norm_w", c_void_p), ("fc_norm_b", c_void_p), ("fc_norm_eps", c_float)]
+                ("fc_norm_w", c_void_p), ("fc_norm_b", c_void_p), ("fc_norm_eps", c_float),
+                ("mlp_act", c_int)]
 
 
 class VitPrefix(C.Structure):

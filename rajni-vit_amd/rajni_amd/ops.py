@@ -365,7 +365,9 @@ def linear(x: torch.Tensor, w_packed: torch.Tensor, n_out: int, bias: Optional[t
     resid [B, N_src, n_out] (+ r_idx [B, Np] int32 to gather its rows) for EPI_BIAS_RESID; an fp32
     resid selects the fp32 residual stream (the output is then fp32 too).
     With `x_scale` (fp32 [M]) x is the uint8 e4m3 tensor of layernorm_fp8() and the product runs on the fp8 matrix
-    pipe (w_scale required); with EPI_BIAS_GELU `y_scale` (fp32 [M]) is required and the result is uint8 e4m3."""
+    pipe (w_scale required); with EPI_BIAS_GELU `y_scale` (fp32 [M]) is required and the result is uint8 e4m3.
+    EPI_BIAS_QUICK_GELU (x * sigmoid(1.702 x)) is EPI_BIAS_GELU with the other function, for every format but `x_scale`
+    (NotImplementedError from the library)."""
     nat.require_device(x, "x")
     x, w_packed = _placed(x, "x"), _placed(w_packed, "w")
     bias, gamma, w_scale = _placed(bias, "bias"), _placed(gamma, "gamma"), _placed(w_scale, "w_scale")

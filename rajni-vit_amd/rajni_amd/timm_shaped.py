@@ -52,6 +52,10 @@ class ViTConfig:
     pre_norm: bool = False                # norm_pre after the pos-embed (CLIP-derived ViTs)
     global_pool: str = "token"            # 'token' (x[:, 0]) or 'avg' (mean of x[:, 1:])
     fc_norm: Optional[bool] = None        # None = timm's default: an fc_norm (and no final norm) iff global_pool == 'avg'
+    act: str = "gelu"                     # MLP activation: "gelu" (exact erf) or "quick_gelu" (x * sigmoid(1.702 x): the OpenAI
+                                          # CLIP, MetaCLIP and DFN towers); no weights are drawn for it.  (Keyword only in
+                                          # practice; it sits in front of reg_tokens because tests/test_prefix_cpu.py holds
+                                          # reg_tokens to be the last field)
     reg_tokens: int = 0                   # register tokens behind the class token (timm reg_tokens; DINOv2 "reg4": 4)
 
     @property
@@ -105,7 +109,7 @@ CONFIGS: Dict[str, ViTConfig] = {
                                           num_classes=10),
     # ---- timm options beyond plain ViT / DeiT ----
     # CLIP-derived ViT-B/16 (timm `vit_base_patch16_clip_224`: pre_norm, LayerNorm eps 1e-5, exact GELU, token head; the
-    # `_quickgelu_` variants are a different activation and stay refused)
+    # `_quickgelu_` variants - the same towers with the other activation - are further down)
     "vit_base_patch16_clip_224": ViTConfig(embed_dim=768, depth=12, num_heads=12, pre_norm=True, ln_eps=1e-5),
     # ViT-B/16 with q/k LayerNorm (timm `vit_base_patch16_224(qk_norm=True)`; not a checkpoint name)
     "vit_base_patch16_qknorm_224": ViTConfig(embed_dim=768, depth=12, num_heads=12, qk_norm=True),
@@ -144,6 +148,23 @@ CONFIGS: Dict[str, ViTConfig] = {
     # the same with 4 registers in the DINOv2 / DeiT-3 layout (630 tokens)
     "vit_micro_reg4_patch16_400": ViTConfig(img_size=400, embed_dim=128, depth=4, num_heads=2, num_classes=10,
                                             layer_scale=1e-6, no_embed_class=True, reg_tokens=4),
+    # ---- QuickGELU MLPs: the original OpenAI CLIP towers, MetaCLIP, DFN (timm `*_clip_quickgelu_*`) ----
+    "vit_base_patch16_clip_quickgelu_224": ViTConfig(embed_dim=768, depth=12, num_heads=12, pre_norm=True, ln_eps=1e-5,
+                                                     act="quick_gelu"),
+    "vit_base_patch32_clip_quickgelu_224": ViTConfig(patch_size=32, embed_dim=768, depth=12, num_heads=12, pre_norm=True,
+                                                     ln_eps=1e-5, act="quick_gelu"),
+    "vit_large_patch14_clip_quickgelu_224": ViTConfig(patch_size=14, embed_dim=1024, depth=24, num_heads=16, pre_norm=True,
+                                                      ln_eps=1e-5, act="quick_gelu"),
+    # micro models (not timm names): the activation alone, the CLIP layout, the fp8-capable dims, and an MLP width that is
+    # not whole 64-wide K steps (344 -> 384 zero-padded hidden columns: act(0) must be exactly 0)
+    "vit_micro_quickgelu_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, num_classes=10,
+                                                act="quick_gelu"),
+    "vit_micro_clip_quickgelu_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, num_classes=10,
+                                                     pre_norm=True, ln_eps=1e-5, act="quick_gelu"),
+    "vit_micro512_quickgelu_patch16_64": ViTConfig(img_size=64, embed_dim=512, depth=4, num_heads=8, num_classes=10,
+                                                   act="quick_gelu"),
+    "vit_micro_quickgelu_h344_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, mlp_ratio=2.6875,
+                                                     num_classes=10, act="quick_gelu"),
 }
 
 
@@ -191,11 +212,20 @@ class LayerScale(nn.Module):
         return x * self.gamma
 
 
+class QuickGELU(nn.Module):
+    """x * sigmoid(1.702 x) (OpenAI CLIP; timm / open_clip `QuickGELU`)"""
+
+    def forward(self, x):
+        return x * torch.sigmoid(1.702 * x)
+
+
 class Mlp(nn.Module):
-    def __init__(self, dim: int, hidden: int):
+    def __init__(self, dim: int, hidden: int, act: str = "gelu"):
         super().__init__()
+        if act not in ("gelu", "quick_gelu"):
+            raise ValueError(f"act must be 'gelu' or 'quick_gelu', got {act!r}")
         self.fc1 = nn.Linear(dim, hidden)
-        self.act = nn.GELU()
+        self.act = nn.GELU() if act == "gelu" else QuickGELU()
         self.drop1 = nn.Dropout(0.0)
         self.norm = nn.Identity()
         self.fc2 = nn.Linear(hidden, dim)
@@ -214,7 +244,7 @@ class Block(nn.Module):
         self.ls1 = LayerScale(C, cfg.layer_scale) if cfg.layer_scale else nn.Identity()
         self.drop_path1 = nn.Identity()
         self.norm2 = nn.LayerNorm(C, eps=cfg.ln_eps)
-        self.mlp = Mlp(C, cfg.hidden_dim)
+        self.mlp = Mlp(C, cfg.hidden_dim, cfg.act)
         self.ls2 = LayerScale(C, cfg.layer_scale) if cfg.layer_scale else nn.Identity()
         self.drop_path2 = nn.Identity()
 

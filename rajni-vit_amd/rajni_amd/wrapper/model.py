@@ -71,6 +71,30 @@ def model_num_prefix(m: nn.Module) -> int:
     return P
 
 
+def classify_mlp_act(act: Optional[nn.Module]) -> str:
+    """"gelu" or "quick_gelu": what a block's `mlp.act` COMPUTES, not what it is called.  Exact-erf `nn.GELU` is GELU.
+    Anything else is probed once on the CPU - a fixed fp32 grid on [-6, 6] through the module - and is QuickGELU when it
+    matches x * sigmoid(1.702 x) to 1e-6: timm's and open_clip's `QuickGELU` and transformers' `QuickGELUActivation` pass
+    without being imported, a class of that name that computes something else does not.  Everything unmatched (tanh-GELU,
+    SiLU, ReLU ...) raises NotImplementedError naming the class."""
+    if isinstance(act, nn.GELU):
+        if getattr(act, "approximate", "none") == "none":
+            return "gelu"
+    elif isinstance(act, nn.Module):
+        grid = torch.linspace(-6.0, 6.0, 193, dtype=torch.float32)
+        try:
+            with torch.no_grad():
+                got = act(grid.clone())
+        except Exception:
+            got = None
+        if (isinstance(got, torch.Tensor) and got.shape == grid.shape and got.dtype == torch.float32
+                and float((got - grid * torch.sigmoid(1.702 * grid)).abs().max()) <= 1e-6):
+            return "quick_gelu"
+    name = type(act).__name__ + ("(approximate=%r)" % act.approximate if isinstance(act, nn.GELU) else "")
+    raise NotImplementedError(f"mlp.act must be exact-erf nn.GELU (timm default) or QuickGELU, x * sigmoid(1.702 x); "
+                              f"{name} computes neither")
+
+
 class RAJNIViTWrapper(nn.Module):
     def __init__(self, base_model: nn.Module, pruning_schedule: Dict[int, Dict]):
         super().__init__()
@@ -163,6 +187,9 @@ class RAJNIViTWrapper(nn.Module):
         embed dim and MLP width that are multiples of 256."""
         if fmt not in ("model", "fp8", "fp8_mfma"):
             raise ValueError('weight format must be "model", "fp8" or "fp8_mfma"')
+        if fmt == "fp8_mfma" and self._mlp_act_or_none() == "quick_gelu":
+            raise NotImplementedError('set_weight_format("fp8_mfma"): the model\'s MLPs use QuickGELU; the fp8 x fp8 FC1 epilogue '
+                                      'and its hidden-activation bound are exact GELU only ("fp8" weights work)')
         if fmt != self._weight_format:
             self._weight_format = fmt
             self._weights = self._weights_key = None
@@ -222,6 +249,14 @@ class RAJNIViTWrapper(nn.Module):
             raise NotImplementedError(f"RAJNIViTWrapper: global_pool={pool!r} is not supported ('token' or 'avg')")
         return pool
 
+    def _mlp_act_or_none(self) -> Optional[str]:
+        """the blocks' MLP activation where they agree on a supported one, else None (`_describe` reports why)"""
+        try:
+            kinds = {classify_mlp_act(getattr(blk.mlp, "act", None)) for blk in self.blocks}
+        except (NotImplementedError, AttributeError):
+            return None
+        return kinds.pop() if len(kinds) == 1 else None
+
     def check_supported(self) -> Dict:
         """Raise NotImplementedError if the base model has a feature the native forward does not compute (host only, no
         device needed; `forward` runs the same check).  Returns the model description."""
@@ -249,9 +284,12 @@ class RAJNIViTWrapper(nn.Module):
             for ln in (blk.norm1, blk.norm2):
                 if not isinstance(ln, nn.LayerNorm) or ln.weight is None or float(ln.eps) != desc["ln_eps"]:
                     raise NotImplementedError(f"block {i}: norm layers must be affine nn.LayerNorm with one eps")
-            act = getattr(blk.mlp, "act", None)
-            if not isinstance(act, nn.GELU) or getattr(act, "approximate", "none") != "none":
-                raise NotImplementedError(f"block {i}: mlp.act must be exact-erf nn.GELU (timm default)")
+            try:
+                kind = classify_mlp_act(getattr(blk.mlp, "act", None))
+            except NotImplementedError as e:
+                raise NotImplementedError(f"block {i}: {e}") from None
+            if desc.setdefault("mlp_act", kind) != kind:
+                raise NotImplementedError(f"block {i}: mlp.act differs between blocks ({kind} after {desc['mlp_act']})")
             mlp_norm = getattr(blk.mlp, "norm", None)
             if mlp_norm is not None and not isinstance(mlp_norm, nn.Identity):
                 raise NotImplementedError(f"block {i}: mlp.norm is not supported")
@@ -291,7 +329,8 @@ class RAJNIViTWrapper(nn.Module):
         if desc["pool"] == "avg" and self._cls_only_last:
             raise ValueError("global_pool='avg' with set_last_block_cls_only(True): that opt-in never forms the rows to be averaged")
         # plans that need none of these keep calling rajni_vit_forward
-        desc["ext"] = desc["qk_norm"] or desc["norm_pre"] or desc["fc_norm"] or not desc["norm"] or desc["pool"] != "token"
+        desc["ext"] = (desc["qk_norm"] or desc["norm_pre"] or desc["fc_norm"] or not desc["norm"] or desc["pool"] != "token"
+                       or desc["mlp_act"] != "gelu")
         return desc
 
     def _all_params(self):
@@ -341,6 +380,8 @@ class RAJNIViTWrapper(nn.Module):
         desc = self._describe()
         m = self.m
         fp8 = self._weight_format in ("fp8", "fp8_mfma")
+        if self._weight_format == "fp8_mfma" and desc["mlp_act"] != "gelu":   # (the activation was swapped after the setter)
+            raise NotImplementedError('weight format "fp8_mfma" with a QuickGELU MLP: the fp8 x fp8 FC1 epilogue is exact GELU only')
         if fp8 and dtype != torch.bfloat16:
             raise NotImplementedError("fp8 weights need a bf16 model (activations stay bf16)")
         pw = lambda w: ops.pack_weight(w, dtype, device)
@@ -379,7 +420,7 @@ class RAJNIViTWrapper(nn.Module):
                     raise NotImplementedError("drop_path in training mode: this is the inference path")
             (qkv_w, qkv_s), (proj_w, proj_s) = pq(a.qkv.weight), pq(a.proj.weight)
             # An MLP width that is not whole 64-wide K steps (so400m: 4304) is zero-padded: fc1 gets zero rows (it
-            # has them anyway, up to the next 256) with zero bias, GELU(0) = 0 lands in the padding columns of the
+            # has them anyway, up to the next 256) with zero bias, GELU(0) = 0 (QuickGELU(0) = 0 alike) lands in the padding columns of the
             # hidden buffer, and fc2's zero-padded input columns ignore them - exact, no kernel involved.
             hid, hpad = desc["hidden"], desc["hidden_pad"]
             (fc1_w, fc1_s) = pq(blk.mlp.fc1.weight)
@@ -516,6 +557,7 @@ class RAJNIViTWrapper(nn.Module):
             ext.fc_norm_w, ext.fc_norm_b, ext.fc_norm_eps = nat.ptr(W["fc_norm_w"]), nat.ptr(W["fc_norm_b"]), W["fc_norm_eps"]
             ext.norm_absent = int(not d["norm"])
             ext.pool = nat.POOL_AVG if d["pool"] == "avg" else nat.POOL_TOKEN
+            ext.mlp_act = nat.MLP_QUICK_GELU if d["mlp_act"] == "quick_gelu" else nat.MLP_GELU
         # W: a stale optimistic launch keeps its weights alive
         self._plan = (key, plan, (blocks, tc, ws, W, ext, qk, pre), bufs, counts)
         if len(self._plans) >= 4:     # workspaces are large: keep only a few batch shapes alive
