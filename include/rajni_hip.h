@@ -373,9 +373,25 @@ int rajni_vit_forward_ext(const rajni_vit_plan* plan, const rajni_vit_ext* ext, 
  * 1 <= num_prefix <= RAJNI_MAX_PREFIX. */
 #define RAJNI_MAX_PREFIX 32
 
-/* The prefix record of the whole forward: travels beside the plan and the ext record (their layouts stay what they are). */
+/* The prefix record of the whole forward: travels beside the plan and the ext record (their layouts stay what they are).
+ *
+ * head_rows = 2 is timm's VisionTransformerDistilled in eval mode (the distilled DeiT checkpoints): token order
+ * [cls, dist, patches], the dist token a prefix token exactly like a register (never pruned, never ranked, no rank slot; its
+ * [1, C] row travels as reg_token, num_prefix = 2), and the head reads rows 0 and 1 of the normalised stream:
+ *   logits = (head(norm(x)[:, 0]) + head_dist(norm(x)[:, 1])) / 2
+ * as ONE linear layer with K = 2C: the final LayerNorm writes the two normalised rows of image b side by side as row b of
+ * [B, 2C], plan.head_w is [classes(pad), 2C] = [0.5 * head.weight | 0.5 * head_dist.weight] and plan.head_b is
+ * 0.5 * (head.bias + head_dist.bias).  Both products accumulate in fp32 and the sum is rounded once.  A last block that
+ * does not prune is computed for those two rows only, bit for bit the all-rows logits.  head_rows = 2 needs num_prefix == 2
+ * (else RAJNI_ERR_INVALID) and a plain token head: ext.pool == RAJNI_POOL_TOKEN, no fc_norm, a final norm
+ * (RAJNI_ERR_UNSUPPORTED); with plan.cls_only_last_block it is RAJNI_ERR_INVALID (that opt-in forms the CLS row only), with
+ * plan.act_fp8 RAJNI_ERR_UNSUPPORTED.  Any value outside 0..2 is RAJNI_ERR_INVALID.  All of it before the first launch. */
 typedef struct {
   int num_prefix;          /* P = 1 + number of register tokens; 0 or 1: CLS only (reg_token is not read) */
+  int head_rows;           /* rows of each image the head reads: 0 or 1 = row 0 (the class token), 2 = rows 0 and 1 (above).  It
+                              sits in what were the four bytes of padding behind num_prefix (offset 4 of 16: reg_token is 8-byte
+                              aligned), so no field moves, the size stays and RAJNI_ABI_VERSION does not move; callers zero the
+                              record, and a zero here is the forward as it was, launch for launch */
   const void* reg_token;   /* [num_prefix-1, C] in the plan's dtype, 16-byte aligned; required when num_prefix > 1.
                               plan.pos_embed then has (plan.pos_has_cls ? num_prefix : 0) + n rows */
 } rajni_vit_prefix;

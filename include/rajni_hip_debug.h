@@ -29,7 +29,8 @@ int rajni_debug_attention_rows(const void* qkv, const int32_t* keep_idx, void* o
  * computed, the reference's op graph row for row.  Token counts, stats and traces are the same either way. */
 void rajni_debug_set_last_block_all_rows(int on);
 /* the eligibility test alone, on the host (ext / prefix may be NULL; no device pointer is followed): 1 when the forward of
- * this plan computes its last block for the CLS rows only, 0 when for all rows */
+ * this plan computes its last block for the rows the head reads only (the CLS rows; with rajni_vit_prefix.head_rows == 2 rows
+ * 0 and 1 of each image, 2B rows), 0 when for all rows */
 int rajni_debug_last_block_cls_rows(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix);
 
 /* GEMM tiling: 0 = by shape (default), 1 = 128x128x64 (4 waves), 4 = 256x256x64 persistent,

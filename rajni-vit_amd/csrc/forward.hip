@@ -8,6 +8,7 @@
 // FC2 GEMM + LayerScale + residual (in place).  The attention form is one of
 //   [score+select] -> attention on the kept tokens (gather fused into its loads), all rows;
 //   the first query tile of that attention, tail on the B CLS rows (last block, the same bits: last_block_cls_rows);
+//   the same tile, its rows 0 and 1 gathered dense, tail on those 2B rows (last block of a distilled model, head_rows == 2);
 //   the CLS-query kernel, tail on the B CLS rows (last block, the cls_only_last_block opt-in);
 // and hands the tail an AttnRows record.  The reference's three gathers (qkv, scores, x) never exist as kernels here.
 //
@@ -22,12 +23,13 @@ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct Workspace {
   char *xa, *xb, *xn, *qkv, *att, *hid, *clsn, *scf, *cols;
+  int32_t* idx01;          // head_rows == 2: [B, 2] = {0, 1} per image, the selection that names the two rows the head reads
   char* sst; size_t sst_bytes;   // scratch of the tiled score kernels: zero bytes wherever one workgroup holds (n0, H, D)
   float *xs, *hs;          // act_fp8 plans: per-row scales of the e4m3 LayerNorm output / MLP hidden activations
   size_t total, cols_bytes;
 };
 
-Workspace carve(const rajni_vit_plan& p, int P) {
+Workspace carve(const rajni_vit_plan& p, int P, int HR) {
   const size_t gw = p.img_size / p.patch_size, n0 = gw * gw + P;
   const size_t rows = (size_t)p.B * n0, es = p.dtype == RAJNI_F32 ? 4 : 2, xs = (p.dtype == RAJNI_F32 || !p.resid_bf16) ? 4 : 2;
   Workspace w{};
@@ -35,17 +37,19 @@ Workspace carve(const rajni_vit_plan& p, int P) {
   auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
   const size_t oxa = take(rows * p.C * xs), oxb = take(rows * p.C * xs), oxn = take(rows * p.C * es);
   const size_t oqkv = take(rows * 3 * p.C * es), oatt = take(rows * p.C * es);
-  const size_t ohid = take(rows * p.hidden * es), ocls = take((size_t)p.B * p.C * es);
+  const size_t ohid = take(rows * p.hidden * es), ocls = take((size_t)p.B * HR * p.C * es);
   const size_t oscf = take(rows * es);
   w.cols_bytes = patch_embed_workspace_bytes(p.B, p.in_chans, p.img_size, p.patch_size, p.dtype);   // 0 when fused
   const size_t ocols = take(w.cols_bytes);
   const size_t oxs = take(p.act_fp8 ? rows * sizeof(float) : 0), ohs = take(p.act_fp8 ? rows * sizeof(float) : 0);
   w.sst_bytes = rajni_score_select_workspace_bytes(p.B, (int)n0, p.H, p.D, p.dtype);
   const size_t osst = take(w.sst_bytes);
+  const size_t oidx = take(HR == 2 ? (size_t)p.B * 2 * sizeof(int32_t) : 0);   // last: nothing above moves
   char* base = (char*)p.workspace;
   w.xa = base + oxa; w.xb = base + oxb; w.xn = base + oxn; w.qkv = base + oqkv; w.att = base + oatt;
   w.hid = base + ohid; w.clsn = base + ocls; w.scf = base + oscf; w.cols = base + ocols;
   w.sst = w.sst_bytes ? base + osst : nullptr;
+  w.idx01 = HR == 2 ? reinterpret_cast<int32_t*>(base + oidx) : nullptr;
   w.xs = reinterpret_cast<float*>(base + oxs); w.hs = reinterpret_cast<float*>(base + ohs);
   w.total = off;
   return w;
@@ -58,6 +62,12 @@ __global__ void carry_scores_kernel(const T* scores, const int* idx, T* out, int
   if (i >= B * np) return;
   const int b = i / np;
   out[i] = scores[(long)b * N + idx[i]];
+}
+
+// idx[b, r] = r for r in {0, 1}: filled on the stream (capturable, no host copy)
+__global__ void head_rows_idx_kernel(int* idx, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) idx[i] = i & 1;
 }
 
 // the placement contract (include/rajni_hip.h) for everything a plan points to, with images and logits
@@ -147,7 +157,8 @@ int g_last_block_all_rows = 0;
 // proj / LN2 / FC1 / fc2 on the B CLS rows - the kernels of the all-rows form on fewer rows, hence the same bits (a row
 // of an attention, LayerNorm or rajni_linear result does not depend on which other rows are in the launch).  Not for: a
 // last block that prunes (its selection is part of the trace), an avg-pooled head (reads every row), act_fp8 plans and
-// the cls_only_last_block opt-in (they keep the opt-in's own branch and numerics contract).
+// the cls_only_last_block opt-in (they keep the opt-in's own branch and numerics contract).  With the distilled head
+// (head_rows == 2) the observable rows are 0 and 1 of each image, and the block runs on those 2B rows under the same test.
 inline bool last_block_cls_rows(const rajni_vit_plan& p, const rajni_vit_ext* ext, int i, int N) {
   return i == p.depth - 1 && p.blocks[i].keep == 0 && N > 1 && (ext == nullptr || ext->pool == RAJNI_POOL_TOKEN) &&
          !p.act_fp8 && !p.cls_only_last_block && !g_last_block_all_rows;
@@ -241,6 +252,8 @@ int launch_tail(const Fwd& f, const rajni_block& blk, const Tail& t) {
 
 // P of a prefix record: NULL, 0 and 1 all mean CLS only
 inline int prefix_count(const rajni_vit_prefix* pre) { return (pre && pre->num_prefix > 1) ? pre->num_prefix : 1; }
+// rows of each image the head reads: NULL, 0 and 1 all mean the CLS row; 2 is the distilled head (cls and dist rows)
+inline int head_row_count(const rajni_vit_prefix* pre) { return (pre && pre->head_rows == 2) ? 2 : 1; }
 
 int check_prefix(const rajni_vit_prefix* pre, const char* who) {
   if (!pre) return RAJNI_OK;
@@ -250,6 +263,21 @@ int check_prefix(const rajni_vit_prefix* pre, const char* who) {
                 "%s: %d prefix tokens but reg_token is null", who, pre->num_prefix);
   RAJNI_REQUIRE(pre->num_prefix > 1 || pre->reg_token == nullptr, RAJNI_ERR_INVALID,
                 "%s: reg_token given but num_prefix is %d", who, pre->num_prefix);
+  RAJNI_REQUIRE(pre->head_rows >= 0 && pre->head_rows <= 2, RAJNI_ERR_INVALID, "%s: head_rows must be 0..2 (%d)", who, pre->head_rows);
+  RAJNI_REQUIRE(pre->head_rows != 2 || pre->num_prefix == 2, RAJNI_ERR_INVALID,
+                "%s: head_rows=2 (the distilled head reads the cls and dist rows) needs num_prefix == 2 (%d)", who, pre->num_prefix);
+  return RAJNI_OK;
+}
+
+// the distilled head (head_rows == 2) against the plan and the ext record: it is norm -> rows 0 and 1 -> one linear layer
+int check_head_rows(const rajni_vit_plan& p, const rajni_vit_ext* e, const rajni_vit_prefix* pre) {
+  if (head_row_count(pre) != 2) return RAJNI_OK;
+  RAJNI_REQUIRE(!e || (e->pool == RAJNI_POOL_TOKEN && !e->fc_norm_w && !e->norm_absent), RAJNI_ERR_UNSUPPORTED,
+                "rajni_vit_forward: head_rows=2 needs a token head behind the final norm (pool=%d, fc_norm %s, norm %s)", e->pool,
+                e->fc_norm_w ? "present" : "absent", e->norm_absent ? "absent" : "present");
+  RAJNI_REQUIRE(!p.cls_only_last_block, RAJNI_ERR_INVALID,
+                "rajni_vit_forward: head_rows=2 with cls_only_last_block - that opt-in forms the CLS row only");
+  RAJNI_REQUIRE(!p.act_fp8, RAJNI_ERR_UNSUPPORTED, "rajni_vit_forward: head_rows=2 is unsupported with act_fp8");
   return RAJNI_OK;
 }
 
@@ -292,7 +320,7 @@ extern "C" size_t rajni_vit_workspace_bytes_prefix(const rajni_vit_plan* plan, c
   if (check_prefix(prefix, "rajni_vit_workspace_bytes_prefix") != RAJNI_OK) return 0;
   rajni_vit_plan tmp = *plan;
   tmp.workspace = nullptr;
-  return carve(tmp, prefix_count(prefix)).total;
+  return carve(tmp, prefix_count(prefix), head_row_count(prefix)).total;
 }
 
 extern "C" size_t rajni_vit_workspace_bytes(const rajni_vit_plan* plan) { return rajni_vit_workspace_bytes_prefix(plan, nullptr); }
@@ -316,8 +344,9 @@ extern "C" int rajni_vit_forward_ext_prefix(const rajni_vit_plan* plan, const ra
 
 extern "C" void rajni_debug_set_last_block_all_rows(int on) { g_last_block_all_rows = on; }
 
-// 1 when the forward of this plan (with this ext / prefix record, either may be NULL) computes its last block for the CLS rows
-// only, 0 when for all rows: the eligibility test alone, on the host, nothing launched and no device pointer followed
+// 1 when the forward of this plan (with this ext / prefix record, either may be NULL) computes its last block for the rows the
+// head reads only (the CLS rows; rows 0 and 1 with head_rows == 2), 0 when for all rows: the eligibility test alone, on the
+// host, nothing launched and no device pointer followed
 extern "C" int rajni_debug_last_block_cls_rows(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix) {
   if (!plan || !plan->blocks || plan->depth <= 0 || plan->patch_size <= 0) return 0;
   const int last = plan->depth - 1;
@@ -339,11 +368,14 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
     rc = check_ext(p, *ext);
     if (rc != RAJNI_OK) return rc;
   }
+  rc = check_head_rows(p, ext, pre);
+  if (rc != RAJNI_OK) return rc;
   const rajni_qk_affine* qkn = ext ? ext->qk_norm : nullptr;
-  const int P = prefix_count(pre);   // prefix tokens: CLS + registers, never pruned
+  const int P = prefix_count(pre);   // prefix tokens: CLS + registers (or the dist token), never pruned
+  const int HR = head_row_count(pre);   // rows of each image the head reads
   rc = check_schedule(p, P);
   if (rc != RAJNI_OK) return rc;
-  const Workspace w = carve(p, P);
+  const Workspace w = carve(p, P, HR);
   RAJNI_REQUIRE(p.workspace != nullptr && p.workspace_bytes >= w.total, RAJNI_ERR_INVALID,
                 "rajni_vit_forward: workspace too small (%zu < %zu)", p.workspace_bytes, w.total);
   const int B = p.B, C = p.C, dt = p.dtype;
@@ -358,6 +390,11 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
   if (ext && ext->norm_pre_w) {   // timm forward_features: x = norm_pre(x), written back into the stream
     rc = launch_layernorm_stream(w.xa, ext->norm_pre_w, ext->norm_pre_b, B * N, C, ext->norm_pre_eps, f.sf32, dt, s);
     if (rc != RAJNI_OK) return rc;
+  }
+
+  if (HR == 2) {
+    hipLaunchKernelGGL(head_rows_idx_kernel, dim3((2 * B + 255) / 256), dim3(256), 0, s, w.idx01, 2 * B);
+    RAJNI_CHECK_LAUNCH("head_rows_idx_kernel");
   }
 
   char* cur = w.xa;
@@ -390,7 +427,22 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
       cur = oth; N = 1;
       break;
     }
-    if (last_block_cls_rows(p, ext, i, N)) {
+    if (HR == 2 && last_block_cls_rows(p, ext, i, N)) {
+      // the distilled head reads rows 0 and 1: the first query tile (into w.xn, which QKV has consumed), its rows 0 and 1
+      // gathered dense into w.att, and the ordinary tail as a pruned block that keeps {0, 1} - the proj epilogue gathers
+      // the two residual rows through idx01 and the stream leaves [B, 2, C] in `oth`
+      const Tail t = tail_args(f, blk, AttnRows{2 * B, C, nullptr, C, w.idx01, 2, N}, cur, oth);
+      if (tail_ok(t)) {
+        rc = launch_attention(w.qkv, nullptr, w.xn, B, N, N, 2, p.H, p.D, p.attn_scale, dt, s);
+        if (rc != RAJNI_OK) return rc;
+        rc = launch_gather_rows(w.xn, w.idx01, w.att, B, N, 2, C * rajni_elem_bytes(dt), s);
+        if (rc != RAJNI_OK) return rc;
+        rc = launch_tail(f, blk, t);
+        if (rc != RAJNI_OK) return rc;
+        cur = oth; N = 2;
+        break;
+      }
+    } else if (last_block_cls_rows(p, ext, i, N)) {
       // the all-rows kernels on the rows the head reads: the first query tile, proj on its CLS rows in place (stride N * C)
       const Tail t = tail_args(f, blk, AttnRows{B, cls_ld, nullptr, cls_ld, nullptr, 0, 0}, cur, oth);
       if (tail_ok(t)) {   // (a refused shape or stride: all rows below, as if this branch were not here)
@@ -458,10 +510,20 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
   if (ext && (ext->pool != RAJNI_POOL_TOKEN || ext->fc_norm_w || ext->norm_absent))
     rc = launch_pool_norm(cur, B, N, C, ext->pool, ext->norm_absent ? nullptr : p.norm_w, p.norm_b, p.ln_eps,
                           ext->fc_norm_w, ext->fc_norm_b, ext->fc_norm_eps, w.clsn, f.sf32, dt, s, P);
-  else
+  else if (HR == 2) {
+    // rows 0 and 1 of every image, normalised side by side: row b of [B, 2C].  A stream that still holds all N rows (a last
+    // block that prunes, or the all-rows form) first gives up its two rows to the other stream buffer, dense
+    if (N > 2) {
+      oth = cur == w.xa ? w.xb : w.xa;
+      rc = launch_gather_rows(cur, w.idx01, oth, B, N, 2, C * ((f.sf32 || dt == RAJNI_F32) ? 4 : 2), s);
+      if (rc != RAJNI_OK) return rc;
+      cur = oth;
+    }
+    rc = launch_layernorm(cur, C, p.norm_w, p.norm_b, w.clsn, 2 * B, C, p.ln_eps, f.sf32, dt, s);
+  } else
     rc = launch_layernorm(cur, (long)N * C, p.norm_w, p.norm_b, w.clsn, B, C, p.ln_eps, f.sf32, dt, s);
   if (rc != RAJNI_OK) return rc;
-  rajni_linear_args head = linear_args(dt, w.clsn, p.head_w, p.head_b, nullptr, logits, B, p.num_classes, C, RAJNI_EPI_BIAS);
+  rajni_linear_args head = linear_args(dt, w.clsn, p.head_w, p.head_b, nullptr, logits, B, p.num_classes, HR * C, RAJNI_EPI_BIAS);
   head.ldc = logits_stride(p);
   return launch_linear(head, s);
 }

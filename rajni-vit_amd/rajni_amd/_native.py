@@ -88,8 +88,13 @@ class VitExt(C.Structure):
 
 
 class VitPrefix(C.Structure):
-    """rajni_vit_prefix: prefix tokens beyond CLS (timm register tokens), beside the plan and the ext record"""
-    _fields_ = [("num_prefix", c_int), ("reg_token", c_void_p)]
+    """rajni_vit_prefix: prefix tokens beyond CLS (timm register tokens, or DeiT's distillation token), beside the plan and
+    the ext record.  `head_rows` (2: the distilled head reads rows 0 and 1) fills what was the padding behind num_prefix:
+    offset 4, size 16 as before.  Positional construction stays (num_prefix, reg_token)."""
+    _fields_ = [("num_prefix", c_int), ("head_rows", c_int), ("reg_token", c_void_p)]
+
+    def __init__(self, num_prefix=0, reg_token=None, head_rows=0):
+        super().__init__(num_prefix=num_prefix, head_rows=head_rows, reg_token=reg_token)
 
 
 MAX_PREFIX = 32     # RAJNI_MAX_PREFIX

@@ -7,7 +7,9 @@ timm is not installed in the build/bench images, and the reference wrapper
   base : .patch_embed(x)->[B,N-1,C]  .cls_token [1,1,C]  .pos_embed [1,N,C]
          .pos_drop  .blocks  .norm  .head
          (+ timm's optional .reg_token [1,R,C] / .num_prefix_tokens = 1 + R: register tokens behind the
-          class token, which the reference does not handle and RAJNIViTWrapper does)
+          class token, which the reference does not handle and RAJNIViTWrapper does; and DeiT's distilled
+          form, timm VisionTransformerDistilled: .dist_token [1,1,C] behind the class token, .head_dist,
+          .num_prefix_tokens = 2, eval logits = (head(x[:, 0]) + head_dist(x[:, 1])) / 2)
   block: .norm1 .attn .norm2 .mlp  (+ optional .ls1 .ls2 .drop_path1 .drop_path2), blk(x)
   attn : .num_heads .scale .qkv (Linear C->3C laid out [3][H][D]) .proj .proj_drop
 
@@ -52,15 +54,22 @@ class ViTConfig:
     pre_norm: bool = False                # norm_pre after the pos-embed (CLIP-derived ViTs)
     global_pool: str = "token"            # 'token' (x[:, 0]) or 'avg' (mean of x[:, 1:])
     fc_norm: Optional[bool] = None        # None = timm's default: an fc_norm (and no final norm) iff global_pool == 'avg'
+    distilled: bool = False               # DeiT distilled (timm VisionTransformerDistilled): a dist_token behind the class
+                                          # token and a second classifier head_dist; not together with reg_tokens.  (In front of
+                                          # act and reg_tokens: existing tests hold those two to be the last fields)
     act: str = "gelu"                     # MLP activation: "gelu" (exact erf) or "quick_gelu" (x * sigmoid(1.702 x): the OpenAI
                                           # CLIP, MetaCLIP and DFN towers); no weights are drawn for it.  (Keyword only in
                                           # practice; it sits in front of reg_tokens because tests/test_prefix_cpu.py holds
                                           # reg_tokens to be the last field)
     reg_tokens: int = 0                   # register tokens behind the class token (timm reg_tokens; DINOv2 "reg4": 4)
 
+    def __post_init__(self):
+        if self.distilled and self.reg_tokens:
+            raise ValueError("ViTConfig: distilled together with reg_tokens is not a timm model")
+
     @property
     def num_prefix_tokens(self) -> int:
-        return 1 + self.reg_tokens
+        return 1 + self.reg_tokens + int(self.distilled)
 
     @property
     def use_fc_norm(self) -> bool:
@@ -165,6 +174,15 @@ CONFIGS: Dict[str, ViTConfig] = {
                                                    act="quick_gelu"),
     "vit_micro_quickgelu_h344_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, mlp_ratio=2.6875,
                                                      num_classes=10, act="quick_gelu"),
+    # ---- DeiT distilled (timm VisionTransformerDistilled): token order [cls, dist, patches], two averaged heads ----
+    "deit_tiny_distilled_patch16_224": ViTConfig(embed_dim=192, depth=12, num_heads=3, distilled=True),
+    "deit_small_distilled_patch16_224": ViTConfig(embed_dim=384, depth=12, num_heads=6, distilled=True),
+    "deit_base_distilled_patch16_224": ViTConfig(embed_dim=768, depth=12, num_heads=12, distilled=True),
+    "deit_base_distilled_patch16_384": ViTConfig(img_size=384, embed_dim=768, depth=12, num_heads=12, distilled=True),
+    # micro models (not timm names): 18 tokens; the second on the fp8-capable dims
+    "vit_micro_distilled_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, num_classes=10, distilled=True),
+    "vit_micro512_distilled_patch16_64": ViTConfig(img_size=64, embed_dim=512, depth=4, num_heads=8, num_classes=10,
+                                                   distilled=True),
 }
 
 
@@ -268,6 +286,9 @@ class VisionTransformer(nn.Module):
         self.patch_embed = PatchEmbed(cfg)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, cfg.embed_dim))
         self.reg_token = nn.Parameter(torch.zeros(1, cfg.reg_tokens, cfg.embed_dim)) if cfg.reg_tokens else None
+        if cfg.distilled:      # timm VisionTransformerDistilled (a plain model has neither attribute, like timm's)
+            self.dist_token = nn.Parameter(torch.zeros(1, 1, cfg.embed_dim))
+            self.distilled_training = False
         n_pos = cfg.num_patches if cfg.no_embed_class else cfg.num_patches + cfg.num_prefix_tokens
         self.pos_embed = nn.Parameter(torch.zeros(1, n_pos, cfg.embed_dim))
         self.pos_drop = nn.Dropout(0.0)
@@ -281,12 +302,18 @@ class VisionTransformer(nn.Module):
         self.fc_norm = nn.LayerNorm(cfg.embed_dim, eps=cfg.ln_eps) if cfg.use_fc_norm else nn.Identity()
         self.head_drop = nn.Dropout(0.0)
         self.head = nn.Linear(cfg.embed_dim, cfg.num_classes)
+        if cfg.distilled:
+            if cfg.global_pool != "token" or cfg.use_fc_norm:
+                raise ValueError("a distilled model has a token head and no fc_norm")
+            self.head_dist = nn.Linear(cfg.embed_dim, cfg.num_classes)
 
     def _pos_embed(self, x):
         # timm: prefix tokens [cls, reg...] in front; the pos-embed covers them unless no_embed_class
         prefix = [self.cls_token.expand(x.shape[0], -1, -1)]
         if self.reg_token is not None:
             prefix.append(self.reg_token.expand(x.shape[0], -1, -1))
+        if self.cfg.distilled:
+            prefix.append(self.dist_token.expand(x.shape[0], -1, -1))
         if self.no_embed_class:
             x = torch.cat(prefix + [x + self.pos_embed], dim=1)
         else:
@@ -301,6 +328,11 @@ class VisionTransformer(nn.Module):
 
     def forward(self, x):
         x = self.forward_features(x)
+        if self.cfg.distilled:     # timm VisionTransformerDistilled.forward_head
+            x, x_dist = self.head(self.head_drop(x[:, 0])), self.head_dist(self.head_drop(x[:, 1]))
+            if self.distilled_training and self.training and not torch.jit.is_scripting():
+                return x, x_dist
+            return (x + x_dist) / 2
         x = x[:, self.num_prefix_tokens:].mean(dim=1) if self.global_pool == "avg" else x[:, 0]
         return self.head(self.head_drop(self.fc_norm(x)))
 
@@ -370,6 +402,10 @@ def synth_state_dict(cfg: ViTConfig, seed: int = 0, std: float = 0.02,
         ln("fc_norm", C)
     if cfg.reg_tokens:      # after every other draw: only pos_embed's row count differs from the register-free config
         sd["reg_token"] = nrm(1, cfg.reg_tokens, C)
+    if cfg.distilled:       # after every other draw too; pos_embed's two extra rows were drawn with it, above
+        sd["dist_token"] = nrm(1, 1, C)
+        sd["head_dist.weight"] = nrm(cfg.num_classes, C)
+        sd["head_dist.bias"] = nrm(cfg.num_classes, s=bias_std) if bias_std else np.zeros(cfg.num_classes, np.float32)
     return sd
 
 

@@ -7,7 +7,9 @@ blocks get a `RAJNIAttention`, every block gets `has_pruner`; model.py:12-23), p
 forward).  Deliberate fixes: schedule keys are normalised to int (B1: a JSON-loaded
 schedule prunes), a `no_embed_class` pos-embed works (B3), and timm's `qk_norm`, `pre_norm`, `global_pool='avg'`
 and `fc_norm` options are computed as timm computes them instead of being dropped (B4), and so are
-timm's register tokens (`reg_tokens=R`: `reg_token` [1, R, C] behind the class token, never pruned, never ranked).
+timm's register tokens (`reg_tokens=R`: `reg_token` [1, R, C] behind the class token, never pruned, never ranked) and
+DeiT's distilled models (timm `VisionTransformerDistilled`: `dist_token` behind the class token, a prefix token like a
+register, and eval logits `(head(x[:, 0]) + head_dist(x[:, 1])) / 2`).
 
 Not kept: the Python per-block loop.  `forward` builds (once per batch shape) a `rajni_vit_plan`
 - packed weights, workspace, per-stage index buffers - and calls `rajni_vit_forward`, which enqueues
@@ -46,16 +48,51 @@ def plan_token_counts(n0: int, depth: int, schedule: Dict[int, Dict], num_prefix
     return counts
 
 
+def model_is_distilled(m: nn.Module) -> bool:
+    """True for timm's VisionTransformerDistilled layout: BOTH `dist_token` [1, 1, C] and `head_dist`, an nn.Linear shaped like
+    `head`, on a token-pooled model without fc_norm or register tokens.  False when the model has neither attribute.  Every
+    half-formed or combined case raises NotImplementedError."""
+    dist, head_dist = getattr(m, "dist_token", None), getattr(m, "head_dist", None)
+    if dist is None and head_dist is None:
+        return False
+    if dist is None or head_dist is None:
+        raise NotImplementedError("RAJNIViTWrapper: a distillation token and head_dist come together (DeiT distilled); the model "
+                                  f"has only {'dist_token' if head_dist is None else 'head_dist'}")
+    if getattr(m, "reg_token", None) is not None:
+        raise NotImplementedError("RAJNIViTWrapper: a distillation token together with register tokens is not supported")
+    Cdim = m.cls_token.shape[-1]
+    if tuple(dist.shape) != (1, 1, Cdim):
+        raise NotImplementedError(f"RAJNIViTWrapper: the distillation token must be [1, 1, {Cdim}], got {tuple(dist.shape)}")
+    head = getattr(m, "head", None)
+    if (not isinstance(head, nn.Linear) or not isinstance(head_dist, nn.Linear) or head_dist.in_features != Cdim
+            or head.in_features != Cdim or head_dist.out_features != head.out_features):
+        raise NotImplementedError("RAJNIViTWrapper: distillation needs head and head_dist to be nn.Linear of one shape "
+                                  f"({Cdim} -> classes)")
+    fc_norm = getattr(m, "fc_norm", None)
+    if getattr(m, "global_pool", "token") != "token" or (fc_norm is not None and not isinstance(fc_norm, nn.Identity)):
+        raise NotImplementedError("RAJNIViTWrapper: distillation needs a token head (global_pool='token', no fc_norm): the two "
+                                  "classifiers read the class row and the distillation row")
+    if getattr(m, "distilled_training", False) and m.training:
+        raise NotImplementedError("RAJNIViTWrapper: distillation training (distilled_training in training mode) returns two "
+                                  "outputs; this is the inference path, which averages them")
+    return True
+
+
 def model_num_prefix(m: nn.Module) -> int:
-    """P = 1 + R prefix tokens the base model's PARAMETERS supply: `cls_token` and `reg_token` [1, R, C] (timm reg_tokens=R).
-    Raises NotImplementedError for what the native forward does not compute (no class token, distillation token, a
-    malformed or oversized register set, a declared `num_prefix_tokens` that disagrees)."""
+    """P prefix tokens the base model's PARAMETERS supply: `cls_token` and `reg_token` [1, R, C] (timm reg_tokens=R, P = 1 + R)
+    or `dist_token` [1, 1, C] (DeiT distilled, P = 2).  Raises NotImplementedError for what the native forward does not
+    compute (no class token, a half-formed distillation pair, a malformed or oversized register set, a declared
+    `num_prefix_tokens` that disagrees)."""
     cls = getattr(m, "cls_token", None)
     if cls is None:
         raise NotImplementedError("RAJNIViTWrapper: the model has no cls_token (class_token=False): the class token is the "
                                   "importance query and is required")
-    if getattr(m, "dist_token", None) is not None or getattr(m, "head_dist", None) is not None:
-        raise NotImplementedError("RAJNIViTWrapper: distillation token / head_dist (DeiT distilled) are not supported")
+    if model_is_distilled(m):
+        declared = getattr(m, "num_prefix_tokens", 2)
+        if declared != 2:
+            raise NotImplementedError(f"RAJNIViTWrapper: the model declares {declared} prefix tokens but a distillation model "
+                                      "has 2 (cls_token + dist_token)")
+        return 2
     reg = getattr(m, "reg_token", None)
     P = 1
     if reg is not None:
@@ -187,6 +224,9 @@ class RAJNIViTWrapper(nn.Module):
         embed dim and MLP width that are multiples of 256."""
         if fmt not in ("model", "fp8", "fp8_mfma"):
             raise ValueError('weight format must be "model", "fp8" or "fp8_mfma"')
+        if fmt == "fp8_mfma" and self._is_distilled():
+            raise NotImplementedError('set_weight_format("fp8_mfma"): not supported on a distillation model (DeiT distilled) '
+                                      'yet; "fp8" weights work')
         if fmt == "fp8_mfma" and self._mlp_act_or_none() == "quick_gelu":
             raise NotImplementedError('set_weight_format("fp8_mfma"): the model\'s MLPs use QuickGELU; the fp8 x fp8 FC1 epilogue '
                                       'and its hidden-activation bound are exact GELU only ("fp8" weights work)')
@@ -218,6 +258,10 @@ class RAJNIViTWrapper(nn.Module):
         tokens, proj / MLP on B rows.  The logits are the same function of the input (the reference's head reads
         x[:, 0] only); the other rows of the last block are never formed.  Off by default: the default forward
         executes the reference's op graph row for row."""
+        if on and self._is_distilled():
+            raise ValueError("set_last_block_cls_only: the model is a distillation model (DeiT distilled) whose head reads two rows; "
+                             "the CLS-only last block forms the class row only (the default forward already computes the last "
+                             "block for those two rows)")
         if on and self._pool_kind() == "avg":
             raise ValueError("set_last_block_cls_only: the model pools with global_pool='avg'; the CLS-only last block never "
                              "forms the rows to be averaged")
@@ -248,6 +292,10 @@ class RAJNIViTWrapper(nn.Module):
         if pool not in ("token", "avg"):
             raise NotImplementedError(f"RAJNIViTWrapper: global_pool={pool!r} is not supported ('token' or 'avg')")
         return pool
+
+    def _is_distilled(self) -> bool:
+        """the base model has the distillation pair, well formed or not (`_describe` reports what is wrong with it)"""
+        return getattr(self.m, "dist_token", None) is not None or getattr(self.m, "head_dist", None) is not None
 
     def _mlp_act_or_none(self) -> Optional[str]:
         """the blocks' MLP activation where they agree on a supported one, else None (`_describe` reports why)"""
@@ -309,6 +357,10 @@ class RAJNIViTWrapper(nn.Module):
             raise NotImplementedError("RAJNIViTWrapper: attn_pool (global_pool='map') is not supported")
         # prefix tokens: the class token plus timm's register tokens (never pruned, never ranked; 'avg' pools behind them)
         desc["num_prefix"] = num_prefix
+        # rows of each image the head reads: 2 = DeiT distilled, the class and distillation rows through two averaged heads
+        desc["head_rows"] = 2 if model_is_distilled(m) else 1
+        if desc["head_rows"] == 2 and self._cls_only_last:
+            raise ValueError("a distillation model with set_last_block_cls_only(True): that opt-in forms the class row only")
         n_patches = getattr(m.patch_embed, "num_patches", None)
         if num_prefix > 1 and isinstance(n_patches, int) and m.pos_embed.shape[-2] not in (n_patches, n_patches + num_prefix):
             raise NotImplementedError(f"RAJNIViTWrapper: pos_embed has {m.pos_embed.shape[-2]} rows; with {num_prefix} prefix tokens "
@@ -380,6 +432,8 @@ class RAJNIViTWrapper(nn.Module):
         desc = self._describe()
         m = self.m
         fp8 = self._weight_format in ("fp8", "fp8_mfma")
+        if self._weight_format == "fp8_mfma" and desc["head_rows"] == 2:
+            raise NotImplementedError('weight format "fp8_mfma" on a distillation model (DeiT distilled) is not supported yet')
         if self._weight_format == "fp8_mfma" and desc["mlp_act"] != "gelu":   # (the activation was swapped after the setter)
             raise NotImplementedError('weight format "fp8_mfma" with a QuickGELU MLP: the fp8 x fp8 FC1 epilogue is exact GELU only')
         if fp8 and dtype != torch.bfloat16:
@@ -393,8 +447,10 @@ class RAJNIViTWrapper(nn.Module):
         W["patch_w"] = ops.pack_weight(m.patch_embed.proj.weight, dtype, device, k_multiple=64)
         W["patch_b"] = pv(m.patch_embed.proj.bias) if m.patch_embed.proj.bias is not None else zeros(desc["C"])
         W["cls"] = m.cls_token.detach().to(device=device, dtype=dtype).reshape(-1).contiguous()
-        W["reg"] = (m.reg_token.detach().to(device=device, dtype=dtype).reshape(-1, desc["C"]).contiguous()
-                    if desc["num_prefix"] > 1 else None)
+        # the prefix rows behind the class token: timm's registers, or the distillation token (one row, the same record)
+        reg_src = m.dist_token if desc["head_rows"] == 2 else (m.reg_token if desc["num_prefix"] > 1 else None)
+        W["reg"] = (reg_src.detach().to(device=device, dtype=dtype).reshape(-1, desc["C"]).contiguous()
+                    if reg_src is not None else None)
         W["pos"] = m.pos_embed.detach().to(device=device, dtype=dtype).reshape(-1, desc["C"]).contiguous()
         W["norm_w"], W["norm_b"] = (pv(m.norm.weight), pv(m.norm.bias)) if desc["norm"] else (None, None)
         if desc["norm"] and W["norm_b"] is None:
@@ -403,8 +459,15 @@ class RAJNIViTWrapper(nn.Module):
             mod = getattr(m, name, None) if desc[name] else None
             W[name + "_w"], W[name + "_b"] = (pv(mod.weight), pv(mod.bias)) if mod is not None else (None, None)
             W[name + "_eps"] = float(mod.eps) if mod is not None else 0.0
-        W["head_w"] = pw(m.head.weight)
-        W["head_b"] = pv(m.head.bias) if m.head.bias is not None else zeros(desc["num_classes"])
+        if desc["head_rows"] == 2:
+            # (head(n0) + head_dist(n1)) / 2 as ONE linear layer over [n0 | n1]: weight [classes, 2C] = [W / 2 | W_dist / 2]
+            # (halving is exact), bias (b + b_dist) / 2 in fp32.  Plain tensors built here, not parameters of the module.
+            W["head_w"] = pw(torch.cat([0.5 * m.head.weight.detach().float(), 0.5 * m.head_dist.weight.detach().float()], dim=1))
+            hb = [pv(h.bias) if h.bias is not None else zeros(desc["num_classes"]) for h in (m.head, m.head_dist)]
+            W["head_b"] = (0.5 * (hb[0] + hb[1])).contiguous()      # the sum of the two held values, not rounded to the model dtype again
+        else:
+            W["head_w"] = pw(m.head.weight)
+            W["head_b"] = pv(m.head.bias) if m.head.bias is not None else zeros(desc["num_classes"])
         blocks = []
         for blk in self.blocks:
             a = blk.attn
@@ -538,6 +601,7 @@ class RAJNIViTWrapper(nn.Module):
         if P > 1:           # the prefix record beside the plan (rajni_vit_prefix); None: CLS only, the entry points as ever
             pre = nat.VitPrefix()
             pre.num_prefix, pre.reg_token = P, W["reg"].data_ptr()
+            pre.head_rows = 2 if d["head_rows"] == 2 else 0      # (register models: the record as it always was)
         nbytes = (nat.lib().rajni_vit_workspace_bytes(C.byref(plan)) if pre is None
                   else nat.lib().rajni_vit_workspace_bytes_prefix(C.byref(plan), C.byref(pre)))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
