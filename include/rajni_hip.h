@@ -47,11 +47,21 @@ enum {
   RAJNI_EPI_BIAS_RESID = 2,/* y = resid[row or gathered row] + gamma*(x W^T + b)
                               attention.py:55 + model.py:55-58 (proj, gather x, ls1, add);
                               model.py:59 (mlp.fc2, ls2, add)                                       */
-  RAJNI_EPI_BIAS_QUICK_GELU = 16 /* y = quick_gelu(x W^T + b), quick_gelu(v) = v * sigmoid(1.702 v): the MLP activation of the
+  RAJNI_EPI_BIAS_QUICK_GELU = 16,/* y = quick_gelu(x W^T + b), quick_gelu(v) = v * sigmoid(1.702 v): the MLP activation of the
                               OpenAI CLIP, MetaCLIP and DFN towers.  BIAS_GELU in every other respect (output type, tilings,
                               profile class); bf16, fp16, fp32 and fp8 WEIGHTS.  With x_scale (fp8 x fp8) it is
                               RAJNI_ERR_UNSUPPORTED: the re-quantising e4m3 epilogue exists for exact GELU only.
-                              Codes 3..15 and >= 17 are unknown.                                       */
+                              Codes 3..15, 17 and >= 19 are unknown.                                      */
+  RAJNI_EPI_BIAS_SWIGLU = 18 /* y[M, N] = silu(x Wg^T + bg) * (x Wv^T + bv), silu(t) = t * sigmoid(t): the gated FC1 of timm's
+                              GluMlp(act_layer=nn.SiLU, gate_last=False) / SwiGLUPacked (the DINOv2 giant ViTs).  w is
+                              [2N, K]: row n is the gate of output column n, row N + n its value (timm's packed order);
+                              it is allocated with 2N padded up to a multiple of 256 rows, which always covers the last
+                              value tile (N + roundup(N, 128) <= roundup(2N, 256)).  bias and w_scale are [2N] in the
+                              same order; ldc >= N; N <= 2^30.  Evaluated in fp32 on the accumulators, rounded once to
+                              `dtype`; a finite (gate, value) never gives NaN and silu(0) * 0 = 0.  bf16, fp16, fp32 and
+                              fp8 WEIGHTS; output type, store path and profile class are BIAS_GELU's.  With x_scale
+                              (fp8 x fp8) it is RAJNI_ERR_UNSUPPORTED: the re-quantising e4m3 epilogue exists for exact
+                              GELU only.                                                                */
 };
 
 /* ---- addressing limits ----
@@ -326,7 +336,7 @@ int rajni_layernorm_stream(void* x, const float* w, const float* b, int rows, in
  * tokens that SURVIVED pruning (what timm computes on whatever token set reaches the head), summed in a fixed order
  * in fp32.  norm_w == NULL / fc_w == NULL: that norm is nn.Identity.  C % 8 == 0, C <= 2048. */
 enum { RAJNI_POOL_TOKEN = 0, RAJNI_POOL_AVG = 1 };
-enum { RAJNI_MLP_GELU = 0, RAJNI_MLP_QUICK_GELU = 1 };   /* rajni_vit_ext.mlp_act */
+enum { RAJNI_MLP_GELU = 0, RAJNI_MLP_QUICK_GELU = 1, RAJNI_MLP_SWIGLU = 3 };   /* rajni_vit_ext.mlp_act */
 int rajni_pool_norm(const void* x, int B, int N, int C, int pool, const float* norm_w, const float* norm_b,
                     float norm_eps, const float* fc_w, const float* fc_b, float fc_eps, void* out, int dtype, int x_f32,
                     rajni_stream_t stream);
@@ -352,7 +362,11 @@ typedef struct {
                                        record without it passes zeroed or ignored padding - callers zero the record, "an
                                        all-zero record is the plain forward" - and gets exact GELU as before.  Hence
                                        RAJNI_ABI_VERSION does not move.  Any other value is RAJNI_ERR_INVALID; QUICK_GELU with
-                                       plan.act_fp8 is RAJNI_ERR_UNSUPPORTED (see RAJNI_EPI_BIAS_QUICK_GELU) */
+                                       plan.act_fp8 is RAJNI_ERR_UNSUPPORTED (see RAJNI_EPI_BIAS_QUICK_GELU).
+                                       RAJNI_MLP_SWIGLU (3; 2 is unknown): every block's FC1 is gated (RAJNI_EPI_BIAS_SWIGLU).  plan.hidden
+                                       stays FC2's K and the hidden buffer's width; rajni_block.fc1_w is [2 * hidden (pad
+                                       256), C] - gate rows, then value rows - and fc1_b / fc1_s are [2 * hidden].  The
+                                       workspace carve does not change.  With plan.act_fp8 it is RAJNI_ERR_UNSUPPORTED */
 } rajni_vit_ext;
 
 /* rajni_vit_forward with the options of `ext` (NULL or all zero: exactly the launches of rajni_vit_forward).

@@ -141,8 +141,12 @@ int check_ext(const rajni_vit_plan& p, const rajni_vit_ext& e) {
     }
   RAJNI_REQUIRE_PLACED("rajni_vit_forward_ext", {"norm_pre_w", e.norm_pre_w, 16}, {"norm_pre_b", e.norm_pre_b, 16},
                        {"fc_norm_w", e.fc_norm_w, 16}, {"fc_norm_b", e.fc_norm_b, 16});
-  RAJNI_REQUIRE(e.mlp_act == RAJNI_MLP_GELU || e.mlp_act == RAJNI_MLP_QUICK_GELU, RAJNI_ERR_INVALID,
+  // (RAJNI_MLP_SWIGLU, the gated FC1, is the third legal value; the wording of this refusal is what callers match on)
+  RAJNI_REQUIRE(e.mlp_act == RAJNI_MLP_GELU || e.mlp_act == RAJNI_MLP_QUICK_GELU || e.mlp_act == RAJNI_MLP_SWIGLU, RAJNI_ERR_INVALID,
                 "rajni_vit_forward_ext: mlp_act must be RAJNI_MLP_GELU or RAJNI_MLP_QUICK_GELU (%d)", e.mlp_act);
+  RAJNI_REQUIRE(!(e.mlp_act == RAJNI_MLP_SWIGLU && p.act_fp8), RAJNI_ERR_UNSUPPORTED,
+                "rajni_vit_forward_ext: a SwiGLU MLP (mlp_act) is unsupported with act_fp8 - the fp8 x fp8 FC1 epilogue and its "
+                "hidden-activation bound are exact GELU only");
   RAJNI_REQUIRE(!(e.mlp_act != RAJNI_MLP_GELU && p.act_fp8), RAJNI_ERR_UNSUPPORTED,
                 "rajni_vit_forward_ext: a QuickGELU MLP (mlp_act) is unsupported with act_fp8 - the fp8 x fp8 FC1 epilogue and its "
                 "hidden-activation bound are exact GELU only");
@@ -200,7 +204,8 @@ rajni_linear_args proj_args(const Fwd& f, const rajni_block& blk, const AttnRows
   if (r.idx) { g.r_idx = r.idx; g.r_np = r.np; g.r_nsrc = r.nsrc; }
   return g;
 }
-// MLP (model.py:59): fc1 + GELU (or the QuickGELU of ext.mlp_act); act_fp8: e4m3 in, e4m3 out (per-row scales)
+// MLP (model.py:59): fc1 + GELU (or the QuickGELU / gated SwiGLU of ext.mlp_act: N = hidden is the OUTPUT width either way,
+// the gated fc1_w has 2 * hidden rows); act_fp8: e4m3 in, e4m3 out (per-row scales)
 rajni_linear_args fc1_args(const Fwd& f, const rajni_block& blk, int M) {
   rajni_linear_args g = linear_args(f.p.dtype, f.w.xn, blk.fc1_w, blk.fc1_b, blk.fc1_s, f.w.hid, M, f.p.hidden, f.p.C, f.fc1_epi);
   if (f.p.act_fp8) { g.x_scale = f.w.xs; g.y_scale = f.w.hs; }
@@ -380,7 +385,8 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
                 "rajni_vit_forward: workspace too small (%zu < %zu)", p.workspace_bytes, w.total);
   const int B = p.B, C = p.C, dt = p.dtype;
   const Fwd f{p, w, (dt != RAJNI_F32 && !p.resid_bf16) ? 1 : 0, s,
-              (ext && ext->mlp_act == RAJNI_MLP_QUICK_GELU) ? RAJNI_EPI_BIAS_QUICK_GELU : RAJNI_EPI_BIAS_GELU};
+              (ext && ext->mlp_act == RAJNI_MLP_QUICK_GELU) ? RAJNI_EPI_BIAS_QUICK_GELU
+              : (ext && ext->mlp_act == RAJNI_MLP_SWIGLU) ? RAJNI_EPI_BIAS_SWIGLU : RAJNI_EPI_BIAS_GELU};
   int N = tokens_entering(p, P, 0);
 
   rc = launch_patch_embed(images, p.patch_w, p.patch_b, p.cls_token, p.pos_embed, p.pos_has_cls,

@@ -32,9 +32,13 @@ namespace {
 
 enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_PATCH = 3,
        EPI_GELU8 = 4,     // fp8 x fp8 kernel only (gemm_f8.h): bias + GELU, output re-quantised to e4m3 with a per-row scale
-       EPI_QGELU = 5 };   // bias + QuickGELU: EPI_GELU in everything but the function applied (see epi_act)
+       EPI_QGELU = 5,     // bias + QuickGELU: EPI_GELU in everything but the function applied (see epi_act)
+       EPI_SWIGLU = 6 };  // gated FC1: W is [2N, K] (gate rows, then value rows), the output silu(gate) * value is [M, N] (see gated_w_row)
 // The activation epilogues of the 16-bit and fp32 kernels: a 16-bit (or fp32) output in the bias epilogue's column order and
-// store path, FC1's non-temporal hidden store, the profile class KC_GEMM_GELU.  Whatever asks "is this FC1's epilogue" asks here.
+// store path, FC1's non-temporal hidden store, the profile class KC_GEMM_GELU.  Whatever asks "is this an UNGATED FC1 epilogue"
+// asks here.  (EPI_SWIGLU is FC1's epilogue too and is NOT one of these on purpose: it has a tail of its own, epilogue_tile_gated -
+// half as many output columns, no TSTORE scratch - and names its non-temporal store, its store count (tile_stores) and its
+// profile class where they are decided.)
 constexpr bool epi_act(int epi) { return epi == EPI_GELU || epi == EPI_QGELU; }
 enum { ALOAD_PLAIN = 0, ALOAD_PATCH = 1 };
 
@@ -121,6 +125,36 @@ __device__ __forceinline__ float quick_gelu1(float x) {
 // (The two sites that apply an activation - epilogue_row and the interior path of epilogue_tile - keep the GELU loop spelled
 //  out as it always was, with the QuickGELU loop beside it: routed through one shared helper, hipcc allocated the GELU
 //  kernels' registers differently, and every kernel that existed before QuickGELU is held to identical machine code.)
+
+// SiLU, the gate of the SwiGLU epilogue (EPI_SWIGLU): quick_gelu1 with the constant -log2(e), t * rcp(1 + exp2(-log2(e) t)).
+// The ends behave as described there (silu(-huge) = -0, silu(0) = 0 exactly, no clamp), and the product silu(g) * v adds no
+// case: silu(g) is finite for every finite g, so with v finite no 0 * inf can form - a finite (g, v) never yields NaN, and
+// silu(0) * 0 = 0 keeps the zero-padded hidden columns zero.
+__device__ __forceinline__ float silu1(float x) {
+  return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
+}
+
+// ---- EPI_SWIGLU: the gated FC1.  W is [2N, K]: row n is the gate of hidden column n, row N + n its value; the output is
+// [M, N].  A tile of BN W rows covers BN / 2 hidden columns, and the permutation that puts a column's gate and value into ONE
+// lane sits in the tile LOADER alone: LDS tile row L is filled from the global W row gated_w_row(L) below, everything behind
+// the loader - the LDS image, the swizzle keys (functions of the LDS row L only), w_frag_row and MAP_SEC - is what the bias
+// epilogue has.  The LDS-DMA writes lane-linear and the swizzle is applied to the SOURCE chunk of a row, so which global row
+// a piece's lanes read changes nothing in LDS: the conflict argument of w_key / w_key8 holds unchanged, row for row.
+//   16-bit tilings: wave wn owns LDS rows 64 wn .. 64 wn + 63.  Its first 32 rows are the gates of hidden columns
+//   h0 + 32 wn .. + 31 (h0 = first hidden column of the tile), its last 32 rows their values.  Under MAP_SEC a lane's v[j]
+//   is tile column 64 wn + 8 g + j and v[8 + j] tile column 64 wn + 32 + 8 g + j: the gate and the value of hidden column
+//   h0 + 32 wn + 8 g + j.  The product needs no exchange, the lane writes 8 consecutive outputs as one 16-byte store and
+//   the 4 lanes of a row one whole 64-byte sector.
+//   fp32 tiling: a lane owns the 16 consecutive tile columns 64 wn + 16 g .. + 15 - the first 8 are gates, the last 8 values.
+// A staging piece is 8 (16-bit, fp32) or 16 (fp8 weights) consecutive LDS rows starting at a multiple of its size, so it never
+// straddles a gate / value boundary of either layout: its lanes' rows stay consecutive global rows.
+// Rows read: gates [h0, h0 + BN/2) - past N for a ragged last tile, into the value rows, never stored - and values
+// [N + h0, N + h0 + BN/2) <= N + roundup(N, 128) <= roundup(2N, 256), the padded allocation of W (include/rajni_hip.h).
+template <bool F32>
+__device__ __forceinline__ long gated_w_row(int L, int N, int h0) {
+  if (F32) return (long)((L >> 3) & 1) * N + h0 + (L >> 6) * 32 + ((L >> 4) & 3) * 8 + (L & 7);
+  return (long)((L >> 5) & 1) * N + h0 + (L >> 6) * 32 + (L & 31);
+}
 
 // load / store 16 consecutive stream elements (the 16-bit activation format A, or fp32) as floats
 template <bool F32, typename A>
@@ -481,6 +515,7 @@ constexpr int stores_acc_layout(bool nat, int mi) { return (nat ? 4 : 2) * mi; }
 constexpr int stores_rowmajor(int mi) { return 2 * 2 * mi; }   // ROWMAJOR, ROWMAJOR_WIDE: per row group 2 column halves x 2 x (8 rows x 128 bytes)
 constexpr int stores_tstore(int mi) { return 2 * mi; }         // TSTORE: per row group 2 x (8 rows x 128 bytes)
 constexpr int tile_stores(int epi, bool sf32, int mi, bool rowmajor, bool tstore) {   // the fewest over the instantiation's paths
+  if (epi == EPI_SWIGLU) return mi;                      // epilogue_tile_gated: one 16-byte store per row group
   int n = stores_acc_layout(nat_order(epi, sf32), mi);   // the path every instantiation has (no scratch, gathered rows)
   if (rowmajor && stores_rowmajor(mi) < n) n = stores_rowmajor(mi);
   if (tstore && stores_tstore(mi) < n) n = stores_tstore(mi);
@@ -727,6 +762,62 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, f32x4 (&acc)[
     else epilogue_row<EPI, SF32, A>(p, m, n0w + 8 * g, n0w + 32 + 8 * g, v, gam);
   }
 }
+// EPI_SWIGLU tail of every 16-bit tiling (see gated_w_row): hw = the wave's first hidden column; the lane's accumulators of
+// n-tiles 0, 1 are the gates and of n-tiles 2, 3 the values of hidden columns hw + 8 g .. + 7.  fp8 weights dequantise inside
+// the bias add with the one fmaf(acc, scale, bias) every path uses, the gate with row n's scale and the value with row N + n's.
+// Stored non-temporal like FC1's GELU output (RAJNI_FC1_NT): an interior tile issues MI 16-byte stores per wave (tile_stores).
+// `interior` additionally means N % 4 == 0, so that the value half of bias / w_scale is 16-byte aligned like the gate half.
+template <typename A, int MI, bool W8>
+__device__ __forceinline__ void epilogue_tile_gated(const GemmParams& p, f32x4 (&acc)[4][MI], int m_base, int hw,
+                                                    int l15, int g, int m_lo, bool interior) {
+  const int hc = hw + 8 * g;
+  A* Y = reinterpret_cast<A*>(p.Y);
+  float bs[16], ws[16];   // [0..7] gate, [8..15] value
+#pragma unroll
+  for (int j = 0; j < 16; ++j) { bs[j] = 0.f; ws[j] = 1.f; }
+  if (interior) {
+    if (p.bias != nullptr) {
+      load8<float>(p.bias + hc, bs);
+      load8<float>(p.bias + (long)p.N + hc, bs + 8);
+    }
+    if constexpr (W8) {
+      load8<float>(p.wscale + hc, ws);
+      load8<float>(p.wscale + (long)p.N + hc, ws + 8);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const bool in = hc + j < p.N;
+      if (p.bias != nullptr && in) { bs[j] = p.bias[hc + j]; bs[8 + j] = p.bias[(long)p.N + hc + j]; }
+      if constexpr (W8) {
+        if (in) { ws[j] = p.wscale[hc + j]; ws[8 + j] = p.wscale[(long)p.N + hc + j]; }
+      }
+    }
+  }
+  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) on every path: see the note in epilogue_tile
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    const int m = m_base + mi * 16 + l15;
+    if (!interior && (m >= p.M || m < m_lo)) continue;
+    float o[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int ni = j >> 2, rg = j & 3;
+      const float gt = W8 ? fmaf(acc[ni][mi][rg], ws[j], bs[j]) : acc[ni][mi][rg] + bs[j];
+      const float vl = W8 ? fmaf(acc[2 + ni][mi][rg], ws[8 + j], bs[8 + j]) : acc[2 + ni][mi][rg] + bs[8 + j];
+      o[j] = silu1(gt) * vl;
+    }
+    A* row = Y + (long)m * p.ldc + hc;
+    if (interior || hc + 8 <= p.N) {
+      store_u4<RAJNI_FC1_NT>(row, pack8<A>(o));
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (hc + j < p.N) st1(row + j, o[j]);
+    }
+  }
+}
+
 // XCD-aware tile id: blocks b and b+8 share an XCD; give each XCD a contiguous range of tiles
 __device__ __forceinline__ int xcd_tile_of(int v, int total) {
   const int q = total >> 3, r = total & 7, xcd = v & 7, loc = v >> 3;
@@ -833,6 +924,9 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_bf16_tn_stream(const Gem
   constexpr int NI = 4;                        // 16-column n-tiles per wave
   using WFrag = typename WFragT<W8>::type;   // a W fragment as it sits in LDS: 8 bf16, or 8 fp8 bytes
   constexpr int MAP = col_map(EPI, SF32);      // W-row permutation = which output columns a lane owns
+  constexpr bool GATED = EPI == EPI_SWIGLU;    // W rows come from two ranges (gated_w_row); a tile has BN / 2 output columns
+  constexpr int BNO = GATED ? C::BN / 2 : C::BN;
+  static_assert(!GATED || C::PW <= C::NPW, "the gated loader has one pointer per W piece: no fixed 32-row stride between pieces");
   static_assert(WM * WN == 8 && WM * MI * 16 == BM, "8 waves covering 256 rows");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -896,10 +990,12 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_bf16_tn_stream(const Gem
     for (int i = 0; i < C::NPW; ++i) {
       if constexpr (W8) {
         const int row = (wave * C::PW + i) * 16 + (lane >> 2);
-        ws[i] = reinterpret_cast<const char*>(p.W) + (long)(tn * C::BN + row) * p.ldw + (((lane & 3) ^ w_key8<MAP>(row)) << 4);
+        const long grow = GATED ? gated_w_row<false>(row, p.N, tn * BNO) : (long)(tn * C::BN + row);
+        ws[i] = reinterpret_cast<const char*>(p.W) + grow * p.ldw + (((lane & 3) ^ w_key8<MAP>(row)) << 4);
       } else {
         const int row = (wave * C::PW + i) * 8 + r_in;
-        ws[i] = reinterpret_cast<const char*>(p.W) + ((long)(tn * C::BN + row) * p.ldw + (pch ^ w_key<MAP>(row)) * 8) * 2;
+        const long grow = GATED ? gated_w_row<false>(row, p.N, tn * BNO) : (long)(tn * C::BN + row);
+        ws[i] = reinterpret_cast<const char*>(p.W) + (grow * p.ldw + (pch ^ w_key<MAP>(row)) * 8) * 2;
       }
     }
   };
@@ -909,7 +1005,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_bf16_tn_stream(const Gem
       tile_mn(from, tm0, tn0);
       tile_mn(to, tm1, tn1);
       const long dx = (long)(tile_m0(tm1) - tile_m0(tm0)) * p.lda * 2;
-      const long dw = (long)(tn1 - tn0) * C::BN * p.ldw * C::WB;
+      const long dw = (long)(tn1 - tn0) * BNO * p.ldw * C::WB;   // gated: both row ranges move by the tile's BN / 2 hidden columns
       xp[0] += dx; xp[1] += dx;
 #pragma unroll
       for (int i = 0; i < C::NPW; ++i) ws[i] += dw;
@@ -1003,6 +1099,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_bf16_tn_stream(const Gem
   auto interior = [&](int t) {   // a tile whose 256 rows and BN columns all exist
     int tm_, tn_;
     tile_mn(t, tm_, tn_);
+    if constexpr (GATED) return tm_ * BM + BM <= p.M && tn_ * BNO + BNO <= p.N && (p.N & 3) == 0;   // see epilogue_tile_gated
     return tm_ * BM + BM <= p.M && tn_ * C::BN + C::BN <= p.N;
   };
   ResidPrefetch<MI> pre;
@@ -1068,8 +1165,11 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_bf16_tn_stream(const Gem
 #endif
 
     // ---- epilogue (the next tile's first loads are in flight)
-    epilogue_tile<A, EPI, SF32, MI, W8>(p, acc, m0 + wm * (MI * 16), n0 + wn * 64, l15, g, pre, m_lo, inter,
-                                     SCRATCH > 0 ? smem + C::LDS_BYTES + wave * SCRATCH : nullptr);
+    if constexpr (GATED)
+      epilogue_tile_gated<A, MI, W8>(p, acc, m0 + wm * (MI * 16), tn * BNO + wn * 32, l15, g, m_lo, inter);
+    else
+      epilogue_tile<A, EPI, SF32, MI, W8>(p, acc, m0 + wm * (MI * 16), n0 + wn * 64, l15, g, pre, m_lo, inter,
+                                       SCRATCH > 0 ? smem + C::LDS_BYTES + wave * SCRATCH : nullptr);
 #ifdef RAJNI_GEMM_STAMPS
     if (p.stamps != nullptr && wave == 0) {
       const unsigned long long ts3 = __builtin_amdgcn_s_memtime();
@@ -1104,6 +1204,7 @@ template <int EPI, int ALOAD, bool SF32, bool W8 = false, typename A = bf16_t>
 __global__ void __launch_bounds__(256, 2) gemm_bf16_tn_128x128(const GemmParams p) {
   constexpr int MAP = col_map(EPI, SF32);      // W-row permutation = which output columns a lane owns
   constexpr int PW = W8 ? 2 : 4;               // W pieces per wave per K step (fp8 tile is 8 KiB)
+  constexpr bool GATED = EPI == EPI_SWIGLU;    // W rows come from two ranges (gated_w_row); a tile has BN / 2 output columns
   using WFrag = typename WFragT<W8>::type;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1127,10 +1228,12 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_tn_128x128(const GemmParams 
   for (int i = 0; i < PW; ++i) {
     if constexpr (W8) {
       const int row = (wave * PW + i) * 16 + (lane >> 2);
-      ws[i] = reinterpret_cast<const char*>(p.W) + (long)(n0 + row) * p.ldw + (((lane & 3) ^ w_key8<MAP>(row)) << 4);
+      const long grow = GATED ? gated_w_row<false>(row, p.N, tn * (BN / 2)) : (long)(n0 + row);
+      ws[i] = reinterpret_cast<const char*>(p.W) + grow * p.ldw + (((lane & 3) ^ w_key8<MAP>(row)) << 4);
     } else {
       const int row = (wave * PW + i) * 8 + r_in;
-      ws[i] = reinterpret_cast<const char*>(p.W) + ((long)(n0 + row) * p.ldw + (pch ^ w_key<MAP>(row)) * 8) * 2;
+      const long grow = GATED ? gated_w_row<false>(row, p.N, tn * (BN / 2)) : (long)(n0 + row);
+      ws[i] = reinterpret_cast<const char*>(p.W) + (grow * p.ldw + (pch ^ w_key<MAP>(row)) * 8) * 2;
     }
   }
   auto stage = [&](int kt, int buf) {
@@ -1193,7 +1296,8 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_tn_128x128(const GemmParams 
     }
   }
 
-  epilogue_tile<A, EPI, SF32, 4, W8>(p, acc, m0 + wm * 64, n0 + wn * 64, l15, g, pre);
+  if constexpr (GATED) epilogue_tile_gated<A, 4, W8>(p, acc, m0 + wm * 64, tn * (BN / 2) + wn * 32, l15, g, 0, false);
+  else epilogue_tile<A, EPI, SF32, 4, W8>(p, acc, m0 + wm * 64, n0 + wn * 64, l15, g, pre);
 }
 }  // namespace small
 
@@ -1271,7 +1375,8 @@ __global__ void __launch_bounds__(256, 2) gemm_f32_tn_128x128(const GemmParams p
     int m = m0 + row;
     if (m > p.M - 1) m = p.M - 1;
     xs[i].init(p, m, pch ^ key_x(row));
-    ws[i] = W + (long)(n0 + row) * p.ldw + (pch ^ key_w(row)) * 4;
+    const long grow = EPI == EPI_SWIGLU ? gated_w_row<true>(row, p.N, tn * (BN / 2)) : (long)(n0 + row);
+    ws[i] = W + grow * p.ldw + (pch ^ key_w(row)) * 4;
   }
   auto stage = [&](int kt, int buf) {
     char* sx = smem + buf * STAGE_BYTES;
@@ -1328,6 +1433,39 @@ __global__ void __launch_bounds__(256, 2) gemm_f32_tn_128x128(const GemmParams p
     }
   }
 
+  if constexpr (EPI == EPI_SWIGLU) {
+    // the lane's tile columns 16 g .. + 7 are the gates and 16 g + 8 .. + 15 the values of hidden columns hc .. hc + 7
+    // (gated_w_row<true>).  This kernel's GELU rule: accurate expf and a true division; expf -> +inf for large -g gives
+    // g / inf = -0, and -0 * v = +-0 for finite v - never NaN
+    const int hc = tn * (BN / 2) + wn * 32 + 8 * g;
+    float bg[8], bv[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const bool in = p.bias != nullptr && hc + j < p.N;
+      bg[j] = in ? p.bias[hc + j] : 0.f;
+      bv[j] = in ? p.bias[(long)p.N + hc + j] : 0.f;
+    }
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+      const int m = m0 + wm * 64 + mi * 16 + l15;
+      if (m >= p.M) continue;
+      float o[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float gt = acc[j >> 2][mi][j & 3] + bg[j], vl = acc[2 + (j >> 2)][mi][j & 3] + bv[j];
+        o[j] = gt / (1.0f + expf(-gt)) * vl;
+      }
+      float* yr = reinterpret_cast<float*>(p.Y) + (long)m * p.ldc + hc;
+      if (hc + 8 <= p.N) {
+        store8<float>(yr, o);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (hc + j < p.N) yr[j] = o[j];
+      }
+    }
+    return;
+  }
   const int nb = n0 + wn * 64 + 16 * g;
   float bias[16], gam[16];
 #pragma unroll
@@ -1443,12 +1581,15 @@ struct TileTraits {
   int lds_wide, lds_narrow;   // dynamic LDS of the 256 x 256 / 256 x 128 kernel (lds_wide = 0: there is no 256 x 256 kernel)
 };
 // tiles of bm x bn.  bm = 256: a persistent stream (grid <= cus) whose tile order runs in N blocks of W, wbytes per element;
-// otherwise one workgroup per tile in the plain order
-rajni_linear_plan make_plan(const GemmParams& p, int tiling, int bm, int bn, int lds, int cus = 0, int wbytes = 0, int nblk_bytes = 0) {
+// otherwise one workgroup per tile in the plain order.  A gated launch (EPI_SWIGLU) computes [M, K] x [2N, K]^T: a tile
+// still stages bn rows of W - which is what the N blocks are sized by - but covers bn / 2 of the N output columns
+rajni_linear_plan make_plan(const GemmParams& p, int tiling, int bm, int bn, int lds, int cus = 0, int wbytes = 0, int nblk_bytes = 0,
+                            bool gated = false) {
   const int tiles_m = (p.M + bm - 1) / bm;
+  const int bno = gated ? bn / 2 : bn;
   rajni_linear_plan c{};
   c.tiling = tiling; c.lds_bytes = lds;
-  c.tiles_n = (p.N + bn - 1) / bn;
+  c.tiles_n = (p.N + bno - 1) / bno;
   c.grid = c.total_tiles = c.tiles_n * tiles_m;
   if (bm == 256) {
     c.nblk = n_block(c.tiles_n, tiles_m, bn, p.K, wbytes, cus, nblk_bytes);
@@ -1460,6 +1601,9 @@ rajni_linear_plan make_plan(const GemmParams& p, int tiling, int bm, int bn, int
 // 16-bit activations (wide / mid / small); `force` = rajni_debug_force_gemm_tiling
 rajni_linear_plan choose_gemm(const GemmParams& p, const TileTraits& r, int cus, int force, int nblk_bytes) {
   int mode = force;
+  // the shape rule sees the GEMM that is computed: a gated launch has 2N columns of W
+  const bool gated = r.epi == EPI_SWIGLU;
+  const int wn = gated ? 2 * p.N : p.N;
   if ((mode == 4 || mode == 5) && p.M < 256) mode = 1;   // stream tiles may start at M - 256
   if (mode == 4 && p.K < 192) mode = 1;                   // the persistent streams need >= NS + 1 K steps
   if (mode == 5 && p.K < 256) mode = 1;
@@ -1473,14 +1617,14 @@ rajni_linear_plan choose_gemm(const GemmParams& p, const TileTraits& r, int cus,
     //   N = 768-class outputs (proj, fc2): 591 tiles of 256x256 make 2.3 rounds on 256 CUs, the
     //   persistent 256x128 3-stage tiling is best (proj 125 us, fc2 284 us vs 127 / 310 for 128x128);
     //   small problems (head, tiny batches): 128x128.
-    if (p.M >= 1024 && p.N >= 1536 && p.K >= 192) mode = 4;
-    else if (p.M >= 1024 && p.K >= 256) mode = (p.K > p.N && p.K >= 1536 && wide_wins_on_rounds(p.M, p.N, cus)) ? 4 : (mid_ok ? 5 : 1);
+    if (p.M >= 1024 && wn >= 1536 && p.K >= 192) mode = 4;
+    else if (p.M >= 1024 && p.K >= 256) mode = (p.K > wn && p.K >= 1536 && wide_wins_on_rounds(p.M, wn, cus)) ? 4 : (mid_ok ? 5 : 1);
     else mode = 1;
   }
   // W blocks of the tile order: fp8 W gets the same blocks as bf16 (measured), hence 2 bytes per element
-  if (mode == 4) return make_plan(p, RAJNI_TILING_WIDE, 256, 256, r.lds_wide, cus, 2, nblk_bytes);
-  if (mode == 5) return make_plan(p, RAJNI_TILING_MID, 256, 128, r.lds_narrow, cus, 2, nblk_bytes);
-  return make_plan(p, RAJNI_TILING_SMALL, 128, 128, small::LDS_BYTES);
+  if (mode == 4) return make_plan(p, RAJNI_TILING_WIDE, 256, 256, r.lds_wide, cus, 2, nblk_bytes, gated);
+  if (mode == 5) return make_plan(p, RAJNI_TILING_MID, 256, 128, r.lds_narrow, cus, 2, nblk_bytes, gated);
+  return make_plan(p, RAJNI_TILING_SMALL, 128, 128, small::LDS_BYTES, 0, 0, 0, gated);
 }
 
 // fp8 x fp8 (gemm_f8.h), persistent: 256 x 256 for wide outputs without a residual epilogue (QKV, FC1), 256 x 128
@@ -1518,6 +1662,8 @@ int g_resid_stagger = 1;
 // gemm_bf16_tn_stream), the stream - and, for rajni_debug_linear_plan, the CU count to plan for (0: the current device's)
 // and where the plan goes INSTEAD of a launch.
 struct LaunchCtl { int kclass; bool sq; hipStream_t s; int cus; rajni_linear_plan* plan_only; };
+// W rows per output column: 2 for the gated epilogue (its flop and byte counts are those of the [2N, K] W it multiplies by)
+constexpr int w_rows_per_col(int epi) { return epi == EPI_SWIGLU ? 2 : 1; }
 inline int cus_of(const LaunchCtl& l) { return l.cus > 0 ? l.cus : rajni_num_cus(); }
 
 // Launch `Kernel` as planned - the one launch of every GEMM kernel.  hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per
@@ -1525,7 +1671,8 @@ inline int cus_of(const LaunchCtl& l) { return l.cus > 0 ? l.cus : rajni_num_cus
 // drive several GPUs; one process per GPU is the deployment, but a model on cuda:1 in a process whose first launch was on
 // cuda:0 must not inherit that device's "done").
 template <auto Kernel>
-int launch_planned(const rajni_linear_plan& c, int threads, GemmParams& p, const LaunchCtl& l, double bytes, const char* name) {
+int launch_planned(const rajni_linear_plan& c, int threads, GemmParams& p, const LaunchCtl& l, double bytes, const char* name,
+                   int wrows = 1) {
   if (l.plan_only != nullptr) { *l.plan_only = c; return RAJNI_OK; }   // the dry run ends here, ahead of every HIP call
   static bool done_by_device[RAJNI_MAX_DEVICES] = {};
   bool& done = done_by_device[rajni_current_device()];
@@ -1538,14 +1685,14 @@ int launch_planned(const rajni_linear_plan& c, int threads, GemmParams& p, const
     done = true;
   }
   p.tiles_n = c.tiles_n; p.total_tiles = c.total_tiles; p.nblk = c.nblk;
-  ProfScope prof(l.kclass, l.s, 2.0 * p.M * (double)p.N * p.K, bytes);
+  ProfScope prof(l.kclass, l.s, 2.0 * p.M * (double)p.N * p.K * wrows, bytes);
   hipLaunchKernelGGL(Kernel, dim3(c.grid), dim3(threads), c.lds_bytes, l.s, p);
   RAJNI_CHECK_LAUNCH(name);
   return RAJNI_OK;
 }
 // algorithmic bytes: X + W + output (+ the residual rows read), each at its element size - fp32 where the residual stream is
-inline double gemm_bytes(const GemmParams& p, double xsz, double wsz, double ysz) {
-  return xsz * (double)p.M * p.K + ysz * (double)p.M * p.N + wsz * (double)p.N * p.K;
+inline double gemm_bytes(const GemmParams& p, double xsz, double wsz, double ysz, int wrows = 1) {   // gated: 2N W rows, N output columns
+  return xsz * (double)p.M * p.K + ysz * (double)p.M * p.N + wsz * (double)p.N * p.K * wrows;
 }
 constexpr double out_bytes(int epi, bool sf32) {   // per output element of the 16-bit and fp8 x fp8 families
   const double ysz = epi == EPI_GELU8 ? 1.0 : (sf32 && (epi == EPI_RESID || epi == EPI_PATCH)) ? 4.0 : 2.0;
@@ -1557,7 +1704,8 @@ template <int EPI, int ALOAD, bool SF32, bool W8, typename A, int WM, int WN, in
 int launch_stream(const rajni_linear_plan& c, GemmParams& p, const LaunchCtl& l, double bytes) {
   if constexpr (EPI == EPI_RESID)
     if (l.sq) return launch_planned<&wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, WM, WN, MI, NS, W8, 1, A>>(c, 512, p, l, bytes, "gemm_bf16_tn");
-  return launch_planned<&wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, WM, WN, MI, NS, W8, 0, A>>(c, 512, p, l, bytes, "gemm_bf16_tn");
+  return launch_planned<&wide::gemm_bf16_tn_stream<EPI, ALOAD, SF32, WM, WN, MI, NS, W8, 0, A>>(c, 512, p, l, bytes, "gemm_bf16_tn",
+                                                                                              w_rows_per_col(EPI));
 }
 template <int EPI, int ALOAD, bool SF32, bool W8 = false, typename A = bf16_t>
 int launch_gemm(GemmParams& p, const LaunchCtl& l) {
@@ -1566,10 +1714,10 @@ int launch_gemm(GemmParams& p, const LaunchCtl& l) {
   const rajni_linear_plan c = choose_gemm(p, T, cus_of(l), g_force_tiling, g_nblk_bytes);
   p.stamps = rajni_g_stamps;
   p.stagger = g_resid_stagger;
-  const double bytes = gemm_bytes(p, 2.0, W8 ? 1.0 : 2.0, out_bytes(EPI, SF32));
+  const double bytes = gemm_bytes(p, 2.0, W8 ? 1.0 : 2.0, out_bytes(EPI, SF32), w_rows_per_col(EPI));
   if (c.tiling == RAJNI_TILING_WIDE) return launch_stream<EPI, ALOAD, SF32, W8, A, 2, 4, 8, NS>(c, p, l, bytes);
   if (c.tiling == RAJNI_TILING_MID) return launch_stream<EPI, ALOAD, SF32, W8, A, 4, 2, 4, 3>(c, p, l, bytes);
-  return launch_planned<&small::gemm_bf16_tn_128x128<EPI, ALOAD, SF32, W8, A>>(c, 256, p, l, bytes, "gemm_bf16_tn");
+  return launch_planned<&small::gemm_bf16_tn_128x128<EPI, ALOAD, SF32, W8, A>>(c, 256, p, l, bytes, "gemm_bf16_tn", w_rows_per_col(EPI));
 }
 template <int EPI, bool SF32>
 int launch_gemm_f8(GemmParams& p, const LaunchCtl& l) {
@@ -1586,8 +1734,9 @@ int launch_gemm_f8(GemmParams& p, const LaunchCtl& l) {
 }
 template <int EPI, int ALOAD>
 int launch_gemm_f32(GemmParams& p, const LaunchCtl& l) {   // (as found: the residual rows a RESID launch reads are not counted)
-  return launch_planned<&f32::gemm_f32_tn_128x128<EPI, ALOAD>>(make_plan(p, RAJNI_TILING_F32, 128, 128, f32::LDS_BYTES), 256, p, l,
-                                                              gemm_bytes(p, 4.0, 4.0, 4.0), "gemm_f32_tn");
+  constexpr int WR = w_rows_per_col(EPI);
+  return launch_planned<&f32::gemm_f32_tn_128x128<EPI, ALOAD>>(make_plan(p, RAJNI_TILING_F32, 128, 128, f32::LDS_BYTES, 0, 0, 0, WR == 2),
+                                                              256, p, l, gemm_bytes(p, 4.0, 4.0, 4.0, WR), "gemm_f32_tn", WR);
 }
 
 // rajni_linear and its dry run: the refusals, then the one table - format x epilogue (x fp32 residual stream for RESID)
@@ -1597,6 +1746,7 @@ int linear16(int epi, bool sf32, GemmParams& p, const LaunchCtl& l) {
   return epi == EPI_BIAS ? launch_gemm<EPI_BIAS, ALOAD_PLAIN, false, W8, A>(p, l)
        : epi == EPI_GELU ? launch_gemm<EPI_GELU, ALOAD_PLAIN, false, W8, A>(p, l)
        : epi == EPI_QGELU ? launch_gemm<EPI_QGELU, ALOAD_PLAIN, false, W8, A>(p, l)
+       : epi == EPI_SWIGLU ? launch_gemm<EPI_SWIGLU, ALOAD_PLAIN, false, W8, A>(p, l)
        : sf32 ? launch_gemm<EPI_RESID, ALOAD_PLAIN, true, W8, A>(p, l) : launch_gemm<EPI_RESID, ALOAD_PLAIN, false, W8, A>(p, l);
 }
 int linear(const rajni_linear_args& a, LaunchCtl l) {
@@ -1661,6 +1811,14 @@ int linear(const rajni_linear_args& a, LaunchCtl l) {
                     "re-quantising epilogue exists for exact GELU only");
       epi = EPI_QGELU; l.kclass = KC_GEMM_GELU;
       break;
+    case RAJNI_EPI_BIAS_SWIGLU:
+      RAJNI_REQUIRE(!f8, RAJNI_ERR_UNSUPPORTED,
+                    "rajni_linear: the SwiGLU epilogue is unsupported with fp8 activations (x_scale): the fp8 x fp8 kernel's "
+                    "re-quantising epilogue exists for exact GELU only");
+      // the N + n row offsets and the 2N-row shape rule are ints
+      RAJNI_REQUIRE(a.N <= (1 << 30), RAJNI_ERR_INVALID, "rajni_linear: the SwiGLU epilogue needs N <= 2^30 (N=%d)", a.N);
+      epi = EPI_SWIGLU; l.kclass = KC_GEMM_GELU;
+      break;
     case RAJNI_EPI_BIAS_RESID:
       // fp32 asks for no ldr rule: its epilogue (epilogue_row_f32) reads the residual row one element at a time, so any
       // stride serves; the 16-bit and fp8 x fp8 epilogues read it 16 bytes at a time.  Only fp8 x fp8 can meet a y_scale
@@ -1682,7 +1840,8 @@ int linear(const rajni_linear_args& a, LaunchCtl l) {
     case FMT_F8F8: return epi == EPI_BIAS ? launch_gemm_f8<EPI_BIAS, false>(p, l) : epi == EPI_GELU8 ? launch_gemm_f8<EPI_GELU8, false>(p, l)
                         : sf32 ? launch_gemm_f8<EPI_RESID, true>(p, l) : launch_gemm_f8<EPI_RESID, false>(p, l);
     case FMT_F32: return epi == EPI_BIAS ? launch_gemm_f32<EPI_BIAS, ALOAD_PLAIN>(p, l) : epi == EPI_GELU ? launch_gemm_f32<EPI_GELU, ALOAD_PLAIN>(p, l)
-                       : epi == EPI_QGELU ? launch_gemm_f32<EPI_QGELU, ALOAD_PLAIN>(p, l) : launch_gemm_f32<EPI_RESID, ALOAD_PLAIN>(p, l);
+                       : epi == EPI_QGELU ? launch_gemm_f32<EPI_QGELU, ALOAD_PLAIN>(p, l)
+                       : epi == EPI_SWIGLU ? launch_gemm_f32<EPI_SWIGLU, ALOAD_PLAIN>(p, l) : launch_gemm_f32<EPI_RESID, ALOAD_PLAIN>(p, l);
     case FMT_W8: return linear16<true, bf16_t>(epi, sf32, p, l);
     case FMT_F16: return linear16<false, f16_t>(epi, sf32, p, l);
     default: return linear16<false, bf16_t>(epi, sf32, p, l);

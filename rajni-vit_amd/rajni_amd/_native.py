@@ -17,9 +17,11 @@ LIB_PATH = os.environ.get("RAJNI_HIP_LIB") or os.path.join(_HERE, "lib", "libraj
 RAJNI_F32, RAJNI_BF16, RAJNI_F16 = 0, 1, 2
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID = 0, 1, 2
 EPI_BIAS_QUICK_GELU = 16      # y = quick_gelu(x W^T + b); not with fp8 activations (x_scale)
+EPI_BIAS_SWIGLU = 18          # y [M, N] = silu(x Wg^T + bg) * (x Wv^T + bv), w [2N, K] gate rows then value rows; not with x_scale
 NUM_KCLASS = 17
 POOL_TOKEN, POOL_AVG = 0, 1
 MLP_GELU, MLP_QUICK_GELU = 0, 1      # rajni_vit_ext.mlp_act
+MLP_SWIGLU = 3                       # ... the gated FC1 (fc1_w [2 * hidden, C]); 2 is an unknown value
 
 c_void_p, c_int, c_long, c_float, c_size_t = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
 

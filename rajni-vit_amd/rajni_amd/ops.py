@@ -367,7 +367,10 @@ def linear(x: torch.Tensor, w_packed: torch.Tensor, n_out: int, bias: Optional[t
     With `x_scale` (fp32 [M]) x is the uint8 e4m3 tensor of layernorm_fp8() and the product runs on the fp8 matrix
     pipe (w_scale required); with EPI_BIAS_GELU `y_scale` (fp32 [M]) is required and the result is uint8 e4m3.
     EPI_BIAS_QUICK_GELU (x * sigmoid(1.702 x)) is EPI_BIAS_GELU with the other function, for every format but `x_scale`
-    (NotImplementedError from the library)."""
+    (NotImplementedError from the library).
+    EPI_BIAS_SWIGLU is the gated FC1, y [.., n_out] = silu(x Wg^T + bg) * (x Wv^T + bv): w_packed is pack_weight() of the
+    [2 n_out, K] weight whose rows [0, n_out) are the gates and [n_out, 2 n_out) the values (timm's packed order), bias and
+    w_scale are [2 n_out] in the same order.  Every format but `x_scale`, like QuickGELU."""
     nat.require_device(x, "x")
     x, w_packed = _placed(x, "x"), _placed(w_packed, "w")
     bias, gamma, w_scale = _placed(bias, "bias"), _placed(gamma, "gamma"), _placed(w_scale, "w_scale")

@@ -67,8 +67,9 @@ def create_base(args):
         model = timm.create_model(args.model, pretrained=args.pretrained)
         source = "timm"
     except ImportError:
-        if args.model not in ts.CONFIGS:
-            raise SystemExit(f"timm is not installed and '{args.model}' is not a built-in config {sorted(ts.CONFIGS)}")
+        if args.model not in ts.CONFIGS and args.model not in ts.SWIGLU_CONFIGS:
+            raise SystemExit(f"timm is not installed and '{args.model}' is not a built-in config "
+                             f"{sorted(ts.CONFIGS) + sorted(ts.SWIGLU_CONFIGS)}")
         model = ts.create_model(args.model, seed=args.seed)
         source = "timm-shaped stand-in, seeded random weights"
     if args.weights:

@@ -54,6 +54,12 @@ class ViTConfig:
     pre_norm: bool = False                # norm_pre after the pos-embed (CLIP-derived ViTs)
     global_pool: str = "token"            # 'token' (x[:, 0]) or 'avg' (mean of x[:, 1:])
     fc_norm: Optional[bool] = None        # None = timm's default: an fc_norm (and no final norm) iff global_pool == 'avg'
+    mlp: str = "mlp"                      # the block's MLP: "mlp" (fc1 -> act -> fc2), "swiglu_packed" (timm GluMlp with
+                                          # act_layer=nn.SiLU, gate_last=False, alias SwiGLUPacked: ONE fc1 of 2 * hidden_dim
+                                          # outputs, gate half first - the DINOv2 giant ViTs) or "swiglu" (timm SwiGLU: fc1_g and
+                                          # fc1_x apart).  hidden_dim stays fc2's input width.  On gated configs `act` keeps its
+                                          # default and is unused: the gate is SiLU.  (In front of distilled, act and reg_tokens:
+                                          # existing tests hold those three to be the last fields)
     distilled: bool = False               # DeiT distilled (timm VisionTransformerDistilled): a dist_token behind the class
                                           # token and a second classifier head_dist; not together with reg_tokens.  (In front of
                                           # act and reg_tokens: existing tests hold those two to be the last fields)
@@ -66,6 +72,8 @@ class ViTConfig:
     def __post_init__(self):
         if self.distilled and self.reg_tokens:
             raise ValueError("ViTConfig: distilled together with reg_tokens is not a timm model")
+        if self.mlp not in ("mlp", "swiglu_packed", "swiglu"):
+            raise ValueError(f"ViTConfig: mlp must be 'mlp', 'swiglu_packed' or 'swiglu', got {self.mlp!r}")
 
     @property
     def num_prefix_tokens(self) -> int:
@@ -185,6 +193,41 @@ CONFIGS: Dict[str, ViTConfig] = {
                                                    distilled=True),
 }
 
+# The gated-MLP configs live in a table of their own: the key list of CONFIGS is held fixed by tests/test_distilled_cpu.py.
+# create_model() and config_of() know both tables.
+SWIGLU_CONFIGS: Dict[str, ViTConfig] = {
+    # ---- SwiGLU MLPs: the DINOv2 giant ViTs (timm `vit_giant_patch14_dinov2`, `vit_giant_patch14_reg4_dinov2`: ViT-g/14,
+    # 1536 wide, 24 heads of 64, 40 blocks, LayerScale, SwiGLUPacked with hidden 4096, pretrained at 518 px) ----
+    "vit_giant_patch14_dinov2": ViTConfig(img_size=518, patch_size=14, embed_dim=1536, depth=40, num_heads=24,
+                                          mlp_ratio=4096 / 1536, layer_scale=1e-5, mlp="swiglu_packed"),
+    "vit_giant_patch14_reg4_dinov2": ViTConfig(img_size=518, patch_size=14, embed_dim=1536, depth=40, num_heads=24,
+                                               mlp_ratio=4096 / 1536, layer_scale=1e-5, no_embed_class=True,
+                                               mlp="swiglu_packed", reg_tokens=4),
+    # micro models (not timm names): the packed form, the split form with the same dims, a hidden width that is not whole
+    # 64-wide K steps (344 -> 384 zero-padded columns PER HALF: silu(0) * 0 must be exactly 0), the fp8-capable dims (at
+    # batch 64 FC1 has 1088 rows and 2048 W rows: the wide tiling), and the giant's combination of features
+    "vit_micro_swiglu_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, mlp_ratio=2.0, num_classes=10,
+                                             mlp="swiglu_packed"),
+    "vit_micro_swiglu_split_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, mlp_ratio=2.0,
+                                                   num_classes=10, mlp="swiglu"),
+    "vit_micro_swiglu_h344_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, mlp_ratio=2.6875,
+                                                  num_classes=10, mlp="swiglu_packed"),
+    "vit_micro512_swiglu_patch16_64": ViTConfig(img_size=64, embed_dim=512, depth=4, num_heads=8, mlp_ratio=2.0,
+                                                num_classes=10, mlp="swiglu_packed"),
+    "vit_micro_reg4_swiglu_patch14_56": ViTConfig(img_size=56, patch_size=14, embed_dim=128, depth=4, num_heads=2,
+                                                  mlp_ratio=2.0, num_classes=10, layer_scale=1e-6, no_embed_class=True,
+                                                  mlp="swiglu_packed", reg_tokens=4),
+}
+
+
+def config_of(name: str) -> ViTConfig:
+    """the built-in config of that name, from CONFIGS or SWIGLU_CONFIGS"""
+    if name in CONFIGS:
+        return CONFIGS[name]
+    if name in SWIGLU_CONFIGS:
+        return SWIGLU_CONFIGS[name]
+    raise KeyError(f"'{name}' is not a built-in config {sorted(CONFIGS) + sorted(SWIGLU_CONFIGS)}")
+
 
 class PatchEmbed(nn.Module):
     def __init__(self, cfg: ViTConfig):
@@ -253,6 +296,53 @@ class Mlp(nn.Module):
         return self.drop2(self.fc2(self.norm(self.drop1(self.act(self.fc1(x))))))
 
 
+class GluMlp(nn.Module):
+    """timm `GluMlp` (with act_layer=nn.SiLU and gate_last=False: `SwiGLUPacked`): one packed fc1 of 2 * hidden outputs,
+    x1, x2 = fc1(x).chunk(2, -1); gate_last=False: act(x1) * x2, gate_last=True: x1 * act(x2)"""
+
+    def __init__(self, dim: int, hidden: int, act_layer=nn.SiLU, gate_last: bool = False):
+        super().__init__()
+        self.chunk_dim = -1
+        self.gate_last = gate_last
+        self.fc1 = nn.Linear(dim, 2 * hidden)
+        self.act = act_layer()
+        self.drop1 = nn.Dropout(0.0)
+        self.norm = nn.Identity()
+        self.fc2 = nn.Linear(hidden, dim)
+        self.drop2 = nn.Dropout(0.0)
+
+    def forward(self, x):
+        x1, x2 = self.fc1(x).chunk(2, dim=self.chunk_dim)
+        x = x1 * self.act(x2) if self.gate_last else self.act(x1) * x2
+        return self.drop2(self.fc2(self.norm(self.drop1(x))))
+
+
+class SwiGLU(nn.Module):
+    """timm `SwiGLU`: the gate and the value projection apart, act(fc1_g(x)) * fc1_x(x)"""
+
+    def __init__(self, dim: int, hidden: int, act_layer=nn.SiLU):
+        super().__init__()
+        self.fc1_g = nn.Linear(dim, hidden)
+        self.fc1_x = nn.Linear(dim, hidden)
+        self.act = act_layer()
+        self.drop1 = nn.Dropout(0.0)
+        self.norm = nn.Identity()
+        self.fc2 = nn.Linear(hidden, dim)
+        self.drop2 = nn.Dropout(0.0)
+
+    def forward(self, x):
+        x = self.act(self.fc1_g(x)) * self.fc1_x(x)
+        return self.drop2(self.fc2(self.norm(self.drop1(x))))
+
+
+def make_mlp(cfg: "ViTConfig") -> nn.Module:
+    if cfg.mlp == "swiglu_packed":
+        return GluMlp(cfg.embed_dim, cfg.hidden_dim)
+    if cfg.mlp == "swiglu":
+        return SwiGLU(cfg.embed_dim, cfg.hidden_dim)
+    return Mlp(cfg.embed_dim, cfg.hidden_dim, cfg.act)
+
+
 class Block(nn.Module):
     def __init__(self, cfg: ViTConfig):
         super().__init__()
@@ -262,7 +352,7 @@ class Block(nn.Module):
         self.ls1 = LayerScale(C, cfg.layer_scale) if cfg.layer_scale else nn.Identity()
         self.drop_path1 = nn.Identity()
         self.norm2 = nn.LayerNorm(C, eps=cfg.ln_eps)
-        self.mlp = Mlp(C, cfg.hidden_dim, cfg.act)
+        self.mlp = make_mlp(cfg)
         self.ls2 = LayerScale(C, cfg.layer_scale) if cfg.layer_scale else nn.Identity()
         self.drop_path2 = nn.Identity()
 
@@ -372,8 +462,14 @@ def synth_state_dict(cfg: ViTConfig, seed: int = 0, std: float = 0.02,
         sd[p + "attn.qkv.bias"] = nrm(3 * C, s=bias_std) if bias_std else np.zeros(3 * C, np.float32)
         sd[p + "attn.proj.weight"] = nrm(C, C)
         sd[p + "attn.proj.bias"] = nrm(C, s=bias_std) if bias_std else np.zeros(C, np.float32)
-        sd[p + "mlp.fc1.weight"] = nrm(Hd, C)
-        sd[p + "mlp.fc1.bias"] = nrm(Hd, s=bias_std) if bias_std else np.zeros(Hd, np.float32)
+        if cfg.mlp == "swiglu":      # timm SwiGLU: gate, then value (a plain config draws exactly what it always drew)
+            for fc in ("fc1_g", "fc1_x"):
+                sd[p + f"mlp.{fc}.weight"] = nrm(Hd, C)
+                sd[p + f"mlp.{fc}.bias"] = nrm(Hd, s=bias_std) if bias_std else np.zeros(Hd, np.float32)
+        else:
+            H1 = 2 * Hd if cfg.mlp == "swiglu_packed" else Hd   # packed: rows [0, Hd) the gate, [Hd, 2 Hd) the value
+            sd[p + "mlp.fc1.weight"] = nrm(H1, C)
+            sd[p + "mlp.fc1.bias"] = nrm(H1, s=bias_std) if bias_std else np.zeros(H1, np.float32)
         sd[p + "mlp.fc2.weight"] = nrm(C, Hd)
         sd[p + "mlp.fc2.bias"] = nrm(C, s=bias_std) if bias_std else np.zeros(C, np.float32)
         if cfg.layer_scale:
@@ -423,7 +519,7 @@ def create_model(name_or_cfg, seed: int = 0, std: float = 0.02, bias_std: float 
     `round_bf16=True` rounds every weight to a bf16-representable value while keeping the
     parameters in fp32, so that an fp32 oracle and a bf16 device model see identical weights.
     """
-    cfg = CONFIGS[name_or_cfg] if isinstance(name_or_cfg, str) else name_or_cfg
+    cfg = config_of(name_or_cfg) if isinstance(name_or_cfg, str) else name_or_cfg
     model = VisionTransformer(cfg)
     sd = synth_state_dict(cfg, seed=seed, std=std, bias_std=bias_std)
     if round_bf16:

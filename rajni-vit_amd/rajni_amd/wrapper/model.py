@@ -132,6 +132,59 @@ def classify_mlp_act(act: Optional[nn.Module]) -> str:
                               f"{name} computes neither")
 
 
+def _is_silu(act) -> bool:
+    """`act` computes t * sigmoid(t): nn.SiLU, or any module that matches it on classify_mlp_act's fp32 probe grid to 1e-6"""
+    if not isinstance(act, nn.Module):
+        return False
+    grid = torch.linspace(-6.0, 6.0, 193, dtype=torch.float32)
+    try:
+        with torch.no_grad():
+            got = act(grid.clone())
+    except Exception:
+        return False
+    return (isinstance(got, torch.Tensor) and got.shape == grid.shape and got.dtype == torch.float32
+            and float((got - grid * torch.sigmoid(grid)).abs().max()) <= 1e-6)
+
+
+def gated_mlp_form(mlp: nn.Module) -> Optional[str]:
+    """None for a plain MLP (fc1 -> act -> fc2); "packed" for timm's GluMlp layout - ONE fc1 whose output is twice fc2's
+    input, chunked into (x1, x2) - and "split" for timm's SwiGLU layout (fc1_g and fc1_x).  Recognised by structure, not by
+    class name.  Raises NotImplementedError for a gated MLP the native forward does not compute: a gate other than SiLU
+    (GELU-gated GEGLU and the like), or an active `norm` between the gate and fc2.  (A plain Mlp whose act is SiLU is not
+    gated: classify_mlp_act refuses it as before.)"""
+    fc1, fc2 = getattr(mlp, "fc1", None), getattr(mlp, "fc2", None)
+    fc1_g, fc1_x = getattr(mlp, "fc1_g", None), getattr(mlp, "fc1_x", None)
+    if isinstance(fc1_g, nn.Linear) and isinstance(fc1_x, nn.Linear) and isinstance(fc2, nn.Linear):
+        if fc1_g.weight.shape != fc1_x.weight.shape or fc1_g.out_features != fc2.in_features:
+            raise NotImplementedError(f"{type(mlp).__name__}: fc1_g and fc1_x must have one shape, with fc2.in_features outputs")
+        form = "split"
+    elif isinstance(fc1, nn.Linear) and isinstance(fc2, nn.Linear) and fc1.out_features == 2 * fc2.in_features:
+        form = "packed"
+    else:
+        return None
+    name = type(mlp).__name__
+    act = getattr(mlp, "act", None)
+    if not _is_silu(act):
+        raise NotImplementedError(f"{name}: a gated MLP is supported with the SiLU gate only (SwiGLU), t * sigmoid(t); its act "
+                                  f"{type(act).__name__} computes something else")
+    norm = getattr(mlp, "norm", None)
+    if norm is not None and not isinstance(norm, nn.Identity):
+        raise NotImplementedError(f"{name}: mlp.norm ({type(norm).__name__}) between the gate and fc2 is not supported")
+    return form
+
+
+def gated_fc1(mlp: nn.Module, form: str):
+    """(gate weight, value weight, gate bias, value bias) of a gated MLP, each [hidden, C] / [hidden] or None.  timm's
+    order (gate_last missing or False) has the gate in the first half of the packed fc1; gate_last=True swaps the halves."""
+    if form == "split":
+        return mlp.fc1_g.weight, mlp.fc1_x.weight, mlp.fc1_g.bias, mlp.fc1_x.bias
+    h = mlp.fc2.in_features
+    w, b = mlp.fc1.weight, mlp.fc1.bias
+    first, second = (w[:h], None if b is None else b[:h]), (w[h:], None if b is None else b[h:])
+    g, v = (second, first) if getattr(mlp, "gate_last", False) else (first, second)
+    return g[0], v[0], g[1], v[1]
+
+
 class RAJNIViTWrapper(nn.Module):
     def __init__(self, base_model: nn.Module, pruning_schedule: Dict[int, Dict]):
         super().__init__()
@@ -230,6 +283,9 @@ class RAJNIViTWrapper(nn.Module):
         if fmt == "fp8_mfma" and self._mlp_act_or_none() == "quick_gelu":
             raise NotImplementedError('set_weight_format("fp8_mfma"): the model\'s MLPs use QuickGELU; the fp8 x fp8 FC1 epilogue '
                                       'and its hidden-activation bound are exact GELU only ("fp8" weights work)')
+        if fmt == "fp8_mfma" and self._mlp_act_or_none() == "swiglu":
+            raise NotImplementedError('set_weight_format("fp8_mfma"): the model\'s MLPs are gated (SwiGLU); the fp8 x fp8 FC1 epilogue '
+                                      'and its hidden-activation bound are exact GELU only ("fp8" weights work)')
         if fmt != self._weight_format:
             self._weight_format = fmt
             self._weights = self._weights_key = None
@@ -242,11 +298,21 @@ class RAJNIViTWrapper(nn.Module):
         if self._weights is None or self._weight_format not in ("fp8", "fp8_mfma"):
             raise RuntimeError("run a forward with set_weight_format('fp8') or ('fp8_mfma') first")
         out = {}
-        hid = self._weights["desc"]["hidden"]
+        hid, hpad = self._weights["desc"]["hidden"], self._weights["desc"]["hidden_pad"]
+        gated = self._weights["desc"]["mlp_act"] == "swiglu"
         for i, bw in enumerate(self._weights["blocks"]):
             for ours, theirs in (("qkv", "attn.qkv"), ("proj", "attn.proj"), ("fc1", "mlp.fc1"), ("fc2", "mlp.fc2")):
                 w = ops.dequantize_fp8(bw[ours + "_w"], bw[ours + "_s"])
-                if ours == "fc1":
+                if ours == "fc1" and gated:
+                    # gate rows, then value rows, as packed; keyed like the base model: a packed fc1 (in ITS order, gate_last
+                    # models have the value first), or the split pair
+                    mlp = self.blocks[i].mlp
+                    wg, wv = w[:hid], w[hpad:hpad + hid]
+                    if gated_mlp_form(mlp) == "split":
+                        out[f"blocks.{i}.mlp.fc1_g.weight"], out[f"blocks.{i}.mlp.fc1_x.weight"] = wg, wv
+                        continue
+                    w = torch.cat([wv, wg] if getattr(mlp, "gate_last", False) else [wg, wv])
+                elif ours == "fc1":
                     w = w[:hid]               # rows / columns past the model's MLP width are zero padding
                 elif ours == "fc2":
                     w = w[:, :hid]
@@ -300,7 +366,7 @@ class RAJNIViTWrapper(nn.Module):
     def _mlp_act_or_none(self) -> Optional[str]:
         """the blocks' MLP activation where they agree on a supported one, else None (`_describe` reports why)"""
         try:
-            kinds = {classify_mlp_act(getattr(blk.mlp, "act", None)) for blk in self.blocks}
+            kinds = {"swiglu" if gated_mlp_form(blk.mlp) else classify_mlp_act(getattr(blk.mlp, "act", None)) for blk in self.blocks}
         except (NotImplementedError, AttributeError):
             return None
         return kinds.pop() if len(kinds) == 1 else None
@@ -324,7 +390,8 @@ class RAJNIViTWrapper(nn.Module):
         blk0 = self.blocks[0]
         Cdim = m.cls_token.shape[-1]
         heads = blk0.attn.num_heads
-        desc = dict(C=Cdim, H=heads, D=Cdim // heads, depth=len(self.blocks), hidden=blk0.mlp.fc1.out_features,
+        # FC2's K and the hidden buffer's width: of a gated MLP (SwiGLU) too, whose FC1 has twice as many rows
+        desc = dict(C=Cdim, H=heads, D=Cdim // heads, depth=len(self.blocks), hidden=blk0.mlp.fc2.in_features,
                     num_classes=m.head.out_features, patch=pe.kernel_size[0], in_chans=pe.in_channels,
                     ln_eps=float(blk0.norm1.eps), scale=float(blk0.attn.scale))
         desc["hidden_pad"] = (desc["hidden"] + 63) // 64 * 64
@@ -333,7 +400,8 @@ class RAJNIViTWrapper(nn.Module):
                 if not isinstance(ln, nn.LayerNorm) or ln.weight is None or float(ln.eps) != desc["ln_eps"]:
                     raise NotImplementedError(f"block {i}: norm layers must be affine nn.LayerNorm with one eps")
             try:
-                kind = classify_mlp_act(getattr(blk.mlp, "act", None))
+                form = gated_mlp_form(blk.mlp)
+                kind = "swiglu" if form else classify_mlp_act(getattr(blk.mlp, "act", None))
             except NotImplementedError as e:
                 raise NotImplementedError(f"block {i}: {e}") from None
             if desc.setdefault("mlp_act", kind) != kind:
@@ -434,6 +502,8 @@ class RAJNIViTWrapper(nn.Module):
         fp8 = self._weight_format in ("fp8", "fp8_mfma")
         if self._weight_format == "fp8_mfma" and desc["head_rows"] == 2:
             raise NotImplementedError('weight format "fp8_mfma" on a distillation model (DeiT distilled) is not supported yet')
+        if self._weight_format == "fp8_mfma" and desc["mlp_act"] == "swiglu":   # (the MLP was swapped after the setter)
+            raise NotImplementedError('weight format "fp8_mfma" with a gated (SwiGLU) MLP: the fp8 x fp8 FC1 epilogue is exact GELU only')
         if self._weight_format == "fp8_mfma" and desc["mlp_act"] != "gelu":   # (the activation was swapped after the setter)
             raise NotImplementedError('weight format "fp8_mfma" with a QuickGELU MLP: the fp8 x fp8 FC1 epilogue is exact GELU only')
         if fp8 and dtype != torch.bfloat16:
@@ -486,16 +556,30 @@ class RAJNIViTWrapper(nn.Module):
             # has them anyway, up to the next 256) with zero bias, GELU(0) = 0 (QuickGELU(0) = 0 alike) lands in the padding columns of the
             # hidden buffer, and fc2's zero-padded input columns ignore them - exact, no kernel involved.
             hid, hpad = desc["hidden"], desc["hidden_pad"]
-            (fc1_w, fc1_s) = pq(blk.mlp.fc1.weight)
+            gated = desc["mlp_act"] == "swiglu"
+            if gated:
+                # SwiGLU: fc1_w is [2 hpad, C] - gate rows [0, hpad), value rows [hpad, 2 hpad), the order RAJNI_EPI_BIAS_SWIGLU
+                # reads with N = hpad.  An odd width is zero-padded PER HALF (zero rows, zero bias, unit scales):
+                # silu(0) * 0 = 0 lands in the padding columns of the hidden buffer
+                wg, wv, bg, bv = gated_fc1(blk.mlp, gated_mlp_form(blk.mlp))
+                rows = lambda w: torch.cat([w.detach(), w.new_zeros((hpad - hid, w.shape[1]))]) if hpad != hid else w.detach()
+                # (fp8: an all-zero row quantises with scale 1, quantize_rows_fp8 - the padding rows' scales need no patching)
+                (fc1_w, fc1_s) = pq(torch.cat([rows(wg), rows(wv)]))
+            else:
+                (fc1_w, fc1_s) = pq(blk.mlp.fc1.weight)
             if fp8:
                 fc2_w, fc2_s = ops.pack_weight_fp8(blk.mlp.fc2.weight, dtype, device, k_multiple=64)
-                if hpad != hid:
+                if hpad != hid and not gated:
                     fc1_s = torch.cat([fc1_s, torch.ones(hpad - hid, dtype=fc1_s.dtype, device=fc1_s.device)])
             else:
                 fc2_w, fc2_s = ops.pack_weight(blk.mlp.fc2.weight, dtype, device, k_multiple=64), None
-            fc1_b = pv(blk.mlp.fc1.bias) if blk.mlp.fc1.bias is not None else zeros(hid)
-            if hpad != hid:
-                fc1_b = torch.cat([fc1_b, zeros(hpad - hid)])
+            if gated:
+                half = lambda b: torch.cat([pv(b) if b is not None else zeros(hid), zeros(hpad - hid)])
+                fc1_b = torch.cat([half(bg), half(bv)]).contiguous()
+            else:
+                fc1_b = pv(blk.mlp.fc1.bias) if blk.mlp.fc1.bias is not None else zeros(hid)
+                if hpad != hid:
+                    fc1_b = torch.cat([fc1_b, zeros(hpad - hid)])
             blocks.append(dict(
                 norm1_w=pv(blk.norm1.weight), norm1_b=pv(blk.norm1.bias),
                 qkv_w=qkv_w, qkv_s=qkv_s, qkv_b=pv(a.qkv.bias) if a.qkv.bias is not None else zeros(3 * desc["C"]),
@@ -621,7 +705,7 @@ class RAJNIViTWrapper(nn.Module):
             ext.fc_norm_w, ext.fc_norm_b, ext.fc_norm_eps = nat.ptr(W["fc_norm_w"]), nat.ptr(W["fc_norm_b"]), W["fc_norm_eps"]
             ext.norm_absent = int(not d["norm"])
             ext.pool = nat.POOL_AVG if d["pool"] == "avg" else nat.POOL_TOKEN
-            ext.mlp_act = nat.MLP_QUICK_GELU if d["mlp_act"] == "quick_gelu" else nat.MLP_GELU
+            ext.mlp_act = {"quick_gelu": nat.MLP_QUICK_GELU, "swiglu": nat.MLP_SWIGLU}.get(d["mlp_act"], nat.MLP_GELU)
         # W: a stale optimistic launch keeps its weights alive
         self._plan = (key, plan, (blocks, tc, ws, W, ext, qk, pre), bufs, counts)
         if len(self._plans) >= 4:     # workspaces are large: keep only a few batch shapes alive

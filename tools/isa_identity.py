@@ -35,6 +35,9 @@ def kernels(path):
         # function-local labels are numbered by the function's index in the file: .LBB12_3 -> .LBB_3
         # (and so are the loop comments that name them: "Header=BB12_8")
         ln = re.sub(r"\bL?BB\d+_(?=\d)", "BB_", ln)
+        # ... and the comment behind a label is aligned to a column, so the padding changes with the index's digit count
+        # (.LBB99_6: -> .LBB100_6: once a file has a hundred functions): one space there
+        ln = re.sub(r"^(\.BB_\d+:)\s+;", r"\1 ;", ln)
         ln = re.sub(r"\.Lfunc_end\d+", ".Lfunc_end", ln)
         ln = re.sub(r"\.Lfunc_begin\d+", ".Lfunc_begin", ln)
         body.append(ln.rstrip())
