@@ -306,7 +306,17 @@ typedef struct {
 } rajni_vit_plan;
 
 size_t rajni_vit_workspace_bytes(const rajni_vit_plan* plan);
-/* images [B,Cin,S,S] dtype; logits [B,num_classes] dtype */
+/* images [B,Cin,S,S] dtype; logits [B,num_classes] dtype
+ *
+ * A HEADLESS plan - head_w == NULL and num_classes == 0 (timm num_classes=0: head is nn.Identity; head_b is not read) - launches
+ * no head GEMM: the buffer passed as `logits` receives the row the head would have read, fc_norm(pool(norm(x))), [B, C] in the
+ * plan's dtype - written by the final LayerNorm / pool_norm launch itself, which writes dense rows: logits_ld is 0 or C (a
+ * stride below C or off a multiple of 8 is RAJNI_ERR_INVALID, a wider one RAJNI_ERR_UNSUPPORTED).  With rajni_vit_ext.pool =
+ * RAJNI_POOL_NONE / RAJNI_POOL_DENSE the buffer receives tokens instead, [B, Nf, C] / [B, P + n, C].  One of head_w and
+ * num_classes without the other is RAJNI_ERR_INVALID (a null weight pointer).  A headless plan with act_fp8 or with
+ * rajni_vit_prefix.head_rows == 2 is RAJNI_ERR_UNSUPPORTED; everything else works as with a head - token or avg pool,
+ * fc_norm, norm_absent, registers, q/k-norm, norm_pre, every mlp_act, e4m3 weights, the 16-bit stream, and the last
+ * block's CLS-rows form.  The workspace is that of the same plan with a head. */
 int rajni_vit_forward(const rajni_vit_plan* plan, const void* images, void* logits,
                       rajni_stream_t stream);
 
@@ -335,7 +345,15 @@ int rajni_layernorm_stream(void* x, const float* w, const float* b, int rows, in
  * row the head GEMM reads.  pool = RAJNI_POOL_TOKEN: x[:, 0]; RAJNI_POOL_AVG: the mean of x[:, 1:], i.e. of the patch
  * tokens that SURVIVED pruning (what timm computes on whatever token set reaches the head), summed in a fixed order
  * in fp32.  norm_w == NULL / fc_w == NULL: that norm is nn.Identity.  C % 8 == 0, C <= 2048. */
-enum { RAJNI_POOL_TOKEN = 0, RAJNI_POOL_AVG = 1 };
+/* Two more values exist for the whole forward only (rajni_vit_ext.pool; rajni_pool_norm refuses them), both for a HEADLESS
+ * plan (below) and both behind the final norm, which must be present and not followed by an fc_norm:
+ *   RAJNI_POOL_NONE (timm global_pool=''): no pooling.  The output is every surviving token of the final stream through the
+ *     final norm, [B, Nf, C] dense, Nf the token count behind the last block - timm's forward_features on the pruned graph.
+ *   RAJNI_POOL_DENSE (this project's own): [B, P + n, C], n = (img_size / patch_size)^2 - the shape the unpruned model's
+ *     forward_features returns.  Row s of image b holds norm(x)[b, j] when token j of the final stream sat at position s of
+ *     the unpruned sequence (prefix tokens at 0..P-1, patch p at P + p: the scheduled blocks' selections composed, the forced
+ *     one where a block has it); every other row is all zero bits.  The normalised rows have the bits RAJNI_POOL_NONE gives. */
+enum { RAJNI_POOL_TOKEN = 0, RAJNI_POOL_AVG = 1, RAJNI_POOL_NONE = 2, RAJNI_POOL_DENSE = 3 };
 enum { RAJNI_MLP_GELU = 0, RAJNI_MLP_QUICK_GELU = 1, RAJNI_MLP_SWIGLU = 3 };   /* rajni_vit_ext.mlp_act */
 int rajni_pool_norm(const void* x, int B, int N, int C, int pool, const float* norm_w, const float* norm_b,
                     float norm_eps, const float* fc_w, const float* fc_b, float fc_eps, void* out, int dtype, int x_f32,
@@ -354,7 +372,12 @@ typedef struct {
   const float* norm_pre_w; const float* norm_pre_b; float norm_pre_eps;   /* norm_pre_w == NULL: no norm_pre */
   int norm_absent;                  /* 1: base_model.norm is nn.Identity (plan.norm_w / norm_b are not read) */
   int pool;                         /* RAJNI_POOL_TOKEN (0) or RAJNI_POOL_AVG; AVG with plan.cls_only_last_block is
-                                       RAJNI_ERR_INVALID: that opt-in never forms the rows to be averaged */
+                                       RAJNI_ERR_INVALID: that opt-in never forms the rows to be averaged.
+                                       RAJNI_POOL_NONE / RAJNI_POOL_DENSE (see the enum): the token outputs of a headless plan.
+                                       With a head (per-token classification), an fc_norm or norm_absent (there is no
+                                       cast-only row kernel) they are RAJNI_ERR_UNSUPPORTED, with plan.cls_only_last_block
+                                       RAJNI_ERR_INVALID; the last block then runs all rows.  Any other value is
+                                       RAJNI_ERR_UNSUPPORTED */
   const float* fc_norm_w; const float* fc_norm_b; float fc_norm_eps;      /* fc_norm_w == NULL: no fc_norm */
   int mlp_act;                      /* RAJNI_MLP_GELU (0) or RAJNI_MLP_QUICK_GELU: the activation of every block's FC1.  It sits in
                                        what were the four bytes of tail padding behind fc_norm_eps (offset 68 of 72: the record

@@ -230,6 +230,12 @@ int launch_score_select(const void* qkv, const void* scores_in, int B, int N, in
                         size_t ws_bytes = 0);
 int launch_gather_rows(const void* src, const int32_t* idx, void* dst, int B, int n_src, int n_dst,
                        int row_bytes, hipStream_t s);
+// RAJNI_POOL_DENSE: the selections composed into src [B, Nf] (levels[0] = the last scheduled block's; host arrays), and the
+// final norm written to the rows of the unpruned sequence [B, S, C] they name, zeros elsewhere
+int launch_source_idx(int32_t* src, const int32_t* const* idx, const int* width, const int* nsrc, int n_levels, int B, int Nf,
+                      hipStream_t s);
+int launch_layernorm_dense(const void* x, const int32_t* src, const float* w, const float* b, void* y, int B, int Nf, int S,
+                           int C, float eps, int x_f32, int dtype, hipStream_t s);
 // variants.hip: the timm options of rajni_vit_ext (b pointers may be NULL = no bias; nw / fw NULL = that norm is absent)
 int launch_qk_norm(void* qkv, const float* qw, const float* qb, const float* kw, const float* kb, int rows, int H, int D,
                    float eps, int dtype, hipStream_t s);

@@ -15,7 +15,14 @@
 // With plan.act_fp8 (opt-in): LN1 / LN2 emit per-row-scaled e4m3 rows, QKV / FC1 / FC2 run on the fp8 matrix pipe
 // (gemm_f8.h) and FC1's GELU epilogue re-quantises the hidden activations; where attention emits e4m3 rows
 // (attn_emits_e4m3) proj runs there too.  The residual stream, patch embed and head are unchanged.
+//
+// The tail is final norm -> pool -> fc_norm -> head GEMM.  A headless plan (head_w NULL, num_classes 0) stops in front of the
+// GEMM and lets the norm launch write the caller's buffer; on such a plan ext.pool = RAJNI_POOL_NONE normalises every surviving
+// row into it, and RAJNI_POOL_DENSE scatters them back to the unpruned sequence (source_idx_kernel + layernorm_dense_kernel,
+// rowops.hip).  The logits path issues the launches it always did.
 #include "common.h"
+
+#include <vector>
 
 namespace {
 
@@ -91,6 +98,10 @@ int check_placement(const rajni_vit_plan& p, const void* images, const void* log
   return RAJNI_OK;
 }
 
+// no head: the buffer passed as `logits` receives the row the head would have read, or the tokens (RAJNI_POOL_NONE / _DENSE)
+inline bool headless(const rajni_vit_plan& p) { return p.head_w == nullptr && p.num_classes == 0; }
+inline bool pool_is_tokens(const rajni_vit_ext* e) { return e && (e->pool == RAJNI_POOL_NONE || e->pool == RAJNI_POOL_DENSE); }
+
 int check_plan(const rajni_vit_plan& p, bool norm_absent) {
   RAJNI_REQUIRE(p.dtype == RAJNI_BF16 || p.dtype == RAJNI_F32 || p.dtype == RAJNI_F16, RAJNI_ERR_INVALID,
                 "rajni_vit_forward: bad dtype %d", p.dtype);
@@ -103,8 +114,12 @@ int check_plan(const rajni_vit_plan& p, bool norm_absent) {
                 "rajni_vit_forward: need C == H*D and a head dim that is a multiple of 8 up to 128 (C=%d H=%d D=%d)", p.C, p.H, p.D);
   RAJNI_REQUIRE(p.C % 64 == 0 && p.hidden % 64 == 0, RAJNI_ERR_UNSUPPORTED,
                 "rajni_vit_forward: C and hidden must be multiples of 64");
-  RAJNI_REQUIRE(p.patch_w && p.cls_token && p.pos_embed && p.head_w && (norm_absent || (p.norm_w && p.norm_b)),
+  // a headless plan (head_w == NULL and num_classes == 0) is legal; half of that pair is a missing weight
+  RAJNI_REQUIRE(p.patch_w && p.cls_token && p.pos_embed && (p.head_w != nullptr) == (p.num_classes != 0) &&
+                    (norm_absent || (p.norm_w && p.norm_b)),
                 RAJNI_ERR_INVALID, "rajni_vit_forward: null weight pointer");
+  RAJNI_REQUIRE(!(headless(p) && p.act_fp8), RAJNI_ERR_UNSUPPORTED,
+                "rajni_vit_forward: a headless plan (feature output) is unsupported with act_fp8");
   if (p.dtype == RAJNI_F16) {
     bool w8 = false;
     for (int i = 0; i < p.depth; ++i)
@@ -124,10 +139,22 @@ int check_plan(const rajni_vit_plan& p, bool norm_absent) {
 }
 
 int check_ext(const rajni_vit_plan& p, const rajni_vit_ext& e) {
-  RAJNI_REQUIRE(e.pool == RAJNI_POOL_TOKEN || e.pool == RAJNI_POOL_AVG, RAJNI_ERR_UNSUPPORTED,
+  // (RAJNI_POOL_NONE and RAJNI_POOL_DENSE, the token outputs, are legal too; the wording of this refusal is what callers match on)
+  RAJNI_REQUIRE(e.pool >= RAJNI_POOL_TOKEN && e.pool <= RAJNI_POOL_DENSE, RAJNI_ERR_UNSUPPORTED,
                 "rajni_vit_forward_ext: pool must be RAJNI_POOL_TOKEN or RAJNI_POOL_AVG (%d)", e.pool);
   RAJNI_REQUIRE(!(e.pool == RAJNI_POOL_AVG && p.cls_only_last_block), RAJNI_ERR_INVALID,
                 "rajni_vit_forward_ext: 'avg' pooling with cls_only_last_block - that opt-in never forms the rows to be averaged");
+  if (pool_is_tokens(&e)) {
+    const char* name = e.pool == RAJNI_POOL_NONE ? "RAJNI_POOL_NONE" : "RAJNI_POOL_DENSE";
+    RAJNI_REQUIRE(headless(p), RAJNI_ERR_UNSUPPORTED,
+                  "rajni_vit_forward_ext: %s needs a headless plan (head_w NULL, num_classes 0) - per-token classification is "
+                  "not implemented", name);
+    RAJNI_REQUIRE(!e.fc_norm_w && !e.norm_absent, RAJNI_ERR_UNSUPPORTED,
+                  "rajni_vit_forward_ext: %s needs the final norm and no fc_norm (fc_norm %s, norm %s) - there is no cast-only "
+                  "row kernel yet", name, e.fc_norm_w ? "present" : "absent", e.norm_absent ? "absent" : "present");
+    RAJNI_REQUIRE(!p.cls_only_last_block, RAJNI_ERR_INVALID,
+                  "rajni_vit_forward_ext: %s with cls_only_last_block - that opt-in never forms the rows to be returned", name);
+  }
   if (e.qk_norm)
     for (int i = 0; i < p.depth; ++i)
       RAJNI_REQUIRE(e.qk_norm[i].q_norm_w && e.qk_norm[i].k_norm_w, RAJNI_ERR_INVALID,
@@ -277,6 +304,8 @@ int check_prefix(const rajni_vit_prefix* pre, const char* who) {
 // the distilled head (head_rows == 2) against the plan and the ext record: it is norm -> rows 0 and 1 -> one linear layer
 int check_head_rows(const rajni_vit_plan& p, const rajni_vit_ext* e, const rajni_vit_prefix* pre) {
   if (head_row_count(pre) != 2) return RAJNI_OK;
+  RAJNI_REQUIRE(!headless(p), RAJNI_ERR_UNSUPPORTED,
+                "rajni_vit_forward: head_rows=2 with a headless plan - the two rows exist to feed the averaged heads");
   RAJNI_REQUIRE(!e || (e->pool == RAJNI_POOL_TOKEN && !e->fc_norm_w && !e->norm_absent), RAJNI_ERR_UNSUPPORTED,
                 "rajni_vit_forward: head_rows=2 needs a token head behind the final norm (pool=%d, fc_norm %s, norm %s)", e->pool,
                 e->fc_norm_w ? "present" : "absent", e->norm_absent ? "absent" : "present");
@@ -296,7 +325,7 @@ int tokens_entering(const rajni_vit_plan& p, int P, int i) {
   return N;
 }
 
-inline int logits_stride(const rajni_vit_plan& p) { return p.logits_ld > 0 ? p.logits_ld : p.num_classes; }
+inline int logits_stride(const rajni_vit_plan& p) { return p.logits_ld > 0 ? p.logits_ld : (headless(p) ? p.C : p.num_classes); }
 
 // the pruning schedule and the logits stride: what the block loop and the head rely on, refused before anything is launched
 int check_schedule(const rajni_vit_plan& p, int P) {
@@ -310,7 +339,29 @@ int check_schedule(const rajni_vit_plan& p, int P) {
   const int ld = logits_stride(p);
   RAJNI_REQUIRE(ld % 8 == 0 && ld >= p.num_classes, RAJNI_ERR_INVALID,
                 "rajni_vit_forward: logits row stride must be a multiple of 8 and >= num_classes (%d)", ld);
+  if (headless(p)) {
+    // the final norm / pool_norm launch writes the caller's buffer directly, and those kernels write dense rows
+    RAJNI_REQUIRE(ld >= p.C, RAJNI_ERR_INVALID, "rajni_vit_forward: a headless plan writes rows of C elements: logits row stride "
+                  "must be >= C (%d < %d)", ld, p.C);
+    RAJNI_REQUIRE(ld == p.C, RAJNI_ERR_UNSUPPORTED, "rajni_vit_forward: a headless plan writes dense rows: logits row stride "
+                  "must be 0 or C (%d, C = %d)", ld, p.C);
+  }
   return RAJNI_OK;
+}
+
+// src [B, Nf] = where each token of the final stream sat in the unpruned sequence: the scheduled blocks' selections (the
+// forced one where a block has it), last block first
+int launch_final_source_idx(const rajni_vit_plan& p, int P, int32_t* src, int Nf, hipStream_t s) {
+  std::vector<const int32_t*> idx;
+  std::vector<int> width, nsrc;
+  for (int i = p.depth - 1; i >= 0; --i) {
+    const rajni_block& blk = p.blocks[i];
+    if (blk.keep <= 0) continue;
+    idx.push_back(blk.forced_keep_idx ? blk.forced_keep_idx : blk.keep_idx);
+    width.push_back(blk.keep + P);
+    nsrc.push_back(tokens_entering(p, P, i));
+  }
+  return launch_source_idx(src, idx.data(), width.data(), nsrc.data(), (int)idx.size(), p.B, Nf, s);
 }
 
 // the whole forward; ext == nullptr (rajni_vit_forward) and an all-zero record enqueue the same launches, and so does
@@ -513,9 +564,21 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
 
   // ---- final norm on the CLS rows only (LN is per token; model.py:65-66) + head
   // (with a pooled head, fc_norm or no norm: norm on every row that is pooled -> pool -> fc_norm, one kernel)
+  // a headless plan: the same launch writes the caller's buffer instead of w.clsn, and there is no head GEMM
+  void* const rowout = headless(p) ? logits : (void*)w.clsn;
+  if (ext && ext->pool == RAJNI_POOL_NONE)   // every surviving token through the final norm: [B, N, C]
+    return launch_layernorm(cur, C, p.norm_w, p.norm_b, logits, B * N, C, p.ln_eps, f.sf32, dt, s);
+  if (ext && ext->pool == RAJNI_POOL_DENSE) {
+    // [B, P + n, C]: token j of the final stream at the row it came from, zeros elsewhere.  The composed selection lives in
+    // w.qkv, dead behind the last block (B * N * 4 bytes always fit)
+    int32_t* src = reinterpret_cast<int32_t*>(w.qkv);
+    rc = launch_final_source_idx(p, P, src, N, s);
+    if (rc != RAJNI_OK) return rc;
+    return launch_layernorm_dense(cur, src, p.norm_w, p.norm_b, logits, B, N, tokens_entering(p, P, 0), C, p.ln_eps, f.sf32, dt, s);
+  }
   if (ext && (ext->pool != RAJNI_POOL_TOKEN || ext->fc_norm_w || ext->norm_absent))
     rc = launch_pool_norm(cur, B, N, C, ext->pool, ext->norm_absent ? nullptr : p.norm_w, p.norm_b, p.ln_eps,
-                          ext->fc_norm_w, ext->fc_norm_b, ext->fc_norm_eps, w.clsn, f.sf32, dt, s, P);
+                          ext->fc_norm_w, ext->fc_norm_b, ext->fc_norm_eps, rowout, f.sf32, dt, s, P);
   else if (HR == 2) {
     // rows 0 and 1 of every image, normalised side by side: row b of [B, 2C].  A stream that still holds all N rows (a last
     // block that prunes, or the all-rows form) first gives up its two rows to the other stream buffer, dense
@@ -527,8 +590,9 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
     }
     rc = launch_layernorm(cur, C, p.norm_w, p.norm_b, w.clsn, 2 * B, C, p.ln_eps, f.sf32, dt, s);
   } else
-    rc = launch_layernorm(cur, (long)N * C, p.norm_w, p.norm_b, w.clsn, B, C, p.ln_eps, f.sf32, dt, s);
+    rc = launch_layernorm(cur, (long)N * C, p.norm_w, p.norm_b, rowout, B, C, p.ln_eps, f.sf32, dt, s);
   if (rc != RAJNI_OK) return rc;
+  if (headless(p)) return RAJNI_OK;
   rajni_linear_args head = linear_args(dt, w.clsn, p.head_w, p.head_b, nullptr, logits, B, p.num_classes, HR * C, RAJNI_EPI_BIAS);
   head.ldc = logits_stride(p);
   return launch_linear(head, s);

@@ -363,6 +363,104 @@ __global__ void __launch_bounds__(256) gather_rows_kernel(const uint4* __restric
   }
 }
 
+// ---- RAJNI_POOL_DENSE (forward.hip): the final norm scattered back to the unpruned sequence ----
+// src[b, j] = position in the unpruned sequence of token j of the final stream: the scheduled blocks' selections composed,
+// walked from the last scheduled block back to the first (t.idx[0] is the last one's).  One thread per (b, j).  A launch
+// walks up to SRC_LEVELS selections; a longer schedule chains launches (`first` = 0: j resumes from src).  Every step is
+// clamped to the tokens that entered its block, so a forced selection with a bad index cannot send the next read outside
+// the previous level's row.
+constexpr int SRC_LEVELS = 4;
+struct SrcLevels {
+  const int32_t* idx[SRC_LEVELS];   // [B, width] keep_idx (or forced_keep_idx) of a scheduled block
+  int width[SRC_LEVELS];            // its row width: prefix tokens + keep
+  int nsrc[SRC_LEVELS];             // tokens that entered that block: its values are < nsrc
+  int n;
+};
+__global__ void __launch_bounds__(256) source_idx_kernel(int32_t* __restrict__ src, SrcLevels t, int B, int Nf, int first) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)B * Nf) return;
+  const int b = (int)(i / Nf);
+  int j = first ? (int)(i - (long)b * Nf) : src[i];
+#pragma unroll
+  for (int k = 0; k < SRC_LEVELS; ++k)
+    if (k < t.n) {
+      j = t.idx[k][(long)b * t.width[k] + j];
+      j = j < 0 ? 0 : (j >= t.nsrc[k] ? t.nsrc[k] - 1 : j);
+    }
+  src[i] = j;
+}
+
+// y[b, s, :] = norm(x[b, j, :]) where src[b, j] == s, else zeros: one wave per OUTPUT row (b, s) of [B, S, C], so every output
+// byte is written exactly once (no memset pass, no atomics, no inverse map).  src[b, :] is strictly ascending (every
+// selection is ascending), so the wave binary-searches it for s - wave-uniform: the row index is made scalar, the search runs
+// on the scalar unit.  A hit is layernorm_kernel's arithmetic instruction for instruction (load8, two-pass fp32 statistics,
+// wave_sum in the same order, fmaf((v - mean) * rstd, w, b)): the same bits.  16-byte stores either way.
+template <typename TX, typename TY>
+__global__ void __launch_bounds__(256) layernorm_dense_kernel(const TX* __restrict__ x, const int32_t* __restrict__ src,
+                                                              const float* __restrict__ w, const float* __restrict__ b,
+                                                              TY* __restrict__ y, int B, int Nf, int S, int C, float eps) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + wave;
+  if (row >= (long)B * S) return;
+  const int img = (int)(row / S), s = (int)(row - (long)img * S);
+  const int32_t* sb = src + (long)img * Nf;
+  int lo = 0, hi = Nf;                    // the first j in [0, Nf) with sb[j] >= s
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (sb[mid] < s) lo = mid + 1; else hi = mid;
+  }
+  const bool hit = lo < Nf && sb[lo] == s;
+  const int nchunk = C >> 3;
+  TY* yr = y + row * C;
+  if (!hit) {
+    const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
+      const int c = lane + i * 64;
+      if (c < nchunk) store8<TY>(yr + c * 8, z);
+    }
+    return;
+  }
+  const TX* xr = x + ((long)img * Nf + lo) * C;
+  float v[LN_MAX_CHUNKS][8];
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
+    const int c = lane + i * 64;
+    if (c < nchunk) {
+      load8<TX>(xr + c * 8, v[i]);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) sum += v[i][j];
+    }
+  }
+  const float mean = wave_sum(sum) / (float)C;
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
+    const int c = lane + i * 64;
+    if (c < nchunk) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float d = v[i][j] - mean;
+        ss += d * d;
+      }
+    }
+  }
+  const float rstd = rsqrtf(wave_sum(ss) / (float)C + eps);
+#pragma unroll
+  for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
+    const int c = lane + i * 64;
+    if (c < nchunk) {
+      float wv[8], bv[8], o[8];
+      load8<float>(w + c * 8, wv);
+      load8<float>(b + c * 8, bv);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = fmaf((v[i][j] - mean) * rstd, wv[j], bv[j]);
+      store8<TY>(yr + c * 8, o);
+    }
+  }
+}
+
 }  // namespace
 
 static int launch_layernorm_f16(const void* x, long xs, const float* w, const float* b, void* y, int rows,
@@ -444,5 +542,53 @@ int launch_gather_rows(const void* src, const int32_t* idx, void* dst, int B, in
   hipLaunchKernelGGL(gather_rows_kernel, dim3((int)blocks), dim3(256), 0, s, (const uint4*)src, idx,
                      (uint4*)dst, B, n_src, n_dst, row_bytes / 16);
   RAJNI_CHECK_LAUNCH("gather_rows_kernel");
+  return RAJNI_OK;
+}
+
+// src [B, Nf] int32 = the composition of `n_levels` selections, levels[0] the LAST scheduled block's (see source_idx_kernel);
+// n_levels == 0 gives the identity.  idx / width / nsrc are host arrays.
+int launch_source_idx(int32_t* src, const int32_t* const* idx, const int* width, const int* nsrc, int n_levels, int B, int Nf,
+                      hipStream_t s) {
+  RAJNI_REQUIRE(src && B > 0 && Nf > 0 && n_levels >= 0, RAJNI_ERR_INVALID, "source_idx: bad arguments");
+  const long total = (long)B * Nf;
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  int done = 0;
+  do {
+    SrcLevels t{};
+    for (; t.n < SRC_LEVELS && done < n_levels; ++t.n, ++done) {
+      RAJNI_REQUIRE(idx[done] && width[done] > 0 && nsrc[done] > 0, RAJNI_ERR_INVALID, "source_idx: level %d is empty", done);
+      t.idx[t.n] = idx[done]; t.width[t.n] = width[done]; t.nsrc[t.n] = nsrc[done];
+    }
+    ProfScope prof(KC_OTHER, s, 0.0, 4.0 * total * (t.n + 1));
+    hipLaunchKernelGGL(source_idx_kernel, grid, block, 0, s, src, t, B, Nf, done == t.n ? 1 : 0);
+    RAJNI_CHECK_LAUNCH("source_idx_kernel");
+  } while (done < n_levels);
+  return RAJNI_OK;
+}
+
+// y [B, S, C] `dtype`: row src[b, j] of image b = LayerNorm(x[b, j]) for the Nf rows of the stream x [B, Nf, C] (fp32 when x_f32,
+// else `dtype`), every other row zero.  src [B, Nf] strictly ascending per image, values in [0, S).
+int launch_layernorm_dense(const void* x, const int32_t* src, const float* w, const float* b, void* y, int B, int Nf, int S,
+                           int C, float eps, int x_f32, int dtype, hipStream_t s) {
+  RAJNI_REQUIRE(x && src && w && b && y, RAJNI_ERR_INVALID, "layernorm_dense: null pointer");
+  RAJNI_REQUIRE(B > 0 && Nf > 0 && S >= Nf && C > 0 && C % 8 == 0 && C <= 64 * 8 * LN_MAX_CHUNKS, RAJNI_ERR_UNSUPPORTED,
+                "layernorm_dense: need C %% 8 == 0, C <= 2048 and 0 < Nf <= S (C=%d Nf=%d S=%d)", C, Nf, S);
+  const long rows = (long)B * S;
+  RAJNI_REQUIRE((rows + 3) / 4 < (1L << 31), RAJNI_ERR_UNSUPPORTED, "layernorm_dense: too many output rows (%ld)", rows);
+  const bool f32io = dtype == RAJNI_F32;
+  const double eb = f32io ? 4.0 : 2.0, xb = (f32io || x_f32) ? 4.0 : 2.0;
+  ProfScope prof(KC_LAYERNORM, s, 8.0 * B * Nf * C, xb * B * Nf * C + eb * rows * C);
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  if (f32io)
+    hipLaunchKernelGGL((layernorm_dense_kernel<float, float>), grid, block, 0, s, (const float*)x, src, w, b, (float*)y, B, Nf, S, C, eps);
+  else if (dtype == RAJNI_F16 && x_f32)
+    hipLaunchKernelGGL((layernorm_dense_kernel<float, f16_t>), grid, block, 0, s, (const float*)x, src, w, b, (f16_t*)y, B, Nf, S, C, eps);
+  else if (dtype == RAJNI_F16)
+    hipLaunchKernelGGL((layernorm_dense_kernel<f16_t, f16_t>), grid, block, 0, s, (const f16_t*)x, src, w, b, (f16_t*)y, B, Nf, S, C, eps);
+  else if (x_f32)
+    hipLaunchKernelGGL((layernorm_dense_kernel<float, bf16_t>), grid, block, 0, s, (const float*)x, src, w, b, (bf16_t*)y, B, Nf, S, C, eps);
+  else
+    hipLaunchKernelGGL((layernorm_dense_kernel<bf16_t, bf16_t>), grid, block, 0, s, (const bf16_t*)x, src, w, b, (bf16_t*)y, B, Nf, S, C, eps);
+  RAJNI_CHECK_LAUNCH("layernorm_dense_kernel");
   return RAJNI_OK;
 }

@@ -9,7 +9,10 @@ schedule prunes), a `no_embed_class` pos-embed works (B3), and timm's `qk_norm`,
 and `fc_norm` options are computed as timm computes them instead of being dropped (B4), and so are
 timm's register tokens (`reg_tokens=R`: `reg_token` [1, R, C] behind the class token, never pruned, never ranked) and
 DeiT's distilled models (timm `VisionTransformerDistilled`: `dist_token` behind the class token, a prefix token like a
-register, and eval logits `(head(x[:, 0]) + head_dist(x[:, 1])) / 2`).
+register, and eval logits `(head(x[:, 0]) + head_dist(x[:, 1])) / 2`).  Beyond the reference's surface: a headless base model
+(`head = nn.Identity`, timm num_classes=0) returns its pooled feature [B, C], and `forward_features(x, dense=False)` returns the
+final normalised tokens of the pruned graph, or the unpruned sequence with pruned positions zero, with their source positions in
+`get_last_stats()["source_idx"]`.
 
 Not kept: the Python per-block loop.  `forward` builds (once per batch shape) a `rajni_vit_plan`
 - packed weights, workspace, per-stage index buffers - and calls `rajni_vit_forward`, which enqueues
@@ -280,6 +283,9 @@ class RAJNIViTWrapper(nn.Module):
         if fmt == "fp8_mfma" and self._is_distilled():
             raise NotImplementedError('set_weight_format("fp8_mfma"): not supported on a distillation model (DeiT distilled) '
                                       'yet; "fp8" weights work')
+        if fmt == "fp8_mfma" and isinstance(getattr(self.m, "head", None), nn.Identity):
+            raise NotImplementedError('set_weight_format("fp8_mfma"): not supported on a headless model (head = nn.Identity); '
+                                      '"fp8" weights work')
         if fmt == "fp8_mfma" and self._mlp_act_or_none() == "quick_gelu":
             raise NotImplementedError('set_weight_format("fp8_mfma"): the model\'s MLPs use QuickGELU; the fp8 x fp8 FC1 epilogue '
                                       'and its hidden-activation bound are exact GELU only ("fp8" weights work)')
@@ -385,15 +391,20 @@ class RAJNIViTWrapper(nn.Module):
         pe_norm = getattr(m.patch_embed, "norm", None)
         if pe_norm is not None and not isinstance(pe_norm, nn.Identity):
             raise NotImplementedError("RAJNIViTWrapper: patch_embed.norm is not supported")
-        if not isinstance(m.head, nn.Linear):
-            raise NotImplementedError("RAJNIViTWrapper: base_model.head must be nn.Linear")
+        # timm num_classes=0 (the DINOv2 checkpoints, any backbone use): head is nn.Identity and forward returns the pooled feature
+        headless = isinstance(m.head, nn.Identity)
+        if not headless and not isinstance(m.head, nn.Linear):
+            raise NotImplementedError("RAJNIViTWrapper: base_model.head must be nn.Linear or nn.Identity")
+        if headless and self._weight_format == "fp8_mfma":
+            raise NotImplementedError('weight format "fp8_mfma" on a headless model (head = nn.Identity) is not supported; '
+                                      '"fp8" weights work')
         blk0 = self.blocks[0]
         Cdim = m.cls_token.shape[-1]
         heads = blk0.attn.num_heads
         # FC2's K and the hidden buffer's width: of a gated MLP (SwiGLU) too, whose FC1 has twice as many rows
         desc = dict(C=Cdim, H=heads, D=Cdim // heads, depth=len(self.blocks), hidden=blk0.mlp.fc2.in_features,
-                    num_classes=m.head.out_features, patch=pe.kernel_size[0], in_chans=pe.in_channels,
-                    ln_eps=float(blk0.norm1.eps), scale=float(blk0.attn.scale))
+                    num_classes=0 if headless else m.head.out_features, patch=pe.kernel_size[0], in_chans=pe.in_channels,
+                    ln_eps=float(blk0.norm1.eps), scale=float(blk0.attn.scale), headless=headless)
         desc["hidden_pad"] = (desc["hidden"] + 63) // 64 * 64
         for i, blk in enumerate(self.blocks):
             for ln in (blk.norm1, blk.norm2):
@@ -529,7 +540,9 @@ class RAJNIViTWrapper(nn.Module):
             mod = getattr(m, name, None) if desc[name] else None
             W[name + "_w"], W[name + "_b"] = (pv(mod.weight), pv(mod.bias)) if mod is not None else (None, None)
             W[name + "_eps"] = float(mod.eps) if mod is not None else 0.0
-        if desc["head_rows"] == 2:
+        if desc["headless"]:
+            W["head_w"] = W["head_b"] = None      # rajni_vit_plan: head_w NULL and num_classes 0, no head GEMM
+        elif desc["head_rows"] == 2:
             # (head(n0) + head_dist(n1)) / 2 as ONE linear layer over [n0 | n1]: weight [classes, 2C] = [W / 2 | W_dist / 2]
             # (halving is exact), bias (b + b_dist) / 2 in fp32.  Plain tensors built here, not parameters of the module.
             W["head_w"] = pw(torch.cat([0.5 * m.head.weight.detach().float(), 0.5 * m.head_dist.weight.detach().float()], dim=1))
@@ -607,12 +620,18 @@ class RAJNIViTWrapper(nn.Module):
         self._drop_plans()
         return W
 
-    def _build_plan(self, B: int, S: int, device, dtype):
+    def _build_plan(self, B: int, S: int, device, dtype, mode: str = "logits"):
+        """`mode`: "logits" (the model's forward: logits, or the pooled feature of a headless model), or the feature outputs
+        "tokens" / "dense" (forward_features): a second plan of the same packed weights with no head and
+        ext.pool = POOL_NONE / POOL_DENSE."""
         W = self._pack_weights(device, dtype)
         d = W["desc"]
         P = d["num_prefix"]
+        features = mode != "logits"
+        if features:
+            self._check_features(d)
         key = (B, S, device, dtype, self._weights_key, tuple(sorted(self._forced)), self._trace_scores, self._resid_bf16,
-               self._cls_only_last, P)
+               self._cls_only_last, P, mode)
         if self._plan is not None and self._plan[0] == key:
             return self._plan
         if key in self._plans:
@@ -668,16 +687,18 @@ class RAJNIViTWrapper(nn.Module):
         plan.dtype = nat.dtype_code(dtype)
         plan.B, plan.in_chans, plan.img_size, plan.patch_size = B, d["in_chans"], S, d["patch"]
         plan.C, plan.H, plan.D, plan.depth, plan.hidden = d["C"], d["H"], d["D"], d["depth"], d["hidden_pad"]
-        plan.num_classes, plan.ln_eps, plan.attn_scale = d["num_classes"], d["ln_eps"], d["scale"]
+        headless = features or d["headless"]
+        plan.num_classes, plan.ln_eps, plan.attn_scale = 0 if headless else d["num_classes"], d["ln_eps"], d["scale"]
         plan.pos_has_cls = pos_has_cls
         plan.patch_w, plan.patch_b = W["patch_w"].data_ptr(), W["patch_b"].data_ptr()
         plan.cls_token, plan.pos_embed = W["cls"].data_ptr(), W["pos"].data_ptr()
         plan.blocks = blocks
         plan.norm_w, plan.norm_b = nat.ptr(W["norm_w"]), nat.ptr(W["norm_b"])
-        plan.head_w, plan.head_b = W["head_w"].data_ptr(), W["head_b"].data_ptr()
+        plan.head_w, plan.head_b = (None, None) if headless else (W["head_w"].data_ptr(), W["head_b"].data_ptr())
         tc = (C.c_int32 * d["depth"])()
         plan.token_counts = tc
-        plan.logits_ld = (d["num_classes"] + 7) // 8 * 8
+        # (a headless plan's output rows are the C elements the final norm writes, dense)
+        plan.logits_ld = d["C"] if headless else (d["num_classes"] + 7) // 8 * 8
         plan.resid_bf16 = int(self._resid_bf16)
         plan.cls_only_last_block = int(self._cls_only_last)
         plan.act_fp8 = int(self._weight_format == "fp8_mfma")
@@ -685,13 +706,14 @@ class RAJNIViTWrapper(nn.Module):
         if P > 1:           # the prefix record beside the plan (rajni_vit_prefix); None: CLS only, the entry points as ever
             pre = nat.VitPrefix()
             pre.num_prefix, pre.reg_token = P, W["reg"].data_ptr()
-            pre.head_rows = 2 if d["head_rows"] == 2 else 0      # (register models: the record as it always was)
+            # (register models: the record as it always was; the feature plan of a distilled model reads no head rows)
+            pre.head_rows = 2 if d["head_rows"] == 2 and not features else 0
         nbytes = (nat.lib().rajni_vit_workspace_bytes(C.byref(plan)) if pre is None
                   else nat.lib().rajni_vit_workspace_bytes_prefix(C.byref(plan), C.byref(pre)))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
         plan.workspace, plan.workspace_bytes = ws.data_ptr(), nbytes
         ext = qk = None
-        if d["ext"]:        # the options beside the plan (rajni_vit_ext); None: the plain rajni_vit_forward
+        if d["ext"] or features:        # the options beside the plan (rajni_vit_ext); None: the plain rajni_vit_forward
             if d["pool"] == "avg" and self._cls_only_last:
                 raise ValueError("global_pool='avg' with set_last_block_cls_only(True): that opt-in never forms the rows to be averaged")
             ext = nat.VitExt()
@@ -705,17 +727,63 @@ class RAJNIViTWrapper(nn.Module):
             ext.fc_norm_w, ext.fc_norm_b, ext.fc_norm_eps = nat.ptr(W["fc_norm_w"]), nat.ptr(W["fc_norm_b"]), W["fc_norm_eps"]
             ext.norm_absent = int(not d["norm"])
             ext.pool = nat.POOL_AVG if d["pool"] == "avg" else nat.POOL_TOKEN
+            if features:      # timm forward_features ends at norm(x): no pool, no fc_norm
+                ext.pool = nat.POOL_DENSE if mode == "dense" else nat.POOL_NONE
+                ext.fc_norm_w = ext.fc_norm_b = None
             ext.mlp_act = {"quick_gelu": nat.MLP_QUICK_GELU, "swiglu": nat.MLP_SWIGLU}.get(d["mlp_act"], nat.MLP_GELU)
+        # what `logits` receives: [B, logits_ld], or the tokens behind the last block / the unpruned sequence's rows
+        n_last = counts[-1] if (d["depth"] - 1) not in self.pruning_schedule else \
+            ops.keep_count(self.pruning_schedule[d["depth"] - 1]["keep_ratio"], counts[-1], P) + P
+        out_shape = {"logits": (B, plan.logits_ld), "tokens": (B, n_last, d["C"]), "dense": (B, n0, d["C"])}[mode]
         # W: a stale optimistic launch keeps its weights alive
-        self._plan = (key, plan, (blocks, tc, ws, W, ext, qk, pre), bufs, counts)
+        # (existing callers index entry[0..4] and unpack entry[2] as seven objects: mode and out_shape go behind `counts`)
+        self._plan = (key, plan, (blocks, tc, ws, W, ext, qk, pre), bufs, counts, mode, out_shape)
         if len(self._plans) >= 4:     # workspaces are large: keep only a few batch shapes alive
             self._plans.pop(next(iter(self._plans)))
         self._plans[key] = self._plan
         return self._plan
 
     # ------------------------------------------------------------------------------------------
+    def _check_features(self, d):
+        """what forward_features does not compute"""
+        if not d["norm"]:
+            raise NotImplementedError("forward_features: base_model.norm is nn.Identity (the fc_norm models): their features are "
+                                      "the un-normalised stream, and there is no cast-only row kernel yet")
+        if self._weight_format == "fp8_mfma":
+            raise NotImplementedError('forward_features: not supported with weight format "fp8_mfma" ("fp8" weights work)')
+        if self._cls_only_last:
+            raise ValueError("forward_features with set_last_block_cls_only(True): that opt-in never forms the rows to be returned")
+
     @torch.no_grad()
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """logits [B, num_classes]; on a headless model (head = nn.Identity, timm num_classes=0) the pooled feature [B, C],
+        fc_norm(pool(norm(x))) on the pruned token set - timm's forward of such a model"""
+        out, entry = self._run(x, "logits")
+        plan = entry[1]
+        if plan.num_classes == 0:
+            return out
+        return out[:, : plan.num_classes] if plan.logits_ld != plan.num_classes else out
+
+    @torch.no_grad()
+    def forward_features(self, x: torch.Tensor, dense: bool = False) -> torch.Tensor:
+        """timm's forward_features on the pruned graph, norm(x), for every model the wrapper supports (with or without a head):
+        `dense=False`: [B, Nf, C], the tokens that survive the last block, in stream order;
+        `dense=True`:  [B, P + n, C], the unpruned sequence's shape - every surviving token at the position it came from, pruned
+                       positions zero.
+        Afterwards `get_last_stats()["source_idx"]` is an int32 device tensor [B, Nf]: the position in the unpruned sequence of
+        each surviving row (slots 0..P-1 are the prefix tokens 0..P-1, the rest strictly ascending), in both modes."""
+        out, entry = self._run(x, "dense" if dense else "tokens")
+        P, n0 = entry[0][-2], entry[4][0]
+        src = None            # the selections composed on the device, last stage first: no host sync
+        for i in sorted(entry[3], reverse=True):
+            idx = self._forced.get(i, entry[3][i]["keep_idx"]).long()
+            src = idx if src is None else torch.gather(idx, 1, src)
+        if src is None:
+            src = torch.arange(n0, device=x.device).expand(x.shape[0], n0)
+        self._last_stats["source_idx"] = src.to(torch.int32).contiguous()
+        return out
+
+    def _run(self, x: torch.Tensor, mode: str):
         nat.require_device(x, "input images")
         if x.dim() != 4 or x.shape[-1] != x.shape[-2]:
             raise ValueError(f"expected images [B, C, S, S], got {tuple(x.shape)}")
@@ -732,7 +800,7 @@ class RAJNIViTWrapper(nn.Module):
         with nat.device_guard(x.device):
             def launch(entry):
                 plan = entry[1]
-                out = torch.empty((B, plan.logits_ld), dtype=dtype, device=x.device)
+                out = torch.empty(entry[6], dtype=dtype, device=x.device)
                 ext, pre = entry[2][4], entry[2][6]
                 if pre is not None:
                     nat.check(nat.lib().rajni_vit_forward_ext_prefix(C.byref(plan), C.byref(ext) if ext is not None else None,
@@ -755,15 +823,15 @@ class RAJNIViTWrapper(nn.Module):
             # this function returns and are handed back to the allocator in stream order - a second stream driving the
             # same wrapper concurrently is not supported (the reference is one-forward-at-a-time too).
             cached = self._plan
-            if cached is not None and cached[0][:4] == (B, S, x.device, dtype):
+            # (the mode is the key's last element: a logits plan must not be launched into a feature buffer)
+            if cached is not None and cached[0][:4] == (B, S, x.device, dtype) and cached[0][-1] == mode:
                 logits = launch(cached)
-                entry = self._build_plan(B, S, x.device, dtype)
+                entry = self._build_plan(B, S, x.device, dtype, mode)
                 if entry is not cached:
                     logits = launch(entry)
             else:
-                entry = self._build_plan(B, S, x.device, dtype)
+                entry = self._build_plan(B, S, x.device, dtype, mode)
                 logits = launch(entry)
         plan, tc = entry[1], entry[2][1]
         self._last_stats = {"token_counts": [int(tc[i]) for i in range(plan.depth)]}   # model.py:68
-        ld = plan.logits_ld
-        return logits[:, : plan.num_classes] if ld != plan.num_classes else logits
+        return logits, entry
