@@ -312,7 +312,8 @@ size_t rajni_vit_workspace_bytes(const rajni_vit_plan* plan);
  * no head GEMM: the buffer passed as `logits` receives the row the head would have read, fc_norm(pool(norm(x))), [B, C] in the
  * plan's dtype - written by the final LayerNorm / pool_norm launch itself, which writes dense rows: logits_ld is 0 or C (a
  * stride below C or off a multiple of 8 is RAJNI_ERR_INVALID, a wider one RAJNI_ERR_UNSUPPORTED).  With rajni_vit_ext.pool =
- * RAJNI_POOL_NONE / RAJNI_POOL_DENSE the buffer receives tokens instead, [B, Nf, C] / [B, P + n, C].  One of head_w and
+ * RAJNI_POOL_NONE / RAJNI_POOL_DENSE / RAJNI_POOL_DENSE_LAST the buffer receives tokens instead, [B, Nf, C] / [B, P + n, C] (the
+ * last: every pruned position holds the token's state at the block that dropped it instead of zeros).  One of head_w and
  * num_classes without the other is RAJNI_ERR_INVALID (a null weight pointer).  A headless plan with act_fp8 or with
  * rajni_vit_prefix.head_rows == 2 is RAJNI_ERR_UNSUPPORTED; everything else works as with a head - token or avg pool,
  * fc_norm, norm_absent, registers, q/k-norm, norm_pre, every mlp_act, e4m3 weights, the 16-bit stream, and the last
@@ -352,8 +353,15 @@ int rajni_layernorm_stream(void* x, const float* w, const float* b, int rows, in
  *   RAJNI_POOL_DENSE (this project's own): [B, P + n, C], n = (img_size / patch_size)^2 - the shape the unpruned model's
  *     forward_features returns.  Row s of image b holds norm(x)[b, j] when token j of the final stream sat at position s of
  *     the unpruned sequence (prefix tokens at 0..P-1, patch p at P + p: the scheduled blocks' selections composed, the forced
- *     one where a block has it); every other row is all zero bits.  The normalised rows have the bits RAJNI_POOL_NONE gives. */
-enum { RAJNI_POOL_TOKEN = 0, RAJNI_POOL_AVG = 1, RAJNI_POOL_NONE = 2, RAJNI_POOL_DENSE = 3 };
+ *     one where a block has it); every other row is all zero bits.  The normalised rows have the bits RAJNI_POOL_NONE gives.
+ *   RAJNI_POOL_DENSE_LAST (5; 4 is unknown): RAJNI_POOL_DENSE with no zero row - a token that leaves the stream keeps the feature
+ *     it had when it left.  Row s holds norm(x)[b, j] for a token that survives the last block, exactly the row RAJNI_POOL_DENSE
+ *     writes; for a token that scheduled block i drops (it entered the block and is not in the block's selection) it holds
+ *     norm(x_entry_i)[b, j], x_entry_i the residual stream at the entry of block i (behind norm_pre; the embedded stream for
+ *     i = 0) and norm the final LayerNorm, as DINOv2's get_intermediate_layers(norm=True) applies it to intermediate states.
+ *     Prefix tokens never leave.  Every row is written exactly once, by the launch behind the block that drops it or by the
+ *     final one; the rows wait in the stream buffer the block's residual gather read from, so no workspace is added. */
+enum { RAJNI_POOL_TOKEN = 0, RAJNI_POOL_AVG = 1, RAJNI_POOL_NONE = 2, RAJNI_POOL_DENSE = 3, RAJNI_POOL_DENSE_LAST = 5 };
 enum { RAJNI_MLP_GELU = 0, RAJNI_MLP_QUICK_GELU = 1, RAJNI_MLP_SWIGLU = 3 };   /* rajni_vit_ext.mlp_act */
 int rajni_pool_norm(const void* x, int B, int N, int C, int pool, const float* norm_w, const float* norm_b,
                     float norm_eps, const float* fc_w, const float* fc_b, float fc_eps, void* out, int dtype, int x_f32,
@@ -376,8 +384,9 @@ typedef struct {
                                        RAJNI_POOL_NONE / RAJNI_POOL_DENSE (see the enum): the token outputs of a headless plan.
                                        With a head (per-token classification), an fc_norm or norm_absent (there is no
                                        cast-only row kernel) they are RAJNI_ERR_UNSUPPORTED, with plan.cls_only_last_block
-                                       RAJNI_ERR_INVALID; the last block then runs all rows.  Any other value is
-                                       RAJNI_ERR_UNSUPPORTED */
+                                       RAJNI_ERR_INVALID; the last block then runs all rows.  RAJNI_POOL_DENSE_LAST (5) is a
+                                       token output too, with the same refusals under its own name.  Any other value (4
+                                       included) is RAJNI_ERR_UNSUPPORTED */
   const float* fc_norm_w; const float* fc_norm_b; float fc_norm_eps;      /* fc_norm_w == NULL: no fc_norm */
   int mlp_act;                      /* RAJNI_MLP_GELU (0) or RAJNI_MLP_QUICK_GELU: the activation of every block's FC1.  It sits in
                                        what were the four bytes of tail padding behind fc_norm_eps (offset 68 of 72: the record

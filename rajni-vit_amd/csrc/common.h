@@ -234,8 +234,13 @@ int launch_gather_rows(const void* src, const int32_t* idx, void* dst, int B, in
 // final norm written to the rows of the unpruned sequence [B, S, C] they name, zeros elsewhere
 int launch_source_idx(int32_t* src, const int32_t* const* idx, const int* width, const int* nsrc, int n_levels, int B, int Nf,
                       hipStream_t s);
+// (zero_fill = 0, RAJNI_POOL_DENSE_LAST: the rows src does not name are left as they are)
 int launch_layernorm_dense(const void* x, const int32_t* src, const float* w, const float* b, void* y, int B, int Nf, int S,
-                           int C, float eps, int x_f32, int dtype, hipStream_t s);
+                           int C, float eps, int x_f32, int dtype, hipStream_t s, int zero_fill = 1);
+// RAJNI_POOL_DENSE_LAST: the patch rows of the stream x [B, N, C] that the selection keep [B, Np] drops, through the final norm to
+// row src[b, j] of y [B, S, C]; src [B, N] = where each token of x sat in the unpruned sequence
+int launch_layernorm_dropped(const void* x, const int32_t* keep, const int32_t* src, const float* w, const float* b, void* y,
+                             int B, int N, int Np, int P, int S, int C, float eps, int x_f32, int dtype, hipStream_t s);
 // variants.hip: the timm options of rajni_vit_ext (b pointers may be NULL = no bias; nw / fw NULL = that norm is absent)
 int launch_qk_norm(void* qkv, const float* qw, const float* qb, const float* kw, const float* kb, int rows, int H, int D,
                    float eps, int dtype, hipStream_t s);

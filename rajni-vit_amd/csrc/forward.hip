@@ -19,7 +19,10 @@
 // The tail is final norm -> pool -> fc_norm -> head GEMM.  A headless plan (head_w NULL, num_classes 0) stops in front of the
 // GEMM and lets the norm launch write the caller's buffer; on such a plan ext.pool = RAJNI_POOL_NONE normalises every surviving
 // row into it, and RAJNI_POOL_DENSE scatters them back to the unpruned sequence (source_idx_kernel + layernorm_dense_kernel,
-// rowops.hip).  The logits path issues the launches it always did.
+// rowops.hip).  RAJNI_POOL_DENSE_LAST fills the pruned positions as well: behind the tail of every scheduled block the rows the
+// block drops - still in the stream buffer its residual gather read from - go through the final norm to their source rows
+// (source_idx_kernel + layernorm_dropped_kernel), and the final launch stores the survivors only.  The logits path and the
+// other outputs issue the launches they always did.
 #include "common.h"
 
 #include <vector>
@@ -98,9 +101,12 @@ int check_placement(const rajni_vit_plan& p, const void* images, const void* log
   return RAJNI_OK;
 }
 
-// no head: the buffer passed as `logits` receives the row the head would have read, or the tokens (RAJNI_POOL_NONE / _DENSE)
+// no head: the buffer passed as `logits` receives the row the head would have read, or the tokens (RAJNI_POOL_NONE / _DENSE /
+// _DENSE_LAST)
 inline bool headless(const rajni_vit_plan& p) { return p.head_w == nullptr && p.num_classes == 0; }
-inline bool pool_is_tokens(const rajni_vit_ext* e) { return e && (e->pool == RAJNI_POOL_NONE || e->pool == RAJNI_POOL_DENSE); }
+inline bool pool_is_tokens(const rajni_vit_ext* e) {
+  return e && (e->pool == RAJNI_POOL_NONE || e->pool == RAJNI_POOL_DENSE || e->pool == RAJNI_POOL_DENSE_LAST);
+}
 
 int check_plan(const rajni_vit_plan& p, bool norm_absent) {
   RAJNI_REQUIRE(p.dtype == RAJNI_BF16 || p.dtype == RAJNI_F32 || p.dtype == RAJNI_F16, RAJNI_ERR_INVALID,
@@ -139,13 +145,14 @@ int check_plan(const rajni_vit_plan& p, bool norm_absent) {
 }
 
 int check_ext(const rajni_vit_plan& p, const rajni_vit_ext& e) {
-  // (RAJNI_POOL_NONE and RAJNI_POOL_DENSE, the token outputs, are legal too; the wording of this refusal is what callers match on)
-  RAJNI_REQUIRE(e.pool >= RAJNI_POOL_TOKEN && e.pool <= RAJNI_POOL_DENSE, RAJNI_ERR_UNSUPPORTED,
+  // (RAJNI_POOL_NONE, RAJNI_POOL_DENSE and RAJNI_POOL_DENSE_LAST, the token outputs, are legal too - 4 is not; the wording of this
+  // refusal is what callers match on)
+  RAJNI_REQUIRE((e.pool >= RAJNI_POOL_TOKEN && e.pool <= RAJNI_POOL_DENSE) || e.pool == RAJNI_POOL_DENSE_LAST, RAJNI_ERR_UNSUPPORTED,
                 "rajni_vit_forward_ext: pool must be RAJNI_POOL_TOKEN or RAJNI_POOL_AVG (%d)", e.pool);
   RAJNI_REQUIRE(!(e.pool == RAJNI_POOL_AVG && p.cls_only_last_block), RAJNI_ERR_INVALID,
                 "rajni_vit_forward_ext: 'avg' pooling with cls_only_last_block - that opt-in never forms the rows to be averaged");
   if (pool_is_tokens(&e)) {
-    const char* name = e.pool == RAJNI_POOL_NONE ? "RAJNI_POOL_NONE" : "RAJNI_POOL_DENSE";
+    const char* name = e.pool == RAJNI_POOL_NONE ? "RAJNI_POOL_NONE" : e.pool == RAJNI_POOL_DENSE ? "RAJNI_POOL_DENSE" : "RAJNI_POOL_DENSE_LAST";
     RAJNI_REQUIRE(headless(p), RAJNI_ERR_UNSUPPORTED,
                   "rajni_vit_forward_ext: %s needs a headless plan (head_w NULL, num_classes 0) - per-token classification is "
                   "not implemented", name);
@@ -349,12 +356,27 @@ int check_schedule(const rajni_vit_plan& p, int P) {
   return RAJNI_OK;
 }
 
-// src [B, Nf] = where each token of the final stream sat in the unpruned sequence: the scheduled blocks' selections (the
-// forced one where a block has it), last block first
-int launch_final_source_idx(const rajni_vit_plan& p, int P, int32_t* src, int Nf, hipStream_t s) {
+// RAJNI_POOL_DENSE_LAST: the refusals of a token output that check_plan, check_head_rows and check_schedule word without the
+// pool, here under its name and with their codes
+int check_dense_last(const rajni_vit_plan& p, const rajni_vit_prefix* pre) {
+  const char* who = "rajni_vit_forward_ext: RAJNI_POOL_DENSE_LAST";
+  RAJNI_REQUIRE(!p.act_fp8, RAJNI_ERR_UNSUPPORTED, "%s is unsupported with act_fp8", who);
+  RAJNI_REQUIRE(head_row_count(pre) != 2, RAJNI_ERR_UNSUPPORTED,
+                "%s with head_rows=2 - the two rows exist to feed the averaged heads, and a token output has no head", who);
+  const int ld = p.logits_ld;
+  RAJNI_REQUIRE(ld == 0 || (ld % 8 == 0 && ld >= p.C), RAJNI_ERR_INVALID,
+                "%s: logits row stride must be a multiple of 8 and >= C (%d, C = %d)", who, ld, p.C);
+  RAJNI_REQUIRE(ld == 0 || ld == p.C, RAJNI_ERR_UNSUPPORTED, "%s writes dense rows: logits row stride must be 0 or C (%d, C = %d)",
+                who, ld, p.C);
+  return RAJNI_OK;
+}
+
+// src [B, Nf] = where each token of the stream that enters block `upto` (p.depth: the final stream) sat in the unpruned
+// sequence: the selections of the scheduled blocks in front of it (the forced one where a block has it), last block first
+int launch_source_idx_before(const rajni_vit_plan& p, int P, int upto, int32_t* src, int Nf, hipStream_t s) {
   std::vector<const int32_t*> idx;
   std::vector<int> width, nsrc;
-  for (int i = p.depth - 1; i >= 0; --i) {
+  for (int i = upto - 1; i >= 0; --i) {
     const rajni_block& blk = p.blocks[i];
     if (blk.keep <= 0) continue;
     idx.push_back(blk.forced_keep_idx ? blk.forced_keep_idx : blk.keep_idx);
@@ -415,7 +437,10 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
                 void* logits, hipStream_t s) {
   RAJNI_REQUIRE(plan && images && logits, RAJNI_ERR_INVALID, "rajni_vit_forward: null pointer");
   const rajni_vit_plan& p = *plan;
-  int rc = check_plan(p, ext != nullptr && ext->norm_absent != 0);
+  const bool dense_last = ext != nullptr && ext->pool == RAJNI_POOL_DENSE_LAST;
+  int rc = dense_last ? check_dense_last(p, pre) : RAJNI_OK;
+  if (rc != RAJNI_OK) return rc;
+  rc = check_plan(p, ext != nullptr && ext->norm_absent != 0);
   if (rc != RAJNI_OK) return rc;
   rc = check_placement(p, images, logits);
   if (rc != RAJNI_OK) return rc;
@@ -558,6 +583,17 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
     char* y = idx ? oth : cur;
     rc = launch_tail(f, blk, tail_args(f, blk, AttnRows{B * Np, C, att8 ? w.xs : nullptr, C, idx, Np, N}, cur, y));
     if (rc != RAJNI_OK) return rc;
+    if (idx && dense_last) {
+      // the rows this block drops leave the stream here and keep the state they entered with: `cur` still holds it (the tail
+      // gathered the kept rows into `oth`).  Where each entering token sat in the unpruned sequence goes to w.qkv, dead
+      // between the tail and the next block's QKV GEMM (B * N * 4 bytes always fit); then the final norm of the dropped rows
+      int32_t* src = reinterpret_cast<int32_t*>(w.qkv);
+      rc = launch_source_idx_before(p, P, i, src, N, s);
+      if (rc != RAJNI_OK) return rc;
+      rc = launch_layernorm_dropped(cur, idx, src, p.norm_w, p.norm_b, logits, B, N, Np, P, tokens_entering(p, P, 0), C, p.ln_eps,
+                                    f.sf32, dt, s);
+      if (rc != RAJNI_OK) return rc;
+    }
     if (idx) { oth = cur; cur = y; }
     N = Np;
   }
@@ -568,13 +604,15 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
   void* const rowout = headless(p) ? logits : (void*)w.clsn;
   if (ext && ext->pool == RAJNI_POOL_NONE)   // every surviving token through the final norm: [B, N, C]
     return launch_layernorm(cur, C, p.norm_w, p.norm_b, logits, B * N, C, p.ln_eps, f.sf32, dt, s);
-  if (ext && ext->pool == RAJNI_POOL_DENSE) {
-    // [B, P + n, C]: token j of the final stream at the row it came from, zeros elsewhere.  The composed selection lives in
-    // w.qkv, dead behind the last block (B * N * 4 bytes always fit)
+  if (ext && (ext->pool == RAJNI_POOL_DENSE || dense_last)) {
+    // [B, P + n, C]: token j of the final stream at the row it came from, zeros elsewhere (RAJNI_POOL_DENSE_LAST: the other
+    // rows were written behind the blocks that dropped them and stay).  The composed selection lives in w.qkv, dead behind
+    // the last block (B * N * 4 bytes always fit)
     int32_t* src = reinterpret_cast<int32_t*>(w.qkv);
-    rc = launch_final_source_idx(p, P, src, N, s);
+    rc = launch_source_idx_before(p, P, p.depth, src, N, s);
     if (rc != RAJNI_OK) return rc;
-    return launch_layernorm_dense(cur, src, p.norm_w, p.norm_b, logits, B, N, tokens_entering(p, P, 0), C, p.ln_eps, f.sf32, dt, s);
+    return launch_layernorm_dense(cur, src, p.norm_w, p.norm_b, logits, B, N, tokens_entering(p, P, 0), C, p.ln_eps, f.sf32, dt, s,
+                                  dense_last ? 0 : 1);
   }
   if (ext && (ext->pool != RAJNI_POOL_TOKEN || ext->fc_norm_w || ext->norm_absent))
     rc = launch_pool_norm(cur, B, N, C, ext->pool, ext->norm_absent ? nullptr : p.norm_w, p.norm_b, p.ln_eps,

@@ -395,7 +395,8 @@ __global__ void __launch_bounds__(256) source_idx_kernel(int32_t* __restrict__ s
 // selection is ascending), so the wave binary-searches it for s - wave-uniform: the row index is made scalar, the search runs
 // on the scalar unit.  A hit is layernorm_kernel's arithmetic instruction for instruction (load8, two-pass fp32 statistics,
 // wave_sum in the same order, fmaf((v - mean) * rstd, w, b)): the same bits.  16-byte stores either way.
-template <typename TX, typename TY>
+// ZERO = false (RAJNI_POOL_DENSE_LAST): a miss stores nothing - layernorm_dropped_kernel wrote that row when its token left.
+template <typename TX, typename TY, bool ZERO = true>
 __global__ void __launch_bounds__(256) layernorm_dense_kernel(const TX* __restrict__ x, const int32_t* __restrict__ src,
                                                               const float* __restrict__ w, const float* __restrict__ b,
                                                               TY* __restrict__ y, int B, int Nf, int S, int C, float eps) {
@@ -413,11 +414,13 @@ __global__ void __launch_bounds__(256) layernorm_dense_kernel(const TX* __restri
   const int nchunk = C >> 3;
   TY* yr = y + row * C;
   if (!hit) {
-    const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if constexpr (ZERO) {
+      const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
-      const int c = lane + i * 64;
-      if (c < nchunk) store8<TY>(yr + c * 8, z);
+      for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
+        const int c = lane + i * 64;
+        if (c < nchunk) store8<TY>(yr + c * 8, z);
+      }
     }
     return;
   }
@@ -456,6 +459,77 @@ __global__ void __launch_bounds__(256) layernorm_dense_kernel(const TX* __restri
       load8<float>(b + c * 8, bv);
 #pragma unroll
       for (int j = 0; j < 8; ++j) o[j] = fmaf((v[i][j] - mean) * rstd, wv[j], bv[j]);
+      store8<TY>(yr + c * 8, o);
+    }
+  }
+}
+
+// ---- RAJNI_POOL_DENSE_LAST (forward.hip): the rows a scheduled block drops, through the final norm, at their source rows ----
+// x [B, N, C] is the stream that ENTERED the block, keep [B, Np] the block's selection (P prefix slots, then strictly
+// ascending patch indices), src [B, N] the position in the unpruned sequence of each entering token (the earlier blocks'
+// selections composed).  One wave per INPUT row (b, j), j >= P: the wave binary-searches keep[b, P:] for j, wave-uniform on
+// the scalar unit as layernorm_dense_kernel searches src.  A hit (the token stays) stores nothing; a miss writes
+// y[b, src[b, j], :] = norm(x[b, j, :]) with layernorm_kernel's arithmetic instruction for instruction (load8, two-pass fp32
+// statistics, wave_sum in the same order, fmaf((v - mean) * rstd, w, b)): the bits layernorm_dense_kernel gives the same row.
+// What is read from keep and src is clamped as source_idx_kernel clamps: keep values are only compared, and a src value
+// outside [0, S) cannot form an address outside y.
+template <typename TX, typename TY>
+__global__ void __launch_bounds__(256) layernorm_dropped_kernel(const TX* __restrict__ x, const int32_t* __restrict__ keep,
+                                                                const int32_t* __restrict__ src, const float* __restrict__ w,
+                                                                const float* __restrict__ b, TY* __restrict__ y, int B, int N,
+                                                                int Np, int P, int S, int C, float eps) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int patches = N - P;
+  const long row = (long)blockIdx.x * 4 + wave;
+  if (row >= (long)B * patches) return;
+  const int img = (int)(row / patches), j = P + (int)(row - (long)img * patches);
+  const int32_t* kb = keep + (long)img * Np;
+  auto kept = [&](int slot) { const int k = kb[slot]; return k < 0 ? 0 : (k >= N ? N - 1 : k); };
+  int lo = P, hi = Np;                    // the first slot in [P, Np) with kept(slot) >= j
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (kept(mid) < j) lo = mid + 1; else hi = mid;
+  }
+  if (lo < Np && kept(lo) == j) return;   // kept: the row travels on
+  int s = src[(long)img * N + j];
+  s = s < 0 ? 0 : (s >= S ? S - 1 : s);
+  const int nchunk = C >> 3;
+  const TX* xr = x + ((long)img * N + j) * C;
+  float v[LN_MAX_CHUNKS][8];
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
+    const int c = lane + i * 64;
+    if (c < nchunk) {
+      load8<TX>(xr + c * 8, v[i]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sum += v[i][e];
+    }
+  }
+  const float mean = wave_sum(sum) / (float)C;
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
+    const int c = lane + i * 64;
+    if (c < nchunk) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float d = v[i][e] - mean;
+        ss += d * d;
+      }
+    }
+  }
+  const float rstd = rsqrtf(wave_sum(ss) / (float)C + eps);
+  TY* yr = y + ((long)img * S + s) * C;
+#pragma unroll
+  for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
+    const int c = lane + i * 64;
+    if (c < nchunk) {
+      float wv[8], bv[8], o[8];
+      load8<float>(w + c * 8, wv);
+      load8<float>(b + c * 8, bv);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = fmaf((v[i][e] - mean) * rstd, wv[e], bv[e]);
       store8<TY>(yr + c * 8, o);
     }
   }
@@ -566,10 +640,26 @@ int launch_source_idx(int32_t* src, const int32_t* const* idx, const int* width,
   return RAJNI_OK;
 }
 
+template <bool ZERO>
+static void launch_dense_kernels(dim3 grid, dim3 block, const void* x, const int32_t* src, const float* w, const float* b, void* y,
+                                 int B, int Nf, int S, int C, float eps, int x_f32, int dtype, hipStream_t s) {
+  if (dtype == RAJNI_F32)
+    hipLaunchKernelGGL((layernorm_dense_kernel<float, float, ZERO>), grid, block, 0, s, (const float*)x, src, w, b, (float*)y, B, Nf, S, C, eps);
+  else if (dtype == RAJNI_F16 && x_f32)
+    hipLaunchKernelGGL((layernorm_dense_kernel<float, f16_t, ZERO>), grid, block, 0, s, (const float*)x, src, w, b, (f16_t*)y, B, Nf, S, C, eps);
+  else if (dtype == RAJNI_F16)
+    hipLaunchKernelGGL((layernorm_dense_kernel<f16_t, f16_t, ZERO>), grid, block, 0, s, (const f16_t*)x, src, w, b, (f16_t*)y, B, Nf, S, C, eps);
+  else if (x_f32)
+    hipLaunchKernelGGL((layernorm_dense_kernel<float, bf16_t, ZERO>), grid, block, 0, s, (const float*)x, src, w, b, (bf16_t*)y, B, Nf, S, C, eps);
+  else
+    hipLaunchKernelGGL((layernorm_dense_kernel<bf16_t, bf16_t, ZERO>), grid, block, 0, s, (const bf16_t*)x, src, w, b, (bf16_t*)y, B, Nf, S, C, eps);
+}
+
 // y [B, S, C] `dtype`: row src[b, j] of image b = LayerNorm(x[b, j]) for the Nf rows of the stream x [B, Nf, C] (fp32 when x_f32,
-// else `dtype`), every other row zero.  src [B, Nf] strictly ascending per image, values in [0, S).
+// else `dtype`), every other row zero - or, with zero_fill == 0 (RAJNI_POOL_DENSE_LAST), left as it is.  src [B, Nf] strictly
+// ascending per image, values in [0, S).
 int launch_layernorm_dense(const void* x, const int32_t* src, const float* w, const float* b, void* y, int B, int Nf, int S,
-                           int C, float eps, int x_f32, int dtype, hipStream_t s) {
+                           int C, float eps, int x_f32, int dtype, hipStream_t s, int zero_fill) {
   RAJNI_REQUIRE(x && src && w && b && y, RAJNI_ERR_INVALID, "layernorm_dense: null pointer");
   RAJNI_REQUIRE(B > 0 && Nf > 0 && S >= Nf && C > 0 && C % 8 == 0 && C <= 64 * 8 * LN_MAX_CHUNKS, RAJNI_ERR_UNSUPPORTED,
                 "layernorm_dense: need C %% 8 == 0, C <= 2048 and 0 < Nf <= S (C=%d Nf=%d S=%d)", C, Nf, S);
@@ -577,18 +667,36 @@ int launch_layernorm_dense(const void* x, const int32_t* src, const float* w, co
   RAJNI_REQUIRE((rows + 3) / 4 < (1L << 31), RAJNI_ERR_UNSUPPORTED, "layernorm_dense: too many output rows (%ld)", rows);
   const bool f32io = dtype == RAJNI_F32;
   const double eb = f32io ? 4.0 : 2.0, xb = (f32io || x_f32) ? 4.0 : 2.0;
-  ProfScope prof(KC_LAYERNORM, s, 8.0 * B * Nf * C, xb * B * Nf * C + eb * rows * C);
+  ProfScope prof(KC_LAYERNORM, s, 8.0 * B * Nf * C, xb * B * Nf * C + eb * (zero_fill ? rows : (long)B * Nf) * C);
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-  if (f32io)
-    hipLaunchKernelGGL((layernorm_dense_kernel<float, float>), grid, block, 0, s, (const float*)x, src, w, b, (float*)y, B, Nf, S, C, eps);
-  else if (dtype == RAJNI_F16 && x_f32)
-    hipLaunchKernelGGL((layernorm_dense_kernel<float, f16_t>), grid, block, 0, s, (const float*)x, src, w, b, (f16_t*)y, B, Nf, S, C, eps);
-  else if (dtype == RAJNI_F16)
-    hipLaunchKernelGGL((layernorm_dense_kernel<f16_t, f16_t>), grid, block, 0, s, (const f16_t*)x, src, w, b, (f16_t*)y, B, Nf, S, C, eps);
-  else if (x_f32)
-    hipLaunchKernelGGL((layernorm_dense_kernel<float, bf16_t>), grid, block, 0, s, (const float*)x, src, w, b, (bf16_t*)y, B, Nf, S, C, eps);
-  else
-    hipLaunchKernelGGL((layernorm_dense_kernel<bf16_t, bf16_t>), grid, block, 0, s, (const bf16_t*)x, src, w, b, (bf16_t*)y, B, Nf, S, C, eps);
+  if (zero_fill) launch_dense_kernels<true>(grid, block, x, src, w, b, y, B, Nf, S, C, eps, x_f32, dtype, s);
+  else launch_dense_kernels<false>(grid, block, x, src, w, b, y, B, Nf, S, C, eps, x_f32, dtype, s);
   RAJNI_CHECK_LAUNCH("layernorm_dense_kernel");
+  return RAJNI_OK;
+}
+
+// RAJNI_POOL_DENSE_LAST: y [B, S, C] `dtype` receives row src[b, j] = LayerNorm(x[b, j]) for every patch token j of the stream
+// x [B, N, C] (fp32 when x_f32, else `dtype`) that the selection keep [B, Np] does NOT name; no other row is touched.  keep
+// holds P prefix slots, then strictly ascending patch indices; src [B, N] holds values in [0, S).
+int launch_layernorm_dropped(const void* x, const int32_t* keep, const int32_t* src, const float* w, const float* b, void* y,
+                             int B, int N, int Np, int P, int S, int C, float eps, int x_f32, int dtype, hipStream_t s) {
+  RAJNI_REQUIRE(x && keep && src && w && b && y, RAJNI_ERR_INVALID, "layernorm_dropped: null pointer");
+  RAJNI_REQUIRE(B > 0 && P > 0 && P < Np && Np <= N && N <= S && C > 0 && C % 8 == 0 && C <= 64 * 8 * LN_MAX_CHUNKS,
+                RAJNI_ERR_UNSUPPORTED, "layernorm_dropped: need C %% 8 == 0, C <= 2048 and 0 < P < Np <= N <= S (C=%d P=%d Np=%d N=%d S=%d)",
+                C, P, Np, N, S);
+  const long rows = (long)B * (N - P), dropped = (long)B * (N - Np);
+  RAJNI_REQUIRE((rows + 3) / 4 < (1L << 31), RAJNI_ERR_UNSUPPORTED, "layernorm_dropped: too many rows (%ld)", rows);
+  const bool f32io = dtype == RAJNI_F32;
+  ProfScope prof(KC_LAYERNORM, s, 8.0 * dropped * C, ((f32io || x_f32 ? 4.0 : 2.0) + (f32io ? 4.0 : 2.0)) * dropped * C);
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+#define RAJNI_LN_DROPPED(TX, TY)                                                                                            \
+  hipLaunchKernelGGL((layernorm_dropped_kernel<TX, TY>), grid, block, 0, s, (const TX*)x, keep, src, w, b, (TY*)y, B, N, Np, P, S, C, eps)
+  if (f32io) RAJNI_LN_DROPPED(float, float);
+  else if (dtype == RAJNI_F16 && x_f32) RAJNI_LN_DROPPED(float, f16_t);
+  else if (dtype == RAJNI_F16) RAJNI_LN_DROPPED(f16_t, f16_t);
+  else if (x_f32) RAJNI_LN_DROPPED(float, bf16_t);
+  else RAJNI_LN_DROPPED(bf16_t, bf16_t);
+#undef RAJNI_LN_DROPPED
+  RAJNI_CHECK_LAUNCH("layernorm_dropped_kernel");
   return RAJNI_OK;
 }

@@ -21,6 +21,7 @@ EPI_BIAS_SWIGLU = 18          # y [M, N] = silu(x Wg^T + bg) * (x Wv^T + bv), w 
 NUM_KCLASS = 17
 POOL_TOKEN, POOL_AVG = 0, 1
 POOL_NONE, POOL_DENSE = 2, 3         # headless plans only: every surviving token [B, Nf, C] / scattered back to [B, P + n, C]
+POOL_DENSE_LAST = 5                  # ... scattered back, pruned positions holding the token's state at the block that dropped it; 4 is unknown
 MLP_GELU, MLP_QUICK_GELU = 0, 1      # rajni_vit_ext.mlp_act
 MLP_SWIGLU = 3                       # ... the gated FC1 (fc1_w [2 * hidden, C]); 2 is an unknown value
 

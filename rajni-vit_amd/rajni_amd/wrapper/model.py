@@ -11,8 +11,8 @@ timm's register tokens (`reg_tokens=R`: `reg_token` [1, R, C] behind the class t
 DeiT's distilled models (timm `VisionTransformerDistilled`: `dist_token` behind the class token, a prefix token like a
 register, and eval logits `(head(x[:, 0]) + head_dist(x[:, 1])) / 2`).  Beyond the reference's surface: a headless base model
 (`head = nn.Identity`, timm num_classes=0) returns its pooled feature [B, C], and `forward_features(x, dense=False)` returns the
-final normalised tokens of the pruned graph, or the unpruned sequence with pruned positions zero, with their source positions in
-`get_last_stats()["source_idx"]`.
+final normalised tokens of the pruned graph, or the unpruned sequence with pruned positions zero (`fill="last"`: holding the
+feature each token had when it left the stream), with their source positions in `get_last_stats()["source_idx"]`.
 
 Not kept: the Python per-block loop.  `forward` builds (once per batch shape) a `rajni_vit_plan`
 - packed weights, workspace, per-stage index buffers - and calls `rajni_vit_forward`, which enqueues
@@ -49,6 +49,20 @@ def plan_token_counts(n0: int, depth: int, schedule: Dict[int, Dict], num_prefix
         if i in schedule:
             n = ops.keep_count(schedule[i]["keep_ratio"], n, num_prefix) + num_prefix
     return counts
+
+
+def compose_exit_block(selections: Dict[int, torch.Tensor], B: int, n0: int, depth: int, device) -> torch.Tensor:
+    """{scheduled block: keep_idx [B, P + keep]} -> int32 [B, n0]: the block that drops the token of each position of the
+    unpruned sequence, `depth` for the tokens that survive.  Block by block: every token that enters scheduled block i is
+    marked i at its source position, and the ones the block keeps are marked again further on - by the next scheduled block,
+    or `depth` at the end.  Torch ops on `device`, no host sync."""
+    pos = torch.arange(n0, device=device).expand(B, n0)
+    exit_block = torch.full((B, n0), depth, dtype=torch.int32, device=device)
+    for i in sorted(selections):
+        exit_block.scatter_(1, pos, torch.full_like(pos, i, dtype=torch.int32))
+        pos = torch.gather(pos, 1, selections[i].long())
+    exit_block.scatter_(1, pos, torch.full_like(pos, depth, dtype=torch.int32))
+    return exit_block
 
 
 def model_is_distilled(m: nn.Module) -> bool:
@@ -622,8 +636,8 @@ class RAJNIViTWrapper(nn.Module):
 
     def _build_plan(self, B: int, S: int, device, dtype, mode: str = "logits"):
         """`mode`: "logits" (the model's forward: logits, or the pooled feature of a headless model), or the feature outputs
-        "tokens" / "dense" (forward_features): a second plan of the same packed weights with no head and
-        ext.pool = POOL_NONE / POOL_DENSE."""
+        "tokens" / "dense" / "dense_last" (forward_features): a second plan of the same packed weights with no head and
+        ext.pool = POOL_NONE / POOL_DENSE / POOL_DENSE_LAST."""
         W = self._pack_weights(device, dtype)
         d = W["desc"]
         P = d["num_prefix"]
@@ -728,13 +742,14 @@ class RAJNIViTWrapper(nn.Module):
             ext.norm_absent = int(not d["norm"])
             ext.pool = nat.POOL_AVG if d["pool"] == "avg" else nat.POOL_TOKEN
             if features:      # timm forward_features ends at norm(x): no pool, no fc_norm
-                ext.pool = nat.POOL_DENSE if mode == "dense" else nat.POOL_NONE
+                ext.pool = {"tokens": nat.POOL_NONE, "dense": nat.POOL_DENSE, "dense_last": nat.POOL_DENSE_LAST}[mode]
                 ext.fc_norm_w = ext.fc_norm_b = None
             ext.mlp_act = {"quick_gelu": nat.MLP_QUICK_GELU, "swiglu": nat.MLP_SWIGLU}.get(d["mlp_act"], nat.MLP_GELU)
         # what `logits` receives: [B, logits_ld], or the tokens behind the last block / the unpruned sequence's rows
         n_last = counts[-1] if (d["depth"] - 1) not in self.pruning_schedule else \
             ops.keep_count(self.pruning_schedule[d["depth"] - 1]["keep_ratio"], counts[-1], P) + P
-        out_shape = {"logits": (B, plan.logits_ld), "tokens": (B, n_last, d["C"]), "dense": (B, n0, d["C"])}[mode]
+        out_shape = {"logits": (B, plan.logits_ld), "tokens": (B, n_last, d["C"]), "dense": (B, n0, d["C"]),
+                     "dense_last": (B, n0, d["C"])}[mode]
         # W: a stale optimistic launch keeps its weights alive
         # (existing callers index entry[0..4] and unpack entry[2] as seven objects: mode and out_shape go behind `counts`)
         self._plan = (key, plan, (blocks, tc, ws, W, ext, qk, pre), bufs, counts, mode, out_shape)
@@ -765,14 +780,23 @@ class RAJNIViTWrapper(nn.Module):
         return out[:, : plan.num_classes] if plan.logits_ld != plan.num_classes else out
 
     @torch.no_grad()
-    def forward_features(self, x: torch.Tensor, dense: bool = False) -> torch.Tensor:
+    def forward_features(self, x: torch.Tensor, dense: bool = False, fill: str = "zero") -> torch.Tensor:
         """timm's forward_features on the pruned graph, norm(x), for every model the wrapper supports (with or without a head):
         `dense=False`: [B, Nf, C], the tokens that survive the last block, in stream order;
         `dense=True`:  [B, P + n, C], the unpruned sequence's shape - every surviving token at the position it came from, pruned
-                       positions zero.
+                       positions zero;
+        `dense=True, fill="last"`: the same, but a token that scheduled block i drops keeps the feature it had when it left:
+                       its position holds norm(x_entry_i), the final norm of the residual stream at the entry of block i (as
+                       DINOv2's get_intermediate_layers(norm=True) normalises intermediate states).  No row is zero.
         Afterwards `get_last_stats()["source_idx"]` is an int32 device tensor [B, Nf]: the position in the unpruned sequence of
-        each surviving row (slots 0..P-1 are the prefix tokens 0..P-1, the rest strictly ascending), in both modes."""
-        out, entry = self._run(x, "dense" if dense else "tokens")
+        each surviving row (slots 0..P-1 are the prefix tokens 0..P-1, the rest strictly ascending), in every mode; with
+        `fill="last"` there is `"exit_block"` too, int32 [B, P + n] on the device: the scheduled block that dropped the token of
+        each position, `depth` for the survivors."""
+        if fill not in ("zero", "last"):
+            raise ValueError(f'forward_features: fill must be "zero" or "last", got {fill!r}')
+        if fill == "last" and not dense:
+            raise ValueError('forward_features: fill="last" fills the pruned positions of the dense output; it needs dense=True')
+        out, entry = self._run(x, ("dense_last" if fill == "last" else "dense") if dense else "tokens")
         P, n0 = entry[0][-2], entry[4][0]
         src = None            # the selections composed on the device, last stage first: no host sync
         for i in sorted(entry[3], reverse=True):
@@ -781,6 +805,9 @@ class RAJNIViTWrapper(nn.Module):
         if src is None:
             src = torch.arange(n0, device=x.device).expand(x.shape[0], n0)
         self._last_stats["source_idx"] = src.to(torch.int32).contiguous()
+        if fill == "last":
+            self._last_stats["exit_block"] = compose_exit_block(
+                {i: self._forced.get(i, entry[3][i]["keep_idx"]) for i in entry[3]}, x.shape[0], n0, entry[1].depth, x.device)
         return out
 
     def _run(self, x: torch.Tensor, mode: str):
