@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include "../../include/rajni_hip.h"
 #include "../../include/rajni_hip_debug.h"
+#include "../../include/rajni_hip_layers.h"
 
 typedef unsigned short bf16_t;  // raw bf16 bits in memory
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -241,6 +242,13 @@ int launch_layernorm_dense(const void* x, const int32_t* src, const float* w, co
 // row src[b, j] of y [B, S, C]; src [B, N] = where each token of x sat in the unpruned sequence
 int launch_layernorm_dropped(const void* x, const int32_t* keep, const int32_t* src, const float* w, const float* b, void* y,
                              int B, int N, int Np, int P, int S, int C, float eps, int x_f32, int dtype, hipStream_t s);
+// rajni_vit_forward_layers: launch_layernorm_dense without the norm (the stream row rounded once to `dtype`), and
+// launch_layernorm_dropped to the `ny` outputs ys[k] [B, S, C] at once (a host array), through the norm or cast only
+int launch_rows_dense_cast(const void* x, const int32_t* src, void* y, int B, int Nf, int S, int C, int x_f32, int dtype,
+                           hipStream_t s, int zero_fill = 1);
+int launch_rows_dropped_multi(const void* x, const int32_t* keep, const int32_t* src, const float* w, const float* b,
+                              void* const* ys, int ny, int norm, int B, int N, int Np, int P, int S, int C, float eps, int x_f32,
+                              int dtype, hipStream_t s);
 // variants.hip: the timm options of rajni_vit_ext (b pointers may be NULL = no bias; nw / fw NULL = that norm is absent)
 int launch_qk_norm(void* qkv, const float* qw, const float* qb, const float* kw, const float* kb, int rows, int H, int D,
                    float eps, int dtype, hipStream_t s);

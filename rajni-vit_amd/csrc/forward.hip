@@ -23,6 +23,11 @@
 // block drops - still in the stream buffer its residual gather read from - go through the final norm to their source rows
 // (source_idx_kernel + layernorm_dropped_kernel), and the final launch stores the survivors only.  The logits path and the
 // other outputs issue the launches they always did.
+//
+// rajni_vit_forward_layers (rajni_hip_layers.h) adds capture points to the block loop: behind the tail of a captured block the
+// stream goes to that block's slab on the unpruned grid (source_idx_kernel + layernorm_dense_kernel or rows_dense_cast_kernel),
+// and with fill = 1 every scheduled block writes the rows it drops to the slabs of all captures at or behind it in one launch
+// (rows_dropped_multi_kernel).  Whatever the plan writes to `logits` it writes unchanged; a NULL record adds nothing.
 #include "common.h"
 
 #include <vector>
@@ -197,9 +202,10 @@ int g_last_block_all_rows = 0;
 // last block that prunes (its selection is part of the trace), an avg-pooled head (reads every row), act_fp8 plans and
 // the cls_only_last_block opt-in (they keep the opt-in's own branch and numerics contract).  With the distilled head
 // (head_rows == 2) the observable rows are 0 and 1 of each image, and the block runs on those 2B rows under the same test.
-inline bool last_block_cls_rows(const rajni_vit_plan& p, const rajni_vit_ext* ext, int i, int N) {
+// Nor for a last block whose output rajni_vit_forward_layers captures (`captured`): the slab reads every row.
+inline bool last_block_cls_rows(const rajni_vit_plan& p, const rajni_vit_ext* ext, int i, int N, bool captured = false) {
   return i == p.depth - 1 && p.blocks[i].keep == 0 && N > 1 && (ext == nullptr || ext->pool == RAJNI_POOL_TOKEN) &&
-         !p.act_fp8 && !p.cls_only_last_block && !g_last_block_all_rows;
+         !p.act_fp8 && !p.cls_only_last_block && !g_last_block_all_rows && !captured;
 }
 
 // what is fixed for one forward, for the builders and launchers below
@@ -371,6 +377,31 @@ int check_dense_last(const rajni_vit_plan& p, const rajni_vit_prefix* pre) {
   return RAJNI_OK;
 }
 
+// the layers record against the plan and the ext record (rajni_hip_layers.h): host-side integer tests, in front of every other
+// refusal of the forward
+int check_layers(const rajni_vit_plan& p, const rajni_vit_ext* e, int P, const rajni_vit_layers& y) {
+  const char* who = "rajni_vit_forward_layers";
+  RAJNI_REQUIRE(y.n >= 1 && y.n <= RAJNI_MAX_LAYERS, RAJNI_ERR_INVALID, "%s: layers.n must be 1..%d (%d)", who, RAJNI_MAX_LAYERS, y.n);
+  RAJNI_REQUIRE(y.blocks != nullptr && y.out != nullptr, RAJNI_ERR_INVALID, "%s: null pointer (layers.%s)", who,
+                y.blocks ? "out" : "blocks");
+  RAJNI_REQUIRE(p.depth > 0 && p.B > 0 && p.C > 0 && p.patch_size > 0 && p.img_size >= p.patch_size, RAJNI_ERR_INVALID, "%s: bad plan", who);
+  for (int l = 0; l < y.n; ++l)
+    RAJNI_REQUIRE(y.blocks[l] >= 0 && y.blocks[l] < p.depth && (l == 0 || y.blocks[l] > y.blocks[l - 1]), RAJNI_ERR_INVALID,
+                  "%s: layers.blocks must be strictly ascending block indices in [0, %d) (blocks[%d] = %d)", who, p.depth, l, y.blocks[l]);
+  RAJNI_REQUIRE(y.norm == 0 || y.norm == 1, RAJNI_ERR_INVALID, "%s: layers.norm must be 0 or 1 (%d)", who, y.norm);
+  RAJNI_REQUIRE(y.fill == 0 || y.fill == 1, RAJNI_ERR_INVALID, "%s: layers.fill must be 0 (zero rows) or 1 (last state) (%d)", who, y.fill);
+  const long long gw = p.img_size / p.patch_size, dense = (long long)p.B * (gw * gw + P) * p.C;
+  RAJNI_REQUIRE(y.slab_stride == 0 || (y.slab_stride >= dense && y.slab_stride % 8 == 0), RAJNI_ERR_INVALID,
+                "%s: layers.slab_stride must be 0 or a multiple of 8 that is >= B * (P + n) * C = %lld (%lld)", who, dense, y.slab_stride);
+  RAJNI_REQUIRE_PLACED(who, {"layers.out", y.out, 16});
+  RAJNI_REQUIRE(!(y.norm == 1 && e && e->norm_absent), RAJNI_ERR_UNSUPPORTED,
+                "%s: layers.norm = 1 on a plan without a final norm (ext.norm_absent) - norm = 0 gives the un-normalised states", who);
+  RAJNI_REQUIRE(!p.act_fp8, RAJNI_ERR_UNSUPPORTED, "%s is unsupported with act_fp8", who);
+  RAJNI_REQUIRE(!(p.cls_only_last_block && y.blocks[y.n - 1] == p.depth - 1), RAJNI_ERR_INVALID,
+                "%s: block %d captured with cls_only_last_block - that opt-in never forms the rows to be returned", who, p.depth - 1);
+  return RAJNI_OK;
+}
+
 // src [B, Nf] = where each token of the stream that enters block `upto` (p.depth: the final stream) sat in the unpruned
 // sequence: the selections of the scheduled blocks in front of it (the forced one where a block has it), last block first
 int launch_source_idx_before(const rajni_vit_plan& p, int P, int upto, int32_t* src, int Nf, hipStream_t s) {
@@ -389,7 +420,7 @@ int launch_source_idx_before(const rajni_vit_plan& p, int P, int upto, int32_t* 
 // the whole forward; ext == nullptr (rajni_vit_forward) and an all-zero record enqueue the same launches, and so does
 // pre == nullptr (or a record with one prefix token) next to any ext
 int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre, const void* images,
-                void* logits, hipStream_t s);
+                void* logits, hipStream_t s, const rajni_vit_layers* lay = nullptr);
 
 }  // namespace
 
@@ -420,6 +451,14 @@ extern "C" int rajni_vit_forward_ext_prefix(const rajni_vit_plan* plan, const ra
   return vit_forward(plan, ext, prefix, images, logits, (hipStream_t)stream);
 }
 
+extern "C" int rajni_vit_forward_layers(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
+                                        const rajni_vit_layers* layers, const void* images, void* logits, rajni_stream_t stream) {
+  if (!layers) return rajni_vit_forward_ext_prefix(plan, ext, prefix, images, logits, stream);
+  const int rc = check_prefix(prefix, "rajni_vit_forward_layers");
+  if (rc != RAJNI_OK) return rc;
+  return vit_forward(plan, ext, prefix, images, logits, (hipStream_t)stream, layers);
+}
+
 extern "C" void rajni_debug_set_last_block_all_rows(int on) { g_last_block_all_rows = on; }
 
 // 1 when the forward of this plan (with this ext / prefix record, either may be NULL) computes its last block for the rows the
@@ -434,11 +473,13 @@ extern "C" int rajni_debug_last_block_cls_rows(const rajni_vit_plan* plan, const
 namespace {
 
 int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre, const void* images,
-                void* logits, hipStream_t s) {
+                void* logits, hipStream_t s, const rajni_vit_layers* lay) {
   RAJNI_REQUIRE(plan && images && logits, RAJNI_ERR_INVALID, "rajni_vit_forward: null pointer");
   const rajni_vit_plan& p = *plan;
   const bool dense_last = ext != nullptr && ext->pool == RAJNI_POOL_DENSE_LAST;
-  int rc = dense_last ? check_dense_last(p, pre) : RAJNI_OK;
+  int rc = lay ? check_layers(p, ext, prefix_count(pre), *lay) : RAJNI_OK;
+  if (rc != RAJNI_OK) return rc;
+  rc = dense_last ? check_dense_last(p, pre) : RAJNI_OK;
   if (rc != RAJNI_OK) return rc;
   rc = check_plan(p, ext != nullptr && ext->norm_absent != 0);
   if (rc != RAJNI_OK) return rc;
@@ -479,6 +520,14 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
     RAJNI_CHECK_LAUNCH("head_rows_idx_kernel");
   }
 
+  // rajni_vit_forward_layers: slab l is lay->out + l * slab_ld elements; `cap` walks the ascending capture list with the
+  // block loop, so slabs [cap, n) are the ones a block at or in front of the next capture still writes to
+  const int S0 = tokens_entering(p, P, 0);
+  const size_t slab_ld = lay ? (lay->slab_stride ? (size_t)lay->slab_stride : (size_t)B * S0 * C) : 0;
+  auto slab = [&](int l) { return static_cast<void*>(static_cast<char*>(lay->out) + (size_t)l * slab_ld * rajni_elem_bytes(dt)); };
+  int cap = 0;
+  const bool last_captured = lay && lay->blocks[lay->n - 1] == p.depth - 1;
+
   char* cur = w.xa;
   char* oth = w.xb;
   const void* carried = nullptr;  // scores of the tokens currently in `cur` (model.py:39,53,63)
@@ -509,7 +558,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
       cur = oth; N = 1;
       break;
     }
-    if (HR == 2 && last_block_cls_rows(p, ext, i, N)) {
+    if (HR == 2 && last_block_cls_rows(p, ext, i, N, last_captured)) {
       // the distilled head reads rows 0 and 1: the first query tile (into w.xn, which QKV has consumed), its rows 0 and 1
       // gathered dense into w.att, and the ordinary tail as a pruned block that keeps {0, 1} - the proj epilogue gathers
       // the two residual rows through idx01 and the stream leaves [B, 2, C] in `oth`
@@ -524,7 +573,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
         cur = oth; N = 2;
         break;
       }
-    } else if (last_block_cls_rows(p, ext, i, N)) {
+    } else if (last_block_cls_rows(p, ext, i, N, last_captured)) {
       // the all-rows kernels on the rows the head reads: the first query tile, proj on its CLS rows in place (stride N * C)
       const Tail t = tail_args(f, blk, AttnRows{B, cls_ld, nullptr, cls_ld, nullptr, 0, 0}, cur, oth);
       if (tail_ok(t)) {   // (a refused shape or stride: all rows below, as if this branch were not here)
@@ -583,19 +632,40 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
     char* y = idx ? oth : cur;
     rc = launch_tail(f, blk, tail_args(f, blk, AttnRows{B * Np, C, att8 ? w.xs : nullptr, C, idx, Np, N}, cur, y));
     if (rc != RAJNI_OK) return rc;
-    if (idx && dense_last) {
+    // (slabs with fill = 1: the same rows, to every slab of a capture at or behind this block)
+    const bool slabs_last = idx && lay && lay->fill == 1 && cap < lay->n;
+    if (idx && (dense_last || slabs_last)) {
       // the rows this block drops leave the stream here and keep the state they entered with: `cur` still holds it (the tail
       // gathered the kept rows into `oth`).  Where each entering token sat in the unpruned sequence goes to w.qkv, dead
       // between the tail and the next block's QKV GEMM (B * N * 4 bytes always fit); then the final norm of the dropped rows
       int32_t* src = reinterpret_cast<int32_t*>(w.qkv);
       rc = launch_source_idx_before(p, P, i, src, N, s);
       if (rc != RAJNI_OK) return rc;
-      rc = launch_layernorm_dropped(cur, idx, src, p.norm_w, p.norm_b, logits, B, N, Np, P, tokens_entering(p, P, 0), C, p.ln_eps,
-                                    f.sf32, dt, s);
-      if (rc != RAJNI_OK) return rc;
+      if (dense_last) {
+        rc = launch_layernorm_dropped(cur, idx, src, p.norm_w, p.norm_b, logits, B, N, Np, P, S0, C, p.ln_eps, f.sf32, dt, s);
+        if (rc != RAJNI_OK) return rc;
+      }
+      if (slabs_last) {
+        void* ys[RAJNI_MAX_LAYERS];
+        for (int l = cap; l < lay->n; ++l) ys[l - cap] = slab(l);
+        rc = launch_rows_dropped_multi(cur, idx, src, p.norm_w, p.norm_b, ys, lay->n - cap, lay->norm, B, N, Np, P, S0, C, p.ln_eps,
+                                       f.sf32, dt, s);
+        if (rc != RAJNI_OK) return rc;
+      }
     }
     if (idx) { oth = cur; cur = y; }
     N = Np;
+    if (lay && cap < lay->n && lay->blocks[cap] == i) {
+      // a captured block: the stream behind it, scattered to slab `cap` through the map of the selections up to and including
+      // this block's (w.qkv again: the launches above have read their map, in stream order)
+      int32_t* src = reinterpret_cast<int32_t*>(w.qkv);
+      rc = launch_source_idx_before(p, P, i + 1, src, N, s);
+      if (rc != RAJNI_OK) return rc;
+      rc = lay->norm ? launch_layernorm_dense(cur, src, p.norm_w, p.norm_b, slab(cap), B, N, S0, C, p.ln_eps, f.sf32, dt, s, lay->fill ? 0 : 1)
+                     : launch_rows_dense_cast(cur, src, slab(cap), B, N, S0, C, f.sf32, dt, s, lay->fill ? 0 : 1);
+      if (rc != RAJNI_OK) return rc;
+      ++cap;
+    }
   }
 
   // ---- final norm on the CLS rows only (LN is per token; model.py:65-66) + head

@@ -535,6 +535,160 @@ __global__ void __launch_bounds__(256) layernorm_dropped_kernel(const TX* __rest
   }
 }
 
+// ---- rajni_vit_forward_layers (forward.hip): the states behind several blocks, each on the unpruned grid ----
+// 8 output elements packed once and stored to several rows: one 16-byte store (two for fp32) each time
+template <typename TY> struct Out8 { uint4 q; };
+template <> struct Out8<float> { float4 a, b; };
+template <typename TY> __device__ __forceinline__ Out8<TY> out8(const float* f) {
+  Out8<TY> o;
+  o.q = pack8<TY>(f);
+  return o;
+}
+template <> __device__ __forceinline__ Out8<float> out8<float>(const float* f) {
+  Out8<float> o;
+  o.a = make_float4(f[0], f[1], f[2], f[3]);
+  o.b = make_float4(f[4], f[5], f[6], f[7]);
+  return o;
+}
+template <typename TY> __device__ __forceinline__ void put8(TY* p, const Out8<TY>& o) { *reinterpret_cast<uint4*>(p) = o.q; }
+template <> __device__ __forceinline__ void put8<float>(float* p, const Out8<float>& o) {
+  reinterpret_cast<float4*>(p)[0] = o.a;
+  reinterpret_cast<float4*>(p)[1] = o.b;
+}
+
+// layernorm_dense_kernel without the norm: y[b, s, :] = the stream row x[b, j, :] rounded once to TY where src[b, j] == s, else
+// zeros (ZERO = false: a miss stores nothing).  The same mapping - one wave per OUTPUT row, the scalar binary search over the
+// strictly ascending src[b, :] - and one pass of 16-byte loads and 16-byte stores; TX == TY == float is a plain copy.
+template <typename TX, typename TY, bool ZERO = true>
+__global__ void __launch_bounds__(256) rows_dense_cast_kernel(const TX* __restrict__ x, const int32_t* __restrict__ src,
+                                                              TY* __restrict__ y, int B, int Nf, int S, int C) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + wave;
+  if (row >= (long)B * S) return;
+  const int img = (int)(row / S), s = (int)(row - (long)img * S);
+  const int32_t* sb = src + (long)img * Nf;
+  int lo = 0, hi = Nf;                    // the first j in [0, Nf) with sb[j] >= s
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (sb[mid] < s) lo = mid + 1; else hi = mid;
+  }
+  const bool hit = lo < Nf && sb[lo] == s;
+  const int nchunk = C >> 3;
+  TY* yr = y + row * C;
+  if (!hit) {
+    if constexpr (ZERO) {
+      const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
+        const int c = lane + i * 64;
+        if (c < nchunk) store8<TY>(yr + c * 8, z);
+      }
+    }
+    return;
+  }
+  const TX* xr = x + ((long)img * Nf + lo) * C;
+#pragma unroll
+  for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
+    const int c = lane + i * 64;
+    if (c < nchunk) {
+      float v[8];
+      load8<TX>(xr + c * 8, v);
+      store8<TY>(yr + c * 8, v);
+    }
+  }
+}
+
+// The rows a scheduled block drops, to several outputs: layernorm_dropped_kernel's mapping (one wave per INPUT row, the scalar
+// search of keep[b, P:], the clamps) and, with NORM, its arithmetic instruction for instruction, so a row has the bits that
+// kernel gives it; without NORM the row is rounded once to TY.  The finished row stays in registers, packed, and goes as whole
+// rows of 16-byte stores to row src[b, j] of every target t.y[k] - each a [B, S, C] slab.  The targets travel by value in the
+// kernel arguments and the loop over them is wave-uniform.
+struct RowTargets {
+  void* y[RAJNI_MAX_LAYERS];
+  int n;
+};
+template <typename TX, typename TY, bool NORM>
+__global__ void __launch_bounds__(256) rows_dropped_multi_kernel(const TX* __restrict__ x, const int32_t* __restrict__ keep,
+                                                                 const int32_t* __restrict__ src, const float* __restrict__ w,
+                                                                 const float* __restrict__ b, RowTargets t, int B, int N, int Np,
+                                                                 int P, int S, int C, float eps) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int patches = N - P;
+  const long row = (long)blockIdx.x * 4 + wave;
+  if (row >= (long)B * patches) return;
+  const int img = (int)(row / patches), j = P + (int)(row - (long)img * patches);
+  const int32_t* kb = keep + (long)img * Np;
+  auto kept = [&](int slot) { const int k = kb[slot]; return k < 0 ? 0 : (k >= N ? N - 1 : k); };
+  int lo = P, hi = Np;                    // the first slot in [P, Np) with kept(slot) >= j
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (kept(mid) < j) lo = mid + 1; else hi = mid;
+  }
+  if (lo < Np && kept(lo) == j) return;   // kept: the row travels on
+  int s = src[(long)img * N + j];
+  s = s < 0 ? 0 : (s >= S ? S - 1 : s);
+  const int nchunk = C >> 3;
+  const TX* xr = x + ((long)img * N + j) * C;
+  float v[LN_MAX_CHUNKS][8];
+  Out8<TY> o8[LN_MAX_CHUNKS];
+  if constexpr (NORM) {
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
+      const int c = lane + i * 64;
+      if (c < nchunk) {
+        load8<TX>(xr + c * 8, v[i]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sum += v[i][e];
+      }
+    }
+    const float mean = wave_sum(sum) / (float)C;
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
+      const int c = lane + i * 64;
+      if (c < nchunk) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float d = v[i][e] - mean;
+          ss += d * d;
+        }
+      }
+    }
+    const float rstd = rsqrtf(wave_sum(ss) / (float)C + eps);
+#pragma unroll
+    for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
+      const int c = lane + i * 64;
+      if (c < nchunk) {
+        float wv[8], bv[8], o[8];
+        load8<float>(w + c * 8, wv);
+        load8<float>(b + c * 8, bv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = fmaf((v[i][e] - mean) * rstd, wv[e], bv[e]);
+        o8[i] = out8<TY>(o);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
+      const int c = lane + i * 64;
+      if (c < nchunk) {
+        load8<TX>(xr + c * 8, v[i]);
+        o8[i] = out8<TY>(v[i]);
+      }
+    }
+  }
+  const long off = ((long)img * S + s) * C;
+  for (int k = 0; k < t.n; ++k) {
+    TY* yr = static_cast<TY*>(t.y[k]) + off;
+#pragma unroll
+    for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
+      const int c = lane + i * 64;
+      if (c < nchunk) put8<TY>(yr + c * 8, o8[i]);
+    }
+  }
+}
+
 }  // namespace
 
 static int launch_layernorm_f16(const void* x, long xs, const float* w, const float* b, void* y, int rows,
@@ -698,5 +852,80 @@ int launch_layernorm_dropped(const void* x, const int32_t* keep, const int32_t* 
   else RAJNI_LN_DROPPED(bf16_t, bf16_t);
 #undef RAJNI_LN_DROPPED
   RAJNI_CHECK_LAUNCH("layernorm_dropped_kernel");
+  return RAJNI_OK;
+}
+
+template <bool ZERO>
+static void launch_dense_cast_kernels(dim3 grid, dim3 block, const void* x, const int32_t* src, void* y, int B, int Nf, int S, int C,
+                                      int x_f32, int dtype, hipStream_t s) {
+  if (dtype == RAJNI_F32)
+    hipLaunchKernelGGL((rows_dense_cast_kernel<float, float, ZERO>), grid, block, 0, s, (const float*)x, src, (float*)y, B, Nf, S, C);
+  else if (dtype == RAJNI_F16 && x_f32)
+    hipLaunchKernelGGL((rows_dense_cast_kernel<float, f16_t, ZERO>), grid, block, 0, s, (const float*)x, src, (f16_t*)y, B, Nf, S, C);
+  else if (dtype == RAJNI_F16)
+    hipLaunchKernelGGL((rows_dense_cast_kernel<f16_t, f16_t, ZERO>), grid, block, 0, s, (const f16_t*)x, src, (f16_t*)y, B, Nf, S, C);
+  else if (x_f32)
+    hipLaunchKernelGGL((rows_dense_cast_kernel<float, bf16_t, ZERO>), grid, block, 0, s, (const float*)x, src, (bf16_t*)y, B, Nf, S, C);
+  else
+    hipLaunchKernelGGL((rows_dense_cast_kernel<bf16_t, bf16_t, ZERO>), grid, block, 0, s, (const bf16_t*)x, src, (bf16_t*)y, B, Nf, S, C);
+}
+
+// launch_layernorm_dense without the norm: row src[b, j] of y [B, S, C] `dtype` = x[b, j] rounded once to `dtype`, every other
+// row zero, or with zero_fill == 0 left as it is
+int launch_rows_dense_cast(const void* x, const int32_t* src, void* y, int B, int Nf, int S, int C, int x_f32, int dtype,
+                           hipStream_t s, int zero_fill) {
+  RAJNI_REQUIRE(x && src && y, RAJNI_ERR_INVALID, "rows_dense_cast: null pointer");
+  RAJNI_REQUIRE(B > 0 && Nf > 0 && S >= Nf && C > 0 && C % 8 == 0 && C <= 64 * 8 * LN_MAX_CHUNKS, RAJNI_ERR_UNSUPPORTED,
+                "rows_dense_cast: need C %% 8 == 0, C <= 2048 and 0 < Nf <= S (C=%d Nf=%d S=%d)", C, Nf, S);
+  const long rows = (long)B * S;
+  RAJNI_REQUIRE((rows + 3) / 4 < (1L << 31), RAJNI_ERR_UNSUPPORTED, "rows_dense_cast: too many output rows (%ld)", rows);
+  const bool f32io = dtype == RAJNI_F32;
+  const double eb = f32io ? 4.0 : 2.0, xb = (f32io || x_f32) ? 4.0 : 2.0;
+  ProfScope prof(KC_LAYERNORM, s, 0.0, xb * B * Nf * C + eb * (zero_fill ? rows : (long)B * Nf) * C);
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  if (zero_fill) launch_dense_cast_kernels<true>(grid, block, x, src, y, B, Nf, S, C, x_f32, dtype, s);
+  else launch_dense_cast_kernels<false>(grid, block, x, src, y, B, Nf, S, C, x_f32, dtype, s);
+  RAJNI_CHECK_LAUNCH("rows_dense_cast_kernel");
+  return RAJNI_OK;
+}
+
+// launch_layernorm_dropped to `ny` outputs ys[k] [B, S, C] at once (1 <= ny <= RAJNI_MAX_LAYERS, a host array): the patch rows
+// of x [B, N, C] that keep [B, Np] does not name, through the norm (norm != 0) or rounded once to `dtype`, to row src[b, j] of
+// every output
+int launch_rows_dropped_multi(const void* x, const int32_t* keep, const int32_t* src, const float* w, const float* b,
+                              void* const* ys, int ny, int norm, int B, int N, int Np, int P, int S, int C, float eps, int x_f32,
+                              int dtype, hipStream_t s) {
+  RAJNI_REQUIRE(x && keep && src && ys && (!norm || (w && b)), RAJNI_ERR_INVALID, "rows_dropped_multi: null pointer");
+  RAJNI_REQUIRE(ny >= 1 && ny <= RAJNI_MAX_LAYERS, RAJNI_ERR_INVALID, "rows_dropped_multi: 1..%d outputs (%d)", RAJNI_MAX_LAYERS, ny);
+  RAJNI_REQUIRE(B > 0 && P > 0 && P < Np && Np <= N && N <= S && C > 0 && C % 8 == 0 && C <= 64 * 8 * LN_MAX_CHUNKS,
+                RAJNI_ERR_UNSUPPORTED, "rows_dropped_multi: need C %% 8 == 0, C <= 2048 and 0 < P < Np <= N <= S (C=%d P=%d Np=%d N=%d S=%d)",
+                C, P, Np, N, S);
+  const long rows = (long)B * (N - P), dropped = (long)B * (N - Np);
+  RAJNI_REQUIRE((rows + 3) / 4 < (1L << 31), RAJNI_ERR_UNSUPPORTED, "rows_dropped_multi: too many rows (%ld)", rows);
+  RowTargets t{};
+  for (t.n = 0; t.n < ny; ++t.n) {
+    RAJNI_REQUIRE(ys[t.n] != nullptr, RAJNI_ERR_INVALID, "rows_dropped_multi: output %d is null", t.n);
+    t.y[t.n] = ys[t.n];
+  }
+  const bool f32io = dtype == RAJNI_F32;
+  ProfScope prof(KC_LAYERNORM, s, norm ? 8.0 * dropped * C : 0.0,
+                 ((f32io || x_f32 ? 4.0 : 2.0) + (f32io ? 4.0 : 2.0) * ny) * dropped * C);
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+#define RAJNI_ROWS_DROPPED(TX, TY)                                                                                              \
+  do {                                                                                                                          \
+    if (norm)                                                                                                                   \
+      hipLaunchKernelGGL((rows_dropped_multi_kernel<TX, TY, true>), grid, block, 0, s, (const TX*)x, keep, src, w, b, t, B, N, Np, \
+                         P, S, C, eps);                                                                                         \
+    else                                                                                                                        \
+      hipLaunchKernelGGL((rows_dropped_multi_kernel<TX, TY, false>), grid, block, 0, s, (const TX*)x, keep, src, w, b, t, B, N, Np, \
+                         P, S, C, eps);                                                                                         \
+  } while (0)
+  if (f32io) RAJNI_ROWS_DROPPED(float, float);
+  else if (dtype == RAJNI_F16 && x_f32) RAJNI_ROWS_DROPPED(float, f16_t);
+  else if (dtype == RAJNI_F16) RAJNI_ROWS_DROPPED(f16_t, f16_t);
+  else if (x_f32) RAJNI_ROWS_DROPPED(float, bf16_t);
+  else RAJNI_ROWS_DROPPED(bf16_t, bf16_t);
+#undef RAJNI_ROWS_DROPPED
+  RAJNI_CHECK_LAUNCH("rows_dropped_multi_kernel");
   return RAJNI_OK;
 }

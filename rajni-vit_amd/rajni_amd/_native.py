@@ -101,6 +101,14 @@ class VitPrefix(C.Structure):
         super().__init__(num_prefix=num_prefix, head_rows=head_rows, reg_token=reg_token)
 
 
+class VitLayers(C.Structure):
+    """rajni_vit_layers (include/rajni_hip_layers.h): the blocks whose output rajni_vit_forward_layers scatters back to the
+    unpruned sequence, one slab [B, P + n, C] each.  `blocks` is a HOST int array the caller keeps alive."""
+    _fields_ = [("n", c_int), ("blocks", C.POINTER(c_int)), ("norm", c_int), ("fill", c_int), ("out", c_void_p),
+                ("slab_stride", C.c_longlong)]
+
+
+MAX_LAYERS = 64     # RAJNI_MAX_LAYERS
 MAX_PREFIX = 32     # RAJNI_MAX_PREFIX
 SCORE_TILE_TOKENS = 32      # ST_TILE of csrc/score_select.hip: tokens per workgroup of the tiled score kernels
 SCORE_TILED_MAX_TOKENS = 16384 + MAX_PREFIX   # ST_MAX_N: the tiled path's cap
@@ -168,6 +176,12 @@ _SIGS = {
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())
+# include/rajni_hip_layers.h, additive to the boundary above: bound beside it, EXPORTED_SYMBOLS and the ABI version stay
+_LAYERS_SIGS = {
+    "rajni_vit_forward_layers": (c_int, [C.POINTER(VitPlan), C.POINTER(VitExt), C.POINTER(VitPrefix), C.POINTER(VitLayers),
+                                         c_void_p, c_void_p, c_void_p]),
+}
+LAYERS_SYMBOLS = ("rajni_vit_forward_layers",)
 ABI_VERSION = 8     # include/rajni_hip.h; bumped whenever a struct or an entry point changes
 _lib: Optional[C.CDLL] = None
 
@@ -182,7 +196,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
             f"librajni_hip.so not found at {path}. Build it with `python rajni-vit_amd/build.py` "
             "(hipcc --offload-arch=gfx950). rajni_amd has no CPU or PyTorch fallback by design.")
     lib = C.CDLL(path)
-    for name, (res, args) in _SIGS.items():
+    for name, (res, args) in list(_SIGS.items()) + list(_LAYERS_SIGS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

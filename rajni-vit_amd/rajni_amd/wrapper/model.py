@@ -12,7 +12,9 @@ DeiT's distilled models (timm `VisionTransformerDistilled`: `dist_token` behind 
 register, and eval logits `(head(x[:, 0]) + head_dist(x[:, 1])) / 2`).  Beyond the reference's surface: a headless base model
 (`head = nn.Identity`, timm num_classes=0) returns its pooled feature [B, C], and `forward_features(x, dense=False)` returns the
 final normalised tokens of the pruned graph, or the unpruned sequence with pruned positions zero (`fill="last"`: holding the
-feature each token had when it left the stream), with their source positions in `get_last_stats()["source_idx"]`.
+feature each token had when it left the stream), with their source positions in `get_last_stats()["source_idx"]`; and
+`forward_intermediates` / `get_intermediate_layers` (timm's and DINOv2's signatures) return the states behind several blocks from
+one forward, each on that unpruned grid.
 
 Not kept: the Python per-block loop.  `forward` builds (once per batch shape) a `rajni_vit_plan`
 - packed weights, workspace, per-stage index buffers - and calls `rajni_vit_forward`, which enqueues
@@ -63,6 +65,33 @@ def compose_exit_block(selections: Dict[int, torch.Tensor], B: int, n0: int, dep
         pos = torch.gather(pos, 1, selections[i].long())
     exit_block.scatter_(1, pos, torch.full_like(pos, depth, dtype=torch.int32))
     return exit_block
+
+
+def take_indices(num_blocks: int, indices=None) -> tuple:
+    """timm's `feature_take_indices` restated (timm is not a dependency): the ascending block indices `forward_intermediates`
+    captures.  None: every block; an int k: the last k; a sequence: those blocks, negative values counting from the end.
+    Duplicates, an empty result and anything outside [-num_blocks, num_blocks) raise ValueError."""
+    if indices is None:
+        out = list(range(num_blocks))
+    elif isinstance(indices, bool):
+        raise ValueError(f"indices must be None, an int or a sequence of ints, got {indices!r}")
+    elif isinstance(indices, int):
+        if not 1 <= indices <= num_blocks:
+            raise ValueError(f"indices={indices}: the last k blocks need 1 <= k <= {num_blocks}")
+        out = list(range(num_blocks - indices, num_blocks))
+    else:
+        out = []
+        for i in indices:
+            if isinstance(i, bool) or not isinstance(i, int):
+                raise ValueError(f"indices must hold ints, got {i!r}")
+            if not -num_blocks <= i < num_blocks:
+                raise ValueError(f"block index {i} is out of range for {num_blocks} blocks")
+            out.append(i + num_blocks if i < 0 else i)
+    if not out:
+        raise ValueError("indices selects no block")
+    if len(set(out)) != len(out):
+        raise ValueError(f"indices names a block twice: {list(indices)}")
+    return tuple(sorted(out))
 
 
 def model_is_distilled(m: nn.Module) -> bool:
@@ -637,15 +666,20 @@ class RAJNIViTWrapper(nn.Module):
     def _build_plan(self, B: int, S: int, device, dtype, mode: str = "logits"):
         """`mode`: "logits" (the model's forward: logits, or the pooled feature of a headless model), or the feature outputs
         "tokens" / "dense" / "dense_last" (forward_features): a second plan of the same packed weights with no head and
-        ext.pool = POOL_NONE / POOL_DENSE / POOL_DENSE_LAST."""
+        ext.pool = POOL_NONE / POOL_DENSE / POOL_DENSE_LAST.  A tuple ("layers", base mode, captured blocks, norm, fill)
+        (forward_intermediates) is the base mode's plan with a layers record beside it, under a key of its own."""
         W = self._pack_weights(device, dtype)
         d = W["desc"]
         P = d["num_prefix"]
+        full_mode, layers = mode, None
+        if isinstance(mode, tuple):
+            _, mode, caps, lnorm, lfill = mode
+            self._check_layers(d, caps, lnorm)
         features = mode != "logits"
         if features:
             self._check_features(d)
         key = (B, S, device, dtype, self._weights_key, tuple(sorted(self._forced)), self._trace_scores, self._resid_bf16,
-               self._cls_only_last, P, mode)
+               self._cls_only_last, P, full_mode)
         if self._plan is not None and self._plan[0] == key:
             return self._plan
         if key in self._plans:
@@ -750,9 +784,13 @@ class RAJNIViTWrapper(nn.Module):
             ops.keep_count(self.pruning_schedule[d["depth"] - 1]["keep_ratio"], counts[-1], P) + P
         out_shape = {"logits": (B, plan.logits_ld), "tokens": (B, n_last, d["C"]), "dense": (B, n0, d["C"]),
                      "dense_last": (B, n0, d["C"])}[mode]
+        if full_mode is not mode:      # the layers record (rajni_vit_layers) minus `out`, and the slabs' shape
+            cap_arr = (C.c_int * len(caps))(*caps)
+            layers = (cap_arr, int(lnorm), int(lfill == "last"), (len(caps), B, n0, d["C"]))
         # W: a stale optimistic launch keeps its weights alive
-        # (existing callers index entry[0..4] and unpack entry[2] as seven objects: mode and out_shape go behind `counts`)
-        self._plan = (key, plan, (blocks, tc, ws, W, ext, qk, pre), bufs, counts, mode, out_shape)
+        # (existing callers index entry[0..4] and unpack entry[2] as seven objects: mode and out_shape go behind `counts`,
+        # the layers record behind those)
+        self._plan = (key, plan, (blocks, tc, ws, W, ext, qk, pre), bufs, counts, full_mode, out_shape, layers)
         if len(self._plans) >= 4:     # workspaces are large: keep only a few batch shapes alive
             self._plans.pop(next(iter(self._plans)))
         self._plans[key] = self._plan
@@ -763,11 +801,23 @@ class RAJNIViTWrapper(nn.Module):
         """what forward_features does not compute"""
         if not d["norm"]:
             raise NotImplementedError("forward_features: base_model.norm is nn.Identity (the fc_norm models): their features are "
-                                      "the un-normalised stream, and there is no cast-only row kernel yet")
+                                      "the un-normalised stream, which forward_intermediates(x, norm=False, "
+                                      "intermediates_only=True) returns")
         if self._weight_format == "fp8_mfma":
             raise NotImplementedError('forward_features: not supported with weight format "fp8_mfma" ("fp8" weights work)')
         if self._cls_only_last:
             raise ValueError("forward_features with set_last_block_cls_only(True): that opt-in never forms the rows to be returned")
+
+    def _check_layers(self, d, caps, norm):
+        """what forward_intermediates does not compute"""
+        if norm and not d["norm"]:
+            raise NotImplementedError("forward_intermediates(norm=True): base_model.norm is nn.Identity (the fc_norm models); "
+                                      "norm=False returns the un-normalised states")
+        if self._weight_format == "fp8_mfma":
+            raise NotImplementedError('forward_intermediates: not supported with weight format "fp8_mfma" ("fp8" weights work)')
+        if self._cls_only_last and caps[-1] == d["depth"] - 1:
+            raise ValueError("forward_intermediates with set_last_block_cls_only(True) and the last block captured: that opt-in "
+                             "never forms the rows to be returned")
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -797,7 +847,12 @@ class RAJNIViTWrapper(nn.Module):
         if fill == "last" and not dense:
             raise ValueError('forward_features: fill="last" fills the pruned positions of the dense output; it needs dense=True')
         out, entry = self._run(x, ("dense_last" if fill == "last" else "dense") if dense else "tokens")
-        P, n0 = entry[0][-2], entry[4][0]
+        self._selection_stats(entry, x, exit_block=fill == "last")
+        return out
+
+    def _selection_stats(self, entry, x, exit_block: bool):
+        """`source_idx` (and `exit_block`) of the forward just run into get_last_stats(): torch ops on the device, no host sync"""
+        n0 = entry[4][0]
         src = None            # the selections composed on the device, last stage first: no host sync
         for i in sorted(entry[3], reverse=True):
             idx = self._forced.get(i, entry[3][i]["keep_idx"]).long()
@@ -805,10 +860,62 @@ class RAJNIViTWrapper(nn.Module):
         if src is None:
             src = torch.arange(n0, device=x.device).expand(x.shape[0], n0)
         self._last_stats["source_idx"] = src.to(torch.int32).contiguous()
-        if fill == "last":
+        if exit_block:
             self._last_stats["exit_block"] = compose_exit_block(
                 {i: self._forced.get(i, entry[3][i]["keep_idx"]) for i in entry[3]}, x.shape[0], n0, entry[1].depth, x.device)
-        return out
+
+    @torch.no_grad()
+    def forward_intermediates(self, x: torch.Tensor, indices=None, return_prefix_tokens: bool = False, norm: bool = False,
+                              stop_early: bool = False, output_fmt: str = "NCHW", intermediates_only: bool = False,
+                              fill: str = "zero"):
+        """timm's forward_intermediates on the pruned graph - its signature and defaults, plus `fill` - from ONE forward: the
+        state behind every block of `indices` (take_indices: None = every block, an int k = the last k, a sequence = those
+        blocks), each scattered back to the unpruned sequence like forward_features(dense=True).
+        A token alive behind captured block c has f(x_after_c) at its position; a token that scheduled block i <= c dropped has
+        zeros (`fill="zero"`) or f(x_entry_i), the state it had when it left (`fill="last"`).  f is base_model.norm with
+        `norm=True` (DINOv2 normalises intermediate states with the final norm) and one rounding of the stream to the model
+        dtype with `norm=False` (timm's default).  A block that is both scheduled and captured drops first.
+        Returns `(final, intermediates)`, `final` = forward_features(x, dense=True, fill=fill) from the same call, or with
+        `intermediates_only=True` the list alone (then the forward is the logits plan's, and models without a final norm work
+        with norm=False).  Each intermediate is the patch rows of its slab: "NLC" [B, n, C], a view into one allocation, or
+        "NCHW" [B, C, h, w], a torch permute made contiguous - a copy; with `return_prefix_tokens=True` a pair (spatial,
+        prefix [B, P, C]).
+        Afterwards get_last_stats() holds `source_idx` and `exit_block` (both fills): the alive mask of the intermediate of
+        block c is `exit_block > c`.  `stop_early=True` is not implemented (the forward always runs every block)."""
+        if fill not in ("zero", "last"):
+            raise ValueError(f'forward_intermediates: fill must be "zero" or "last", got {fill!r}')
+        if output_fmt not in ("NCHW", "NLC"):
+            raise ValueError(f'forward_intermediates: output_fmt must be "NCHW" or "NLC", got {output_fmt!r}')
+        if stop_early:
+            raise NotImplementedError("forward_intermediates(stop_early=True): the native forward runs every block; cut the base "
+                                      "model's blocks instead")
+        caps = take_indices(len(self.blocks), indices)
+        self._check_layers(dict(norm=not isinstance(self.m.norm, nn.Identity), depth=len(self.blocks)), caps, norm)
+        base = "logits" if intermediates_only else ("dense_last" if fill == "last" else "dense")
+        (final, slabs), entry = self._run(x, ("layers", base, caps, bool(norm), fill))
+        self._selection_stats(entry, x, exit_block=True)
+        P = entry[0][-2]
+        B, g, Cdim = x.shape[0], x.shape[-1] // entry[1].patch_size, entry[1].C
+        inter = []
+        for l in range(len(caps)):
+            spatial = slabs[l, :, P:]
+            if output_fmt == "NCHW":
+                spatial = spatial.reshape(B, g, g, Cdim).permute(0, 3, 1, 2).contiguous()
+            inter.append((spatial, slabs[l, :, :P]) if return_prefix_tokens else spatial)
+        return inter if intermediates_only else (final, inter)
+
+    @torch.no_grad()
+    def get_intermediate_layers(self, x: torch.Tensor, n=1, reshape: bool = False, return_class_token: bool = False,
+                                norm: bool = True, fill: str = "zero"):
+        """DINOv2's get_intermediate_layers on the pruned graph (its signature and tuple return, plus `fill`): the patch tokens
+        behind the last `n` blocks (or the blocks of a sequence `n`), through the final norm by default, [B, n, C] each or with
+        `reshape=True` [B, C, h, w]; `return_class_token=True` gives (patches, class_token [B, C]) pairs.  A thin layer over
+        forward_intermediates."""
+        inter = self.forward_intermediates(x, indices=n, return_prefix_tokens=True, norm=norm,
+                                           output_fmt="NCHW" if reshape else "NLC", intermediates_only=True, fill=fill)
+        if return_class_token:
+            return tuple((spatial, prefix[:, 0]) for spatial, prefix in inter)
+        return tuple(spatial for spatial, _ in inter)
 
     def _run(self, x: torch.Tensor, mode: str):
         nat.require_device(x, "input images")
@@ -829,6 +936,16 @@ class RAJNIViTWrapper(nn.Module):
                 plan = entry[1]
                 out = torch.empty(entry[6], dtype=dtype, device=x.device)
                 ext, pre = entry[2][4], entry[2][6]
+                if entry[7] is not None:      # forward_intermediates: the slabs beside `out`, one allocation
+                    cap_arr, lnorm, lfill, slab_shape = entry[7]
+                    slabs = torch.empty(slab_shape, dtype=dtype, device=x.device)
+                    lay = nat.VitLayers()
+                    lay.n, lay.blocks, lay.norm, lay.fill, lay.out, lay.slab_stride = len(cap_arr), cap_arr, lnorm, lfill, slabs.data_ptr(), 0
+                    nat.check(nat.lib().rajni_vit_forward_layers(C.byref(plan), C.byref(ext) if ext is not None else None,
+                                                                 C.byref(pre) if pre is not None else None, C.byref(lay),
+                                                                 x.data_ptr(), out.data_ptr(), nat.stream_ptr(x.device)),
+                              "rajni_vit_forward_layers")
+                    return out, slabs
                 if pre is not None:
                     nat.check(nat.lib().rajni_vit_forward_ext_prefix(C.byref(plan), C.byref(ext) if ext is not None else None,
                                                                      C.byref(pre), x.data_ptr(), out.data_ptr(),
