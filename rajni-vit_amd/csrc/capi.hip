@@ -297,7 +297,7 @@ int rajni_patch_embed(const void* images, const void* w, const float* bias, cons
   NEED_DTYPE("rajni_patch_embed");
   RAJNI_REQUIRE_PLACED("rajni_patch_embed", {"images", images, 16}, {"w", w, 16}, {"bias", bias, 16}, {"cls", cls, 16}, {"pos", pos, 16},
                        {"x", x, 16}, {"workspace", workspace, 16});
-  return launch_patch_embed(images, w, bias, cls, pos, pos_has_cls, x, x_f32, B, Cin, S, P, C, dtype,
+  return launch_patch_embed(images, w, bias, cls, pos, pos_has_cls, x, x_f32, B, Cin, S, S, P, C, dtype,
                             workspace, workspace_bytes, (hipStream_t)stream);
 }
 int rajni_patch_embed_prefix(const void* images, const void* w, const float* bias, const void* cls, const void* reg,
@@ -311,11 +311,36 @@ int rajni_patch_embed_prefix(const void* images, const void* w, const float* bia
                 "rajni_patch_embed_prefix: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
   RAJNI_REQUIRE(num_prefix == 1 || reg != nullptr, RAJNI_ERR_INVALID,
                 "rajni_patch_embed_prefix: %d prefix tokens but reg is null", num_prefix);
-  return launch_patch_embed(images, w, bias, cls, pos, pos_has_cls, x, x_f32, B, Cin, S, P, C, dtype,
+  return launch_patch_embed(images, w, bias, cls, pos, pos_has_cls, x, x_f32, B, Cin, S, S, P, C, dtype,
                             workspace, workspace_bytes, (hipStream_t)stream, num_prefix, num_prefix > 1 ? reg : nullptr);
 }
 size_t rajni_patch_embed_workspace_bytes(int B, int Cin, int S, int P, int dtype) {
-  return patch_embed_workspace_bytes(B, Cin, S, P, dtype);
+  return patch_embed_workspace_bytes(B, Cin, S, S, P, dtype);
+}
+
+// ---- include/rajni_hip_image.h
+int rajni_patch_embed_image(const void* images, const void* w, const float* bias, const void* cls, const void* reg,
+                            int num_prefix, const void* pos, int pos_has_cls, void* x, int x_f32, int B, int Cin, int H, int W,
+                            int P, int C, int dtype, void* workspace, size_t workspace_bytes, rajni_stream_t stream) {
+  NEED_DTYPE("rajni_patch_embed_image");
+  RAJNI_REQUIRE_PLACED("rajni_patch_embed_image", {"images", images, 16}, {"w", w, 16}, {"bias", bias, 16}, {"cls", cls, 16},
+                       {"reg", reg, 16}, {"pos", pos, 16}, {"x", x, 16}, {"workspace", workspace, 16});
+  RAJNI_REQUIRE(images && w && cls && pos && x, RAJNI_ERR_INVALID, "rajni_patch_embed_image: null pointer");
+  RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
+                "rajni_patch_embed_image: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
+  RAJNI_REQUIRE(num_prefix == 1 || reg != nullptr, RAJNI_ERR_INVALID,
+                "rajni_patch_embed_image: %d prefix tokens but reg is null", num_prefix);
+  return launch_patch_embed(images, w, bias, cls, pos, pos_has_cls, x, x_f32, B, Cin, H, W, P, C, dtype,
+                            workspace, workspace_bytes, (hipStream_t)stream, num_prefix, num_prefix > 1 ? reg : nullptr);
+}
+size_t rajni_patch_embed_workspace_bytes_image(int B, int Cin, int H, int W, int P, int dtype) {
+  return patch_embed_workspace_bytes(B, Cin, H, W, P, dtype);
+}
+int rajni_resample_pos_embed(const void* src, int src_h, int src_w, void* dst, int dst_h, int dst_w, int C, int prefix_rows,
+                             int dtype, rajni_stream_t stream) {
+  NEED_DTYPE("rajni_resample_pos_embed");
+  RAJNI_REQUIRE_PLACED("rajni_resample_pos_embed", {"src", src, 16}, {"dst", dst, 16});
+  return launch_resample_pos_embed(src, src_h, src_w, dst, dst_h, dst_w, C, prefix_rows, dtype, (hipStream_t)stream);
 }
 
 void rajni_profile_enable(unsigned mask) { g_prof_mask = mask; }

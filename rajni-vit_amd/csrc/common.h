@@ -6,6 +6,7 @@
 #include "../../include/rajni_hip.h"
 #include "../../include/rajni_hip_debug.h"
 #include "../../include/rajni_hip_layers.h"
+#include "../../include/rajni_hip_image.h"
 
 typedef unsigned short bf16_t;  // raw bf16 bits in memory
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -209,10 +210,10 @@ extern unsigned long long* rajni_g_stamps;
 // internal launchers shared between the per-op ABI and the whole-forward plan
 int launch_linear(const rajni_linear_args& a, hipStream_t s);
 int launch_patch_embed(const void* images, const void* w, const float* bias, const void* cls,
-                       const void* pos, int pos_has_cls, void* x, int out_f32, int B, int Cin, int S,
+                       const void* pos, int pos_has_cls, void* x, int out_f32, int B, int Cin, int H, int W,
                        int P, int C, int dtype, void* ws, size_t ws_bytes, hipStream_t s,
                        int num_prefix = 1, const void* reg = nullptr);   // reg: [num_prefix-1, C] register tokens behind CLS
-size_t patch_embed_workspace_bytes(int B, int Cin, int S, int P, int dtype);   // 0: im2col fused into the GEMM loads
+size_t patch_embed_workspace_bytes(int B, int Cin, int H, int W, int P, int dtype);   // images [B, Cin, H, W]; 0: im2col fused into the GEMM loads
 int launch_layernorm(const void* x, long xs, const float* w, const float* b, void* y, int rows,
                      int C, float eps, int x_f32, int dtype, hipStream_t s);
 int launch_layernorm_fp8(const void* x, long xs, const float* w, const float* b, void* yq, float* yscale,
@@ -256,3 +257,6 @@ int launch_layernorm_stream(void* x, const float* w, const float* b, int rows, i
 int launch_pool_norm(const void* x, int B, int N, int C, int pool, const float* nw, const float* nb, float neps,
                      const float* fw, const float* fb, float feps, void* out, int x_f32, int dtype, hipStream_t s,
                      int num_prefix = 1);
+// image.hip: position-embedding rows [prefix + sh * sw, C] -> [prefix + dh * dw, C], bicubic with antialiasing (timm's
+// resample_abs_pos_embed); prefix rows copied
+int launch_resample_pos_embed(const void* src, int sh, int sw, void* dst, int dh, int dw, int C, int prefix, int dtype, hipStream_t s);

@@ -28,6 +28,11 @@
 // stream goes to that block's slab on the unpruned grid (source_idx_kernel + layernorm_dense_kernel or rows_dense_cast_kernel),
 // and with fill = 1 every scheduled block writes the rows it drops to the slabs of all captures at or behind it in one launch
 // (rows_dropped_multi_kernel).  Whatever the plan writes to `logits` it writes unchanged; a NULL record adds nothing.
+//
+// rajni_vit_forward_image (rajni_hip_image.h) takes [B, Cin, height, width] images: the record reaches check_image, the
+// workspace carve, the token walk and the patch-embed call, where n0 = (height / patch) * (width / patch) + P replaces the
+// square count; plan.pos_embed holds the rows of that grid (rajni_resample_pos_embed makes them).  Nothing behind the
+// embedding changes, and a NULL or square record enqueues the launches it always did.
 #include "common.h"
 
 #include <vector>
@@ -35,6 +40,7 @@
 namespace {
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+constexpr int RAJNI_IMAGE_MAX_TOKENS = 16384 + RAJNI_MAX_PREFIX;   // ST_MAX_N of score_select.hip: the score path's cap
 
 struct Workspace {
   char *xa, *xb, *xn, *qkv, *att, *hid, *clsn, *scf, *cols;
@@ -44,8 +50,15 @@ struct Workspace {
   size_t total, cols_bytes;
 };
 
-Workspace carve(const rajni_vit_plan& p, int P, int HR) {
-  const size_t gw = p.img_size / p.patch_size, n0 = gw * gw + P;
+// the image record (rajni_hip_image.h) beside the plan: NULL is the square image of plan.img_size pixels
+inline int image_height(const rajni_vit_plan& p, const rajni_vit_image* img) { return img ? img->height : p.img_size; }
+inline int image_width(const rajni_vit_plan& p, const rajni_vit_image* img) { return img ? img->width : p.img_size; }
+inline int patch_tokens(const rajni_vit_plan& p, const rajni_vit_image* img) {
+  return (image_height(p, img) / p.patch_size) * (image_width(p, img) / p.patch_size);
+}
+
+Workspace carve(const rajni_vit_plan& p, int P, int HR, const rajni_vit_image* img = nullptr) {
+  const size_t n0 = (size_t)patch_tokens(p, img) + P;
   const size_t rows = (size_t)p.B * n0, es = p.dtype == RAJNI_F32 ? 4 : 2, xs = (p.dtype == RAJNI_F32 || !p.resid_bf16) ? 4 : 2;
   Workspace w{};
   size_t off = 0;
@@ -54,7 +67,7 @@ Workspace carve(const rajni_vit_plan& p, int P, int HR) {
   const size_t oqkv = take(rows * 3 * p.C * es), oatt = take(rows * p.C * es);
   const size_t ohid = take(rows * p.hidden * es), ocls = take((size_t)p.B * HR * p.C * es);
   const size_t oscf = take(rows * es);
-  w.cols_bytes = patch_embed_workspace_bytes(p.B, p.in_chans, p.img_size, p.patch_size, p.dtype);   // 0 when fused
+  w.cols_bytes = patch_embed_workspace_bytes(p.B, p.in_chans, image_height(p, img), image_width(p, img), p.patch_size, p.dtype);   // 0 when fused
   const size_t ocols = take(w.cols_bytes);
   const size_t oxs = take(p.act_fp8 ? rows * sizeof(float) : 0), ohs = take(p.act_fp8 ? rows * sizeof(float) : 0);
   w.sst_bytes = rajni_score_select_workspace_bytes(p.B, (int)n0, p.H, p.D, p.dtype);
@@ -331,9 +344,8 @@ int check_head_rows(const rajni_vit_plan& p, const rajni_vit_ext* e, const rajni
 // the token walk (model.py:43,50): a scheduled block leaves its kept patch tokens and the P prefix tokens ...
 inline int tokens_after(const rajni_block& blk, int N, int P) { return blk.keep > 0 ? blk.keep + P : N; }
 // ... so this many enter block i
-int tokens_entering(const rajni_vit_plan& p, int P, int i) {
-  const int gw = p.img_size / p.patch_size;
-  int N = gw * gw + P;
+int tokens_entering(const rajni_vit_plan& p, int P, int i, const rajni_vit_image* img = nullptr) {
+  int N = patch_tokens(p, img) + P;
   for (int j = 0; j < i; ++j) N = tokens_after(p.blocks[j], N, P);
   return N;
 }
@@ -341,11 +353,11 @@ int tokens_entering(const rajni_vit_plan& p, int P, int i) {
 inline int logits_stride(const rajni_vit_plan& p) { return p.logits_ld > 0 ? p.logits_ld : (headless(p) ? p.C : p.num_classes); }
 
 // the pruning schedule and the logits stride: what the block loop and the head rely on, refused before anything is launched
-int check_schedule(const rajni_vit_plan& p, int P) {
+int check_schedule(const rajni_vit_plan& p, int P, const rajni_vit_image* img) {
   for (int i = 0; i < p.depth; ++i) {
     const rajni_block& blk = p.blocks[i];
     if (blk.keep <= 0) continue;
-    const int patches = tokens_entering(p, P, i) - P;
+    const int patches = tokens_entering(p, P, i, img) - P;
     RAJNI_REQUIRE(blk.keep <= patches, RAJNI_ERR_INVALID, "block %d: keep=%d but only %d patch tokens", i, blk.keep, patches);
     RAJNI_REQUIRE(blk.keep_idx && blk.next_scores, RAJNI_ERR_INVALID, "block %d: keep_idx/next_scores buffers missing", i);
   }
@@ -379,7 +391,7 @@ int check_dense_last(const rajni_vit_plan& p, const rajni_vit_prefix* pre) {
 
 // the layers record against the plan and the ext record (rajni_hip_layers.h): host-side integer tests, in front of every other
 // refusal of the forward
-int check_layers(const rajni_vit_plan& p, const rajni_vit_ext* e, int P, const rajni_vit_layers& y) {
+int check_layers(const rajni_vit_plan& p, const rajni_vit_ext* e, int P, const rajni_vit_layers& y, const rajni_vit_image* img) {
   const char* who = "rajni_vit_forward_layers";
   RAJNI_REQUIRE(y.n >= 1 && y.n <= RAJNI_MAX_LAYERS, RAJNI_ERR_INVALID, "%s: layers.n must be 1..%d (%d)", who, RAJNI_MAX_LAYERS, y.n);
   RAJNI_REQUIRE(y.blocks != nullptr && y.out != nullptr, RAJNI_ERR_INVALID, "%s: null pointer (layers.%s)", who,
@@ -390,7 +402,7 @@ int check_layers(const rajni_vit_plan& p, const rajni_vit_ext* e, int P, const r
                   "%s: layers.blocks must be strictly ascending block indices in [0, %d) (blocks[%d] = %d)", who, p.depth, l, y.blocks[l]);
   RAJNI_REQUIRE(y.norm == 0 || y.norm == 1, RAJNI_ERR_INVALID, "%s: layers.norm must be 0 or 1 (%d)", who, y.norm);
   RAJNI_REQUIRE(y.fill == 0 || y.fill == 1, RAJNI_ERR_INVALID, "%s: layers.fill must be 0 (zero rows) or 1 (last state) (%d)", who, y.fill);
-  const long long gw = p.img_size / p.patch_size, dense = (long long)p.B * (gw * gw + P) * p.C;
+  const long long dense = (long long)p.B * (patch_tokens(p, img) + P) * p.C;
   RAJNI_REQUIRE(y.slab_stride == 0 || (y.slab_stride >= dense && y.slab_stride % 8 == 0), RAJNI_ERR_INVALID,
                 "%s: layers.slab_stride must be 0 or a multiple of 8 that is >= B * (P + n) * C = %lld (%lld)", who, dense, y.slab_stride);
   RAJNI_REQUIRE_PLACED(who, {"layers.out", y.out, 16});
@@ -402,9 +414,25 @@ int check_layers(const rajni_vit_plan& p, const rajni_vit_ext* e, int P, const r
   return RAJNI_OK;
 }
 
+// the image record against the plan (rajni_hip_image.h): host-side integer tests, in front of every other refusal
+int check_image(const rajni_vit_plan& p, const rajni_vit_prefix* pre, const rajni_vit_image& im) {
+  const char* who = "rajni_vit_forward_image";
+  RAJNI_REQUIRE(p.patch_size > 0, RAJNI_ERR_INVALID, "%s: bad plan (patch_size %d)", who, p.patch_size);
+  RAJNI_REQUIRE(im.height > 0 && im.width > 0 && im.height % p.patch_size == 0 && im.width % p.patch_size == 0, RAJNI_ERR_INVALID,
+                "%s: image.height and image.width must be positive multiples of the patch size %d (%d x %d)", who, p.patch_size,
+                im.height, im.width);
+  RAJNI_REQUIRE(p.img_size == im.height, RAJNI_ERR_INVALID, "%s: plan.img_size must equal image.height (%d != %d)", who, p.img_size,
+                im.height);
+  const long long n0 = (long long)(im.height / p.patch_size) * (im.width / p.patch_size) + prefix_count(pre);
+  RAJNI_REQUIRE(n0 <= RAJNI_IMAGE_MAX_TOKENS, RAJNI_ERR_UNSUPPORTED,
+                "%s: N=%lld is beyond the tiled path's cap of %d tokens (%d x %d patches and %d prefix tokens)", who, n0,
+                RAJNI_IMAGE_MAX_TOKENS, im.height / p.patch_size, im.width / p.patch_size, prefix_count(pre));
+  return RAJNI_OK;
+}
+
 // src [B, Nf] = where each token of the stream that enters block `upto` (p.depth: the final stream) sat in the unpruned
 // sequence: the selections of the scheduled blocks in front of it (the forced one where a block has it), last block first
-int launch_source_idx_before(const rajni_vit_plan& p, int P, int upto, int32_t* src, int Nf, hipStream_t s) {
+int launch_source_idx_before(const rajni_vit_plan& p, int P, int upto, int32_t* src, int Nf, hipStream_t s, const rajni_vit_image* img) {
   std::vector<const int32_t*> idx;
   std::vector<int> width, nsrc;
   for (int i = upto - 1; i >= 0; --i) {
@@ -412,7 +440,7 @@ int launch_source_idx_before(const rajni_vit_plan& p, int P, int upto, int32_t* 
     if (blk.keep <= 0) continue;
     idx.push_back(blk.forced_keep_idx ? blk.forced_keep_idx : blk.keep_idx);
     width.push_back(blk.keep + P);
-    nsrc.push_back(tokens_entering(p, P, i));
+    nsrc.push_back(tokens_entering(p, P, i, img));
   }
   return launch_source_idx(src, idx.data(), width.data(), nsrc.data(), (int)idx.size(), p.B, Nf, s);
 }
@@ -420,7 +448,7 @@ int launch_source_idx_before(const rajni_vit_plan& p, int P, int upto, int32_t* 
 // the whole forward; ext == nullptr (rajni_vit_forward) and an all-zero record enqueue the same launches, and so does
 // pre == nullptr (or a record with one prefix token) next to any ext
 int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre, const void* images,
-                void* logits, hipStream_t s, const rajni_vit_layers* lay = nullptr);
+                void* logits, hipStream_t s, const rajni_vit_layers* lay = nullptr, const rajni_vit_image* img = nullptr);
 
 }  // namespace
 
@@ -459,6 +487,24 @@ extern "C" int rajni_vit_forward_layers(const rajni_vit_plan* plan, const rajni_
   return vit_forward(plan, ext, prefix, images, logits, (hipStream_t)stream, layers);
 }
 
+extern "C" size_t rajni_vit_workspace_bytes_image(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix, const rajni_vit_image* image) {
+  if (!image) return rajni_vit_workspace_bytes_prefix(plan, prefix);
+  if (!plan || plan->patch_size <= 0) return 0;
+  if (check_prefix(prefix, "rajni_vit_workspace_bytes_image") != RAJNI_OK || check_image(*plan, prefix, *image) != RAJNI_OK) return 0;
+  rajni_vit_plan tmp = *plan;
+  tmp.workspace = nullptr;
+  return carve(tmp, prefix_count(prefix), head_row_count(prefix), image).total;
+}
+
+extern "C" int rajni_vit_forward_image(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
+                                       const rajni_vit_layers* layers, const rajni_vit_image* image, const void* images, void* logits,
+                                       rajni_stream_t stream) {
+  if (!image) return rajni_vit_forward_layers(plan, ext, prefix, layers, images, logits, stream);
+  const int rc = check_prefix(prefix, "rajni_vit_forward_image");
+  if (rc != RAJNI_OK) return rc;
+  return vit_forward(plan, ext, prefix, images, logits, (hipStream_t)stream, layers, image);
+}
+
 extern "C" void rajni_debug_set_last_block_all_rows(int on) { g_last_block_all_rows = on; }
 
 // 1 when the forward of this plan (with this ext / prefix record, either may be NULL) computes its last block for the rows the
@@ -473,11 +519,13 @@ extern "C" int rajni_debug_last_block_cls_rows(const rajni_vit_plan* plan, const
 namespace {
 
 int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre, const void* images,
-                void* logits, hipStream_t s, const rajni_vit_layers* lay) {
+                void* logits, hipStream_t s, const rajni_vit_layers* lay, const rajni_vit_image* img) {
   RAJNI_REQUIRE(plan && images && logits, RAJNI_ERR_INVALID, "rajni_vit_forward: null pointer");
   const rajni_vit_plan& p = *plan;
   const bool dense_last = ext != nullptr && ext->pool == RAJNI_POOL_DENSE_LAST;
-  int rc = lay ? check_layers(p, ext, prefix_count(pre), *lay) : RAJNI_OK;
+  int rc = img ? check_image(p, pre, *img) : RAJNI_OK;   // first: every count below is against the record's grid
+  if (rc != RAJNI_OK) return rc;
+  rc = lay ? check_layers(p, ext, prefix_count(pre), *lay, img) : RAJNI_OK;
   if (rc != RAJNI_OK) return rc;
   rc = dense_last ? check_dense_last(p, pre) : RAJNI_OK;
   if (rc != RAJNI_OK) return rc;
@@ -495,19 +543,19 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
   const rajni_qk_affine* qkn = ext ? ext->qk_norm : nullptr;
   const int P = prefix_count(pre);   // prefix tokens: CLS + registers (or the dist token), never pruned
   const int HR = head_row_count(pre);   // rows of each image the head reads
-  rc = check_schedule(p, P);
+  rc = check_schedule(p, P, img);
   if (rc != RAJNI_OK) return rc;
-  const Workspace w = carve(p, P, HR);
+  const Workspace w = carve(p, P, HR, img);
   RAJNI_REQUIRE(p.workspace != nullptr && p.workspace_bytes >= w.total, RAJNI_ERR_INVALID,
                 "rajni_vit_forward: workspace too small (%zu < %zu)", p.workspace_bytes, w.total);
   const int B = p.B, C = p.C, dt = p.dtype;
   const Fwd f{p, w, (dt != RAJNI_F32 && !p.resid_bf16) ? 1 : 0, s,
               (ext && ext->mlp_act == RAJNI_MLP_QUICK_GELU) ? RAJNI_EPI_BIAS_QUICK_GELU
               : (ext && ext->mlp_act == RAJNI_MLP_SWIGLU) ? RAJNI_EPI_BIAS_SWIGLU : RAJNI_EPI_BIAS_GELU};
-  int N = tokens_entering(p, P, 0);
+  int N = tokens_entering(p, P, 0, img);
 
   rc = launch_patch_embed(images, p.patch_w, p.patch_b, p.cls_token, p.pos_embed, p.pos_has_cls,
-                          w.xa, f.sf32, B, p.in_chans, p.img_size, p.patch_size, C, dt, w.cols, w.cols_bytes, s,
+                          w.xa, f.sf32, B, p.in_chans, image_height(p, img), image_width(p, img), p.patch_size, C, dt, w.cols, w.cols_bytes, s,
                           P, P > 1 ? pre->reg_token : nullptr);
   if (rc != RAJNI_OK) return rc;
   if (ext && ext->norm_pre_w) {   // timm forward_features: x = norm_pre(x), written back into the stream
@@ -522,7 +570,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
 
   // rajni_vit_forward_layers: slab l is lay->out + l * slab_ld elements; `cap` walks the ascending capture list with the
   // block loop, so slabs [cap, n) are the ones a block at or in front of the next capture still writes to
-  const int S0 = tokens_entering(p, P, 0);
+  const int S0 = tokens_entering(p, P, 0, img);
   const size_t slab_ld = lay ? (lay->slab_stride ? (size_t)lay->slab_stride : (size_t)B * S0 * C) : 0;
   auto slab = [&](int l) { return static_cast<void*>(static_cast<char*>(lay->out) + (size_t)l * slab_ld * rajni_elem_bytes(dt)); };
   int cap = 0;
@@ -639,7 +687,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
       // gathered the kept rows into `oth`).  Where each entering token sat in the unpruned sequence goes to w.qkv, dead
       // between the tail and the next block's QKV GEMM (B * N * 4 bytes always fit); then the final norm of the dropped rows
       int32_t* src = reinterpret_cast<int32_t*>(w.qkv);
-      rc = launch_source_idx_before(p, P, i, src, N, s);
+      rc = launch_source_idx_before(p, P, i, src, N, s, img);
       if (rc != RAJNI_OK) return rc;
       if (dense_last) {
         rc = launch_layernorm_dropped(cur, idx, src, p.norm_w, p.norm_b, logits, B, N, Np, P, S0, C, p.ln_eps, f.sf32, dt, s);
@@ -659,7 +707,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
       // a captured block: the stream behind it, scattered to slab `cap` through the map of the selections up to and including
       // this block's (w.qkv again: the launches above have read their map, in stream order)
       int32_t* src = reinterpret_cast<int32_t*>(w.qkv);
-      rc = launch_source_idx_before(p, P, i + 1, src, N, s);
+      rc = launch_source_idx_before(p, P, i + 1, src, N, s, img);
       if (rc != RAJNI_OK) return rc;
       rc = lay->norm ? launch_layernorm_dense(cur, src, p.norm_w, p.norm_b, slab(cap), B, N, S0, C, p.ln_eps, f.sf32, dt, s, lay->fill ? 0 : 1)
                      : launch_rows_dense_cast(cur, src, slab(cap), B, N, S0, C, f.sf32, dt, s, lay->fill ? 0 : 1);
@@ -679,9 +727,9 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
     // rows were written behind the blocks that dropped them and stay).  The composed selection lives in w.qkv, dead behind
     // the last block (B * N * 4 bytes always fit)
     int32_t* src = reinterpret_cast<int32_t*>(w.qkv);
-    rc = launch_source_idx_before(p, P, p.depth, src, N, s);
+    rc = launch_source_idx_before(p, P, p.depth, src, N, s, img);
     if (rc != RAJNI_OK) return rc;
-    return launch_layernorm_dense(cur, src, p.norm_w, p.norm_b, logits, B, N, tokens_entering(p, P, 0), C, p.ln_eps, f.sf32, dt, s,
+    return launch_layernorm_dense(cur, src, p.norm_w, p.norm_b, logits, B, N, S0, C, p.ln_eps, f.sf32, dt, s,
                                   dense_last ? 0 : 1);
   }
   if (ext && (ext->pool != RAJNI_POOL_TOKEN || ext->fc_norm_w || ext->norm_absent))

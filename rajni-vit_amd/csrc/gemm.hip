@@ -57,7 +57,8 @@ struct GemmParams {
   int tiles_n, total_tiles;
   int nblk;                     // persistent tilings: column tiles per N block of the tile order (tile_mn)
   // patch-embed A loader / epilogue
-  int cin, S, log2ps, gw, npatch;
+  int cin, S, log2ps, gw, npatch;   // S: image width in pixels, the row stride
+  int IH;                       // image height in pixels: the channel stride is IH * S
   int nprefix;                  // prefix rows per image ahead of the patch rows: CLS + register tokens (>= 1)
   const void* pos; int pos_off; // pos-embed rows, activation dtype
   unsigned long long* stamps;   // diagnostic builds only (RAJNI_GEMM_STAMPS): 4 s_memtime values per block
@@ -839,7 +840,7 @@ struct XSource {
     } else {
       const int b = m / p.npatch, pp = m - b * p.npatch;
       const int py = pp / p.gw, px = pp - py * p.gw;
-      base = X + ((long)b * p.cin * p.S + (py << p.log2ps)) * p.S + (px << p.log2ps);
+      base = X + ((long)b * p.cin * p.IH + (py << p.log2ps)) * p.S + (px << p.log2ps);
       kofs = chunk * CH;
     }
   }
@@ -848,7 +849,7 @@ struct XSource {
     const int k = k0 + kofs, ps2 = 2 * p.log2ps;
     const int ch = k >> ps2, rem = k & ((1 << ps2) - 1);
     const int ky = rem >> p.log2ps, kx = rem & ((1 << p.log2ps) - 1);
-    return base + ((long)ch * p.S + ky) * p.S + kx;
+    return base + ((long)ch * p.IH + ky) * p.S + kx;
   }
 };
 
@@ -1868,24 +1869,25 @@ extern "C" int rajni_debug_linear_plan(const rajni_linear_args* args, int cus, r
 // the fused im2col loader reads 16-byte runs of a patch row with shifts: power-of-two patches of >= 8 pixels
 // whose K = Cin*P*P is whole K steps.  Everything else (P = 14: ViT-L/14, ViT-H/14, DINOv2, CLIP) goes through a
 // materialised, zero-padded column matrix.
-static bool patch_fused(int Cin, int S, int P) {
-  return P >= 8 && (P & (P - 1)) == 0 && S % 8 == 0 && (Cin * P * P) % 64 == 0;
+// (W is the image width, the row stride: a 16-byte run must not straddle rows; the height is free)
+static bool patch_fused(int Cin, int W, int P) {
+  return P >= 8 && (P & (P - 1)) == 0 && W % 8 == 0 && (Cin * P * P) % 64 == 0;
 }
-size_t patch_embed_workspace_bytes(int B, int Cin, int S, int P, int dtype) {
-  if (P <= 0 || S <= 0 || S % P != 0 || patch_fused(Cin, S, P)) return 0;
-  const size_t kpad = ((size_t)Cin * P * P + 63) / 64 * 64, gw = S / P;
-  return (size_t)B * gw * gw * kpad * (dtype == RAJNI_F32 ? 4 : 2);
+size_t patch_embed_workspace_bytes(int B, int Cin, int H, int W, int P, int dtype) {
+  if (P <= 0 || H <= 0 || W <= 0 || H % P != 0 || W % P != 0 || patch_fused(Cin, W, P)) return 0;
+  const size_t kpad = ((size_t)Cin * P * P + 63) / 64 * 64, gh = H / P, gw = W / P;
+  return (size_t)B * gh * gw * kpad * (dtype == RAJNI_F32 ? 4 : 2);
 }
-// cols[m, k] = images[b, c, gy*P + py, gx*P + px] for k = (c*P + py)*P + px < Cin*P*P, 0 for the padding;
+// cols[m, k] = images[b, c, gy*P + py, gx*P + px] for k = (c*P + py)*P + px < Cin*P*P, 0 for the padding; images are
+// [B, Cin, H, W], npatch = (H/P) * gw patches per image, gw = W/P;
 // one thread = 8 consecutive k of one patch row (one 16-byte store for bf16)
 template <typename T>
-__global__ void __launch_bounds__(256) im2col_kernel(const T* img, T* cols, int Cin, int S, int P, int gw, int kpad, long total8) {
+__global__ void __launch_bounds__(256) im2col_kernel(const T* img, T* cols, int Cin, int H, int W, int P, int gw, int npatch, int kpad, long total8) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total8) return;
   const int k8 = kpad >> 3;
   const long m = i / k8;
   const int k0 = (int)(i - m * k8) * 8;
-  const int npatch = gw * gw;
   const int b = (int)(m / npatch), pp = (int)(m - (long)b * npatch);
   const int gy = pp / gw, gx = pp - gy * gw;
   const int K = Cin * P * P;
@@ -1896,7 +1898,7 @@ __global__ void __launch_bounds__(256) im2col_kernel(const T* img, T* cols, int 
     T e = T(0);
     if (k < K) {
       const int c = k / (P * P), r = k - c * P * P, py = r / P, px = r - py * P;
-      e = img[(((long)b * Cin + c) * S + gy * P + py) * S + gx * P + px];
+      e = img[(((long)b * Cin + c) * H + gy * P + py) * W + gx * P + px];
     }
     v[j] = e;
   }
@@ -1913,7 +1915,7 @@ static void with_stream_types(int dtype, int out_f32, F&& f) {
   else out_f32 ? f(std::true_type{}, bf16_t{}) : f(std::false_type{}, bf16_t{});
 }
 int launch_patch_embed(const void* images, const void* w, const float* bias, const void* cls,
-                       const void* pos, int pos_has_cls, void* x, int out_f32, int B, int Cin, int S,
+                       const void* pos, int pos_has_cls, void* x, int out_f32, int B, int Cin, int H, int W,
                        int P, int C, int dtype, void* ws, size_t ws_bytes, hipStream_t s, int num_prefix, const void* reg) {
   RAJNI_REQUIRE(images && w && cls && pos && x, RAJNI_ERR_INVALID, "rajni_patch_embed: null pointer");
   RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
@@ -1921,13 +1923,16 @@ int launch_patch_embed(const void* images, const void* w, const float* bias, con
   RAJNI_REQUIRE(num_prefix == 1 || reg != nullptr, RAJNI_ERR_INVALID, "rajni_patch_embed: %d prefix tokens but reg_token is null", num_prefix);
   RAJNI_REQUIRE(num_prefix == 1 || ((uintptr_t)cls % 16 == 0 && (uintptr_t)reg % 16 == 0 && (uintptr_t)pos % 16 == 0),
                 RAJNI_ERR_INVALID, "rajni_patch_embed: cls, reg_token and pos must be 16-byte aligned");
-  RAJNI_REQUIRE(P >= 1 && S % P == 0 && B > 0 && Cin > 0, RAJNI_ERR_INVALID,
-                "rajni_patch_embed: the patch size must divide the image (P=%d S=%d)", P, S);
+  if (H == W)   // (the square entry points: their wording)
+    RAJNI_REQUIRE(P >= 1 && W % P == 0 && B > 0 && Cin > 0, RAJNI_ERR_INVALID,
+                  "rajni_patch_embed: the patch size must divide the image (P=%d S=%d)", P, W);
+  RAJNI_REQUIRE(P >= 1 && H > 0 && W > 0 && H % P == 0 && W % P == 0 && B > 0 && Cin > 0, RAJNI_ERR_INVALID,
+                "rajni_patch_embed: the patch size must divide the image (P=%d H=%d W=%d)", P, H, W);
   RAJNI_REQUIRE(C % 8 == 0, RAJNI_ERR_UNSUPPORTED, "rajni_patch_embed: C %% 8 == 0 required");
   RAJNI_REQUIRE(dtype == RAJNI_BF16 || dtype == RAJNI_F32 || dtype == RAJNI_F16, RAJNI_ERR_INVALID,
                 "rajni_patch_embed: bad dtype %d", dtype);
   const int K = Cin * P * P, kpad = (K + 63) / 64 * 64;
-  const int gw = S / P, npatch = gw * gw;
+  const int gw = W / P, npatch = (H / P) * gw;
   GemmParams p{};
   p.W = w; p.ldw = kpad;
   p.bias = bias;
@@ -1936,23 +1941,23 @@ int launch_patch_embed(const void* images, const void* w, const float* bias, con
   p.gw = gw; p.npatch = npatch;
   p.pos = pos; p.pos_off = pos_has_cls ? num_prefix : 0;
   p.nprefix = num_prefix;
-  const bool fused = patch_fused(Cin, S, P);
+  const bool fused = patch_fused(Cin, W, P);
   if (fused) {
     int log2ps = 0;
     while ((1 << log2ps) < P) ++log2ps;
     p.X = images; p.lda = 0;
-    p.cin = Cin; p.S = S; p.log2ps = log2ps;
+    p.cin = Cin; p.S = W; p.IH = H; p.log2ps = log2ps;
   } else {
-    const size_t need = patch_embed_workspace_bytes(B, Cin, S, P, dtype);
+    const size_t need = patch_embed_workspace_bytes(B, Cin, H, W, P, dtype);
     RAJNI_REQUIRE(ws != nullptr && ws_bytes >= need && (uintptr_t)ws % 16 == 0, RAJNI_ERR_INVALID,
                   "rajni_patch_embed: patch size %d needs a %zu-byte, 16-byte aligned column workspace (got %zu)", P, need, ws_bytes);
     ProfScope prof(KC_CLS_POS, s, 0.0, 2.0 * (double)need);
     const long total8 = (long)B * npatch * (kpad / 8);
     const dim3 grid((unsigned)((total8 + 255) / 256)), block(256);
     if (dtype == RAJNI_F32)
-      hipLaunchKernelGGL(im2col_kernel<float>, grid, block, 0, s, (const float*)images, (float*)ws, Cin, S, P, gw, kpad, total8);
+      hipLaunchKernelGGL(im2col_kernel<float>, grid, block, 0, s, (const float*)images, (float*)ws, Cin, H, W, P, gw, npatch, kpad, total8);
     else   // a byte copy: the bf16 instantiation serves fp16 images too
-      hipLaunchKernelGGL(im2col_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)images, (bf16_t*)ws, Cin, S, P, gw, kpad, total8);
+      hipLaunchKernelGGL(im2col_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)images, (bf16_t*)ws, Cin, H, W, P, gw, npatch, kpad, total8);
     RAJNI_CHECK_LAUNCH("im2col_kernel");
     p.X = ws; p.lda = kpad;
   }

@@ -108,6 +108,11 @@ class VitLayers(C.Structure):
                 ("slab_stride", C.c_longlong)]
 
 
+class VitImage(C.Structure):
+    """rajni_vit_image (include/rajni_hip_image.h): the input's height and width in pixels, beside the plan"""
+    _fields_ = [("height", c_int), ("width", c_int)]
+
+
 MAX_LAYERS = 64     # RAJNI_MAX_LAYERS
 MAX_PREFIX = 32     # RAJNI_MAX_PREFIX
 SCORE_TILE_TOKENS = 32      # ST_TILE of csrc/score_select.hip: tokens per workgroup of the tiled score kernels
@@ -182,6 +187,18 @@ _LAYERS_SIGS = {
                                          c_void_p, c_void_p, c_void_p]),
 }
 LAYERS_SYMBOLS = ("rajni_vit_forward_layers",)
+# include/rajni_hip_image.h, additive in the same way: rectangular images and the position-embedding resample
+_IMAGE_SIGS = {
+    "rajni_resample_pos_embed": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "rajni_patch_embed_image": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                        c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "rajni_patch_embed_workspace_bytes_image": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "rajni_vit_workspace_bytes_image": (c_size_t, [C.POINTER(VitPlan), C.POINTER(VitPrefix), C.POINTER(VitImage)]),
+    "rajni_vit_forward_image": (c_int, [C.POINTER(VitPlan), C.POINTER(VitExt), C.POINTER(VitPrefix), C.POINTER(VitLayers),
+                                        C.POINTER(VitImage), c_void_p, c_void_p, c_void_p]),
+}
+IMAGE_SYMBOLS = tuple(_IMAGE_SIGS.keys())
+RESAMPLE_MAX_GRID = 128     # RAJNI_RESAMPLE_MAX_GRID: grid cells per axis, source and destination
 ABI_VERSION = 8     # include/rajni_hip.h; bumped whenever a struct or an entry point changes
 _lib: Optional[C.CDLL] = None
 
@@ -196,7 +213,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
             f"librajni_hip.so not found at {path}. Build it with `python rajni-vit_amd/build.py` "
             "(hipcc --offload-arch=gfx950). rajni_amd has no CPU or PyTorch fallback by design.")
     lib = C.CDLL(path)
-    for name, (res, args) in list(_SIGS.items()) + list(_LAYERS_SIGS.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_LAYERS_SIGS.items()) + list(_IMAGE_SIGS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -411,27 +411,39 @@ def linear(x: torch.Tensor, w_packed: torch.Tensor, n_out: int, bias: Optional[t
 
 def patch_embed(images: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, cls: torch.Tensor,
                 pos: torch.Tensor, pos_has_cls: bool, patch: int, embed_dim: int,
-                out_f32: bool = False, reg: Optional[torch.Tensor] = None) -> torch.Tensor:
+                out_f32: bool = False, reg: Optional[torch.Tensor] = None, size: Optional[Tuple[int, int]] = None) -> torch.Tensor:
     """images [B, Cin, S, S] -> x [B, P + (S/patch)^2, C]: CLS, the R = P - 1 register tokens `reg` ([R, C] in the images'
-    dtype, None = no registers), then the patches; `pos` has (P if pos_has_cls else 0) + (S/patch)^2 rows."""
+    dtype, None = no registers), then the patches; `pos` has (P if pos_has_cls else 0) + (S/patch)^2 rows.
+    With `size=(H, W)` the images are [B, Cin, H, W] (rajni_patch_embed_image): (H/patch) * (W/patch) patches, row-major."""
     nat.require_device(images, "images")
     images, w_packed, bias = _placed(images, "images"), _placed(w_packed, "w"), _placed(bias, "bias")
     cls, pos = _placed(cls, "cls"), _placed(pos, "pos")
-    B, Cin, S, _ = images.shape
+    B, Cin, S, Wd = images.shape
+    if size is None and S != Wd:
+        raise ValueError(f"patch_embed: images [B, Cin, S, S] expected, got {tuple(images.shape)}; pass size=(H, W) for a rectangle")
+    if size is not None and (int(size[0]), int(size[1])) != (S, Wd):
+        raise ValueError(f"patch_embed: size={tuple(size)} but the images are {tuple(images.shape)}")
     if reg is not None:
         if reg.dim() != 2 or reg.shape[1] != embed_dim or reg.shape[0] < 1 or reg.dtype != images.dtype:
             raise ValueError(f"patch_embed: reg must be [R, {embed_dim}] in the images' dtype, got {tuple(reg.shape)} {reg.dtype}")
         reg = _placed(reg, "reg")
     P = 1 + (reg.shape[0] if reg is not None else 0)
-    n = (S // patch) ** 2 + P
+    n = (S // patch) * (Wd // patch) + P
     x = torch.empty((B, n, embed_dim), dtype=torch.float32 if out_f32 else images.dtype, device=images.device)
     kpad = (Cin * patch * patch + 63) // 64 * 64
     if w_packed.shape[1] != kpad:
         raise ValueError(f"patch_embed: weight must be packed with k_multiple=64 ([*, {kpad}]), got {tuple(w_packed.shape)}")
-    nbytes = nat.lib().rajni_patch_embed_workspace_bytes(B, Cin, S, patch, _dt(images))   # 0: im2col fused into the loads
+    # 0: im2col fused into the loads
+    nbytes = (nat.lib().rajni_patch_embed_workspace_bytes(B, Cin, S, patch, _dt(images)) if size is None
+              else nat.lib().rajni_patch_embed_workspace_bytes_image(B, Cin, S, Wd, patch, _dt(images)))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=images.device) if nbytes else None
     with nat.device_guard(images.device):
-        if reg is None:
+        if size is not None:
+            nat.check(nat.lib().rajni_patch_embed_image(images.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), cls.data_ptr(),
+                                                        nat.ptr(reg), P, pos.data_ptr(), int(pos_has_cls), x.data_ptr(),
+                                                        int(out_f32), B, Cin, S, Wd, patch, embed_dim, _dt(images), nat.ptr(ws),
+                                                        nbytes, nat.stream_ptr(images.device)), "rajni_patch_embed_image")
+        elif reg is None:
             nat.check(nat.lib().rajni_patch_embed(images.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), cls.data_ptr(),
                                                   pos.data_ptr(), int(pos_has_cls), x.data_ptr(), int(out_f32), B, Cin, S, patch,
                                                   embed_dim, _dt(images), nat.ptr(ws), nbytes, nat.stream_ptr(images.device)),
@@ -442,3 +454,26 @@ def patch_embed(images: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor
                                                          int(out_f32), B, Cin, S, patch, embed_dim, _dt(images), nat.ptr(ws),
                                                          nbytes, nat.stream_ptr(images.device)), "rajni_patch_embed_prefix")
     return x
+
+
+def resample_pos_embed(pos: torch.Tensor, src_grid: Tuple[int, int], dst_grid: Tuple[int, int], prefix_rows: int = 0,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """timm's resample_abs_pos_embed (rajni_resample_pos_embed): pos [prefix_rows + sh * sw, C] -> [prefix_rows + dh * dw, C]
+    in pos's dtype; the prefix rows are copied, the patch rows go fp32 -> bicubic with antialiasing -> one rounding.  Equal
+    grids return the source's bits.  `out` (contiguous, 16-byte aligned, the result's shape and dtype) is written in place."""
+    nat.require_device(pos, "pos")
+    (sh, sw), (dh, dw), pr = (int(v) for v in src_grid), (int(v) for v in dst_grid), int(prefix_rows)
+    if pos.dim() != 2 or pos.shape[0] != pr + sh * sw:
+        raise ValueError(f"resample_pos_embed: pos must be [{pr} + {sh} * {sw}, C], got {tuple(pos.shape)}")
+    pos = _placed(pos, "pos")
+    Cc = pos.shape[1]
+    if out is None:
+        out = torch.empty((pr + dh * dw, Cc), dtype=pos.dtype, device=pos.device)
+    else:
+        if tuple(out.shape) != (pr + dh * dw, Cc) or out.dtype != pos.dtype or out.device != pos.device:
+            raise ValueError(f"resample_pos_embed: out must be [{pr + dh * dw}, {Cc}] {pos.dtype} on {pos.device}")
+        out = _placed(out, "out", in_place=True)
+    with nat.device_guard(pos.device):
+        nat.check(nat.lib().rajni_resample_pos_embed(pos.data_ptr(), sh, sw, out.data_ptr(), dh, dw, Cc, pr, _dt(pos),
+                                                     nat.stream_ptr(pos.device)), "rajni_resample_pos_embed")
+    return out

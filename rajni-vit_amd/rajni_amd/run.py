@@ -50,7 +50,16 @@ def get_args(argv=None):
     p.add_argument("--residual", type=str, default="float32", choices=["float32", "bfloat16", "float16"],
                    help="residual stream precision between blocks (RAJNIViTWrapper.set_residual_dtype; "
                         "a 16-bit stream must match --dtype)")
-    return p.parse_args(argv)
+    p.add_argument("--img_size", type=int, nargs="+", default=None, metavar=("H", "W"),
+                   help="synthetic loader: image height and width in pixels (one value: a square); sizes other than the "
+                        "model's own need --dynamic_img_size")
+    p.add_argument("--dynamic_img_size", action="store_true",
+                   help="RAJNIViTWrapper.set_dynamic_img_size: any H x W the patch size divides, the position embedding resampled "
+                        "as timm's dynamic_img_size=True does (the stock base model of --compare_base must accept the size itself)")
+    args = p.parse_args(argv)
+    if args.img_size is not None and len(args.img_size) > 2:
+        p.error("--img_size takes H or H W")
+    return args
 
 
 def load_schedule(path):
@@ -119,8 +128,9 @@ class SyntheticLoader:
     """`n_batches` seeded (images, labels) batches resident on the device."""
 
     def __init__(self, n_batches, batch, img, device, dtype, seed):
+        h, w = (img, img) if isinstance(img, int) else img
         g = torch.Generator(device=device).manual_seed(seed)
-        self.images = torch.randn(batch, 3, img, img, generator=g, device=device).to(dtype)
+        self.images = torch.randn(batch, 3, h, w, generator=g, device=device).to(dtype)
         self.labels = torch.randint(0, 1000, (batch,), generator=g, device=device)
         self.n = n_batches
 
@@ -146,6 +156,8 @@ def build_loader(args, img_size, device, dtype, rank, world):
         return torch.utils.data.DataLoader(ds, batch_size=args.batch_size, shuffle=False, sampler=sampler,
                                            num_workers=args.num_workers, pin_memory=True, drop_last=False)
     n = args.max_batches if args.max_batches is not None else 20
+    if args.img_size is not None:
+        img_size = (args.img_size[0], args.img_size[-1])
     return SyntheticLoader(n, args.batch_size, img_size, device, dtype, 1234 + rank)
 
 
@@ -188,6 +200,8 @@ def main(argv=None):
         model.set_weight_format(args.weight_format)
     if args.residual != "float32":
         model.set_residual_dtype(getattr(torch, args.residual))
+    if args.dynamic_img_size:
+        model.set_dynamic_img_size(True)
     say("Evaluating RAJNI model (HIP path)...")
     acc, thr = evaluate_model(model, loader, device=device, max_batches=args.max_batches, warmup=args.warmup)
     say(f"RAJNI accuracy: {acc:.2f}%  throughput: {thr:.1f} img/s")

@@ -14,7 +14,8 @@ register, and eval logits `(head(x[:, 0]) + head_dist(x[:, 1])) / 2`).  Beyond t
 final normalised tokens of the pruned graph, or the unpruned sequence with pruned positions zero (`fill="last"`: holding the
 feature each token had when it left the stream), with their source positions in `get_last_stats()["source_idx"]`; and
 `forward_intermediates` / `get_intermediate_layers` (timm's and DINOv2's signatures) return the states behind several blocks from
-one forward, each on that unpruned grid.
+one forward, each on that unpruned grid; and `set_dynamic_img_size(True)` (timm's `dynamic_img_size`): any [B, C, H, W] the
+patch size divides, the position embedding resampled to the input's token grid as timm's resample_abs_pos_embed does.
 
 Not kept: the Python per-block loop.  `forward` builds (once per batch shape) a `rajni_vit_plan`
 - packed weights, workspace, per-stage index buffers - and calls `rajni_vit_forward`, which enqueues
@@ -23,6 +24,7 @@ every kernel of the network on the current stream with no host synchronisation.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, List, Optional
 
 import torch
@@ -273,6 +275,8 @@ class RAJNIViTWrapper(nn.Module):
         self._weight_format = "model"
         # opt-in: compute the last block for the CLS row only (the head reads nothing else, model.py:65-66)
         self._cls_only_last = False
+        # timm's dynamic_img_size: any [B, C, H, W] the patch size divides, the position embedding resampled to its grid
+        self._dynamic_img_size = bool(getattr(base_model, "dynamic_img_size", False))
 
     # ------------------------------------------------------------------------------------------
     def get_last_stats(self):
@@ -309,6 +313,47 @@ class RAJNIViTWrapper(nn.Module):
         self._resid_dtype = dtype
         self._drop_plans()
         return self
+
+    def set_dynamic_img_size(self, on: bool = True):
+        """timm's `dynamic_img_size=True`: accept any [B, C, H, W] whose H and W are multiples of the patch size.  The position
+        embedding is resampled to the input's token grid as timm's resample_abs_pos_embed does (bicubic, antialias; one native
+        launch per new grid, cached), prefix rows passed through.  Off (the default unless the base model says otherwise) the
+        wrapper takes square inputs at the embedding's own grid, plus the reference's `pos_embed[:, :N]` slice."""
+        if bool(on) != self._dynamic_img_size:
+            self._dynamic_img_size = bool(on)
+            self._drop_plans()
+        return self
+
+    def _pos_source_grid(self, pos_rows: int, P: int):
+        """(prefix rows of pos_embed, (src_h, src_w)): `patch_embed.grid_size` when it is a pair whose product is the embedding's
+        patch-row count, else the integer square root of that count; the embedding has P prefix rows or none (no_embed_class)"""
+        gs = getattr(self.m.patch_embed, "grid_size", None)
+        if isinstance(gs, (tuple, list)) and len(gs) == 2 and all(isinstance(v, int) and v > 0 for v in gs):
+            for pr in (P, 0):
+                if gs[0] * gs[1] == pos_rows - pr:
+                    return pr, (int(gs[0]), int(gs[1]))
+        for pr in (P, 0):
+            n = pos_rows - pr
+            r = math.isqrt(n) if n > 0 else 0
+            if r > 0 and r * r == n:
+                return pr, (r, r)
+        raise NotImplementedError(f"RAJNIViTWrapper: dynamic_img_size cannot tell the grid of a pos_embed of {pos_rows} rows "
+                                  f"({P} prefix tokens): patch_embed.grid_size does not give it and it is not square")
+
+    def _pos_for_grid(self, W, gh: int, gw: int, P: int, device, dtype):
+        """(pos tensor [pr + gh * gw, C], pos_has_cls) under dynamic_img_size: the packed embedding itself at its own grid,
+        otherwise the resampled rows - one launch, cached per (gh, gw, device, dtype) beside the packed weights, 8 entries"""
+        pr, src = self._pos_source_grid(W["pos"].shape[0], P)
+        if (gh, gw) == src:
+            return W["pos"], int(pr > 0)
+        cache = W.setdefault("pos_cache", {})
+        key = (gh, gw, device, dtype)
+        if key not in cache:
+            if len(cache) >= 8:
+                cache.pop(next(iter(cache)))
+            with nat.device_guard(device):
+                cache[key] = ops.resample_pos_embed(W["pos"], src, (gh, gw), pr)
+        return cache[key], int(pr > 0)
 
     def set_weight_format(self, fmt: str):
         """"model" (default), "fp8" or "fp8_mfma".
@@ -667,7 +712,9 @@ class RAJNIViTWrapper(nn.Module):
         """`mode`: "logits" (the model's forward: logits, or the pooled feature of a headless model), or the feature outputs
         "tokens" / "dense" / "dense_last" (forward_features): a second plan of the same packed weights with no head and
         ext.pool = POOL_NONE / POOL_DENSE / POOL_DENSE_LAST.  A tuple ("layers", base mode, captured blocks, norm, fill)
-        (forward_intermediates) is the base mode's plan with a layers record beside it, under a key of its own."""
+        (forward_intermediates) is the base mode's plan with a layers record beside it, under a key of its own.
+        `S` is the side of a square input or, under dynamic_img_size, (H, W) of a rectangular one: the plan then carries an image
+        record (rajni_vit_image) and runs through rajni_vit_forward_image."""
         W = self._pack_weights(device, dtype)
         d = W["desc"]
         P = d["num_prefix"]
@@ -685,16 +732,26 @@ class RAJNIViTWrapper(nn.Module):
         if key in self._plans:
             self._plan = self._plans[key]
             return self._plan
-        if S % d["patch"] != 0:
+        # S: the side of a square input, or (H, W) of a rectangular one (dynamic_img_size only)
+        Hh, Wd = (S, S) if isinstance(S, int) else S
+        if Hh % d["patch"] != 0 or Wd % d["patch"] != 0:
             raise ValueError(f"image size {S} is not a multiple of the patch size {d['patch']}")
-        n0 = (S // d["patch"]) ** 2 + P
+        gh, gw = Hh // d["patch"], Wd // d["patch"]
+        n0 = gh * gw + P
         pos_rows = W["pos"].shape[0]
-        if pos_rows == n0 or (P == 1 and pos_rows > n0):
+        pos = W["pos"]
+        if self._dynamic_img_size:
+            if getattr(self.m, "dynamic_img_pad", False) or getattr(self.m.patch_embed, "dynamic_img_pad", False):
+                raise NotImplementedError("RAJNIViTWrapper: dynamic_img_pad (padding images to a multiple of the patch size) is "
+                                          "not supported")
+            pos, pos_has_cls = self._pos_for_grid(W, gh, gw, P, device, dtype)
+        elif pos_rows == n0 or (P == 1 and pos_rows > n0):
             pos_has_cls = 1      # reference: x + pos_embed[:, :N]  (model.py:37); timm: a row for every prefix token too
         elif pos_rows == n0 - P:
             pos_has_cls = 0      # timm no_embed_class: the prefix rows get no pos-embed
         else:
-            raise ValueError(f"pos_embed has {pos_rows} rows but the input yields {n0} tokens ({P} of them prefix tokens)")
+            raise ValueError(f"pos_embed has {pos_rows} rows but the input yields {n0} tokens ({P} of them prefix tokens); "
+                             "set_dynamic_img_size(True) resamples the embedding to the input's grid")
         counts = plan_token_counts(n0, d["depth"], self.pruning_schedule, P)
 
         blocks = (nat.Block * d["depth"])()
@@ -733,13 +790,13 @@ class RAJNIViTWrapper(nn.Module):
 
         plan = nat.VitPlan()
         plan.dtype = nat.dtype_code(dtype)
-        plan.B, plan.in_chans, plan.img_size, plan.patch_size = B, d["in_chans"], S, d["patch"]
+        plan.B, plan.in_chans, plan.img_size, plan.patch_size = B, d["in_chans"], Hh, d["patch"]
         plan.C, plan.H, plan.D, plan.depth, plan.hidden = d["C"], d["H"], d["D"], d["depth"], d["hidden_pad"]
         headless = features or d["headless"]
         plan.num_classes, plan.ln_eps, plan.attn_scale = 0 if headless else d["num_classes"], d["ln_eps"], d["scale"]
         plan.pos_has_cls = pos_has_cls
         plan.patch_w, plan.patch_b = W["patch_w"].data_ptr(), W["patch_b"].data_ptr()
-        plan.cls_token, plan.pos_embed = W["cls"].data_ptr(), W["pos"].data_ptr()
+        plan.cls_token, plan.pos_embed = W["cls"].data_ptr(), pos.data_ptr()
         plan.blocks = blocks
         plan.norm_w, plan.norm_b = nat.ptr(W["norm_w"]), nat.ptr(W["norm_b"])
         plan.head_w, plan.head_b = (None, None) if headless else (W["head_w"].data_ptr(), W["head_b"].data_ptr())
@@ -756,8 +813,17 @@ class RAJNIViTWrapper(nn.Module):
             pre.num_prefix, pre.reg_token = P, W["reg"].data_ptr()
             # (register models: the record as it always was; the feature plan of a distilled model reads no head rows)
             pre.head_rows = 2 if d["head_rows"] == 2 and not features else 0
-        nbytes = (nat.lib().rajni_vit_workspace_bytes(C.byref(plan)) if pre is None
-                  else nat.lib().rajni_vit_workspace_bytes_prefix(C.byref(plan), C.byref(pre)))
+        img = None
+        if Hh != Wd:        # the image record beside the plan (rajni_vit_image); None: a square input, the entry points as ever
+            img = nat.VitImage(Hh, Wd)
+        if img is not None:
+            nbytes = nat.lib().rajni_vit_workspace_bytes_image(C.byref(plan), C.byref(pre) if pre is not None else None, C.byref(img))
+            if nbytes == 0:       # the record is refused: say why (the forward's own refusal, nothing is launched)
+                nat.check(nat.lib().rajni_vit_forward_image(C.byref(plan), None, C.byref(pre) if pre is not None else None, None,
+                                                            C.byref(img), 16, 16, None), "rajni_vit_forward_image")
+        else:
+            nbytes = (nat.lib().rajni_vit_workspace_bytes(C.byref(plan)) if pre is None
+                      else nat.lib().rajni_vit_workspace_bytes_prefix(C.byref(plan), C.byref(pre)))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
         plan.workspace, plan.workspace_bytes = ws.data_ptr(), nbytes
         ext = qk = None
@@ -790,7 +856,8 @@ class RAJNIViTWrapper(nn.Module):
         # W: a stale optimistic launch keeps its weights alive
         # (existing callers index entry[0..4] and unpack entry[2] as seven objects: mode and out_shape go behind `counts`,
         # the layers record behind those)
-        self._plan = (key, plan, (blocks, tc, ws, W, ext, qk, pre), bufs, counts, full_mode, out_shape, layers)
+        # (the image record and the position rows the plan points to, with the grid, last)
+        self._plan = (key, plan, (blocks, tc, ws, W, ext, qk, pre), bufs, counts, full_mode, out_shape, layers, (img, pos, gh, gw))
         if len(self._plans) >= 4:     # workspaces are large: keep only a few batch shapes alive
             self._plans.pop(next(iter(self._plans)))
         self._plans[key] = self._plan
@@ -895,12 +962,12 @@ class RAJNIViTWrapper(nn.Module):
         (final, slabs), entry = self._run(x, ("layers", base, caps, bool(norm), fill))
         self._selection_stats(entry, x, exit_block=True)
         P = entry[0][-2]
-        B, g, Cdim = x.shape[0], x.shape[-1] // entry[1].patch_size, entry[1].C
+        B, (gh, gw), Cdim = x.shape[0], entry[8][2:], entry[1].C
         inter = []
         for l in range(len(caps)):
             spatial = slabs[l, :, P:]
             if output_fmt == "NCHW":
-                spatial = spatial.reshape(B, g, g, Cdim).permute(0, 3, 1, 2).contiguous()
+                spatial = spatial.reshape(B, gh, gw, Cdim).permute(0, 3, 1, 2).contiguous()
             inter.append((spatial, slabs[l, :, :P]) if return_prefix_tokens else spatial)
         return inter if intermediates_only else (final, inter)
 
@@ -917,10 +984,18 @@ class RAJNIViTWrapper(nn.Module):
             return tuple((spatial, prefix[:, 0]) for spatial, prefix in inter)
         return tuple(spatial for spatial, _ in inter)
 
+    @property
+    def dynamic_img_size(self) -> bool:
+        return self._dynamic_img_size
+
+    def _check_input_shape(self, x: torch.Tensor):
+        if x.dim() != 4 or (x.shape[-1] != x.shape[-2] and not self._dynamic_img_size):
+            raise ValueError(f"expected images [B, C, S, S], got {tuple(x.shape)}"
+                             + ("" if x.dim() != 4 else "; set_dynamic_img_size(True) takes [B, C, H, W]"))
+
     def _run(self, x: torch.Tensor, mode: str):
         nat.require_device(x, "input images")
-        if x.dim() != 4 or x.shape[-1] != x.shape[-2]:
-            raise ValueError(f"expected images [B, C, S, S], got {tuple(x.shape)}")
+        self._check_input_shape(x)
         dtype = self.m.cls_token.dtype
         if self._resid_bf16 and dtype in (torch.bfloat16, torch.float16) and self._resid_dtype != dtype:
             raise ValueError(f"a {self._resid_dtype} residual stream needs a {self._resid_dtype} model (the model is {dtype}); "
@@ -930,12 +1005,25 @@ class RAJNIViTWrapper(nn.Module):
         if x.dtype != dtype:
             x = x.to(dtype)
         x = x.contiguous()
-        B, S = x.shape[0], x.shape[-1]
+        # (a square input keeps the key it always had; a rectangle carries (H, W) where that had S)
+        B, S = x.shape[0], (x.shape[-1] if x.shape[-1] == x.shape[-2] else (x.shape[-2], x.shape[-1]))
         with nat.device_guard(x.device):
             def launch(entry):
                 plan = entry[1]
                 out = torch.empty(entry[6], dtype=dtype, device=x.device)
                 ext, pre = entry[2][4], entry[2][6]
+                ref = lambda rec: C.byref(rec) if rec is not None else None
+                if entry[8][0] is not None:   # a rectangular input: every record through rajni_vit_forward_image
+                    lay = slabs = None
+                    if entry[7] is not None:
+                        cap_arr, lnorm, lfill, slab_shape = entry[7]
+                        slabs = torch.empty(slab_shape, dtype=dtype, device=x.device)
+                        lay = nat.VitLayers()
+                        lay.n, lay.blocks, lay.norm, lay.fill, lay.out, lay.slab_stride = len(cap_arr), cap_arr, lnorm, lfill, slabs.data_ptr(), 0
+                    nat.check(nat.lib().rajni_vit_forward_image(C.byref(plan), ref(ext), ref(pre), ref(lay), C.byref(entry[8][0]),
+                                                                x.data_ptr(), out.data_ptr(), nat.stream_ptr(x.device)),
+                              "rajni_vit_forward_image")
+                    return out if lay is None else (out, slabs)
                 if entry[7] is not None:      # forward_intermediates: the slabs beside `out`, one allocation
                     cap_arr, lnorm, lfill, slab_shape = entry[7]
                     slabs = torch.empty(slab_shape, dtype=dtype, device=x.device)
