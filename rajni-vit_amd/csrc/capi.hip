@@ -343,6 +343,68 @@ int rajni_resample_pos_embed(const void* src, int src_h, int src_w, void* dst, i
   return launch_resample_pos_embed(src, src_h, src_w, dst, dst_h, dst_w, C, prefix_rows, dtype, (hipStream_t)stream);
 }
 
+// ---- include/rajni_hip_query.h
+int rajni_score_select_query(const void* qkv, int B, int N, int H, int D, float eps, int num_prefix, int keep, int query,
+                             void* scores_out, int32_t* keep_idx, void* next_scores, int dtype, void* workspace,
+                             size_t workspace_bytes, rajni_stream_t stream) {
+  if (query == RAJNI_QUERY_CLS && num_prefix >= 1)   // the launches and the bits of rajni_score_select_ws
+    return rajni_score_select_ws(qkv, B, N, H, D, eps, num_prefix, keep, scores_out, keep_idx, next_scores, dtype, workspace,
+                                 workspace_bytes, stream);
+  NEED_DTYPE("rajni_score_select_query");
+  RAJNI_REQUIRE(query == RAJNI_QUERY_CLS || query == RAJNI_QUERY_MEAN, RAJNI_ERR_INVALID,
+                "rajni_score_select_query: query must be RAJNI_QUERY_CLS or RAJNI_QUERY_MEAN (%d)", query);
+  const size_t need = rajni_score_select_query_workspace_bytes(B, N, H, D, dtype, query);
+  RAJNI_REQUIRE(B <= RAJNI_MAX_GRID_YZ || need == 0, RAJNI_ERR_UNSUPPORTED,
+                "rajni_score_select_query: B=%d - one launch of the tiled path takes at most %d images (grid: token tiles x images)",
+                B, RAJNI_MAX_GRID_YZ);
+  RAJNI_REQUIRE_PLACED("rajni_score_select_query", {"qkv", qkv, 16}, {"scores_out", scores_out, rajni_elem_bytes(dtype)},
+                       {"keep_idx", keep_idx, 4}, {"next_scores", next_scores, rajni_elem_bytes(dtype)}, {"workspace", workspace, 256});
+  RAJNI_REQUIRE(qkv != nullptr, RAJNI_ERR_INVALID, "rajni_score_select_query: qkv is null");
+  RAJNI_REQUIRE(num_prefix >= 0 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
+                "rajni_score_select_query: num_prefix must be 0..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
+  RAJNI_REQUIRE(B > 0 && N >= num_prefix + 1 && N >= 2, RAJNI_ERR_INVALID,
+                "rajni_score_select_query: need B > 0, at least one patch token and N >= 2 (B=%d N=%d num_prefix=%d)", B, N, num_prefix);
+  RAJNI_REQUIRE(keep >= 0 && keep <= N - num_prefix, RAJNI_ERR_INVALID,
+                "rajni_score_select_query: keep must be 0 (scores only) or 1..%d (%d)", N - num_prefix, keep);
+  RAJNI_REQUIRE(keep == 0 || keep_idx != nullptr, RAJNI_ERR_INVALID, "rajni_score_select_query: keep_idx is null with keep=%d", keep);
+  RAJNI_REQUIRE(keep > 0 || scores_out != nullptr, RAJNI_ERR_INVALID, "rajni_score_select_query: scores_out is null with keep=0");
+  RAJNI_REQUIRE(need == 0 || workspace != nullptr, RAJNI_ERR_INVALID,
+                "rajni_score_select_query: workspace is null but N=%d H=%d D=%d needs %zu B (rajni_score_select_query_workspace_bytes)",
+                N, H, D, need);
+  RAJNI_REQUIRE(workspace_bytes >= need, RAJNI_ERR_INVALID,
+                "rajni_score_select_query: workspace_bytes=%zu but N=%d H=%d D=%d needs %zu B", workspace_bytes, N, H, D, need);
+  return launch_score_select(qkv, nullptr, B, N, H, D, eps, keep, scores_out, keep_idx, next_scores, dtype,
+                             (hipStream_t)stream, num_prefix, need ? workspace : nullptr, need ? workspace_bytes : 0, query);
+}
+
+int rajni_select_topk_query(const void* scores, int B, int N, int num_prefix, int keep, int32_t* keep_idx, void* next_scores,
+                            int dtype, rajni_stream_t stream) {
+  if (num_prefix >= 1) return rajni_select_topk_prefix(scores, B, N, num_prefix, keep, keep_idx, next_scores, dtype, stream);
+  NEED_DTYPE("rajni_select_topk_query");
+  RAJNI_REQUIRE_PLACED("rajni_select_topk_query", {"scores", scores, rajni_elem_bytes(dtype)}, {"keep_idx", keep_idx, 4},
+                       {"next_scores", next_scores, rajni_elem_bytes(dtype)});
+  RAJNI_REQUIRE(scores && keep_idx, RAJNI_ERR_INVALID, "rajni_select_topk_query: null pointer");
+  RAJNI_REQUIRE(num_prefix == 0, RAJNI_ERR_INVALID, "rajni_select_topk_query: num_prefix must be 0..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
+  RAJNI_REQUIRE(B > 0 && N >= 2, RAJNI_ERR_INVALID, "rajni_select_topk_query: need B > 0 and N >= 2 (B=%d N=%d)", B, N);
+  RAJNI_REQUIRE(keep >= 1 && keep <= N, RAJNI_ERR_INVALID, "rajni_select_topk_query: keep must be 1..%d (%d)", N, keep);
+  return launch_score_select(nullptr, scores, B, N, 0, 0, 0.f, keep, nullptr, keep_idx, next_scores, dtype, (hipStream_t)stream, 0);
+}
+
+int rajni_patch_embed_query(const void* images, const void* w, const float* bias, const void* reg, int num_reg, const void* pos,
+                            int pos_has_cls, void* x, int x_f32, int B, int Cin, int H, int W, int P, int C, int dtype,
+                            void* workspace, size_t workspace_bytes, rajni_stream_t stream) {
+  NEED_DTYPE("rajni_patch_embed_query");
+  RAJNI_REQUIRE_PLACED("rajni_patch_embed_query", {"images", images, 16}, {"w", w, 16}, {"bias", bias, 16}, {"reg", reg, 16},
+                       {"pos", pos, 16}, {"x", x, 16}, {"workspace", workspace, 16});
+  RAJNI_REQUIRE(images && w && pos && x, RAJNI_ERR_INVALID, "rajni_patch_embed_query: null pointer");
+  RAJNI_REQUIRE(num_reg >= 0 && num_reg <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
+                "rajni_patch_embed_query: num_reg must be 0..%d (%d)", RAJNI_MAX_PREFIX, num_reg);
+  RAJNI_REQUIRE((num_reg > 0) == (reg != nullptr), RAJNI_ERR_INVALID, "rajni_patch_embed_query: num_reg = %d but reg is %s", num_reg,
+                reg ? "given" : "null");
+  return launch_patch_embed(images, w, bias, nullptr, pos, pos_has_cls, x, x_f32, B, Cin, H, W, P, C, dtype, workspace,
+                            workspace_bytes, (hipStream_t)stream, num_reg, reg, 0);
+}
+
 void rajni_profile_enable(unsigned mask) { g_prof_mask = mask; }
 const char* rajni_profile_class_name(int k) {
   return (k >= 0 && k < RAJNI_NUM_KCLASS) ? kNames[k] : "";

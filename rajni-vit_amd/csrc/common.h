@@ -7,6 +7,7 @@
 #include "../../include/rajni_hip_debug.h"
 #include "../../include/rajni_hip_layers.h"
 #include "../../include/rajni_hip_image.h"
+#include "../../include/rajni_hip_query.h"
 
 typedef unsigned short bf16_t;  // raw bf16 bits in memory
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -212,7 +213,8 @@ int launch_linear(const rajni_linear_args& a, hipStream_t s);
 int launch_patch_embed(const void* images, const void* w, const float* bias, const void* cls,
                        const void* pos, int pos_has_cls, void* x, int out_f32, int B, int Cin, int H, int W,
                        int P, int C, int dtype, void* ws, size_t ws_bytes, hipStream_t s,
-                       int num_prefix = 1, const void* reg = nullptr);   // reg: [num_prefix-1, C] register tokens behind CLS
+                       int num_prefix = 1, const void* reg = nullptr,    // reg: [num_prefix-1, C] register tokens behind CLS
+                       int has_cls = 1);   // 0 (rajni_hip_query.h): no class row - cls is not read, num_prefix = R >= 0, reg [R, C]
 size_t patch_embed_workspace_bytes(int B, int Cin, int H, int W, int P, int dtype);   // images [B, Cin, H, W]; 0: im2col fused into the GEMM loads
 int launch_layernorm(const void* x, long xs, const float* w, const float* b, void* y, int rows,
                      int C, float eps, int x_f32, int dtype, hipStream_t s);
@@ -229,7 +231,7 @@ int launch_attention_cls(const void* qkv, void* out, int B, int N, int H, int D,
 int launch_score_select(const void* qkv, const void* scores_in, int B, int N, int H, int D,
                         float eps, int keep, void* scores_out, int32_t* keep_idx,
                         void* next_scores, int dtype, hipStream_t s, int num_prefix = 1, void* ws = nullptr,
-                        size_t ws_bytes = 0);
+                        size_t ws_bytes = 0, int query = RAJNI_QUERY_CLS);   // RAJNI_QUERY_MEAN: ws sized by rajni_score_select_query_workspace_bytes
 int launch_gather_rows(const void* src, const int32_t* idx, void* dst, int B, int n_src, int n_dst,
                        int row_bytes, hipStream_t s);
 // RAJNI_POOL_DENSE: the selections composed into src [B, Nf] (levels[0] = the last scheduled block's; host arrays), and the

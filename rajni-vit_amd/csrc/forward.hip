@@ -33,6 +33,11 @@
 // workspace carve, the token walk and the patch-embed call, where n0 = (height / patch) * (width / patch) + P replaces the
 // square count; plan.pos_embed holds the rows of that grid (rajni_resample_pos_embed makes them).  Nothing behind the
 // embedding changes, and a NULL or square record enqueues the launches it always did.
+//
+// rajni_vit_forward_query (rajni_hip_query.h) names the importance query of the scoring blocks (row 0, or the mean of the query
+// rows) and whether the sequence has a class row at all.  Without one the prefix tokens are the R >= 0 registers alone: P = R
+// goes through embed, select, the gathered residual, the 'avg' pool, the source map and the dense outputs, the last block always
+// runs every row, and check_query refuses what has no meaning there.  A NULL record or {1, RAJNI_QUERY_CLS} changes no launch.
 #include "common.h"
 
 #include <vector>
@@ -57,7 +62,7 @@ inline int patch_tokens(const rajni_vit_plan& p, const rajni_vit_image* img) {
   return (image_height(p, img) / p.patch_size) * (image_width(p, img) / p.patch_size);
 }
 
-Workspace carve(const rajni_vit_plan& p, int P, int HR, const rajni_vit_image* img = nullptr) {
+Workspace carve(const rajni_vit_plan& p, int P, int HR, const rajni_vit_image* img = nullptr, int query = RAJNI_QUERY_CLS) {
   const size_t n0 = (size_t)patch_tokens(p, img) + P;
   const size_t rows = (size_t)p.B * n0, es = p.dtype == RAJNI_F32 ? 4 : 2, xs = (p.dtype == RAJNI_F32 || !p.resid_bf16) ? 4 : 2;
   Workspace w{};
@@ -70,7 +75,7 @@ Workspace carve(const rajni_vit_plan& p, int P, int HR, const rajni_vit_image* i
   w.cols_bytes = patch_embed_workspace_bytes(p.B, p.in_chans, image_height(p, img), image_width(p, img), p.patch_size, p.dtype);   // 0 when fused
   const size_t ocols = take(w.cols_bytes);
   const size_t oxs = take(p.act_fp8 ? rows * sizeof(float) : 0), ohs = take(p.act_fp8 ? rows * sizeof(float) : 0);
-  w.sst_bytes = rajni_score_select_workspace_bytes(p.B, (int)n0, p.H, p.D, p.dtype);
+  w.sst_bytes = rajni_score_select_query_workspace_bytes(p.B, (int)n0, p.H, p.D, p.dtype, query);   // (CLS: rajni_score_select_workspace_bytes)
   const size_t osst = take(w.sst_bytes);
   const size_t oidx = take(HR == 2 ? (size_t)p.B * 2 * sizeof(int32_t) : 0);   // last: nothing above moves
   char* base = (char*)p.workspace;
@@ -126,7 +131,7 @@ inline bool pool_is_tokens(const rajni_vit_ext* e) {
   return e && (e->pool == RAJNI_POOL_NONE || e->pool == RAJNI_POOL_DENSE || e->pool == RAJNI_POOL_DENSE_LAST);
 }
 
-int check_plan(const rajni_vit_plan& p, bool norm_absent) {
+int check_plan(const rajni_vit_plan& p, bool norm_absent, bool nocls = false) {
   RAJNI_REQUIRE(p.dtype == RAJNI_BF16 || p.dtype == RAJNI_F32 || p.dtype == RAJNI_F16, RAJNI_ERR_INVALID,
                 "rajni_vit_forward: bad dtype %d", p.dtype);
   RAJNI_REQUIRE(p.B > 0 && p.depth > 0 && p.blocks != nullptr, RAJNI_ERR_INVALID, "rajni_vit_forward: bad plan");
@@ -139,7 +144,7 @@ int check_plan(const rajni_vit_plan& p, bool norm_absent) {
   RAJNI_REQUIRE(p.C % 64 == 0 && p.hidden % 64 == 0, RAJNI_ERR_UNSUPPORTED,
                 "rajni_vit_forward: C and hidden must be multiples of 64");
   // a headless plan (head_w == NULL and num_classes == 0) is legal; half of that pair is a missing weight
-  RAJNI_REQUIRE(p.patch_w && p.cls_token && p.pos_embed && (p.head_w != nullptr) == (p.num_classes != 0) &&
+  RAJNI_REQUIRE(p.patch_w && (p.cls_token || nocls) && p.pos_embed && (p.head_w != nullptr) == (p.num_classes != 0) &&
                     (norm_absent || (p.norm_w && p.norm_b)),
                 RAJNI_ERR_INVALID, "rajni_vit_forward: null weight pointer");
   RAJNI_REQUIRE(!(headless(p) && p.act_fp8), RAJNI_ERR_UNSUPPORTED,
@@ -216,9 +221,10 @@ int g_last_block_all_rows = 0;
 // the cls_only_last_block opt-in (they keep the opt-in's own branch and numerics contract).  With the distilled head
 // (head_rows == 2) the observable rows are 0 and 1 of each image, and the block runs on those 2B rows under the same test.
 // Nor for a last block whose output rajni_vit_forward_layers captures (`captured`): the slab reads every row.
-inline bool last_block_cls_rows(const rajni_vit_plan& p, const rajni_vit_ext* ext, int i, int N, bool captured = false) {
+// Nor for a sequence without a class row (`nocls`, rajni_hip_query.h): no head reads a single row of it.
+inline bool last_block_cls_rows(const rajni_vit_plan& p, const rajni_vit_ext* ext, int i, int N, bool captured = false, bool nocls = false) {
   return i == p.depth - 1 && p.blocks[i].keep == 0 && N > 1 && (ext == nullptr || ext->pool == RAJNI_POOL_TOKEN) &&
-         !p.act_fp8 && !p.cls_only_last_block && !g_last_block_all_rows && !captured;
+         !p.act_fp8 && !p.cls_only_last_block && !g_last_block_all_rows && !captured && !nocls;
 }
 
 // what is fixed for one forward, for the builders and launchers below
@@ -310,13 +316,29 @@ int launch_tail(const Fwd& f, const rajni_block& blk, const Tail& t) {
 
 // P of a prefix record: NULL, 0 and 1 all mean CLS only
 inline int prefix_count(const rajni_vit_prefix* pre) { return (pre && pre->num_prefix > 1) ? pre->num_prefix : 1; }
+// the query record (rajni_hip_query.h): NULL is {1, RAJNI_QUERY_CLS}
+inline bool no_class_row(const rajni_vit_query* q) { return q != nullptr && q->class_token == 0; }
+inline int query_mode(const rajni_vit_query* q) { return q ? q->query : RAJNI_QUERY_CLS; }
+// ... without a class row the record counts the registers alone: NULL and 0 mean no prefix token at all
+inline int prefix_count(const rajni_vit_prefix* pre, const rajni_vit_query* q) {
+  return no_class_row(q) ? (pre ? pre->num_prefix : 0) : prefix_count(pre);
+}
 // rows of each image the head reads: NULL, 0 and 1 all mean the CLS row; 2 is the distilled head (cls and dist rows)
 inline int head_row_count(const rajni_vit_prefix* pre) { return (pre && pre->head_rows == 2) ? 2 : 1; }
 
-int check_prefix(const rajni_vit_prefix* pre, const char* who) {
+int check_prefix(const rajni_vit_prefix* pre, const char* who, bool nocls = false) {
   if (!pre) return RAJNI_OK;
   RAJNI_REQUIRE(pre->num_prefix >= 0 && pre->num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
                 "%s: num_prefix must be 0..%d (%d)", who, RAJNI_MAX_PREFIX, pre->num_prefix);
+  if (nocls) {   // the registers alone: reg_token [num_prefix, C]
+    RAJNI_REQUIRE((pre->num_prefix > 0) == (pre->reg_token != nullptr), RAJNI_ERR_INVALID,
+                  "%s: query.class_token = 0 with prefix.num_prefix = %d registers but reg_token is %s", who, pre->num_prefix,
+                  pre->reg_token ? "given" : "null");
+    RAJNI_REQUIRE(pre->head_rows == 0 || pre->head_rows == 1, RAJNI_ERR_INVALID,
+                  "%s: prefix.head_rows = %d with query.class_token = 0 - a sequence without a class row has no head rows", who,
+                  pre->head_rows);
+    return RAJNI_OK;
+  }
   RAJNI_REQUIRE(pre->num_prefix <= 1 || pre->reg_token != nullptr, RAJNI_ERR_INVALID,
                 "%s: %d prefix tokens but reg_token is null", who, pre->num_prefix);
   RAJNI_REQUIRE(pre->num_prefix > 1 || pre->reg_token == nullptr, RAJNI_ERR_INVALID,
@@ -338,6 +360,25 @@ int check_head_rows(const rajni_vit_plan& p, const rajni_vit_ext* e, const rajni
   RAJNI_REQUIRE(!p.cls_only_last_block, RAJNI_ERR_INVALID,
                 "rajni_vit_forward: head_rows=2 with cls_only_last_block - that opt-in forms the CLS row only");
   RAJNI_REQUIRE(!p.act_fp8, RAJNI_ERR_UNSUPPORTED, "rajni_vit_forward: head_rows=2 is unsupported with act_fp8");
+  return RAJNI_OK;
+}
+
+// the query record against the plan, the ext and the prefix record (rajni_hip_query.h): host-side integer tests, every refusal
+// names its field
+int check_query(const rajni_vit_plan& p, const rajni_vit_ext* e, const rajni_vit_query& q) {
+  const char* who = "rajni_vit_forward_query";
+  RAJNI_REQUIRE(q.class_token == 0 || q.class_token == 1, RAJNI_ERR_INVALID, "%s: query.class_token must be 0 or 1 (%d)", who, q.class_token);
+  RAJNI_REQUIRE(q.query == RAJNI_QUERY_CLS || q.query == RAJNI_QUERY_MEAN, RAJNI_ERR_INVALID,
+                "%s: query.query must be RAJNI_QUERY_CLS or RAJNI_QUERY_MEAN (%d)", who, q.query);
+  if (q.class_token) return RAJNI_OK;
+  RAJNI_REQUIRE(q.query == RAJNI_QUERY_MEAN, RAJNI_ERR_INVALID,
+                "%s: query.query must be RAJNI_QUERY_MEAN with query.class_token = 0 - there is no class row to be the query", who);
+  RAJNI_REQUIRE(!p.cls_only_last_block, RAJNI_ERR_INVALID,
+                "%s: plan.cls_only_last_block with query.class_token = 0 - there is no class row to form", who);
+  RAJNI_REQUIRE(e != nullptr && (e->pool == RAJNI_POOL_AVG || pool_is_tokens(e)), RAJNI_ERR_INVALID,
+                "%s: ext.pool must be RAJNI_POOL_AVG or a token output with query.class_token = 0 - a token head has no row to "
+                "read (%s)", who, e ? "RAJNI_POOL_TOKEN" : "ext is NULL");
+  RAJNI_REQUIRE(!p.act_fp8, RAJNI_ERR_UNSUPPORTED, "%s: plan.act_fp8 is unsupported with query.class_token = 0", who);
   return RAJNI_OK;
 }
 
@@ -415,7 +456,7 @@ int check_layers(const rajni_vit_plan& p, const rajni_vit_ext* e, int P, const r
 }
 
 // the image record against the plan (rajni_hip_image.h): host-side integer tests, in front of every other refusal
-int check_image(const rajni_vit_plan& p, const rajni_vit_prefix* pre, const rajni_vit_image& im) {
+int check_image(const rajni_vit_plan& p, const rajni_vit_prefix* pre, const rajni_vit_image& im, const rajni_vit_query* qry = nullptr) {
   const char* who = "rajni_vit_forward_image";
   RAJNI_REQUIRE(p.patch_size > 0, RAJNI_ERR_INVALID, "%s: bad plan (patch_size %d)", who, p.patch_size);
   RAJNI_REQUIRE(im.height > 0 && im.width > 0 && im.height % p.patch_size == 0 && im.width % p.patch_size == 0, RAJNI_ERR_INVALID,
@@ -423,10 +464,10 @@ int check_image(const rajni_vit_plan& p, const rajni_vit_prefix* pre, const rajn
                 im.height, im.width);
   RAJNI_REQUIRE(p.img_size == im.height, RAJNI_ERR_INVALID, "%s: plan.img_size must equal image.height (%d != %d)", who, p.img_size,
                 im.height);
-  const long long n0 = (long long)(im.height / p.patch_size) * (im.width / p.patch_size) + prefix_count(pre);
+  const long long n0 = (long long)(im.height / p.patch_size) * (im.width / p.patch_size) + prefix_count(pre, qry);
   RAJNI_REQUIRE(n0 <= RAJNI_IMAGE_MAX_TOKENS, RAJNI_ERR_UNSUPPORTED,
                 "%s: N=%lld is beyond the tiled path's cap of %d tokens (%d x %d patches and %d prefix tokens)", who, n0,
-                RAJNI_IMAGE_MAX_TOKENS, im.height / p.patch_size, im.width / p.patch_size, prefix_count(pre));
+                RAJNI_IMAGE_MAX_TOKENS, im.height / p.patch_size, im.width / p.patch_size, prefix_count(pre, qry));
   return RAJNI_OK;
 }
 
@@ -448,7 +489,8 @@ int launch_source_idx_before(const rajni_vit_plan& p, int P, int upto, int32_t* 
 // the whole forward; ext == nullptr (rajni_vit_forward) and an all-zero record enqueue the same launches, and so does
 // pre == nullptr (or a record with one prefix token) next to any ext
 int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre, const void* images,
-                void* logits, hipStream_t s, const rajni_vit_layers* lay = nullptr, const rajni_vit_image* img = nullptr);
+                void* logits, hipStream_t s, const rajni_vit_layers* lay = nullptr, const rajni_vit_image* img = nullptr,
+                const rajni_vit_query* qry = nullptr);
 
 }  // namespace
 
@@ -505,6 +547,32 @@ extern "C" int rajni_vit_forward_image(const rajni_vit_plan* plan, const rajni_v
   return vit_forward(plan, ext, prefix, images, logits, (hipStream_t)stream, layers, image);
 }
 
+// ---- include/rajni_hip_query.h
+extern "C" size_t rajni_vit_workspace_bytes_query(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix, const rajni_vit_image* image,
+                                                  const rajni_vit_query* query) {
+  if (!query || (query->class_token == 1 && query->query == RAJNI_QUERY_CLS)) return rajni_vit_workspace_bytes_image(plan, prefix, image);
+  if (!plan || plan->patch_size <= 0) return 0;
+  if ((query->class_token != 0 && query->class_token != 1) || (query->query != RAJNI_QUERY_CLS && query->query != RAJNI_QUERY_MEAN) ||
+      (query->class_token == 0 && query->query != RAJNI_QUERY_MEAN))
+    return 0;
+  const bool nocls = no_class_row(query);
+  if (check_prefix(prefix, "rajni_vit_workspace_bytes_query", nocls) != RAJNI_OK) return 0;
+  if (image && check_image(*plan, prefix, *image, query) != RAJNI_OK) return 0;
+  rajni_vit_plan tmp = *plan;
+  tmp.workspace = nullptr;
+  return carve(tmp, prefix_count(prefix, query), nocls ? 1 : head_row_count(prefix), image, query->query).total;
+}
+
+extern "C" int rajni_vit_forward_query(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
+                                       const rajni_vit_layers* layers, const rajni_vit_image* image, const rajni_vit_query* query,
+                                       const void* images, void* logits, rajni_stream_t stream) {
+  if (!query || (query->class_token == 1 && query->query == RAJNI_QUERY_CLS))
+    return rajni_vit_forward_image(plan, ext, prefix, layers, image, images, logits, stream);
+  const int rc = check_prefix(prefix, "rajni_vit_forward_query", no_class_row(query));
+  if (rc != RAJNI_OK) return rc;
+  return vit_forward(plan, ext, prefix, images, logits, (hipStream_t)stream, layers, image, query);
+}
+
 extern "C" void rajni_debug_set_last_block_all_rows(int on) { g_last_block_all_rows = on; }
 
 // 1 when the forward of this plan (with this ext / prefix record, either may be NULL) computes its last block for the rows the
@@ -519,17 +587,21 @@ extern "C" int rajni_debug_last_block_cls_rows(const rajni_vit_plan* plan, const
 namespace {
 
 int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre, const void* images,
-                void* logits, hipStream_t s, const rajni_vit_layers* lay, const rajni_vit_image* img) {
+                void* logits, hipStream_t s, const rajni_vit_layers* lay, const rajni_vit_image* img, const rajni_vit_query* qry) {
   RAJNI_REQUIRE(plan && images && logits, RAJNI_ERR_INVALID, "rajni_vit_forward: null pointer");
   const rajni_vit_plan& p = *plan;
   const bool dense_last = ext != nullptr && ext->pool == RAJNI_POOL_DENSE_LAST;
-  int rc = img ? check_image(p, pre, *img) : RAJNI_OK;   // first: every count below is against the record's grid
+  int rc = qry ? check_query(p, ext, *qry) : RAJNI_OK;   // first of all: whether there is a class row decides every count
   if (rc != RAJNI_OK) return rc;
-  rc = lay ? check_layers(p, ext, prefix_count(pre), *lay, img) : RAJNI_OK;
+  const bool nocls = no_class_row(qry);
+  const int qmode = query_mode(qry);
+  rc = img ? check_image(p, pre, *img, qry) : RAJNI_OK;   // every count below is against the record's grid
   if (rc != RAJNI_OK) return rc;
-  rc = dense_last ? check_dense_last(p, pre) : RAJNI_OK;
+  rc = lay ? check_layers(p, ext, prefix_count(pre, qry), *lay, img) : RAJNI_OK;
   if (rc != RAJNI_OK) return rc;
-  rc = check_plan(p, ext != nullptr && ext->norm_absent != 0);
+  rc = dense_last ? check_dense_last(p, nocls ? nullptr : pre) : RAJNI_OK;
+  if (rc != RAJNI_OK) return rc;
+  rc = check_plan(p, ext != nullptr && ext->norm_absent != 0, nocls);
   if (rc != RAJNI_OK) return rc;
   rc = check_placement(p, images, logits);
   if (rc != RAJNI_OK) return rc;
@@ -538,14 +610,14 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
     rc = check_ext(p, *ext);
     if (rc != RAJNI_OK) return rc;
   }
-  rc = check_head_rows(p, ext, pre);
+  rc = nocls ? RAJNI_OK : check_head_rows(p, ext, pre);
   if (rc != RAJNI_OK) return rc;
   const rajni_qk_affine* qkn = ext ? ext->qk_norm : nullptr;
-  const int P = prefix_count(pre);   // prefix tokens: CLS + registers (or the dist token), never pruned
-  const int HR = head_row_count(pre);   // rows of each image the head reads
+  const int P = prefix_count(pre, qry);   // prefix tokens: CLS + registers (or the dist token), never pruned; the registers alone without a class row
+  const int HR = nocls ? 1 : head_row_count(pre);   // rows of each image the head reads
   rc = check_schedule(p, P, img);
   if (rc != RAJNI_OK) return rc;
-  const Workspace w = carve(p, P, HR, img);
+  const Workspace w = carve(p, P, HR, img, qmode);
   RAJNI_REQUIRE(p.workspace != nullptr && p.workspace_bytes >= w.total, RAJNI_ERR_INVALID,
                 "rajni_vit_forward: workspace too small (%zu < %zu)", p.workspace_bytes, w.total);
   const int B = p.B, C = p.C, dt = p.dtype;
@@ -556,7 +628,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
 
   rc = launch_patch_embed(images, p.patch_w, p.patch_b, p.cls_token, p.pos_embed, p.pos_has_cls,
                           w.xa, f.sf32, B, p.in_chans, image_height(p, img), image_width(p, img), p.patch_size, C, dt, w.cols, w.cols_bytes, s,
-                          P, P > 1 ? pre->reg_token : nullptr);
+                          P, nocls ? (P > 0 ? pre->reg_token : nullptr) : (P > 1 ? pre->reg_token : nullptr), nocls ? 0 : 1);
   if (rc != RAJNI_OK) return rc;
   if (ext && ext->norm_pre_w) {   // timm forward_features: x = norm_pre(x), written back into the stream
     rc = launch_layernorm_stream(w.xa, ext->norm_pre_w, ext->norm_pre_b, B * N, C, ext->norm_pre_eps, f.sf32, dt, s);
@@ -606,7 +678,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
       cur = oth; N = 1;
       break;
     }
-    if (HR == 2 && last_block_cls_rows(p, ext, i, N, last_captured)) {
+    if (HR == 2 && last_block_cls_rows(p, ext, i, N, last_captured, nocls)) {
       // the distilled head reads rows 0 and 1: the first query tile (into w.xn, which QKV has consumed), its rows 0 and 1
       // gathered dense into w.att, and the ordinary tail as a pruned block that keeps {0, 1} - the proj epilogue gathers
       // the two residual rows through idx01 and the stream leaves [B, 2, C] in `oth`
@@ -621,7 +693,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
         cur = oth; N = 2;
         break;
       }
-    } else if (last_block_cls_rows(p, ext, i, N, last_captured)) {
+    } else if (last_block_cls_rows(p, ext, i, N, last_captured, nocls)) {
       // the all-rows kernels on the rows the head reads: the first query tile, proj on its CLS rows in place (stride N * C)
       const Tail t = tail_args(f, blk, AttnRows{B, cls_ld, nullptr, cls_ld, nullptr, 0, 0}, cur, oth);
       if (tail_ok(t)) {   // (a refused shape or stride: all rows below, as if this branch were not here)
@@ -642,7 +714,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
         const void* full = carried;
         if (recompute) {
           void* dst = blk.scores ? blk.scores : (void*)w.scf;
-          rc = launch_score_select(w.qkv, nullptr, B, N, p.H, p.D, 1e-6f, 0, dst, nullptr, nullptr, dt, s, 1, w.sst, w.sst_bytes);
+          rc = launch_score_select(w.qkv, nullptr, B, N, p.H, p.D, 1e-6f, 0, dst, nullptr, nullptr, dt, s, nocls ? P : 1, w.sst, w.sst_bytes, qmode);
           if (rc != RAJNI_OK) return rc;
           full = dst;
         }
@@ -658,7 +730,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
       } else {
         if (recompute)
           rc = launch_score_select(w.qkv, nullptr, B, N, p.H, p.D, 1e-6f, blk.keep, blk.scores,
-                                   blk.keep_idx, blk.next_scores, dt, s, P, w.sst, w.sst_bytes);
+                                   blk.keep_idx, blk.next_scores, dt, s, P, w.sst, w.sst_bytes, qmode);
         else
           rc = launch_score_select(nullptr, carried, B, N, 0, 0, 0.f, blk.keep, nullptr,
                                    blk.keep_idx, blk.next_scores, dt, s, P);

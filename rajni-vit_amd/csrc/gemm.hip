@@ -1916,13 +1916,23 @@ static void with_stream_types(int dtype, int out_f32, F&& f) {
 }
 int launch_patch_embed(const void* images, const void* w, const float* bias, const void* cls,
                        const void* pos, int pos_has_cls, void* x, int out_f32, int B, int Cin, int H, int W,
-                       int P, int C, int dtype, void* ws, size_t ws_bytes, hipStream_t s, int num_prefix, const void* reg) {
-  RAJNI_REQUIRE(images && w && cls && pos && x, RAJNI_ERR_INVALID, "rajni_patch_embed: null pointer");
-  RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
-                "rajni_patch_embed: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
-  RAJNI_REQUIRE(num_prefix == 1 || reg != nullptr, RAJNI_ERR_INVALID, "rajni_patch_embed: %d prefix tokens but reg_token is null", num_prefix);
-  RAJNI_REQUIRE(num_prefix == 1 || ((uintptr_t)cls % 16 == 0 && (uintptr_t)reg % 16 == 0 && (uintptr_t)pos % 16 == 0),
-                RAJNI_ERR_INVALID, "rajni_patch_embed: cls, reg_token and pos must be 16-byte aligned");
+                       int P, int C, int dtype, void* ws, size_t ws_bytes, hipStream_t s, int num_prefix, const void* reg, int has_cls) {
+  if (has_cls) {
+    RAJNI_REQUIRE(images && w && cls && pos && x, RAJNI_ERR_INVALID, "rajni_patch_embed: null pointer");
+    RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
+                  "rajni_patch_embed: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
+    RAJNI_REQUIRE(num_prefix == 1 || reg != nullptr, RAJNI_ERR_INVALID, "rajni_patch_embed: %d prefix tokens but reg_token is null", num_prefix);
+    RAJNI_REQUIRE(num_prefix == 1 || ((uintptr_t)cls % 16 == 0 && (uintptr_t)reg % 16 == 0 && (uintptr_t)pos % 16 == 0),
+                  RAJNI_ERR_INVALID, "rajni_patch_embed: cls, reg_token and pos must be 16-byte aligned");
+  } else {   // no class row: the prefix rows are the num_prefix registers, possibly none
+    RAJNI_REQUIRE(images && w && pos && x, RAJNI_ERR_INVALID, "rajni_patch_embed: null pointer");
+    RAJNI_REQUIRE(num_prefix >= 0 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
+                  "rajni_patch_embed: without a class row num_prefix (the register count) must be 0..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
+    RAJNI_REQUIRE((num_prefix > 0) == (reg != nullptr), RAJNI_ERR_INVALID,
+                  "rajni_patch_embed: %d register tokens but reg_token is %s", num_prefix, reg ? "given" : "null");
+    RAJNI_REQUIRE((uintptr_t)reg % 16 == 0 && (uintptr_t)pos % 16 == 0, RAJNI_ERR_INVALID,
+                  "rajni_patch_embed: reg_token and pos must be 16-byte aligned");
+  }
   if (H == W)   // (the square entry points: their wording)
     RAJNI_REQUIRE(P >= 1 && W % P == 0 && B > 0 && Cin > 0, RAJNI_ERR_INVALID,
                   "rajni_patch_embed: the patch size must divide the image (P=%d S=%d)", P, W);
@@ -1975,7 +1985,18 @@ int launch_patch_embed(const void* images, const void* w, const float* bias, con
   ProfScope prof(KC_CLS_POS, s, 0.0, 6.0 * B * num_prefix * C);
   const long stride = (long)(npatch + num_prefix) * C;
   const dim3 block(256);
-  if (num_prefix > 1) {
+  if (!has_cls) {
+    // the R register rows: prefix_pos_kernel with register 0 in the class row's place and the others behind it (R = 0: no
+    // prefix row, no launch)
+    if (num_prefix == 0) return RAJNI_OK;
+    const dim3 grid((B * num_prefix * (C / 8) + 255) / 256);
+    with_stream_types(dtype, out_f32, [&](auto sf32, auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((prefix_pos_kernel<decltype(sf32)::value, T>), grid, block, 0, s, (const T*)reg, (const T*)reg + C, (const T*)pos,
+                         pos_has_cls, x, stride, B, num_prefix, C);
+    });
+    RAJNI_CHECK_LAUNCH("prefix_pos_kernel");
+  } else if (num_prefix > 1) {
     const dim3 grid((B * num_prefix * (C / 8) + 255) / 256);
     with_stream_types(dtype, out_f32, [&](auto sf32, auto t) {
       using T = decltype(t);

@@ -835,8 +835,8 @@ int launch_layernorm_dense(const void* x, const int32_t* src, const float* w, co
 int launch_layernorm_dropped(const void* x, const int32_t* keep, const int32_t* src, const float* w, const float* b, void* y,
                              int B, int N, int Np, int P, int S, int C, float eps, int x_f32, int dtype, hipStream_t s) {
   RAJNI_REQUIRE(x && keep && src && w && b && y, RAJNI_ERR_INVALID, "layernorm_dropped: null pointer");
-  RAJNI_REQUIRE(B > 0 && P > 0 && P < Np && Np <= N && N <= S && C > 0 && C % 8 == 0 && C <= 64 * 8 * LN_MAX_CHUNKS,
-                RAJNI_ERR_UNSUPPORTED, "layernorm_dropped: need C %% 8 == 0, C <= 2048 and 0 < P < Np <= N <= S (C=%d P=%d Np=%d N=%d S=%d)",
+  RAJNI_REQUIRE(B > 0 && P >= 0 && P < Np && Np <= N && N <= S && C > 0 && C % 8 == 0 && C <= 64 * 8 * LN_MAX_CHUNKS,
+                RAJNI_ERR_UNSUPPORTED, "layernorm_dropped: need C %% 8 == 0, C <= 2048 and 0 <= P < Np <= N <= S (C=%d P=%d Np=%d N=%d S=%d)",
                 C, P, Np, N, S);
   const long rows = (long)B * (N - P), dropped = (long)B * (N - Np);
   RAJNI_REQUIRE((rows + 3) / 4 < (1L << 31), RAJNI_ERR_UNSUPPORTED, "layernorm_dropped: too many rows (%ld)", rows);
@@ -897,8 +897,8 @@ int launch_rows_dropped_multi(const void* x, const int32_t* keep, const int32_t*
                               int dtype, hipStream_t s) {
   RAJNI_REQUIRE(x && keep && src && ys && (!norm || (w && b)), RAJNI_ERR_INVALID, "rows_dropped_multi: null pointer");
   RAJNI_REQUIRE(ny >= 1 && ny <= RAJNI_MAX_LAYERS, RAJNI_ERR_INVALID, "rows_dropped_multi: 1..%d outputs (%d)", RAJNI_MAX_LAYERS, ny);
-  RAJNI_REQUIRE(B > 0 && P > 0 && P < Np && Np <= N && N <= S && C > 0 && C % 8 == 0 && C <= 64 * 8 * LN_MAX_CHUNKS,
-                RAJNI_ERR_UNSUPPORTED, "rows_dropped_multi: need C %% 8 == 0, C <= 2048 and 0 < P < Np <= N <= S (C=%d P=%d Np=%d N=%d S=%d)",
+  RAJNI_REQUIRE(B > 0 && P >= 0 && P < Np && Np <= N && N <= S && C > 0 && C % 8 == 0 && C <= 64 * 8 * LN_MAX_CHUNKS,
+                RAJNI_ERR_UNSUPPORTED, "rows_dropped_multi: need C %% 8 == 0, C <= 2048 and 0 <= P < Np <= N <= S (C=%d P=%d Np=%d N=%d S=%d)",
                 C, P, Np, N, S);
   const long rows = (long)B * (N - P), dropped = (long)B * (N - Np);
   RAJNI_REQUIRE((rows + 3) / 4 < (1L << 31), RAJNI_ERR_UNSUPPORTED, "rows_dropped_multi: too many rows (%ld)", rows);

@@ -37,7 +37,7 @@ struct ScoreArgs {          // T = activation dtype (bf16_t, f16_t or float)
   int N, H, D;
   float eps;
   int keep;                 // 0: scores only
-  int P;                    // prefix tokens (CLS + registers): rows 0..P-1 are always kept and never ranked
+  int P;                    // prefix tokens (CLS + registers; registers alone, possibly none, without a class row): rows 0..P-1 are always kept and never ranked
   void* scores_out;         // T [B,N] or null
   int* keep_idx;            // [B,P+keep]
   void* next_scores;        // T [B,P+keep] or null
@@ -63,11 +63,20 @@ __host__ __device__ inline int ss_key_words(int N, int P) {
   const int chunks = (N + 3) >> 2, cps = (chunks + tpt - 1) / tpt;
   return (cps | 1) * tpt * 4;
 }
-__host__ __device__ inline int ss_region_words(int N, int H, int D, int P, bool merged) {
+// The mean query (RAJNI_QUERY_MEAN, rajni_hip_query.h): row partitions of the column sums of the Q third.  Partition q sums
+// rows q, q + QP, ... in row order and the QP partial sums join in partition order: a fixed order that hangs on C alone.
+__host__ __device__ inline int ss_qparts(int C) {
+  const int cp = C >> 3, a = cp > 0 && cp <= SS_THREADS ? SS_THREADS / cp : 1;
+  return a < 16 ? a : 16;
+}
+// (qmean: the partial sums [QP][C] of the mean query live in the region before the logits do)
+__host__ __device__ inline int ss_region_words(int N, int H, int D, int P, bool merged, bool qmean = false) {
   const int lg = (H * N + 3) & ~3;
-  const int r = merged ? lg + N * D : (((H * N > N * D) ? H * N : N * D) + 3) & ~3;
+  int r = merged ? lg + N * D : (((H * N > N * D) ? H * N : N * D) + 3) & ~3;
   const int kw = ss_key_words(N, P);
-  return r > kw ? r : kw;
+  r = r > kw ? r : kw;
+  const int qw = qmean ? ss_qparts(H * D) * H * D : 0;
+  return r > qw ? r : qw;
 }
 
 // sum over an aligned group of `width` (4, 8 or 16) consecutive lanes, every lane gets the total; DPP adds in
@@ -204,15 +213,17 @@ __device__ __forceinline__ void select_tail(const ScoreArgs& a, int b, float* sc
 // MERGED: logits and vbar have LDS regions of their own and K and V rows are read in ONE pass (a token's K and V
 // thirds are 3072 contiguous bytes of its 4608-byte qkv row, and no V load has to wait for the softmax statistics);
 // otherwise (N = 577 with 16 heads: 185 KiB would be needed) vbar reuses the logits' region after the statistics.
-template <bool COMPUTE, typename T, bool MERGED>
+// QMEAN: the importance query is the mean of the N query rows (RAJNI_QUERY_MEAN) instead of row 0; everything behind the
+// fill of `qcls` is the same code.
+template <bool COMPUTE, typename T, bool MERGED, bool QMEAN = false>
 __global__ void __launch_bounds__(SS_THREADS) score_select_kernel(const ScoreArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int b = blockIdx.x;
   const int N = a.N, H = a.H, D = a.D, C = H * D;
   const int lg_sz = (H * N + 3) & ~3;
-  const int region_sz = ss_region_words(N, H, D, a.P, MERGED);
-  float* qcls = sm;                    // [C]
+  const int region_sz = ss_region_words(N, H, D, a.P, MERGED, QMEAN);
+  float* qcls = sm;                    // [C]: the query, row 0 or the mean row
   float* region = qcls + C;            // logits [H][N]  (then / followed by)  vbar [N][D]
   float* vbar = MERGED ? region + lg_sz : region;
   float* acls = region + region_sz;    // [N]
@@ -233,14 +244,48 @@ __global__ void __launch_bounds__(SS_THREADS) score_select_kernel(const ScoreArg
     const int sub = tid % LP;
     const int grp = tid / LP, ngrp = SS_THREADS / LP;   // threads past ngrp * LP sit the head-row passes out
 
-    // ---- CLS query row -> LDS (importance.py:18)
-    for (int c = tid; c < (C >> 3); c += SS_THREADS) {
-      float f[8];
-      load8<T>(base + c * 8, f);
+    if constexpr (QMEAN) {
+      // ---- mean query row -> LDS: qcls[c] = (1 / N) sum_n q[n, c], fp32.  Item (partition q, 16-byte chunk c) sums rows
+      //      q, q + QP, ... in row order (four loads in flight, added in order) into region[q][c]; then column c joins its QP
+      //      partial sums in partition order.  No atomics: the same bits on every run and in both LDS layouts.
+      const int CPQ = C >> 3, QP = ss_qparts(C);
+      for (int item = tid; item < QP * CPQ; item += SS_THREADS) {
+        const int q = item / CPQ, c = item - q * CPQ;
+        const T* qp = base + c * 8;
+        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int n = q; n < N; n += 4 * QP) {
+          float f[4][8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) qcls[c * 8 + j] = f[j];
+          for (int u = 0; u < 4; ++u)
+            if (n + u * QP < N) load8<T>(qp + (long)(n + u * QP) * 3 * C, f[u]);
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (n + u * QP < N) {
+#pragma unroll
+              for (int j = 0; j < 8; ++j) acc[j] += f[u][j];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) region[q * C + c * 8 + j] = acc[j];
+      }
+      __syncthreads();
+      const float inv_n = 1.0f / (float)N;
+      for (int c = tid; c < C; c += SS_THREADS) {
+        float t = 0.f;
+        for (int q = 0; q < QP; ++q) t += region[q * C + c];
+        qcls[c] = t * inv_n;
+      }
+      __syncthreads();   // the partial sums are dead: the region takes the logits
+    } else {
+      // ---- CLS query row -> LDS (importance.py:18)
+      for (int c = tid; c < (C >> 3); c += SS_THREADS) {
+        float f[8];
+        load8<T>(base + c * 8, f);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qcls[c * 8 + j] = f[j];
+      }
+      __syncthreads();
     }
-    __syncthreads();
 
     // ---- logits[h][n] = q_cls[h] . k[n,h] / sqrt(D)   (importance.py:19)
     // Work item = one 16-byte chunk c of K row n (C/8 chunks per row, lane-contiguous -> coalesced); the LP
@@ -501,9 +546,9 @@ __global__ void __launch_bounds__(SS_THREADS) score_select_kernel(const ScoreArg
   select_tail<T>(a, b, sc, acls, reinterpret_cast<unsigned*>(region), wcount);
 }
 
-size_t ss_lds_bytes(int N, int H, int D, int P, bool merged) {
+size_t ss_lds_bytes(int N, int H, int D, int P, bool merged, bool qmean = false) {
   const size_t C = (size_t)H * D;
-  const size_t region = (size_t)ss_region_words(N, H, D, P, merged);
+  const size_t region = (size_t)ss_region_words(N, H, D, P, merged, qmean);
   return (C + region + 2 * (size_t)N + 2 * (size_t)H + SS_PART + D + 16 + SS_THREADS / 64) * sizeof(float);
 }
 
@@ -530,7 +575,46 @@ struct TiledArgs {
   float* vbar;      // [B][N][D]
   float* colsum;    // [B][tiles][D]
   float* stats;     // [B][tiles][H][2]: max, sum of exp(l - max) over the tile's tokens
+  float* qbar;      // [B][C] the mean query (score_qmean_kernel wrote it), or null: the query is row 0
 };
+
+// RAJNI_QUERY_MEAN on the tiled path: qbar[b][c] = (1 / N) sum_n q[b, n, c], fp32, before the tiles launch.  A workgroup owns
+// SQ_COLS consecutive columns of one image: thread (partition q, 16-byte chunk c) sums rows q, q + SQ_PARTS, ... in row order
+// (four loads in flight, added in order), the partial sums meet in LDS and column c joins them in partition order.  The order
+// hangs on nothing but N: bit-repeatable, the same bits at any batch size and position.
+constexpr int SQ_COLS = 64, SQ_PARTS = 32, SQ_THREADS = (SQ_COLS / 8) * SQ_PARTS;
+template <typename T>
+__global__ void __launch_bounds__(SQ_THREADS) score_qmean_kernel(const T* __restrict__ qkv, float* __restrict__ qbar, int N, int C) {
+  __shared__ float part[SQ_PARTS][SQ_COLS];
+  const int tid = threadIdx.x, b = blockIdx.y;
+  const int q = tid / (SQ_COLS / 8), cl = tid - q * (SQ_COLS / 8);
+  const int c0 = blockIdx.x * SQ_COLS + cl * 8;      // first of this thread's 8 columns
+  const T* qp = qkv + (size_t)b * N * 3 * C + c0;
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (c0 < C) {
+    for (int n = q; n < N; n += 4 * SQ_PARTS) {
+      float f[4][8];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (n + u * SQ_PARTS < N) load8<T>(qp + (size_t)(n + u * SQ_PARTS) * 3 * C, f[u]);
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (n + u * SQ_PARTS < N) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) acc[j] += f[u][j];
+        }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) part[q][cl * 8 + j] = acc[j];
+  __syncthreads();
+  const int c = blockIdx.x * SQ_COLS + tid;
+  if (tid < SQ_COLS && c < C) {
+    float t = 0.f;
+    for (int r = 0; r < SQ_PARTS; ++r) t += part[r][tid];
+    qbar[(size_t)b * C + c] = t * (1.0f / (float)N);
+  }
+}
 
 template <typename T>
 __global__ void __launch_bounds__(ST_THREADS) score_tile_kernel(const ScoreArgs a, const TiledArgs t) {
@@ -548,11 +632,15 @@ __global__ void __launch_bounds__(ST_THREADS) score_tile_kernel(const ScoreArgs 
   const bool pow2 = LP == 4 || LP == 8 || LP == 16;     // as in score_select_kernel: DPP group sums, else the plain forms
   const int sub = tid % LP, grp = tid / LP, ngrp = ST_THREADS / LP;
 
-  for (int c = tid; c < (C >> 3); c += ST_THREADS) {
-    float f[8];
-    load8<T>(base + c * 8, f);
+  if (t.qbar != nullptr) {   // the mean query (workgroup-uniform)
+    for (int c = tid; c < C; c += ST_THREADS) qcls[c] = t.qbar[(size_t)b * C + c];
+  } else {
+    for (int c = tid; c < (C >> 3); c += ST_THREADS) {
+      float f[8];
+      load8<T>(base + c * 8, f);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) qcls[c * 8 + j] = f[j];
+      for (int j = 0; j < 8; ++j) qcls[c * 8 + j] = f[j];
+    }
   }
   __syncthreads();
 
@@ -780,8 +868,9 @@ size_t st_finish_lds_bytes(int N, int H, int D, int P) {
   return ((kw > n4 ? kw : n4) + (size_t)N + 2 * (size_t)H + SS_THREADS + D + 16 + SS_THREADS / 64) * sizeof(float);
 }
 inline size_t st_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-struct TiledLayout { int tiles; size_t logits, vbar, colsum, stats, total; };   // byte offsets of the scratch regions
-TiledLayout st_layout(int B, int N, int H, int D) {
+struct TiledLayout { int tiles; size_t logits, vbar, colsum, stats, qbar, total; };   // byte offsets of the scratch regions
+// (qmean: the mean query [B][C] behind everything else, so that no other offset moves)
+TiledLayout st_layout(int B, int N, int H, int D, bool qmean = false) {
   TiledLayout l{};
   l.tiles = (N + ST_TILE - 1) / ST_TILE;
   size_t off = 0;
@@ -790,6 +879,7 @@ TiledLayout st_layout(int B, int N, int H, int D) {
   l.vbar = take((size_t)B * N * D);
   l.colsum = take((size_t)B * l.tiles * D);
   l.stats = take((size_t)B * l.tiles * H * 2);
+  l.qbar = qmean ? take((size_t)B * H * D) : 0;
   l.total = off;
   return l;
 }
@@ -798,7 +888,7 @@ int g_ss_force_tiled = 0;      // test hook: 1 = the tiled path wherever scratch
 
 inline bool ss_shape_ok(int B, int N, int H, int D) { return B > 0 && N >= 2 && H > 0 && D >= 8 && D <= 128 && D % 8 == 0; }
 // the single-workgroup layout cannot hold the shape (P = 1: the prefix count only matters for a handful of tokens)
-inline bool ss_needs_tiles(int N, int H, int D) { return ss_lds_bytes(N, H, D, 1, false) > 160 * 1024; }
+inline bool ss_needs_tiles(int N, int H, int D, bool qmean = false) { return ss_lds_bytes(N, H, D, 1, false, qmean) > 160 * 1024; }
 
 int g_ss_force_two_pass = 0;   // test hook (rajni_hip_debug.h): 1 = the two-pass layout even when the merged one fits
 
@@ -814,9 +904,18 @@ extern "C" size_t rajni_score_select_workspace_bytes(int B, int N, int H, int D,
   return st_layout(B, N, H, D).total;
 }
 
+// Scratch bytes rajni_score_select_query needs (rajni_hip_query.h): with RAJNI_QUERY_CLS what rajni_score_select_workspace_bytes
+// returns; the mean query adds its [B][C] fp32 row behind that layout wherever the tiled path runs
+extern "C" size_t rajni_score_select_query_workspace_bytes(int B, int N, int H, int D, int dtype, int query) {
+  if (query != RAJNI_QUERY_MEAN) return query == RAJNI_QUERY_CLS ? rajni_score_select_workspace_bytes(B, N, H, D, dtype) : 0;
+  if (!(dtype == RAJNI_BF16 || dtype == RAJNI_F32 || dtype == RAJNI_F16) || !ss_shape_ok(B, N, H, D) || N > ST_MAX_N) return 0;
+  if (!ss_needs_tiles(N, H, D, true) && g_ss_force_tiled == 0) return 0;
+  return st_layout(B, N, H, D, true).total;
+}
+
 namespace {
-// the tiled path: tile kernel + finish kernel, nothing else on the stream
-int launch_score_tiled(ScoreArgs a, int B, int dtype, void* ws, size_t ws_bytes, hipStream_t s) {
+// the tiled path: (the mean query's launch,) tile kernel + finish kernel, nothing else on the stream
+int launch_score_tiled(ScoreArgs a, int B, int dtype, void* ws, size_t ws_bytes, hipStream_t s, bool qmean) {
   const int N = a.N, H = a.H, D = a.D;
   RAJNI_REQUIRE(B <= RAJNI_MAX_GRID_YZ, RAJNI_ERR_UNSUPPORTED,
                 "score/select: B=%d - one launch of the tiled path takes at most %d images (grid: token tiles x images)", B,
@@ -828,15 +927,17 @@ int launch_score_tiled(ScoreArgs a, int B, int dtype, void* ws, size_t ws_bytes,
   RAJNI_REQUIRE(tl <= 64 * 1024 && fl <= 160 * 1024, RAJNI_ERR_UNSUPPORTED,
                 "score/select: N=%d H=%d D=%d needs %zu B (tile) / %zu B (finish) of LDS (caps: 64 KiB, 160 KiB; N <= %d)",
                 N, H, D, tl, fl, ST_MAX_N);
-  const TiledLayout l = st_layout(B, N, H, D);
+  const TiledLayout l = st_layout(B, N, H, D, qmean);
   RAJNI_REQUIRE(ws != nullptr && ws_bytes >= l.total, RAJNI_ERR_INVALID,
-                "score/select: the tiled path needs %zu B of scratch (rajni_score_select_workspace_bytes), got %zu", l.total, ws_bytes);
+                "score/select: the tiled path needs %zu B of scratch (%s), got %zu", l.total,
+                qmean ? "rajni_score_select_query_workspace_bytes" : "rajni_score_select_workspace_bytes", ws_bytes);
   RAJNI_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, RAJNI_ERR_INVALID, "score/select: scratch must be 256-byte aligned");
   char* base = static_cast<char*>(ws);
   TiledArgs t{};
   t.tiles = l.tiles;
   t.logits = reinterpret_cast<float*>(base + l.logits); t.vbar = reinterpret_cast<float*>(base + l.vbar);
   t.colsum = reinterpret_cast<float*>(base + l.colsum); t.stats = reinterpret_cast<float*>(base + l.stats);
+  t.qbar = qmean ? reinterpret_cast<float*>(base + l.qbar) : nullptr;
   typedef void (*kern_t)(const ScoreArgs, const TiledArgs);
   const kern_t tile = dtype == RAJNI_F16 ? &score_tile_kernel<f16_t> : dtype == RAJNI_F32 ? &score_tile_kernel<float> : &score_tile_kernel<bf16_t>;
   const kern_t fin = dtype == RAJNI_F16 ? &score_finish_kernel<f16_t> : dtype == RAJNI_F32 ? &score_finish_kernel<float> : &score_finish_kernel<bf16_t>;
@@ -847,10 +948,19 @@ int launch_score_tiled(ScoreArgs a, int B, int dtype, void* ws, size_t ws_bytes,
       return RAJNI_ERR_LAUNCH;
     }
   }
-  // algorithmic bytes: the K and V thirds and the CLS query row once, the scratch written once and read once, the scores
+  // algorithmic bytes: the K and V thirds and the CLS query row (mean query: the Q third) once, the scratch written once and
+  // read once, the scores
   const double es = dtype == RAJNI_F32 ? 4.0 : 2.0;
-  const double bytes = (2.0 * N * H * D + H * D) * es * B + 2.0 * (double)l.total + 4.0 * N * B;
+  const double bytes = ((qmean ? 3.0 : 2.0) * N * H * D + (qmean ? 0 : H * D)) * es * B + 2.0 * (double)l.total + 4.0 * N * B;
   ProfScope prof(a.keep > 0 ? KC_SCORE_SELECT : KC_IMPORTANCE, s, 0.0, bytes);
+  if (qmean) {
+    const int C = H * D;
+    const dim3 grid((C + SQ_COLS - 1) / SQ_COLS, B), block(SQ_THREADS);
+    if (dtype == RAJNI_F32) hipLaunchKernelGGL(score_qmean_kernel<float>, grid, block, 0, s, (const float*)a.qkv, t.qbar, N, C);
+    else if (dtype == RAJNI_F16) hipLaunchKernelGGL(score_qmean_kernel<f16_t>, grid, block, 0, s, (const f16_t*)a.qkv, t.qbar, N, C);
+    else hipLaunchKernelGGL(score_qmean_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)a.qkv, t.qbar, N, C);
+    RAJNI_CHECK_LAUNCH("score_qmean_kernel");
+  }
   hipLaunchKernelGGL(tile, dim3(l.tiles, B), dim3(ST_THREADS), tl, s, a, t);
   RAJNI_CHECK_LAUNCH("score_tile_kernel");
   hipLaunchKernelGGL(fin, dim3(B), dim3(SS_THREADS), fl, s, a, t);
@@ -862,10 +972,13 @@ int launch_score_tiled(ScoreArgs a, int B, int dtype, void* ws, size_t ws_bytes,
 // qkv != null: compute scores (and select when keep > 0); qkv == null: select from scores_in.
 int launch_score_select(const void* qkv, const void* scores_in, int B, int N, int H, int D,
                         float eps, int keep, void* scores_out, int32_t* keep_idx,
-                        void* next_scores, int dtype, hipStream_t s, int P, void* ws, size_t ws_bytes) {
+                        void* next_scores, int dtype, hipStream_t s, int P, void* ws, size_t ws_bytes, int query) {
   RAJNI_REQUIRE(dtype == RAJNI_BF16 || dtype == RAJNI_F32 || dtype == RAJNI_F16, RAJNI_ERR_INVALID, "score/select: bad dtype %d", dtype);
-  RAJNI_REQUIRE(P >= 1 && P <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID, "score/select: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, P);
-  RAJNI_REQUIRE(B > 0 && N >= P + 1, RAJNI_ERR_INVALID, "score/select: need B > 0 and N >= %d (B=%d N=%d)", P + 1, B, N);
+  // (P = 0, a sequence without a class row, reaches here from rajni_hip_query.h alone: the other entry points refuse it themselves)
+  RAJNI_REQUIRE(P >= 0 && P <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID, "score/select: num_prefix must be 0..%d (%d)", RAJNI_MAX_PREFIX, P);
+  RAJNI_REQUIRE(query == RAJNI_QUERY_CLS || query == RAJNI_QUERY_MEAN, RAJNI_ERR_INVALID,
+                "score/select: query must be RAJNI_QUERY_CLS or RAJNI_QUERY_MEAN (%d)", query);
+  RAJNI_REQUIRE(B > 0 && N >= P + 1 && N >= 2, RAJNI_ERR_INVALID, "score/select: need B > 0 and N >= %d (B=%d N=%d)", P + 1 > 2 ? P + 1 : 2, B, N);
   RAJNI_REQUIRE(keep >= 0 && keep <= N - P, RAJNI_ERR_INVALID,
                 "score/select: keep=%d out of range for N=%d with %d prefix tokens (keep_ratio must be <= 1)", keep, N, P);
   RAJNI_REQUIRE(keep == 0 || keep_idx != nullptr, RAJNI_ERR_INVALID, "score/select: keep_idx is null");
@@ -875,15 +988,16 @@ int launch_score_select(const void* qkv, const void* scores_in, int B, int N, in
   a.stamps = rajni_g_stamps;
   size_t lds;
   bool merged = false;
+  const bool qmean = qkv != nullptr && query == RAJNI_QUERY_MEAN;
   if (qkv != nullptr) {
     RAJNI_REQUIRE(D >= 8 && D <= 128 && D % 8 == 0, RAJNI_ERR_UNSUPPORTED,
                   "importance: head dim %d not supported (multiples of 8 up to 128)", D);
     RAJNI_REQUIRE(H > 0, RAJNI_ERR_INVALID, "importance: H must be positive");
     a.qkv = qkv; a.H = H; a.D = D;
     // a shape one workgroup holds takes the kernel it always took; scratch serves the others (and any shape under the test hook)
-    if (ws != nullptr && (ss_needs_tiles(N, H, D) || g_ss_force_tiled != 0)) return launch_score_tiled(a, B, dtype, ws, ws_bytes, s);
-    merged = ss_lds_bytes(N, H, D, P, true) <= 160 * 1024 && g_ss_force_two_pass == 0;   // else vbar reuses the logits' region
-    lds = ss_lds_bytes(N, H, D, P, merged);
+    if (ws != nullptr && (ss_needs_tiles(N, H, D, qmean) || g_ss_force_tiled != 0)) return launch_score_tiled(a, B, dtype, ws, ws_bytes, s, qmean);
+    merged = ss_lds_bytes(N, H, D, P, true, qmean) <= 160 * 1024 && g_ss_force_two_pass == 0;   // else vbar reuses the logits' region
+    lds = ss_lds_bytes(N, H, D, P, merged, qmean);
   } else {
     RAJNI_REQUIRE(scores_in != nullptr, RAJNI_ERR_INVALID, "select: scores is null");
     a.scores_in = scores_in; a.H = 1; a.D = 32;
@@ -897,7 +1011,11 @@ int launch_score_select(const void* qkv, const void* scores_in, int B, int N, in
                 qkv != nullptr ? "; rajni_score_select_ws scores such shapes through caller-provided scratch" : "");
   const bool f32 = dtype == RAJNI_F32;
   typedef void (*kern_t)(const ScoreArgs);
-  const kern_t kern = dtype == RAJNI_F16
+  const kern_t kern = qmean
+      ? (dtype == RAJNI_F16 ? (merged ? &score_select_kernel<true, f16_t, true, true> : &score_select_kernel<true, f16_t, false, true>)
+         : f32 ? (merged ? &score_select_kernel<true, float, true, true> : &score_select_kernel<true, float, false, true>)
+               : (merged ? &score_select_kernel<true, bf16_t, true, true> : &score_select_kernel<true, bf16_t, false, true>))
+      : dtype == RAJNI_F16
       ? (qkv ? (merged ? &score_select_kernel<true, f16_t, true> : &score_select_kernel<true, f16_t, false>)
              : &score_select_kernel<false, f16_t, false>)
       : qkv ? (merged ? (f32 ? &score_select_kernel<true, float, true> : &score_select_kernel<true, bf16_t, true>)
@@ -911,7 +1029,7 @@ int launch_score_select(const void* qkv, const void* scores_in, int B, int N, in
     }
   }
   const double es = f32 ? 4.0 : 2.0;
-  const double bytes = qkv ? (2.0 * N * H * D + H * D) * es * B + 4.0 * N * B : 6.0 * N * B;
+  const double bytes = qkv ? ((qmean ? 3.0 : 2.0) * N * H * D + (qmean ? 0 : H * D)) * es * B + 4.0 * N * B : 6.0 * N * B;
   ProfScope prof(qkv ? (keep > 0 ? KC_SCORE_SELECT : KC_IMPORTANCE) : KC_SELECT, s, 0.0, bytes);
   hipLaunchKernelGGL(kern, dim3(B), dim3(SS_THREADS), lds, s, a);
   RAJNI_CHECK_LAUNCH("score_select_kernel");

@@ -306,8 +306,9 @@ int launch_layernorm_stream(void* x, const float* w, const float* b, int rows, i
 int launch_pool_norm(const void* x, int B, int N, int C, int pool, const float* nw, const float* nb, float neps,
                      const float* fw, const float* fb, float feps, void* out, int x_f32, int dtype, hipStream_t s, int num_prefix) {
   RAJNI_REQUIRE(x && out, RAJNI_ERR_INVALID, "rajni_pool_norm: null pointer");
-  RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
-                "rajni_pool_norm: num_prefix must be 1..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
+  // (0: a sequence without a class row, from rajni_hip_query.h's forward alone - rajni_pool_norm_prefix refuses it itself)
+  RAJNI_REQUIRE(num_prefix >= 0 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
+                "rajni_pool_norm: num_prefix must be 0..%d (%d)", RAJNI_MAX_PREFIX, num_prefix);
   RAJNI_REQUIRE(pool == RAJNI_POOL_TOKEN || pool == RAJNI_POOL_AVG, RAJNI_ERR_UNSUPPORTED,
                 "rajni_pool_norm: pool must be RAJNI_POOL_TOKEN or RAJNI_POOL_AVG (%d)", pool);
   RAJNI_REQUIRE(B > 0 && N > 0 && C > 0 && C % 8 == 0 && C <= 64 * 8 * LS_MAX_CHUNKS, RAJNI_ERR_UNSUPPORTED,

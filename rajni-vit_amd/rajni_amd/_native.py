@@ -113,6 +113,12 @@ class VitImage(C.Structure):
     _fields_ = [("height", c_int), ("width", c_int)]
 
 
+class VitQuery(C.Structure):
+    """rajni_vit_query (include/rajni_hip_query.h): whether the sequence has a class row, and the importance query"""
+    _fields_ = [("class_token", c_int), ("query", c_int)]
+
+
+QUERY_CLS, QUERY_MEAN = 0, 1     # RAJNI_QUERY_CLS, RAJNI_QUERY_MEAN
 MAX_LAYERS = 64     # RAJNI_MAX_LAYERS
 MAX_PREFIX = 32     # RAJNI_MAX_PREFIX
 SCORE_TILE_TOKENS = 32      # ST_TILE of csrc/score_select.hip: tokens per workgroup of the tiled score kernels
@@ -198,6 +204,20 @@ _IMAGE_SIGS = {
                                         C.POINTER(VitImage), c_void_p, c_void_p, c_void_p]),
 }
 IMAGE_SYMBOLS = tuple(_IMAGE_SIGS.keys())
+# include/rajni_hip_query.h, additive in the same way: the mean importance query and sequences without a class row
+_QUERY_SIGS = {
+    "rajni_score_select_query_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "rajni_score_select_query": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "rajni_select_topk_query": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "rajni_patch_embed_query": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                                        c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "rajni_vit_workspace_bytes_query": (c_size_t, [C.POINTER(VitPlan), C.POINTER(VitPrefix), C.POINTER(VitImage),
+                                                   C.POINTER(VitQuery)]),
+    "rajni_vit_forward_query": (c_int, [C.POINTER(VitPlan), C.POINTER(VitExt), C.POINTER(VitPrefix), C.POINTER(VitLayers),
+                                        C.POINTER(VitImage), C.POINTER(VitQuery), c_void_p, c_void_p, c_void_p]),
+}
+QUERY_SYMBOLS = tuple(_QUERY_SIGS.keys())
 RESAMPLE_MAX_GRID = 128     # RAJNI_RESAMPLE_MAX_GRID: grid cells per axis, source and destination
 ABI_VERSION = 8     # include/rajni_hip.h; bumped whenever a struct or an entry point changes
 _lib: Optional[C.CDLL] = None
@@ -213,7 +233,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
             f"librajni_hip.so not found at {path}. Build it with `python rajni-vit_amd/build.py` "
             "(hipcc --offload-arch=gfx950). rajni_amd has no CPU or PyTorch fallback by design.")
     lib = C.CDLL(path)
-    for name, (res, args) in list(_SIGS.items()) + list(_LAYERS_SIGS.items()) + list(_IMAGE_SIGS.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_LAYERS_SIGS.items()) + list(_IMAGE_SIGS.items()) + list(_QUERY_SIGS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -109,12 +109,36 @@ def _score_scratch(qkv: torch.Tensor, B: int, N: int, H: int, D: int) -> Optiona
     return torch.empty(nbytes, dtype=torch.uint8, device=qkv.device) if nbytes else None
 
 
-def importance(qkv: torch.Tensor, num_heads: int, eps: float = 1e-6) -> torch.Tensor:
+QUERIES = {"cls": nat.QUERY_CLS, "mean": nat.QUERY_MEAN}
+
+
+def query_code(query: str) -> int:
+    """"cls" (row 0 is the importance query) or "mean" (the mean of the N query rows, include/rajni_hip_query.h)"""
+    if query not in QUERIES:
+        raise ValueError(f'query must be "cls" or "mean", got {query!r}')
+    return QUERIES[query]
+
+
+def _score_select_query(qkv, B, N, H, D, eps, P, keep, query, scores, idx, nxt):
+    """rajni_score_select_query with its own scratch (the mean query, or a sequence without prefix tokens)"""
+    qc = query_code(query)
+    nbytes = nat.lib().rajni_score_select_query_workspace_bytes(B, N, H, D, _dt(qkv), qc)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=qkv.device) if nbytes else None
+    with nat.device_guard(qkv.device):
+        nat.check(nat.lib().rajni_score_select_query(qkv.data_ptr(), B, N, H, D, eps, P, keep, qc, nat.ptr(scores), nat.ptr(idx),
+                                                     nat.ptr(nxt), _dt(qkv), nat.ptr(ws), nbytes, nat.stream_ptr(qkv.device)),
+                  "rajni_score_select_query")
+
+
+def importance(qkv: torch.Tensor, num_heads: int, eps: float = 1e-6, query: str = "cls") -> torch.Tensor:
     nat.require_device(qkv, "qkv")
     qkv = _placed(qkv, "qkv")
     B, N, threeC = qkv.shape
     D = threeC // 3 // num_heads
     out = torch.empty((B, N), dtype=qkv.dtype, device=qkv.device)
+    if query != "cls":
+        _score_select_query(qkv, B, N, num_heads, D, eps, 0, 0, query, out, None, None)
+        return out
     ws = _score_scratch(qkv, B, N, num_heads, D)
     with nat.device_guard(qkv.device):
         if ws is None:
@@ -137,7 +161,10 @@ def select_topk(scores: torch.Tensor, keep: int, num_prefix: int = 1) -> Tuple[t
     idx = torch.empty((B, keep + P), dtype=torch.int32, device=scores.device)
     nxt = torch.empty((B, keep + P), dtype=scores.dtype, device=scores.device)
     with nat.device_guard(scores.device):
-        if P == 1:
+        if P == 0:      # a sequence without a class row (include/rajni_hip_query.h)
+            nat.check(nat.lib().rajni_select_topk_query(scores.data_ptr(), B, N, 0, keep, idx.data_ptr(), nxt.data_ptr(),
+                                                        _dt(scores), nat.stream_ptr(scores.device)), "rajni_select_topk_query")
+        elif P == 1:
             nat.check(nat.lib().rajni_select_topk(scores.data_ptr(), B, N, keep, idx.data_ptr(), nxt.data_ptr(),
                                                   _dt(scores), nat.stream_ptr(scores.device)), "rajni_select_topk")
         else:
@@ -147,9 +174,10 @@ def select_topk(scores: torch.Tensor, keep: int, num_prefix: int = 1) -> Tuple[t
 
 
 def score_select(qkv: torch.Tensor, num_heads: int, keep: int, eps: float = 1e-6, want_scores: bool = True,
-                 num_prefix: int = 1):
+                 num_prefix: int = 1, query: str = "cls"):
     """qkv [B, N, 3C] -> (scores [B, N] or None, keep_idx int32 [B, P+keep], next_scores [B, P+keep]), P = `num_prefix`
-    as in select_topk (the scores themselves do not depend on P)."""
+    as in select_topk (the scores themselves do not depend on P).  `query`: "cls" (row 0) or "mean" (the mean query row);
+    P = 0 (a sequence without a class row) goes through rajni_score_select_query with either."""
     nat.require_device(qkv, "qkv")
     qkv = _placed(qkv, "qkv")
     B, N, threeC = qkv.shape
@@ -158,6 +186,9 @@ def score_select(qkv: torch.Tensor, num_heads: int, keep: int, eps: float = 1e-6
     scores = torch.empty((B, N), dtype=qkv.dtype, device=qkv.device) if want_scores else None
     idx = torch.empty((B, keep + P), dtype=torch.int32, device=qkv.device)
     nxt = torch.empty((B, keep + P), dtype=qkv.dtype, device=qkv.device)
+    if query != "cls" or P == 0:
+        _score_select_query(qkv, B, N, num_heads, D, eps, P, keep, query, scores, idx, nxt)
+        return scores, idx, nxt
     ws = _score_scratch(qkv, B, N, num_heads, D)
     with nat.device_guard(qkv.device):
         if ws is not None:      # more tokens than one workgroup's LDS holds: the tiled kernels, through scratch

@@ -56,6 +56,9 @@ def get_args(argv=None):
     p.add_argument("--dynamic_img_size", action="store_true",
                    help="RAJNIViTWrapper.set_dynamic_img_size: any H x W the patch size divides, the position embedding resampled "
                         "as timm's dynamic_img_size=True does (the stock base model of --compare_base must accept the size itself)")
+    p.add_argument("--importance_query", type=str, default=None, choices=["cls", "mean"],
+                   help="RAJNIViTWrapper.set_importance_query: the class row (the default with a class token) or the mean of the "
+                        "query rows (the default and the only choice for a model without one)")
     args = p.parse_args(argv)
     if args.img_size is not None and len(args.img_size) > 2:
         p.error("--img_size takes H or H W")
@@ -76,9 +79,9 @@ def create_base(args):
         model = timm.create_model(args.model, pretrained=args.pretrained)
         source = "timm"
     except ImportError:
-        if args.model not in ts.CONFIGS and args.model not in ts.SWIGLU_CONFIGS:
+        if args.model not in ts.CONFIGS and args.model not in ts.SWIGLU_CONFIGS and args.model not in ts.NOCLASS_CONFIGS:
             raise SystemExit(f"timm is not installed and '{args.model}' is not a built-in config "
-                             f"{sorted(ts.CONFIGS) + sorted(ts.SWIGLU_CONFIGS)}")
+                             f"{sorted(ts.CONFIGS) + sorted(ts.SWIGLU_CONFIGS) + sorted(ts.NOCLASS_CONFIGS)}")
         model = ts.create_model(args.model, seed=args.seed)
         source = "timm-shaped stand-in, seeded random weights"
     if args.weights:
@@ -202,6 +205,8 @@ def main(argv=None):
         model.set_residual_dtype(getattr(torch, args.residual))
     if args.dynamic_img_size:
         model.set_dynamic_img_size(True)
+    if args.importance_query is not None:
+        model.set_importance_query(args.importance_query)
     say("Evaluating RAJNI model (HIP path)...")
     acc, thr = evaluate_model(model, loader, device=device, max_batches=args.max_batches, warmup=args.warmup)
     say(f"RAJNI accuracy: {acc:.2f}%  throughput: {thr:.1f} img/s")

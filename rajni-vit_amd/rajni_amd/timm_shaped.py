@@ -5,6 +5,8 @@ timm is not installed in the build/bench images, and the reference wrapper
 `attention.py:8-12`) only consumes an attribute contract, not timm itself:
 
   base : .patch_embed(x)->[B,N-1,C]  .cls_token [1,1,C]  .pos_embed [1,N,C]
+         (timm class_token=False: .cls_token is None and the sequence has no class row - the `*_gap_*` models; the
+          reference cannot run those, RAJNIViTWrapper scores them with the mean query)
          .pos_drop  .blocks  .norm  .head
          (+ timm's optional .reg_token [1,R,C] / .num_prefix_tokens = 1 + R: register tokens behind the
           class token, which the reference does not handle and RAJNIViTWrapper does; and DeiT's distilled
@@ -54,6 +56,10 @@ class ViTConfig:
     pre_norm: bool = False                # norm_pre after the pos-embed (CLIP-derived ViTs)
     global_pool: str = "token"            # 'token' (x[:, 0]) or 'avg' (mean of x[:, 1:])
     fc_norm: Optional[bool] = None        # None = timm's default: an fc_norm (and no final norm) iff global_pool == 'avg'
+    class_token: bool = True              # timm class_token: False = no class row at all (cls_token is None, the prefix tokens
+                                          # are the registers alone; needs global_pool='avg' and no distillation, as timm
+                                          # asserts).  (In front of mlp, distilled, act and reg_tokens, which existing tests
+                                          # hold to be the last four fields)
     mlp: str = "mlp"                      # the block's MLP: "mlp" (fc1 -> act -> fc2), "swiglu_packed" (timm GluMlp with
                                           # act_layer=nn.SiLU, gate_last=False, alias SwiGLUPacked: ONE fc1 of 2 * hidden_dim
                                           # outputs, gate half first - the DINOv2 giant ViTs) or "swiglu" (timm SwiGLU: fc1_g and
@@ -74,10 +80,14 @@ class ViTConfig:
             raise ValueError("ViTConfig: distilled together with reg_tokens is not a timm model")
         if self.mlp not in ("mlp", "swiglu_packed", "swiglu"):
             raise ValueError(f"ViTConfig: mlp must be 'mlp', 'swiglu_packed' or 'swiglu', got {self.mlp!r}")
+        if not self.class_token and self.global_pool == "token":
+            raise ValueError("ViTConfig: class_token=False needs global_pool='avg' (timm asserts it: a token head has no row to read)")
+        if not self.class_token and self.distilled:
+            raise ValueError("ViTConfig: class_token=False together with distilled is not a timm model")
 
     @property
     def num_prefix_tokens(self) -> int:
-        return 1 + self.reg_tokens + int(self.distilled)
+        return int(self.class_token) + self.reg_tokens + int(self.distilled)
 
     @property
     def use_fc_norm(self) -> bool:
@@ -220,13 +230,34 @@ SWIGLU_CONFIGS: Dict[str, ViTConfig] = {
 }
 
 
+# Models without a class token (timm class_token=False, global_pool='avg'), in a table of their own for the same reason.
+NOCLASS_CONFIGS: Dict[str, ViTConfig] = {
+    # micro models (not timm names): no prefix token at all (timm's default head for 'avg': fc_norm behind the pool, no final
+    # norm); 4 registers in the DINOv2 / DeiT-3 layout (no_embed_class, LayerScale) with the final norm in front of the pool
+    # (fc_norm=False, so the feature outputs exist); head dim 80 with one register and a pos-embed row for it (R + n rows)
+    "vit_micro_nocls_gap_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, num_classes=10,
+                                                global_pool="avg", class_token=False),
+    "vit_micro_reg4_nocls_gap_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, num_classes=10,
+                                                     layer_scale=1e-6, no_embed_class=True, global_pool="avg", fc_norm=False,
+                                                     class_token=False, reg_tokens=4),
+    "vit_micro_reg1_nocls_gap_d80_patch16_64": ViTConfig(img_size=64, embed_dim=320, depth=4, num_heads=4, num_classes=10,
+                                                         global_pool="avg", class_token=False, reg_tokens=1),
+    # The dimensions of two timm checkpoints of the family.  timm is not importable where this was written: both entries were
+    # WRITTEN FROM MEMORY AND ARE UNVERIFIED (width, depth, heads, MLP ratio, fc_norm and LayerScale may each be off); no test
+    # depends on their being exact - they exist to give the cost tools a real-size shape.
+    "vit_medium_patch16_gap_256": ViTConfig(img_size=256, embed_dim=512, depth=12, num_heads=8, layer_scale=1e-6,
+                                            global_pool="avg", fc_norm=False, class_token=False),
+    "vit_betwixt_patch16_reg4_gap_256": ViTConfig(img_size=256, embed_dim=640, depth=12, num_heads=10, layer_scale=1e-5,
+                                                  no_embed_class=True, global_pool="avg", class_token=False, reg_tokens=4),
+}
+
+
 def config_of(name: str) -> ViTConfig:
-    """the built-in config of that name, from CONFIGS or SWIGLU_CONFIGS"""
-    if name in CONFIGS:
-        return CONFIGS[name]
-    if name in SWIGLU_CONFIGS:
-        return SWIGLU_CONFIGS[name]
-    raise KeyError(f"'{name}' is not a built-in config {sorted(CONFIGS) + sorted(SWIGLU_CONFIGS)}")
+    """the built-in config of that name, from CONFIGS, SWIGLU_CONFIGS or NOCLASS_CONFIGS"""
+    for table in (CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS):
+        if name in table:
+            return table[name]
+    raise KeyError(f"'{name}' is not a built-in config {sorted(CONFIGS) + sorted(SWIGLU_CONFIGS) + sorted(NOCLASS_CONFIGS)}")
 
 
 class PatchEmbed(nn.Module):
@@ -374,7 +405,7 @@ class VisionTransformer(nn.Module):
         self.num_reg_tokens = cfg.reg_tokens
         self.no_embed_class = cfg.no_embed_class
         self.patch_embed = PatchEmbed(cfg)
-        self.cls_token = nn.Parameter(torch.zeros(1, 1, cfg.embed_dim))
+        self.cls_token = nn.Parameter(torch.zeros(1, 1, cfg.embed_dim)) if cfg.class_token else None   # timm: None
         self.reg_token = nn.Parameter(torch.zeros(1, cfg.reg_tokens, cfg.embed_dim)) if cfg.reg_tokens else None
         if cfg.distilled:      # timm VisionTransformerDistilled (a plain model has neither attribute, like timm's)
             self.dist_token = nn.Parameter(torch.zeros(1, 1, cfg.embed_dim))
@@ -399,7 +430,7 @@ class VisionTransformer(nn.Module):
 
     def _pos_embed(self, x):
         # timm: prefix tokens [cls, reg...] in front; the pos-embed covers them unless no_embed_class
-        prefix = [self.cls_token.expand(x.shape[0], -1, -1)]
+        prefix = [self.cls_token.expand(x.shape[0], -1, -1)] if self.cls_token is not None else []
         if self.reg_token is not None:
             prefix.append(self.reg_token.expand(x.shape[0], -1, -1))
         if self.cfg.distilled:
@@ -447,7 +478,8 @@ def synth_state_dict(cfg: ViTConfig, seed: int = 0, std: float = 0.02,
         return (rng.standard_normal(shape, dtype=np.float32) * np.float32(s)).astype(np.float32)
 
     sd: Dict[str, np.ndarray] = {}
-    sd["cls_token"] = nrm(1, 1, C)
+    if cfg.class_token:      # (a model without one draws nothing in its place)
+        sd["cls_token"] = nrm(1, 1, C)
     n_pos = cfg.num_patches if cfg.no_embed_class else cfg.num_patches + cfg.num_prefix_tokens
     sd["pos_embed"] = nrm(1, n_pos, C)
     fan_in = cfg.in_chans * P * P

@@ -58,6 +58,9 @@ class RAJNIAttention(nn.Module):
         # prefix tokens at the front of x (CLS + timm register tokens): always kept, never ranked.  RAJNIViTWrapper sets it
         # from the base model; 1 = the reference's single class token
         self.num_prefix_tokens = 1
+        # the importance query: "cls" (row 0, the reference's rule) or "mean" (the mean of the query rows: the rule of a model
+        # without a class token, whose num_prefix_tokens is its register count R >= 0).  RAJNIViTWrapper sets both
+        self.importance_query = "cls"
         self._packed = None
         self._packed_key = None
 
@@ -94,7 +97,8 @@ class RAJNIAttention(nn.Module):
         P = int(getattr(self, "num_prefix_tokens", 1))
         keep = ops.keep_count(self.keep_ratio, N, P)                                  # attention.py:31-32
         if self.update or prev_scores is None:                                        # attention.py:25-28
-            _, keep_idx, next_scores = ops.score_select(qkv, self.num_heads, keep, want_scores=False, num_prefix=P)
+            _, keep_idx, next_scores = ops.score_select(qkv, self.num_heads, keep, want_scores=False, num_prefix=P,
+                                                        query=getattr(self, "importance_query", "cls"))
         else:
             keep_idx, next_scores = ops.select_topk(prev_scores.to(x.dtype), keep, num_prefix=P)   # attention.py:34-39,58
         out = ops.attention(qkv, keep_idx, self.num_heads, self.scale)                # attention.py:42-54

@@ -15,7 +15,10 @@ final normalised tokens of the pruned graph, or the unpruned sequence with prune
 feature each token had when it left the stream), with their source positions in `get_last_stats()["source_idx"]`; and
 `forward_intermediates` / `get_intermediate_layers` (timm's and DINOv2's signatures) return the states behind several blocks from
 one forward, each on that unpruned grid; and `set_dynamic_img_size(True)` (timm's `dynamic_img_size`): any [B, C, H, W] the
-patch size divides, the position embedding resampled to the input's token grid as timm's resample_abs_pos_embed does.
+patch size divides, the position embedding resampled to the input's token grid as timm's resample_abs_pos_embed does; and
+models WITHOUT a class token (timm `class_token=False, global_pool='avg'`: the `*_gap_*` checkpoints, with or without
+registers), which the reference cannot run at all: their importance query is the mean of the query rows
+(`set_importance_query`, include/rajni_hip_query.h - this project's own rule), selectable on class-token models too.
 
 Not kept: the Python per-block loop.  `forward` builds (once per batch shape) a `rajni_vit_plan`
 - packed weights, workspace, per-stage index buffers - and calls `rajni_vit_forward`, which enqueues
@@ -126,15 +129,51 @@ def model_is_distilled(m: nn.Module) -> bool:
     return True
 
 
+def model_has_class_token(m: nn.Module) -> bool:
+    return getattr(m, "cls_token", None) is not None
+
+
+def _num_prefix_without_class_token(m: nn.Module) -> int:
+    """R of a model whose `cls_token` is None (timm class_token=False): the prefix tokens are its registers alone.  Accepted
+    only when the model is consistent - no distillation pair, a well-formed `reg_token`, a declared `num_prefix_tokens` equal
+    to R, a pos_embed of n or R + n rows, and an 'avg' pool or no head; everything else keeps the refusal a missing class token
+    always had (NotImplementedError naming cls_token)."""
+    why = "RAJNIViTWrapper: the model has no cls_token (class_token=False)"
+    if getattr(m, "dist_token", None) is not None or getattr(m, "head_dist", None) is not None:
+        raise NotImplementedError(f"{why} but a distillation token or head_dist: distillation reads the class row")
+    reg = getattr(m, "reg_token", None)
+    Cdim = m.pos_embed.shape[-1]
+    R = 0
+    if reg is not None:
+        if reg.dim() != 3 or reg.shape[0] != 1 or reg.shape[1] < 1 or reg.shape[2] != Cdim:
+            raise NotImplementedError(f"{why}: reg_token must be [1, R, {Cdim}] with R >= 1, got {tuple(reg.shape)}")
+        R = int(reg.shape[1])
+    declared = getattr(m, "num_prefix_tokens", R)
+    if declared != R:
+        raise NotImplementedError(f"{why} and declares {declared} prefix tokens but its parameters supply {R} (reg_token alone): "
+                                  "the class token is the importance query of such a model and is required")
+    if R > nat.MAX_PREFIX:
+        raise NotImplementedError(f"{why} and {R} prefix tokens; at most {nat.MAX_PREFIX} are supported")
+    n_patches = getattr(m.patch_embed, "num_patches", None)
+    if isinstance(n_patches, int) and m.pos_embed.shape[-2] not in (n_patches, n_patches + R):
+        raise NotImplementedError(f"{why}: pos_embed has {m.pos_embed.shape[-2]} rows; with {R} register tokens and {n_patches} "
+                                  f"patches it must have {n_patches} (no_embed_class) or {n_patches + R}")
+    pool = getattr(m, "global_pool", "token")
+    if pool != "avg" and not isinstance(getattr(m, "head", None), nn.Identity):
+        raise NotImplementedError(f"{why} and global_pool={pool!r}: without a class row the head must pool with 'avg' "
+                                  "(or be nn.Identity)")
+    return R
+
+
 def model_num_prefix(m: nn.Module) -> int:
     """P prefix tokens the base model's PARAMETERS supply: `cls_token` and `reg_token` [1, R, C] (timm reg_tokens=R, P = 1 + R)
-    or `dist_token` [1, 1, C] (DeiT distilled, P = 2).  Raises NotImplementedError for what the native forward does not
-    compute (no class token, a half-formed distillation pair, a malformed or oversized register set, a declared
-    `num_prefix_tokens` that disagrees)."""
+    or `dist_token` [1, 1, C] (DeiT distilled, P = 2); R alone for a consistent model without a class token (timm
+    class_token=False).  Raises NotImplementedError for what the native forward does not compute (a half-formed model without a
+    class token, a half-formed distillation pair, a malformed or oversized register set, a declared `num_prefix_tokens` that
+    disagrees)."""
     cls = getattr(m, "cls_token", None)
     if cls is None:
-        raise NotImplementedError("RAJNIViTWrapper: the model has no cls_token (class_token=False): the class token is the "
-                                  "importance query and is required")
+        return _num_prefix_without_class_token(m)
     if model_is_distilled(m):
         declared = getattr(m, "num_prefix_tokens", 2)
         if declared != 2:
@@ -244,6 +283,8 @@ class RAJNIViTWrapper(nn.Module):
             prefix = model_num_prefix(base_model)
         except NotImplementedError:
             prefix = 1
+        # the importance query (set_importance_query): None = the model's default, "cls" with a class token, "mean" without
+        self._query = None
         for i, blk in enumerate(self.blocks):
             if i in self.pruning_schedule:
                 cfg = self.pruning_schedule[i]
@@ -252,6 +293,7 @@ class RAJNIViTWrapper(nn.Module):
                 else:  # re-wrapping an already wrapped base
                     blk.attn.keep_ratio, blk.attn.update = cfg["keep_ratio"], cfg["update"]
                 blk.attn.num_prefix_tokens = prefix
+                blk.attn.importance_query = self.importance_query
                 blk.has_pruner = True
             else:
                 blk.has_pruner = False
@@ -312,6 +354,29 @@ class RAJNIViTWrapper(nn.Module):
         self._resid_bf16 = dtype != torch.float32
         self._resid_dtype = dtype
         self._drop_plans()
+        return self
+
+    @property
+    def importance_query(self) -> str:
+        """"cls" or "mean": what every scoring block uses as the importance query"""
+        if self._query is not None:
+            return self._query
+        return "cls" if model_has_class_token(self.m) else "mean"
+
+    def set_importance_query(self, query: str):
+        """"cls": the class row (row 0) is the importance query - the reference's rule, the default of every model that has a
+        class token.  "mean": the mean of the N query rows of the block's current sequence (include/rajni_hip_query.h; this
+        project's own rule, pruning quality unmeasured) - the default and the only legal value for a model without a class
+        token, selectable on class-token models too (the avg-pooled ones read the mean of the tokens)."""
+        ops.query_code(query)
+        if query == "cls" and not model_has_class_token(self.m):
+            raise ValueError('set_importance_query("cls"): the model has no class token; "mean" is its only importance query')
+        if query != self.importance_query:
+            self._drop_plans()
+        self._query = query
+        for blk in self.blocks:
+            if isinstance(blk.attn, RAJNIAttention):
+                blk.attn.importance_query = query
         return self
 
     def set_dynamic_img_size(self, on: bool = True):
@@ -418,6 +483,8 @@ class RAJNIViTWrapper(nn.Module):
         tokens, proj / MLP on B rows.  The logits are the same function of the input (the reference's head reads
         x[:, 0] only); the other rows of the last block are never formed.  Off by default: the default forward
         executes the reference's op graph row for row."""
+        if on and not model_has_class_token(self.m):
+            raise ValueError("set_last_block_cls_only: the model has no class token; there is no class row to form")
         if on and self._is_distilled():
             raise ValueError("set_last_block_cls_only: the model is a distillation model (DeiT distilled) whose head reads two rows; "
                              "the CLS-only last block forms the class row only (the default forward already computes the last "
@@ -487,7 +554,12 @@ class RAJNIViTWrapper(nn.Module):
             raise NotImplementedError('weight format "fp8_mfma" on a headless model (head = nn.Identity) is not supported; '
                                       '"fp8" weights work')
         blk0 = self.blocks[0]
-        Cdim = m.cls_token.shape[-1]
+        has_cls = model_has_class_token(m)
+        if not has_cls and self._cls_only_last:
+            raise ValueError("a model without a class token with set_last_block_cls_only(True): there is no class row to form")
+        if not has_cls and self._weight_format == "fp8_mfma":
+            raise NotImplementedError('weight format "fp8_mfma" on a model without a class token is not supported; "fp8" weights work')
+        Cdim = m.cls_token.shape[-1] if has_cls else m.pos_embed.shape[-1]
         heads = blk0.attn.num_heads
         # FC2's K and the hidden buffer's width: of a gated MLP (SwiGLU) too, whose FC1 has twice as many rows
         desc = dict(C=Cdim, H=heads, D=Cdim // heads, depth=len(self.blocks), hidden=blk0.mlp.fc2.in_features,
@@ -524,12 +596,13 @@ class RAJNIViTWrapper(nn.Module):
             raise NotImplementedError("RAJNIViTWrapper: attn_pool (global_pool='map') is not supported")
         # prefix tokens: the class token plus timm's register tokens (never pruned, never ranked; 'avg' pools behind them)
         desc["num_prefix"] = num_prefix
+        desc["class_token"] = has_cls
         # rows of each image the head reads: 2 = DeiT distilled, the class and distillation rows through two averaged heads
-        desc["head_rows"] = 2 if model_is_distilled(m) else 1
+        desc["head_rows"] = 2 if has_cls and model_is_distilled(m) else 1
         if desc["head_rows"] == 2 and self._cls_only_last:
             raise ValueError("a distillation model with set_last_block_cls_only(True): that opt-in forms the class row only")
         n_patches = getattr(m.patch_embed, "num_patches", None)
-        if num_prefix > 1 and isinstance(n_patches, int) and m.pos_embed.shape[-2] not in (n_patches, n_patches + num_prefix):
+        if has_cls and num_prefix > 1 and isinstance(n_patches, int) and m.pos_embed.shape[-2] not in (n_patches, n_patches + num_prefix):
             raise NotImplementedError(f"RAJNIViTWrapper: pos_embed has {m.pos_embed.shape[-2]} rows; with {num_prefix} prefix tokens "
                                       f"and {n_patches} patches it must have {n_patches} (no_embed_class) or {n_patches + num_prefix}")
         fc_norm = getattr(m, "fc_norm", None)
@@ -615,9 +688,11 @@ class RAJNIViTWrapper(nn.Module):
         W = dict(desc=desc)
         W["patch_w"] = ops.pack_weight(m.patch_embed.proj.weight, dtype, device, k_multiple=64)
         W["patch_b"] = pv(m.patch_embed.proj.bias) if m.patch_embed.proj.bias is not None else zeros(desc["C"])
-        W["cls"] = m.cls_token.detach().to(device=device, dtype=dtype).reshape(-1).contiguous()
-        # the prefix rows behind the class token: timm's registers, or the distillation token (one row, the same record)
-        reg_src = m.dist_token if desc["head_rows"] == 2 else (m.reg_token if desc["num_prefix"] > 1 else None)
+        W["cls"] = m.cls_token.detach().to(device=device, dtype=dtype).reshape(-1).contiguous() if desc["class_token"] else None
+        # the prefix rows behind the class token: timm's registers, or the distillation token (one row, the same record);
+        # without a class token the registers are all the prefix rows there are
+        reg_src = m.dist_token if desc["head_rows"] == 2 else \
+            (m.reg_token if desc["num_prefix"] > (1 if desc["class_token"] else 0) else None)
         W["reg"] = (reg_src.detach().to(device=device, dtype=dtype).reshape(-1, desc["C"]).contiguous()
                     if reg_src is not None else None)
         W["pos"] = m.pos_embed.detach().to(device=device, dtype=dtype).reshape(-1, desc["C"]).contiguous()
@@ -718,6 +793,9 @@ class RAJNIViTWrapper(nn.Module):
         W = self._pack_weights(device, dtype)
         d = W["desc"]
         P = d["num_prefix"]
+        has_cls, query = d["class_token"], self.importance_query
+        if query == "cls" and not has_cls:      # (the class token was removed after the setter)
+            raise ValueError('importance query "cls" on a model without a class token; set_importance_query("mean")')
         full_mode, layers = mode, None
         if isinstance(mode, tuple):
             _, mode, caps, lnorm, lfill = mode
@@ -726,7 +804,7 @@ class RAJNIViTWrapper(nn.Module):
         if features:
             self._check_features(d)
         key = (B, S, device, dtype, self._weights_key, tuple(sorted(self._forced)), self._trace_scores, self._resid_bf16,
-               self._cls_only_last, P, full_mode)
+               self._cls_only_last) + ((query, has_cls) if (query, has_cls) != ("cls", True) else ()) + (P, full_mode)
         if self._plan is not None and self._plan[0] == key:
             return self._plan
         if key in self._plans:
@@ -745,7 +823,7 @@ class RAJNIViTWrapper(nn.Module):
                 raise NotImplementedError("RAJNIViTWrapper: dynamic_img_pad (padding images to a multiple of the patch size) is "
                                           "not supported")
             pos, pos_has_cls = self._pos_for_grid(W, gh, gw, P, device, dtype)
-        elif pos_rows == n0 or (P == 1 and pos_rows > n0):
+        elif pos_rows == n0 or (P == 1 and has_cls and pos_rows > n0):
             pos_has_cls = 1      # reference: x + pos_embed[:, :N]  (model.py:37); timm: a row for every prefix token too
         elif pos_rows == n0 - P:
             pos_has_cls = 0      # timm no_embed_class: the prefix rows get no pos-embed
@@ -781,7 +859,7 @@ class RAJNIViTWrapper(nn.Module):
                     f = self._forced[i].to(device)
                     if tuple(f.shape) != (B, keep + P):
                         raise ValueError(f"forced keep_idx for block {i} has shape {tuple(f.shape)}, want {(B, keep + P)}")
-                    if P > 1 and not bool((f[:, :P].cpu() == torch.arange(P, dtype=torch.int32)).all()):
+                    if (P > 1 or not has_cls) and not bool((f[:, :P].cpu() == torch.arange(P, dtype=torch.int32)).all()):
                         raise ValueError(f"forced keep_idx for block {i}: slots 0..{P - 1} must hold the prefix tokens 0..{P - 1}")
                     self._forced[i] = f
                     cb.forced_keep_idx = f.data_ptr()
@@ -796,7 +874,7 @@ class RAJNIViTWrapper(nn.Module):
         plan.num_classes, plan.ln_eps, plan.attn_scale = 0 if headless else d["num_classes"], d["ln_eps"], d["scale"]
         plan.pos_has_cls = pos_has_cls
         plan.patch_w, plan.patch_b = W["patch_w"].data_ptr(), W["patch_b"].data_ptr()
-        plan.cls_token, plan.pos_embed = W["cls"].data_ptr(), pos.data_ptr()
+        plan.cls_token, plan.pos_embed = nat.ptr(W["cls"]), pos.data_ptr()
         plan.blocks = blocks
         plan.norm_w, plan.norm_b = nat.ptr(W["norm_w"]), nat.ptr(W["norm_b"])
         plan.head_w, plan.head_b = (None, None) if headless else (W["head_w"].data_ptr(), W["head_b"].data_ptr())
@@ -807,8 +885,14 @@ class RAJNIViTWrapper(nn.Module):
         plan.resid_bf16 = int(self._resid_bf16)
         plan.cls_only_last_block = int(self._cls_only_last)
         plan.act_fp8 = int(self._weight_format == "fp8_mfma")
-        pre = None
-        if P > 1:           # the prefix record beside the plan (rajni_vit_prefix); None: CLS only, the entry points as ever
+        pre = qry = None
+        if (query, has_cls) != ("cls", True):   # the query record beside the plan (rajni_vit_query); None: the entry points as ever
+            qry = nat.VitQuery(int(has_cls), ops.query_code(query))
+        if not has_cls:     # no class row: the record counts the registers alone (R = 0: no record)
+            if P > 0:
+                pre = nat.VitPrefix()
+                pre.num_prefix, pre.reg_token, pre.head_rows = P, W["reg"].data_ptr(), 0
+        elif P > 1:         # the prefix record beside the plan (rajni_vit_prefix); None: CLS only, the entry points as ever
             pre = nat.VitPrefix()
             pre.num_prefix, pre.reg_token = P, W["reg"].data_ptr()
             # (register models: the record as it always was; the feature plan of a distilled model reads no head rows)
@@ -816,7 +900,13 @@ class RAJNIViTWrapper(nn.Module):
         img = None
         if Hh != Wd:        # the image record beside the plan (rajni_vit_image); None: a square input, the entry points as ever
             img = nat.VitImage(Hh, Wd)
-        if img is not None:
+        if qry is not None:
+            ref = lambda rec: C.byref(rec) if rec is not None else None
+            nbytes = nat.lib().rajni_vit_workspace_bytes_query(C.byref(plan), ref(pre), ref(img), C.byref(qry))
+            if nbytes == 0:       # a record is refused: say why (the forward's own refusal, nothing is launched)
+                nat.check(nat.lib().rajni_vit_forward_query(C.byref(plan), None, ref(pre), None, ref(img), C.byref(qry), 16, 16, None),
+                          "rajni_vit_forward_query")
+        elif img is not None:
             nbytes = nat.lib().rajni_vit_workspace_bytes_image(C.byref(plan), C.byref(pre) if pre is not None else None, C.byref(img))
             if nbytes == 0:       # the record is refused: say why (the forward's own refusal, nothing is launched)
                 nat.check(nat.lib().rajni_vit_forward_image(C.byref(plan), None, C.byref(pre) if pre is not None else None, None,
@@ -857,7 +947,8 @@ class RAJNIViTWrapper(nn.Module):
         # (existing callers index entry[0..4] and unpack entry[2] as seven objects: mode and out_shape go behind `counts`,
         # the layers record behind those)
         # (the image record and the position rows the plan points to, with the grid, last)
-        self._plan = (key, plan, (blocks, tc, ws, W, ext, qk, pre), bufs, counts, full_mode, out_shape, layers, (img, pos, gh, gw))
+        # (the query record behind the grid: index 4 of the last element)
+        self._plan = (key, plan, (blocks, tc, ws, W, ext, qk, pre), bufs, counts, full_mode, out_shape, layers, (img, pos, gh, gw, qry))
         if len(self._plans) >= 4:     # workspaces are large: keep only a few batch shapes alive
             self._plans.pop(next(iter(self._plans)))
         self._plans[key] = self._plan
@@ -962,7 +1053,7 @@ class RAJNIViTWrapper(nn.Module):
         (final, slabs), entry = self._run(x, ("layers", base, caps, bool(norm), fill))
         self._selection_stats(entry, x, exit_block=True)
         P = entry[0][-2]
-        B, (gh, gw), Cdim = x.shape[0], entry[8][2:], entry[1].C
+        B, (gh, gw), Cdim = x.shape[0], entry[8][2:4], entry[1].C
         inter = []
         for l in range(len(caps)):
             spatial = slabs[l, :, P:]
@@ -996,12 +1087,13 @@ class RAJNIViTWrapper(nn.Module):
     def _run(self, x: torch.Tensor, mode: str):
         nat.require_device(x, "input images")
         self._check_input_shape(x)
-        dtype = self.m.cls_token.dtype
+        anchor = self.m.cls_token if model_has_class_token(self.m) else self.m.pos_embed   # a parameter every model has
+        dtype = anchor.dtype
         if self._resid_bf16 and dtype in (torch.bfloat16, torch.float16) and self._resid_dtype != dtype:
             raise ValueError(f"a {self._resid_dtype} residual stream needs a {self._resid_dtype} model (the model is {dtype}); "
                              f"the 16-bit stream is kept in the model dtype")
-        if self.m.cls_token.device != x.device:
-            raise nat.NativeError(f"model is on {self.m.cls_token.device} but images are on {x.device}")
+        if anchor.device != x.device:
+            raise nat.NativeError(f"model is on {anchor.device} but images are on {x.device}")
         if x.dtype != dtype:
             x = x.to(dtype)
         x = x.contiguous()
@@ -1013,6 +1105,17 @@ class RAJNIViTWrapper(nn.Module):
                 out = torch.empty(entry[6], dtype=dtype, device=x.device)
                 ext, pre = entry[2][4], entry[2][6]
                 ref = lambda rec: C.byref(rec) if rec is not None else None
+                if entry[8][4] is not None:   # a query record (the mean query, or no class row): every record through rajni_vit_forward_query
+                    lay = slabs = None
+                    if entry[7] is not None:
+                        cap_arr, lnorm, lfill, slab_shape = entry[7]
+                        slabs = torch.empty(slab_shape, dtype=dtype, device=x.device)
+                        lay = nat.VitLayers()
+                        lay.n, lay.blocks, lay.norm, lay.fill, lay.out, lay.slab_stride = len(cap_arr), cap_arr, lnorm, lfill, slabs.data_ptr(), 0
+                    nat.check(nat.lib().rajni_vit_forward_query(C.byref(plan), ref(ext), ref(pre), ref(lay), ref(entry[8][0]),
+                                                                C.byref(entry[8][4]), x.data_ptr(), out.data_ptr(),
+                                                                nat.stream_ptr(x.device)), "rajni_vit_forward_query")
+                    return out if lay is None else (out, slabs)
                 if entry[8][0] is not None:   # a rectangular input: every record through rajni_vit_forward_image
                     lay = slabs = None
                     if entry[7] is not None:
