@@ -405,6 +405,13 @@ int rajni_patch_embed_query(const void* images, const void* w, const float* bias
                             workspace_bytes, (hipStream_t)stream, num_reg, reg, 0);
 }
 
+// ---- include/rajni_hip_attnpool.h
+int rajni_attention_pool(const void* kv, const float* q, void* out, int B, int N, int H, int D, int dtype, rajni_stream_t stream) {
+  NEED_DTYPE("rajni_attention_pool");
+  RAJNI_REQUIRE_PLACED("rajni_attention_pool", {"kv", kv, 16}, {"q", q, 16}, {"out", out, 16});
+  return launch_attention_pool(kv, q, out, B, N, H, D, dtype, (hipStream_t)stream);
+}
+
 void rajni_profile_enable(unsigned mask) { g_prof_mask = mask; }
 const char* rajni_profile_class_name(int k) {
   return (k >= 0 && k < RAJNI_NUM_KCLASS) ? kNames[k] : "";

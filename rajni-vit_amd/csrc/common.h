@@ -8,6 +8,7 @@
 #include "../../include/rajni_hip_layers.h"
 #include "../../include/rajni_hip_image.h"
 #include "../../include/rajni_hip_query.h"
+#include "../../include/rajni_hip_attnpool.h"
 
 typedef unsigned short bf16_t;  // raw bf16 bits in memory
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -226,6 +227,10 @@ int launch_attention_fp8(const void* qkv, const int32_t* keep_idx, void* out_q, 
                          int B, int n_src, int np, int H, int D, float scale, hipStream_t s);
 int launch_attention_cls(const void* qkv, void* out, int B, int N, int H, int D, float scale, int dtype,
                          hipStream_t s, float q_scale = 0.f);   // q_scale > 0: the row passes through rajni_attention_fp8's e4m3 rounding
+// the latent-query attention pool (rajni_hip_attnpool.h): kv [B, N, 2 * H * D], q [H, D] fp32 with the scale folded in, out [B, H * D]
+// in `dtype`, or fp32 with out_f32 (the whole forward's tail)
+int launch_attention_pool(const void* kv, const float* q, void* out, int B, int N, int H, int D, int dtype, hipStream_t s,
+                          int out_f32 = 0);
 // ws: scratch of rajni_score_select_workspace_bytes(B, N, H, D, dtype) bytes (256-byte aligned; may be null when that
 // is 0): shapes beyond one workgroup's LDS are scored by the tiled kernels through it
 int launch_score_select(const void* qkv, const void* scores_in, int B, int N, int H, int D,

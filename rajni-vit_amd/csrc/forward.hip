@@ -38,6 +38,12 @@
 // rows) and whether the sequence has a class row at all.  Without one the prefix tokens are the R >= 0 registers alone: P = R
 // goes through embed, select, the gathered residual, the 'avg' pool, the source map and the dense outputs, the last block always
 // runs every row, and check_query refuses what has no meaning there.  A NULL record or {1, RAJNI_QUERY_CLS} changes no launch.
+//
+// rajni_vit_forward_pool (rajni_hip_attnpool.h) adds the attention-pool head (timm global_pool='map') as a tail of its own,
+// launch_pool_tail: final norm on every surviving row -> kv GEMM into w.qkv -> launch_attention_pool -> proj, the pool's
+// LayerNorm, FC1 + act and FC2 + residual on B rows IN FP32 (PoolRows: carved BEHIND the workspace of rajni_vit_forward_query,
+// which does not move) -> fc_norm or one rounding to the model dtype -> head.  A NULL record changes no launch; RAJNI_POOL_MAP without one is the unknown pool value it
+// always was.
 #include "common.h"
 
 #include <vector>
@@ -86,6 +92,19 @@ Workspace carve(const rajni_vit_plan& p, int P, int HR, const rajni_vit_image* i
   w.xs = reinterpret_cast<float*>(base + oxs); w.hs = reinterpret_cast<float*>(base + ohs);
   w.total = off;
   return w;
+}
+
+// the B-row intermediates of the attention-pool tail (rajni_hip_attnpool.h), behind the `base_total` bytes carve() hands out:
+// o [B, C] the pool kernel's output, y [B, C] proj's output and the MLP's residual stream (FC2 adds in place), n [B, C] the
+// pool LayerNorm's rows, hid [B, pool.hidden] - all fp32 whatever the plan's dtype: the B-row part of the tail runs in fp32
+struct PoolRows { char *o, *y, *n, *hid; size_t total; };
+PoolRows carve_pool(const rajni_vit_plan& p, const rajni_vit_attn_pool& ap, size_t base_total) {
+  size_t off = align256(base_total);
+  auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
+  const size_t row = (size_t)p.B * p.C * sizeof(float);
+  const size_t oo = take(row), oy = take(row), on = take(row), oh = take((size_t)p.B * ap.hidden * sizeof(float));
+  char* base = (char*)p.workspace;
+  return PoolRows{base + oo, base + oy, base + on, base + oh, off};
 }
 
 // next_scores[b, j] = scores[b, idx[b, j]]   (attention.py:58) - used with a forced selection
@@ -167,11 +186,14 @@ int check_plan(const rajni_vit_plan& p, bool norm_absent, bool nocls = false) {
   return RAJNI_OK;
 }
 
-int check_ext(const rajni_vit_plan& p, const rajni_vit_ext& e) {
+// map_ok: the call came through rajni_vit_forward_pool with a record - RAJNI_POOL_MAP is an unknown value everywhere else
+int check_ext(const rajni_vit_plan& p, const rajni_vit_ext& e, bool map_ok = false) {
   // (RAJNI_POOL_NONE, RAJNI_POOL_DENSE and RAJNI_POOL_DENSE_LAST, the token outputs, are legal too - 4 is not; the wording of this
   // refusal is what callers match on)
-  RAJNI_REQUIRE((e.pool >= RAJNI_POOL_TOKEN && e.pool <= RAJNI_POOL_DENSE) || e.pool == RAJNI_POOL_DENSE_LAST, RAJNI_ERR_UNSUPPORTED,
-                "rajni_vit_forward_ext: pool must be RAJNI_POOL_TOKEN or RAJNI_POOL_AVG (%d)", e.pool);
+  RAJNI_REQUIRE((e.pool >= RAJNI_POOL_TOKEN && e.pool <= RAJNI_POOL_DENSE) || e.pool == RAJNI_POOL_DENSE_LAST ||
+                    (map_ok && e.pool == RAJNI_POOL_MAP), RAJNI_ERR_UNSUPPORTED,
+                "rajni_vit_forward_ext: pool must be RAJNI_POOL_TOKEN or RAJNI_POOL_AVG (%d)%s", e.pool,
+                e.pool == RAJNI_POOL_MAP ? " - RAJNI_POOL_MAP needs rajni_vit_forward_pool and its rajni_vit_attn_pool record" : "");
   RAJNI_REQUIRE(!(e.pool == RAJNI_POOL_AVG && p.cls_only_last_block), RAJNI_ERR_INVALID,
                 "rajni_vit_forward_ext: 'avg' pooling with cls_only_last_block - that opt-in never forms the rows to be averaged");
   if (pool_is_tokens(&e)) {
@@ -375,10 +397,41 @@ int check_query(const rajni_vit_plan& p, const rajni_vit_ext* e, const rajni_vit
                 "%s: query.query must be RAJNI_QUERY_MEAN with query.class_token = 0 - there is no class row to be the query", who);
   RAJNI_REQUIRE(!p.cls_only_last_block, RAJNI_ERR_INVALID,
                 "%s: plan.cls_only_last_block with query.class_token = 0 - there is no class row to form", who);
-  RAJNI_REQUIRE(e != nullptr && (e->pool == RAJNI_POOL_AVG || pool_is_tokens(e)), RAJNI_ERR_INVALID,
+  // (RAJNI_POOL_MAP reads every row too; whether it is legal at this entry point is check_ext's to say)
+  RAJNI_REQUIRE(e != nullptr && (e->pool == RAJNI_POOL_AVG || e->pool == RAJNI_POOL_MAP || pool_is_tokens(e)), RAJNI_ERR_INVALID,
                 "%s: ext.pool must be RAJNI_POOL_AVG or a token output with query.class_token = 0 - a token head has no row to "
                 "read (%s)", who, e ? "RAJNI_POOL_TOKEN" : "ext is NULL");
   RAJNI_REQUIRE(!p.act_fp8, RAJNI_ERR_UNSUPPORTED, "%s: plan.act_fp8 is unsupported with query.class_token = 0", who);
+  return RAJNI_OK;
+}
+
+// the attention-pool record against the plan, the ext and the prefix record (rajni_hip_attnpool.h): host-side tests, every
+// refusal names its field
+int check_pool(const rajni_vit_plan& p, const rajni_vit_ext* e, const rajni_vit_prefix* pre, bool nocls, const rajni_vit_attn_pool& ap) {
+  const char* who = "rajni_vit_forward_pool";
+  RAJNI_REQUIRE(e != nullptr && e->pool == RAJNI_POOL_MAP, RAJNI_ERR_INVALID,
+                "%s: ext.pool must be RAJNI_POOL_MAP with a rajni_vit_attn_pool record (%s%d)", who, e ? "ext.pool = " : "ext is NULL: pool ",
+                e ? e->pool : RAJNI_POOL_TOKEN);
+  RAJNI_REQUIRE(!p.cls_only_last_block, RAJNI_ERR_INVALID,
+                "%s: plan.cls_only_last_block with RAJNI_POOL_MAP - that opt-in never forms the rows to be pooled", who);
+  RAJNI_REQUIRE(!p.act_fp8, RAJNI_ERR_UNSUPPORTED, "%s: plan.act_fp8 is unsupported with RAJNI_POOL_MAP", who);
+  RAJNI_REQUIRE(nocls || head_row_count(pre) != 2, RAJNI_ERR_UNSUPPORTED,
+                "%s: prefix.head_rows = 2 with RAJNI_POOL_MAP - the two rows exist to feed the averaged token heads", who);
+  RAJNI_REQUIRE(!e->norm_absent, RAJNI_ERR_UNSUPPORTED,
+                "%s: ext.norm_absent with RAJNI_POOL_MAP - the pool reads norm(x), and there is no cast-only row kernel", who);
+  const char* missing = !ap.q ? "q" : !ap.kv_w ? "kv_w" : !ap.proj_w ? "proj_w" : !ap.norm_w ? "norm_w" : !ap.norm_b ? "norm_b"
+                        : !ap.fc1_w ? "fc1_w" : !ap.fc2_w ? "fc2_w" : nullptr;
+  RAJNI_REQUIRE(missing == nullptr, RAJNI_ERR_INVALID, "%s: null weight pointer (pool.%s)", who, missing ? missing : "");
+  RAJNI_REQUIRE(ap.heads > 0 && p.C > 0 && p.C % ap.heads == 0 && (p.C / ap.heads) % 8 == 0 && p.C / ap.heads >= 8 && p.C / ap.heads <= 128,
+                RAJNI_ERR_INVALID, "%s: pool.heads must divide C into head dims that are multiples of 8 in 8..128 (heads=%d C=%d)", who,
+                ap.heads, p.C);
+  RAJNI_REQUIRE(ap.hidden > 0 && ap.hidden % 64 == 0, RAJNI_ERR_INVALID,
+                "%s: pool.hidden must be a positive multiple of 64 (zero-pad the MLP width) (%d)", who, ap.hidden);
+  RAJNI_REQUIRE(ap.act == RAJNI_MLP_GELU || ap.act == RAJNI_MLP_QUICK_GELU, RAJNI_ERR_INVALID,
+                "%s: pool.act must be RAJNI_MLP_GELU or RAJNI_MLP_QUICK_GELU (%d)", who, ap.act);
+  RAJNI_REQUIRE_PLACED("rajni_vit_forward_pool: pool", {"q", ap.q, 16}, {"kv_w", ap.kv_w, 16}, {"kv_b", ap.kv_b, 16}, {"proj_w", ap.proj_w, 16},
+                       {"proj_b", ap.proj_b, 16}, {"norm_w", ap.norm_w, 16}, {"norm_b", ap.norm_b, 16}, {"fc1_w", ap.fc1_w, 16},
+                       {"fc1_b", ap.fc1_b, 16}, {"fc2_w", ap.fc2_w, 16}, {"fc2_b", ap.fc2_b, 16});
   return RAJNI_OK;
 }
 
@@ -471,6 +524,46 @@ int check_image(const rajni_vit_plan& p, const rajni_vit_prefix* pre, const rajn
   return RAJNI_OK;
 }
 
+// the attention-pool tail (rajni_hip_attnpool.h) on the final stream `cur` [B, N, C]: every launch but the pool kernel is one
+// the blocks and the head use.  w.xn, w.qkv and w.att are dead behind the last block: B * N rows of C and of 2C <= 3C fit
+int launch_pool_tail(const Fwd& f, const rajni_vit_attn_pool& ap, const PoolRows& r, const rajni_vit_ext& e, const void* cur, int N,
+                     void* logits) {
+  const rajni_vit_plan& p = f.p;
+  const int B = p.B, C = p.C, dt = p.dtype;
+  int rc = launch_layernorm(cur, C, p.norm_w, p.norm_b, f.w.xn, B * N, C, p.ln_eps, f.sf32, dt, f.s);
+  if (rc != RAJNI_OK) return rc;
+  rc = launch_linear(linear_args(dt, f.w.xn, ap.kv_w, ap.kv_b, nullptr, f.w.qkv, B * N, 2 * C, C, RAJNI_EPI_BIAS), f.s);
+  if (rc != RAJNI_OK) return rc;
+  // From here on B rows, in fp32 whatever the model dtype (fp32 copies of proj / fc1 / fc2, the fp32 GEMMs and LayerNorm of an
+  // fp32 model): each 16-bit rounding of a pooled row costs 0.2 - 0.4 % of the logit scale and there would be five of them
+  // (DESIGN.md section 1, B7), while B rows cost next to nothing.  The pooled row is rounded ONCE, where the head reads it.
+  rc = launch_attention_pool(f.w.qkv, ap.q, r.o, B, N, ap.heads, C / ap.heads, dt, f.s, 1);
+  if (rc != RAJNI_OK) return rc;
+  // y = proj(o), then y += fc2(act(fc1(norm(y)))) in place
+  const int f32 = RAJNI_F32;
+  rc = launch_linear(linear_args(f32, r.o, ap.proj_w, ap.proj_b, nullptr, r.y, B, C, C, RAJNI_EPI_BIAS), f.s);
+  if (rc != RAJNI_OK) return rc;
+  rc = launch_layernorm(r.y, C, ap.norm_w, ap.norm_b, r.n, B, C, ap.norm_eps, 0, f32, f.s);
+  if (rc != RAJNI_OK) return rc;
+  rc = launch_linear(linear_args(f32, r.n, ap.fc1_w, ap.fc1_b, nullptr, r.hid, B, ap.hidden, C,
+                                 ap.act == RAJNI_MLP_QUICK_GELU ? RAJNI_EPI_BIAS_QUICK_GELU : RAJNI_EPI_BIAS_GELU), f.s);
+  if (rc != RAJNI_OK) return rc;
+  rajni_linear_args fc2 = linear_args(f32, r.hid, ap.fc2_w, ap.fc2_b, nullptr, r.y, B, C, ap.hidden, RAJNI_EPI_BIAS_RESID);
+  fc2.resid = r.y; fc2.ldr = C;
+  rc = launch_linear(fc2, f.s);
+  if (rc != RAJNI_OK) return rc;
+  // timm forward_head: fc_norm behind the pool, or none - rajni_pool_norm's token form on [B, 1, C] fp32 rows with no norm in
+  // front: with fc_norm_w NULL it is the one rounding to the model dtype (the caller's buffer on a headless plan)
+  void* const row = headless(p) ? logits : (void*)f.w.clsn;
+  rc = launch_pool_norm(r.y, B, 1, C, RAJNI_POOL_TOKEN, nullptr, nullptr, 0.f, e.fc_norm_w, e.fc_norm_b, e.fc_norm_eps, row,
+                        dt != RAJNI_F32, dt, f.s, 1);
+  if (rc != RAJNI_OK) return rc;
+  if (headless(p)) return RAJNI_OK;
+  rajni_linear_args head = linear_args(dt, row, p.head_w, p.head_b, nullptr, logits, B, p.num_classes, C, RAJNI_EPI_BIAS);
+  head.ldc = logits_stride(p);
+  return launch_linear(head, f.s);
+}
+
 // src [B, Nf] = where each token of the stream that enters block `upto` (p.depth: the final stream) sat in the unpruned
 // sequence: the selections of the scheduled blocks in front of it (the forced one where a block has it), last block first
 int launch_source_idx_before(const rajni_vit_plan& p, int P, int upto, int32_t* src, int Nf, hipStream_t s, const rajni_vit_image* img) {
@@ -490,7 +583,7 @@ int launch_source_idx_before(const rajni_vit_plan& p, int P, int upto, int32_t* 
 // pre == nullptr (or a record with one prefix token) next to any ext
 int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre, const void* images,
                 void* logits, hipStream_t s, const rajni_vit_layers* lay = nullptr, const rajni_vit_image* img = nullptr,
-                const rajni_vit_query* qry = nullptr);
+                const rajni_vit_query* qry = nullptr, const rajni_vit_attn_pool* ap = nullptr);
 
 }  // namespace
 
@@ -573,6 +666,26 @@ extern "C" int rajni_vit_forward_query(const rajni_vit_plan* plan, const rajni_v
   return vit_forward(plan, ext, prefix, images, logits, (hipStream_t)stream, layers, image, query);
 }
 
+// ---- include/rajni_hip_attnpool.h
+extern "C" size_t rajni_vit_workspace_bytes_pool(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix, const rajni_vit_image* image,
+                                                 const rajni_vit_query* query, const rajni_vit_attn_pool* pool) {
+  const size_t base = rajni_vit_workspace_bytes_query(plan, prefix, image, query);
+  if (!pool || base == 0) return base;
+  if (pool->hidden <= 0 || pool->hidden % 64 != 0 || plan->B <= 0 || plan->C <= 0) return 0;
+  rajni_vit_plan tmp = *plan;
+  tmp.workspace = nullptr;
+  return carve_pool(tmp, *pool, base).total;
+}
+
+extern "C" int rajni_vit_forward_pool(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
+                                      const rajni_vit_layers* layers, const rajni_vit_image* image, const rajni_vit_query* query,
+                                      const rajni_vit_attn_pool* pool, const void* images, void* logits, rajni_stream_t stream) {
+  if (!pool) return rajni_vit_forward_query(plan, ext, prefix, layers, image, query, images, logits, stream);
+  const int rc = check_prefix(prefix, "rajni_vit_forward_pool", no_class_row(query));
+  if (rc != RAJNI_OK) return rc;
+  return vit_forward(plan, ext, prefix, images, logits, (hipStream_t)stream, layers, image, query, pool);
+}
+
 extern "C" void rajni_debug_set_last_block_all_rows(int on) { g_last_block_all_rows = on; }
 
 // 1 when the forward of this plan (with this ext / prefix record, either may be NULL) computes its last block for the rows the
@@ -587,13 +700,16 @@ extern "C" int rajni_debug_last_block_cls_rows(const rajni_vit_plan* plan, const
 namespace {
 
 int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre, const void* images,
-                void* logits, hipStream_t s, const rajni_vit_layers* lay, const rajni_vit_image* img, const rajni_vit_query* qry) {
+                void* logits, hipStream_t s, const rajni_vit_layers* lay, const rajni_vit_image* img, const rajni_vit_query* qry,
+                const rajni_vit_attn_pool* ap) {
   RAJNI_REQUIRE(plan && images && logits, RAJNI_ERR_INVALID, "rajni_vit_forward: null pointer");
   const rajni_vit_plan& p = *plan;
   const bool dense_last = ext != nullptr && ext->pool == RAJNI_POOL_DENSE_LAST;
   int rc = qry ? check_query(p, ext, *qry) : RAJNI_OK;   // first of all: whether there is a class row decides every count
   if (rc != RAJNI_OK) return rc;
   const bool nocls = no_class_row(qry);
+  rc = ap ? check_pool(p, ext, pre, nocls, *ap) : RAJNI_OK;
+  if (rc != RAJNI_OK) return rc;
   const int qmode = query_mode(qry);
   rc = img ? check_image(p, pre, *img, qry) : RAJNI_OK;   // every count below is against the record's grid
   if (rc != RAJNI_OK) return rc;
@@ -607,7 +723,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
   if (rc != RAJNI_OK) return rc;
   if (pre) RAJNI_REQUIRE_PLACED("rajni_vit_forward", {"reg_token", pre->reg_token, 16});
   if (ext) {
-    rc = check_ext(p, *ext);
+    rc = check_ext(p, *ext, ap != nullptr);
     if (rc != RAJNI_OK) return rc;
   }
   rc = nocls ? RAJNI_OK : check_head_rows(p, ext, pre);
@@ -618,8 +734,9 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
   rc = check_schedule(p, P, img);
   if (rc != RAJNI_OK) return rc;
   const Workspace w = carve(p, P, HR, img, qmode);
-  RAJNI_REQUIRE(p.workspace != nullptr && p.workspace_bytes >= w.total, RAJNI_ERR_INVALID,
-                "rajni_vit_forward: workspace too small (%zu < %zu)", p.workspace_bytes, w.total);
+  const PoolRows pool_rows = ap ? carve_pool(p, *ap, w.total) : PoolRows{nullptr, nullptr, nullptr, nullptr, w.total};
+  RAJNI_REQUIRE(p.workspace != nullptr && p.workspace_bytes >= pool_rows.total, RAJNI_ERR_INVALID,
+                "rajni_vit_forward: workspace too small (%zu < %zu)", p.workspace_bytes, pool_rows.total);
   const int B = p.B, C = p.C, dt = p.dtype;
   const Fwd f{p, w, (dt != RAJNI_F32 && !p.resid_bf16) ? 1 : 0, s,
               (ext && ext->mlp_act == RAJNI_MLP_QUICK_GELU) ? RAJNI_EPI_BIAS_QUICK_GELU
@@ -792,7 +909,8 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
   // (with a pooled head, fc_norm or no norm: norm on every row that is pooled -> pool -> fc_norm, one kernel)
   // a headless plan: the same launch writes the caller's buffer instead of w.clsn, and there is no head GEMM
   void* const rowout = headless(p) ? logits : (void*)w.clsn;
-  if (ext && ext->pool == RAJNI_POOL_NONE)   // every surviving token through the final norm: [B, N, C]
+  if (ap) return launch_pool_tail(f, *ap, pool_rows, *ext, cur, N, logits);   // (check_pool: ext.pool is RAJNI_POOL_MAP)
+  if (ext && ext->pool == RAJNI_POOL_NONE)  // every surviving token through the final norm: [B, N, C]
     return launch_layernorm(cur, C, p.norm_w, p.norm_b, logits, B * N, C, p.ln_eps, f.sf32, dt, s);
   if (ext && (ext->pool == RAJNI_POOL_DENSE || dense_last)) {
     // [B, P + n, C]: token j of the final stream at the row it came from, zeros elsewhere (RAJNI_POOL_DENSE_LAST: the other

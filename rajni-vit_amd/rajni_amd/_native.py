@@ -218,6 +218,27 @@ _QUERY_SIGS = {
                                         C.POINTER(VitImage), C.POINTER(VitQuery), c_void_p, c_void_p, c_void_p]),
 }
 QUERY_SYMBOLS = tuple(_QUERY_SIGS.keys())
+# include/rajni_hip_attnpool.h, additive in the same way: the attention-pool head (timm global_pool='map')
+POOL_MAP = 6                         # rajni_vit_ext.pool through rajni_vit_forward_pool with a record; 4 stays unknown
+
+
+class VitAttnPool(C.Structure):
+    """rajni_vit_attn_pool (include/rajni_hip_attnpool.h): the weights of timm's AttentionPoolLatent, beside the plan"""
+    _fields_ = [("q", c_void_p), ("kv_w", c_void_p), ("kv_b", c_void_p), ("proj_w", c_void_p), ("proj_b", c_void_p),
+                ("norm_w", c_void_p), ("norm_b", c_void_p), ("norm_eps", c_float),
+                ("fc1_w", c_void_p), ("fc1_b", c_void_p), ("fc2_w", c_void_p), ("fc2_b", c_void_p),
+                ("hidden", c_int), ("heads", c_int), ("act", c_int)]
+
+
+_ATTNPOOL_SIGS = {
+    "rajni_attention_pool": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "rajni_vit_workspace_bytes_pool": (c_size_t, [C.POINTER(VitPlan), C.POINTER(VitPrefix), C.POINTER(VitImage),
+                                                  C.POINTER(VitQuery), C.POINTER(VitAttnPool)]),
+    "rajni_vit_forward_pool": (c_int, [C.POINTER(VitPlan), C.POINTER(VitExt), C.POINTER(VitPrefix), C.POINTER(VitLayers),
+                                       C.POINTER(VitImage), C.POINTER(VitQuery), C.POINTER(VitAttnPool), c_void_p, c_void_p,
+                                       c_void_p]),
+}
+ATTNPOOL_SYMBOLS = tuple(_ATTNPOOL_SIGS.keys())
 RESAMPLE_MAX_GRID = 128     # RAJNI_RESAMPLE_MAX_GRID: grid cells per axis, source and destination
 ABI_VERSION = 8     # include/rajni_hip.h; bumped whenever a struct or an entry point changes
 _lib: Optional[C.CDLL] = None
@@ -233,7 +254,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
             f"librajni_hip.so not found at {path}. Build it with `python rajni-vit_amd/build.py` "
             "(hipcc --offload-arch=gfx950). rajni_amd has no CPU or PyTorch fallback by design.")
     lib = C.CDLL(path)
-    for name, (res, args) in list(_SIGS.items()) + list(_LAYERS_SIGS.items()) + list(_IMAGE_SIGS.items()) + list(_QUERY_SIGS.items()):
+    for name, (res, args) in (list(_SIGS.items()) + list(_LAYERS_SIGS.items()) + list(_IMAGE_SIGS.items()) + list(_QUERY_SIGS.items())
+                              + list(_ATTNPOOL_SIGS.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -239,6 +239,25 @@ def attention(qkv: torch.Tensor, keep_idx: Optional[torch.Tensor], num_heads: in
     return out
 
 
+def attention_pool(kv: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
+    """The attention of timm's AttentionPoolLatent alone (rajni_attention_pool, include/rajni_hip_attnpool.h): kv [B, N, 2C]
+    (K half, then V half, each [H][D]) in the model dtype, q [H, D] fp32 with the scale folded in -> [B, C] in kv's dtype.
+    fp32 logits, softmax and weighted sum; an image's bits do not depend on the batch."""
+    nat.require_device(kv, "kv")
+    if kv.dim() != 3 or q.dim() != 2 or kv.shape[2] != 2 * q.shape[0] * q.shape[1]:
+        raise ValueError(f"attention_pool: kv must be [B, N, 2 * H * D] and q [H, D], got {tuple(kv.shape)} and {tuple(q.shape)}")
+    if q.dtype != torch.float32:
+        raise ValueError(f"attention_pool: q must be float32 (the pre-scaled query), got {q.dtype}")
+    kv, q = _placed(kv, "kv"), _placed(q.to(kv.device), "q")
+    B, N, _ = kv.shape
+    H, D = q.shape
+    out = torch.empty((B, H * D), dtype=kv.dtype, device=kv.device)
+    with nat.device_guard(kv.device):
+        nat.check(nat.lib().rajni_attention_pool(kv.data_ptr(), q.data_ptr(), out.data_ptr(), B, N, H, D, _dt(kv),
+                                                 nat.stream_ptr(kv.device)), "rajni_attention_pool")
+    return out
+
+
 def attention_out_scale(norm1_w: torch.Tensor, norm1_b: torch.Tensor, wv: torch.Tensor, bv: Optional[torch.Tensor]) -> float:
     """out_scale of `attention_fp8` from a block's parameters (the bound of rajni_attention_fp8, include/rajni_hip.h):
     (1.0625 * (sqrt(C) * max|gamma1| + ||beta1||_2) * max_c ||Wv[c]||_2 + max|bv|) / 448, evaluated in fp32.

@@ -79,9 +79,10 @@ def create_base(args):
         model = timm.create_model(args.model, pretrained=args.pretrained)
         source = "timm"
     except ImportError:
-        if args.model not in ts.CONFIGS and args.model not in ts.SWIGLU_CONFIGS and args.model not in ts.NOCLASS_CONFIGS:
+        tables = (ts.CONFIGS, ts.SWIGLU_CONFIGS, ts.NOCLASS_CONFIGS, ts.MAP_CONFIGS)
+        if not any(args.model in t for t in tables):
             raise SystemExit(f"timm is not installed and '{args.model}' is not a built-in config "
-                             f"{sorted(ts.CONFIGS) + sorted(ts.SWIGLU_CONFIGS) + sorted(ts.NOCLASS_CONFIGS)}")
+                             f"{[n for t in tables for n in sorted(t)]}")
         model = ts.create_model(args.model, seed=args.seed)
         source = "timm-shaped stand-in, seeded random weights"
     if args.weights:

@@ -54,10 +54,11 @@ class ViTConfig:
     # config above this line are unchanged)
     qk_norm: bool = False                 # LayerNorm(head_dim) on q and k in every block
     pre_norm: bool = False                # norm_pre after the pos-embed (CLIP-derived ViTs)
-    global_pool: str = "token"            # 'token' (x[:, 0]) or 'avg' (mean of x[:, 1:])
+    global_pool: str = "token"            # 'token' (x[:, 0]), 'avg' (mean of x[:, 1:]) or 'map' (an AttentionPoolLatent head
+                                          # over every row: the SigLIP towers)
     fc_norm: Optional[bool] = None        # None = timm's default: an fc_norm (and no final norm) iff global_pool == 'avg'
     class_token: bool = True              # timm class_token: False = no class row at all (cls_token is None, the prefix tokens
-                                          # are the registers alone; needs global_pool='avg' and no distillation, as timm
+                                          # are the registers alone; needs global_pool='avg' or 'map' and no distillation, as timm
                                           # asserts).  (In front of mlp, distilled, act and reg_tokens, which existing tests
                                           # hold to be the last four fields)
     mlp: str = "mlp"                      # the block's MLP: "mlp" (fc1 -> act -> fc2), "swiglu_packed" (timm GluMlp with
@@ -81,7 +82,7 @@ class ViTConfig:
         if self.mlp not in ("mlp", "swiglu_packed", "swiglu"):
             raise ValueError(f"ViTConfig: mlp must be 'mlp', 'swiglu_packed' or 'swiglu', got {self.mlp!r}")
         if not self.class_token and self.global_pool == "token":
-            raise ValueError("ViTConfig: class_token=False needs global_pool='avg' (timm asserts it: a token head has no row to read)")
+            raise ValueError("ViTConfig: class_token=False needs global_pool='avg' or 'map' (timm asserts it: a token head has no row to read)")
         if not self.class_token and self.distilled:
             raise ValueError("ViTConfig: class_token=False together with distilled is not a timm model")
 
@@ -252,12 +253,40 @@ NOCLASS_CONFIGS: Dict[str, ViTConfig] = {
 }
 
 
+# Models with an attention-pool head (timm global_pool='map': AttentionPoolLatent over every row of norm(x)), in a table of
+# their own for the same reason.
+MAP_CONFIGS: Dict[str, ViTConfig] = {
+    # micro models (not timm names): the SigLIP layout (no class token, 16 tokens); a class token in front of the pool (17
+    # tokens, the pool reads the class row too); head dim 80 with 4 registers; 625 tokens (more than one pass of the pool
+    # kernel's token slots, and the tiled score kernels); the fp8-capable dims
+    "vit_micro_map_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, num_classes=10,
+                                          global_pool="map", class_token=False),
+    "vit_micro_cls_map_patch16_64": ViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, num_classes=10,
+                                              global_pool="map"),
+    "vit_micro_reg4_map_d80_patch16_64": ViTConfig(img_size=64, embed_dim=320, depth=4, num_heads=4, num_classes=10,
+                                                   global_pool="map", class_token=False, reg_tokens=4),
+    "vit_micro_map_patch16_400": ViTConfig(img_size=400, embed_dim=128, depth=4, num_heads=2, num_classes=10,
+                                           global_pool="map", class_token=False),
+    "vit_micro512_map_patch16_64": ViTConfig(img_size=64, embed_dim=512, depth=4, num_heads=8, num_classes=10,
+                                             global_pool="map", class_token=False),
+    # The dimensions of two SigLIP image towers.  timm is not importable where this was written: both entries were WRITTEN FROM
+    # MEMORY AND ARE UNVERIFIED (width, depth, heads, MLP width and eps may each be off; the checkpoints ship with
+    # num_classes=0, here they keep a 1000-way head like every other real-size entry); no test depends on their being exact -
+    # they exist to give the cost tools a real-size shape.  so400m: 1152 wide, 27 blocks, 16 heads of 72, MLP width 4304
+    # (not whole 64-wide K steps: zero-padded to 4352)
+    "vit_base_patch16_siglip_224": ViTConfig(embed_dim=768, depth=12, num_heads=12, global_pool="map", class_token=False),
+    "vit_so400m_patch14_siglip_224": ViTConfig(patch_size=14, embed_dim=1152, depth=27, num_heads=16, mlp_ratio=4304 / 1152,
+                                               global_pool="map", class_token=False),
+}
+
+
 def config_of(name: str) -> ViTConfig:
-    """the built-in config of that name, from CONFIGS, SWIGLU_CONFIGS or NOCLASS_CONFIGS"""
-    for table in (CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS):
+    """the built-in config of that name, from CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS or MAP_CONFIGS"""
+    tables = (CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS, MAP_CONFIGS)
+    for table in tables:
         if name in table:
             return table[name]
-    raise KeyError(f"'{name}' is not a built-in config {sorted(CONFIGS) + sorted(SWIGLU_CONFIGS) + sorted(NOCLASS_CONFIGS)}")
+    raise KeyError(f"'{name}' is not a built-in config {[n for t in tables for n in sorted(t)]}")
 
 
 class PatchEmbed(nn.Module):
@@ -374,6 +403,43 @@ def make_mlp(cfg: "ViTConfig") -> nn.Module:
     return Mlp(cfg.embed_dim, cfg.hidden_dim, cfg.act)
 
 
+class AttentionPoolLatent(nn.Module):
+    """timm `AttentionPoolLatent` as `VisionTransformer(global_pool='map')` builds it (latent_len=1, no pool pos_embed, no
+    q/k-norm, pool='token'): ONE learned query attends over every row of x, then proj and a residual MLP.  Written from memory of
+    timm 1.x (timm is not importable here) - attribute names and forward are the contract the wrapper recognises."""
+
+    def __init__(self, dim: int, num_heads: int, mlp_ratio: float = 4.0, ln_eps: float = 1e-6, act: str = "gelu"):
+        super().__init__()
+        assert dim % num_heads == 0
+        self.num_heads = num_heads
+        self.head_dim = dim // num_heads
+        self.scale = self.head_dim ** -0.5
+        self.pool = "token"
+        self.latent_dim = dim
+        self.latent_len = 1
+        self.latent = nn.Parameter(torch.zeros(1, 1, dim))
+        self.pos_embed = None
+        self.q = nn.Linear(dim, dim)
+        self.kv = nn.Linear(dim, dim * 2)
+        self.q_norm = nn.Identity()
+        self.k_norm = nn.Identity()
+        self.proj = nn.Linear(dim, dim)
+        self.proj_drop = nn.Dropout(0.0)
+        self.norm = nn.LayerNorm(dim, eps=ln_eps)
+        self.mlp = Mlp(dim, int(dim * mlp_ratio), act)
+
+    def forward(self, x):
+        B, N, C = x.shape
+        q = self.q(self.latent.expand(B, -1, -1)).reshape(B, self.latent_len, self.num_heads, self.head_dim).transpose(1, 2)
+        kv = self.kv(x).reshape(B, N, 2, self.num_heads, self.head_dim).permute(2, 0, 3, 1, 4)
+        k, v = kv.unbind(0)
+        q, k = self.q_norm(q), self.k_norm(k)
+        x = F.scaled_dot_product_attention(q, k, v)
+        x = self.proj_drop(self.proj(x.transpose(1, 2).reshape(B, self.latent_len, C)))
+        x = x + self.mlp(self.norm(x))
+        return x[:, 0]      # pool == 'token'
+
+
 class Block(nn.Module):
     def __init__(self, cfg: ViTConfig):
         super().__init__()
@@ -413,9 +479,12 @@ class VisionTransformer(nn.Module):
         n_pos = cfg.num_patches if cfg.no_embed_class else cfg.num_patches + cfg.num_prefix_tokens
         self.pos_embed = nn.Parameter(torch.zeros(1, n_pos, cfg.embed_dim))
         self.pos_drop = nn.Dropout(0.0)
-        if cfg.global_pool not in ("token", "avg"):
-            raise ValueError(f"global_pool must be 'token' or 'avg', got {cfg.global_pool!r}")
+        if cfg.global_pool not in ("token", "avg", "map"):
+            raise ValueError(f"global_pool must be 'token', 'avg' or 'map', got {cfg.global_pool!r}")
         self.global_pool = cfg.global_pool
+        # timm: an attn_pool attribute on every model, None unless global_pool == 'map'
+        self.attn_pool = (AttentionPoolLatent(cfg.embed_dim, cfg.num_heads, cfg.mlp_ratio, cfg.ln_eps, cfg.act)
+                          if cfg.global_pool == "map" else None)
         self.norm_pre = nn.LayerNorm(cfg.embed_dim, eps=cfg.ln_eps) if cfg.pre_norm else nn.Identity()
         self.blocks = nn.Sequential(*[Block(cfg) for _ in range(cfg.depth)])
         # timm: the final norm moves behind the pooling (fc_norm) when fc_norm is in use
@@ -454,7 +523,10 @@ class VisionTransformer(nn.Module):
             if self.distilled_training and self.training and not torch.jit.is_scripting():
                 return x, x_dist
             return (x + x_dist) / 2
-        x = x[:, self.num_prefix_tokens:].mean(dim=1) if self.global_pool == "avg" else x[:, 0]
+        if self.attn_pool is not None:      # timm forward_head: the pool reads every row, prefix rows included
+            x = self.attn_pool(x)
+        else:
+            x = x[:, self.num_prefix_tokens:].mean(dim=1) if self.global_pool == "avg" else x[:, 0]
         return self.head(self.head_drop(self.fc_norm(x)))
 
 
@@ -534,6 +606,17 @@ def synth_state_dict(cfg: ViTConfig, seed: int = 0, std: float = 0.02,
         sd["dist_token"] = nrm(1, 1, C)
         sd["head_dist.weight"] = nrm(cfg.num_classes, C)
         sd["head_dist.bias"] = nrm(cfg.num_classes, s=bias_std) if bias_std else np.zeros(cfg.num_classes, np.float32)
+    if cfg.global_pool == "map":      # after every other draw: the attention pool (timm AttentionPoolLatent)
+        p = "attn_pool."
+        sd[p + "latent"] = nrm(1, 1, C, s=C ** -0.5)      # timm: trunc_normal_(std=latent_dim ** -0.5)
+        for name, rows, cols in (("q", C, C), ("kv", 2 * C, C), ("proj", C, C)):
+            sd[p + name + ".weight"] = nrm(rows, cols)
+            sd[p + name + ".bias"] = nrm(rows, s=bias_std) if bias_std else np.zeros(rows, np.float32)
+        ln(p + "norm", C)
+        sd[p + "mlp.fc1.weight"] = nrm(Hd, C)
+        sd[p + "mlp.fc1.bias"] = nrm(Hd, s=bias_std) if bias_std else np.zeros(Hd, np.float32)
+        sd[p + "mlp.fc2.weight"] = nrm(C, Hd)
+        sd[p + "mlp.fc2.bias"] = nrm(C, s=bias_std) if bias_std else np.zeros(C, np.float32)
     return sd
 
 

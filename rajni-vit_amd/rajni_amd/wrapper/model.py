@@ -18,7 +18,10 @@ one forward, each on that unpruned grid; and `set_dynamic_img_size(True)` (timm'
 patch size divides, the position embedding resampled to the input's token grid as timm's resample_abs_pos_embed does; and
 models WITHOUT a class token (timm `class_token=False, global_pool='avg'`: the `*_gap_*` checkpoints, with or without
 registers), which the reference cannot run at all: their importance query is the mean of the query rows
-(`set_importance_query`, include/rajni_hip_query.h - this project's own rule), selectable on class-token models too.
+(`set_importance_query`, include/rajni_hip_query.h - this project's own rule), selectable on class-token models too; and
+attention-pool heads (timm `global_pool='map'`, `attn_pool` = AttentionPoolLatent: the SigLIP image towers, with or without a
+class token): one learned query over every token that survives the last block, then proj and a residual MLP on B rows
+(include/rajni_hip_attnpool.h; `attn_pool_module` holds the pool to its contract).
 
 Not kept: the Python per-block loop.  `forward` builds (once per batch shape) a `rajni_vit_plan`
 - packed weights, workspace, per-stage index buffers - and calls `rajni_vit_forward`, which enqueues
@@ -159,8 +162,8 @@ def _num_prefix_without_class_token(m: nn.Module) -> int:
         raise NotImplementedError(f"{why}: pos_embed has {m.pos_embed.shape[-2]} rows; with {R} register tokens and {n_patches} "
                                   f"patches it must have {n_patches} (no_embed_class) or {n_patches + R}")
     pool = getattr(m, "global_pool", "token")
-    if pool != "avg" and not isinstance(getattr(m, "head", None), nn.Identity):
-        raise NotImplementedError(f"{why} and global_pool={pool!r}: without a class row the head must pool with 'avg' "
+    if pool not in ("avg", "map") and not isinstance(getattr(m, "head", None), nn.Identity):
+        raise NotImplementedError(f"{why} and global_pool={pool!r}: without a class row the head must pool with 'avg' or 'map' "
                                   "(or be nn.Identity)")
     return R
 
@@ -270,6 +273,69 @@ def gated_fc1(mlp: nn.Module, form: str):
     first, second = (w[:h], None if b is None else b[:h]), (w[h:], None if b is None else b[h:])
     g, v = (second, first) if getattr(mlp, "gate_last", False) else (first, second)
     return g[0], v[0], g[1], v[1]
+
+
+def attn_pool_module(m: nn.Module) -> Optional[nn.Module]:
+    """The model's attention pool (timm `global_pool='map'`: `attn_pool`, an AttentionPoolLatent) or None for every other
+    head.  Recognised by structure, not by class name: `latent` [1, 1, C], Linear `q` (C -> C), `kv` (C -> 2C) and `proj`
+    (C -> C), `num_heads` dividing C with `scale` = head_dim ** -0.5, `latent_len == 1`, no pool `pos_embed`, Identity
+    `q_norm` / `k_norm`, an affine LayerNorm `norm` over C and a plain `mlp` (fc1 -> act -> fc2) whose act classify_mlp_act
+    accepts.  (The contract is written from memory of timm 1.x - include/rajni_hip_attnpool.h.)  Raises NotImplementedError
+    naming `global_pool` for 'map' without a pool, and naming `attn_pool` for a pool beside another global_pool or one that is
+    not this contract."""
+    pool_kind = getattr(m, "global_pool", "token")
+    ap = getattr(m, "attn_pool", None)
+    if ap is None:
+        if pool_kind == "map":
+            raise NotImplementedError("RAJNIViTWrapper: global_pool='map' needs the model's attn_pool (timm AttentionPoolLatent); "
+                                      "it has none")
+        return None
+    if pool_kind != "map":
+        raise NotImplementedError(f"RAJNIViTWrapper: attn_pool beside global_pool={pool_kind!r} is not supported (an attention "
+                                  "pool is the head of global_pool='map')")
+    why = "RAJNIViTWrapper: attn_pool is not timm's AttentionPoolLatent as global_pool='map' builds it"
+    Cdim = m.pos_embed.shape[-1]
+    latent = getattr(ap, "latent", None)
+    lin = {name: getattr(ap, name, None) for name in ("q", "kv", "proj")}
+    if not isinstance(latent, torch.Tensor) or any(not isinstance(v, nn.Linear) for v in lin.values()):
+        raise NotImplementedError(f"{why}: it needs `latent` and Linear `q`, `kv` and `proj`")
+    if int(getattr(ap, "latent_len", 1)) != 1 or tuple(latent.shape) != (1, 1, Cdim):
+        raise NotImplementedError(f"{why}: latent_len > 1 (latent {tuple(latent.shape)}) is not supported - one query row, "
+                                  f"latent [1, 1, {Cdim}]")
+    if getattr(ap, "pos_embed", None) is not None:
+        raise NotImplementedError(f"{why}: a position embedding inside the pool (attn_pool.pos_embed) is not supported")
+    for name in ("q_norm", "k_norm"):
+        mod = getattr(ap, name, None)
+        if mod is not None and not isinstance(mod, nn.Identity):
+            raise NotImplementedError(f"{why}: attn_pool.{name} ({type(mod).__name__}) is not supported - the pool's q/k-norm "
+                                      "must be nn.Identity")
+    for name, rows in (("q", Cdim), ("kv", 2 * Cdim), ("proj", Cdim)):
+        if tuple(lin[name].weight.shape) != (rows, Cdim):
+            raise NotImplementedError(f"{why}: attn_pool.{name} must be Linear({Cdim}, {rows}), got weight "
+                                      f"{tuple(lin[name].weight.shape)}")
+    heads = getattr(ap, "num_heads", None)
+    if not isinstance(heads, int) or heads < 1 or Cdim % heads or (Cdim // heads) % 8 or not 8 <= Cdim // heads <= 128:
+        raise NotImplementedError(f"{why}: attn_pool.num_heads = {heads!r} must divide {Cdim} into head dims that are multiples "
+                                  "of 8 in 8..128")
+    scale = getattr(ap, "scale", None)
+    if scale is None or abs(float(scale) - (Cdim // heads) ** -0.5) > 1e-6 * (Cdim // heads) ** -0.5:
+        raise NotImplementedError(f"{why}: attn_pool.scale = {scale!r} must be head_dim ** -0.5")
+    if getattr(ap, "pool", "token") != "token":
+        raise NotImplementedError(f"{why}: attn_pool.pool = {ap.pool!r} is not supported ('token')")
+    norm = getattr(ap, "norm", None)
+    if not isinstance(norm, nn.LayerNorm) or norm.weight is None or tuple(norm.normalized_shape) != (Cdim,):
+        raise NotImplementedError(f"{why}: attn_pool.norm must be an affine nn.LayerNorm over the embed dim")
+    mlp = getattr(ap, "mlp", None)
+    fc1, fc2 = getattr(mlp, "fc1", None), getattr(mlp, "fc2", None)
+    mlp_norm = getattr(mlp, "norm", None)
+    if (not isinstance(fc1, nn.Linear) or not isinstance(fc2, nn.Linear) or fc1.in_features != Cdim or fc2.out_features != Cdim
+            or fc1.out_features != fc2.in_features or (mlp_norm is not None and not isinstance(mlp_norm, nn.Identity))):
+        raise NotImplementedError(f"{why}: attn_pool.mlp must be a plain Mlp (fc1 -> act -> fc2, no norm, not gated)")
+    try:
+        classify_mlp_act(getattr(mlp, "act", None))
+    except NotImplementedError as e:
+        raise NotImplementedError(f"{why}: attn_pool.{e}") from None
+    return ap
 
 
 class RAJNIViTWrapper(nn.Module):
@@ -439,6 +505,9 @@ class RAJNIViTWrapper(nn.Module):
         if fmt == "fp8_mfma" and isinstance(getattr(self.m, "head", None), nn.Identity):
             raise NotImplementedError('set_weight_format("fp8_mfma"): not supported on a headless model (head = nn.Identity); '
                                       '"fp8" weights work')
+        if fmt == "fp8_mfma" and getattr(self.m, "global_pool", "token") == "map":
+            raise NotImplementedError('set_weight_format("fp8_mfma"): not supported on a model with an attention pool '
+                                      '(global_pool=\'map\'); "fp8" weights work')
         if fmt == "fp8_mfma" and self._mlp_act_or_none() == "quick_gelu":
             raise NotImplementedError('set_weight_format("fp8_mfma"): the model\'s MLPs use QuickGELU; the fp8 x fp8 FC1 epilogue '
                                       'and its hidden-activation bound are exact GELU only ("fp8" weights work)')
@@ -492,6 +561,9 @@ class RAJNIViTWrapper(nn.Module):
         if on and self._pool_kind() == "avg":
             raise ValueError("set_last_block_cls_only: the model pools with global_pool='avg'; the CLS-only last block never "
                              "forms the rows to be averaged")
+        if on and self._pool_kind() == "map":
+            raise ValueError("set_last_block_cls_only: the model pools with global_pool='map'; the CLS-only last block never "
+                             "forms the rows the attention pool reads")
         if bool(on) != self._cls_only_last:
             self._cls_only_last = bool(on)
             self._drop_plans()
@@ -514,10 +586,11 @@ class RAJNIViTWrapper(nn.Module):
 
     # ------------------------------------------------------------------------------------------
     def _pool_kind(self) -> str:
-        """'token' or 'avg': `base_model.global_pool` when the attribute exists, else 'token'."""
+        """'token', 'avg' or 'map': `base_model.global_pool` when the attribute exists, else 'token'.  ('map' is the attention
+        pool; `attn_pool_module` holds the model's `attn_pool` to its contract.)"""
         pool = getattr(self.m, "global_pool", "token")
-        if pool not in ("token", "avg"):
-            raise NotImplementedError(f"RAJNIViTWrapper: global_pool={pool!r} is not supported ('token' or 'avg')")
+        if pool not in ("token", "avg", "map"):
+            raise NotImplementedError(f"RAJNIViTWrapper: global_pool={pool!r} is not supported ('token', 'avg' or 'map')")
         return pool
 
     def _is_distilled(self) -> bool:
@@ -592,8 +665,18 @@ class RAJNIViTWrapper(nn.Module):
                 raise NotImplementedError(f"block {i}: heads/scale differ between blocks")
         # timm's head: norm -> pool -> fc_norm -> head, `norm` and `fc_norm` each an affine LayerNorm or Identity
         desc["pool"] = self._pool_kind()
-        if getattr(m, "attn_pool", None) is not None:
-            raise NotImplementedError("RAJNIViTWrapper: attn_pool (global_pool='map') is not supported")
+        # the attention pool of global_pool='map' (None for every other head): its heads, its MLP's width and activation
+        ap = attn_pool_module(m)
+        if ap is not None:
+            if self._cls_only_last:
+                raise ValueError("global_pool='map' with set_last_block_cls_only(True): that opt-in never forms the rows the "
+                                 "attention pool reads")
+            if self._weight_format == "fp8_mfma":
+                raise NotImplementedError('weight format "fp8_mfma" on a model with an attention pool (global_pool=\'map\') is '
+                                          'not supported; "fp8" weights work')
+            hid = ap.mlp.fc2.in_features
+            desc["attn_pool"] = dict(heads=int(ap.num_heads), hidden=hid, hidden_pad=(hid + 63) // 64 * 64,
+                                     act=classify_mlp_act(ap.mlp.act), eps=float(ap.norm.eps))
         # prefix tokens: the class token plus timm's register tokens (never pruned, never ranked; 'avg' pools behind them)
         desc["num_prefix"] = num_prefix
         desc["class_token"] = has_cls
@@ -613,6 +696,10 @@ class RAJNIViTWrapper(nn.Module):
         if not desc["norm"] and not desc["fc_norm"]:
             raise NotImplementedError("RAJNIViTWrapper: base_model.norm must be nn.LayerNorm with the blocks' eps "
                                       "(nn.Identity only together with an fc_norm)")
+        if desc["pool"] == "map" and not desc["norm"]:
+            raise NotImplementedError("RAJNIViTWrapper: global_pool='map' on a model whose norm is nn.Identity (timm fc_norm=True "
+                                      "moves the final norm behind the pool): the attention pool then reads the un-normalised "
+                                      "stream, which has no native row kernel yet")
         norm_pre = getattr(m, "norm_pre", None)
         desc["norm_pre"] = norm_pre is not None and not isinstance(norm_pre, nn.Identity)
         for name, mod, on in (("fc_norm", fc_norm, desc["fc_norm"]), ("norm_pre", norm_pre, desc["norm_pre"])):
@@ -714,6 +801,26 @@ class RAJNIViTWrapper(nn.Module):
         else:
             W["head_w"] = pw(m.head.weight)
             W["head_b"] = pv(m.head.bias) if m.head.bias is not None else zeros(desc["num_classes"])
+        if "attn_pool" in desc:
+            # the attention pool (rajni_vit_attn_pool), never e4m3 whatever the block weights' format is - like the head.  kv runs
+            # on all surviving rows and is packed in the model dtype; proj / fc1 / fc2 run on B rows in fp32 (the 16-bit roundings
+            # of a pooled row cost 0.2 - 0.4 % of the logit scale each): fp32 copies of the values the model dtype holds.
+            # Its query does not depend on the image: q = q_lin(latent) * scale, once per pack, fp32 from the same values.
+            # An MLP width that is not whole 64-wide K steps is zero-padded as the blocks' is.
+            ap, pd = m.attn_pool, desc["attn_pool"]
+            f32 = lambda t: t.detach().to(device=device, dtype=dtype).to(torch.float32)
+            pw32 = lambda w_, **kw: ops.pack_weight(f32(w_), torch.float32, device, **kw)
+            qv = f32(ap.latent).reshape(1, desc["C"]) @ f32(ap.q.weight).t()
+            if ap.q.bias is not None:
+                qv = qv + f32(ap.q.bias)
+            hid, hpad = pd["hidden"], pd["hidden_pad"]
+            fc1_b = pv(ap.mlp.fc1.bias) if ap.mlp.fc1.bias is not None else zeros(hid)
+            W["attn_pool"] = dict(
+                q=(qv * float(ap.scale)).reshape(pd["heads"], desc["C"] // pd["heads"]).contiguous(),
+                kv_w=pw(ap.kv.weight), kv_b=pv(ap.kv.bias), proj_w=pw32(ap.proj.weight), proj_b=pv(ap.proj.bias),
+                norm_w=pv(ap.norm.weight), norm_b=pv(ap.norm.bias) if ap.norm.bias is not None else zeros(desc["C"]),
+                fc1_w=pw32(ap.mlp.fc1.weight), fc1_b=torch.cat([fc1_b, zeros(hpad - hid)]) if hpad != hid else fc1_b,
+                fc2_w=pw32(ap.mlp.fc2.weight, k_multiple=64), fc2_b=pv(ap.mlp.fc2.bias))
         blocks = []
         for blk in self.blocks:
             a = blk.attn
@@ -900,7 +1007,24 @@ class RAJNIViTWrapper(nn.Module):
         img = None
         if Hh != Wd:        # the image record beside the plan (rajni_vit_image); None: a square input, the entry points as ever
             img = nat.VitImage(Hh, Wd)
-        if qry is not None:
+        apr = None
+        if d["pool"] == "map" and not features:   # the attention-pool record beside the plan (rajni_vit_attn_pool); the feature
+            pw_, pd = W["attn_pool"], d["attn_pool"]   # outputs end at norm(x), in front of the pool, and carry none
+            apr = nat.VitAttnPool()
+            for name in ("q", "kv_w", "kv_b", "proj_w", "proj_b", "norm_w", "norm_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b"):
+                setattr(apr, name, nat.ptr(pw_[name]))
+            apr.norm_eps, apr.hidden, apr.heads = pd["eps"], pd["hidden_pad"], pd["heads"]
+            apr.act = nat.MLP_QUICK_GELU if pd["act"] == "quick_gelu" else nat.MLP_GELU
+        if apr is not None:
+            ref = lambda rec: C.byref(rec) if rec is not None else None
+            nbytes = nat.lib().rajni_vit_workspace_bytes_pool(C.byref(plan), ref(pre), ref(img), ref(qry), C.byref(apr))
+            if nbytes == 0:       # a record is refused: say why (the forward's own refusal, nothing is launched)
+                dry = nat.VitExt()
+                dry.pool = nat.POOL_MAP
+                nat.check(nat.lib().rajni_vit_forward_pool(C.byref(plan), C.byref(dry), ref(pre), None, ref(img), ref(qry),
+                                                           C.byref(apr), 16, 16, None), "rajni_vit_forward_pool")
+                raise nat.NativeError("rajni_vit_workspace_bytes_pool refused the plan")
+        elif qry is not None:
             ref = lambda rec: C.byref(rec) if rec is not None else None
             nbytes = nat.lib().rajni_vit_workspace_bytes_query(C.byref(plan), ref(pre), ref(img), C.byref(qry))
             if nbytes == 0:       # a record is refused: say why (the forward's own refusal, nothing is launched)
@@ -930,7 +1054,7 @@ class RAJNIViTWrapper(nn.Module):
             ext.norm_pre_w, ext.norm_pre_b, ext.norm_pre_eps = nat.ptr(W["norm_pre_w"]), nat.ptr(W["norm_pre_b"]), W["norm_pre_eps"]
             ext.fc_norm_w, ext.fc_norm_b, ext.fc_norm_eps = nat.ptr(W["fc_norm_w"]), nat.ptr(W["fc_norm_b"]), W["fc_norm_eps"]
             ext.norm_absent = int(not d["norm"])
-            ext.pool = nat.POOL_AVG if d["pool"] == "avg" else nat.POOL_TOKEN
+            ext.pool = {"avg": nat.POOL_AVG, "map": nat.POOL_MAP}.get(d["pool"], nat.POOL_TOKEN)
             if features:      # timm forward_features ends at norm(x): no pool, no fc_norm
                 ext.pool = {"tokens": nat.POOL_NONE, "dense": nat.POOL_DENSE, "dense_last": nat.POOL_DENSE_LAST}[mode]
                 ext.fc_norm_w = ext.fc_norm_b = None
@@ -948,7 +1072,9 @@ class RAJNIViTWrapper(nn.Module):
         # the layers record behind those)
         # (the image record and the position rows the plan points to, with the grid, last)
         # (the query record behind the grid: index 4 of the last element)
-        self._plan = (key, plan, (blocks, tc, ws, W, ext, qk, pre), bufs, counts, full_mode, out_shape, layers, (img, pos, gh, gw, qry))
+        # (the attention-pool record behind the query record: index 5 of the last element)
+        self._plan = (key, plan, (blocks, tc, ws, W, ext, qk, pre), bufs, counts, full_mode, out_shape, layers,
+                      (img, pos, gh, gw, qry, apr))
         if len(self._plans) >= 4:     # workspaces are large: keep only a few batch shapes alive
             self._plans.pop(next(iter(self._plans)))
         self._plans[key] = self._plan
@@ -1105,6 +1231,17 @@ class RAJNIViTWrapper(nn.Module):
                 out = torch.empty(entry[6], dtype=dtype, device=x.device)
                 ext, pre = entry[2][4], entry[2][6]
                 ref = lambda rec: C.byref(rec) if rec is not None else None
+                if entry[8][5] is not None:   # an attention-pool record (global_pool='map'): every record through rajni_vit_forward_pool
+                    lay = slabs = None
+                    if entry[7] is not None:
+                        cap_arr, lnorm, lfill, slab_shape = entry[7]
+                        slabs = torch.empty(slab_shape, dtype=dtype, device=x.device)
+                        lay = nat.VitLayers()
+                        lay.n, lay.blocks, lay.norm, lay.fill, lay.out, lay.slab_stride = len(cap_arr), cap_arr, lnorm, lfill, slabs.data_ptr(), 0
+                    nat.check(nat.lib().rajni_vit_forward_pool(C.byref(plan), ref(ext), ref(pre), ref(lay), ref(entry[8][0]),
+                                                               ref(entry[8][4]), C.byref(entry[8][5]), x.data_ptr(), out.data_ptr(),
+                                                               nat.stream_ptr(x.device)), "rajni_vit_forward_pool")
+                    return out if lay is None else (out, slabs)
                 if entry[8][4] is not None:   # a query record (the mean query, or no class row): every record through rajni_vit_forward_query
                     lay = slabs = None
                     if entry[7] is not None:
