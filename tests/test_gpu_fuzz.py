@@ -36,7 +36,9 @@ def test_forward_fuzz_random_models_and_schedules_against_oracle():
     """Random small timm-shaped models (width, depth, heads, LayerScale, no_embed_class, image size), random
     pruning schedules (ratios, update flags, consecutive stages) and batch sizes: the whole HIP forward against
     the oracle (the numpy restatement of the reference) run with the device's selections injected, plus the
-    exact selection rule and the token counts."""
+    exact selection rule and the token counts.  These are the options of the reference's own model; the options added since
+    (registers, distillation, no class token, QuickGELU, SwiGLU, qk-norm, pre-norm, the pooled heads, any input size, the
+    feature outputs, dtypes and weight formats) are crossed pairwise in tests/test_gpu_combined_forward.py."""
     import numpy as np
     import torch
     import rajni_amd
