@@ -80,7 +80,9 @@ int rajni_attention_pool(const void* kv, const float* q, void* out, int B, int N
  * rows to be pooled), plan.act_fp8 and prefix.head_rows == 2 (RAJNI_ERR_UNSUPPORTED), a NULL weight, pool.hidden,
  * pool.heads, pool.act out of range (RAJNI_ERR_INVALID).
  * The workspace is rajni_vit_workspace_bytes_pool(...) bytes: rajni_vit_workspace_bytes_query's (unchanged, in front) plus
- * the fp32 B-row intermediates of the pool ([B, C] three times and [B, hidden]); pool == NULL returns exactly rajni_vit_workspace_bytes_query's size.  0 = refused.
+ * the fp32 B-row intermediates of the pool ([B, C] three times and [B, hidden]); pool == NULL returns exactly rajni_vit_workspace_bytes_query's size.  0 = refused:
+ * the size functions run the forward's own checks of the records that size the workspace (prefix, image, query, pool.hidden)
+ * and the forward's own carve, so a non-zero size is the byte count the forward asks for.
  * Placement: as rajni_vit_forward_query, and the record's pointers 16. */
 size_t rajni_vit_workspace_bytes_pool(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix, const rajni_vit_image* image,
                                       const rajni_vit_query* query, const rajni_vit_attn_pool* pool);

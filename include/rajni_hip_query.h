@@ -83,6 +83,7 @@ int rajni_patch_embed_query(const void* images, const void* w, const float* bias
  * that entry point and the same bits.  {1, RAJNI_QUERY_MEAN}: the same forward with the mean query in every scoring block.
  * {0, RAJNI_QUERY_MEAN}: the sequence without a class row (above); n0 = (height / patch) * (width / patch) + R, and every count
  * the other records speak of is against that n0 and P = R.  ext, prefix, layers and image may each be NULL.
+ * rajni_vit_workspace_bytes_query returns 0 for a record the forward refuses (rajni_last_error then holds that refusal).
  * Placement: as rajni_vit_forward_image (rajni_vit_query holds no pointer). */
 size_t rajni_vit_workspace_bytes_query(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix, const rajni_vit_image* image,
                                        const rajni_vit_query* query);

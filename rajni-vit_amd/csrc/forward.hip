@@ -1,49 +1,38 @@
 // Whole-forward orchestration: RAJNIViTWrapper.forward (reference model.py:30-69) as one host call
 // that enqueues every kernel on the caller's stream.  Token counts are data independent,
-// so all shapes are known up front: no allocation, no host sync, no device->host traffic inside, and
-// every refusal that depends on the plan alone (check_plan, check_placement, check_ext, check_schedule) comes before the first launch.
+// so all shapes are known up front: no allocation, no host sync, no device->host traffic inside.
+//
+// A call is a plan and up to six optional records.  make_spec resolves them once into a Spec, and everything below takes that
+// Spec: check_all (every refusal, before the first launch), carve (the workspace), the block loop and the tails.
 //
 // Per block:  LN1 -> QKV GEMM (all N tokens) -> an attention form -> the tail (launch_tail):
 // proj GEMM whose epilogue gathers the residual row, applies LayerScale and adds -> LN2 -> FC1 GEMM + GELU ->
 // FC2 GEMM + LayerScale + residual (in place).  The attention form is one of
 //   [score+select] -> attention on the kept tokens (gather fused into its loads), all rows;
 //   the first query tile of that attention, tail on the B CLS rows (last block, the same bits: last_block_cls_rows);
-//   the same tile, its rows 0 and 1 gathered dense, tail on those 2B rows (last block of a distilled model, head_rows == 2);
+//   the same tile, its rows 0 and 1 gathered dense, tail on those 2B rows (last block of a distilled model, HR == 2);
 //   the CLS-query kernel, tail on the B CLS rows (last block, the cls_only_last_block opt-in);
 // and hands the tail an AttnRows record.  The reference's three gathers (qkv, scores, x) never exist as kernels here.
-//
 // With plan.act_fp8 (opt-in): LN1 / LN2 emit per-row-scaled e4m3 rows, QKV / FC1 / FC2 run on the fp8 matrix pipe
 // (gemm_f8.h) and FC1's GELU epilogue re-quantises the hidden activations; where attention emits e4m3 rows
 // (attn_emits_e4m3) proj runs there too.  The residual stream, patch embed and head are unchanged.
 //
-// The tail is final norm -> pool -> fc_norm -> head GEMM.  A headless plan (head_w NULL, num_classes 0) stops in front of the
-// GEMM and lets the norm launch write the caller's buffer; on such a plan ext.pool = RAJNI_POOL_NONE normalises every surviving
-// row into it, and RAJNI_POOL_DENSE scatters them back to the unpruned sequence (source_idx_kernel + layernorm_dense_kernel,
-// rowops.hip).  RAJNI_POOL_DENSE_LAST fills the pruned positions as well: behind the tail of every scheduled block the rows the
-// block drops - still in the stream buffer its residual gather read from - go through the final norm to their source rows
-// (source_idx_kernel + layernorm_dropped_kernel), and the final launch stores the survivors only.  The logits path and the
-// other outputs issue the launches they always did.
+// Behind the last block, one of the tails:
+//   final norm of the rows the head reads -> pool -> fc_norm -> head GEMM.  A headless plan (head_w NULL, num_classes 0) stops
+//     in front of the GEMM and lets the norm launch write the caller's buffer;
+//   the token outputs of a headless plan: RAJNI_POOL_NONE normalises every surviving row into the caller's buffer, and
+//     RAJNI_POOL_DENSE / _DENSE_LAST scatter them back to the unpruned sequence (source_idx_kernel + layernorm_dense_kernel);
+//   the attention pool (launch_pool_tail): final norm on every surviving row -> kv GEMM -> launch_attention_pool -> proj, the
+//     pool's LayerNorm, FC1 + act and FC2 + residual on B rows in fp32 -> fc_norm or one rounding to the model dtype -> head.
 //
-// rajni_vit_forward_layers (rajni_hip_layers.h) adds capture points to the block loop: behind the tail of a captured block the
-// stream goes to that block's slab on the unpruned grid (source_idx_kernel + layernorm_dense_kernel or rows_dense_cast_kernel),
-// and with fill = 1 every scheduled block writes the rows it drops to the slabs of all captures at or behind it in one launch
-// (rows_dropped_multi_kernel).  Whatever the plan writes to `logits` it writes unchanged; a NULL record adds nothing.
-//
-// rajni_vit_forward_image (rajni_hip_image.h) takes [B, Cin, height, width] images: the record reaches check_image, the
-// workspace carve, the token walk and the patch-embed call, where n0 = (height / patch) * (width / patch) + P replaces the
-// square count; plan.pos_embed holds the rows of that grid (rajni_resample_pos_embed makes them).  Nothing behind the
-// embedding changes, and a NULL or square record enqueues the launches it always did.
-//
-// rajni_vit_forward_query (rajni_hip_query.h) names the importance query of the scoring blocks (row 0, or the mean of the query
-// rows) and whether the sequence has a class row at all.  Without one the prefix tokens are the R >= 0 registers alone: P = R
-// goes through embed, select, the gathered residual, the 'avg' pool, the source map and the dense outputs, the last block always
-// runs every row, and check_query refuses what has no meaning there.  A NULL record or {1, RAJNI_QUERY_CLS} changes no launch.
-//
-// rajni_vit_forward_pool (rajni_hip_attnpool.h) adds the attention-pool head (timm global_pool='map') as a tail of its own,
-// launch_pool_tail: final norm on every surviving row -> kv GEMM into w.qkv -> launch_attention_pool -> proj, the pool's
-// LayerNorm, FC1 + act and FC2 + residual on B rows IN FP32 (PoolRows: carved BEHIND the workspace of rajni_vit_forward_query,
-// which does not move) -> fc_norm or one rounding to the model dtype -> head.  A NULL record changes no launch; RAJNI_POOL_MAP without one is the unknown pool value it
-// always was.
+// What each record changes (a NULL record changes no launch): ext - q/k-norm behind QKV, norm_pre behind the embedding, FC1's
+// epilogue, and which tail runs; RAJNI_POOL_DENSE_LAST also sends the rows each scheduled block drops through the final norm to
+// their source rows, behind that block's tail.  prefix - P prefix tokens (never pruned) instead of the class token alone, and
+// with head_rows 2 the distilled head.  layers - behind a captured block the stream goes to that block's slab on the unpruned
+// grid, and with fill = 1 every scheduled block writes the rows it drops to the slabs of all captures at or behind it.  image -
+// n0 = (height / patch) * (width / patch) + P tokens, and plan.pos_embed holds the rows of that grid.  query - the importance
+// query of the scoring blocks and whether there is a class row; without one P counts the registers alone and the last block
+// runs every row.  pool - the attention-pool tail and its B fp32 rows, carved behind everything else.
 #include "common.h"
 
 #include <vector>
@@ -58,18 +47,84 @@ struct Workspace {
   int32_t* idx01;          // head_rows == 2: [B, 2] = {0, 1} per image, the selection that names the two rows the head reads
   char* sst; size_t sst_bytes;   // scratch of the tiled score kernels: zero bytes wherever one workgroup holds (n0, H, D)
   float *xs, *hs;          // act_fp8 plans: per-row scales of the e4m3 LayerNorm output / MLP hidden activations
+  // the B-row intermediates of the attention-pool tail (rajni_hip_attnpool.h), behind everything above: po [B, C] the pool
+  // kernel's output, py [B, C] proj's output and the MLP's residual stream (FC2 adds in place), pn [B, C] the pool LayerNorm's
+  // rows, phid [B, pool.hidden] - all fp32 whatever the plan's dtype: the B-row part of the tail runs in fp32
+  char *po, *py, *pn, *phid;
   size_t total, cols_bytes;
 };
 
-// the image record (rajni_hip_image.h) beside the plan: NULL is the square image of plan.img_size pixels
-inline int image_height(const rajni_vit_plan& p, const rajni_vit_image* img) { return img ? img->height : p.img_size; }
-inline int image_width(const rajni_vit_plan& p, const rajni_vit_image* img) { return img ? img->width : p.img_size; }
-inline int patch_tokens(const rajni_vit_plan& p, const rajni_vit_image* img) {
-  return (image_height(p, img) / p.patch_size) * (image_width(p, img) / p.patch_size);
+// One call, resolved: the plan, the optional records beside it (NULL: absent) and every fact derived from them, each computed
+// here once with the NULL defaults applied.  make_spec follows no pointer a refusal has yet to vouch for; `w` is carved by
+// check_all behind every other refusal, since the workspace size is the last of them.
+struct Spec {
+  const char* who;                  // the entry point a prefix refusal names: that of the widest record present
+  const rajni_vit_plan* p;
+  const rajni_vit_ext* ext; const rajni_vit_prefix* pre; const rajni_vit_layers* lay; const rajni_vit_image* img;
+  const rajni_vit_query* qry;       // {1, RAJNI_QUERY_CLS} arrives here as NULL
+  const rajni_vit_attn_pool* ap;
+  hipStream_t s;
+  bool nocls;                       // no class row: the prefix tokens are the registers alone
+  int qmode;                        // the importance query of the scoring blocks
+  int has_cls, P, HR;               // class rows (0 / 1); prefix tokens, never pruned; rows of each image the head reads (1 / 2)
+  int height, width, n0;            // the input in pixels; tokens entering block 0, prefix tokens included
+  int pool;                         // ext.pool (RAJNI_POOL_TOKEN without ext)
+  bool dense_last, norm_absent;
+  const void* reg_token;            // the registers (or the dist token) the patch embed writes behind the class row, or NULL
+  int fc1_epi, sf32;                // FC1's epilogue (ext.mlp_act); 16-bit model with an fp32 residual stream
+  const rajni_qk_affine* qk_norm;
+  bool last_captured;               // the layers record captures the last block
+  size_t slab_ld;                   // elements between two slabs of the layers record
+  Workspace w;
+};
+
+enum { ENTRY_FORWARD = 0, ENTRY_SIZE = 1 };
+
+Spec make_spec(int family, const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre,
+               const rajni_vit_layers* lay, const rajni_vit_image* img, const rajni_vit_query* qry, const rajni_vit_attn_pool* ap,
+               hipStream_t s) {
+  // a NULL trailing record makes a call the next-narrower entry point's, by name too (the size of a pool record is the query
+  // size function's plus the pool rows, and there is no size function for a layers record)
+  static const char* const names[2][5] = {
+      {"rajni_vit_forward_ext_prefix", "rajni_vit_forward_layers", "rajni_vit_forward_image", "rajni_vit_forward_query",
+       "rajni_vit_forward_pool"},
+      {"rajni_vit_workspace_bytes_prefix", "rajni_vit_workspace_bytes_prefix", "rajni_vit_workspace_bytes_image",
+       "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_query"}};
+  if (qry && qry->class_token == 1 && qry->query == RAJNI_QUERY_CLS) qry = nullptr;
+  Spec c{};
+  c.who = names[family][(ap && family == ENTRY_FORWARD) ? 4 : qry ? 3 : img ? 2 : lay ? 1 : 0];
+  c.p = plan; c.ext = ext; c.pre = pre; c.lay = lay; c.img = img; c.qry = qry; c.ap = ap; c.s = s;
+  c.nocls = qry != nullptr && qry->class_token == 0;
+  c.qmode = qry ? qry->query : RAJNI_QUERY_CLS;
+  c.has_cls = c.nocls ? 0 : 1;
+  // NULL, 0 and 1 all mean CLS only; without a class row the record counts the registers alone
+  c.P = c.nocls ? (pre ? pre->num_prefix : 0) : ((pre && pre->num_prefix > 1) ? pre->num_prefix : 1);
+  // NULL, 0 and 1 all mean the CLS row; 2 is the distilled head (cls and dist rows); no class row, no head rows
+  c.HR = (!c.nocls && pre && pre->head_rows == 2) ? 2 : 1;
+  c.reg_token = c.P > c.has_cls ? pre->reg_token : nullptr;
+  c.pool = ext ? ext->pool : RAJNI_POOL_TOKEN;
+  c.dense_last = c.pool == RAJNI_POOL_DENSE_LAST;
+  c.norm_absent = ext != nullptr && ext->norm_absent != 0;
+  c.qk_norm = ext ? ext->qk_norm : nullptr;
+  c.fc1_epi = (ext && ext->mlp_act == RAJNI_MLP_QUICK_GELU) ? RAJNI_EPI_BIAS_QUICK_GELU
+              : (ext && ext->mlp_act == RAJNI_MLP_SWIGLU) ? RAJNI_EPI_BIAS_SWIGLU : RAJNI_EPI_BIAS_GELU;
+  if (!plan) return c;
+  const rajni_vit_plan& p = *plan;
+  c.height = img ? img->height : p.img_size;   // NULL is the square image of plan.img_size pixels
+  c.width = img ? img->width : p.img_size;
+  // (check_image refuses a grid beyond the int range before anything reads n0)
+  c.n0 = p.patch_size > 0 ? (int)((long long)(c.height / p.patch_size) * (c.width / p.patch_size) + c.P) : c.P;
+  c.sf32 = (p.dtype != RAJNI_F32 && !p.resid_bf16) ? 1 : 0;
+  c.last_captured = lay && lay->blocks && lay->n >= 1 && lay->n <= RAJNI_MAX_LAYERS && lay->blocks[lay->n - 1] == p.depth - 1;
+  c.slab_ld = lay ? (lay->slab_stride ? (size_t)lay->slab_stride : (size_t)p.B * c.n0 * p.C) : 0;
+  return c;
 }
 
-Workspace carve(const rajni_vit_plan& p, int P, int HR, const rajni_vit_image* img = nullptr, int query = RAJNI_QUERY_CLS) {
-  const size_t n0 = (size_t)patch_tokens(p, img) + P;
+// the workspace and, with a pool record, the pool rows behind it: one layout, one total
+Workspace carve(const Spec& c) {
+  const rajni_vit_plan& p = *c.p;
+  const int HR = c.HR;
+  const size_t n0 = (size_t)c.n0;
   const size_t rows = (size_t)p.B * n0, es = p.dtype == RAJNI_F32 ? 4 : 2, xs = (p.dtype == RAJNI_F32 || !p.resid_bf16) ? 4 : 2;
   Workspace w{};
   size_t off = 0;
@@ -78,33 +133,23 @@ Workspace carve(const rajni_vit_plan& p, int P, int HR, const rajni_vit_image* i
   const size_t oqkv = take(rows * 3 * p.C * es), oatt = take(rows * p.C * es);
   const size_t ohid = take(rows * p.hidden * es), ocls = take((size_t)p.B * HR * p.C * es);
   const size_t oscf = take(rows * es);
-  w.cols_bytes = patch_embed_workspace_bytes(p.B, p.in_chans, image_height(p, img), image_width(p, img), p.patch_size, p.dtype);   // 0 when fused
+  w.cols_bytes = patch_embed_workspace_bytes(p.B, p.in_chans, c.height, c.width, p.patch_size, p.dtype);   // 0 when fused
   const size_t ocols = take(w.cols_bytes);
   const size_t oxs = take(p.act_fp8 ? rows * sizeof(float) : 0), ohs = take(p.act_fp8 ? rows * sizeof(float) : 0);
-  w.sst_bytes = rajni_score_select_query_workspace_bytes(p.B, (int)n0, p.H, p.D, p.dtype, query);   // (CLS: rajni_score_select_workspace_bytes)
+  w.sst_bytes = rajni_score_select_query_workspace_bytes(p.B, (int)n0, p.H, p.D, p.dtype, c.qmode);   // (CLS: rajni_score_select_workspace_bytes)
   const size_t osst = take(w.sst_bytes);
-  const size_t oidx = take(HR == 2 ? (size_t)p.B * 2 * sizeof(int32_t) : 0);   // last: nothing above moves
+  const size_t oidx = take(HR == 2 ? (size_t)p.B * 2 * sizeof(int32_t) : 0);   // behind the rest: nothing above moves
+  const size_t prow = c.ap ? (size_t)p.B * p.C * sizeof(float) : 0;            // the pool rows likewise
+  const size_t opo = take(prow), opy = take(prow), opn = take(prow), oph = take(c.ap ? (size_t)p.B * c.ap->hidden * sizeof(float) : 0);
   char* base = (char*)p.workspace;
   w.xa = base + oxa; w.xb = base + oxb; w.xn = base + oxn; w.qkv = base + oqkv; w.att = base + oatt;
   w.hid = base + ohid; w.clsn = base + ocls; w.scf = base + oscf; w.cols = base + ocols;
   w.sst = w.sst_bytes ? base + osst : nullptr;
   w.idx01 = HR == 2 ? reinterpret_cast<int32_t*>(base + oidx) : nullptr;
   w.xs = reinterpret_cast<float*>(base + oxs); w.hs = reinterpret_cast<float*>(base + ohs);
+  w.po = base + opo; w.py = base + opy; w.pn = base + opn; w.phid = base + oph;
   w.total = off;
   return w;
-}
-
-// the B-row intermediates of the attention-pool tail (rajni_hip_attnpool.h), behind the `base_total` bytes carve() hands out:
-// o [B, C] the pool kernel's output, y [B, C] proj's output and the MLP's residual stream (FC2 adds in place), n [B, C] the
-// pool LayerNorm's rows, hid [B, pool.hidden] - all fp32 whatever the plan's dtype: the B-row part of the tail runs in fp32
-struct PoolRows { char *o, *y, *n, *hid; size_t total; };
-PoolRows carve_pool(const rajni_vit_plan& p, const rajni_vit_attn_pool& ap, size_t base_total) {
-  size_t off = align256(base_total);
-  auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
-  const size_t row = (size_t)p.B * p.C * sizeof(float);
-  const size_t oo = take(row), oy = take(row), on = take(row), oh = take((size_t)p.B * ap.hidden * sizeof(float));
-  char* base = (char*)p.workspace;
-  return PoolRows{base + oo, base + oy, base + on, base + oh, off};
 }
 
 // next_scores[b, j] = scores[b, idx[b, j]]   (attention.py:58) - used with a forced selection
@@ -150,7 +195,8 @@ inline bool pool_is_tokens(const rajni_vit_ext* e) {
   return e && (e->pool == RAJNI_POOL_NONE || e->pool == RAJNI_POOL_DENSE || e->pool == RAJNI_POOL_DENSE_LAST);
 }
 
-int check_plan(const rajni_vit_plan& p, bool norm_absent, bool nocls = false) {
+int check_plan(const Spec& c) {
+  const rajni_vit_plan& p = *c.p;
   RAJNI_REQUIRE(p.dtype == RAJNI_BF16 || p.dtype == RAJNI_F32 || p.dtype == RAJNI_F16, RAJNI_ERR_INVALID,
                 "rajni_vit_forward: bad dtype %d", p.dtype);
   RAJNI_REQUIRE(p.B > 0 && p.depth > 0 && p.blocks != nullptr, RAJNI_ERR_INVALID, "rajni_vit_forward: bad plan");
@@ -163,8 +209,8 @@ int check_plan(const rajni_vit_plan& p, bool norm_absent, bool nocls = false) {
   RAJNI_REQUIRE(p.C % 64 == 0 && p.hidden % 64 == 0, RAJNI_ERR_UNSUPPORTED,
                 "rajni_vit_forward: C and hidden must be multiples of 64");
   // a headless plan (head_w == NULL and num_classes == 0) is legal; half of that pair is a missing weight
-  RAJNI_REQUIRE(p.patch_w && (p.cls_token || nocls) && p.pos_embed && (p.head_w != nullptr) == (p.num_classes != 0) &&
-                    (norm_absent || (p.norm_w && p.norm_b)),
+  RAJNI_REQUIRE(p.patch_w && (p.cls_token || c.nocls) && p.pos_embed && (p.head_w != nullptr) == (p.num_classes != 0) &&
+                    (c.norm_absent || (p.norm_w && p.norm_b)),
                 RAJNI_ERR_INVALID, "rajni_vit_forward: null weight pointer");
   RAJNI_REQUIRE(!(headless(p) && p.act_fp8), RAJNI_ERR_UNSUPPORTED,
                 "rajni_vit_forward: a headless plan (feature output) is unsupported with act_fp8");
@@ -186,12 +232,14 @@ int check_plan(const rajni_vit_plan& p, bool norm_absent, bool nocls = false) {
   return RAJNI_OK;
 }
 
-// map_ok: the call came through rajni_vit_forward_pool with a record - RAJNI_POOL_MAP is an unknown value everywhere else
-int check_ext(const rajni_vit_plan& p, const rajni_vit_ext& e, bool map_ok = false) {
+// the ext record against the plan (RAJNI_POOL_MAP is an unknown value without a pool record)
+int check_ext(const Spec& c) {
+  const rajni_vit_plan& p = *c.p;
+  const rajni_vit_ext& e = *c.ext;
   // (RAJNI_POOL_NONE, RAJNI_POOL_DENSE and RAJNI_POOL_DENSE_LAST, the token outputs, are legal too - 4 is not; the wording of this
   // refusal is what callers match on)
   RAJNI_REQUIRE((e.pool >= RAJNI_POOL_TOKEN && e.pool <= RAJNI_POOL_DENSE) || e.pool == RAJNI_POOL_DENSE_LAST ||
-                    (map_ok && e.pool == RAJNI_POOL_MAP), RAJNI_ERR_UNSUPPORTED,
+                    (c.ap && e.pool == RAJNI_POOL_MAP), RAJNI_ERR_UNSUPPORTED,
                 "rajni_vit_forward_ext: pool must be RAJNI_POOL_TOKEN or RAJNI_POOL_AVG (%d)%s", e.pool,
                 e.pool == RAJNI_POOL_MAP ? " - RAJNI_POOL_MAP needs rajni_vit_forward_pool and its rajni_vit_attn_pool record" : "");
   RAJNI_REQUIRE(!(e.pool == RAJNI_POOL_AVG && p.cls_only_last_block), RAJNI_ERR_INVALID,
@@ -242,16 +290,13 @@ int g_last_block_all_rows = 0;
 // last block that prunes (its selection is part of the trace), an avg-pooled head (reads every row), act_fp8 plans and
 // the cls_only_last_block opt-in (they keep the opt-in's own branch and numerics contract).  With the distilled head
 // (head_rows == 2) the observable rows are 0 and 1 of each image, and the block runs on those 2B rows under the same test.
-// Nor for a last block whose output rajni_vit_forward_layers captures (`captured`): the slab reads every row.
-// Nor for a sequence without a class row (`nocls`, rajni_hip_query.h): no head reads a single row of it.
-inline bool last_block_cls_rows(const rajni_vit_plan& p, const rajni_vit_ext* ext, int i, int N, bool captured = false, bool nocls = false) {
-  return i == p.depth - 1 && p.blocks[i].keep == 0 && N > 1 && (ext == nullptr || ext->pool == RAJNI_POOL_TOKEN) &&
-         !p.act_fp8 && !p.cls_only_last_block && !g_last_block_all_rows && !captured && !nocls;
+// Nor for a last block whose output the layers record captures: the slab reads every row.
+// Nor for a sequence without a class row (rajni_hip_query.h): no head reads a single row of it.
+inline bool last_block_cls_rows(const Spec& c, int i, int N) {
+  const rajni_vit_plan& p = *c.p;
+  return i == p.depth - 1 && p.blocks[i].keep == 0 && N > 1 && c.pool == RAJNI_POOL_TOKEN &&
+         !p.act_fp8 && !p.cls_only_last_block && !g_last_block_all_rows && !c.last_captured && !c.nocls;
 }
-
-// what is fixed for one forward, for the builders and launchers below
-// sf32: 16-bit model, fp32 residual stream; fc1_epi: FC1's epilogue (ext.mlp_act)
-struct Fwd { const rajni_vit_plan& p; const Workspace& w; int sf32; hipStream_t s; int fc1_epi; };
 
 // y[M, N] = epi(x[M, K] wt[N, K]^T + bias), every operand dense
 rajni_linear_args linear_args(int dtype, const void* x, const void* wt, const float* bias, const float* w_scale, void* y,
@@ -272,14 +317,14 @@ struct AttnRows {
 };
 
 // norm1 + qkv on ALL N tokens (model.py:51, attention.py:21-22)
-rajni_linear_args qkv_args(const Fwd& f, const rajni_block& blk, int M) {
-  rajni_linear_args g = linear_args(f.p.dtype, f.w.xn, blk.qkv_w, blk.qkv_b, blk.qkv_s, f.w.qkv, M, 3 * f.p.C, f.p.C, RAJNI_EPI_BIAS);
-  if (f.p.act_fp8) g.x_scale = f.w.xs;
+rajni_linear_args qkv_args(const Spec& f, const rajni_block& blk, int M) {
+  rajni_linear_args g = linear_args(f.p->dtype, f.w.xn, blk.qkv_w, blk.qkv_b, blk.qkv_s, f.w.qkv, M, 3 * f.p->C, f.p->C, RAJNI_EPI_BIAS);
+  if (f.p->act_fp8) g.x_scale = f.w.xs;
   return g;
 }
 // proj + (gathered) residual + LayerScale (attention.py:55-56, model.py:55-58): x -> y is the stream before / after
-rajni_linear_args proj_args(const Fwd& f, const rajni_block& blk, const AttnRows& r, const void* x, void* y) {
-  rajni_linear_args g = linear_args(f.p.dtype, f.w.att, blk.proj_w, blk.proj_b, blk.proj_s, y, r.M, f.p.C, f.p.C, RAJNI_EPI_BIAS_RESID);
+rajni_linear_args proj_args(const Spec& f, const rajni_block& blk, const AttnRows& r, const void* x, void* y) {
+  rajni_linear_args g = linear_args(f.p->dtype, f.w.att, blk.proj_w, blk.proj_b, blk.proj_s, y, r.M, f.p->C, f.p->C, RAJNI_EPI_BIAS_RESID);
   g.lda = r.lda; g.x_scale = r.x_scale;
   g.gamma = blk.ls1; g.resid = x; g.ldr = r.ldr; g.stream_f32 = f.sf32;
   if (r.idx) { g.r_idx = r.idx; g.r_np = r.np; g.r_nsrc = r.nsrc; }
@@ -287,24 +332,23 @@ rajni_linear_args proj_args(const Fwd& f, const rajni_block& blk, const AttnRows
 }
 // MLP (model.py:59): fc1 + GELU (or the QuickGELU / gated SwiGLU of ext.mlp_act: N = hidden is the OUTPUT width either way,
 // the gated fc1_w has 2 * hidden rows); act_fp8: e4m3 in, e4m3 out (per-row scales)
-rajni_linear_args fc1_args(const Fwd& f, const rajni_block& blk, int M) {
-  rajni_linear_args g = linear_args(f.p.dtype, f.w.xn, blk.fc1_w, blk.fc1_b, blk.fc1_s, f.w.hid, M, f.p.hidden, f.p.C, f.fc1_epi);
-  if (f.p.act_fp8) { g.x_scale = f.w.xs; g.y_scale = f.w.hs; }
+rajni_linear_args fc1_args(const Spec& f, const rajni_block& blk, int M) {
+  rajni_linear_args g = linear_args(f.p->dtype, f.w.xn, blk.fc1_w, blk.fc1_b, blk.fc1_s, f.w.hid, M, f.p->hidden, f.p->C, f.fc1_epi);
+  if (f.p->act_fp8) { g.x_scale = f.w.xs; g.y_scale = f.w.hs; }
   return g;
 }
 // fc2 + LayerScale + residual, in place on the stream y
-rajni_linear_args fc2_args(const Fwd& f, const rajni_block& blk, int M, void* y) {
-  rajni_linear_args g = linear_args(f.p.dtype, f.w.hid, blk.fc2_w, blk.fc2_b, blk.fc2_s, y, M, f.p.C, f.p.hidden, RAJNI_EPI_BIAS_RESID);
-  if (f.p.act_fp8) g.x_scale = f.w.hs;
-  g.gamma = blk.ls2; g.resid = y; g.ldr = f.p.C; g.stream_f32 = f.sf32;
+rajni_linear_args fc2_args(const Spec& f, const rajni_block& blk, int M, void* y) {
+  rajni_linear_args g = linear_args(f.p->dtype, f.w.hid, blk.fc2_w, blk.fc2_b, blk.fc2_s, y, M, f.p->C, f.p->hidden, RAJNI_EPI_BIAS_RESID);
+  if (f.p->act_fp8) g.x_scale = f.w.hs;
+  g.gamma = blk.ls2; g.resid = y; g.ldr = f.p->C; g.stream_f32 = f.sf32;
   return g;
 }
 
 // LayerNorm of `rows` stream rows into w.xn; act_fp8 plans: e4m3 rows + their scales into w.xs, and with hs the hidden
-// scale of the rows' MLP (norm2 only)
-int layernorm(const Fwd& f, const void* x, const float* g, const float* b, int rows, float* hs = nullptr, float wnorm = 0.f,
-              float bmax = 0.f) {
-  const rajni_vit_plan& p = f.p;
+// scale of the rows' MLP (norm2 only; norm1 passes null and zeros)
+int layernorm(const Spec& f, const void* x, const float* g, const float* b, int rows, float* hs, float wnorm, float bmax) {
+  const rajni_vit_plan& p = *f.p;
   if (p.act_fp8) return launch_layernorm_fp8(x, p.C, g, b, f.w.xn, f.w.xs, hs, wnorm, bmax, rows, p.C, p.ln_eps, f.sf32, f.s);
   return launch_layernorm(x, p.C, g, b, f.w.xn, rows, p.C, p.ln_eps, f.sf32, p.dtype, f.s);
 }
@@ -317,7 +361,7 @@ inline bool attn_emits_e4m3(const rajni_vit_plan& p, const rajni_block& blk, int
 
 // everything of a block behind its attention: proj + residual -> LN2 -> fc1 + GELU -> fc2 + residual
 struct Tail { rajni_linear_args proj, fc1, fc2; };
-Tail tail_args(const Fwd& f, const rajni_block& blk, const AttnRows& r, const void* x, void* y) {
+Tail tail_args(const Spec& f, const rajni_block& blk, const AttnRows& r, const void* x, void* y) {
   return Tail{proj_args(f, blk, r, x, y), fc1_args(f, blk, r.M), fc2_args(f, blk, r.M, y)};
 }
 // would rajni_linear take all three?  (the dry run: every refusal, no launch; 256 CUs - no refusal depends on the count)
@@ -326,7 +370,7 @@ bool tail_ok(const Tail& t) {
   return rajni_debug_linear_plan(&t.proj, 256, &unused) == RAJNI_OK && rajni_debug_linear_plan(&t.fc1, 256, &unused) == RAJNI_OK &&
          rajni_debug_linear_plan(&t.fc2, 256, &unused) == RAJNI_OK;
 }
-int launch_tail(const Fwd& f, const rajni_block& blk, const Tail& t) {
+int launch_tail(const Spec& f, const rajni_block& blk, const Tail& t) {
   int rc = launch_linear(t.proj, f.s);
   if (rc != RAJNI_OK) return rc;
   rc = layernorm(f, t.proj.y, blk.norm2_w, blk.norm2_b, t.proj.M, f.w.hs, blk.fc1_rownorm_max, blk.fc1_bias_absmax);
@@ -336,23 +380,14 @@ int launch_tail(const Fwd& f, const rajni_block& blk, const Tail& t) {
   return launch_linear(t.fc2, f.s);
 }
 
-// P of a prefix record: NULL, 0 and 1 all mean CLS only
-inline int prefix_count(const rajni_vit_prefix* pre) { return (pre && pre->num_prefix > 1) ? pre->num_prefix : 1; }
-// the query record (rajni_hip_query.h): NULL is {1, RAJNI_QUERY_CLS}
-inline bool no_class_row(const rajni_vit_query* q) { return q != nullptr && q->class_token == 0; }
-inline int query_mode(const rajni_vit_query* q) { return q ? q->query : RAJNI_QUERY_CLS; }
-// ... without a class row the record counts the registers alone: NULL and 0 mean no prefix token at all
-inline int prefix_count(const rajni_vit_prefix* pre, const rajni_vit_query* q) {
-  return no_class_row(q) ? (pre ? pre->num_prefix : 0) : prefix_count(pre);
-}
-// rows of each image the head reads: NULL, 0 and 1 all mean the CLS row; 2 is the distilled head (cls and dist rows)
-inline int head_row_count(const rajni_vit_prefix* pre) { return (pre && pre->head_rows == 2) ? 2 : 1; }
-
-int check_prefix(const rajni_vit_prefix* pre, const char* who, bool nocls = false) {
+// the prefix record on its own terms, under the name of the entry point the call came through
+int check_prefix(const Spec& c) {
+  const rajni_vit_prefix* pre = c.pre;
+  const char* who = c.who;
   if (!pre) return RAJNI_OK;
   RAJNI_REQUIRE(pre->num_prefix >= 0 && pre->num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
                 "%s: num_prefix must be 0..%d (%d)", who, RAJNI_MAX_PREFIX, pre->num_prefix);
-  if (nocls) {   // the registers alone: reg_token [num_prefix, C]
+  if (c.nocls) {   // the registers alone: reg_token [num_prefix, C]
     RAJNI_REQUIRE((pre->num_prefix > 0) == (pre->reg_token != nullptr), RAJNI_ERR_INVALID,
                   "%s: query.class_token = 0 with prefix.num_prefix = %d registers but reg_token is %s", who, pre->num_prefix,
                   pre->reg_token ? "given" : "null");
@@ -372,8 +407,10 @@ int check_prefix(const rajni_vit_prefix* pre, const char* who, bool nocls = fals
 }
 
 // the distilled head (head_rows == 2) against the plan and the ext record: it is norm -> rows 0 and 1 -> one linear layer
-int check_head_rows(const rajni_vit_plan& p, const rajni_vit_ext* e, const rajni_vit_prefix* pre) {
-  if (head_row_count(pre) != 2) return RAJNI_OK;
+int check_head_rows(const Spec& c) {
+  const rajni_vit_plan& p = *c.p;
+  const rajni_vit_ext* e = c.ext;
+  if (c.HR != 2) return RAJNI_OK;
   RAJNI_REQUIRE(!headless(p), RAJNI_ERR_UNSUPPORTED,
                 "rajni_vit_forward: head_rows=2 with a headless plan - the two rows exist to feed the averaged heads");
   RAJNI_REQUIRE(!e || (e->pool == RAJNI_POOL_TOKEN && !e->fc_norm_w && !e->norm_absent), RAJNI_ERR_UNSUPPORTED,
@@ -387,14 +424,22 @@ int check_head_rows(const rajni_vit_plan& p, const rajni_vit_ext* e, const rajni
 
 // the query record against the plan, the ext and the prefix record (rajni_hip_query.h): host-side integer tests, every refusal
 // names its field
-int check_query(const rajni_vit_plan& p, const rajni_vit_ext* e, const rajni_vit_query& q) {
+// (query_form: the record on its own terms - all a size function asks of it; the rest is what a missing class row rules out)
+int query_form(const rajni_vit_query& q) {
   const char* who = "rajni_vit_forward_query";
   RAJNI_REQUIRE(q.class_token == 0 || q.class_token == 1, RAJNI_ERR_INVALID, "%s: query.class_token must be 0 or 1 (%d)", who, q.class_token);
   RAJNI_REQUIRE(q.query == RAJNI_QUERY_CLS || q.query == RAJNI_QUERY_MEAN, RAJNI_ERR_INVALID,
                 "%s: query.query must be RAJNI_QUERY_CLS or RAJNI_QUERY_MEAN (%d)", who, q.query);
-  if (q.class_token) return RAJNI_OK;
-  RAJNI_REQUIRE(q.query == RAJNI_QUERY_MEAN, RAJNI_ERR_INVALID,
+  RAJNI_REQUIRE(q.class_token || q.query == RAJNI_QUERY_MEAN, RAJNI_ERR_INVALID,
                 "%s: query.query must be RAJNI_QUERY_MEAN with query.class_token = 0 - there is no class row to be the query", who);
+  return RAJNI_OK;
+}
+int check_query(const Spec& c) {
+  const char* who = "rajni_vit_forward_query";
+  const rajni_vit_plan& p = *c.p;
+  const rajni_vit_ext* e = c.ext;
+  const int rc = query_form(*c.qry);
+  if (rc != RAJNI_OK || !c.nocls) return rc;
   RAJNI_REQUIRE(!p.cls_only_last_block, RAJNI_ERR_INVALID,
                 "%s: plan.cls_only_last_block with query.class_token = 0 - there is no class row to form", who);
   // (RAJNI_POOL_MAP reads every row too; whether it is legal at this entry point is check_ext's to say)
@@ -407,15 +452,19 @@ int check_query(const rajni_vit_plan& p, const rajni_vit_ext* e, const rajni_vit
 
 // the attention-pool record against the plan, the ext and the prefix record (rajni_hip_attnpool.h): host-side tests, every
 // refusal names its field
-int check_pool(const rajni_vit_plan& p, const rajni_vit_ext* e, const rajni_vit_prefix* pre, bool nocls, const rajni_vit_attn_pool& ap) {
+inline bool pool_hidden_ok(const rajni_vit_attn_pool& ap) { return ap.hidden > 0 && ap.hidden % 64 == 0; }
+int check_pool(const Spec& c) {
   const char* who = "rajni_vit_forward_pool";
+  const rajni_vit_plan& p = *c.p;
+  const rajni_vit_ext* e = c.ext;
+  const rajni_vit_attn_pool& ap = *c.ap;
   RAJNI_REQUIRE(e != nullptr && e->pool == RAJNI_POOL_MAP, RAJNI_ERR_INVALID,
                 "%s: ext.pool must be RAJNI_POOL_MAP with a rajni_vit_attn_pool record (%s%d)", who, e ? "ext.pool = " : "ext is NULL: pool ",
                 e ? e->pool : RAJNI_POOL_TOKEN);
   RAJNI_REQUIRE(!p.cls_only_last_block, RAJNI_ERR_INVALID,
                 "%s: plan.cls_only_last_block with RAJNI_POOL_MAP - that opt-in never forms the rows to be pooled", who);
   RAJNI_REQUIRE(!p.act_fp8, RAJNI_ERR_UNSUPPORTED, "%s: plan.act_fp8 is unsupported with RAJNI_POOL_MAP", who);
-  RAJNI_REQUIRE(nocls || head_row_count(pre) != 2, RAJNI_ERR_UNSUPPORTED,
+  RAJNI_REQUIRE(c.HR != 2, RAJNI_ERR_UNSUPPORTED,
                 "%s: prefix.head_rows = 2 with RAJNI_POOL_MAP - the two rows exist to feed the averaged token heads", who);
   RAJNI_REQUIRE(!e->norm_absent, RAJNI_ERR_UNSUPPORTED,
                 "%s: ext.norm_absent with RAJNI_POOL_MAP - the pool reads norm(x), and there is no cast-only row kernel", who);
@@ -425,7 +474,7 @@ int check_pool(const rajni_vit_plan& p, const rajni_vit_ext* e, const rajni_vit_
   RAJNI_REQUIRE(ap.heads > 0 && p.C > 0 && p.C % ap.heads == 0 && (p.C / ap.heads) % 8 == 0 && p.C / ap.heads >= 8 && p.C / ap.heads <= 128,
                 RAJNI_ERR_INVALID, "%s: pool.heads must divide C into head dims that are multiples of 8 in 8..128 (heads=%d C=%d)", who,
                 ap.heads, p.C);
-  RAJNI_REQUIRE(ap.hidden > 0 && ap.hidden % 64 == 0, RAJNI_ERR_INVALID,
+  RAJNI_REQUIRE(pool_hidden_ok(ap), RAJNI_ERR_INVALID,
                 "%s: pool.hidden must be a positive multiple of 64 (zero-pad the MLP width) (%d)", who, ap.hidden);
   RAJNI_REQUIRE(ap.act == RAJNI_MLP_GELU || ap.act == RAJNI_MLP_QUICK_GELU, RAJNI_ERR_INVALID,
                 "%s: pool.act must be RAJNI_MLP_GELU or RAJNI_MLP_QUICK_GELU (%d)", who, ap.act);
@@ -438,20 +487,21 @@ int check_pool(const rajni_vit_plan& p, const rajni_vit_ext* e, const rajni_vit_
 // the token walk (model.py:43,50): a scheduled block leaves its kept patch tokens and the P prefix tokens ...
 inline int tokens_after(const rajni_block& blk, int N, int P) { return blk.keep > 0 ? blk.keep + P : N; }
 // ... so this many enter block i
-int tokens_entering(const rajni_vit_plan& p, int P, int i, const rajni_vit_image* img = nullptr) {
-  int N = patch_tokens(p, img) + P;
-  for (int j = 0; j < i; ++j) N = tokens_after(p.blocks[j], N, P);
+int tokens_entering(const Spec& c, int i) {
+  int N = c.n0;
+  for (int j = 0; j < i; ++j) N = tokens_after(c.p->blocks[j], N, c.P);
   return N;
 }
 
 inline int logits_stride(const rajni_vit_plan& p) { return p.logits_ld > 0 ? p.logits_ld : (headless(p) ? p.C : p.num_classes); }
 
 // the pruning schedule and the logits stride: what the block loop and the head rely on, refused before anything is launched
-int check_schedule(const rajni_vit_plan& p, int P, const rajni_vit_image* img) {
+int check_schedule(const Spec& c) {
+  const rajni_vit_plan& p = *c.p;
   for (int i = 0; i < p.depth; ++i) {
     const rajni_block& blk = p.blocks[i];
     if (blk.keep <= 0) continue;
-    const int patches = tokens_entering(p, P, i, img) - P;
+    const int patches = tokens_entering(c, i) - c.P;
     RAJNI_REQUIRE(blk.keep <= patches, RAJNI_ERR_INVALID, "block %d: keep=%d but only %d patch tokens", i, blk.keep, patches);
     RAJNI_REQUIRE(blk.keep_idx && blk.next_scores, RAJNI_ERR_INVALID, "block %d: keep_idx/next_scores buffers missing", i);
   }
@@ -470,10 +520,11 @@ int check_schedule(const rajni_vit_plan& p, int P, const rajni_vit_image* img) {
 
 // RAJNI_POOL_DENSE_LAST: the refusals of a token output that check_plan, check_head_rows and check_schedule word without the
 // pool, here under its name and with their codes
-int check_dense_last(const rajni_vit_plan& p, const rajni_vit_prefix* pre) {
+int check_dense_last(const Spec& c) {
   const char* who = "rajni_vit_forward_ext: RAJNI_POOL_DENSE_LAST";
+  const rajni_vit_plan& p = *c.p;
   RAJNI_REQUIRE(!p.act_fp8, RAJNI_ERR_UNSUPPORTED, "%s is unsupported with act_fp8", who);
-  RAJNI_REQUIRE(head_row_count(pre) != 2, RAJNI_ERR_UNSUPPORTED,
+  RAJNI_REQUIRE(c.HR != 2, RAJNI_ERR_UNSUPPORTED,
                 "%s with head_rows=2 - the two rows exist to feed the averaged heads, and a token output has no head", who);
   const int ld = p.logits_ld;
   RAJNI_REQUIRE(ld == 0 || (ld % 8 == 0 && ld >= p.C), RAJNI_ERR_INVALID,
@@ -485,8 +536,10 @@ int check_dense_last(const rajni_vit_plan& p, const rajni_vit_prefix* pre) {
 
 // the layers record against the plan and the ext record (rajni_hip_layers.h): host-side integer tests, in front of every other
 // refusal of the forward
-int check_layers(const rajni_vit_plan& p, const rajni_vit_ext* e, int P, const rajni_vit_layers& y, const rajni_vit_image* img) {
+int check_layers(const Spec& c) {
   const char* who = "rajni_vit_forward_layers";
+  const rajni_vit_plan& p = *c.p;
+  const rajni_vit_layers& y = *c.lay;
   RAJNI_REQUIRE(y.n >= 1 && y.n <= RAJNI_MAX_LAYERS, RAJNI_ERR_INVALID, "%s: layers.n must be 1..%d (%d)", who, RAJNI_MAX_LAYERS, y.n);
   RAJNI_REQUIRE(y.blocks != nullptr && y.out != nullptr, RAJNI_ERR_INVALID, "%s: null pointer (layers.%s)", who,
                 y.blocks ? "out" : "blocks");
@@ -496,11 +549,11 @@ int check_layers(const rajni_vit_plan& p, const rajni_vit_ext* e, int P, const r
                   "%s: layers.blocks must be strictly ascending block indices in [0, %d) (blocks[%d] = %d)", who, p.depth, l, y.blocks[l]);
   RAJNI_REQUIRE(y.norm == 0 || y.norm == 1, RAJNI_ERR_INVALID, "%s: layers.norm must be 0 or 1 (%d)", who, y.norm);
   RAJNI_REQUIRE(y.fill == 0 || y.fill == 1, RAJNI_ERR_INVALID, "%s: layers.fill must be 0 (zero rows) or 1 (last state) (%d)", who, y.fill);
-  const long long dense = (long long)p.B * (patch_tokens(p, img) + P) * p.C;
+  const long long dense = (long long)p.B * c.n0 * p.C;
   RAJNI_REQUIRE(y.slab_stride == 0 || (y.slab_stride >= dense && y.slab_stride % 8 == 0), RAJNI_ERR_INVALID,
                 "%s: layers.slab_stride must be 0 or a multiple of 8 that is >= B * (P + n) * C = %lld (%lld)", who, dense, y.slab_stride);
   RAJNI_REQUIRE_PLACED(who, {"layers.out", y.out, 16});
-  RAJNI_REQUIRE(!(y.norm == 1 && e && e->norm_absent), RAJNI_ERR_UNSUPPORTED,
+  RAJNI_REQUIRE(!(y.norm == 1 && c.norm_absent), RAJNI_ERR_UNSUPPORTED,
                 "%s: layers.norm = 1 on a plan without a final norm (ext.norm_absent) - norm = 0 gives the un-normalised states", who);
   RAJNI_REQUIRE(!p.act_fp8, RAJNI_ERR_UNSUPPORTED, "%s is unsupported with act_fp8", who);
   RAJNI_REQUIRE(!(p.cls_only_last_block && y.blocks[y.n - 1] == p.depth - 1), RAJNI_ERR_INVALID,
@@ -509,26 +562,29 @@ int check_layers(const rajni_vit_plan& p, const rajni_vit_ext* e, int P, const r
 }
 
 // the image record against the plan (rajni_hip_image.h): host-side integer tests, in front of every other refusal
-int check_image(const rajni_vit_plan& p, const rajni_vit_prefix* pre, const rajni_vit_image& im, const rajni_vit_query* qry = nullptr) {
+int check_image(const Spec& c) {
   const char* who = "rajni_vit_forward_image";
+  const rajni_vit_plan& p = *c.p;
+  const rajni_vit_image& im = *c.img;
   RAJNI_REQUIRE(p.patch_size > 0, RAJNI_ERR_INVALID, "%s: bad plan (patch_size %d)", who, p.patch_size);
   RAJNI_REQUIRE(im.height > 0 && im.width > 0 && im.height % p.patch_size == 0 && im.width % p.patch_size == 0, RAJNI_ERR_INVALID,
                 "%s: image.height and image.width must be positive multiples of the patch size %d (%d x %d)", who, p.patch_size,
                 im.height, im.width);
   RAJNI_REQUIRE(p.img_size == im.height, RAJNI_ERR_INVALID, "%s: plan.img_size must equal image.height (%d != %d)", who, p.img_size,
                 im.height);
-  const long long n0 = (long long)(im.height / p.patch_size) * (im.width / p.patch_size) + prefix_count(pre, qry);
+  const long long n0 = (long long)(im.height / p.patch_size) * (im.width / p.patch_size) + c.P;   // (c.n0 is an int)
   RAJNI_REQUIRE(n0 <= RAJNI_IMAGE_MAX_TOKENS, RAJNI_ERR_UNSUPPORTED,
                 "%s: N=%lld is beyond the tiled path's cap of %d tokens (%d x %d patches and %d prefix tokens)", who, n0,
-                RAJNI_IMAGE_MAX_TOKENS, im.height / p.patch_size, im.width / p.patch_size, prefix_count(pre, qry));
+                RAJNI_IMAGE_MAX_TOKENS, im.height / p.patch_size, im.width / p.patch_size, c.P);
   return RAJNI_OK;
 }
 
 // the attention-pool tail (rajni_hip_attnpool.h) on the final stream `cur` [B, N, C]: every launch but the pool kernel is one
 // the blocks and the head use.  w.xn, w.qkv and w.att are dead behind the last block: B * N rows of C and of 2C <= 3C fit
-int launch_pool_tail(const Fwd& f, const rajni_vit_attn_pool& ap, const PoolRows& r, const rajni_vit_ext& e, const void* cur, int N,
-                     void* logits) {
-  const rajni_vit_plan& p = f.p;
+int launch_pool_tail(const Spec& f, const void* cur, int N, void* logits) {
+  const rajni_vit_plan& p = *f.p;
+  const rajni_vit_attn_pool& ap = *f.ap;
+  const rajni_vit_ext& e = *f.ext;   // (check_pool: there is one, and its pool is RAJNI_POOL_MAP)
   const int B = p.B, C = p.C, dt = p.dtype;
   int rc = launch_layernorm(cur, C, p.norm_w, p.norm_b, f.w.xn, B * N, C, p.ln_eps, f.sf32, dt, f.s);
   if (rc != RAJNI_OK) return rc;
@@ -537,25 +593,25 @@ int launch_pool_tail(const Fwd& f, const rajni_vit_attn_pool& ap, const PoolRows
   // From here on B rows, in fp32 whatever the model dtype (fp32 copies of proj / fc1 / fc2, the fp32 GEMMs and LayerNorm of an
   // fp32 model): each 16-bit rounding of a pooled row costs 0.2 - 0.4 % of the logit scale and there would be five of them
   // (DESIGN.md section 1, B7), while B rows cost next to nothing.  The pooled row is rounded ONCE, where the head reads it.
-  rc = launch_attention_pool(f.w.qkv, ap.q, r.o, B, N, ap.heads, C / ap.heads, dt, f.s, 1);
+  rc = launch_attention_pool(f.w.qkv, ap.q, f.w.po, B, N, ap.heads, C / ap.heads, dt, f.s, 1);
   if (rc != RAJNI_OK) return rc;
   // y = proj(o), then y += fc2(act(fc1(norm(y)))) in place
   const int f32 = RAJNI_F32;
-  rc = launch_linear(linear_args(f32, r.o, ap.proj_w, ap.proj_b, nullptr, r.y, B, C, C, RAJNI_EPI_BIAS), f.s);
+  rc = launch_linear(linear_args(f32, f.w.po, ap.proj_w, ap.proj_b, nullptr, f.w.py, B, C, C, RAJNI_EPI_BIAS), f.s);
   if (rc != RAJNI_OK) return rc;
-  rc = launch_layernorm(r.y, C, ap.norm_w, ap.norm_b, r.n, B, C, ap.norm_eps, 0, f32, f.s);
+  rc = launch_layernorm(f.w.py, C, ap.norm_w, ap.norm_b, f.w.pn, B, C, ap.norm_eps, 0, f32, f.s);
   if (rc != RAJNI_OK) return rc;
-  rc = launch_linear(linear_args(f32, r.n, ap.fc1_w, ap.fc1_b, nullptr, r.hid, B, ap.hidden, C,
+  rc = launch_linear(linear_args(f32, f.w.pn, ap.fc1_w, ap.fc1_b, nullptr, f.w.phid, B, ap.hidden, C,
                                  ap.act == RAJNI_MLP_QUICK_GELU ? RAJNI_EPI_BIAS_QUICK_GELU : RAJNI_EPI_BIAS_GELU), f.s);
   if (rc != RAJNI_OK) return rc;
-  rajni_linear_args fc2 = linear_args(f32, r.hid, ap.fc2_w, ap.fc2_b, nullptr, r.y, B, C, ap.hidden, RAJNI_EPI_BIAS_RESID);
-  fc2.resid = r.y; fc2.ldr = C;
+  rajni_linear_args fc2 = linear_args(f32, f.w.phid, ap.fc2_w, ap.fc2_b, nullptr, f.w.py, B, C, ap.hidden, RAJNI_EPI_BIAS_RESID);
+  fc2.resid = f.w.py; fc2.ldr = C;
   rc = launch_linear(fc2, f.s);
   if (rc != RAJNI_OK) return rc;
   // timm forward_head: fc_norm behind the pool, or none - rajni_pool_norm's token form on [B, 1, C] fp32 rows with no norm in
   // front: with fc_norm_w NULL it is the one rounding to the model dtype (the caller's buffer on a headless plan)
   void* const row = headless(p) ? logits : (void*)f.w.clsn;
-  rc = launch_pool_norm(r.y, B, 1, C, RAJNI_POOL_TOKEN, nullptr, nullptr, 0.f, e.fc_norm_w, e.fc_norm_b, e.fc_norm_eps, row,
+  rc = launch_pool_norm(f.w.py, B, 1, C, RAJNI_POOL_TOKEN, nullptr, nullptr, 0.f, e.fc_norm_w, e.fc_norm_b, e.fc_norm_eps, row,
                         dt != RAJNI_F32, dt, f.s, 1);
   if (rc != RAJNI_OK) return rc;
   if (headless(p)) return RAJNI_OK;
@@ -566,186 +622,71 @@ int launch_pool_tail(const Fwd& f, const rajni_vit_attn_pool& ap, const PoolRows
 
 // src [B, Nf] = where each token of the stream that enters block `upto` (p.depth: the final stream) sat in the unpruned
 // sequence: the selections of the scheduled blocks in front of it (the forced one where a block has it), last block first
-int launch_source_idx_before(const rajni_vit_plan& p, int P, int upto, int32_t* src, int Nf, hipStream_t s, const rajni_vit_image* img) {
+int launch_source_idx_before(const Spec& c, int upto, int32_t* src, int Nf) {
+  const rajni_vit_plan& p = *c.p;
   std::vector<const int32_t*> idx;
   std::vector<int> width, nsrc;
   for (int i = upto - 1; i >= 0; --i) {
     const rajni_block& blk = p.blocks[i];
     if (blk.keep <= 0) continue;
     idx.push_back(blk.forced_keep_idx ? blk.forced_keep_idx : blk.keep_idx);
-    width.push_back(blk.keep + P);
-    nsrc.push_back(tokens_entering(p, P, i, img));
+    width.push_back(blk.keep + c.P);
+    nsrc.push_back(tokens_entering(c, i));
   }
-  return launch_source_idx(src, idx.data(), width.data(), nsrc.data(), (int)idx.size(), p.B, Nf, s);
+  return launch_source_idx(src, idx.data(), width.data(), nsrc.data(), (int)idx.size(), p.B, Nf, c.s);
 }
 
-// the whole forward; ext == nullptr (rajni_vit_forward) and an all-zero record enqueue the same launches, and so does
-// pre == nullptr (or a record with one prefix token) next to any ext
-int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre, const void* images,
-                void* logits, hipStream_t s, const rajni_vit_layers* lay = nullptr, const rajni_vit_image* img = nullptr,
-                const rajni_vit_query* qry = nullptr, const rajni_vit_attn_pool* ap = nullptr);
-
-}  // namespace
-
-extern "C" size_t rajni_vit_workspace_bytes_prefix(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix) {
-  if (!plan || plan->patch_size <= 0) return 0;
-  if (check_prefix(prefix, "rajni_vit_workspace_bytes_prefix") != RAJNI_OK) return 0;
-  rajni_vit_plan tmp = *plan;
-  tmp.workspace = nullptr;
-  return carve(tmp, prefix_count(prefix), head_row_count(prefix)).total;
+// Every refusal of the forward, before the first launch.  The order is part of the contract - callers match the first message:
+// the prefix record under the entry point's name; null pointers; the query record (whether there is a class row decides every
+// count); the pool record; the image record (every count below is against its grid); the layers record; then the plan, the
+// placement of what it points to, the ext record, the distilled head, the schedule, and last the workspace, carved here.
+int check_all(Spec& c, const void* images, const void* logits) {
+  int rc = check_prefix(c);
+  if (rc != RAJNI_OK) return rc;
+  RAJNI_REQUIRE(c.p && images && logits, RAJNI_ERR_INVALID, "rajni_vit_forward: null pointer");
+  const rajni_vit_plan& p = *c.p;
+  if (c.qry && (rc = check_query(c)) != RAJNI_OK) return rc;
+  if (c.ap && (rc = check_pool(c)) != RAJNI_OK) return rc;
+  if (c.img && (rc = check_image(c)) != RAJNI_OK) return rc;
+  if (c.lay && (rc = check_layers(c)) != RAJNI_OK) return rc;
+  if (c.dense_last && (rc = check_dense_last(c)) != RAJNI_OK) return rc;
+  if ((rc = check_plan(c)) != RAJNI_OK) return rc;
+  if ((rc = check_placement(p, images, logits)) != RAJNI_OK) return rc;
+  if (c.pre) RAJNI_REQUIRE_PLACED("rajni_vit_forward", {"reg_token", c.pre->reg_token, 16});
+  if (c.ext && (rc = check_ext(c)) != RAJNI_OK) return rc;
+  if ((rc = check_head_rows(c)) != RAJNI_OK) return rc;
+  if ((rc = check_schedule(c)) != RAJNI_OK) return rc;
+  c.w = carve(c);
+  RAJNI_REQUIRE(p.workspace != nullptr && p.workspace_bytes >= c.w.total, RAJNI_ERR_INVALID,
+                "rajni_vit_forward: workspace too small (%zu < %zu)", p.workspace_bytes, c.w.total);
+  return RAJNI_OK;
 }
 
-extern "C" size_t rajni_vit_workspace_bytes(const rajni_vit_plan* plan) { return rajni_vit_workspace_bytes_prefix(plan, nullptr); }
-
-extern "C" int rajni_vit_forward(const rajni_vit_plan* plan, const void* images, void* logits,
-                                 rajni_stream_t stream) {
-  return vit_forward(plan, nullptr, nullptr, images, logits, (hipStream_t)stream);
+// what the forward of this call needs in plan.workspace, 0 where the records that size it (prefix, image, query, pool) are
+// refused: the same checks and the same carve as the forward's, so the two cannot disagree
+size_t workspace_bytes(const Spec& c) {
+  if (!c.p || c.p->patch_size <= 0) return 0;
+  if (c.qry && query_form(*c.qry) != RAJNI_OK) return 0;
+  if (check_prefix(c) != RAJNI_OK || (c.img && check_image(c) != RAJNI_OK)) return 0;
+  if (c.ap && (!pool_hidden_ok(*c.ap) || c.p->B <= 0 || c.p->C <= 0)) return 0;
+  return carve(c).total;
 }
 
-extern "C" int rajni_vit_forward_ext(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const void* images, void* logits,
-                                     rajni_stream_t stream) {
-  return vit_forward(plan, ext, nullptr, images, logits, (hipStream_t)stream);
-}
-
-extern "C" int rajni_vit_forward_ext_prefix(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
-                                            const void* images, void* logits, rajni_stream_t stream) {
-  const int rc = check_prefix(prefix, "rajni_vit_forward_ext_prefix");
+// the whole forward; NULL records and records that say what NULL means enqueue the same launches
+int vit_forward(Spec f, const void* images, void* logits) {
+  int rc = check_all(f, images, logits);
   if (rc != RAJNI_OK) return rc;
-  return vit_forward(plan, ext, prefix, images, logits, (hipStream_t)stream);
-}
-
-extern "C" int rajni_vit_forward_layers(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
-                                        const rajni_vit_layers* layers, const void* images, void* logits, rajni_stream_t stream) {
-  if (!layers) return rajni_vit_forward_ext_prefix(plan, ext, prefix, images, logits, stream);
-  const int rc = check_prefix(prefix, "rajni_vit_forward_layers");
-  if (rc != RAJNI_OK) return rc;
-  return vit_forward(plan, ext, prefix, images, logits, (hipStream_t)stream, layers);
-}
-
-extern "C" size_t rajni_vit_workspace_bytes_image(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix, const rajni_vit_image* image) {
-  if (!image) return rajni_vit_workspace_bytes_prefix(plan, prefix);
-  if (!plan || plan->patch_size <= 0) return 0;
-  if (check_prefix(prefix, "rajni_vit_workspace_bytes_image") != RAJNI_OK || check_image(*plan, prefix, *image) != RAJNI_OK) return 0;
-  rajni_vit_plan tmp = *plan;
-  tmp.workspace = nullptr;
-  return carve(tmp, prefix_count(prefix), head_row_count(prefix), image).total;
-}
-
-extern "C" int rajni_vit_forward_image(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
-                                       const rajni_vit_layers* layers, const rajni_vit_image* image, const void* images, void* logits,
-                                       rajni_stream_t stream) {
-  if (!image) return rajni_vit_forward_layers(plan, ext, prefix, layers, images, logits, stream);
-  const int rc = check_prefix(prefix, "rajni_vit_forward_image");
-  if (rc != RAJNI_OK) return rc;
-  return vit_forward(plan, ext, prefix, images, logits, (hipStream_t)stream, layers, image);
-}
-
-// ---- include/rajni_hip_query.h
-extern "C" size_t rajni_vit_workspace_bytes_query(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix, const rajni_vit_image* image,
-                                                  const rajni_vit_query* query) {
-  if (!query || (query->class_token == 1 && query->query == RAJNI_QUERY_CLS)) return rajni_vit_workspace_bytes_image(plan, prefix, image);
-  if (!plan || plan->patch_size <= 0) return 0;
-  if ((query->class_token != 0 && query->class_token != 1) || (query->query != RAJNI_QUERY_CLS && query->query != RAJNI_QUERY_MEAN) ||
-      (query->class_token == 0 && query->query != RAJNI_QUERY_MEAN))
-    return 0;
-  const bool nocls = no_class_row(query);
-  if (check_prefix(prefix, "rajni_vit_workspace_bytes_query", nocls) != RAJNI_OK) return 0;
-  if (image && check_image(*plan, prefix, *image, query) != RAJNI_OK) return 0;
-  rajni_vit_plan tmp = *plan;
-  tmp.workspace = nullptr;
-  return carve(tmp, prefix_count(prefix, query), nocls ? 1 : head_row_count(prefix), image, query->query).total;
-}
-
-extern "C" int rajni_vit_forward_query(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
-                                       const rajni_vit_layers* layers, const rajni_vit_image* image, const rajni_vit_query* query,
-                                       const void* images, void* logits, rajni_stream_t stream) {
-  if (!query || (query->class_token == 1 && query->query == RAJNI_QUERY_CLS))
-    return rajni_vit_forward_image(plan, ext, prefix, layers, image, images, logits, stream);
-  const int rc = check_prefix(prefix, "rajni_vit_forward_query", no_class_row(query));
-  if (rc != RAJNI_OK) return rc;
-  return vit_forward(plan, ext, prefix, images, logits, (hipStream_t)stream, layers, image, query);
-}
-
-// ---- include/rajni_hip_attnpool.h
-extern "C" size_t rajni_vit_workspace_bytes_pool(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix, const rajni_vit_image* image,
-                                                 const rajni_vit_query* query, const rajni_vit_attn_pool* pool) {
-  const size_t base = rajni_vit_workspace_bytes_query(plan, prefix, image, query);
-  if (!pool || base == 0) return base;
-  if (pool->hidden <= 0 || pool->hidden % 64 != 0 || plan->B <= 0 || plan->C <= 0) return 0;
-  rajni_vit_plan tmp = *plan;
-  tmp.workspace = nullptr;
-  return carve_pool(tmp, *pool, base).total;
-}
-
-extern "C" int rajni_vit_forward_pool(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
-                                      const rajni_vit_layers* layers, const rajni_vit_image* image, const rajni_vit_query* query,
-                                      const rajni_vit_attn_pool* pool, const void* images, void* logits, rajni_stream_t stream) {
-  if (!pool) return rajni_vit_forward_query(plan, ext, prefix, layers, image, query, images, logits, stream);
-  const int rc = check_prefix(prefix, "rajni_vit_forward_pool", no_class_row(query));
-  if (rc != RAJNI_OK) return rc;
-  return vit_forward(plan, ext, prefix, images, logits, (hipStream_t)stream, layers, image, query, pool);
-}
-
-extern "C" void rajni_debug_set_last_block_all_rows(int on) { g_last_block_all_rows = on; }
-
-// 1 when the forward of this plan (with this ext / prefix record, either may be NULL) computes its last block for the rows the
-// head reads only (the CLS rows; rows 0 and 1 with head_rows == 2), 0 when for all rows: the eligibility test alone, on the
-// host, nothing launched and no device pointer followed
-extern "C" int rajni_debug_last_block_cls_rows(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix) {
-  if (!plan || !plan->blocks || plan->depth <= 0 || plan->patch_size <= 0) return 0;
-  const int last = plan->depth - 1;
-  return last_block_cls_rows(*plan, ext, last, tokens_entering(*plan, prefix_count(prefix), last)) ? 1 : 0;
-}
-
-namespace {
-
-int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre, const void* images,
-                void* logits, hipStream_t s, const rajni_vit_layers* lay, const rajni_vit_image* img, const rajni_vit_query* qry,
-                const rajni_vit_attn_pool* ap) {
-  RAJNI_REQUIRE(plan && images && logits, RAJNI_ERR_INVALID, "rajni_vit_forward: null pointer");
-  const rajni_vit_plan& p = *plan;
-  const bool dense_last = ext != nullptr && ext->pool == RAJNI_POOL_DENSE_LAST;
-  int rc = qry ? check_query(p, ext, *qry) : RAJNI_OK;   // first of all: whether there is a class row decides every count
-  if (rc != RAJNI_OK) return rc;
-  const bool nocls = no_class_row(qry);
-  rc = ap ? check_pool(p, ext, pre, nocls, *ap) : RAJNI_OK;
-  if (rc != RAJNI_OK) return rc;
-  const int qmode = query_mode(qry);
-  rc = img ? check_image(p, pre, *img, qry) : RAJNI_OK;   // every count below is against the record's grid
-  if (rc != RAJNI_OK) return rc;
-  rc = lay ? check_layers(p, ext, prefix_count(pre, qry), *lay, img) : RAJNI_OK;
-  if (rc != RAJNI_OK) return rc;
-  rc = dense_last ? check_dense_last(p, nocls ? nullptr : pre) : RAJNI_OK;
-  if (rc != RAJNI_OK) return rc;
-  rc = check_plan(p, ext != nullptr && ext->norm_absent != 0, nocls);
-  if (rc != RAJNI_OK) return rc;
-  rc = check_placement(p, images, logits);
-  if (rc != RAJNI_OK) return rc;
-  if (pre) RAJNI_REQUIRE_PLACED("rajni_vit_forward", {"reg_token", pre->reg_token, 16});
-  if (ext) {
-    rc = check_ext(p, *ext, ap != nullptr);
-    if (rc != RAJNI_OK) return rc;
-  }
-  rc = nocls ? RAJNI_OK : check_head_rows(p, ext, pre);
-  if (rc != RAJNI_OK) return rc;
-  const rajni_qk_affine* qkn = ext ? ext->qk_norm : nullptr;
-  const int P = prefix_count(pre, qry);   // prefix tokens: CLS + registers (or the dist token), never pruned; the registers alone without a class row
-  const int HR = nocls ? 1 : head_row_count(pre);   // rows of each image the head reads
-  rc = check_schedule(p, P, img);
-  if (rc != RAJNI_OK) return rc;
-  const Workspace w = carve(p, P, HR, img, qmode);
-  const PoolRows pool_rows = ap ? carve_pool(p, *ap, w.total) : PoolRows{nullptr, nullptr, nullptr, nullptr, w.total};
-  RAJNI_REQUIRE(p.workspace != nullptr && p.workspace_bytes >= pool_rows.total, RAJNI_ERR_INVALID,
-                "rajni_vit_forward: workspace too small (%zu < %zu)", p.workspace_bytes, pool_rows.total);
-  const int B = p.B, C = p.C, dt = p.dtype;
-  const Fwd f{p, w, (dt != RAJNI_F32 && !p.resid_bf16) ? 1 : 0, s,
-              (ext && ext->mlp_act == RAJNI_MLP_QUICK_GELU) ? RAJNI_EPI_BIAS_QUICK_GELU
-              : (ext && ext->mlp_act == RAJNI_MLP_SWIGLU) ? RAJNI_EPI_BIAS_SWIGLU : RAJNI_EPI_BIAS_GELU};
-  int N = tokens_entering(p, P, 0, img);
+  const rajni_vit_plan& p = *f.p;
+  const rajni_vit_ext* ext = f.ext;
+  const rajni_vit_layers* lay = f.lay;
+  const Workspace& w = f.w;
+  hipStream_t s = f.s;
+  const int B = p.B, C = p.C, dt = p.dtype, P = f.P, HR = f.HR, S0 = f.n0;
+  int N = f.n0;
 
   rc = launch_patch_embed(images, p.patch_w, p.patch_b, p.cls_token, p.pos_embed, p.pos_has_cls,
-                          w.xa, f.sf32, B, p.in_chans, image_height(p, img), image_width(p, img), p.patch_size, C, dt, w.cols, w.cols_bytes, s,
-                          P, nocls ? (P > 0 ? pre->reg_token : nullptr) : (P > 1 ? pre->reg_token : nullptr), nocls ? 0 : 1);
+                          w.xa, f.sf32, B, p.in_chans, f.height, f.width, p.patch_size, C, dt, w.cols, w.cols_bytes, s,
+                          P, f.reg_token, f.has_cls);
   if (rc != RAJNI_OK) return rc;
   if (ext && ext->norm_pre_w) {   // timm forward_features: x = norm_pre(x), written back into the stream
     rc = launch_layernorm_stream(w.xa, ext->norm_pre_w, ext->norm_pre_b, B * N, C, ext->norm_pre_eps, f.sf32, dt, s);
@@ -757,13 +698,10 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
     RAJNI_CHECK_LAUNCH("head_rows_idx_kernel");
   }
 
-  // rajni_vit_forward_layers: slab l is lay->out + l * slab_ld elements; `cap` walks the ascending capture list with the
+  // the layers record: slab l is lay->out + l * slab_ld elements; `cap` walks the ascending capture list with the
   // block loop, so slabs [cap, n) are the ones a block at or in front of the next capture still writes to
-  const int S0 = tokens_entering(p, P, 0, img);
-  const size_t slab_ld = lay ? (lay->slab_stride ? (size_t)lay->slab_stride : (size_t)B * S0 * C) : 0;
-  auto slab = [&](int l) { return static_cast<void*>(static_cast<char*>(lay->out) + (size_t)l * slab_ld * rajni_elem_bytes(dt)); };
+  auto slab = [&](int l) { return static_cast<void*>(static_cast<char*>(lay->out) + (size_t)l * f.slab_ld * rajni_elem_bytes(dt)); };
   int cap = 0;
-  const bool last_captured = lay && lay->blocks[lay->n - 1] == p.depth - 1;
 
   char* cur = w.xa;
   char* oth = w.xb;
@@ -773,11 +711,11 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
     const rajni_block& blk = p.blocks[i];
     if (p.token_counts) p.token_counts[i] = N;  // model.py:43
     const int M = B * N;
-    rc = layernorm(f, cur, blk.norm1_w, blk.norm1_b, M);
+    rc = layernorm(f, cur, blk.norm1_w, blk.norm1_b, M, nullptr, 0.f, 0.f);
     if (rc != RAJNI_OK) return rc;
     rc = launch_linear(qkv_args(f, blk, M), s);
     if (rc != RAJNI_OK) return rc;
-    if (qkn) {   // timm Attention.forward: q, k = q_norm(q), k_norm(k) - in place, so everything below reads normalised q and k
+    if (const rajni_qk_affine* qkn = f.qk_norm) {   // timm Attention.forward: q, k = q_norm(q), k_norm(k) - in place, so everything below reads normalised q and k
       rc = launch_qk_norm(w.qkv, qkn[i].q_norm_w, qkn[i].q_norm_b, qkn[i].k_norm_w, qkn[i].k_norm_b, M, p.H, p.D, ext->qk_eps, dt, s);
       if (rc != RAJNI_OK) return rc;
     }
@@ -795,7 +733,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
       cur = oth; N = 1;
       break;
     }
-    if (HR == 2 && last_block_cls_rows(p, ext, i, N, last_captured, nocls)) {
+    if (HR == 2 && last_block_cls_rows(f, i, N)) {
       // the distilled head reads rows 0 and 1: the first query tile (into w.xn, which QKV has consumed), its rows 0 and 1
       // gathered dense into w.att, and the ordinary tail as a pruned block that keeps {0, 1} - the proj epilogue gathers
       // the two residual rows through idx01 and the stream leaves [B, 2, C] in `oth`
@@ -810,7 +748,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
         cur = oth; N = 2;
         break;
       }
-    } else if (last_block_cls_rows(p, ext, i, N, last_captured, nocls)) {
+    } else if (last_block_cls_rows(f, i, N)) {
       // the all-rows kernels on the rows the head reads: the first query tile, proj on its CLS rows in place (stride N * C)
       const Tail t = tail_args(f, blk, AttnRows{B, cls_ld, nullptr, cls_ld, nullptr, 0, 0}, cur, oth);
       if (tail_ok(t)) {   // (a refused shape or stride: all rows below, as if this branch were not here)
@@ -831,7 +769,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
         const void* full = carried;
         if (recompute) {
           void* dst = blk.scores ? blk.scores : (void*)w.scf;
-          rc = launch_score_select(w.qkv, nullptr, B, N, p.H, p.D, 1e-6f, 0, dst, nullptr, nullptr, dt, s, nocls ? P : 1, w.sst, w.sst_bytes, qmode);
+          rc = launch_score_select(w.qkv, nullptr, B, N, p.H, p.D, 1e-6f, 0, dst, nullptr, nullptr, dt, s, f.nocls ? P : 1, w.sst, w.sst_bytes, f.qmode);
           if (rc != RAJNI_OK) return rc;
           full = dst;
         }
@@ -847,7 +785,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
       } else {
         if (recompute)
           rc = launch_score_select(w.qkv, nullptr, B, N, p.H, p.D, 1e-6f, blk.keep, blk.scores,
-                                   blk.keep_idx, blk.next_scores, dt, s, P, w.sst, w.sst_bytes, qmode);
+                                   blk.keep_idx, blk.next_scores, dt, s, P, w.sst, w.sst_bytes, f.qmode);
         else
           rc = launch_score_select(nullptr, carried, B, N, 0, 0, 0.f, blk.keep, nullptr,
                                    blk.keep_idx, blk.next_scores, dt, s, P);
@@ -871,14 +809,14 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
     if (rc != RAJNI_OK) return rc;
     // (slabs with fill = 1: the same rows, to every slab of a capture at or behind this block)
     const bool slabs_last = idx && lay && lay->fill == 1 && cap < lay->n;
-    if (idx && (dense_last || slabs_last)) {
+    if (idx && (f.dense_last || slabs_last)) {
       // the rows this block drops leave the stream here and keep the state they entered with: `cur` still holds it (the tail
       // gathered the kept rows into `oth`).  Where each entering token sat in the unpruned sequence goes to w.qkv, dead
       // between the tail and the next block's QKV GEMM (B * N * 4 bytes always fit); then the final norm of the dropped rows
       int32_t* src = reinterpret_cast<int32_t*>(w.qkv);
-      rc = launch_source_idx_before(p, P, i, src, N, s, img);
+      rc = launch_source_idx_before(f, i, src, N);
       if (rc != RAJNI_OK) return rc;
-      if (dense_last) {
+      if (f.dense_last) {
         rc = launch_layernorm_dropped(cur, idx, src, p.norm_w, p.norm_b, logits, B, N, Np, P, S0, C, p.ln_eps, f.sf32, dt, s);
         if (rc != RAJNI_OK) return rc;
       }
@@ -896,7 +834,7 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
       // a captured block: the stream behind it, scattered to slab `cap` through the map of the selections up to and including
       // this block's (w.qkv again: the launches above have read their map, in stream order)
       int32_t* src = reinterpret_cast<int32_t*>(w.qkv);
-      rc = launch_source_idx_before(p, P, i + 1, src, N, s, img);
+      rc = launch_source_idx_before(f, i + 1, src, N);
       if (rc != RAJNI_OK) return rc;
       rc = lay->norm ? launch_layernorm_dense(cur, src, p.norm_w, p.norm_b, slab(cap), B, N, S0, C, p.ln_eps, f.sf32, dt, s, lay->fill ? 0 : 1)
                      : launch_rows_dense_cast(cur, src, slab(cap), B, N, S0, C, f.sf32, dt, s, lay->fill ? 0 : 1);
@@ -909,21 +847,21 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
   // (with a pooled head, fc_norm or no norm: norm on every row that is pooled -> pool -> fc_norm, one kernel)
   // a headless plan: the same launch writes the caller's buffer instead of w.clsn, and there is no head GEMM
   void* const rowout = headless(p) ? logits : (void*)w.clsn;
-  if (ap) return launch_pool_tail(f, *ap, pool_rows, *ext, cur, N, logits);   // (check_pool: ext.pool is RAJNI_POOL_MAP)
-  if (ext && ext->pool == RAJNI_POOL_NONE)  // every surviving token through the final norm: [B, N, C]
+  if (f.ap) return launch_pool_tail(f, cur, N, logits);
+  if (f.pool == RAJNI_POOL_NONE)  // every surviving token through the final norm: [B, N, C]
     return launch_layernorm(cur, C, p.norm_w, p.norm_b, logits, B * N, C, p.ln_eps, f.sf32, dt, s);
-  if (ext && (ext->pool == RAJNI_POOL_DENSE || dense_last)) {
+  if (f.pool == RAJNI_POOL_DENSE || f.dense_last) {
     // [B, P + n, C]: token j of the final stream at the row it came from, zeros elsewhere (RAJNI_POOL_DENSE_LAST: the other
     // rows were written behind the blocks that dropped them and stay).  The composed selection lives in w.qkv, dead behind
     // the last block (B * N * 4 bytes always fit)
     int32_t* src = reinterpret_cast<int32_t*>(w.qkv);
-    rc = launch_source_idx_before(p, P, p.depth, src, N, s, img);
+    rc = launch_source_idx_before(f, p.depth, src, N);
     if (rc != RAJNI_OK) return rc;
     return launch_layernorm_dense(cur, src, p.norm_w, p.norm_b, logits, B, N, S0, C, p.ln_eps, f.sf32, dt, s,
-                                  dense_last ? 0 : 1);
+                                  f.dense_last ? 0 : 1);
   }
-  if (ext && (ext->pool != RAJNI_POOL_TOKEN || ext->fc_norm_w || ext->norm_absent))
-    rc = launch_pool_norm(cur, B, N, C, ext->pool, ext->norm_absent ? nullptr : p.norm_w, p.norm_b, p.ln_eps,
+  if (ext && (f.pool != RAJNI_POOL_TOKEN || ext->fc_norm_w || f.norm_absent))
+    rc = launch_pool_norm(cur, B, N, C, f.pool, f.norm_absent ? nullptr : p.norm_w, p.norm_b, p.ln_eps,
                           ext->fc_norm_w, ext->fc_norm_b, ext->fc_norm_eps, rowout, f.sf32, dt, s, P);
   else if (HR == 2) {
     // rows 0 and 1 of every image, normalised side by side: row b of [B, 2C].  A stream that still holds all N rows (a last
@@ -945,3 +883,64 @@ int vit_forward(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajn
 }
 
 }  // namespace
+
+// The entry points (include/rajni_hip*.h): each passes the records it takes.  A NULL trailing record behaves as the
+// next-narrower entry point, including the name a prefix refusal carries: make_spec names the call by its widest record.
+extern "C" int rajni_vit_forward(const rajni_vit_plan* plan, const void* images, void* logits, rajni_stream_t stream) {
+  return vit_forward(make_spec(ENTRY_FORWARD, plan, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream), images, logits);
+}
+extern "C" int rajni_vit_forward_ext(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const void* images, void* logits,
+                                     rajni_stream_t stream) {
+  return vit_forward(make_spec(ENTRY_FORWARD, plan, ext, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream), images, logits);
+}
+extern "C" int rajni_vit_forward_ext_prefix(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
+                                            const void* images, void* logits, rajni_stream_t stream) {
+  return vit_forward(make_spec(ENTRY_FORWARD, plan, ext, prefix, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream), images, logits);
+}
+extern "C" int rajni_vit_forward_layers(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
+                                        const rajni_vit_layers* layers, const void* images, void* logits, rajni_stream_t stream) {
+  return vit_forward(make_spec(ENTRY_FORWARD, plan, ext, prefix, layers, nullptr, nullptr, nullptr, (hipStream_t)stream), images, logits);
+}
+extern "C" int rajni_vit_forward_image(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
+                                       const rajni_vit_layers* layers, const rajni_vit_image* image, const void* images, void* logits,
+                                       rajni_stream_t stream) {
+  return vit_forward(make_spec(ENTRY_FORWARD, plan, ext, prefix, layers, image, nullptr, nullptr, (hipStream_t)stream), images, logits);
+}
+extern "C" int rajni_vit_forward_query(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
+                                       const rajni_vit_layers* layers, const rajni_vit_image* image, const rajni_vit_query* query,
+                                       const void* images, void* logits, rajni_stream_t stream) {
+  return vit_forward(make_spec(ENTRY_FORWARD, plan, ext, prefix, layers, image, query, nullptr, (hipStream_t)stream), images, logits);
+}
+extern "C" int rajni_vit_forward_pool(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
+                                      const rajni_vit_layers* layers, const rajni_vit_image* image, const rajni_vit_query* query,
+                                      const rajni_vit_attn_pool* pool, const void* images, void* logits, rajni_stream_t stream) {
+  return vit_forward(make_spec(ENTRY_FORWARD, plan, ext, prefix, layers, image, query, pool, (hipStream_t)stream), images, logits);
+}
+extern "C" size_t rajni_vit_workspace_bytes(const rajni_vit_plan* plan) {
+  return workspace_bytes(make_spec(ENTRY_SIZE, plan, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+}
+extern "C" size_t rajni_vit_workspace_bytes_prefix(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix) {
+  return workspace_bytes(make_spec(ENTRY_SIZE, plan, nullptr, prefix, nullptr, nullptr, nullptr, nullptr, nullptr));
+}
+extern "C" size_t rajni_vit_workspace_bytes_image(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix, const rajni_vit_image* image) {
+  return workspace_bytes(make_spec(ENTRY_SIZE, plan, nullptr, prefix, nullptr, image, nullptr, nullptr, nullptr));
+}
+extern "C" size_t rajni_vit_workspace_bytes_query(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix, const rajni_vit_image* image,
+                                                  const rajni_vit_query* query) {
+  return workspace_bytes(make_spec(ENTRY_SIZE, plan, nullptr, prefix, nullptr, image, query, nullptr, nullptr));
+}
+extern "C" size_t rajni_vit_workspace_bytes_pool(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix, const rajni_vit_image* image,
+                                                 const rajni_vit_query* query, const rajni_vit_attn_pool* pool) {
+  return workspace_bytes(make_spec(ENTRY_SIZE, plan, nullptr, prefix, nullptr, image, query, pool, nullptr));
+}
+
+extern "C" void rajni_debug_set_last_block_all_rows(int on) { g_last_block_all_rows = on; }
+
+// 1 when the forward of this plan (with this ext / prefix record, either may be NULL) computes its last block for the rows the
+// head reads only (the CLS rows; rows 0 and 1 with head_rows == 2), 0 when for all rows: the eligibility test alone, on the
+// host, nothing launched and no device pointer followed
+extern "C" int rajni_debug_last_block_cls_rows(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix) {
+  if (!plan || !plan->blocks || plan->depth <= 0 || plan->patch_size <= 0) return 0;
+  const Spec c = make_spec(ENTRY_FORWARD, plan, ext, prefix, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return last_block_cls_rows(c, plan->depth - 1, tokens_entering(c, plan->depth - 1)) ? 1 : 0;
+}

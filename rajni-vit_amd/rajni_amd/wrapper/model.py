@@ -31,7 +31,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -39,6 +39,56 @@ import torch.nn as nn
 from .. import _native as nat
 from .. import ops
 from .attention import RAJNIAttention, qk_norm_modules
+
+
+class PlanRefs(NamedTuple):
+    """what a native plan points to, kept alive with it"""
+    blocks: object
+    tc: object        # token_counts, written by every forward
+    ws: object        # the workspace
+    W: object         # the packed weights: a stale optimistic launch keeps them alive
+    ext: object       # rajni_vit_ext, or None
+    qk: object
+    pre: object       # rajni_vit_prefix, or None
+
+
+class PlanInput(NamedTuple):
+    """the records that depend on the input and the model's head, each None where absent, and the patch grid"""
+    img: object       # rajni_vit_image
+    pos: object       # the position rows the plan points to
+    gh: int
+    gw: int
+    qry: object       # rajni_vit_query
+    apr: object       # rajni_vit_attn_pool
+
+
+class PlanEntry(NamedTuple):
+    """one cached plan of RAJNIViTWrapper (callers outside this module index it by position)"""
+    key: tuple
+    plan: object
+    refs: PlanRefs
+    bufs: dict        # per scheduled block: keep_idx, next_scores, scores
+    counts: list
+    mode: object
+    out_shape: tuple
+    layers: object    # (blocks array, norm, fill, slab shape): the layers record minus `out`, or None
+    input: PlanInput
+
+
+# The native entry points, narrowest first: each takes the records of the one in front of it and one more, and a call goes
+# through the one that takes the widest record it has - a pool record: _pool, else a query record: _query, else an image
+# record: _image, else layers: _layers, else prefix: _ext_prefix, else ext: _ext, else the plain one.  (The symbol is part of
+# the interface: nat.check puts it into the error message.)
+_FORWARDS = ("rajni_vit_forward", "rajni_vit_forward_ext", "rajni_vit_forward_ext_prefix", "rajni_vit_forward_layers",
+             "rajni_vit_forward_image", "rajni_vit_forward_query", "rajni_vit_forward_pool")     # (ext, pre, lay, img, qry, apr)
+_SIZES = ("rajni_vit_workspace_bytes", "rajni_vit_workspace_bytes_prefix", "rajni_vit_workspace_bytes_image",
+          "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_pool")                   # (pre, img, qry, apr)
+
+
+def _native_call(symbols, *records):
+    """(symbol, record arguments) for records given in the order the entry points take them, None where absent"""
+    n = max((i + 1 for i, rec in enumerate(records) if rec is not None), default=0)
+    return symbols[n], [C.byref(rec) if rec is not None else None for rec in records[:n]]
 
 
 def normalise_schedule(schedule) -> Dict[int, Dict]:
@@ -396,7 +446,7 @@ class RAJNIViTWrapper(nn.Module):
         if self._plan is None:
             return {}
         out = {}
-        for i, bufs in self._plan[3].items():
+        for i, bufs in self._plan.bufs.items():
             idx = self._forced.get(i, bufs["keep_idx"])
             d = {"keep_idx": idx.long(), "next_scores": bufs["next_scores"]}
             # a stage ranks freshly computed scores iff `update` or nothing was carried into it
@@ -406,7 +456,7 @@ class RAJNIViTWrapper(nn.Module):
             if bufs["scores"] is not None and recomputed:
                 d["scores"] = bufs["scores"]
             elif not recomputed:
-                d["scores"] = self._plan[3][i - 1]["next_scores"]
+                d["scores"] = self._plan.bufs[i - 1]["next_scores"]
             out[i] = d
         return out
 
@@ -912,7 +962,7 @@ class RAJNIViTWrapper(nn.Module):
             self._check_features(d)
         key = (B, S, device, dtype, self._weights_key, tuple(sorted(self._forced)), self._trace_scores, self._resid_bf16,
                self._cls_only_last) + ((query, has_cls) if (query, has_cls) != ("cls", True) else ()) + (P, full_mode)
-        if self._plan is not None and self._plan[0] == key:
+        if self._plan is not None and self._plan.key == key:
             return self._plan
         if key in self._plans:
             self._plan = self._plans[key]
@@ -1015,29 +1065,14 @@ class RAJNIViTWrapper(nn.Module):
                 setattr(apr, name, nat.ptr(pw_[name]))
             apr.norm_eps, apr.hidden, apr.heads = pd["eps"], pd["hidden_pad"], pd["heads"]
             apr.act = nat.MLP_QUICK_GELU if pd["act"] == "quick_gelu" else nat.MLP_GELU
-        if apr is not None:
-            ref = lambda rec: C.byref(rec) if rec is not None else None
-            nbytes = nat.lib().rajni_vit_workspace_bytes_pool(C.byref(plan), ref(pre), ref(img), ref(qry), C.byref(apr))
-            if nbytes == 0:       # a record is refused: say why (the forward's own refusal, nothing is launched)
-                dry = nat.VitExt()
-                dry.pool = nat.POOL_MAP
-                nat.check(nat.lib().rajni_vit_forward_pool(C.byref(plan), C.byref(dry), ref(pre), None, ref(img), ref(qry),
-                                                           C.byref(apr), 16, 16, None), "rajni_vit_forward_pool")
-                raise nat.NativeError("rajni_vit_workspace_bytes_pool refused the plan")
-        elif qry is not None:
-            ref = lambda rec: C.byref(rec) if rec is not None else None
-            nbytes = nat.lib().rajni_vit_workspace_bytes_query(C.byref(plan), ref(pre), ref(img), C.byref(qry))
-            if nbytes == 0:       # a record is refused: say why (the forward's own refusal, nothing is launched)
-                nat.check(nat.lib().rajni_vit_forward_query(C.byref(plan), None, ref(pre), None, ref(img), C.byref(qry), 16, 16, None),
-                          "rajni_vit_forward_query")
-        elif img is not None:
-            nbytes = nat.lib().rajni_vit_workspace_bytes_image(C.byref(plan), C.byref(pre) if pre is not None else None, C.byref(img))
-            if nbytes == 0:       # the record is refused: say why (the forward's own refusal, nothing is launched)
-                nat.check(nat.lib().rajni_vit_forward_image(C.byref(plan), None, C.byref(pre) if pre is not None else None, None,
-                                                            C.byref(img), 16, 16, None), "rajni_vit_forward_image")
-        else:
-            nbytes = (nat.lib().rajni_vit_workspace_bytes(C.byref(plan)) if pre is None
-                      else nat.lib().rajni_vit_workspace_bytes_prefix(C.byref(plan), C.byref(pre)))
+        symbol, records = _native_call(_SIZES, pre, img, qry, apr)
+        nbytes = getattr(nat.lib(), symbol)(C.byref(plan), *records)
+        if nbytes == 0 and symbol not in _SIZES[:2]:
+            # the image, query or pool record is refused: say why (the forward's own refusal; nothing is launched)
+            dry = nat.VitExt(pool=nat.POOL_MAP) if apr is not None else None
+            forward, records = _native_call(_FORWARDS, dry, pre, None, img, qry, apr)
+            nat.check(getattr(nat.lib(), forward)(C.byref(plan), *records, 16, 16, None), forward)
+            raise nat.NativeError(f"{symbol} refused the plan")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
         plan.workspace, plan.workspace_bytes = ws.data_ptr(), nbytes
         ext = qk = None
@@ -1067,14 +1102,8 @@ class RAJNIViTWrapper(nn.Module):
         if full_mode is not mode:      # the layers record (rajni_vit_layers) minus `out`, and the slabs' shape
             cap_arr = (C.c_int * len(caps))(*caps)
             layers = (cap_arr, int(lnorm), int(lfill == "last"), (len(caps), B, n0, d["C"]))
-        # W: a stale optimistic launch keeps its weights alive
-        # (existing callers index entry[0..4] and unpack entry[2] as seven objects: mode and out_shape go behind `counts`,
-        # the layers record behind those)
-        # (the image record and the position rows the plan points to, with the grid, last)
-        # (the query record behind the grid: index 4 of the last element)
-        # (the attention-pool record behind the query record: index 5 of the last element)
-        self._plan = (key, plan, (blocks, tc, ws, W, ext, qk, pre), bufs, counts, full_mode, out_shape, layers,
-                      (img, pos, gh, gw, qry, apr))
+        self._plan = PlanEntry(key, plan, PlanRefs(blocks, tc, ws, W, ext, qk, pre), bufs, counts, full_mode, out_shape, layers,
+                               PlanInput(img, pos, gh, gw, qry, apr))
         if len(self._plans) >= 4:     # workspaces are large: keep only a few batch shapes alive
             self._plans.pop(next(iter(self._plans)))
         self._plans[key] = self._plan
@@ -1108,7 +1137,7 @@ class RAJNIViTWrapper(nn.Module):
         """logits [B, num_classes]; on a headless model (head = nn.Identity, timm num_classes=0) the pooled feature [B, C],
         fc_norm(pool(norm(x))) on the pruned token set - timm's forward of such a model"""
         out, entry = self._run(x, "logits")
-        plan = entry[1]
+        plan = entry.plan
         if plan.num_classes == 0:
             return out
         return out[:, : plan.num_classes] if plan.logits_ld != plan.num_classes else out
@@ -1136,17 +1165,17 @@ class RAJNIViTWrapper(nn.Module):
 
     def _selection_stats(self, entry, x, exit_block: bool):
         """`source_idx` (and `exit_block`) of the forward just run into get_last_stats(): torch ops on the device, no host sync"""
-        n0 = entry[4][0]
+        n0 = entry.counts[0]
         src = None            # the selections composed on the device, last stage first: no host sync
-        for i in sorted(entry[3], reverse=True):
-            idx = self._forced.get(i, entry[3][i]["keep_idx"]).long()
+        for i in sorted(entry.bufs, reverse=True):
+            idx = self._forced.get(i, entry.bufs[i]["keep_idx"]).long()
             src = idx if src is None else torch.gather(idx, 1, src)
         if src is None:
             src = torch.arange(n0, device=x.device).expand(x.shape[0], n0)
         self._last_stats["source_idx"] = src.to(torch.int32).contiguous()
         if exit_block:
             self._last_stats["exit_block"] = compose_exit_block(
-                {i: self._forced.get(i, entry[3][i]["keep_idx"]) for i in entry[3]}, x.shape[0], n0, entry[1].depth, x.device)
+                {i: self._forced.get(i, entry.bufs[i]["keep_idx"]) for i in entry.bufs}, x.shape[0], n0, entry.plan.depth, x.device)
 
     @torch.no_grad()
     def forward_intermediates(self, x: torch.Tensor, indices=None, return_prefix_tokens: bool = False, norm: bool = False,
@@ -1178,8 +1207,8 @@ class RAJNIViTWrapper(nn.Module):
         base = "logits" if intermediates_only else ("dense_last" if fill == "last" else "dense")
         (final, slabs), entry = self._run(x, ("layers", base, caps, bool(norm), fill))
         self._selection_stats(entry, x, exit_block=True)
-        P = entry[0][-2]
-        B, (gh, gw), Cdim = x.shape[0], entry[8][2:4], entry[1].C
+        P = entry.key[-2]
+        B, gh, gw, Cdim = x.shape[0], entry.input.gh, entry.input.gw, entry.plan.C
         inter = []
         for l in range(len(caps)):
             spatial = slabs[l, :, P:]
@@ -1227,64 +1256,18 @@ class RAJNIViTWrapper(nn.Module):
         B, S = x.shape[0], (x.shape[-1] if x.shape[-1] == x.shape[-2] else (x.shape[-2], x.shape[-1]))
         with nat.device_guard(x.device):
             def launch(entry):
-                plan = entry[1]
-                out = torch.empty(entry[6], dtype=dtype, device=x.device)
-                ext, pre = entry[2][4], entry[2][6]
-                ref = lambda rec: C.byref(rec) if rec is not None else None
-                if entry[8][5] is not None:   # an attention-pool record (global_pool='map'): every record through rajni_vit_forward_pool
-                    lay = slabs = None
-                    if entry[7] is not None:
-                        cap_arr, lnorm, lfill, slab_shape = entry[7]
-                        slabs = torch.empty(slab_shape, dtype=dtype, device=x.device)
-                        lay = nat.VitLayers()
-                        lay.n, lay.blocks, lay.norm, lay.fill, lay.out, lay.slab_stride = len(cap_arr), cap_arr, lnorm, lfill, slabs.data_ptr(), 0
-                    nat.check(nat.lib().rajni_vit_forward_pool(C.byref(plan), ref(ext), ref(pre), ref(lay), ref(entry[8][0]),
-                                                               ref(entry[8][4]), C.byref(entry[8][5]), x.data_ptr(), out.data_ptr(),
-                                                               nat.stream_ptr(x.device)), "rajni_vit_forward_pool")
-                    return out if lay is None else (out, slabs)
-                if entry[8][4] is not None:   # a query record (the mean query, or no class row): every record through rajni_vit_forward_query
-                    lay = slabs = None
-                    if entry[7] is not None:
-                        cap_arr, lnorm, lfill, slab_shape = entry[7]
-                        slabs = torch.empty(slab_shape, dtype=dtype, device=x.device)
-                        lay = nat.VitLayers()
-                        lay.n, lay.blocks, lay.norm, lay.fill, lay.out, lay.slab_stride = len(cap_arr), cap_arr, lnorm, lfill, slabs.data_ptr(), 0
-                    nat.check(nat.lib().rajni_vit_forward_query(C.byref(plan), ref(ext), ref(pre), ref(lay), ref(entry[8][0]),
-                                                                C.byref(entry[8][4]), x.data_ptr(), out.data_ptr(),
-                                                                nat.stream_ptr(x.device)), "rajni_vit_forward_query")
-                    return out if lay is None else (out, slabs)
-                if entry[8][0] is not None:   # a rectangular input: every record through rajni_vit_forward_image
-                    lay = slabs = None
-                    if entry[7] is not None:
-                        cap_arr, lnorm, lfill, slab_shape = entry[7]
-                        slabs = torch.empty(slab_shape, dtype=dtype, device=x.device)
-                        lay = nat.VitLayers()
-                        lay.n, lay.blocks, lay.norm, lay.fill, lay.out, lay.slab_stride = len(cap_arr), cap_arr, lnorm, lfill, slabs.data_ptr(), 0
-                    nat.check(nat.lib().rajni_vit_forward_image(C.byref(plan), ref(ext), ref(pre), ref(lay), C.byref(entry[8][0]),
-                                                                x.data_ptr(), out.data_ptr(), nat.stream_ptr(x.device)),
-                              "rajni_vit_forward_image")
-                    return out if lay is None else (out, slabs)
-                if entry[7] is not None:      # forward_intermediates: the slabs beside `out`, one allocation
-                    cap_arr, lnorm, lfill, slab_shape = entry[7]
+                out = torch.empty(entry.out_shape, dtype=dtype, device=x.device)
+                lay = slabs = None
+                if entry.layers is not None:      # forward_intermediates: the slabs beside `out`, one allocation
+                    cap_arr, lnorm, lfill, slab_shape = entry.layers
                     slabs = torch.empty(slab_shape, dtype=dtype, device=x.device)
                     lay = nat.VitLayers()
                     lay.n, lay.blocks, lay.norm, lay.fill, lay.out, lay.slab_stride = len(cap_arr), cap_arr, lnorm, lfill, slabs.data_ptr(), 0
-                    nat.check(nat.lib().rajni_vit_forward_layers(C.byref(plan), C.byref(ext) if ext is not None else None,
-                                                                 C.byref(pre) if pre is not None else None, C.byref(lay),
-                                                                 x.data_ptr(), out.data_ptr(), nat.stream_ptr(x.device)),
-                              "rajni_vit_forward_layers")
-                    return out, slabs
-                if pre is not None:
-                    nat.check(nat.lib().rajni_vit_forward_ext_prefix(C.byref(plan), C.byref(ext) if ext is not None else None,
-                                                                     C.byref(pre), x.data_ptr(), out.data_ptr(),
-                                                                     nat.stream_ptr(x.device)), "rajni_vit_forward_ext_prefix")
-                elif ext is None:
-                    nat.check(nat.lib().rajni_vit_forward(C.byref(plan), x.data_ptr(), out.data_ptr(),
-                                                          nat.stream_ptr(x.device)), "rajni_vit_forward")
-                else:
-                    nat.check(nat.lib().rajni_vit_forward_ext(C.byref(plan), C.byref(ext), x.data_ptr(), out.data_ptr(),
-                                                              nat.stream_ptr(x.device)), "rajni_vit_forward_ext")
-                return out
+                symbol, records = _native_call(_FORWARDS, entry.refs.ext, entry.refs.pre, lay, entry.input.img, entry.input.qry,
+                                               entry.input.apr)
+                nat.check(getattr(nat.lib(), symbol)(C.byref(entry.plan), *records, x.data_ptr(), out.data_ptr(),
+                                                     nat.stream_ptr(x.device)), symbol)
+                return out if lay is None else (out, slabs)
             # Optimistic launch: with a plan of this batch shape at hand the kernels are enqueued FIRST and the check
             # that the base model's weights are still the packed ones (a walk over ~150 parameters, ~0.1 ms of Python)
             # runs while the GPU works - in the sync -> forward -> sync metric of evaluate_model that check would
@@ -1296,7 +1279,7 @@ class RAJNIViTWrapper(nn.Module):
             # same wrapper concurrently is not supported (the reference is one-forward-at-a-time too).
             cached = self._plan
             # (the mode is the key's last element: a logits plan must not be launched into a feature buffer)
-            if cached is not None and cached[0][:4] == (B, S, x.device, dtype) and cached[0][-1] == mode:
+            if cached is not None and cached.key[:4] == (B, S, x.device, dtype) and cached.key[-1] == mode:
                 logits = launch(cached)
                 entry = self._build_plan(B, S, x.device, dtype, mode)
                 if entry is not cached:
@@ -1304,6 +1287,6 @@ class RAJNIViTWrapper(nn.Module):
             else:
                 entry = self._build_plan(B, S, x.device, dtype, mode)
                 logits = launch(entry)
-        plan, tc = entry[1], entry[2][1]
+        plan, tc = entry.plan, entry.refs.tc
         self._last_stats = {"token_counts": [int(tc[i]) for i in range(plan.depth)]}   # model.py:68
         return logits, entry
