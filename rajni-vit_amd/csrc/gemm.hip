@@ -217,6 +217,17 @@ __device__ __forceinline__ void store_u4(void* ptr, const uint4& v) {
   else *reinterpret_cast<uint4*>(ptr) = v;
 }
 
+// Vector stores per wave that an epilogue path issues for an INTERIOR tile of mi row groups (16 rows x 64 columns each).  The
+// stream kernels let a tile's first counted wait leave that many outstanding (NSTORE, through tile_stores below), so count and
+// code must not drift apart: a store loop's trip count is the constant counted here, spelled-out stores carry a static_assert.
+constexpr int LINE_ROWS = 8;          // a whole-line access of a wave: 8 rows x 128 bytes per instruction (the LDS transpose below)
+constexpr int ROW_STORES_SEC = 2;     // accumulator layout, per row: 2 x 8 16-bit values (MAP_SEC) ...
+constexpr int ROW_STORES_NAT = 4;     // ... or 4 float4 (natural order)
+constexpr int RM_HALVES = 2;          // ROWMAJOR, ROWMAJOR_WIDE: a row group's 64 fp32 columns leave as 2 halves of 128 bytes
+constexpr int stores_acc_layout(bool nat, int mi) { return (nat ? ROW_STORES_NAT : ROW_STORES_SEC) * mi; }
+constexpr int stores_rowmajor(int mi) { return RM_HALVES * (16 / LINE_ROWS) * mi; }
+constexpr int stores_tstore(int mi) { return (16 / LINE_ROWS) * mi; }   // TSTORE: a row group's 64 16-bit columns are one line per row
+
 // One output row m, columns nb..nb+15 (v = accumulators + bias on entry).
 // SF32: the residual-stream tensors this launch touches (R and Y of RESID, Y of PATCH) are fp32.
 // v[0..7] are columns nbA..nbA+7 and v[8..15] columns nbB..nbB+7 of output row m (nbB = nbA + 32: the
@@ -276,6 +287,7 @@ __device__ __forceinline__ void epilogue_row(const GemmParams& p, int m, int nbA
   constexpr bool OUT32 = SF32 && (EPI == EPI_RESID || EPI == EPI_PATCH);
   const long ybase = orow * p.ldc;
   if (full) {
+    static_assert(ROW_STORES_SEC == 2, "the two stores of a full row below");
     store8s<OUT32, A>(p.Y, ybase + nbA, v);
     store8s<OUT32, A>(p.Y, ybase + nbB, v + 8);
   } else {
@@ -319,9 +331,10 @@ constexpr int col_map(int epi, bool sf32) { return epi == EPI_GELU8 ? MAP_F8 : n
 #endif
 constexpr bool resid_nat(int epi, bool sf32) { return nat_order(epi, sf32) && epi == EPI_RESID; }
 // fp32-stream RESID of gemm_bf16_tn_stream (mi = row groups per wave: 4 on 256 x 128, 8 on 256 x 256):
-//   ROWMAJOR       256 x 128, both weight formats: residual rows prefetched in full lines (prefetch_resid_rowmajor)
-//   ROWMAJOR_WIDE  256 x 256: loads in the epilogue, group by group; bf16 weights only (with the fp8-weight scale on top the
-//                  instantiation spills - it keeps the accumulator-layout epilogue)
+//   ROWMAJOR       256 x 128, 16-bit and fp8 weights alike: residual rows prefetched in full lines (prefetch_resid_rowmajor)
+//   ROWMAJOR_WIDE  256 x 256: loads in the epilogue, group by group; the only one of the two that excludes fp8 weights (with
+//                  the weight scale on top that instantiation spills: 256 x 256 with fp8 weights keeps the accumulator-layout
+//                  epilogue)
 constexpr bool epi_rowmajor(int epi, bool sf32, int mi) { return resid_nat(epi, sf32) && mi <= 4; }
 constexpr bool epi_rowmajor_wide(int epi, bool sf32, int mi, bool w8) { return resid_nat(epi, sf32) && mi > 4 && !w8; }
 constexpr bool epi_tstore(int epi) { return RAJNI_TSTORE && (epi == EPI_BIAS || epi_act(epi)); }
@@ -333,6 +346,26 @@ constexpr int f8_scratch_bytes(int epi, bool sf32) {   // f8::gemm_f8_tn_stream:
 }
 constexpr int f8w_scratch_bytes(int epi) { return (epi == EPI_BIAS && RAJNI_F8W_LINES) ? 4096 : 0; }   // f8w::gemm_f8_tn_wide
 constexpr int LDS_MAX_BYTES = 160 * 1024;   // per workgroup on gfx950
+
+// The per-wave transpose through that scratch, rows of 128 bytes: a lane WRITES 16-byte chunks of the row it owns in the MFMA
+// layout (lines_put), the wave passes lines_turn, and every read instruction (lines_get: row 8 j + (lane >> 3), chunk lane & 7)
+// fetches LINE_ROWS rows x 128 bytes, which meet global memory as whole lines.  Chunk c of row r sits in slot c ^ (r & 7) of
+// its row, a row being one half of a 256-byte bank row.  Conflict free both ways: the eight contiguous lanes of a ds_write_b128
+// group write one chunk of eight consecutive rows - eight keys, eight slots; the sixteen lanes of a ds_read_b128 group read
+// the eight chunks of two consecutive rows, the two halves of the bank row.  A block ends with a plain wave barrier behind
+// its reads: they are issued before the next block's writes (LDS is in order per wave).
+__device__ __forceinline__ void lines_put(char* scratch, int row, int chunk, const bf16x8& v) {
+  const int slot = chunk ^ (row & 7);
+  *reinterpret_cast<bf16x8*>(scratch + row * 128 + slot * 16) = v;
+}
+__device__ __forceinline__ void lines_turn() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+__device__ __forceinline__ bf16x8 lines_get(const char* scratch, int row, int chunk) {
+  const int slot = chunk ^ (row & 7);
+  return *reinterpret_cast<const bf16x8*>(scratch + row * 128 + slot * 16);
+}
 
 template <int MAP>
 __device__ __forceinline__ int out_col(int n0w, int g, int j) {
@@ -400,7 +433,7 @@ __device__ __forceinline__ void epilogue_row_nat(const GemmParams& p, int m, int
   const A* P = reinterpret_cast<const A*>(p.pos);
   float* Y = reinterpret_cast<float*>(p.Y);
 #pragma unroll
-  for (int ni = 0; ni < 4; ++ni) {
+  for (int ni = 0; ni < ROW_STORES_NAT; ++ni) {   // one float4 store per n-tile
     const int c = n0w + 16 * ni + 4 * g;
     float* vv = v + 4 * ni;
     if (c + 4 <= p.N) {
@@ -509,19 +542,46 @@ __device__ __forceinline__ void prefetch_resid(const GemmParams& p, ResidPrefetc
   }
 }
 
-// Vector stores per wave that epilogue_tile issues for an INTERIOR tile of mi row groups (16 rows x 64 columns each), by
-// path.  The stream kernels let their first counted wait of a tile leave that many stores outstanding (NSTORE there), so
-// the count of every path an instantiation can take has to stay at or above what tile_stores returns.
-constexpr int stores_acc_layout(bool nat, int mi) { return (nat ? 4 : 2) * mi; }   // per row: 4 float4 (natural order) or 2 x 8 16-bit values
-constexpr int stores_rowmajor(int mi) { return 2 * 2 * mi; }   // ROWMAJOR, ROWMAJOR_WIDE: per row group 2 column halves x 2 x (8 rows x 128 bytes)
-constexpr int stores_tstore(int mi) { return 2 * mi; }         // TSTORE: per row group 2 x (8 rows x 128 bytes)
-constexpr int tile_stores(int epi, bool sf32, int mi, bool rowmajor, bool tstore) {   // the fewest over the instantiation's paths
+// The fewest vector stores per wave over the paths an instantiation's epilogue_tile can take for an INTERIOR tile (the
+// per-path counts stand ahead of epilogue_row): NSTORE of the stream kernels.
+constexpr int tile_stores(int epi, bool sf32, int mi, bool rowmajor, bool tstore) {
   if (epi == EPI_SWIGLU) return mi;                      // epilogue_tile_gated: one 16-byte store per row group
   int n = stores_acc_layout(nat_order(epi, sf32), mi);   // the path every instantiation has (no scratch, gathered rows)
   if (rowmajor && stores_rowmajor(mi) < n) n = stores_rowmajor(mi);
   if (tstore && stores_tstore(mi) < n) n = stores_tstore(mi);
   return n;
 }
+
+// Column constants of a lane on the read side of the fp32-stream transposes (ROWMAJOR, ROWMAJOR_WIDE): its 4 columns n0w + 32 hc
+// + 4 cc .. of either half hc.  fp8 weights: out = resid + gamma * (acc * ws + bias); resid + (gamma * ws) * acc ... is NOT used -
+// gamma * ws would round differently from the other tilings' (acc * ws) + bias, and sub-batches (128 x 128) must match bit for bit.
+template <bool W8>
+struct LineConsts {
+  float bias[RM_HALVES][4], gam[RM_HALVES][4], wsc[RM_HALVES][W8 ? 4 : 1];
+  __device__ __forceinline__ void load(const GemmParams& p, int n0w, int cc) {
+#pragma unroll
+    for (int hc = 0; hc < RM_HALVES; ++hc) {
+      const int n = n0w + 32 * hc + 4 * cc;
+      const float4 bq = p.bias != nullptr ? *reinterpret_cast<const float4*>(p.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 gq = p.gamma != nullptr ? *reinterpret_cast<const float4*>(p.gamma + n) : make_float4(1.f, 1.f, 1.f, 1.f);
+      bias[hc][0] = bq.x; bias[hc][1] = bq.y; bias[hc][2] = bq.z; bias[hc][3] = bq.w;
+      gam[hc][0] = gq.x; gam[hc][1] = gq.y; gam[hc][2] = gq.z; gam[hc][3] = gq.w;
+      if constexpr (W8) {
+        const float4 wq = *reinterpret_cast<const float4*>(p.wscale + n);
+        wsc[hc][0] = wq.x; wsc[hc][1] = wq.y; wsc[hc][2] = wq.z; wsc[hc][3] = wq.w;
+      }
+    }
+  }
+  // one float4 of outputs: accumulators a of column half hc onto the residual values r
+  __device__ __forceinline__ float4 out(int hc, const f32x4& a, const float4& r) const {
+    float4 o;
+    o.x = fmaf(gam[hc][0], W8 ? fmaf(a[0], wsc[hc][0], bias[hc][0]) : a[0] + bias[hc][0], r.x);
+    o.y = fmaf(gam[hc][1], W8 ? fmaf(a[1], wsc[hc][1], bias[hc][1]) : a[1] + bias[hc][1], r.y);
+    o.z = fmaf(gam[hc][2], W8 ? fmaf(a[2], wsc[hc][2], bias[hc][2]) : a[2] + bias[hc][2], r.z);
+    o.w = fmaf(gam[hc][3], W8 ? fmaf(a[3], wsc[hc][3], bias[hc][3]) : a[3] + bias[hc][3], r.w);
+    return o;
+  }
+};
 
 // shared tail of every 16-bit tiling: bias/gamma for this lane's columns, then one row per m-tile (A: bf16_t or f16_t,
 // the format of the 16-bit outputs and of the residual stream when it is not fp32)
@@ -534,54 +594,28 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, f32x4 (&acc)[
   if constexpr (NAT && EPI == EPI_RESID && MI <= 4) {
     if (scratch != nullptr && pre.valid) {
       // ROWMAJOR epilogue of an interior tile (see prefetch_resid_rowmajor): per row group and column half, the wave's 16 x 32
-      // accumulator block goes through its 2 KiB LDS scratch - written in the MFMA layout (lane = row l15, columns 4 g..),
-      // read back as 8 rows x 128 bytes per instruction (16-byte chunk c of row r in slot c ^ (r & 7): the eight contiguous
-      // lanes of a ds_write_b128 group hit eight slots, the sixteen lanes of a ds_read_b128 group sixteen of a 256-byte bank row) - meets the residual rows loaded in that shape, and leaves as whole 128-byte lines.
+      // accumulator block goes through its 2 KiB LDS scratch, meets the residual rows loaded in that shape, and leaves as lines.
       int lane = g * 16 + l15;
       asm volatile("" : "+v"(lane));                              // (not hoisted out of the tile loop: see prefetch_resid_rowmajor)
       const int rr = lane >> 3, cc = lane & 7;                    // read-back: row rr (+ 8 j), 16-byte chunk cc of the half
-      // column constants of the lane's 2 x 4 columns; fp8 weights: out = resid + gamma * (acc * ws + bias) = resid + (gamma
-      // * ws) * acc ... is NOT used - the product gamma * ws would round differently from the other tilings' (acc * ws) +
-      // bias, and sub-batches (128 x 128 tiling) must reproduce the full batch bit for bit
-      float bias[2][4], gam[2][4], wsc[2][W8 ? 4 : 1];
-#pragma unroll
-      for (int hc = 0; hc < 2; ++hc) {
-        const int n = n0w + 32 * hc + 4 * cc;
-        const float4 bq = p.bias != nullptr ? *reinterpret_cast<const float4*>(p.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float4 gq = p.gamma != nullptr ? *reinterpret_cast<const float4*>(p.gamma + n) : make_float4(1.f, 1.f, 1.f, 1.f);
-        bias[hc][0] = bq.x; bias[hc][1] = bq.y; bias[hc][2] = bq.z; bias[hc][3] = bq.w;
-        gam[hc][0] = gq.x; gam[hc][1] = gq.y; gam[hc][2] = gq.z; gam[hc][3] = gq.w;
-        if constexpr (W8) {
-          const float4 wq = *reinterpret_cast<const float4*>(p.wscale + n);
-          wsc[hc][0] = wq.x; wsc[hc][1] = wq.y; wsc[hc][2] = wq.z; wsc[hc][3] = wq.w;
-        }
-      }
+      LineConsts<W8> k;
+      k.load(p, n0w, cc);
       __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): every load so far has landed, on every path (see the note below)
       float* Y = reinterpret_cast<float*>(p.Y) + n0w + 4 * cc;
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-        for (int hc = 0; hc < 2; ++hc) {
+        for (int hc = 0; hc < RM_HALVES; ++hc) {
 #pragma unroll
-          for (int q = 0; q < 2; ++q) {   // n-tile 2 hc + q: chunk 4 q + g of row l15
-            const int slot = (4 * q + g) ^ (l15 & 7);
-            *reinterpret_cast<bf16x8*>(scratch + l15 * 128 + slot * 16) = __builtin_bit_cast(bf16x8, acc[2 * hc + q][mi]);
+          for (int q = 0; q < 2; ++q) lines_put(scratch, l15, 4 * q + g, __builtin_bit_cast(bf16x8, acc[2 * hc + q][mi]));   // n-tile 2 hc + q
+          lines_turn();
+#pragma unroll
+          for (int j = 0; j < 16 / LINE_ROWS; ++j) {
+            const int row = LINE_ROWS * j + rr;
+            const f32x4 a = __builtin_bit_cast(f32x4, lines_get(scratch, row, cc));
+            *reinterpret_cast<float4*>(Y + (long)(m_base + mi * 16 + row) * p.ldc + 32 * hc) = k.out(hc, a, pre.r[mi][2 * hc + j]);
           }
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
           __builtin_amdgcn_wave_barrier();
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const int row = 8 * j + rr, slot = cc ^ (row & 7);
-            const f32x4 a = __builtin_bit_cast(f32x4, *reinterpret_cast<const bf16x8*>(scratch + row * 128 + slot * 16));
-            const float4 r = pre.r[mi][2 * hc + j];
-            float4 o;
-            o.x = fmaf(gam[hc][0], W8 ? fmaf(a[0], wsc[hc][0], bias[hc][0]) : a[0] + bias[hc][0], r.x);
-            o.y = fmaf(gam[hc][1], W8 ? fmaf(a[1], wsc[hc][1], bias[hc][1]) : a[1] + bias[hc][1], r.y);
-            o.z = fmaf(gam[hc][2], W8 ? fmaf(a[2], wsc[hc][2], bias[hc][2]) : a[2] + bias[hc][2], r.z);
-            o.w = fmaf(gam[hc][3], W8 ? fmaf(a[3], wsc[hc][3], bias[hc][3]) : a[3] + bias[hc][3], r.w);
-            *reinterpret_cast<float4*>(Y + (long)(m_base + mi * 16 + row) * p.ldc + 32 * hc) = o;
-          }
-          __builtin_amdgcn_wave_barrier();   // the block's reads are issued before the next block's writes (LDS is in order per wave)
         }
       return;
     }
@@ -594,15 +628,8 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, f32x4 (&acc)[
       int lane = g * 16 + l15;
       asm volatile("" : "+v"(lane));
       const int rr = lane >> 3, cc = lane & 7;
-      float bias[2][4], gam[2][4];
-#pragma unroll
-      for (int hc = 0; hc < 2; ++hc) {
-        const int n = n0w + 32 * hc + 4 * cc;
-        const float4 bq = p.bias != nullptr ? *reinterpret_cast<const float4*>(p.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float4 gq = p.gamma != nullptr ? *reinterpret_cast<const float4*>(p.gamma + n) : make_float4(1.f, 1.f, 1.f, 1.f);
-        bias[hc][0] = bq.x; bias[hc][1] = bq.y; bias[hc][2] = bq.z; bias[hc][3] = bq.w;
-        gam[hc][0] = gq.x; gam[hc][1] = gq.y; gam[hc][2] = gq.z; gam[hc][3] = gq.w;
-      }
+      LineConsts<false> k;
+      k.load(p, n0w, cc);
       const float* R = reinterpret_cast<const float*>(p.R) + n0w + 4 * cc;
       float* Y = reinterpret_cast<float*>(p.Y) + n0w + 4 * cc;
 #pragma unroll
@@ -615,24 +642,15 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, f32x4 (&acc)[
           r[2 + j] = *reinterpret_cast<const float4*>(R + ro + 32);
         }
 #pragma unroll
-        for (int hc = 0; hc < 2; ++hc) {
+        for (int hc = 0; hc < RM_HALVES; ++hc) {
 #pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            const int slot = (4 * q + g) ^ (l15 & 7);
-            *reinterpret_cast<bf16x8*>(scratch + l15 * 128 + slot * 16) = __builtin_bit_cast(bf16x8, acc[2 * hc + q][mi]);
-          }
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
+          for (int q = 0; q < 2; ++q) lines_put(scratch, l15, 4 * q + g, __builtin_bit_cast(bf16x8, acc[2 * hc + q][mi]));
+          lines_turn();
 #pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const int row = 8 * j + rr, slot = cc ^ (row & 7);
-            const f32x4 a = __builtin_bit_cast(f32x4, *reinterpret_cast<const bf16x8*>(scratch + row * 128 + slot * 16));
-            float4 o;
-            o.x = fmaf(gam[hc][0], a[0] + bias[hc][0], r[2 * hc + j].x);
-            o.y = fmaf(gam[hc][1], a[1] + bias[hc][1], r[2 * hc + j].y);
-            o.z = fmaf(gam[hc][2], a[2] + bias[hc][2], r[2 * hc + j].z);
-            o.w = fmaf(gam[hc][3], a[3] + bias[hc][3], r[2 * hc + j].w);
-            *reinterpret_cast<float4*>(Y + (long)(m_base + mi * 16 + row) * p.ldc + 32 * hc) = o;
+          for (int j = 0; j < 16 / LINE_ROWS; ++j) {
+            const int row = LINE_ROWS * j + rr;
+            const f32x4 a = __builtin_bit_cast(f32x4, lines_get(scratch, row, cc));
+            *reinterpret_cast<float4*>(Y + (long)(m_base + mi * 16 + row) * p.ldc + 32 * hc) = k.out(hc, a, r[2 * hc + j]);
           }
           __builtin_amdgcn_wave_barrier();
         }
@@ -682,24 +700,22 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, f32x4 (&acc)[
         if (scratch != nullptr) {
           // whole 128-byte lines: the wave's 16 x 64 bf16 block (one line per row) through its 2 KiB LDS scratch - written as
           // the lane's two 16-byte pieces (chunks g and 4 + g of row l15), read back 8 rows x 128 bytes per instruction
-          // (same swizzle as the fp32-stream transpose above: conflict free both ways)
           int lane = g * 16 + l15;
           asm volatile("" : "+v"(lane));
           const int rr = lane >> 3, cc = lane & 7;
-          const int key = l15 & 7;
-          *reinterpret_cast<bf16x8*>(scratch + l15 * 128 + ((g ^ key) << 4)) = __builtin_bit_cast(bf16x8, pack8<A>(v));
-          *reinterpret_cast<bf16x8*>(scratch + l15 * 128 + (((4 + g) ^ key) << 4)) = __builtin_bit_cast(bf16x8, pack8<A>(v + 8));
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
+          lines_put(scratch, l15, g, __builtin_bit_cast(bf16x8, pack8<A>(v)));
+          lines_put(scratch, l15, 4 + g, __builtin_bit_cast(bf16x8, pack8<A>(v + 8)));
+          lines_turn();
 #pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const int row = 8 * j + rr;
-            const uint4 q = __builtin_bit_cast(uint4, *reinterpret_cast<const bf16x8*>(scratch + row * 128 + ((cc ^ (row & 7)) << 4)));
+          for (int j = 0; j < 16 / LINE_ROWS; ++j) {
+            const int row = LINE_ROWS * j + rr;
+            const uint4 q = __builtin_bit_cast(uint4, lines_get(scratch, row, cc));
             store_u4<RAJNI_FC1_NT && epi_act(EPI)>(Y + (long)(m_base + mi * 16 + row) * p.ldc + n0w + 8 * cc, q);
           }
           __builtin_amdgcn_wave_barrier();
         } else {
           A* row = Y + (long)(m_base + mi * 16 + l15) * p.ldc;
+          static_assert(ROW_STORES_SEC == 2, "the two stores of a row below");
           store_u4<RAJNI_FC1_NT && epi_act(EPI)>(row + ca, pack8<A>(v));
           store_u4<RAJNI_FC1_NT && epi_act(EPI)>(row + cb, pack8<A>(v + 8));
         }
@@ -738,7 +754,7 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, f32x4 (&acc)[
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
+        for (int ni = 0; ni < ROW_STORES_NAT; ++ni) {
           float4 o;
           o.x = fmaf(gam[4 * ni + 0], sb(acc[ni][mi][0], 4 * ni + 0), pre.r[mi][ni].x);
           o.y = fmaf(gam[4 * ni + 1], sb(acc[ni][mi][1], 4 * ni + 1), pre.r[mi][ni].y);
@@ -826,6 +842,67 @@ __device__ __forceinline__ int xcd_tile_of(int v, int total) {
 }
 __device__ __forceinline__ int xcd_tile(int total) { return xcd_tile_of(blockIdx.x, total); }
 
+// Tile order of the stream kernels.  An XCD works through a contiguous range of tile ids, its 32 CUs on 32 consecutive ones.
+// With id = (row tile, column tile) column-fastest, those 32 tiles span ALL column tiles: every XCD
+// streams the whole W once per round, and W (4.7 MB for FC1) does not stay in a 4 MB L2 next to the X
+// panels - measured 387 MB fetched per FC1 launch for 63 MB of operands.  Instead the columns are cut
+// into blocks of `nblk` column tiles and the ids run (block, row tile, column in block): an XCD stays in
+// one block for many rounds (its W slice stays L2 resident), at the price of reading X once per block.
+__device__ __forceinline__ void stream_tile_mn(const GemmParams& p, int tiles_m, int t, int& tm, int& tn) {
+  if (p.nblk >= p.tiles_n) { tm = t / p.tiles_n; tn = t - tm * p.tiles_n; return; }
+  const int per = p.nblk * tiles_m, blk = t / per, r = t - blk * per;
+  const int left = p.tiles_n - blk * p.nblk, nb = left < p.nblk ? left : p.nblk;
+  const int rr = r / nb;
+  tm = rr; tn = blk * p.nblk + (r - rr * nb);
+}
+
+// DMA source (K offset 0, swizzled) of a lane's 16 bytes of a W staging piece: chunk `unit` of tile row `row` = global row `grow`.
+// 16-bit weights: 8 rows x 128 bytes per piece (row lane >> 3, chunk lane & 7); fp8: 16 rows x 64 bytes (lane >> 2, lane & 3).
+template <int MAP, bool W8>
+__device__ __forceinline__ const char* w_row_src(const GemmParams& p, long grow, int row, int unit) {
+  if constexpr (W8) return reinterpret_cast<const char*>(p.W) + grow * p.ldw + ((unit ^ w_key8<MAP>(row)) << 4);
+  else return reinterpret_cast<const char*>(p.W) + (grow * p.ldw + (unit ^ w_key<MAP>(row)) * 8) * 2;
+}
+
+namespace wide { __device__ __forceinline__ int key_x(int row) { return (row >> 1) & 7; } }   // swizzle key of an X tile row (128-byte rows)
+
+// Staging of the two fp8 x fp8 kernels (gemm_f8.h): rows of 128 bytes, a piece = 1 KiB = 8 rows, wave w stages X pieces XP w ..
+// and W pieces PW w .. of a 256-row X tile and the BN-row W tile behind it (at X_BYTES).  One source pointer per piece and lane:
+// row r_in = lane >> 3, chunk pch = lane & 7 swizzled with the row's key (key_w(row) for W).  X rows are clamped to M - 1
+// (duplicates are computed but never stored); W is allocated with its rows padded to a multiple of 256.
+template <int BN, int XP, int PW, typename KeyW>
+__device__ __forceinline__ void byte_tile_point_at(const GemmParams& p, int tm, int tn, int wave, int r_in, int pch, KeyW key_w,
+                                                   const char* (&xp)[XP], const char* (&wp)[PW]) {
+#pragma unroll
+  for (int i = 0; i < XP; ++i) {
+    const int row = (wave * XP + i) * 8 + r_in;
+    int m = tm * 256 + row;
+    if (m > p.M - 1) m = p.M - 1;
+    xp[i] = reinterpret_cast<const char*>(p.X) + (long)m * p.lda + ((pch ^ wide::key_x(row)) << 4);
+  }
+#pragma unroll
+  for (int i = 0; i < PW; ++i) {
+    const int row = (wave * PW + i) * 8 + r_in;
+    wp[i] = reinterpret_cast<const char*>(p.W) + (long)(tn * BN + row) * p.ldw + ((pch ^ key_w(row)) << 4);
+  }
+}
+// piece q of this wave (X 0 .. XP-1, then W), K byte offset k0, into the stage at dx
+template <int X_BYTES, int XP, int PW>
+__device__ __forceinline__ void byte_tile_dma_piece(const char* const (&xp)[XP], const char* const (&wp)[PW], int wave, int q,
+                                                    int k0, char* dx) {
+  if (q < XP)
+    __builtin_amdgcn_global_load_lds(GLB_PTR(xp[q] + k0), LDS_PTR(dx + (wave * XP + q) * 1024), 16, 0, 0);
+  else
+    __builtin_amdgcn_global_load_lds(GLB_PTR(wp[q - XP] + k0), LDS_PTR(dx + X_BYTES + (wave * PW + q - XP) * 1024), 16, 0, 0);
+}
+
+// RAJNI_GEMM_STAMPS builds: the four s_memtime values of a tile (tools/gemm_stamps.py, tools/f8_stamps.py)
+__device__ __forceinline__ void write_stamps(const GemmParams& p, int tile, unsigned long long t0, unsigned long long t1,
+                                             unsigned long long t2, unsigned long long t3) {
+  unsigned long long* o = p.stamps + (size_t)tile * 4;
+  o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3;
+}
+
 // global source of the 16-byte chunk (row m, K offset k..) of the X operand; ET = element type
 template <int ALOAD, typename ET = bf16_t>
 struct XSource {
@@ -876,7 +953,6 @@ struct XSource {
 namespace wide {
 constexpr int BM = 256, BK = 64;
 constexpr int X_BYTES = BM * BK * 2;            // 32 KiB
-__device__ __forceinline__ int key_x(int row) { return (row >> 1) & 7; }
 
 template <int WN_, int NS_, bool W8_ = false, int NW_ = 8> struct Cfg {   // WN_ = 64-column groups of the tile
   static constexpr int BN = WN_ * 64;
@@ -951,20 +1027,8 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_bf16_tn_stream(const Gem
   //   * going to the next tile is `pointer += scalar delta` - no second pointer set, nothing for the
   //     compiler to hoist (it used to precompute the next tile's 6 pointers at the start of every tile).
   auto tile_m0 = [&](int tm_) { return tm_ * BM + BM > p.M ? p.M - BM : tm_ * BM; };   // host: M >= 256
-  // Tile order.  An XCD works through a contiguous range of tile ids, its 32 CUs on 32 consecutive ones.
-  // With id = (row tile, column tile) column-fastest, those 32 tiles span ALL column tiles: every XCD
-  // streams the whole W once per round, and W (4.7 MB for FC1) does not stay in a 4 MB L2 next to the X
-  // panels - measured 387 MB fetched per FC1 launch for 63 MB of operands.  Instead the columns are cut
-  // into blocks of `nblk` column tiles and the ids run (block, row tile, column in block): an XCD stays in
-  // one block for many rounds (its W slice stays L2 resident), at the price of reading X once per block.
   const int tiles_m = p.total_tiles / p.tiles_n;
-  auto tile_mn = [&](int t, int& tm_, int& tn_) {
-    if (p.nblk >= p.tiles_n) { tm_ = t / p.tiles_n; tn_ = t - tm_ * p.tiles_n; return; }
-    const int per = p.nblk * tiles_m, blk = t / per, r = t - blk * per;
-    const int left = p.tiles_n - blk * p.nblk, nb = left < p.nblk ? left : p.nblk;
-    const int rr = r / nb;
-    tm_ = rr; tn_ = blk * p.nblk + (r - rr * nb);
-  };
+  auto tile_mn = [&](int t, int& tm_, int& tn_) { stream_tile_mn(p, tiles_m, t, tm_, tn_); };
   XSource<ALOAD> xs[ALOAD == ALOAD_PLAIN ? 1 : C::XP];   // fused im2col loader: one source per piece
   const char* xp[2];                                 // plain loader: even and odd pieces (16 rows apart each)
   const char* ws[C::NPW];
@@ -989,15 +1053,9 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_bf16_tn_stream(const Gem
     }
 #pragma unroll
     for (int i = 0; i < C::NPW; ++i) {
-      if constexpr (W8) {
-        const int row = (wave * C::PW + i) * 16 + (lane >> 2);
-        const long grow = GATED ? gated_w_row<false>(row, p.N, tn * BNO) : (long)(tn * C::BN + row);
-        ws[i] = reinterpret_cast<const char*>(p.W) + grow * p.ldw + (((lane & 3) ^ w_key8<MAP>(row)) << 4);
-      } else {
-        const int row = (wave * C::PW + i) * 8 + r_in;
-        const long grow = GATED ? gated_w_row<false>(row, p.N, tn * BNO) : (long)(tn * C::BN + row);
-        ws[i] = reinterpret_cast<const char*>(p.W) + (grow * p.ldw + (pch ^ w_key<MAP>(row)) * 8) * 2;
-      }
+      const int row = W8 ? (wave * C::PW + i) * 16 + (lane >> 2) : (wave * C::PW + i) * 8 + r_in;
+      const long grow = GATED ? gated_w_row<false>(row, p.N, tn * BNO) : (long)(tn * C::BN + row);
+      ws[i] = w_row_src<MAP, W8>(p, grow, row, W8 ? lane & 3 : pch);
     }
   };
   auto advance = [&](int from, int to) {   // retarget the DMA from tile `from` to tile `to`
@@ -1174,10 +1232,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_bf16_tn_stream(const Gem
 #ifdef RAJNI_GEMM_STAMPS
     if (p.stamps != nullptr && wave == 0) {
       const unsigned long long ts3 = __builtin_amdgcn_s_memtime();
-      if (lane == 0) {
-        unsigned long long* o = p.stamps + (size_t)tile * 4;
-        o[0] = ts0; o[1] = ts0; o[2] = ts2; o[3] = ts3;
-      }
+      if (lane == 0) write_stamps(p, tile, ts0, ts0, ts2, ts3);
     }
 #endif
     prev_full = inter;
@@ -1227,15 +1282,9 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_tn_128x128(const GemmParams 
   }
 #pragma unroll
   for (int i = 0; i < PW; ++i) {
-    if constexpr (W8) {
-      const int row = (wave * PW + i) * 16 + (lane >> 2);
-      const long grow = GATED ? gated_w_row<false>(row, p.N, tn * (BN / 2)) : (long)(n0 + row);
-      ws[i] = reinterpret_cast<const char*>(p.W) + grow * p.ldw + (((lane & 3) ^ w_key8<MAP>(row)) << 4);
-    } else {
-      const int row = (wave * PW + i) * 8 + r_in;
-      const long grow = GATED ? gated_w_row<false>(row, p.N, tn * (BN / 2)) : (long)(n0 + row);
-      ws[i] = reinterpret_cast<const char*>(p.W) + (grow * p.ldw + (pch ^ w_key<MAP>(row)) * 8) * 2;
-    }
+    const int row = W8 ? (wave * PW + i) * 16 + (lane >> 2) : (wave * PW + i) * 8 + r_in;
+    const long grow = GATED ? gated_w_row<false>(row, p.N, tn * (BN / 2)) : (long)(n0 + row);
+    ws[i] = w_row_src<MAP, W8>(p, grow, row, W8 ? lane & 3 : pch);
   }
   auto stage = [&](int kt, int buf) {
     char* sx = smem + buf * STAGE_BYTES;

@@ -59,6 +59,20 @@ __device__ __forceinline__ unsigned pack4_e4m3(float a, float b, float c, float 
   r = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, r, true);
   return (unsigned)r;
 }
+// the 16 e4m3 bytes of an EPI_GELU8 output row piece: gelu(v[0..15]) * inv, saturated and rounded
+__device__ __forceinline__ uint4 gelu_e4m3x16(const float (&v)[16], float inv) {
+  float y[16];
+#pragma unroll
+  for (int j = 0; j < 16; j += 4) {
+    f32x2 ta = f32x2{v[j], v[j + 1]}, tb = f32x2{v[j + 2], v[j + 3]};
+    gelu_pk4(ta, tb);
+    y[j] = ta[0] * inv; y[j + 1] = ta[1] * inv; y[j + 2] = tb[0] * inv; y[j + 3] = tb[1] * inv;
+  }
+  uint4 q;
+  q.x = pack4_e4m3(y[0], y[1], y[2], y[3]);   q.y = pack4_e4m3(y[4], y[5], y[6], y[7]);
+  q.z = pack4_e4m3(y[8], y[9], y[10], y[11]); q.w = pack4_e4m3(y[12], y[13], y[14], y[15]);
+  return q;
+}
 
 template <int EPI, bool SF32, int TAG = 0>
 __global__ void __launch_bounds__(512, 2) gemm_f8_tn_stream(const GemmParams p) {
@@ -69,39 +83,16 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_stream(const GemmParams p) 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tiles_m = p.total_tiles / p.tiles_n;
-  auto tile_mn = [&](int t, int& tm_, int& tn_) {   // (N block, row tile, column in block): see gemm_bf16_tn_stream
-    if (p.nblk >= p.tiles_n) { tm_ = t / p.tiles_n; tn_ = t - tm_ * p.tiles_n; return; }
-    const int per = p.nblk * tiles_m, blk = t / per, r = t - blk * per;
-    const int left = p.tiles_n - blk * p.nblk, nb = left < p.nblk ? left : p.nblk;
-    const int rr = r / nb;
-    tm_ = rr; tn_ = blk * p.nblk + (r - rr * nb);
-  };
   // ---- staging: a piece = 8 rows x 128 B; wave w stages X pieces 4w..4w+3 and W pieces 2w, 2w+1
   const char* xp[XP];
   const char* wp[PW];
   const int r_in = lane >> 3, pch = lane & 7;
   auto point_at = [&](int tile) {
     int tm, tn;
-    tile_mn(tile, tm, tn);
-#pragma unroll
-    for (int i = 0; i < XP; ++i) {
-      const int row = (wave * XP + i) * 8 + r_in;
-      int m = tm * BM + row;
-      if (m > p.M - 1) m = p.M - 1;   // clamp: duplicates are computed but never stored
-      xp[i] = reinterpret_cast<const char*>(p.X) + (long)m * p.lda + ((pch ^ key_x(row)) << 4);
-    }
-#pragma unroll
-    for (int i = 0; i < PW; ++i) {
-      const int row = (wave * PW + i) * 8 + r_in;
-      wp[i] = reinterpret_cast<const char*>(p.W) + (long)(tn * BN + row) * p.ldw + ((pch ^ w_key<MAP>(row)) << 4);
-    }
+    stream_tile_mn(p, tiles_m, tile, tm, tn);
+    byte_tile_point_at<BN>(p, tm, tn, wave, r_in, pch, [](int row) { return w_key<MAP>(row); }, xp, wp);
   };
-  auto dma_piece = [&](int q, int k0, char* dx) {
-    if (q < XP)
-      __builtin_amdgcn_global_load_lds(GLB_PTR(xp[q] + k0), LDS_PTR(dx + (wave * XP + q) * 1024), 16, 0, 0);
-    else
-      __builtin_amdgcn_global_load_lds(GLB_PTR(wp[q - XP] + k0), LDS_PTR(dx + X_BYTES + (wave * PW + q - XP) * 1024), 16, 0, 0);
-  };
+  auto dma_piece = [&](int q, int k0, char* dx) { byte_tile_dma_piece<X_BYTES>(xp, wp, wave, q, k0, dx); };
   // ---- fragment addresses (chunks 2g, 2g+1 of the lane's row; one swizzle key per operand, see gemm_bf16_tn_stream)
   const int wm = wave / WN, wn = wave % WN;
   const int l15 = lane & 15, g = lane >> 4;
@@ -114,18 +105,19 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_stream(const GemmParams p) 
     xo[h] = xr0 * KB + (((2 * g + h) ^ key_x(xr0)) << 4);
     wo[h] = X_BYTES + wr0 * KB + (((2 * g + h) ^ w_key<MAP>(wr0)) << 4);
   }
+  // the two 16-byte halves of X fragment i (row group i) / W fragment i (n-tile i) in the stage at sb
+  auto x_frag = [&](const char* sb, int i) {
+    return Frag{*reinterpret_cast<const bf16x8*>(sb + xo[0] + i * 16 * KB), *reinterpret_cast<const bf16x8*>(sb + xo[1] + i * 16 * KB)};
+  };
+  auto w_frag = [&](const char* sb, int i) {
+    return Frag{*reinterpret_cast<const bf16x8*>(sb + wo[0] + w_ni_off(i)), *reinterpret_cast<const bf16x8*>(sb + wo[1] + w_ni_off(i))};
+  };
   auto read_frags = [&](Frag (&xf)[MI], Frag (&wf)[NI], int st) {
     const char* sb = smem + st * STAGE_BYTES;
 #pragma unroll
-    for (int i = 0; i < MI; ++i) {
-      xf[i].lo = *reinterpret_cast<const bf16x8*>(sb + xo[0] + i * 16 * KB);
-      xf[i].hi = *reinterpret_cast<const bf16x8*>(sb + xo[1] + i * 16 * KB);
-    }
+    for (int i = 0; i < MI; ++i) xf[i] = x_frag(sb, i);
 #pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      wf[i].lo = *reinterpret_cast<const bf16x8*>(sb + wo[0] + w_ni_off(i));
-      wf[i].hi = *reinterpret_cast<const bf16x8*>(sb + wo[1] + w_ni_off(i));
-    }
+    for (int i = 0; i < NI; ++i) wf[i] = w_frag(sb, i);
   };
 
   f32x4 acc[4][MI];   // [ni][mi]
@@ -146,10 +138,8 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_stream(const GemmParams p) 
       for (int ni = 0; ni < NI; ++ni)
         acc[ni][mi] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wv[ni], xv, acc[ni][mi], 0, 0, 0, 0, 0, 0);
       if constexpr (READ) {
-        xn[mi].lo = *reinterpret_cast<const bf16x8*>(sb + xo[0] + mi * 16 * KB);
-        xn[mi].hi = *reinterpret_cast<const bf16x8*>(sb + xo[1] + mi * 16 * KB);
-        wn_[mi].lo = *reinterpret_cast<const bf16x8*>(sb + wo[0] + w_ni_off(mi));     // MI == NI: one W fragment per group
-        wn_[mi].hi = *reinterpret_cast<const bf16x8*>(sb + wo[1] + w_ni_off(mi));
+        xn[mi] = x_frag(sb, mi);
+        wn_[mi] = w_frag(sb, mi);     // MI == NI: one W fragment per group
       }
 #pragma unroll
       for (int q = mi * PIECES / MI; q < (mi + 1) * PIECES / MI; ++q) dma_piece(q, k0, dx);
@@ -185,7 +175,7 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_stream(const GemmParams p) 
     const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
 #endif
     int tm, tn;
-    tile_mn(tile, tm, tn);
+    stream_tile_mn(p, tiles_m, tile, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
     const bool inter = m0 + BM <= p.M && n0 + BN <= p.N;
     const int vn = v + gridDim.x;
@@ -271,15 +261,7 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_stream(const GemmParams p) 
         float y[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) y[j] = fmaf(acc[j >> 2][mi][j & 3], ws[j], bs[j]);
-#pragma unroll
-        for (int j = 0; j < 16; j += 4) {
-          f32x2 ta = f32x2{y[j], y[j + 1]}, tb = f32x2{y[j + 2], y[j + 3]};
-          gelu_pk4(ta, tb);
-          y[j] = ta[0] * inv[mi]; y[j + 1] = ta[1] * inv[mi]; y[j + 2] = tb[0] * inv[mi]; y[j + 3] = tb[1] * inv[mi];
-        }
-        uint4 q;
-        q.x = pack4_e4m3(y[0], y[1], y[2], y[3]);   q.y = pack4_e4m3(y[4], y[5], y[6], y[7]);
-        q.z = pack4_e4m3(y[8], y[9], y[10], y[11]); q.w = pack4_e4m3(y[12], y[13], y[14], y[15]);
+        const uint4 q = gelu_e4m3x16(y, inv[mi]);
         unsigned char* row = Y + (long)m * p.ldc + c0;
         if (full) {
           *reinterpret_cast<uint4*>(row) = q;
@@ -350,10 +332,7 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_stream(const GemmParams p) 
     if (p.stamps != nullptr && wave == 0) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       const unsigned long long ts3 = __builtin_amdgcn_s_memtime();
-      if (lane == 0) {
-        unsigned long long* o = p.stamps + (size_t)tile * 4;
-        o[0] = ts0; o[1] = ts1; o[2] = ts2; o[3] = ts3;
-      }
+      if (lane == 0) write_stamps(p, tile, ts0, ts1, ts2, ts3);
     }
 #endif
     prev_full = inter;
@@ -384,7 +363,7 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_stream(const GemmParams p) 
 namespace f8w {
 using f8::Frag;
 using f8::frag_bits;
-using f8::pack4_e4m3;
+using f8::gelu_e4m3x16;
 using f8::v8i;
 using wide::key_x;
 using wide::wait_step;
@@ -396,8 +375,9 @@ constexpr int MT = 4, NT = 2;     // 32 x 32 tiles per wave: 128 rows x 64 colum
 constexpr int lds_bytes(int epi) { return LDS_BYTES + 8 * f8w_scratch_bytes(epi); }
 // vector stores per wave of an interior tile, by epilogue path (NSTORE below must not exceed what a path issues)
 constexpr int STORES_GELU8 = MT * NT;       // one 16-byte e4m3 store per 32 x 32 tile
-constexpr int STORES_ACC = 2 * MT * NT;     // bf16 from the accumulator layout: two 16-byte stores per 32 x 32 tile
-constexpr int STORES_LINES = 4 * MT;        // bf16 as whole lines: per 32-row group 4 x (8 rows x 128 bytes)
+constexpr int ROW_STORES_BF16 = 2;                        // bf16 from the accumulator layout: two 16-byte stores per row ...
+constexpr int STORES_ACC = ROW_STORES_BF16 * MT * NT;     // ... of a 32 x 32 tile
+constexpr int STORES_LINES = (32 / LINE_ROWS) * MT;       // bf16 as whole lines: per 32-row group 4 x (8 rows x 128 bytes)
 // W tile row (of 32) read by A-row i, and the swizzle key of a W tile row: the 16 rows one ds_read_b128 lane group
 // touches ({0-3, 16-19, 4-7, 20-23} + 8 for the second group) must land in 16 distinct 16-byte slots of 256 bytes
 __device__ __forceinline__ int w_row32(int i) { return 16 * ((i >> 2) & 1) + (i & 3) + 4 * (i >> 3); }
@@ -422,38 +402,15 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_wide(const GemmParams p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tiles_m = p.total_tiles / p.tiles_n;
-  auto tile_mn = [&](int t, int& tm_, int& tn_) {   // (N block, row tile, column in block): see gemm_bf16_tn_stream
-    if (p.nblk >= p.tiles_n) { tm_ = t / p.tiles_n; tn_ = t - tm_ * p.tiles_n; return; }
-    const int per = p.nblk * tiles_m, blk = t / per, r = t - blk * per;
-    const int left = p.tiles_n - blk * p.nblk, nb = left < p.nblk ? left : p.nblk;
-    const int rr = r / nb;
-    tm_ = rr; tn_ = blk * p.nblk + (r - rr * nb);
-  };
   const char* xp[XP];
   const char* wp[PW];
   const int r_in = lane >> 3, pch = lane & 7;
   auto point_at = [&](int tile) {
     int tm, tn;
-    tile_mn(tile, tm, tn);
-#pragma unroll
-    for (int i = 0; i < XP; ++i) {
-      const int row = (wave * XP + i) * 8 + r_in;
-      int m = tm * BM + row;
-      if (m > p.M - 1) m = p.M - 1;   // clamp: duplicates are computed but never stored
-      xp[i] = reinterpret_cast<const char*>(p.X) + (long)m * p.lda + ((pch ^ key_x(row)) << 4);
-    }
-#pragma unroll
-    for (int i = 0; i < PW; ++i) {
-      const int row = (wave * PW + i) * 8 + r_in;    // W is allocated with its rows padded to a multiple of 256
-      wp[i] = reinterpret_cast<const char*>(p.W) + (long)(tn * BN + row) * p.ldw + ((pch ^ key_w(row)) << 4);
-    }
+    stream_tile_mn(p, tiles_m, tile, tm, tn);
+    byte_tile_point_at<BN>(p, tm, tn, wave, r_in, pch, [](int row) { return key_w(row); }, xp, wp);
   };
-  auto dma_piece = [&](int q, int k0, char* dx) {
-    if (q < XP)
-      __builtin_amdgcn_global_load_lds(GLB_PTR(xp[q] + k0), LDS_PTR(dx + (wave * XP + q) * 1024), 16, 0, 0);
-    else
-      __builtin_amdgcn_global_load_lds(GLB_PTR(wp[q - XP] + k0), LDS_PTR(dx + X_BYTES + (wave * PW + q - XP) * 1024), 16, 0, 0);
-  };
+  auto dma_piece = [&](int q, int k0, char* dx) { byte_tile_dma_piece<X_BYTES>(xp, wp, wave, q, k0, dx); };
   const int wm = wave >> 2, wn = wave & 3;
   const int r = lane & 31, h = lane >> 5;
   const int xr0 = wm * 128 + r;                    // + 32 * mi: same key
@@ -466,6 +423,10 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_wide(const GemmParams p) {
       xo[ks][c] = xr0 * KB + (((4 * ks + 2 * h + c) ^ key_x(xr0)) << 4);
       wo[ks][c] = X_BYTES + wr0 * KB + (((4 * ks + 2 * h + c) ^ key_w(wr0)) << 4);
     }
+
+  // chunk c (of the lane's pair) of X fragment i (32-row group i) / W fragment i (32-column tile i), half step ks, stage at sb
+  auto x_chunk = [&](const char* sb, int ks, int c, int i) { return *reinterpret_cast<const bf16x8*>(sb + xo[ks][c] + i * 32 * KB); };
+  auto w_chunk = [&](const char* sb, int ks, int c, int i) { return *reinterpret_cast<const bf16x8*>(sb + wo[ks][c] + i * 32 * KB); };
 
   f32x16 acc[NT][MT];
   // one half step: MFMAs on (xc, wc)  ||  if READ: fragments (stage rst, half rks) -> (xn, wn_)  ||  if DMA: K-tile dkt
@@ -486,10 +447,10 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_wide(const GemmParams p) {
       for (int ni = 0; ni < NT; ++ni)
         acc[ni][mi] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wv[ni], xv, acc[ni][mi], 0, 0, 0, 0, 0, 0);
       if constexpr (READ) {
-        xn[mi].lo = *reinterpret_cast<const bf16x8*>(sb + xo[rks][0] + mi * 32 * KB);
-        xn[mi].hi = *reinterpret_cast<const bf16x8*>(sb + xo[rks][1] + mi * 32 * KB);
-        if (mi < NT) wn_[mi].lo = *reinterpret_cast<const bf16x8*>(sb + wo[rks][0] + mi * 32 * KB);
-        else wn_[mi - NT].hi = *reinterpret_cast<const bf16x8*>(sb + wo[rks][1] + (mi - NT) * 32 * KB);
+        xn[mi].lo = x_chunk(sb, rks, 0, mi);
+        xn[mi].hi = x_chunk(sb, rks, 1, mi);
+        if (mi < NT) wn_[mi].lo = w_chunk(sb, rks, 0, mi);
+        else wn_[mi - NT].hi = w_chunk(sb, rks, 1, mi - NT);
       }
       if constexpr (DMA) {
 #pragma unroll
@@ -508,13 +469,13 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_wide(const GemmParams p) {
     const char* sb = smem + st * STAGE_BYTES;
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
-      xa[i].lo = *reinterpret_cast<const bf16x8*>(sb + xo[0][0] + i * 32 * KB);
-      xa[i].hi = *reinterpret_cast<const bf16x8*>(sb + xo[0][1] + i * 32 * KB);
+      xa[i].lo = x_chunk(sb, 0, 0, i);
+      xa[i].hi = x_chunk(sb, 0, 1, i);
     }
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
-      wa[i].lo = *reinterpret_cast<const bf16x8*>(sb + wo[0][0] + i * 32 * KB);
-      wa[i].hi = *reinterpret_cast<const bf16x8*>(sb + wo[0][1] + i * 32 * KB);
+      wa[i].lo = w_chunk(sb, 0, 0, i);
+      wa[i].hi = w_chunk(sb, 0, 1, i);
     }
   };
   constexpr int NSTORE = EPI == EPI_GELU8 ? STORES_GELU8 : (SCRATCH > 0 && STORES_LINES < STORES_ACC) ? STORES_LINES : STORES_ACC;
@@ -536,7 +497,7 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_wide(const GemmParams p) {
     const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
 #endif
     int tm, tn;
-    tile_mn(tile, tm, tn);
+    stream_tile_mn(p, tiles_m, tile, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
     const bool inter = m0 + BM <= p.M && n0 + BN <= p.N;
     const int vn = v + gridDim.x;
@@ -594,10 +555,10 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_wide(const GemmParams p) {
     if constexpr (SCRATCH > 0) {
       if (inter) {
         // interior tile, bf16 output as whole 128-byte lines: per 32-row group the wave's 32 x 64 block (two 16-byte pieces
-        // per lane and column tile: chunks 4 ni + 2 h, + 1 of row r) goes through 4 KiB of LDS behind the stages - slot =
-        // chunk ^ (row & 7), conflict free both ways - and leaves as 8 rows x 128 bytes per instruction.  Stored
-        // straight from the accumulator layout an instruction touches 32 rows x 64 bytes (two lanes per row): half lines,
-        // which a CU moves at a third of the rate (tools/pull_probe.hip) - the reason QKV used the 256 x 128 kernel.
+        // per lane and column tile: chunks 4 ni + 2 h, + 1 of row r) goes through 4 KiB of LDS behind the stages (lines_put /
+        // lines_get in gemm.hip) and leaves as 8 rows x 128 bytes per instruction.  Stored straight from the accumulator layout
+        // an instruction touches 32 rows x 64 bytes (two lanes per row): half lines, which a CU moves at a third of the rate
+        // (tools/pull_probe.hip) - the reason QKV used the 256 x 128 kernel.
         char* scratch = smem + LDS_BYTES + wave * SCRATCH;
         int lane_v = lane;
         asm volatile("" : "+v"(lane_v));
@@ -618,21 +579,19 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_wide(const GemmParams p) {
         bf16_t* Y = reinterpret_cast<bf16_t*>(p.Y) + n0w + 8 * cc;
 #pragma unroll
         for (int mi = 0; mi < MT; ++mi) {
-          const int key = r & 7;
 #pragma unroll
           for (int ni = 0; ni < NT; ++ni) {
             float y[16];
 #pragma unroll
             for (int j = 0; j < 16; ++j) y[j] = fmaf(acc[ni][mi][j] * xsr[mi], ws[ni][j], bs[ni][j]);
-            *reinterpret_cast<bf16x8*>(scratch + r * 128 + (((4 * ni + 2 * h) ^ key) << 4)) = __builtin_bit_cast(bf16x8, pack8(y));
-            *reinterpret_cast<bf16x8*>(scratch + r * 128 + (((4 * ni + 2 * h + 1) ^ key) << 4)) = __builtin_bit_cast(bf16x8, pack8(y + 8));
+            lines_put(scratch, r, 4 * ni + 2 * h, __builtin_bit_cast(bf16x8, pack8(y)));
+            lines_put(scratch, r, 4 * ni + 2 * h + 1, __builtin_bit_cast(bf16x8, pack8(y + 8)));
           }
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
+          lines_turn();
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int row = 8 * j + rr;
-            const uint4 q = __builtin_bit_cast(uint4, *reinterpret_cast<const bf16x8*>(scratch + row * 128 + ((cc ^ (row & 7)) << 4)));
+          for (int j = 0; j < 32 / LINE_ROWS; ++j) {
+            const int row = LINE_ROWS * j + rr;
+            const uint4 q = __builtin_bit_cast(uint4, lines_get(scratch, row, cc));
             *reinterpret_cast<uint4*>(Y + (long)(m_base + mi * 32 + row) * p.ldc) = q;
           }
           __builtin_amdgcn_wave_barrier();   // the group's reads are issued before the next group's writes
@@ -661,15 +620,7 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_wide(const GemmParams p) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) y[j] = fmaf(acc[ni][mi][j] * xsr[mi], ws[j], bs[j]);
         if constexpr (EPI == EPI_GELU8) {
-#pragma unroll
-          for (int j = 0; j < 16; j += 4) {
-            f32x2 ta = f32x2{y[j], y[j + 1]}, tb = f32x2{y[j + 2], y[j + 3]};
-            gelu_pk4(ta, tb);
-            y[j] = ta[0] * inv[mi]; y[j + 1] = ta[1] * inv[mi]; y[j + 2] = tb[0] * inv[mi]; y[j + 3] = tb[1] * inv[mi];
-          }
-          uint4 q;
-          q.x = pack4_e4m3(y[0], y[1], y[2], y[3]);   q.y = pack4_e4m3(y[4], y[5], y[6], y[7]);
-          q.z = pack4_e4m3(y[8], y[9], y[10], y[11]); q.w = pack4_e4m3(y[12], y[13], y[14], y[15]);
+          const uint4 q = gelu_e4m3x16(y, inv[mi]);
           unsigned char* row = reinterpret_cast<unsigned char*>(p.Y) + (long)m * p.ldc + c0;
           if (full) {
             *reinterpret_cast<uint4*>(row) = q;
@@ -682,6 +633,7 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_wide(const GemmParams p) {
         } else {
           bf16_t* row = reinterpret_cast<bf16_t*>(p.Y) + (long)m * p.ldc + c0;
           if (full) {
+            static_assert(ROW_STORES_BF16 == 2, "the two stores below");
             *reinterpret_cast<uint4*>(row) = pack8(y);
             *reinterpret_cast<uint4*>(row + 8) = pack8(y + 8);
           } else {
@@ -701,10 +653,7 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_tn_wide(const GemmParams p) {
     if (p.stamps != nullptr && wave == 0) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       const unsigned long long ts3 = __builtin_amdgcn_s_memtime();
-      if (lane == 0) {
-        unsigned long long* o = p.stamps + (size_t)tile * 4;
-        o[0] = ts0; o[1] = ts1; o[2] = ts2; o[3] = ts3;
-      }
+      if (lane == 0) write_stamps(p, tile, ts0, ts1, ts2, ts3);
     }
 #endif
     prev_full = inter;
