@@ -239,6 +239,20 @@ int rajni_layernorm(const void* x, long x_row_stride, const float* w, const floa
   return launch_layernorm(x, x_row_stride, w, b, y, rows, C, eps, x_f32, dtype, (hipStream_t)stream);
 }
 
+int rajni_norm_rows(int kind, const void* x, long x_row_stride, const float* w, const float* b, void* y, int rows, int C,
+                    float eps, int dtype, int x_f32, rajni_stream_t stream) {
+  NEED_DTYPE("rajni_norm_rows");
+  RAJNI_REQUIRE_PLACED("rajni_norm_rows", {"x", x, 16}, {"w", w, 16}, {"b", b, 16}, {"y", y, 16});
+  return launch_layernorm(x, x_row_stride, w, b, y, rows, C, eps, x_f32, dtype, (hipStream_t)stream, kind);
+}
+
+int rajni_embed_norm(int kind, void* x, const float* w, const float* b, const void* pos, int pos_off, int B, int N,
+                     int num_prefix, int C, float eps, int dtype, int x_f32, rajni_stream_t stream) {
+  NEED_DTYPE("rajni_embed_norm");
+  RAJNI_REQUIRE_PLACED("rajni_embed_norm", {"x", x, 16}, {"w", w, 16}, {"b", b, 16}, {"pos", pos, 16});
+  return launch_embed_norm(kind, x, w, b, pos, pos_off, B, N, num_prefix, C, eps, dtype, x_f32, (hipStream_t)stream);
+}
+
 int rajni_layernorm_fp8(const void* x, long x_row_stride, const float* w, const float* b, void* y_q,
                         float* y_scale, float* hid_scale, float w1_rownorm_max, float b1_absmax,
                         int rows, int C, float eps, int x_f32, rajni_stream_t stream) {

@@ -9,6 +9,7 @@
 #include "../../include/rajni_hip_image.h"
 #include "../../include/rajni_hip_query.h"
 #include "../../include/rajni_hip_attnpool.h"
+#include "../../include/rajni_hip_norm.h"
 
 typedef unsigned short bf16_t;  // raw bf16 bits in memory
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -217,8 +218,9 @@ int launch_patch_embed(const void* images, const void* w, const float* bias, con
                        int num_prefix = 1, const void* reg = nullptr,    // reg: [num_prefix-1, C] register tokens behind CLS
                        int has_cls = 1);   // 0 (rajni_hip_query.h): no class row - cls is not read, num_prefix = R >= 0, reg [R, C]
 size_t patch_embed_workspace_bytes(int B, int Cin, int H, int W, int P, int dtype);   // images [B, Cin, H, W]; 0: im2col fused into the GEMM loads
+// (kind, here and below: RAJNI_NORM_LAYERNORM, or RAJNI_NORM_RMS of rajni_hip_norm.h - the same kernel's RMS form, b not read)
 int launch_layernorm(const void* x, long xs, const float* w, const float* b, void* y, int rows,
-                     int C, float eps, int x_f32, int dtype, hipStream_t s);
+                     int C, float eps, int x_f32, int dtype, hipStream_t s, int kind = RAJNI_NORM_LAYERNORM);
 int launch_layernorm_fp8(const void* x, long xs, const float* w, const float* b, void* yq, float* yscale,
                          float* hscale, float wnorm, float bmax, int rows, int C, float eps, int x_f32, hipStream_t s);
 int launch_attention(const void* qkv, const int32_t* keep_idx, void* out, int B, int n_src, int np, int nq,
@@ -245,11 +247,12 @@ int launch_source_idx(int32_t* src, const int32_t* const* idx, const int* width,
                       hipStream_t s);
 // (zero_fill = 0, RAJNI_POOL_DENSE_LAST: the rows src does not name are left as they are)
 int launch_layernorm_dense(const void* x, const int32_t* src, const float* w, const float* b, void* y, int B, int Nf, int S,
-                           int C, float eps, int x_f32, int dtype, hipStream_t s, int zero_fill = 1);
+                           int C, float eps, int x_f32, int dtype, hipStream_t s, int zero_fill = 1, int kind = RAJNI_NORM_LAYERNORM);
 // RAJNI_POOL_DENSE_LAST: the patch rows of the stream x [B, N, C] that the selection keep [B, Np] drops, through the final norm to
 // row src[b, j] of y [B, S, C]; src [B, N] = where each token of x sat in the unpruned sequence
 int launch_layernorm_dropped(const void* x, const int32_t* keep, const int32_t* src, const float* w, const float* b, void* y,
-                             int B, int N, int Np, int P, int S, int C, float eps, int x_f32, int dtype, hipStream_t s);
+                             int B, int N, int Np, int P, int S, int C, float eps, int x_f32, int dtype, hipStream_t s,
+                             int kind = RAJNI_NORM_LAYERNORM);
 // rajni_vit_forward_layers: launch_layernorm_dense without the norm (the stream row rounded once to `dtype`), and
 // launch_layernorm_dropped to the `ny` outputs ys[k] [B, S, C] at once (a host array), through the norm or cast only
 int launch_rows_dense_cast(const void* x, const int32_t* src, void* y, int B, int Nf, int S, int C, int x_f32, int dtype,
@@ -260,10 +263,14 @@ int launch_rows_dropped_multi(const void* x, const int32_t* keep, const int32_t*
 // variants.hip: the timm options of rajni_vit_ext (b pointers may be NULL = no bias; nw / fw NULL = that norm is absent)
 int launch_qk_norm(void* qkv, const float* qw, const float* qb, const float* kw, const float* kb, int rows, int H, int D,
                    float eps, int dtype, hipStream_t s);
-int launch_layernorm_stream(void* x, const float* w, const float* b, int rows, int C, float eps, int x_f32, int dtype, hipStream_t s);
+int launch_layernorm_stream(void* x, const float* w, const float* b, int rows, int C, float eps, int x_f32, int dtype, hipStream_t s,
+                            int kind = RAJNI_NORM_LAYERNORM);
 int launch_pool_norm(const void* x, int B, int N, int C, int pool, const float* nw, const float* nb, float neps,
                      const float* fw, const float* fb, float feps, void* out, int x_f32, int dtype, hipStream_t s,
-                     int num_prefix = 1);
+                     int num_prefix = 1, int kind = RAJNI_NORM_LAYERNORM);
+// patch_embed.norm (rajni_hip_norm.h): the patch rows of the stream x [B, N, C] normalised in place, + pos[pos_off + j]
+int launch_embed_norm(int kind, void* x, const float* w, const float* b, const void* pos, int pos_off, int B, int N, int num_prefix,
+                      int C, float eps, int dtype, int x_f32, hipStream_t s);
 // image.hip: position-embedding rows [prefix + sh * sw, C] -> [prefix + dh * dw, C], bicubic with antialiasing (timm's
 // resample_abs_pos_embed); prefix rows copied
 int launch_resample_pos_embed(const void* src, int sh, int sw, void* dst, int dh, int dw, int C, int prefix, int dtype, hipStream_t s);

@@ -2,7 +2,7 @@
 // that enqueues every kernel on the caller's stream.  Token counts are data independent,
 // so all shapes are known up front: no allocation, no host sync, no device->host traffic inside.
 //
-// A call is a plan and up to six optional records.  make_spec resolves them once into a Spec, and everything below takes that
+// A call is a plan and up to seven optional records.  make_spec resolves them once into a Spec, and everything below takes that
 // Spec: check_all (every refusal, before the first launch), carve (the workspace), the block loop and the tails.
 //
 // Per block:  LN1 -> QKV GEMM (all N tokens) -> an attention form -> the tail (launch_tail):
@@ -32,7 +32,9 @@
 // grid, and with fill = 1 every scheduled block writes the rows it drops to the slabs of all captures at or behind it.  image -
 // n0 = (height / patch) * (width / patch) + P tokens, and plan.pos_embed holds the rows of that grid.  query - the importance
 // query of the scoring blocks and whether there is a class row; without one P counts the registers alone and the last block
-// runs every row.  pool - the attention-pool tail and its B fp32 rows, carved behind everything else.
+// runs every row.  pool - the attention-pool tail and its B fp32 rows, carved behind everything else.  norm - with kind RMS every
+// norm launch is the RMS form of the same kernel; with an embedding norm the patch GEMM adds a zeroed position table and
+// launch_embed_norm follows it (rajni_hip_norm.h).
 #include "common.h"
 
 #include <vector>
@@ -63,6 +65,9 @@ struct Spec {
   const rajni_vit_ext* ext; const rajni_vit_prefix* pre; const rajni_vit_layers* lay; const rajni_vit_image* img;
   const rajni_vit_query* qry;       // {1, RAJNI_QUERY_CLS} arrives here as NULL
   const rajni_vit_attn_pool* ap;
+  const rajni_vit_norm* nrm;        // all zero arrives here as NULL
+  int kind;                         // every norm of the forward but q/k-norm: RAJNI_NORM_LAYERNORM without the record
+  bool rms, embed_norm;             // kind == RAJNI_NORM_RMS; the record carries a patch_embed.norm
   hipStream_t s;
   bool nocls;                       // no class row: the prefix tokens are the registers alone
   int qmode;                        // the importance query of the scoring blocks
@@ -82,18 +87,22 @@ enum { ENTRY_FORWARD = 0, ENTRY_SIZE = 1 };
 
 Spec make_spec(int family, const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre,
                const rajni_vit_layers* lay, const rajni_vit_image* img, const rajni_vit_query* qry, const rajni_vit_attn_pool* ap,
-               hipStream_t s) {
+               hipStream_t s, const rajni_vit_norm* nrm = nullptr) {
   // a NULL trailing record makes a call the next-narrower entry point's, by name too (the size of a pool record is the query
   // size function's plus the pool rows, and there is no size function for a layers record)
-  static const char* const names[2][5] = {
+  static const char* const names[2][6] = {
       {"rajni_vit_forward_ext_prefix", "rajni_vit_forward_layers", "rajni_vit_forward_image", "rajni_vit_forward_query",
-       "rajni_vit_forward_pool"},
+       "rajni_vit_forward_pool", "rajni_vit_forward_norm"},
       {"rajni_vit_workspace_bytes_prefix", "rajni_vit_workspace_bytes_prefix", "rajni_vit_workspace_bytes_image",
-       "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_query"}};
+       "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_norm"}};
   if (qry && qry->class_token == 1 && qry->query == RAJNI_QUERY_CLS) qry = nullptr;
+  if (nrm && nrm->kind == RAJNI_NORM_LAYERNORM && !nrm->embed_norm_w) nrm = nullptr;   // what NULL means
   Spec c{};
-  c.who = names[family][(ap && family == ENTRY_FORWARD) ? 4 : qry ? 3 : img ? 2 : lay ? 1 : 0];
-  c.p = plan; c.ext = ext; c.pre = pre; c.lay = lay; c.img = img; c.qry = qry; c.ap = ap; c.s = s;
+  c.who = names[family][nrm ? 5 : (ap && family == ENTRY_FORWARD) ? 4 : qry ? 3 : img ? 2 : lay ? 1 : 0];
+  c.p = plan; c.ext = ext; c.pre = pre; c.lay = lay; c.img = img; c.qry = qry; c.ap = ap; c.nrm = nrm; c.s = s;
+  c.kind = nrm ? nrm->kind : RAJNI_NORM_LAYERNORM;
+  c.rms = c.kind == RAJNI_NORM_RMS;
+  c.embed_norm = nrm != nullptr && nrm->embed_norm_w != nullptr;
   c.nocls = qry != nullptr && qry->class_token == 0;
   c.qmode = qry ? qry->query : RAJNI_QUERY_CLS;
   c.has_cls = c.nocls ? 0 : 1;
@@ -210,7 +219,7 @@ int check_plan(const Spec& c) {
                 "rajni_vit_forward: C and hidden must be multiples of 64");
   // a headless plan (head_w == NULL and num_classes == 0) is legal; half of that pair is a missing weight
   RAJNI_REQUIRE(p.patch_w && (p.cls_token || c.nocls) && p.pos_embed && (p.head_w != nullptr) == (p.num_classes != 0) &&
-                    (c.norm_absent || (p.norm_w && p.norm_b)),
+                    (c.norm_absent || (p.norm_w && (p.norm_b || c.rms))),
                 RAJNI_ERR_INVALID, "rajni_vit_forward: null weight pointer");
   RAJNI_REQUIRE(!(headless(p) && p.act_fp8), RAJNI_ERR_UNSUPPORTED,
                 "rajni_vit_forward: a headless plan (feature output) is unsupported with act_fp8");
@@ -350,7 +359,7 @@ rajni_linear_args fc2_args(const Spec& f, const rajni_block& blk, int M, void* y
 int layernorm(const Spec& f, const void* x, const float* g, const float* b, int rows, float* hs, float wnorm, float bmax) {
   const rajni_vit_plan& p = *f.p;
   if (p.act_fp8) return launch_layernorm_fp8(x, p.C, g, b, f.w.xn, f.w.xs, hs, wnorm, bmax, rows, p.C, p.ln_eps, f.sf32, f.s);
-  return launch_layernorm(x, p.C, g, b, f.w.xn, rows, p.C, p.ln_eps, f.sf32, p.dtype, f.s);
+  return launch_layernorm(x, p.C, g, b, f.w.xn, rows, p.C, p.ln_eps, f.sf32, p.dtype, f.s, f.kind);
 }
 
 // act_fp8 plans: this block's attention over np tokens emits e4m3 rows + their (one) scale into w.xs - norm1's row scales
@@ -481,6 +490,28 @@ int check_pool(const Spec& c) {
   RAJNI_REQUIRE_PLACED("rajni_vit_forward_pool: pool", {"q", ap.q, 16}, {"kv_w", ap.kv_w, 16}, {"kv_b", ap.kv_b, 16}, {"proj_w", ap.proj_w, 16},
                        {"proj_b", ap.proj_b, 16}, {"norm_w", ap.norm_w, 16}, {"norm_b", ap.norm_b, 16}, {"fc1_w", ap.fc1_w, 16},
                        {"fc1_b", ap.fc1_b, 16}, {"fc2_w", ap.fc2_w, 16}, {"fc2_b", ap.fc2_b, 16});
+  return RAJNI_OK;
+}
+
+// the norm record against the plan and the pool and layers records (rajni_hip_norm.h): host-side tests, every refusal names the
+// combination
+int check_norm(const Spec& c) {
+  const char* who = "rajni_vit_forward_norm";
+  const rajni_vit_plan& p = *c.p;
+  const rajni_vit_norm& n = *c.nrm;
+  RAJNI_REQUIRE(n.kind == RAJNI_NORM_LAYERNORM || n.kind == RAJNI_NORM_RMS, RAJNI_ERR_INVALID,
+                "%s: norm.kind must be RAJNI_NORM_LAYERNORM or RAJNI_NORM_RMS (%d)", who, n.kind);
+  const char* what = c.rms ? "RMSNorm (norm.kind = RAJNI_NORM_RMS)" : "a patch-embedding norm (norm.embed_norm_w)";
+  RAJNI_REQUIRE(!p.act_fp8, RAJNI_ERR_UNSUPPORTED,
+                "%s: %s is unsupported with plan.act_fp8 - the e4m3-output norm kernels are LayerNorm only", who, what);
+  RAJNI_REQUIRE(!c.ap, RAJNI_ERR_UNSUPPORTED,
+                "%s: %s is unsupported with an attention-pool record (RAJNI_POOL_MAP) - that tail's norms are LayerNorm only", who, what);
+  RAJNI_REQUIRE(!(c.rms && c.lay && c.lay->norm == 1), RAJNI_ERR_UNSUPPORTED,
+                "%s: RMSNorm (norm.kind = RAJNI_NORM_RMS) with layers.norm = 1 - the normalised slabs are LayerNorm only; "
+                "layers.norm = 0 gives the un-normalised states", who);
+  RAJNI_REQUIRE(!c.embed_norm || (p.C > 0 && p.C % 8 == 0 && p.C <= 2048), RAJNI_ERR_UNSUPPORTED,
+                "%s: a patch-embedding norm needs C %% 8 == 0, C <= 2048 (C=%d)", who, p.C);
+  RAJNI_REQUIRE_PLACED("rajni_vit_forward_norm: norm", {"embed_norm_w", n.embed_norm_w, 16}, {"embed_norm_b", n.embed_norm_b, 16});
   return RAJNI_OK;
 }
 
@@ -638,7 +669,7 @@ int launch_source_idx_before(const Spec& c, int upto, int32_t* src, int Nf) {
 
 // Every refusal of the forward, before the first launch.  The order is part of the contract - callers match the first message:
 // the prefix record under the entry point's name; null pointers; the query record (whether there is a class row decides every
-// count); the pool record; the image record (every count below is against its grid); the layers record; then the plan, the
+// count); the pool record; the norm record; the image record (every count below is against its grid); the layers record; then the plan, the
 // placement of what it points to, the ext record, the distilled head, the schedule, and last the workspace, carved here.
 int check_all(Spec& c, const void* images, const void* logits) {
   int rc = check_prefix(c);
@@ -647,6 +678,7 @@ int check_all(Spec& c, const void* images, const void* logits) {
   const rajni_vit_plan& p = *c.p;
   if (c.qry && (rc = check_query(c)) != RAJNI_OK) return rc;
   if (c.ap && (rc = check_pool(c)) != RAJNI_OK) return rc;
+  if (c.nrm && (rc = check_norm(c)) != RAJNI_OK) return rc;
   if (c.img && (rc = check_image(c)) != RAJNI_OK) return rc;
   if (c.lay && (rc = check_layers(c)) != RAJNI_OK) return rc;
   if (c.dense_last && (rc = check_dense_last(c)) != RAJNI_OK) return rc;
@@ -669,6 +701,7 @@ size_t workspace_bytes(const Spec& c) {
   if (c.qry && query_form(*c.qry) != RAJNI_OK) return 0;
   if (check_prefix(c) != RAJNI_OK || (c.img && check_image(c) != RAJNI_OK)) return 0;
   if (c.ap && (!pool_hidden_ok(*c.ap) || c.p->B <= 0 || c.p->C <= 0)) return 0;
+  if (c.nrm && check_norm(c) != RAJNI_OK) return 0;
   return carve(c).total;
 }
 
@@ -684,12 +717,30 @@ int vit_forward(Spec f, const void* images, void* logits) {
   const int B = p.B, C = p.C, dt = p.dtype, P = f.P, HR = f.HR, S0 = f.n0;
   int N = f.n0;
 
-  rc = launch_patch_embed(images, p.patch_w, p.patch_b, p.cls_token, p.pos_embed, p.pos_has_cls,
+  // patch_embed.norm sits between the projection and the position embedding: the patch GEMM then adds a table whose patch rows
+  // are zero and launch_embed_norm adds the real rows behind its norm.  The table lives in w.xb, idle until a block's tail writes
+  // it ((P + n) * C elements of the model dtype fit in B times as many of the stream's); its prefix rows are the real ones, for
+  // the kernel that writes the prefix rows
+  const void* pos = p.pos_embed;
+  const int poff = p.pos_has_cls ? P : 0;
+  if (f.embed_norm) {
+    const size_t rowb = (size_t)C * rajni_elem_bytes(dt);
+    hipError_t e = poff ? hipMemcpyAsync(w.xb, p.pos_embed, poff * rowb, hipMemcpyDeviceToDevice, s) : hipSuccess;
+    if (e == hipSuccess) e = hipMemsetAsync(w.xb + poff * rowb, 0, (size_t)(N - P) * rowb, s);
+    RAJNI_REQUIRE(e == hipSuccess, RAJNI_ERR_LAUNCH, "rajni_vit_forward_norm: zeroed position table: %s", hipGetErrorString(e));
+    pos = w.xb;
+  }
+  rc = launch_patch_embed(images, p.patch_w, p.patch_b, p.cls_token, pos, p.pos_has_cls,
                           w.xa, f.sf32, B, p.in_chans, f.height, f.width, p.patch_size, C, dt, w.cols, w.cols_bytes, s,
                           P, f.reg_token, f.has_cls);
   if (rc != RAJNI_OK) return rc;
+  if (f.embed_norm) {
+    rc = launch_embed_norm(f.kind, w.xa, f.nrm->embed_norm_w, f.nrm->embed_norm_b, p.pos_embed, poff, B, N, P, C,
+                           f.nrm->embed_norm_eps, dt, f.sf32, s);
+    if (rc != RAJNI_OK) return rc;
+  }
   if (ext && ext->norm_pre_w) {   // timm forward_features: x = norm_pre(x), written back into the stream
-    rc = launch_layernorm_stream(w.xa, ext->norm_pre_w, ext->norm_pre_b, B * N, C, ext->norm_pre_eps, f.sf32, dt, s);
+    rc = launch_layernorm_stream(w.xa, ext->norm_pre_w, ext->norm_pre_b, B * N, C, ext->norm_pre_eps, f.sf32, dt, s, f.kind);
     if (rc != RAJNI_OK) return rc;
   }
 
@@ -817,7 +868,7 @@ int vit_forward(Spec f, const void* images, void* logits) {
       rc = launch_source_idx_before(f, i, src, N);
       if (rc != RAJNI_OK) return rc;
       if (f.dense_last) {
-        rc = launch_layernorm_dropped(cur, idx, src, p.norm_w, p.norm_b, logits, B, N, Np, P, S0, C, p.ln_eps, f.sf32, dt, s);
+        rc = launch_layernorm_dropped(cur, idx, src, p.norm_w, p.norm_b, logits, B, N, Np, P, S0, C, p.ln_eps, f.sf32, dt, s, f.kind);
         if (rc != RAJNI_OK) return rc;
       }
       if (slabs_last) {
@@ -836,7 +887,7 @@ int vit_forward(Spec f, const void* images, void* logits) {
       int32_t* src = reinterpret_cast<int32_t*>(w.qkv);
       rc = launch_source_idx_before(f, i + 1, src, N);
       if (rc != RAJNI_OK) return rc;
-      rc = lay->norm ? launch_layernorm_dense(cur, src, p.norm_w, p.norm_b, slab(cap), B, N, S0, C, p.ln_eps, f.sf32, dt, s, lay->fill ? 0 : 1)
+      rc = lay->norm ? launch_layernorm_dense(cur, src, p.norm_w, p.norm_b, slab(cap), B, N, S0, C, p.ln_eps, f.sf32, dt, s, lay->fill ? 0 : 1, f.kind)
                      : launch_rows_dense_cast(cur, src, slab(cap), B, N, S0, C, f.sf32, dt, s, lay->fill ? 0 : 1);
       if (rc != RAJNI_OK) return rc;
       ++cap;
@@ -849,7 +900,7 @@ int vit_forward(Spec f, const void* images, void* logits) {
   void* const rowout = headless(p) ? logits : (void*)w.clsn;
   if (f.ap) return launch_pool_tail(f, cur, N, logits);
   if (f.pool == RAJNI_POOL_NONE)  // every surviving token through the final norm: [B, N, C]
-    return launch_layernorm(cur, C, p.norm_w, p.norm_b, logits, B * N, C, p.ln_eps, f.sf32, dt, s);
+    return launch_layernorm(cur, C, p.norm_w, p.norm_b, logits, B * N, C, p.ln_eps, f.sf32, dt, s, f.kind);
   if (f.pool == RAJNI_POOL_DENSE || f.dense_last) {
     // [B, P + n, C]: token j of the final stream at the row it came from, zeros elsewhere (RAJNI_POOL_DENSE_LAST: the other
     // rows were written behind the blocks that dropped them and stay).  The composed selection lives in w.qkv, dead behind
@@ -858,11 +909,11 @@ int vit_forward(Spec f, const void* images, void* logits) {
     rc = launch_source_idx_before(f, p.depth, src, N);
     if (rc != RAJNI_OK) return rc;
     return launch_layernorm_dense(cur, src, p.norm_w, p.norm_b, logits, B, N, S0, C, p.ln_eps, f.sf32, dt, s,
-                                  f.dense_last ? 0 : 1);
+                                  f.dense_last ? 0 : 1, f.kind);
   }
   if (ext && (f.pool != RAJNI_POOL_TOKEN || ext->fc_norm_w || f.norm_absent))
     rc = launch_pool_norm(cur, B, N, C, f.pool, f.norm_absent ? nullptr : p.norm_w, p.norm_b, p.ln_eps,
-                          ext->fc_norm_w, ext->fc_norm_b, ext->fc_norm_eps, rowout, f.sf32, dt, s, P);
+                          ext->fc_norm_w, ext->fc_norm_b, ext->fc_norm_eps, rowout, f.sf32, dt, s, P, f.kind);
   else if (HR == 2) {
     // rows 0 and 1 of every image, normalised side by side: row b of [B, 2C].  A stream that still holds all N rows (a last
     // block that prunes, or the all-rows form) first gives up its two rows to the other stream buffer, dense
@@ -872,9 +923,9 @@ int vit_forward(Spec f, const void* images, void* logits) {
       if (rc != RAJNI_OK) return rc;
       cur = oth;
     }
-    rc = launch_layernorm(cur, C, p.norm_w, p.norm_b, w.clsn, 2 * B, C, p.ln_eps, f.sf32, dt, s);
+    rc = launch_layernorm(cur, C, p.norm_w, p.norm_b, w.clsn, 2 * B, C, p.ln_eps, f.sf32, dt, s, f.kind);
   } else
-    rc = launch_layernorm(cur, (long)N * C, p.norm_w, p.norm_b, rowout, B, C, p.ln_eps, f.sf32, dt, s);
+    rc = launch_layernorm(cur, (long)N * C, p.norm_w, p.norm_b, rowout, B, C, p.ln_eps, f.sf32, dt, s, f.kind);
   if (rc != RAJNI_OK) return rc;
   if (headless(p)) return RAJNI_OK;
   rajni_linear_args head = linear_args(dt, w.clsn, p.head_w, p.head_b, nullptr, logits, B, p.num_classes, HR * C, RAJNI_EPI_BIAS);
@@ -916,6 +967,12 @@ extern "C" int rajni_vit_forward_pool(const rajni_vit_plan* plan, const rajni_vi
                                       const rajni_vit_attn_pool* pool, const void* images, void* logits, rajni_stream_t stream) {
   return vit_forward(make_spec(ENTRY_FORWARD, plan, ext, prefix, layers, image, query, pool, (hipStream_t)stream), images, logits);
 }
+extern "C" int rajni_vit_forward_norm(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
+                                      const rajni_vit_layers* layers, const rajni_vit_image* image, const rajni_vit_query* query,
+                                      const rajni_vit_attn_pool* pool, const rajni_vit_norm* norm, const void* images, void* logits,
+                                      rajni_stream_t stream) {
+  return vit_forward(make_spec(ENTRY_FORWARD, plan, ext, prefix, layers, image, query, pool, (hipStream_t)stream, norm), images, logits);
+}
 extern "C" size_t rajni_vit_workspace_bytes(const rajni_vit_plan* plan) {
   return workspace_bytes(make_spec(ENTRY_SIZE, plan, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
 }
@@ -932,6 +989,11 @@ extern "C" size_t rajni_vit_workspace_bytes_query(const rajni_vit_plan* plan, co
 extern "C" size_t rajni_vit_workspace_bytes_pool(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix, const rajni_vit_image* image,
                                                  const rajni_vit_query* query, const rajni_vit_attn_pool* pool) {
   return workspace_bytes(make_spec(ENTRY_SIZE, plan, nullptr, prefix, nullptr, image, query, pool, nullptr));
+}
+
+extern "C" size_t rajni_vit_workspace_bytes_norm(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix, const rajni_vit_image* image,
+                                                 const rajni_vit_query* query, const rajni_vit_attn_pool* pool, const rajni_vit_norm* norm) {
+  return workspace_bytes(make_spec(ENTRY_SIZE, plan, nullptr, prefix, nullptr, image, query, pool, nullptr, norm));
 }
 
 extern "C" void rajni_debug_set_last_block_all_rows(int on) { g_last_block_all_rows = on; }

@@ -12,7 +12,43 @@ namespace {
 #endif
 constexpr int LN_MAX_CHUNKS = 4;  // 16-byte chunks per lane: C <= 64*8*4 = 2048
 
-template <typename TX, typename TY>
+// the RMS forms' last pass: the row a wave holds in v -> (v * rstd) * w, rounded once to TY, as whole 16-byte stores
+template <typename TY>
+__device__ __forceinline__ void rms_store_row(const float (&v)[LN_MAX_CHUNKS][8], int lane, int nchunk, float rstd,
+                                              const float* __restrict__ w, TY* __restrict__ yr) {
+#pragma unroll
+  for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
+    const int c = lane + i * 64;
+    if (c < nchunk) {
+      float wv[8], o[8];
+      load8<float>(w + c * 8, wv);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = (v[i][j] * rstd) * wv[j];
+      store8<TY>(yr + c * 8, o);
+    }
+  }
+}
+// ... and their first: the row -> v, and rsqrt(mean(v^2) + eps)
+template <typename TX>
+__device__ __forceinline__ float rms_load_row(const TX* __restrict__ xr, float (&v)[LN_MAX_CHUNKS][8], int lane, int nchunk, int C,
+                                              float eps) {
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
+    const int c = lane + i * 64;
+    if (c < nchunk) {
+      load8<TX>(xr + c * 8, v[i]);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ss += v[i][j] * v[i][j];
+    }
+  }
+  return rsqrtf(wave_sum(ss) / (float)C + eps);
+}
+
+// RMS (rajni_hip_norm.h): y = (x * rsqrt(mean(x^2) + eps)) * w - no mean, and b is never read.  The sum of squares runs in the
+// order of the LayerNorm sums: a lane's chunks in order, their 8 elements in order, then wave_sum.  The same holds for every
+// kernel below that takes the flag; RMS = false is the code as it always was.
+template <typename TX, typename TY, bool RMS = false>
 __global__ void __launch_bounds__(256) layernorm_kernel(const TX* __restrict__ x, long xs,
                                                         const float* __restrict__ w,
                                                         const float* __restrict__ b,
@@ -23,6 +59,11 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const TX* __restrict__ x
   const int nchunk = C >> 3;
   const TX* xr = x + (long)row * xs;
   float v[LN_MAX_CHUNKS][8];
+  if constexpr (RMS) {
+    const float rstd = rms_load_row<TX>(xr, v, lane, nchunk, C, eps);
+    rms_store_row<TY>(v, lane, nchunk, rstd, w, y + (long)row * C);
+    return;
+  }
   float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
@@ -65,7 +106,7 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const TX* __restrict__ x
 // R rows per wave (fp32 rows in, bf16 out, C <= 1024): R times the loads in flight per wave.  The one-row kernel keeps 3 KB per wave in
 // flight at 8 waves per SIMD - Little's law put that short of the HBM rate: LayerNorm was a latency-bound kernel, not a bandwidth-bound one
 // (two rows, still 64 VGPRs = 8 waves: 772 -> 715 us per forward; the e4m3-output kernel, with four wave reductions per row, loses with two).
-template <int NC, int R, typename TY = bf16_t>
+template <int NC, int R, typename TY = bf16_t, bool RMS = false>
 __global__ void __launch_bounds__(256) layernorm_rows_kernel(const float* __restrict__ x, long xs, const float* __restrict__ w,
                                                              const float* __restrict__ b, TY* __restrict__ y, int rows, int C, float eps) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -83,6 +124,37 @@ __global__ void __launch_bounds__(256) layernorm_rows_kernel(const float* __rest
     }
   }
   float mean[R], rstd[R];
+  if constexpr (RMS) {   // one reduction per row, no mean, no bias: the RMS form of everything below
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      float ss = 0.f;
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {
+        const int c = lane + i * 64;
+        if (c < nchunk) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) ss += v[r][i][j] * v[r][i][j];
+        }
+      }
+      rstd[r] = rsqrtf(wave_sum(ss) / (float)C + eps);
+    }
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+      const int c = lane + i * 64;
+      if (c < nchunk) {
+        float wv[8];
+        load8<float>(w + c * 8, wv);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          float o[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) o[j] = (v[r][i][j] * rstd[r]) * wv[j];
+          if (r0 + r < rows) store8<TY>(y + (long)(r0 + r) * C + c * 8, o);
+        }
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     float sum = 0.f;
@@ -396,7 +468,7 @@ __global__ void __launch_bounds__(256) source_idx_kernel(int32_t* __restrict__ s
 // on the scalar unit.  A hit is layernorm_kernel's arithmetic instruction for instruction (load8, two-pass fp32 statistics,
 // wave_sum in the same order, fmaf((v - mean) * rstd, w, b)): the same bits.  16-byte stores either way.
 // ZERO = false (RAJNI_POOL_DENSE_LAST): a miss stores nothing - layernorm_dropped_kernel wrote that row when its token left.
-template <typename TX, typename TY, bool ZERO = true>
+template <typename TX, typename TY, bool ZERO = true, bool RMS = false>
 __global__ void __launch_bounds__(256) layernorm_dense_kernel(const TX* __restrict__ x, const int32_t* __restrict__ src,
                                                               const float* __restrict__ w, const float* __restrict__ b,
                                                               TY* __restrict__ y, int B, int Nf, int S, int C, float eps) {
@@ -426,6 +498,11 @@ __global__ void __launch_bounds__(256) layernorm_dense_kernel(const TX* __restri
   }
   const TX* xr = x + ((long)img * Nf + lo) * C;
   float v[LN_MAX_CHUNKS][8];
+  if constexpr (RMS) {
+    const float rstd = rms_load_row<TX>(xr, v, lane, nchunk, C, eps);
+    rms_store_row<TY>(v, lane, nchunk, rstd, w, yr);
+    return;
+  }
   float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
@@ -473,7 +550,7 @@ __global__ void __launch_bounds__(256) layernorm_dense_kernel(const TX* __restri
 // statistics, wave_sum in the same order, fmaf((v - mean) * rstd, w, b)): the bits layernorm_dense_kernel gives the same row.
 // What is read from keep and src is clamped as source_idx_kernel clamps: keep values are only compared, and a src value
 // outside [0, S) cannot form an address outside y.
-template <typename TX, typename TY>
+template <typename TX, typename TY, bool RMS = false>
 __global__ void __launch_bounds__(256) layernorm_dropped_kernel(const TX* __restrict__ x, const int32_t* __restrict__ keep,
                                                                 const int32_t* __restrict__ src, const float* __restrict__ w,
                                                                 const float* __restrict__ b, TY* __restrict__ y, int B, int N,
@@ -496,6 +573,11 @@ __global__ void __launch_bounds__(256) layernorm_dropped_kernel(const TX* __rest
   const int nchunk = C >> 3;
   const TX* xr = x + ((long)img * N + j) * C;
   float v[LN_MAX_CHUNKS][8];
+  if constexpr (RMS) {
+    const float rstd = rms_load_row<TX>(xr, v, lane, nchunk, C, eps);
+    rms_store_row<TY>(v, lane, nchunk, rstd, w, y + ((long)img * S + s) * C);
+    return;
+  }
   float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
@@ -693,9 +775,14 @@ __global__ void __launch_bounds__(256) rows_dropped_multi_kernel(const TX* __res
 
 static int launch_layernorm_f16(const void* x, long xs, const float* w, const float* b, void* y, int rows,
                                 int C, float eps, int x_f32, hipStream_t s);
+static int launch_rmsnorm(const void* x, long xs, const float* w, void* y, int rows, int C, float eps, int x_f32, int dtype,
+                          hipStream_t s);
 
 int launch_layernorm(const void* x, long xs, const float* w, const float* b, void* y, int rows,
-                     int C, float eps, int x_f32, int dtype, hipStream_t s) {
+                     int C, float eps, int x_f32, int dtype, hipStream_t s, int kind) {
+  RAJNI_REQUIRE(kind == RAJNI_NORM_LAYERNORM || kind == RAJNI_NORM_RMS, RAJNI_ERR_INVALID,
+                "rajni_norm_rows: kind must be RAJNI_NORM_LAYERNORM or RAJNI_NORM_RMS (%d)", kind);
+  if (kind == RAJNI_NORM_RMS) return launch_rmsnorm(x, xs, w, y, rows, C, eps, x_f32, dtype, s);
   RAJNI_REQUIRE(x && w && b && y, RAJNI_ERR_INVALID, "rajni_layernorm: null pointer");
   RAJNI_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && C <= 64 * 8 * LN_MAX_CHUNKS && xs % 8 == 0,
                 RAJNI_ERR_UNSUPPORTED, "rajni_layernorm: need C %% 8 == 0, C <= 2048, stride %% 8 == 0 (C=%d)", C);
@@ -727,6 +814,36 @@ static int launch_layernorm_f16(const void* x, long xs, const float* w, const fl
   else
     hipLaunchKernelGGL((layernorm_kernel<f16_t, f16_t>), grid, block, 0, s, (const f16_t*)x, xs, w, b, (f16_t*)y, rows, C, eps);
   RAJNI_CHECK_LAUNCH("layernorm_kernel");
+  return RAJNI_OK;
+}
+
+// kind RMS: launch_layernorm's choice of kernel, row mapping and profile class on the RMS instantiations; b does not exist
+template <typename TX, typename TY>
+static void launch_rmsnorm_t(const void* x, long xs, const float* w, void* y, int rows, int C, float eps, hipStream_t s) {
+  const dim3 block(256);
+  if constexpr (__is_same(TX, float) && !__is_same(TY, float)) {
+    if (RAJNI_LN_ROWS > 1 && C <= 1024 && rows >= 4096) {
+      hipLaunchKernelGGL((layernorm_rows_kernel<2, RAJNI_LN_ROWS, TY, true>), dim3((rows + 4 * RAJNI_LN_ROWS - 1) / (4 * RAJNI_LN_ROWS)),
+                         block, 0, s, (const float*)x, xs, w, (const float*)nullptr, (TY*)y, rows, C, eps);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((layernorm_kernel<TX, TY, true>), dim3((rows + 3) / 4), block, 0, s, (const TX*)x, xs, w, (const float*)nullptr,
+                     (TY*)y, rows, C, eps);
+}
+static int launch_rmsnorm(const void* x, long xs, const float* w, void* y, int rows, int C, float eps, int x_f32, int dtype,
+                          hipStream_t s) {
+  RAJNI_REQUIRE(x && w && y, RAJNI_ERR_INVALID, "rajni_norm_rows: null pointer");
+  RAJNI_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && C <= 64 * 8 * LN_MAX_CHUNKS && xs % 8 == 0,
+                RAJNI_ERR_UNSUPPORTED, "rajni_norm_rows: need C %% 8 == 0, C <= 2048, stride %% 8 == 0 (C=%d)", C);
+  const bool f32io = dtype == RAJNI_F32;
+  ProfScope prof(KC_LAYERNORM, s, 4.0 * rows * C, (f32io ? 8.0 : (x_f32 ? 6.0 : 4.0)) * rows * C);
+  if (f32io) launch_rmsnorm_t<float, float>(x, xs, w, y, rows, C, eps, s);
+  else if (dtype == RAJNI_F16 && x_f32) launch_rmsnorm_t<float, f16_t>(x, xs, w, y, rows, C, eps, s);
+  else if (dtype == RAJNI_F16) launch_rmsnorm_t<f16_t, f16_t>(x, xs, w, y, rows, C, eps, s);
+  else if (x_f32) launch_rmsnorm_t<float, bf16_t>(x, xs, w, y, rows, C, eps, s);
+  else launch_rmsnorm_t<bf16_t, bf16_t>(x, xs, w, y, rows, C, eps, s);
+  RAJNI_CHECK_LAUNCH("layernorm_kernel<rms>");
   return RAJNI_OK;
 }
 
@@ -794,27 +911,28 @@ int launch_source_idx(int32_t* src, const int32_t* const* idx, const int* width,
   return RAJNI_OK;
 }
 
-template <bool ZERO>
+template <bool ZERO, bool RMS = false>
 static void launch_dense_kernels(dim3 grid, dim3 block, const void* x, const int32_t* src, const float* w, const float* b, void* y,
                                  int B, int Nf, int S, int C, float eps, int x_f32, int dtype, hipStream_t s) {
   if (dtype == RAJNI_F32)
-    hipLaunchKernelGGL((layernorm_dense_kernel<float, float, ZERO>), grid, block, 0, s, (const float*)x, src, w, b, (float*)y, B, Nf, S, C, eps);
+    hipLaunchKernelGGL((layernorm_dense_kernel<float, float, ZERO, RMS>), grid, block, 0, s, (const float*)x, src, w, b, (float*)y, B, Nf, S, C, eps);
   else if (dtype == RAJNI_F16 && x_f32)
-    hipLaunchKernelGGL((layernorm_dense_kernel<float, f16_t, ZERO>), grid, block, 0, s, (const float*)x, src, w, b, (f16_t*)y, B, Nf, S, C, eps);
+    hipLaunchKernelGGL((layernorm_dense_kernel<float, f16_t, ZERO, RMS>), grid, block, 0, s, (const float*)x, src, w, b, (f16_t*)y, B, Nf, S, C, eps);
   else if (dtype == RAJNI_F16)
-    hipLaunchKernelGGL((layernorm_dense_kernel<f16_t, f16_t, ZERO>), grid, block, 0, s, (const f16_t*)x, src, w, b, (f16_t*)y, B, Nf, S, C, eps);
+    hipLaunchKernelGGL((layernorm_dense_kernel<f16_t, f16_t, ZERO, RMS>), grid, block, 0, s, (const f16_t*)x, src, w, b, (f16_t*)y, B, Nf, S, C, eps);
   else if (x_f32)
-    hipLaunchKernelGGL((layernorm_dense_kernel<float, bf16_t, ZERO>), grid, block, 0, s, (const float*)x, src, w, b, (bf16_t*)y, B, Nf, S, C, eps);
+    hipLaunchKernelGGL((layernorm_dense_kernel<float, bf16_t, ZERO, RMS>), grid, block, 0, s, (const float*)x, src, w, b, (bf16_t*)y, B, Nf, S, C, eps);
   else
-    hipLaunchKernelGGL((layernorm_dense_kernel<bf16_t, bf16_t, ZERO>), grid, block, 0, s, (const bf16_t*)x, src, w, b, (bf16_t*)y, B, Nf, S, C, eps);
+    hipLaunchKernelGGL((layernorm_dense_kernel<bf16_t, bf16_t, ZERO, RMS>), grid, block, 0, s, (const bf16_t*)x, src, w, b, (bf16_t*)y, B, Nf, S, C, eps);
 }
 
 // y [B, S, C] `dtype`: row src[b, j] of image b = LayerNorm(x[b, j]) for the Nf rows of the stream x [B, Nf, C] (fp32 when x_f32,
 // else `dtype`), every other row zero - or, with zero_fill == 0 (RAJNI_POOL_DENSE_LAST), left as it is.  src [B, Nf] strictly
 // ascending per image, values in [0, S).
 int launch_layernorm_dense(const void* x, const int32_t* src, const float* w, const float* b, void* y, int B, int Nf, int S,
-                           int C, float eps, int x_f32, int dtype, hipStream_t s, int zero_fill) {
-  RAJNI_REQUIRE(x && src && w && b && y, RAJNI_ERR_INVALID, "layernorm_dense: null pointer");
+                           int C, float eps, int x_f32, int dtype, hipStream_t s, int zero_fill, int kind) {
+  const bool rms = kind == RAJNI_NORM_RMS;   // (b is not read)
+  RAJNI_REQUIRE(x && src && w && (b || rms) && y, RAJNI_ERR_INVALID, "layernorm_dense: null pointer");
   RAJNI_REQUIRE(B > 0 && Nf > 0 && S >= Nf && C > 0 && C % 8 == 0 && C <= 64 * 8 * LN_MAX_CHUNKS, RAJNI_ERR_UNSUPPORTED,
                 "layernorm_dense: need C %% 8 == 0, C <= 2048 and 0 < Nf <= S (C=%d Nf=%d S=%d)", C, Nf, S);
   const long rows = (long)B * S;
@@ -823,7 +941,9 @@ int launch_layernorm_dense(const void* x, const int32_t* src, const float* w, co
   const double eb = f32io ? 4.0 : 2.0, xb = (f32io || x_f32) ? 4.0 : 2.0;
   ProfScope prof(KC_LAYERNORM, s, 8.0 * B * Nf * C, xb * B * Nf * C + eb * (zero_fill ? rows : (long)B * Nf) * C);
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-  if (zero_fill) launch_dense_kernels<true>(grid, block, x, src, w, b, y, B, Nf, S, C, eps, x_f32, dtype, s);
+  if (rms && zero_fill) launch_dense_kernels<true, true>(grid, block, x, src, w, nullptr, y, B, Nf, S, C, eps, x_f32, dtype, s);
+  else if (rms) launch_dense_kernels<false, true>(grid, block, x, src, w, nullptr, y, B, Nf, S, C, eps, x_f32, dtype, s);
+  else if (zero_fill) launch_dense_kernels<true>(grid, block, x, src, w, b, y, B, Nf, S, C, eps, x_f32, dtype, s);
   else launch_dense_kernels<false>(grid, block, x, src, w, b, y, B, Nf, S, C, eps, x_f32, dtype, s);
   RAJNI_CHECK_LAUNCH("layernorm_dense_kernel");
   return RAJNI_OK;
@@ -833,8 +953,9 @@ int launch_layernorm_dense(const void* x, const int32_t* src, const float* w, co
 // x [B, N, C] (fp32 when x_f32, else `dtype`) that the selection keep [B, Np] does NOT name; no other row is touched.  keep
 // holds P prefix slots, then strictly ascending patch indices; src [B, N] holds values in [0, S).
 int launch_layernorm_dropped(const void* x, const int32_t* keep, const int32_t* src, const float* w, const float* b, void* y,
-                             int B, int N, int Np, int P, int S, int C, float eps, int x_f32, int dtype, hipStream_t s) {
-  RAJNI_REQUIRE(x && keep && src && w && b && y, RAJNI_ERR_INVALID, "layernorm_dropped: null pointer");
+                             int B, int N, int Np, int P, int S, int C, float eps, int x_f32, int dtype, hipStream_t s, int kind) {
+  const bool rms = kind == RAJNI_NORM_RMS;   // (b is not read)
+  RAJNI_REQUIRE(x && keep && src && w && (b || rms) && y, RAJNI_ERR_INVALID, "layernorm_dropped: null pointer");
   RAJNI_REQUIRE(B > 0 && P >= 0 && P < Np && Np <= N && N <= S && C > 0 && C % 8 == 0 && C <= 64 * 8 * LN_MAX_CHUNKS,
                 RAJNI_ERR_UNSUPPORTED, "layernorm_dropped: need C %% 8 == 0, C <= 2048 and 0 <= P < Np <= N <= S (C=%d P=%d Np=%d N=%d S=%d)",
                 C, P, Np, N, S);
@@ -844,7 +965,14 @@ int launch_layernorm_dropped(const void* x, const int32_t* keep, const int32_t* 
   ProfScope prof(KC_LAYERNORM, s, 8.0 * dropped * C, ((f32io || x_f32 ? 4.0 : 2.0) + (f32io ? 4.0 : 2.0)) * dropped * C);
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
 #define RAJNI_LN_DROPPED(TX, TY)                                                                                            \
-  hipLaunchKernelGGL((layernorm_dropped_kernel<TX, TY>), grid, block, 0, s, (const TX*)x, keep, src, w, b, (TY*)y, B, N, Np, P, S, C, eps)
+  do {                                                                                                                      \
+    if (rms)                                                                                                                \
+      hipLaunchKernelGGL((layernorm_dropped_kernel<TX, TY, true>), grid, block, 0, s, (const TX*)x, keep, src, w,           \
+                         (const float*)nullptr, (TY*)y, B, N, Np, P, S, C, eps);                                            \
+    else                                                                                                                    \
+      hipLaunchKernelGGL((layernorm_dropped_kernel<TX, TY>), grid, block, 0, s, (const TX*)x, keep, src, w, b, (TY*)y, B, N, \
+                         Np, P, S, C, eps);                                                                                 \
+  } while (0)
   if (f32io) RAJNI_LN_DROPPED(float, float);
   else if (dtype == RAJNI_F16 && x_f32) RAJNI_LN_DROPPED(float, f16_t);
   else if (dtype == RAJNI_F16) RAJNI_LN_DROPPED(f16_t, f16_t);

@@ -101,8 +101,32 @@ constexpr int QK_NORM_R4_GROUPS = 65536;   // launches of at least this many gro
 constexpr int LS_MAX_CHUNKS = 4;  // 16-byte chunks per lane: C <= 2048, as in rowops.hip
 
 // the row a wave holds in v[][] (chunks c = lane + 64 i < nchunk) -> its LayerNorm, in place in the registers
+// RMS (rajni_hip_norm.h): v -> (v * rsqrt(mean(v^2) + eps)) * w instead - no mean, b never read; the sum of squares in the
+// order of the sums below
+template <bool RMS = false>
 __device__ __forceinline__ void wave_layernorm(float (&v)[LS_MAX_CHUNKS][8], int lane, int nchunk, int C,
                                                const float* __restrict__ w, const float* __restrict__ b, float eps) {
+  if constexpr (RMS) {
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < LS_MAX_CHUNKS; ++i)
+      if (lane + i * 64 < nchunk) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ss += v[i][j] * v[i][j];
+      }
+    const float rstd = rsqrtf(wave_sum(ss) / (float)C + eps);
+#pragma unroll
+    for (int i = 0; i < LS_MAX_CHUNKS; ++i) {
+      const int c = lane + i * 64;
+      if (c < nchunk) {
+        float wv[8];
+        load8<float>(w + c * 8, wv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[i][j] = (v[i][j] * rstd) * wv[j];
+      }
+    }
+    return;
+  }
   float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < LS_MAX_CHUNKS; ++i)
@@ -139,7 +163,7 @@ __device__ __forceinline__ void wave_layernorm(float (&v)[LS_MAX_CHUNKS][8], int
 
 // x[row] = LayerNorm(x[row]) in the stream's own type; a row is owned by one wave and held in registers between its
 // load and its store, so in place is safe
-template <typename T>
+template <typename T, bool RMS = false>
 __global__ void __launch_bounds__(256) layernorm_stream_kernel(T* x, const float* __restrict__ w, const float* __restrict__ b,
                                                                int rows, int C, float eps) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -151,10 +175,41 @@ __global__ void __launch_bounds__(256) layernorm_stream_kernel(T* x, const float
 #pragma unroll
   for (int i = 0; i < LS_MAX_CHUNKS; ++i)
     if (lane + i * 64 < nchunk) load8<T>(xr + (lane + i * 64) * 8, v[i]);
-  wave_layernorm(v, lane, nchunk, C, w, b, eps);
+  wave_layernorm<RMS>(v, lane, nchunk, C, w, b, eps);
 #pragma unroll
   for (int i = 0; i < LS_MAX_CHUNKS; ++i)
     if (lane + i * 64 < nchunk) store8<T>(xr + (lane + i * 64) * 8, v[i]);
+}
+
+// patch_embed.norm (rajni_hip_norm.h): x[b, P + j] = norm(x[b, P + j]) + pos[pos_off + j] for the N - P patch rows of every image
+// of the stream x [B, N, C], in place and in the stream's own type; the P prefix rows are not touched.  pos rows are in the
+// model's 16-bit type TP (float with an fp32 model).  One wave per patch row: the row waits in registers between its load and
+// its store, the norm is wave_layernorm's and the position row is added in fp32 before the one rounding of the store.
+template <typename T, typename TP, bool RMS>
+__global__ void __launch_bounds__(256) embed_norm_kernel(T* x, const float* __restrict__ w, const float* __restrict__ b,
+                                                         const TP* __restrict__ pos, int pos_off, int B, int N, int P, int C, float eps) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int patches = N - P;
+  const long row = (long)blockIdx.x * 4 + wave;
+  if (row >= (long)B * patches) return;
+  const int img = (int)(row / patches), j = (int)(row - (long)img * patches);
+  const int nchunk = C >> 3;
+  T* xr = x + ((long)img * N + P + j) * C;
+  const TP* pr = pos + (long)(pos_off + j) * C;
+  float v[LS_MAX_CHUNKS][8];
+#pragma unroll
+  for (int i = 0; i < LS_MAX_CHUNKS; ++i)
+    if (lane + i * 64 < nchunk) load8<T>(xr + (lane + i * 64) * 8, v[i]);
+  wave_layernorm<RMS>(v, lane, nchunk, C, w, b, eps);
+#pragma unroll
+  for (int i = 0; i < LS_MAX_CHUNKS; ++i)
+    if (lane + i * 64 < nchunk) {
+      float pv[8];
+      load8<TP>(pr + (lane + i * 64) * 8, pv);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[i][e] += pv[e];
+      store8<T>(xr + (lane + i * 64) * 8, v[i]);
+    }
 }
 
 // One workgroup of 8 waves per image.  out[img] = fc_norm(mean_{r0 <= r < r1} norm(x[img, r])), either norm optional.
@@ -162,7 +217,7 @@ __global__ void __launch_bounds__(256) layernorm_stream_kernel(T* x, const float
 // then ((s_0 + s_1) + s_2) + s_3.  'token' pooling is r0 = 0, r1 = 1: one row, the sums are that row; 'avg' is r0 = the number
 // of prefix tokens (CLS + registers), r1 = N.
 constexpr int POOL_WAVES = 8;
-template <typename TX, typename TY>
+template <typename TX, typename TY, bool RMS = false>
 __global__ void __launch_bounds__(64 * POOL_WAVES) pool_norm_kernel(const TX* __restrict__ x, int N, int C, int r0, int r1,
                                                                    const float* __restrict__ nw, const float* __restrict__ nb, float neps,
                                                                    const float* __restrict__ fw, const float* __restrict__ fb, float feps,
@@ -181,7 +236,7 @@ __global__ void __launch_bounds__(64 * POOL_WAVES) pool_norm_kernel(const TX* __
 #pragma unroll
     for (int i = 0; i < LS_MAX_CHUNKS; ++i)
       if (lane + i * 64 < nchunk) load8<TX>(xi + (long)r * C + (lane + i * 64) * 8, v[i]);
-    if (nw != nullptr) wave_layernorm(v, lane, nchunk, C, nw, nb, neps);
+    if (nw != nullptr) wave_layernorm<RMS>(v, lane, nchunk, C, nw, nb, neps);
 #pragma unroll
     for (int i = 0; i < LS_MAX_CHUNKS; ++i)
       if (lane + i * 64 < nchunk) {
@@ -224,7 +279,7 @@ __global__ void __launch_bounds__(64 * POOL_WAVES) pool_norm_kernel(const TX* __
         acc[i][j] = r1 - r0 > 1 ? s * inv : s;
       }
     }
-  if (fw != nullptr) wave_layernorm(acc, lane, nchunk, C, fw, fb, feps);
+  if (fw != nullptr) wave_layernorm<RMS>(acc, lane, nchunk, C, fw, fb, feps);
   TY* o = out + (long)blockIdx.x * C;
 #pragma unroll
   for (int i = 0; i < LS_MAX_CHUNKS; ++i)
@@ -254,16 +309,16 @@ void launch_qk_norm_lw(void* qkv, const float* qw, const float* qb, const float*
   else launch_qk_norm_t<T, 16>(qkv, qw, qb, kw, kb, groups, H, D, eps, s);
 }
 
-template <typename TX>
+template <typename TX, bool RMS = false>
 void launch_pool_norm_t(const void* x, int B, int N, int C, int r0, int r1, const float* nw, const float* nb, float neps,
                         const float* fw, const float* fb, float feps, void* out, int dtype, hipStream_t s) {
   const dim3 grid(B), block(64 * POOL_WAVES);
   if (dtype == RAJNI_F32)
-    hipLaunchKernelGGL((pool_norm_kernel<TX, float>), grid, block, 0, s, (const TX*)x, N, C, r0, r1, nw, nb, neps, fw, fb, feps, (float*)out);
+    hipLaunchKernelGGL((pool_norm_kernel<TX, float, RMS>), grid, block, 0, s, (const TX*)x, N, C, r0, r1, nw, nb, neps, fw, fb, feps, (float*)out);
   else if (dtype == RAJNI_F16)
-    hipLaunchKernelGGL((pool_norm_kernel<TX, f16_t>), grid, block, 0, s, (const TX*)x, N, C, r0, r1, nw, nb, neps, fw, fb, feps, (f16_t*)out);
+    hipLaunchKernelGGL((pool_norm_kernel<TX, f16_t, RMS>), grid, block, 0, s, (const TX*)x, N, C, r0, r1, nw, nb, neps, fw, fb, feps, (f16_t*)out);
   else
-    hipLaunchKernelGGL((pool_norm_kernel<TX, bf16_t>), grid, block, 0, s, (const TX*)x, N, C, r0, r1, nw, nb, neps, fw, fb, feps, (bf16_t*)out);
+    hipLaunchKernelGGL((pool_norm_kernel<TX, bf16_t, RMS>), grid, block, 0, s, (const TX*)x, N, C, r0, r1, nw, nb, neps, fw, fb, feps, (bf16_t*)out);
 }
 
 }  // namespace
@@ -289,14 +344,20 @@ int launch_qk_norm(void* qkv, const float* qw, const float* qb, const float* kw,
   return RAJNI_OK;
 }
 
-int launch_layernorm_stream(void* x, const float* w, const float* b, int rows, int C, float eps, int x_f32, int dtype, hipStream_t s) {
+int launch_layernorm_stream(void* x, const float* w, const float* b, int rows, int C, float eps, int x_f32, int dtype, hipStream_t s,
+                            int kind) {
   RAJNI_REQUIRE(x && w, RAJNI_ERR_INVALID, "rajni_layernorm_stream: null pointer");
   RAJNI_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && C <= 64 * 8 * LS_MAX_CHUNKS, RAJNI_ERR_UNSUPPORTED,
                 "rajni_layernorm_stream: need C %% 8 == 0, C <= 2048 (C=%d)", C);
   const bool f32 = dtype == RAJNI_F32 || x_f32;
   ProfScope prof(KC_LAYERNORM, s, 8.0 * rows * C, (f32 ? 8.0 : 4.0) * rows * C);
   const dim3 grid((rows + 3) / 4), block(256);
-  if (f32) hipLaunchKernelGGL((layernorm_stream_kernel<float>), grid, block, 0, s, (float*)x, w, b, rows, C, eps);
+  if (kind == RAJNI_NORM_RMS) {
+    const float* nob = nullptr;
+    if (f32) hipLaunchKernelGGL((layernorm_stream_kernel<float, true>), grid, block, 0, s, (float*)x, w, nob, rows, C, eps);
+    else if (dtype == RAJNI_F16) hipLaunchKernelGGL((layernorm_stream_kernel<f16_t, true>), grid, block, 0, s, (f16_t*)x, w, nob, rows, C, eps);
+    else hipLaunchKernelGGL((layernorm_stream_kernel<bf16_t, true>), grid, block, 0, s, (bf16_t*)x, w, nob, rows, C, eps);
+  } else if (f32) hipLaunchKernelGGL((layernorm_stream_kernel<float>), grid, block, 0, s, (float*)x, w, b, rows, C, eps);
   else if (dtype == RAJNI_F16) hipLaunchKernelGGL((layernorm_stream_kernel<f16_t>), grid, block, 0, s, (f16_t*)x, w, b, rows, C, eps);
   else hipLaunchKernelGGL((layernorm_stream_kernel<bf16_t>), grid, block, 0, s, (bf16_t*)x, w, b, rows, C, eps);
   RAJNI_CHECK_LAUNCH("layernorm_stream_kernel");
@@ -304,7 +365,8 @@ int launch_layernorm_stream(void* x, const float* w, const float* b, int rows, i
 }
 
 int launch_pool_norm(const void* x, int B, int N, int C, int pool, const float* nw, const float* nb, float neps,
-                     const float* fw, const float* fb, float feps, void* out, int x_f32, int dtype, hipStream_t s, int num_prefix) {
+                     const float* fw, const float* fb, float feps, void* out, int x_f32, int dtype, hipStream_t s, int num_prefix,
+                     int kind) {
   RAJNI_REQUIRE(x && out, RAJNI_ERR_INVALID, "rajni_pool_norm: null pointer");
   // (0: a sequence without a class row, from rajni_hip_query.h's forward alone - rajni_pool_norm_prefix refuses it itself)
   RAJNI_REQUIRE(num_prefix >= 0 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID,
@@ -318,9 +380,50 @@ int launch_pool_norm(const void* x, int B, int N, int C, int pool, const float* 
   const int r0 = pool == RAJNI_POOL_AVG ? num_prefix : 0, r1 = pool == RAJNI_POOL_AVG ? N : 1;
   const bool f32 = dtype == RAJNI_F32 || x_f32;
   ProfScope prof(KC_LAYERNORM, s, 8.0 * B * (r1 - r0) * C, (f32 ? 4.0 : 2.0) * B * (r1 - r0) * C);
-  if (f32) launch_pool_norm_t<float>(x, B, N, C, r0, r1, nw, nb, neps, fw, fb, feps, out, dtype, s);
+  if (kind == RAJNI_NORM_RMS) {   // (neither bias is read)
+    if (f32) launch_pool_norm_t<float, true>(x, B, N, C, r0, r1, nw, nullptr, neps, fw, nullptr, feps, out, dtype, s);
+    else if (dtype == RAJNI_F16) launch_pool_norm_t<f16_t, true>(x, B, N, C, r0, r1, nw, nullptr, neps, fw, nullptr, feps, out, dtype, s);
+    else launch_pool_norm_t<bf16_t, true>(x, B, N, C, r0, r1, nw, nullptr, neps, fw, nullptr, feps, out, dtype, s);
+  } else if (f32) launch_pool_norm_t<float>(x, B, N, C, r0, r1, nw, nb, neps, fw, fb, feps, out, dtype, s);
   else if (dtype == RAJNI_F16) launch_pool_norm_t<f16_t>(x, B, N, C, r0, r1, nw, nb, neps, fw, fb, feps, out, dtype, s);
   else launch_pool_norm_t<bf16_t>(x, B, N, C, r0, r1, nw, nb, neps, fw, fb, feps, out, dtype, s);
   RAJNI_CHECK_LAUNCH("pool_norm_kernel");
+  return RAJNI_OK;
+}
+
+// the patch rows of the stream x [B, N, C] (fp32 when x_f32, else `dtype`) through patch_embed.norm, then + pos[pos_off + j]
+// (pos in `dtype`); see embed_norm_kernel
+int launch_embed_norm(int kind, void* x, const float* w, const float* b, const void* pos, int pos_off, int B, int N, int num_prefix,
+                      int C, float eps, int dtype, int x_f32, hipStream_t s) {
+  RAJNI_REQUIRE(kind == RAJNI_NORM_LAYERNORM || kind == RAJNI_NORM_RMS, RAJNI_ERR_INVALID,
+                "rajni_embed_norm: kind must be RAJNI_NORM_LAYERNORM or RAJNI_NORM_RMS (%d)", kind);
+  RAJNI_REQUIRE(x && w && pos, RAJNI_ERR_INVALID, "rajni_embed_norm: null pointer");
+  RAJNI_REQUIRE(B > 0 && num_prefix >= 0 && num_prefix <= RAJNI_MAX_PREFIX && N > num_prefix && pos_off >= 0, RAJNI_ERR_INVALID,
+                "rajni_embed_norm: need B > 0, 0 <= num_prefix <= %d, N > num_prefix and pos_off >= 0 (B=%d N=%d num_prefix=%d pos_off=%d)",
+                RAJNI_MAX_PREFIX, B, N, num_prefix, pos_off);
+  RAJNI_REQUIRE(C > 0 && C % 8 == 0 && C <= 64 * 8 * LS_MAX_CHUNKS, RAJNI_ERR_UNSUPPORTED,
+                "rajni_embed_norm: need C %% 8 == 0, C <= 2048 (C=%d)", C);
+  const long rows = (long)B * (N - num_prefix);
+  RAJNI_REQUIRE((rows + 3) / 4 < (1L << 31), RAJNI_ERR_UNSUPPORTED, "rajni_embed_norm: too many rows (%ld)", rows);
+  const bool f32 = dtype == RAJNI_F32 || x_f32;
+  ProfScope prof(KC_LAYERNORM, s, 9.0 * rows * C, ((f32 ? 8.0 : 4.0) + (dtype == RAJNI_F32 ? 4.0 : 2.0)) * rows * C);
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  const float* nob = nullptr;
+#define RAJNI_EMBED_NORM(T, TP)                                                                                                 \
+  do {                                                                                                                          \
+    if (kind == RAJNI_NORM_RMS)                                                                                                 \
+      hipLaunchKernelGGL((embed_norm_kernel<T, TP, true>), grid, block, 0, s, (T*)x, w, nob, (const TP*)pos, pos_off, B, N,      \
+                         num_prefix, C, eps);                                                                                   \
+    else                                                                                                                        \
+      hipLaunchKernelGGL((embed_norm_kernel<T, TP, false>), grid, block, 0, s, (T*)x, w, b, (const TP*)pos, pos_off, B, N,       \
+                         num_prefix, C, eps);                                                                                   \
+  } while (0)
+  if (dtype == RAJNI_F32) RAJNI_EMBED_NORM(float, float);
+  else if (dtype == RAJNI_F16 && x_f32) RAJNI_EMBED_NORM(float, f16_t);
+  else if (dtype == RAJNI_F16) RAJNI_EMBED_NORM(f16_t, f16_t);
+  else if (x_f32) RAJNI_EMBED_NORM(float, bf16_t);
+  else RAJNI_EMBED_NORM(bf16_t, bf16_t);
+#undef RAJNI_EMBED_NORM
+  RAJNI_CHECK_LAUNCH("embed_norm_kernel");
   return RAJNI_OK;
 }

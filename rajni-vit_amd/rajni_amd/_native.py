@@ -239,6 +239,27 @@ _ATTNPOOL_SIGS = {
                                        c_void_p]),
 }
 ATTNPOOL_SYMBOLS = tuple(_ATTNPOOL_SIGS.keys())
+# include/rajni_hip_norm.h, additive in the same way: RMSNorm trunks and the patch-embedding norm (the AIMv2 ViTs)
+NORM_LAYERNORM, NORM_RMS = 0, 1      # rajni_vit_norm.kind
+
+
+class VitNorm(C.Structure):
+    """rajni_vit_norm (include/rajni_hip_norm.h): the kind of every norm of the forward but q/k-norm, and patch_embed.norm"""
+    _fields_ = [("kind", c_int), ("embed_norm_eps", c_float), ("embed_norm_w", c_void_p), ("embed_norm_b", c_void_p)]
+
+
+_NORM_SIGS = {
+    "rajni_norm_rows": (c_int, [c_int, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_int,
+                                c_void_p]),
+    "rajni_embed_norm": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                 c_int, c_int, c_void_p]),
+    "rajni_vit_workspace_bytes_norm": (c_size_t, [C.POINTER(VitPlan), C.POINTER(VitPrefix), C.POINTER(VitImage),
+                                                  C.POINTER(VitQuery), C.POINTER(VitAttnPool), C.POINTER(VitNorm)]),
+    "rajni_vit_forward_norm": (c_int, [C.POINTER(VitPlan), C.POINTER(VitExt), C.POINTER(VitPrefix), C.POINTER(VitLayers),
+                                       C.POINTER(VitImage), C.POINTER(VitQuery), C.POINTER(VitAttnPool), C.POINTER(VitNorm),
+                                       c_void_p, c_void_p, c_void_p]),
+}
+NORM_SYMBOLS = tuple(_NORM_SIGS.keys())
 RESAMPLE_MAX_GRID = 128     # RAJNI_RESAMPLE_MAX_GRID: grid cells per axis, source and destination
 ABI_VERSION = 8     # include/rajni_hip.h; bumped whenever a struct or an entry point changes
 _lib: Optional[C.CDLL] = None
@@ -255,7 +276,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
             "(hipcc --offload-arch=gfx950). rajni_amd has no CPU or PyTorch fallback by design.")
     lib = C.CDLL(path)
     for name, (res, args) in (list(_SIGS.items()) + list(_LAYERS_SIGS.items()) + list(_IMAGE_SIGS.items()) + list(_QUERY_SIGS.items())
-                              + list(_ATTNPOOL_SIGS.items())):
+                              + list(_ATTNPOOL_SIGS.items()) + list(_NORM_SIGS.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

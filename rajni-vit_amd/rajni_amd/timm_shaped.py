@@ -76,7 +76,15 @@ class ViTConfig:
                                           # reg_tokens to be the last field)
     reg_tokens: int = 0                   # register tokens behind the class token (timm reg_tokens; DINOv2 "reg4": 4)
 
+    # What NormViTConfig (below) makes fields: plain class attributes here, so that every config answers `cfg.norm`,
+    # `cfg.embed_norm` and `cfg.bias` while this class keeps the twenty fields existing tests count.
+    norm = "layernorm"
+    embed_norm = False
+    bias = True
+
     def __post_init__(self):
+        if self.norm not in ("layernorm", "rms"):
+            raise ValueError(f"ViTConfig: norm must be 'layernorm' or 'rms', got {self.norm!r}")
         if self.distilled and self.reg_tokens:
             raise ValueError("ViTConfig: distilled together with reg_tokens is not a timm model")
         if self.mlp not in ("mlp", "swiglu_packed", "swiglu"):
@@ -108,6 +116,17 @@ class ViTConfig:
 
     def to_dict(self):
         return asdict(self)
+
+
+@dataclass(frozen=True)
+class NormViTConfig(ViTConfig):
+    """ViTConfig plus the norm options of the AIMv2 image towers.  A subclass, not three more fields of ViTConfig: existing
+    tests hold that class to its twenty fields and to the order of the last five.  (Keyword only in practice.)"""
+    norm: str = "layernorm"               # every norm of the trunk but q/k-norm: "layernorm" or "rms" (timm RmsNorm: a weight,
+                                          # no bias, no mean)
+    embed_norm: bool = False              # timm embed_norm_layer: PatchEmbed.norm of that kind on the projected patch rows,
+                                          # in front of the position embedding
+    bias: bool = True                     # False: no bias in qkv, proj and the MLP (the patch projection keeps its own)
 
 
 # The model names BASELINE.json's configs use.
@@ -280,13 +299,59 @@ MAP_CONFIGS: Dict[str, ViTConfig] = {
 }
 
 
+# RMSNorm trunks and a norm inside the patch embedding, in a table of their own for the same reason.
+_AIMV2 = dict(patch_size=14, depth=24, num_classes=0, ln_eps=1e-5, global_pool="avg", fc_norm=False, class_token=False,
+              mlp="swiglu", norm="rms", embed_norm=True, bias=False)
+NORM_CONFIGS: Dict[str, ViTConfig] = {
+    # Apple's AIMv2 image towers (timm `aimv2_*_patch14_224`): RmsNorm(eps=1e-5) for norm1, norm2, norm and patch_embed.norm, the
+    # split SwiGLU MLP, no class token, global_pool='avg' without fc_norm, headless, no bias in qkv / proj / the MLP.  timm is
+    # not importable where this was written: the entries were WRITTEN FROM MEMORY OF timm 1.x AND ARE UNVERIFIED (width, depth,
+    # heads, MLP width, eps and which linears carry a bias may each be off); no test depends on their being exact.  The _336 and
+    # _448 checkpoints differ in img_size alone.  aimv2_3b is 3072 wide: beyond the row kernels' C <= 2048, so RAJNIViTWrapper
+    # refuses it - it is listed to say so.
+    "aimv2_large_patch14_224": NormViTConfig(embed_dim=1024, num_heads=8, mlp_ratio=2816 / 1024, **_AIMV2),
+    "aimv2_huge_patch14_224": NormViTConfig(embed_dim=1536, num_heads=12, mlp_ratio=4096 / 1536, **_AIMV2),
+    "aimv2_1b_patch14_224": NormViTConfig(embed_dim=2048, num_heads=16, mlp_ratio=5632 / 2048, **_AIMV2),
+    "aimv2_3b_patch14_224": NormViTConfig(embed_dim=3072, num_heads=24, mlp_ratio=8192 / 3072, **_AIMV2),
+    # micro models (not timm names): vit_micro_patch16_64 with RMS norms; the AIMv2 recipe at micro cost (16 tokens, head dim
+    # 64); the same with head dim 128 and patch 14 (the general head-dim kernels, the materialised patch columns); a LayerNorm
+    # model with a LayerNorm patch_embed.norm, a class token and 4 registers and a pos-embed row for each of them
+    "vit_micro_rms_patch16_64": NormViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, num_classes=10, norm="rms"),
+    "vit_micro_aimv2_patch16_64": NormViTConfig(img_size=64, embed_dim=128, num_heads=2, mlp_ratio=2.0,
+                                                **{**_AIMV2, "patch_size": 16, "depth": 4}),
+    "vit_micro_aimv2_d128_patch14_56": NormViTConfig(img_size=56, embed_dim=256, num_heads=2, mlp_ratio=2.0,
+                                                     **{**_AIMV2, "depth": 4}),
+    "vit_micro_reg4_embednorm_patch16_64": NormViTConfig(img_size=64, embed_dim=128, depth=4, num_heads=2, num_classes=10,
+                                                         reg_tokens=4, embed_norm=True),
+}
+
+
 def config_of(name: str) -> ViTConfig:
-    """the built-in config of that name, from CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS or MAP_CONFIGS"""
-    tables = (CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS, MAP_CONFIGS)
+    """the built-in config of that name, from CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS, MAP_CONFIGS or NORM_CONFIGS"""
+    tables = (CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS, MAP_CONFIGS, NORM_CONFIGS)
     for table in tables:
         if name in table:
             return table[name]
     raise KeyError(f"'{name}' is not a built-in config {[n for t in tables for n in sorted(t)]}")
+
+
+class RmsNorm(nn.Module):
+    """timm `RmsNorm`: x * rsqrt(mean(x^2) + eps) * weight over the last axis - a weight, no bias, no mean.  The statistics are
+    fp32 whatever the input's dtype; the normalised row returns to that dtype before the weight multiplies it."""
+
+    def __init__(self, dim: int, eps: float = 1e-6):
+        super().__init__()
+        self.normalized_shape = (dim,)
+        self.eps = eps
+        self.weight = nn.Parameter(torch.ones(dim))
+
+    def forward(self, x):
+        xf = x.float()
+        return (xf * torch.rsqrt(xf.pow(2).mean(dim=-1, keepdim=True) + self.eps)).to(x.dtype) * self.weight
+
+
+def make_norm(cfg: "ViTConfig", dim: int) -> nn.Module:
+    return RmsNorm(dim, eps=cfg.ln_eps) if cfg.norm == "rms" else nn.LayerNorm(dim, eps=cfg.ln_eps)
 
 
 class PatchEmbed(nn.Module):
@@ -296,23 +361,23 @@ class PatchEmbed(nn.Module):
         self.patch_size = (cfg.patch_size, cfg.patch_size)
         self.num_patches = cfg.num_patches
         self.proj = nn.Conv2d(cfg.in_chans, cfg.embed_dim, cfg.patch_size, cfg.patch_size)
-        self.norm = nn.Identity()
+        self.norm = make_norm(cfg, cfg.embed_dim) if cfg.embed_norm else nn.Identity()
 
     def forward(self, x):
         return self.norm(self.proj(x).flatten(2).transpose(1, 2))
 
 
 class Attention(nn.Module):
-    def __init__(self, dim: int, num_heads: int, qk_norm: bool = False, ln_eps: float = 1e-6):
+    def __init__(self, dim: int, num_heads: int, qk_norm: bool = False, ln_eps: float = 1e-6, bias: bool = True):
         super().__init__()
         self.num_heads = num_heads
         self.head_dim = dim // num_heads
         self.scale = self.head_dim ** -0.5
-        self.qkv = nn.Linear(dim, dim * 3, bias=True)
+        self.qkv = nn.Linear(dim, dim * 3, bias=bias)
         self.q_norm = nn.LayerNorm(self.head_dim, eps=ln_eps) if qk_norm else nn.Identity()
         self.k_norm = nn.LayerNorm(self.head_dim, eps=ln_eps) if qk_norm else nn.Identity()
         self.attn_drop = nn.Dropout(0.0)
-        self.proj = nn.Linear(dim, dim)
+        self.proj = nn.Linear(dim, dim, bias=bias)
         self.proj_drop = nn.Dropout(0.0)
 
     def forward(self, x):
@@ -341,15 +406,15 @@ class QuickGELU(nn.Module):
 
 
 class Mlp(nn.Module):
-    def __init__(self, dim: int, hidden: int, act: str = "gelu"):
+    def __init__(self, dim: int, hidden: int, act: str = "gelu", bias: bool = True):
         super().__init__()
         if act not in ("gelu", "quick_gelu"):
             raise ValueError(f"act must be 'gelu' or 'quick_gelu', got {act!r}")
-        self.fc1 = nn.Linear(dim, hidden)
+        self.fc1 = nn.Linear(dim, hidden, bias=bias)
         self.act = nn.GELU() if act == "gelu" else QuickGELU()
         self.drop1 = nn.Dropout(0.0)
         self.norm = nn.Identity()
-        self.fc2 = nn.Linear(hidden, dim)
+        self.fc2 = nn.Linear(hidden, dim, bias=bias)
         self.drop2 = nn.Dropout(0.0)
 
     def forward(self, x):
@@ -360,15 +425,15 @@ class GluMlp(nn.Module):
     """timm `GluMlp` (with act_layer=nn.SiLU and gate_last=False: `SwiGLUPacked`): one packed fc1 of 2 * hidden outputs,
     x1, x2 = fc1(x).chunk(2, -1); gate_last=False: act(x1) * x2, gate_last=True: x1 * act(x2)"""
 
-    def __init__(self, dim: int, hidden: int, act_layer=nn.SiLU, gate_last: bool = False):
+    def __init__(self, dim: int, hidden: int, act_layer=nn.SiLU, gate_last: bool = False, bias: bool = True):
         super().__init__()
         self.chunk_dim = -1
         self.gate_last = gate_last
-        self.fc1 = nn.Linear(dim, 2 * hidden)
+        self.fc1 = nn.Linear(dim, 2 * hidden, bias=bias)
         self.act = act_layer()
         self.drop1 = nn.Dropout(0.0)
         self.norm = nn.Identity()
-        self.fc2 = nn.Linear(hidden, dim)
+        self.fc2 = nn.Linear(hidden, dim, bias=bias)
         self.drop2 = nn.Dropout(0.0)
 
     def forward(self, x):
@@ -380,14 +445,14 @@ class GluMlp(nn.Module):
 class SwiGLU(nn.Module):
     """timm `SwiGLU`: the gate and the value projection apart, act(fc1_g(x)) * fc1_x(x)"""
 
-    def __init__(self, dim: int, hidden: int, act_layer=nn.SiLU):
+    def __init__(self, dim: int, hidden: int, act_layer=nn.SiLU, bias: bool = True):
         super().__init__()
-        self.fc1_g = nn.Linear(dim, hidden)
-        self.fc1_x = nn.Linear(dim, hidden)
+        self.fc1_g = nn.Linear(dim, hidden, bias=bias)
+        self.fc1_x = nn.Linear(dim, hidden, bias=bias)
         self.act = act_layer()
         self.drop1 = nn.Dropout(0.0)
         self.norm = nn.Identity()
-        self.fc2 = nn.Linear(hidden, dim)
+        self.fc2 = nn.Linear(hidden, dim, bias=bias)
         self.drop2 = nn.Dropout(0.0)
 
     def forward(self, x):
@@ -397,10 +462,10 @@ class SwiGLU(nn.Module):
 
 def make_mlp(cfg: "ViTConfig") -> nn.Module:
     if cfg.mlp == "swiglu_packed":
-        return GluMlp(cfg.embed_dim, cfg.hidden_dim)
+        return GluMlp(cfg.embed_dim, cfg.hidden_dim, bias=cfg.bias)
     if cfg.mlp == "swiglu":
-        return SwiGLU(cfg.embed_dim, cfg.hidden_dim)
-    return Mlp(cfg.embed_dim, cfg.hidden_dim, cfg.act)
+        return SwiGLU(cfg.embed_dim, cfg.hidden_dim, bias=cfg.bias)
+    return Mlp(cfg.embed_dim, cfg.hidden_dim, cfg.act, bias=cfg.bias)
 
 
 class AttentionPoolLatent(nn.Module):
@@ -444,11 +509,11 @@ class Block(nn.Module):
     def __init__(self, cfg: ViTConfig):
         super().__init__()
         C = cfg.embed_dim
-        self.norm1 = nn.LayerNorm(C, eps=cfg.ln_eps)
-        self.attn = Attention(C, cfg.num_heads, cfg.qk_norm, cfg.ln_eps)
+        self.norm1 = make_norm(cfg, C)
+        self.attn = Attention(C, cfg.num_heads, cfg.qk_norm, cfg.ln_eps, cfg.bias)
         self.ls1 = LayerScale(C, cfg.layer_scale) if cfg.layer_scale else nn.Identity()
         self.drop_path1 = nn.Identity()
-        self.norm2 = nn.LayerNorm(C, eps=cfg.ln_eps)
+        self.norm2 = make_norm(cfg, C)
         self.mlp = make_mlp(cfg)
         self.ls2 = LayerScale(C, cfg.layer_scale) if cfg.layer_scale else nn.Identity()
         self.drop_path2 = nn.Identity()
@@ -485,13 +550,13 @@ class VisionTransformer(nn.Module):
         # timm: an attn_pool attribute on every model, None unless global_pool == 'map'
         self.attn_pool = (AttentionPoolLatent(cfg.embed_dim, cfg.num_heads, cfg.mlp_ratio, cfg.ln_eps, cfg.act)
                           if cfg.global_pool == "map" else None)
-        self.norm_pre = nn.LayerNorm(cfg.embed_dim, eps=cfg.ln_eps) if cfg.pre_norm else nn.Identity()
+        self.norm_pre = make_norm(cfg, cfg.embed_dim) if cfg.pre_norm else nn.Identity()
         self.blocks = nn.Sequential(*[Block(cfg) for _ in range(cfg.depth)])
         # timm: the final norm moves behind the pooling (fc_norm) when fc_norm is in use
-        self.norm = nn.Identity() if cfg.use_fc_norm else nn.LayerNorm(cfg.embed_dim, eps=cfg.ln_eps)
-        self.fc_norm = nn.LayerNorm(cfg.embed_dim, eps=cfg.ln_eps) if cfg.use_fc_norm else nn.Identity()
+        self.norm = nn.Identity() if cfg.use_fc_norm else make_norm(cfg, cfg.embed_dim)
+        self.fc_norm = make_norm(cfg, cfg.embed_dim) if cfg.use_fc_norm else nn.Identity()
         self.head_drop = nn.Dropout(0.0)
-        self.head = nn.Linear(cfg.embed_dim, cfg.num_classes)
+        self.head = nn.Linear(cfg.embed_dim, cfg.num_classes) if cfg.num_classes > 0 else nn.Identity()   # timm num_classes=0
         if cfg.distilled:
             if cfg.global_pool != "token" or cfg.use_fc_norm:
                 raise ValueError("a distilled model has a token head and no fc_norm")
@@ -550,6 +615,7 @@ def synth_state_dict(cfg: ViTConfig, seed: int = 0, std: float = 0.02,
         return (rng.standard_normal(shape, dtype=np.float32) * np.float32(s)).astype(np.float32)
 
     sd: Dict[str, np.ndarray] = {}
+    rms, lin_bias = cfg.norm == "rms", cfg.bias      # (an RmsNorm has no bias and a bias-free linear none: nothing is drawn)
     if cfg.class_token:      # (a model without one draws nothing in its place)
         sd["cls_token"] = nrm(1, 1, C)
     n_pos = cfg.num_patches if cfg.no_embed_class else cfg.num_patches + cfg.num_prefix_tokens
@@ -561,21 +627,27 @@ def synth_state_dict(cfg: ViTConfig, seed: int = 0, std: float = 0.02,
         p = f"blocks.{i}."
         for ln in ("norm1", "norm2"):
             sd[p + ln + ".weight"] = (1.0 + nrm(C, s=bias_std)).astype(np.float32)
-            sd[p + ln + ".bias"] = nrm(C, s=bias_std) if bias_std else np.zeros(C, np.float32)
+            if not rms:
+                sd[p + ln + ".bias"] = nrm(C, s=bias_std) if bias_std else np.zeros(C, np.float32)
         sd[p + "attn.qkv.weight"] = nrm(3 * C, C)
-        sd[p + "attn.qkv.bias"] = nrm(3 * C, s=bias_std) if bias_std else np.zeros(3 * C, np.float32)
+        if lin_bias:
+            sd[p + "attn.qkv.bias"] = nrm(3 * C, s=bias_std) if bias_std else np.zeros(3 * C, np.float32)
         sd[p + "attn.proj.weight"] = nrm(C, C)
-        sd[p + "attn.proj.bias"] = nrm(C, s=bias_std) if bias_std else np.zeros(C, np.float32)
+        if lin_bias:
+            sd[p + "attn.proj.bias"] = nrm(C, s=bias_std) if bias_std else np.zeros(C, np.float32)
         if cfg.mlp == "swiglu":      # timm SwiGLU: gate, then value (a plain config draws exactly what it always drew)
             for fc in ("fc1_g", "fc1_x"):
                 sd[p + f"mlp.{fc}.weight"] = nrm(Hd, C)
-                sd[p + f"mlp.{fc}.bias"] = nrm(Hd, s=bias_std) if bias_std else np.zeros(Hd, np.float32)
+                if lin_bias:
+                    sd[p + f"mlp.{fc}.bias"] = nrm(Hd, s=bias_std) if bias_std else np.zeros(Hd, np.float32)
         else:
             H1 = 2 * Hd if cfg.mlp == "swiglu_packed" else Hd   # packed: rows [0, Hd) the gate, [Hd, 2 Hd) the value
             sd[p + "mlp.fc1.weight"] = nrm(H1, C)
-            sd[p + "mlp.fc1.bias"] = nrm(H1, s=bias_std) if bias_std else np.zeros(H1, np.float32)
+            if lin_bias:
+                sd[p + "mlp.fc1.bias"] = nrm(H1, s=bias_std) if bias_std else np.zeros(H1, np.float32)
         sd[p + "mlp.fc2.weight"] = nrm(C, Hd)
-        sd[p + "mlp.fc2.bias"] = nrm(C, s=bias_std) if bias_std else np.zeros(C, np.float32)
+        if lin_bias:
+            sd[p + "mlp.fc2.bias"] = nrm(C, s=bias_std) if bias_std else np.zeros(C, np.float32)
         if cfg.layer_scale:
             # a trained DeiT-3 has gammas of order 0.1-1; keep the configured init but jitter it
             # so the LayerScale multiply is observable in parity tests.
@@ -583,21 +655,27 @@ def synth_state_dict(cfg: ViTConfig, seed: int = 0, std: float = 0.02,
             sd[p + "ls2.gamma"] = (np.float32(cfg.layer_scale) + np.abs(nrm(C, s=0.5))).astype(np.float32)
     if not cfg.use_fc_norm:
         sd["norm.weight"] = (1.0 + nrm(C, s=bias_std)).astype(np.float32)
-        sd["norm.bias"] = nrm(C, s=bias_std) if bias_std else np.zeros(C, np.float32)
-    sd["head.weight"] = nrm(cfg.num_classes, C)
-    sd["head.bias"] = nrm(cfg.num_classes, s=bias_std) if bias_std else np.zeros(cfg.num_classes, np.float32)
+        if not rms:
+            sd["norm.bias"] = nrm(C, s=bias_std) if bias_std else np.zeros(C, np.float32)
+    if cfg.num_classes > 0:      # (timm num_classes=0: head is nn.Identity)
+        sd["head.weight"] = nrm(cfg.num_classes, C)
+        sd["head.bias"] = nrm(cfg.num_classes, s=bias_std) if bias_std else np.zeros(cfg.num_classes, np.float32)
 
     # the timm options' tensors are drawn AFTER everything above, so a config without them keeps its stream
     def ln(prefix, n):
         sd[prefix + ".weight"] = (1.0 + nrm(n, s=bias_std)).astype(np.float32)
-        sd[prefix + ".bias"] = nrm(n, s=bias_std) if bias_std else np.zeros(n, np.float32)
+        if affine_bias:
+            sd[prefix + ".bias"] = nrm(n, s=bias_std) if bias_std else np.zeros(n, np.float32)
 
+    affine_bias = not rms
     if cfg.pre_norm:
         ln("norm_pre", C)
-    if cfg.qk_norm:
+    if cfg.qk_norm:      # (q/k-norm stays a LayerNorm whatever cfg.norm says)
+        affine_bias = True
         for i in range(cfg.depth):
             ln(f"blocks.{i}.attn.q_norm", cfg.head_dim)
             ln(f"blocks.{i}.attn.k_norm", cfg.head_dim)
+        affine_bias = not rms
     if cfg.use_fc_norm:
         ln("fc_norm", C)
     if cfg.reg_tokens:      # after every other draw: only pos_embed's row count differs from the register-free config
@@ -617,6 +695,8 @@ def synth_state_dict(cfg: ViTConfig, seed: int = 0, std: float = 0.02,
         sd[p + "mlp.fc1.bias"] = nrm(Hd, s=bias_std) if bias_std else np.zeros(Hd, np.float32)
         sd[p + "mlp.fc2.weight"] = nrm(C, Hd)
         sd[p + "mlp.fc2.bias"] = nrm(C, s=bias_std) if bias_std else np.zeros(C, np.float32)
+    if cfg.embed_norm:      # after every other draw: the norm inside the patch embedding
+        ln("patch_embed.norm", C)
     return sd
 
 

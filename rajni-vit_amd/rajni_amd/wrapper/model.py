@@ -29,6 +29,7 @@ every kernel of the network on the current stream with no host synchronisation.
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import math
 from typing import Dict, List, NamedTuple, Optional
@@ -60,6 +61,7 @@ class PlanInput(NamedTuple):
     gw: int
     qry: object       # rajni_vit_query
     apr: object       # rajni_vit_attn_pool
+    nrm: object = None   # rajni_vit_norm
 
 
 class PlanEntry(NamedTuple):
@@ -76,13 +78,16 @@ class PlanEntry(NamedTuple):
 
 
 # The native entry points, narrowest first: each takes the records of the one in front of it and one more, and a call goes
-# through the one that takes the widest record it has - a pool record: _pool, else a query record: _query, else an image
+# through the one that takes the widest record it has - a norm record: _norm, else a pool record: _pool, else a query record: _query, else an image
 # record: _image, else layers: _layers, else prefix: _ext_prefix, else ext: _ext, else the plain one.  (The symbol is part of
 # the interface: nat.check puts it into the error message.)
 _FORWARDS = ("rajni_vit_forward", "rajni_vit_forward_ext", "rajni_vit_forward_ext_prefix", "rajni_vit_forward_layers",
-             "rajni_vit_forward_image", "rajni_vit_forward_query", "rajni_vit_forward_pool")     # (ext, pre, lay, img, qry, apr)
+             "rajni_vit_forward_image", "rajni_vit_forward_query", "rajni_vit_forward_pool",
+             "rajni_vit_forward_norm")                                                      # (ext, pre, lay, img, qry, apr, nrm)
 _SIZES = ("rajni_vit_workspace_bytes", "rajni_vit_workspace_bytes_prefix", "rajni_vit_workspace_bytes_image",
-          "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_pool")                   # (pre, img, qry, apr)
+          "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_pool",
+          "rajni_vit_workspace_bytes_norm")                                                 # (pre, img, qry, apr, nrm)
+NORM_MAX_C = 2048      # the row kernels hold a row in one wave's registers: C <= 64 lanes * 4 chunks * 8 elements
 
 
 def _native_call(symbols, *records):
@@ -270,6 +275,41 @@ def classify_mlp_act(act: Optional[nn.Module]) -> str:
     name = type(act).__name__ + ("(approximate=%r)" % act.approximate if isinstance(act, nn.GELU) else "")
     raise NotImplementedError(f"mlp.act must be exact-erf nn.GELU (timm default) or QuickGELU, x * sigmoid(1.702 x); "
                               f"{name} computes neither")
+
+
+def classify_norm(mod: Optional[nn.Module], dim: int) -> str:
+    """"layernorm" or "rms": what a norm module over `dim` channels COMPUTES, not what it is called.  An affine `nn.LayerNorm`
+    over (dim,) is "layernorm".  Anything else is "rms" when it has a `weight` of shape [dim], no bias, a float `eps`, and its
+    output on a fixed fp32 probe (a CPU fp32 copy of the module, 4 rows with non-zero means) matches
+    x * rsqrt(mean(x^2) + eps) * weight to 1e-6: `torch.nn.RMSNorm` with an explicit eps, timm's `RmsNorm` and look-alikes pass
+    without being imported, a class of that name that computes something else does not.  `eps=None` is refused - torch resolves
+    it per dtype, so the module has no one eps.  Everything unmatched raises NotImplementedError naming the class."""
+    name = type(mod).__name__
+    if isinstance(mod, nn.LayerNorm):
+        if mod.weight is not None and tuple(mod.normalized_shape) == (dim,):
+            return "layernorm"
+        raise NotImplementedError(f"{name} must be affine (elementwise_affine=True) over the {dim} channels")
+    weight = getattr(mod, "weight", None)
+    if isinstance(mod, nn.Module) and isinstance(weight, torch.Tensor) and tuple(weight.shape) == (dim,) \
+            and getattr(mod, "bias", None) is None:
+        eps = getattr(mod, "eps", None)
+        if eps is None:
+            raise NotImplementedError(f"{name} has eps=None, which torch resolves per dtype: give the module an explicit eps")
+        if isinstance(eps, float):
+            g = torch.Generator().manual_seed(0)
+            x = torch.randn(4, dim, generator=g, dtype=torch.float32) * 1.5 + torch.tensor([[0.0], [0.5], [-1.0], [2.0]])
+            try:
+                with torch.no_grad():
+                    probe = copy.deepcopy(mod).to(device="cpu", dtype=torch.float32)
+                    got = probe(x.clone())
+                    want = x * torch.rsqrt(x.pow(2).mean(dim=-1, keepdim=True) + eps) * probe.weight
+            except Exception:
+                got = None
+            if (isinstance(got, torch.Tensor) and got.shape == x.shape and got.dtype == torch.float32
+                    and float((got - want).abs().max()) <= 1e-6 * max(1.0, float(want.abs().max()))):
+                return "rms"
+    raise NotImplementedError(f"a norm layer must be an affine nn.LayerNorm or an RMSNorm, x * rsqrt(mean(x^2) + eps) * weight "
+                              f"without a bias; {name} computes neither")
 
 
 def _is_silu(act) -> bool:
@@ -558,6 +598,9 @@ class RAJNIViTWrapper(nn.Module):
         if fmt == "fp8_mfma" and getattr(self.m, "global_pool", "token") == "map":
             raise NotImplementedError('set_weight_format("fp8_mfma"): not supported on a model with an attention pool '
                                       '(global_pool=\'map\'); "fp8" weights work')
+        if fmt == "fp8_mfma" and self._norm_feature_or_none():
+            raise NotImplementedError(f'set_weight_format("fp8_mfma"): not supported on a model with {self._norm_feature_or_none()}: '
+                                      'the e4m3-output norm kernels are LayerNorm only ("fp8" weights work)')
         if fmt == "fp8_mfma" and self._mlp_act_or_none() == "quick_gelu":
             raise NotImplementedError('set_weight_format("fp8_mfma"): the model\'s MLPs use QuickGELU; the fp8 x fp8 FC1 epilogue '
                                       'and its hidden-activation bound are exact GELU only ("fp8" weights work)')
@@ -655,6 +698,18 @@ class RAJNIViTWrapper(nn.Module):
             return None
         return kinds.pop() if len(kinds) == 1 else None
 
+    def _norm_feature_or_none(self) -> Optional[str]:
+        """"RMSNorm" / "patch_embed.norm" where the model needs the norm record (rajni_vit_norm), else None (`_describe` reports
+        what is wrong with a norm it does not recognise)"""
+        pe_norm = getattr(self.m.patch_embed, "norm", None)
+        try:
+            dim = self.m.pos_embed.shape[-1]
+            if classify_norm(self.blocks[0].norm1, dim) == "rms":
+                return "RMSNorm"
+        except (NotImplementedError, AttributeError):
+            pass
+        return "patch_embed.norm" if pe_norm is not None and not isinstance(pe_norm, nn.Identity) else None
+
     def check_supported(self) -> Dict:
         """Raise NotImplementedError if the base model has a feature the native forward does not compute (host only, no
         device needed; `forward` runs the same check).  Returns the model description."""
@@ -667,8 +722,7 @@ class RAJNIViTWrapper(nn.Module):
         if not isinstance(pe, nn.Conv2d) or pe.kernel_size != pe.stride or pe.kernel_size[0] != pe.kernel_size[1]:
             raise NotImplementedError("RAJNIViTWrapper: patch_embed.proj must be a square Conv2d with stride == kernel")
         pe_norm = getattr(m.patch_embed, "norm", None)
-        if pe_norm is not None and not isinstance(pe_norm, nn.Identity):
-            raise NotImplementedError("RAJNIViTWrapper: patch_embed.norm is not supported")
+        pe_norm = None if isinstance(pe_norm, nn.Identity) else pe_norm
         # timm num_classes=0 (the DINOv2 checkpoints, any backbone use): head is nn.Identity and forward returns the pooled feature
         headless = isinstance(m.head, nn.Identity)
         if not headless and not isinstance(m.head, nn.Linear):
@@ -684,15 +738,49 @@ class RAJNIViTWrapper(nn.Module):
             raise NotImplementedError('weight format "fp8_mfma" on a model without a class token is not supported; "fp8" weights work')
         Cdim = m.cls_token.shape[-1] if has_cls else m.pos_embed.shape[-1]
         heads = blk0.attn.num_heads
+        try:      # (before anything reads its eps: an unrecognised norm is refused as that)
+            classify_norm(blk0.norm1, Cdim)
+        except NotImplementedError as e:
+            raise NotImplementedError(f"RAJNIViTWrapper: blocks.0.norm1: {e}") from None
         # FC2's K and the hidden buffer's width: of a gated MLP (SwiGLU) too, whose FC1 has twice as many rows
         desc = dict(C=Cdim, H=heads, D=Cdim // heads, depth=len(self.blocks), hidden=blk0.mlp.fc2.in_features,
                     num_classes=0 if headless else m.head.out_features, patch=pe.kernel_size[0], in_chans=pe.in_channels,
                     ln_eps=float(blk0.norm1.eps), scale=float(blk0.attn.scale), headless=headless)
         desc["hidden_pad"] = (desc["hidden"] + 63) // 64 * 64
+
+        # ONE norm kind per model (rajni_vit_norm.kind): norm1, norm2, norm, fc_norm, norm_pre and patch_embed.norm are all
+        # affine LayerNorms or all RMSNorms; blocks.0.norm1 says which, and every other one is held to it by name
+        def kind_of(mod, name):
+            try:
+                return classify_norm(mod, Cdim)
+            except NotImplementedError as e:
+                raise NotImplementedError(f"RAJNIViTWrapper: {name}: {e}") from None
+
+        desc["norm_kind"] = kind_of(blk0.norm1, "blocks.0.norm1")
+
+        def same_kind(mod, name):
+            kind = kind_of(mod, name)
+            if kind != desc["norm_kind"]:
+                raise NotImplementedError(f"RAJNIViTWrapper: {name} is {kind} but blocks.0.norm1 is {desc['norm_kind']}: mixed "
+                                          f"norm kinds in one model are not supported")
+
+        desc["embed_norm"] = pe_norm is not None
+        if pe_norm is not None:
+            same_kind(pe_norm, "patch_embed.norm")
+            desc["embed_norm_eps"] = float(pe_norm.eps)
+        feature = "RMSNorm" if desc["norm_kind"] == "rms" else ("patch_embed.norm" if pe_norm is not None else None)
+        if feature and Cdim > NORM_MAX_C:
+            raise NotImplementedError(f"RAJNIViTWrapper: {feature} on an embed dim of {Cdim}: the row kernels hold a row in one "
+                                      f"wave's registers and take C <= {NORM_MAX_C}")
+        if feature and self._weight_format == "fp8_mfma":
+            raise NotImplementedError(f'weight format "fp8_mfma" on a model with {feature} is not supported: the e4m3-output norm '
+                                      f'kernels are LayerNorm only; "fp8" weights work')
         for i, blk in enumerate(self.blocks):
-            for ln in (blk.norm1, blk.norm2):
-                if not isinstance(ln, nn.LayerNorm) or ln.weight is None or float(ln.eps) != desc["ln_eps"]:
-                    raise NotImplementedError(f"block {i}: norm layers must be affine nn.LayerNorm with one eps")
+            for nm, ln in (("norm1", blk.norm1), ("norm2", blk.norm2)):
+                same_kind(ln, f"blocks.{i}.{nm}")
+                if float(ln.eps) != desc["ln_eps"]:
+                    raise NotImplementedError(f"RAJNIViTWrapper: blocks.{i}.{nm} has eps {float(ln.eps)} but blocks.0.norm1 has "
+                                              f"{desc['ln_eps']}: the block norms and the final norm share one eps")
             try:
                 form = gated_mlp_form(blk.mlp)
                 kind = "swiglu" if form else classify_mlp_act(getattr(blk.mlp, "act", None))
@@ -718,6 +806,9 @@ class RAJNIViTWrapper(nn.Module):
         # the attention pool of global_pool='map' (None for every other head): its heads, its MLP's width and activation
         ap = attn_pool_module(m)
         if ap is not None:
+            if feature:
+                raise NotImplementedError(f"RAJNIViTWrapper: global_pool='map' on a model with {feature} is not supported: the "
+                                          f"attention-pool tail's norms are LayerNorm only")
             if self._cls_only_last:
                 raise ValueError("global_pool='map' with set_last_block_cls_only(True): that opt-in never forms the rows the "
                                  "attention pool reads")
@@ -741,10 +832,13 @@ class RAJNIViTWrapper(nn.Module):
         fc_norm = getattr(m, "fc_norm", None)
         desc["fc_norm"] = fc_norm is not None and not isinstance(fc_norm, nn.Identity)
         desc["norm"] = not isinstance(m.norm, nn.Identity)
-        if desc["norm"] and (not isinstance(m.norm, nn.LayerNorm) or m.norm.weight is None or float(m.norm.eps) != desc["ln_eps"]):
-            raise NotImplementedError("RAJNIViTWrapper: base_model.norm must be nn.LayerNorm with the blocks' eps")
+        if desc["norm"]:
+            same_kind(m.norm, "norm")
+            if float(m.norm.eps) != desc["ln_eps"]:
+                raise NotImplementedError(f"RAJNIViTWrapper: base_model.norm has eps {float(m.norm.eps)} but the blocks' norms "
+                                          f"have {desc['ln_eps']}: the block norms and the final norm share one eps")
         if not desc["norm"] and not desc["fc_norm"]:
-            raise NotImplementedError("RAJNIViTWrapper: base_model.norm must be nn.LayerNorm with the blocks' eps "
+            raise NotImplementedError("RAJNIViTWrapper: base_model.norm must be a norm layer with the blocks' eps "
                                       "(nn.Identity only together with an fc_norm)")
         if desc["pool"] == "map" and not desc["norm"]:
             raise NotImplementedError("RAJNIViTWrapper: global_pool='map' on a model whose norm is nn.Identity (timm fc_norm=True "
@@ -753,13 +847,15 @@ class RAJNIViTWrapper(nn.Module):
         norm_pre = getattr(m, "norm_pre", None)
         desc["norm_pre"] = norm_pre is not None and not isinstance(norm_pre, nn.Identity)
         for name, mod, on in (("fc_norm", fc_norm, desc["fc_norm"]), ("norm_pre", norm_pre, desc["norm_pre"])):
-            if on and (not isinstance(mod, nn.LayerNorm) or mod.weight is None or tuple(mod.normalized_shape) != (Cdim,)):
-                raise NotImplementedError(f"RAJNIViTWrapper: base_model.{name} must be an affine nn.LayerNorm over the embed dim")
+            if on:
+                same_kind(mod, name)
         if desc["pool"] == "avg" and self._cls_only_last:
             raise ValueError("global_pool='avg' with set_last_block_cls_only(True): that opt-in never forms the rows to be averaged")
         # plans that need none of these keep calling rajni_vit_forward
         desc["ext"] = (desc["qk_norm"] or desc["norm_pre"] or desc["fc_norm"] or not desc["norm"] or desc["pool"] != "token"
                        or desc["mlp_act"] != "gelu")
+        # ... and plans that need no norm record keep the entry point they had
+        desc["norm_record"] = feature is not None
         return desc
 
     def _all_params(self):
@@ -833,12 +929,16 @@ class RAJNIViTWrapper(nn.Module):
         W["reg"] = (reg_src.detach().to(device=device, dtype=dtype).reshape(-1, desc["C"]).contiguous()
                     if reg_src is not None else None)
         W["pos"] = m.pos_embed.detach().to(device=device, dtype=dtype).reshape(-1, desc["C"]).contiguous()
-        W["norm_w"], W["norm_b"] = (pv(m.norm.weight), pv(m.norm.bias)) if desc["norm"] else (None, None)
-        if desc["norm"] and W["norm_b"] is None:
+        rms = desc["norm_kind"] == "rms"      # no bias vector is packed or passed: the RMS kernels read none
+        nb = lambda mod: None if rms else pv(getattr(mod, "bias", None))
+        W["norm_w"], W["norm_b"] = (pv(m.norm.weight), nb(m.norm)) if desc["norm"] else (None, None)
+        if desc["norm"] and W["norm_b"] is None and not rms:
             W["norm_b"] = zeros(desc["C"])
+        pe_norm = m.patch_embed.norm if desc["embed_norm"] else None
+        W["embed_norm_w"], W["embed_norm_b"] = (pv(pe_norm.weight), nb(pe_norm)) if pe_norm is not None else (None, None)
         for name in ("norm_pre", "fc_norm"):      # rajni_vit_ext (a missing bias stays None = 0)
             mod = getattr(m, name, None) if desc[name] else None
-            W[name + "_w"], W[name + "_b"] = (pv(mod.weight), pv(mod.bias)) if mod is not None else (None, None)
+            W[name + "_w"], W[name + "_b"] = (pv(mod.weight), nb(mod)) if mod is not None else (None, None)
             W[name + "_eps"] = float(mod.eps) if mod is not None else 0.0
         if desc["headless"]:
             W["head_w"] = W["head_b"] = None      # rajni_vit_plan: head_w NULL and num_classes 0, no head GEMM
@@ -914,10 +1014,10 @@ class RAJNIViTWrapper(nn.Module):
                 if hpad != hid:
                     fc1_b = torch.cat([fc1_b, zeros(hpad - hid)])
             blocks.append(dict(
-                norm1_w=pv(blk.norm1.weight), norm1_b=pv(blk.norm1.bias),
+                norm1_w=pv(blk.norm1.weight), norm1_b=nb(blk.norm1),
                 qkv_w=qkv_w, qkv_s=qkv_s, qkv_b=pv(a.qkv.bias) if a.qkv.bias is not None else zeros(3 * desc["C"]),
                 proj_w=proj_w, proj_s=proj_s, proj_b=pv(a.proj.bias) if a.proj.bias is not None else zeros(desc["C"]),
-                ls1=g1, norm2_w=pv(blk.norm2.weight), norm2_b=pv(blk.norm2.bias),
+                ls1=g1, norm2_w=pv(blk.norm2.weight), norm2_b=nb(blk.norm2),
                 fc1_w=fc1_w, fc1_s=fc1_s, fc1_b=fc1_b,
                 fc2_w=fc2_w, fc2_s=fc2_s, fc2_b=pv(blk.mlp.fc2.bias), ls2=g2))
             if desc["qk_norm"]:
@@ -1065,12 +1165,19 @@ class RAJNIViTWrapper(nn.Module):
                 setattr(apr, name, nat.ptr(pw_[name]))
             apr.norm_eps, apr.hidden, apr.heads = pd["eps"], pd["hidden_pad"], pd["heads"]
             apr.act = nat.MLP_QUICK_GELU if pd["act"] == "quick_gelu" else nat.MLP_GELU
-        symbol, records = _native_call(_SIZES, pre, img, qry, apr)
+        nrm = None
+        if d["norm_record"]:      # the norm record beside the plan (rajni_vit_norm); None: LayerNorm everywhere, the entry points as ever
+            nrm = nat.VitNorm()
+            nrm.kind = nat.NORM_RMS if d["norm_kind"] == "rms" else nat.NORM_LAYERNORM
+            if d["embed_norm"]:
+                nrm.embed_norm_w, nrm.embed_norm_b = nat.ptr(W["embed_norm_w"]), nat.ptr(W["embed_norm_b"])
+                nrm.embed_norm_eps = d["embed_norm_eps"]
+        symbol, records = _native_call(_SIZES, pre, img, qry, apr, nrm)
         nbytes = getattr(nat.lib(), symbol)(C.byref(plan), *records)
         if nbytes == 0 and symbol not in _SIZES[:2]:
-            # the image, query or pool record is refused: say why (the forward's own refusal; nothing is launched)
+            # the image, query, pool or norm record is refused: say why (the forward's own refusal; nothing is launched)
             dry = nat.VitExt(pool=nat.POOL_MAP) if apr is not None else None
-            forward, records = _native_call(_FORWARDS, dry, pre, None, img, qry, apr)
+            forward, records = _native_call(_FORWARDS, dry, pre, None, img, qry, apr, nrm)
             nat.check(getattr(nat.lib(), forward)(C.byref(plan), *records, 16, 16, None), forward)
             raise nat.NativeError(f"{symbol} refused the plan")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
@@ -1103,7 +1210,7 @@ class RAJNIViTWrapper(nn.Module):
             cap_arr = (C.c_int * len(caps))(*caps)
             layers = (cap_arr, int(lnorm), int(lfill == "last"), (len(caps), B, n0, d["C"]))
         self._plan = PlanEntry(key, plan, PlanRefs(blocks, tc, ws, W, ext, qk, pre), bufs, counts, full_mode, out_shape, layers,
-                               PlanInput(img, pos, gh, gw, qry, apr))
+                               PlanInput(img, pos, gh, gw, qry, apr, nrm))
         if len(self._plans) >= 4:     # workspaces are large: keep only a few batch shapes alive
             self._plans.pop(next(iter(self._plans)))
         self._plans[key] = self._plan
@@ -1123,6 +1230,9 @@ class RAJNIViTWrapper(nn.Module):
 
     def _check_layers(self, d, caps, norm):
         """what forward_intermediates does not compute"""
+        if norm and self._norm_feature_or_none() == "RMSNorm":
+            raise NotImplementedError("forward_intermediates(norm=True): the model's norms are RMSNorm and the normalised slabs "
+                                      "are LayerNorm only; norm=False returns the un-normalised states")
         if norm and not d["norm"]:
             raise NotImplementedError("forward_intermediates(norm=True): base_model.norm is nn.Identity (the fc_norm models); "
                                       "norm=False returns the un-normalised states")
@@ -1264,7 +1374,7 @@ class RAJNIViTWrapper(nn.Module):
                     lay = nat.VitLayers()
                     lay.n, lay.blocks, lay.norm, lay.fill, lay.out, lay.slab_stride = len(cap_arr), cap_arr, lnorm, lfill, slabs.data_ptr(), 0
                 symbol, records = _native_call(_FORWARDS, entry.refs.ext, entry.refs.pre, lay, entry.input.img, entry.input.qry,
-                                               entry.input.apr)
+                                               entry.input.apr, entry.input.nrm)
                 nat.check(getattr(nat.lib(), symbol)(C.byref(entry.plan), *records, x.data_ptr(), out.data_ptr(),
                                                      nat.stream_ptr(x.device)), symbol)
                 return out if lay is None else (out, slabs)
