@@ -10,6 +10,7 @@
 #include "../../include/rajni_hip_query.h"
 #include "../../include/rajni_hip_attnpool.h"
 #include "../../include/rajni_hip_norm.h"
+#include "../../include/rajni_hip_rope.h"
 
 typedef unsigned short bf16_t;  // raw bf16 bits in memory
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -271,6 +272,10 @@ int launch_pool_norm(const void* x, int B, int N, int C, int pool, const float* 
 // patch_embed.norm (rajni_hip_norm.h): the patch rows of the stream x [B, N, C] normalised in place, + pos[pos_off + j]
 int launch_embed_norm(int kind, void* x, const float* w, const float* b, const void* pos, int pos_off, int B, int N, int num_prefix,
                       int C, float eps, int dtype, int x_f32, hipStream_t s);
+// rope.hip (rajni_hip_rope.h): q and k of qkv [B * N, 3, H, D] rotated in place by the row of cos / sin [rows, D] that
+// src [B, N] (NULL: the row index) names for each patch token; head_stride 0 = one table for all heads
+int launch_rope_qk(void* qkv, const int32_t* src, const float* cost, const float* sint, long head_stride, int B, int N, int num_prefix,
+                   int H, int D, int layout, int dtype, hipStream_t s);
 // image.hip: position-embedding rows [prefix + sh * sw, C] -> [prefix + dh * dw, C], bicubic with antialiasing (timm's
 // resample_abs_pos_embed); prefix rows copied
 int launch_resample_pos_embed(const void* src, int sh, int sw, void* dst, int dh, int dw, int C, int prefix, int dtype, hipStream_t s);

@@ -2,7 +2,7 @@
 // that enqueues every kernel on the caller's stream.  Token counts are data independent,
 // so all shapes are known up front: no allocation, no host sync, no device->host traffic inside.
 //
-// A call is a plan and up to seven optional records.  make_spec resolves them once into a Spec, and everything below takes that
+// A call is a plan and up to eight optional records.  make_spec resolves them once into a Spec, and everything below takes that
 // Spec: check_all (every refusal, before the first launch), carve (the workspace), the block loop and the tails.
 //
 // Per block:  LN1 -> QKV GEMM (all N tokens) -> an attention form -> the tail (launch_tail):
@@ -34,7 +34,9 @@
 // query of the scoring blocks and whether there is a class row; without one P counts the registers alone and the last block
 // runs every row.  pool - the attention-pool tail and its B fp32 rows, carved behind everything else.  norm - with kind RMS every
 // norm launch is the RMS form of the same kernel; with an embedding norm the patch GEMM adds a zeroed position table and
-// launch_embed_norm follows it (rajni_hip_norm.h).
+// launch_embed_norm follows it (rajni_hip_norm.h).  rope - every block rotates q and k in place behind q/k-norm, in front of
+// everything that reads w.qkv, by the table row of each token's place in the image; behind a scheduled block that place comes
+// from the composed selections in w.rsrc (rajni_hip_rope.h).
 #include "common.h"
 
 #include <vector>
@@ -53,6 +55,7 @@ struct Workspace {
   // kernel's output, py [B, C] proj's output and the MLP's residual stream (FC2 adds in place), pn [B, C] the pool LayerNorm's
   // rows, phid [B, pool.hidden] - all fp32 whatever the plan's dtype: the B-row part of the tail runs in fp32
   char *po, *py, *pn, *phid;
+  int32_t* rsrc;           // a rope record: [B, n0] = where each token of the stream sat in the unpruned sequence (w.qkv is live there)
   size_t total, cols_bytes;
 };
 
@@ -68,6 +71,7 @@ struct Spec {
   const rajni_vit_norm* nrm;        // all zero arrives here as NULL
   int kind;                         // every norm of the forward but q/k-norm: RAJNI_NORM_LAYERNORM without the record
   bool rms, embed_norm;             // kind == RAJNI_NORM_RMS; the record carries a patch_embed.norm
+  const rajni_vit_rope* rop;        // all zero arrives here as NULL
   hipStream_t s;
   bool nocls;                       // no class row: the prefix tokens are the registers alone
   int qmode;                        // the importance query of the scoring blocks
@@ -87,18 +91,21 @@ enum { ENTRY_FORWARD = 0, ENTRY_SIZE = 1 };
 
 Spec make_spec(int family, const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre,
                const rajni_vit_layers* lay, const rajni_vit_image* img, const rajni_vit_query* qry, const rajni_vit_attn_pool* ap,
-               hipStream_t s, const rajni_vit_norm* nrm = nullptr) {
+               hipStream_t s, const rajni_vit_norm* nrm = nullptr, const rajni_vit_rope* rop = nullptr) {
   // a NULL trailing record makes a call the next-narrower entry point's, by name too (the size of a pool record is the query
   // size function's plus the pool rows, and there is no size function for a layers record)
-  static const char* const names[2][6] = {
+  static const char* const names[2][7] = {
       {"rajni_vit_forward_ext_prefix", "rajni_vit_forward_layers", "rajni_vit_forward_image", "rajni_vit_forward_query",
-       "rajni_vit_forward_pool", "rajni_vit_forward_norm"},
+       "rajni_vit_forward_pool", "rajni_vit_forward_norm", "rajni_vit_forward_rope"},
       {"rajni_vit_workspace_bytes_prefix", "rajni_vit_workspace_bytes_prefix", "rajni_vit_workspace_bytes_image",
-       "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_norm"}};
+       "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_norm",
+       "rajni_vit_workspace_bytes_rope"}};
   if (qry && qry->class_token == 1 && qry->query == RAJNI_QUERY_CLS) qry = nullptr;
   if (nrm && nrm->kind == RAJNI_NORM_LAYERNORM && !nrm->embed_norm_w) nrm = nullptr;   // what NULL means
+  if (rop && !rop->cos && !rop->sin && !rop->head_stride && !rop->block_stride && !rop->rows && !rop->layout) rop = nullptr;
   Spec c{};
-  c.who = names[family][nrm ? 5 : (ap && family == ENTRY_FORWARD) ? 4 : qry ? 3 : img ? 2 : lay ? 1 : 0];
+  c.rop = rop;
+  c.who = names[family][rop ? 6 : nrm ? 5 : (ap && family == ENTRY_FORWARD) ? 4 : qry ? 3 : img ? 2 : lay ? 1 : 0];
   c.p = plan; c.ext = ext; c.pre = pre; c.lay = lay; c.img = img; c.qry = qry; c.ap = ap; c.nrm = nrm; c.s = s;
   c.kind = nrm ? nrm->kind : RAJNI_NORM_LAYERNORM;
   c.rms = c.kind == RAJNI_NORM_RMS;
@@ -150,6 +157,7 @@ Workspace carve(const Spec& c) {
   const size_t oidx = take(HR == 2 ? (size_t)p.B * 2 * sizeof(int32_t) : 0);   // behind the rest: nothing above moves
   const size_t prow = c.ap ? (size_t)p.B * p.C * sizeof(float) : 0;            // the pool rows likewise
   const size_t opo = take(prow), opy = take(prow), opn = take(prow), oph = take(c.ap ? (size_t)p.B * c.ap->hidden * sizeof(float) : 0);
+  const size_t orsrc = take(c.rop ? rows * sizeof(int32_t) : 0);               // and the rope record's source map
   char* base = (char*)p.workspace;
   w.xa = base + oxa; w.xb = base + oxb; w.xn = base + oxn; w.qkv = base + oqkv; w.att = base + oatt;
   w.hid = base + ohid; w.clsn = base + ocls; w.scf = base + oscf; w.cols = base + ocols;
@@ -157,6 +165,7 @@ Workspace carve(const Spec& c) {
   w.idx01 = HR == 2 ? reinterpret_cast<int32_t*>(base + oidx) : nullptr;
   w.xs = reinterpret_cast<float*>(base + oxs); w.hs = reinterpret_cast<float*>(base + ohs);
   w.po = base + opo; w.py = base + opy; w.pn = base + opn; w.phid = base + oph;
+  w.rsrc = c.rop ? reinterpret_cast<int32_t*>(base + orsrc) : nullptr;
   w.total = off;
   return w;
 }
@@ -515,6 +524,31 @@ int check_norm(const Spec& c) {
   return RAJNI_OK;
 }
 
+// the rope record against the plan and the grid (rajni_hip_rope.h): host-side integer tests, every refusal names the combination
+int check_rope(const Spec& c) {
+  const char* who = c.who;          // (a rope record is the widest there is: the rope entry point of the call's family)
+  const rajni_vit_plan& p = *c.p;
+  const rajni_vit_rope& r = *c.rop;
+  RAJNI_REQUIRE(r.layout == RAJNI_ROPE_INTERLEAVED || r.layout == RAJNI_ROPE_HALF, RAJNI_ERR_INVALID,
+                "%s: rope.layout must be RAJNI_ROPE_INTERLEAVED or RAJNI_ROPE_HALF (%d)", who, r.layout);
+  RAJNI_REQUIRE(r.cos && r.sin, RAJNI_ERR_INVALID, "%s: null pointer (rope.%s) with a non-zero rope record", who, r.cos ? "sin" : "cos");
+  RAJNI_REQUIRE(p.patch_size > 0 && p.H > 0 && p.D > 0, RAJNI_ERR_INVALID, "%s: bad plan", who);
+  RAJNI_REQUIRE(r.rows == c.n0 - c.P, RAJNI_ERR_INVALID,
+                "%s: rope.rows must equal the patches of the grid, n0 - P = %d (%d): one table row per patch", who, c.n0 - c.P, r.rows);
+  const long long table = (long long)r.rows * p.D;
+  RAJNI_REQUIRE(r.head_stride == 0 || r.head_stride == table, RAJNI_ERR_INVALID,
+                "%s: rope.head_stride must be 0 (one table for all heads) or rows * D = %lld (%lld)", who, table, r.head_stride);
+  const long long per_block = (r.head_stride ? p.H : 1) * table;
+  RAJNI_REQUIRE(r.block_stride == 0 || r.block_stride == per_block, RAJNI_ERR_INVALID,
+                "%s: rope.block_stride must be 0 (one table for all blocks) or (head_stride ? H : 1) * rows * D = %lld (%lld)", who,
+                per_block, r.block_stride);
+  RAJNI_REQUIRE(!p.act_fp8, RAJNI_ERR_UNSUPPORTED,
+                "%s: RoPE (a rope record) is unsupported with plan.act_fp8 - the e4m3 attention and its bounds were fitted to "
+                "unrotated q and k", who);
+  RAJNI_REQUIRE_PLACED("rajni_vit_forward_rope: rope", {"cos", r.cos, 16}, {"sin", r.sin, 16});
+  return RAJNI_OK;
+}
+
 // the token walk (model.py:43,50): a scheduled block leaves its kept patch tokens and the P prefix tokens ...
 inline int tokens_after(const rajni_block& blk, int N, int P) { return blk.keep > 0 ? blk.keep + P : N; }
 // ... so this many enter block i
@@ -669,7 +703,8 @@ int launch_source_idx_before(const Spec& c, int upto, int32_t* src, int Nf) {
 
 // Every refusal of the forward, before the first launch.  The order is part of the contract - callers match the first message:
 // the prefix record under the entry point's name; null pointers; the query record (whether there is a class row decides every
-// count); the pool record; the norm record; the image record (every count below is against its grid); the layers record; then the plan, the
+// count); the pool record; the norm record; the image record (every count below is against its grid); the rope record; the layers
+// record; then the plan, the
 // placement of what it points to, the ext record, the distilled head, the schedule, and last the workspace, carved here.
 int check_all(Spec& c, const void* images, const void* logits) {
   int rc = check_prefix(c);
@@ -680,6 +715,7 @@ int check_all(Spec& c, const void* images, const void* logits) {
   if (c.ap && (rc = check_pool(c)) != RAJNI_OK) return rc;
   if (c.nrm && (rc = check_norm(c)) != RAJNI_OK) return rc;
   if (c.img && (rc = check_image(c)) != RAJNI_OK) return rc;
+  if (c.rop && (rc = check_rope(c)) != RAJNI_OK) return rc;
   if (c.lay && (rc = check_layers(c)) != RAJNI_OK) return rc;
   if (c.dense_last && (rc = check_dense_last(c)) != RAJNI_OK) return rc;
   if ((rc = check_plan(c)) != RAJNI_OK) return rc;
@@ -702,6 +738,7 @@ size_t workspace_bytes(const Spec& c) {
   if (check_prefix(c) != RAJNI_OK || (c.img && check_image(c) != RAJNI_OK)) return 0;
   if (c.ap && (!pool_hidden_ok(*c.ap) || c.p->B <= 0 || c.p->C <= 0)) return 0;
   if (c.nrm && check_norm(c) != RAJNI_OK) return 0;
+  if (c.rop && check_rope(c) != RAJNI_OK) return 0;
   return carve(c).total;
 }
 
@@ -757,6 +794,9 @@ int vit_forward(Spec f, const void* images, void* logits) {
   char* cur = w.xa;
   char* oth = w.xb;
   const void* carried = nullptr;  // scores of the tokens currently in `cur` (model.py:39,53,63)
+  // the rope record: w.rsrc names the place of every token of `cur` in the unpruned sequence once a scheduled block has run
+  // (before that the place is the row index and the kernel gets no map); stale whenever a selection has changed the token set
+  bool rope_mapped = false, rope_stale = false;
 
   for (int i = 0; i < p.depth; ++i) {
     const rajni_block& blk = p.blocks[i];
@@ -768,6 +808,16 @@ int vit_forward(Spec f, const void* images, void* logits) {
     if (rc != RAJNI_OK) return rc;
     if (const rajni_qk_affine* qkn = f.qk_norm) {   // timm Attention.forward: q, k = q_norm(q), k_norm(k) - in place, so everything below reads normalised q and k
       rc = launch_qk_norm(w.qkv, qkn[i].q_norm_w, qkn[i].q_norm_b, qkn[i].k_norm_w, qkn[i].k_norm_b, M, p.H, p.D, ext->qk_eps, dt, s);
+      if (rc != RAJNI_OK) return rc;
+    }
+    if (const rajni_vit_rope* rp = f.rop) {   // behind q/k-norm, in front of scoring, the last-block forms and attention
+      if (rope_stale) {
+        rc = launch_source_idx_before(f, i, w.rsrc, N);
+        if (rc != RAJNI_OK) return rc;
+        rope_stale = false; rope_mapped = true;
+      }
+      rc = launch_rope_qk(w.qkv, rope_mapped ? w.rsrc : nullptr, rp->cos + (size_t)i * rp->block_stride, rp->sin + (size_t)i * rp->block_stride,
+                          (long)rp->head_stride, B, N, P, p.H, p.D, rp->layout, dt, s);
       if (rc != RAJNI_OK) return rc;
     }
 
@@ -879,7 +929,7 @@ int vit_forward(Spec f, const void* images, void* logits) {
         if (rc != RAJNI_OK) return rc;
       }
     }
-    if (idx) { oth = cur; cur = y; }
+    if (idx) { oth = cur; cur = y; rope_stale = true; }
     N = Np;
     if (lay && cap < lay->n && lay->blocks[cap] == i) {
       // a captured block: the stream behind it, scattered to slab `cap` through the map of the selections up to and including
@@ -973,6 +1023,12 @@ extern "C" int rajni_vit_forward_norm(const rajni_vit_plan* plan, const rajni_vi
                                       rajni_stream_t stream) {
   return vit_forward(make_spec(ENTRY_FORWARD, plan, ext, prefix, layers, image, query, pool, (hipStream_t)stream, norm), images, logits);
 }
+extern "C" int rajni_vit_forward_rope(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
+                                      const rajni_vit_layers* layers, const rajni_vit_image* image, const rajni_vit_query* query,
+                                      const rajni_vit_attn_pool* pool, const rajni_vit_norm* norm, const rajni_vit_rope* rope,
+                                      const void* images, void* logits, rajni_stream_t stream) {
+  return vit_forward(make_spec(ENTRY_FORWARD, plan, ext, prefix, layers, image, query, pool, (hipStream_t)stream, norm, rope), images, logits);
+}
 extern "C" size_t rajni_vit_workspace_bytes(const rajni_vit_plan* plan) {
   return workspace_bytes(make_spec(ENTRY_SIZE, plan, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
 }
@@ -994,6 +1050,12 @@ extern "C" size_t rajni_vit_workspace_bytes_pool(const rajni_vit_plan* plan, con
 extern "C" size_t rajni_vit_workspace_bytes_norm(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix, const rajni_vit_image* image,
                                                  const rajni_vit_query* query, const rajni_vit_attn_pool* pool, const rajni_vit_norm* norm) {
   return workspace_bytes(make_spec(ENTRY_SIZE, plan, nullptr, prefix, nullptr, image, query, pool, nullptr, norm));
+}
+
+extern "C" size_t rajni_vit_workspace_bytes_rope(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix, const rajni_vit_image* image,
+                                                 const rajni_vit_query* query, const rajni_vit_attn_pool* pool, const rajni_vit_norm* norm,
+                                                 const rajni_vit_rope* rope) {
+  return workspace_bytes(make_spec(ENTRY_SIZE, plan, nullptr, prefix, nullptr, image, query, pool, nullptr, norm, rope));
 }
 
 extern "C" void rajni_debug_set_last_block_all_rows(int on) { g_last_block_all_rows = on; }

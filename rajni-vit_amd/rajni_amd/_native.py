@@ -260,6 +260,28 @@ _NORM_SIGS = {
                                        c_void_p, c_void_p, c_void_p]),
 }
 NORM_SYMBOLS = tuple(_NORM_SIGS.keys())
+# include/rajni_hip_rope.h, additive in the same way: rotary position embeddings on the pruned token set
+ROPE_INTERLEAVED, ROPE_HALF = 0, 1   # rajni_vit_rope.layout
+
+
+class VitRope(C.Structure):
+    """rajni_vit_rope (include/rajni_hip_rope.h): fp32 cos / sin tables [rows, D] per patch of the grid, shared or per head
+    (head_stride) and per block (block_stride), and the pairing of the rotation"""
+    _fields_ = [("cos", c_void_p), ("sin", c_void_p), ("head_stride", C.c_longlong), ("block_stride", C.c_longlong),
+                ("rows", c_int), ("layout", c_int)]
+
+
+_ROPE_SIGS = {
+    "rajni_rope_qk": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, C.c_longlong, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                              c_void_p]),
+    "rajni_vit_workspace_bytes_rope": (c_size_t, [C.POINTER(VitPlan), C.POINTER(VitPrefix), C.POINTER(VitImage),
+                                                  C.POINTER(VitQuery), C.POINTER(VitAttnPool), C.POINTER(VitNorm),
+                                                  C.POINTER(VitRope)]),
+    "rajni_vit_forward_rope": (c_int, [C.POINTER(VitPlan), C.POINTER(VitExt), C.POINTER(VitPrefix), C.POINTER(VitLayers),
+                                       C.POINTER(VitImage), C.POINTER(VitQuery), C.POINTER(VitAttnPool), C.POINTER(VitNorm),
+                                       C.POINTER(VitRope), c_void_p, c_void_p, c_void_p]),
+}
+ROPE_SYMBOLS = tuple(_ROPE_SIGS.keys())
 RESAMPLE_MAX_GRID = 128     # RAJNI_RESAMPLE_MAX_GRID: grid cells per axis, source and destination
 ABI_VERSION = 8     # include/rajni_hip.h; bumped whenever a struct or an entry point changes
 _lib: Optional[C.CDLL] = None
@@ -276,7 +298,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
             "(hipcc --offload-arch=gfx950). rajni_amd has no CPU or PyTorch fallback by design.")
     lib = C.CDLL(path)
     for name, (res, args) in (list(_SIGS.items()) + list(_LAYERS_SIGS.items()) + list(_IMAGE_SIGS.items()) + list(_QUERY_SIGS.items())
-                              + list(_ATTNPOOL_SIGS.items()) + list(_NORM_SIGS.items())):
+                              + list(_ATTNPOOL_SIGS.items()) + list(_NORM_SIGS.items()) + list(_ROPE_SIGS.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

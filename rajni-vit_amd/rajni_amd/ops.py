@@ -357,6 +357,45 @@ def qk_norm(qkv: torch.Tensor, num_heads: int, q_w: torch.Tensor, q_b: Optional[
     return qkv
 
 
+def rope_qk(qkv: torch.Tensor, num_heads: int, cos: torch.Tensor, sin: torch.Tensor, num_prefix: int = 1,
+            src: Optional[torch.Tensor] = None, half: bool = False) -> torch.Tensor:
+    """Rotary position embedding of the q and k thirds of qkv [B, N, 3C], IN PLACE (v and the first `num_prefix` rows of every
+    image are not touched; include/rajni_hip_rope.h).  cos / sin: fp32 [rows, D] (one table for all heads) or [H, rows, D],
+    one row per patch of the grid.  Row t >= num_prefix of image b takes table row (src[b, t] if src is given else t) -
+    num_prefix; `src` int32 [B, N] is checked here against the tables' rows (the native entry point does not).  `half`:
+    rotate_half pairs (j, j + D/2) instead of timm rot()'s (2i, 2i + 1).  Returns qkv.  (With `src` the check reads its extremes back:
+    one host synchronisation per call - a stand-alone op's price; the whole forward composes its own map and has none.)"""
+    nat.require_device(qkv, "qkv")
+    if qkv.dim() != 3:
+        raise ValueError(f"rope_qk: qkv must be [B, N, 3C], got {tuple(qkv.shape)}")
+    qkv = _placed(qkv, "qkv", in_place=True)
+    B, N, threeC = qkv.shape
+    if num_heads < 1 or threeC % (3 * num_heads):
+        raise ValueError(f"rope_qk: qkv's last axis ({threeC}) must be 3 * num_heads * head_dim with num_heads = {num_heads}")
+    D = threeC // 3 // num_heads
+    if cos.shape != sin.shape or cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.dim() not in (2, 3) \
+            or cos.shape[-1] != D or (cos.dim() == 3 and cos.shape[0] != num_heads):
+        raise ValueError(f"rope_qk: cos and sin must be fp32 [rows, {D}] or [{num_heads}, rows, {D}] of one shape, got "
+                         f"{tuple(cos.shape)} / {tuple(sin.shape)}")
+    rows = cos.shape[-2]
+    if src is None:
+        if N - num_prefix > rows:
+            raise ValueError(f"rope_qk: {N - num_prefix} patch rows but the tables have {rows}")
+    else:
+        if src.dtype != torch.int32 or tuple(src.shape) != (B, N):
+            raise ValueError(f"rope_qk: src must be int32 [{B}, {N}]")
+        p = src[:, num_prefix:]
+        if p.numel() and (int(p.min()) < num_prefix or int(p.max()) >= num_prefix + rows):
+            raise ValueError(f"rope_qk: src names positions outside the tables' {rows} rows")
+    cos, sin, src = _placed(cos, "cos"), _placed(sin, "sin"), _placed(src, "src", 4)
+    with nat.device_guard(qkv.device):
+        nat.check(nat.lib().rajni_rope_qk(qkv.data_ptr(), nat.ptr(src), cos.data_ptr(), sin.data_ptr(),
+                                          rows * D if cos.dim() == 3 else 0, B, N, num_prefix, num_heads, D,
+                                          nat.ROPE_HALF if half else nat.ROPE_INTERLEAVED, _dt(qkv), nat.stream_ptr(qkv.device)),
+                  "rajni_rope_qk")
+    return qkv
+
+
 def layernorm_stream(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], eps: float,
                      model_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """timm's `x = norm_pre(x)`: LayerNorm over the last axis written back IN PLACE into the residual stream x (fp32, or the

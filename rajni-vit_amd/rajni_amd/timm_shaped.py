@@ -81,8 +81,16 @@ class ViTConfig:
     norm = "layernorm"
     embed_norm = False
     bias = True
+    # ... and what RopeViTConfig makes fields, in the same way
+    rope = "none"
+    rope_half = False
+    abs_pos = True
 
     def __post_init__(self):
+        if self.rope not in ("none", "axial", "mixed"):
+            raise ValueError(f"ViTConfig: rope must be 'none', 'axial' or 'mixed', got {self.rope!r}")
+        if self.rope != "none" and self.head_dim % 4:
+            raise ValueError(f"ViTConfig: rope needs a head dim that is a multiple of 4 (two axes of rotated pairs), got {self.head_dim}")
         if self.norm not in ("layernorm", "rms"):
             raise ValueError(f"ViTConfig: norm must be 'layernorm' or 'rms', got {self.norm!r}")
         if self.distilled and self.reg_tokens:
@@ -127,6 +135,16 @@ class NormViTConfig(ViTConfig):
     embed_norm: bool = False              # timm embed_norm_layer: PatchEmbed.norm of that kind on the projected patch rows,
                                           # in front of the position embedding
     bias: bool = True                     # False: no bias in qkv, proj and the MLP (the patch projection keeps its own)
+
+
+@dataclass(frozen=True)
+class RopeViTConfig(NormViTConfig):
+    """NormViTConfig plus rotary position embeddings (EVA02, timm's vit_*_rope_* line, the Perception Encoder towers, DINOv3).  A
+    subclass for NormViTConfig's reason.  (Keyword only in practice.)"""
+    rope: str = "none"                    # "none"; "axial": one table for all heads and blocks, D / 4 frequency bands per image
+                                          # axis; "mixed": learned per-block, per-head frequencies over both axes (RoPE-Mixed)
+    rope_half: bool = False               # False: the pairs are (2i, 2i + 1) (timm rot()); True: (i, i + D / 2) (rotate_half)
+    abs_pos: bool = True                  # False: no learned absolute position embedding at all (pos_embed is None)
 
 
 # The model names BASELINE.json's configs use.
@@ -326,9 +344,30 @@ NORM_CONFIGS: Dict[str, ViTConfig] = {
 }
 
 
+# Rotary position embeddings, in a table of their own for the same reason.
+_MICRO = dict(img_size=64, embed_dim=128, depth=4, num_heads=2, num_classes=10)
+ROPE_CONFIGS: Dict[str, ViTConfig] = {
+    # micro models (not timm names).  Axial, interleaved pairs, a class token, the absolute embedding kept, head dim 64 (EVA02's
+    # combination); axial, rotate_half, a class token and 4 registers, no absolute embedding, LayerScale (the DINOv3 recipe);
+    # mixed - a table per block and head -, no class token, 'avg' pool; head dim 40 (the half-layout partner straddles a
+    # 16-byte chunk), rotate_half, patch 14
+    "vit_micro_rope_patch16_64": RopeViTConfig(**_MICRO, rope="axial"),
+    "vit_micro_rope_half_reg4_patch16_64": RopeViTConfig(**_MICRO, layer_scale=1e-6, reg_tokens=4, rope="axial", rope_half=True,
+                                                         abs_pos=False),
+    "vit_micro_rope_mixed_gap_patch16_64": RopeViTConfig(**_MICRO, global_pool="avg", class_token=False, rope="mixed"),
+    "vit_micro_rope_d40_patch14_56": RopeViTConfig(img_size=56, patch_size=14, embed_dim=320, depth=4, num_heads=8, num_classes=10,
+                                                   rope="axial", rope_half=True),
+    # ViT-B/16 dimensions for the cost tools (not checkpoint names: EVA02's SwiGLU-with-norm MLP and DINOv3's checkpoints are
+    # out of scope): axial with the absolute embedding, and the DINOv3 recipe
+    "vit_base_patch16_rope_224": RopeViTConfig(embed_dim=768, depth=12, num_heads=12, rope="axial"),
+    "vit_base_patch16_rope_half_reg4_224": RopeViTConfig(embed_dim=768, depth=12, num_heads=12, layer_scale=1e-5, reg_tokens=4,
+                                                         rope="axial", rope_half=True, abs_pos=False),
+}
+
+
 def config_of(name: str) -> ViTConfig:
-    """the built-in config of that name, from CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS, MAP_CONFIGS or NORM_CONFIGS"""
-    tables = (CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS, MAP_CONFIGS, NORM_CONFIGS)
+    """the built-in config of that name, from CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS, MAP_CONFIGS, NORM_CONFIGS or ROPE_CONFIGS"""
+    tables = (CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS, MAP_CONFIGS, NORM_CONFIGS, ROPE_CONFIGS)
     for table in tables:
         if name in table:
             return table[name]
@@ -367,9 +406,65 @@ class PatchEmbed(nn.Module):
         return self.norm(self.proj(x).flatten(2).transpose(1, 2))
 
 
-class Attention(nn.Module):
-    def __init__(self, dim: int, num_heads: int, qk_norm: bool = False, ln_eps: float = 1e-6, bias: bool = True):
+def rot_interleaved(x):
+    """timm rot(): y[2i] = -x[2i + 1], y[2i + 1] = x[2i]"""
+    return torch.stack([-x[..., 1::2], x[..., ::2]], -1).reshape(x.shape)
+
+
+def rot_half(x):
+    """rotate_half: y[j] = -x[j + D/2] for j < D/2, x[j - D/2] otherwise"""
+    h = x.shape[-1] // 2
+    return torch.cat([-x[..., h:], x[..., :h]], -1)
+
+
+def apply_rot_embed_cat(x, emb, half: bool = False):
+    """timm apply_rot_embed_cat: x [B, H, n, D], emb [n, 2D] or [H, n, 2D] = sin || cos on the last axis.  fp32 arithmetic,
+    cast back to x's dtype."""
+    sin, cos = emb.float().chunk(2, dim=-1)
+    xf = x.float()
+    return (xf * cos + (rot_half(xf) if half else rot_interleaved(xf)) * sin).to(x.dtype)
+
+
+class RotaryEmbedding(nn.Module):
+    """The rotary tables of a model, after timm's `RotaryEmbeddingCat` (written from memory of timm 1.x, unverified against an
+    installed timm): `get_embed(shape=None)` returns sin || cos on the last axis for the patches of a (gh, gw) grid (default: the
+    model's own), row-major - [n, 2D] for "axial" (one table for all heads and blocks), [depth, H, n, 2D] for "mixed".  The
+    tables are deterministic functions of the grid: positions are the patch coordinates (y, x) = 0, 1, 2 ...
+
+    axial: D / 4 bands w_i = temperature ** (-i / (D / 4)); the D / 2 angles of patch (y, x) are [y w_0 .. y w_{D/4-1},
+           x w_0 .. x w_{D/4-1}].
+    mixed: `freqs` [depth, H, D / 2, 2], a parameter (drawn from the synthetic weight stream); angle i is
+           x freqs[..., i, 0] + y freqs[..., i, 1].
+    Angle i goes to the pair the layout names: elements (2i, 2i + 1) (interleaved) or (i, i + D / 2) (half)."""
+
+    def __init__(self, head_dim: int, grid, kind: str = "axial", half: bool = False, num_heads: int = 1, depth: int = 1,
+                 temperature: float = 100.0):
         super().__init__()
+        assert kind in ("axial", "mixed") and head_dim % 4 == 0
+        self.dim, self.kind, self.half, self.grid, self.temperature = head_dim, kind, half, tuple(grid), temperature
+        self.freqs = nn.Parameter(torch.zeros(depth, num_heads, head_dim // 2, 2)) if kind == "mixed" else None
+
+    def get_embed(self, shape=None):
+        gh, gw = shape if shape is not None else self.grid
+        y, x = torch.meshgrid(torch.arange(gh, dtype=torch.float32), torch.arange(gw, dtype=torch.float32), indexing="ij")
+        y, x = y.reshape(-1), x.reshape(-1)                               # [n], row-major like the patch embedding
+        if self.kind == "axial":
+            bands = self.temperature ** (-torch.arange(self.dim // 4, dtype=torch.float32) / (self.dim // 4))
+            ang = torch.cat([y[:, None] * bands, x[:, None] * bands], -1)  # [n, D / 2]
+        else:
+            f = self.freqs.detach().float().cpu()
+            ang = x[:, None] * f[:, :, None, :, 0] + y[:, None] * f[:, :, None, :, 1]   # [depth, H, n, D / 2]
+        ang = torch.cat([ang, ang], -1) if self.half else ang.repeat_interleave(2, dim=-1)
+        dev = self.freqs.device if self.freqs is not None else None
+        return torch.cat([ang.sin(), ang.cos()], -1).to(dev)
+
+
+class Attention(nn.Module):
+    def __init__(self, dim: int, num_heads: int, qk_norm: bool = False, ln_eps: float = 1e-6, bias: bool = True,
+                 rotate_half: bool = False, num_prefix_tokens: int = 1):
+        super().__init__()
+        self.rotate_half = rotate_half                  # the pairing of a rotary table handed to forward (timm Eva's attribute)
+        self.num_prefix_tokens = num_prefix_tokens      # rows in front that carry no position
         self.num_heads = num_heads
         self.head_dim = dim // num_heads
         self.scale = self.head_dim ** -0.5
@@ -380,11 +475,15 @@ class Attention(nn.Module):
         self.proj = nn.Linear(dim, dim, bias=bias)
         self.proj_drop = nn.Dropout(0.0)
 
-    def forward(self, x):
+    def forward(self, x, rope=None):
         B, N, C = x.shape
         qkv = self.qkv(x).reshape(B, N, 3, self.num_heads, self.head_dim).permute(2, 0, 3, 1, 4)
         q, k, v = qkv.unbind(0)
         q, k = self.q_norm(q), self.k_norm(k)
+        if rope is not None:      # timm EvaAttention: behind q/k-norm, the prefix rows pass through
+            P = self.num_prefix_tokens
+            q = torch.cat([q[:, :, :P], apply_rot_embed_cat(q[:, :, P:], rope, self.rotate_half)], 2)
+            k = torch.cat([k[:, :, :P], apply_rot_embed_cat(k[:, :, P:], rope, self.rotate_half)], 2)
         x = F.scaled_dot_product_attention(q, k, v)
         return self.proj_drop(self.proj(x.transpose(1, 2).reshape(B, N, C)))
 
@@ -510,7 +609,8 @@ class Block(nn.Module):
         super().__init__()
         C = cfg.embed_dim
         self.norm1 = make_norm(cfg, C)
-        self.attn = Attention(C, cfg.num_heads, cfg.qk_norm, cfg.ln_eps, cfg.bias)
+        self.attn = Attention(C, cfg.num_heads, cfg.qk_norm, cfg.ln_eps, cfg.bias, rotate_half=cfg.rope_half,
+                              num_prefix_tokens=cfg.num_prefix_tokens)
         self.ls1 = LayerScale(C, cfg.layer_scale) if cfg.layer_scale else nn.Identity()
         self.drop_path1 = nn.Identity()
         self.norm2 = make_norm(cfg, C)
@@ -518,8 +618,8 @@ class Block(nn.Module):
         self.ls2 = LayerScale(C, cfg.layer_scale) if cfg.layer_scale else nn.Identity()
         self.drop_path2 = nn.Identity()
 
-    def forward(self, x):
-        x = x + self.drop_path1(self.ls1(self.attn(self.norm1(x))))
+    def forward(self, x, rope=None):
+        x = x + self.drop_path1(self.ls1(self.attn(self.norm1(x)) if rope is None else self.attn(self.norm1(x), rope=rope)))
         x = x + self.drop_path2(self.ls2(self.mlp(self.norm2(x))))
         return x
 
@@ -542,7 +642,10 @@ class VisionTransformer(nn.Module):
             self.dist_token = nn.Parameter(torch.zeros(1, 1, cfg.embed_dim))
             self.distilled_training = False
         n_pos = cfg.num_patches if cfg.no_embed_class else cfg.num_patches + cfg.num_prefix_tokens
-        self.pos_embed = nn.Parameter(torch.zeros(1, n_pos, cfg.embed_dim))
+        self.pos_embed = nn.Parameter(torch.zeros(1, n_pos, cfg.embed_dim)) if cfg.abs_pos else None
+        g = cfg.img_size // cfg.patch_size
+        self.rope = (RotaryEmbedding(cfg.head_dim, (g, g), cfg.rope, cfg.rope_half, cfg.num_heads, cfg.depth)
+                     if cfg.rope != "none" else None)
         self.pos_drop = nn.Dropout(0.0)
         if cfg.global_pool not in ("token", "avg", "map"):
             raise ValueError(f"global_pool must be 'token', 'avg' or 'map', got {cfg.global_pool!r}")
@@ -569,7 +672,9 @@ class VisionTransformer(nn.Module):
             prefix.append(self.reg_token.expand(x.shape[0], -1, -1))
         if self.cfg.distilled:
             prefix.append(self.dist_token.expand(x.shape[0], -1, -1))
-        if self.no_embed_class:
+        if self.pos_embed is None:
+            x = torch.cat(prefix + [x], dim=1)
+        elif self.no_embed_class:
             x = torch.cat(prefix + [x + self.pos_embed], dim=1)
         else:
             x = torch.cat(prefix + [x], dim=1) + self.pos_embed
@@ -578,7 +683,12 @@ class VisionTransformer(nn.Module):
     def forward_features(self, x):
         x = self._pos_embed(self.patch_embed(x))
         x = self.norm_pre(x)
-        x = self.blocks(x)
+        if self.rope is None:
+            x = self.blocks(x)
+        else:      # timm Eva.forward_features: the table (a per-block slice of a mixed one) goes to every block
+            emb = self.rope.get_embed()
+            for i, blk in enumerate(self.blocks):
+                x = blk(x, rope=emb[i] if emb.dim() == 4 else emb)
         return self.norm(x)
 
     def forward(self, x):
@@ -619,7 +729,8 @@ def synth_state_dict(cfg: ViTConfig, seed: int = 0, std: float = 0.02,
     if cfg.class_token:      # (a model without one draws nothing in its place)
         sd["cls_token"] = nrm(1, 1, C)
     n_pos = cfg.num_patches if cfg.no_embed_class else cfg.num_patches + cfg.num_prefix_tokens
-    sd["pos_embed"] = nrm(1, n_pos, C)
+    if cfg.abs_pos:          # (a model without an absolute embedding draws nothing in its place)
+        sd["pos_embed"] = nrm(1, n_pos, C)
     fan_in = cfg.in_chans * P * P
     sd["patch_embed.proj.weight"] = nrm(C, cfg.in_chans, P, P, s=1.0 / math.sqrt(fan_in))
     sd["patch_embed.proj.bias"] = nrm(C, s=bias_std) if bias_std else np.zeros(C, np.float32)
@@ -697,6 +808,8 @@ def synth_state_dict(cfg: ViTConfig, seed: int = 0, std: float = 0.02,
         sd[p + "mlp.fc2.bias"] = nrm(C, s=bias_std) if bias_std else np.zeros(C, np.float32)
     if cfg.embed_norm:      # after every other draw: the norm inside the patch embedding
         ln("patch_embed.norm", C)
+    if cfg.rope == "mixed":      # after every other draw: per-block, per-head frequencies, radians per patch on each axis
+        sd["rope.freqs"] = nrm(cfg.depth, cfg.num_heads, cfg.head_dim // 2, 2, s=1.0)
     return sd
 
 

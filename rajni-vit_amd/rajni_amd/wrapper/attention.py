@@ -53,6 +53,9 @@ class RAJNIAttention(nn.Module):
         qk = qk_norm_modules(attn)
         self.q_norm = qk[0] if qk else getattr(attn, "q_norm", None) or nn.Identity()
         self.k_norm = qk[1] if qk else getattr(attn, "k_norm", None) or nn.Identity()
+        # the pairing of a model's rotary table (timm Eva's attribute; RAJNIViTWrapper reads it from every block).  This module's
+        # own forward takes no table: the rotation of a RoPE model runs in the whole-forward plan only
+        self.rotate_half = bool(getattr(attn, "rotate_half", False))
         self.keep_ratio = keep_ratio
         self.update = update
         # prefix tokens at the front of x (CLS + timm register tokens): always kept, never ranked.  RAJNIViTWrapper sets it

@@ -21,7 +21,9 @@ registers), which the reference cannot run at all: their importance query is the
 (`set_importance_query`, include/rajni_hip_query.h - this project's own rule), selectable on class-token models too; and
 attention-pool heads (timm `global_pool='map'`, `attn_pool` = AttentionPoolLatent: the SigLIP image towers, with or without a
 class token): one learned query over every token that survives the last block, then proj and a residual MLP on B rows
-(include/rajni_hip_attnpool.h; `attn_pool_module` holds the pool to its contract).
+(include/rajni_hip_attnpool.h; `attn_pool_module` holds the pool to its contract); and rotary position embeddings (`model.rope`, a module whose `get_embed`
+returns sin || cos tables - `rope_tables` holds it to its contract; include/rajni_hip_rope.h): q and k of every block rotated by
+the place each surviving token had in the image, with or without a learned absolute embedding (`pos_embed` None).
 
 Not kept: the Python per-block loop.  `forward` builds (once per batch shape) a `rajni_vit_plan`
 - packed weights, workspace, per-stage index buffers - and calls `rajni_vit_forward`, which enqueues
@@ -62,6 +64,8 @@ class PlanInput(NamedTuple):
     qry: object       # rajni_vit_query
     apr: object       # rajni_vit_attn_pool
     nrm: object = None   # rajni_vit_norm
+    rop: object = None   # rajni_vit_rope
+    rot: object = None   # the (cos, sin) tensors that record points to: a plan owns what it points to, whatever the cache evicts
 
 
 class PlanEntry(NamedTuple):
@@ -78,15 +82,15 @@ class PlanEntry(NamedTuple):
 
 
 # The native entry points, narrowest first: each takes the records of the one in front of it and one more, and a call goes
-# through the one that takes the widest record it has - a norm record: _norm, else a pool record: _pool, else a query record: _query, else an image
+# through the one that takes the widest record it has - a rope record: _rope, else a norm record: _norm, else a pool record: _pool, else a query record: _query, else an image
 # record: _image, else layers: _layers, else prefix: _ext_prefix, else ext: _ext, else the plain one.  (The symbol is part of
 # the interface: nat.check puts it into the error message.)
 _FORWARDS = ("rajni_vit_forward", "rajni_vit_forward_ext", "rajni_vit_forward_ext_prefix", "rajni_vit_forward_layers",
              "rajni_vit_forward_image", "rajni_vit_forward_query", "rajni_vit_forward_pool",
-             "rajni_vit_forward_norm")                                                      # (ext, pre, lay, img, qry, apr, nrm)
+             "rajni_vit_forward_norm", "rajni_vit_forward_rope")                            # (ext, pre, lay, img, qry, apr, nrm, rop)
 _SIZES = ("rajni_vit_workspace_bytes", "rajni_vit_workspace_bytes_prefix", "rajni_vit_workspace_bytes_image",
           "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_pool",
-          "rajni_vit_workspace_bytes_norm")                                                 # (pre, img, qry, apr, nrm)
+          "rajni_vit_workspace_bytes_norm", "rajni_vit_workspace_bytes_rope")               # (pre, img, qry, apr, nrm, rop)
 NORM_MAX_C = 2048      # the row kernels hold a row in one wave's registers: C <= 64 lanes * 4 chunks * 8 elements
 
 
@@ -191,6 +195,60 @@ def model_has_class_token(m: nn.Module) -> bool:
     return getattr(m, "cls_token", None) is not None
 
 
+def model_embed_dim(m: nn.Module) -> int:
+    """C: the width of the class token, else of the position embedding, else (a model with neither: no class token and rotary
+    positions alone) the patch projection's output channels"""
+    for t in (getattr(m, "cls_token", None), getattr(m, "pos_embed", None)):
+        if t is not None:
+            return int(t.shape[-1])
+    return int(m.patch_embed.proj.out_channels)
+
+
+def classify_rope_embed(emb, heads: int, head_dim: int, depth: int) -> str:
+    """"shared", "per_head" or "per_block": what a rotary table returned by `rope.get_embed` covers - [n, 2D] one table for all
+    heads and blocks, [H, n, 2D] one per head, [depth, H, n, 2D] one per block and head (mixed RoPE) - sin on the first D of
+    the last axis, cos on the last D.  Anything else raises NotImplementedError naming the shape."""
+    why = "RAJNIViTWrapper: model.rope.get_embed() must return sin || cos tables"
+    if not isinstance(emb, torch.Tensor) or not emb.is_floating_point() or emb.dim() not in (2, 3, 4):
+        raise NotImplementedError(f"{why} [n, 2D], [H, n, 2D] or [depth, H, n, 2D]; got "
+                                  f"{tuple(emb.shape) if isinstance(emb, torch.Tensor) else type(emb).__name__}")
+    if emb.shape[-1] != 2 * head_dim:
+        raise NotImplementedError(f"{why} whose last axis is 2 * head_dim = {2 * head_dim}; got {tuple(emb.shape)} "
+                                  f"(a table for part of the head dim, or sin and cos apart, is not supported)")
+    if emb.dim() >= 3 and emb.shape[-3] != heads:
+        raise NotImplementedError(f"{why}; a per-head table needs {heads} heads, got {tuple(emb.shape)}")
+    if emb.dim() == 4 and emb.shape[0] != depth:
+        raise NotImplementedError(f"{why}; a per-block table needs {depth} blocks, got {tuple(emb.shape)}")
+    return {2: "shared", 3: "per_head", 4: "per_block"}[emb.dim()]
+
+
+def rope_tables(m: nn.Module, heads: int, head_dim: int, depth: int, grid=None):
+    """None for a model without rotary positions (`model.rope` missing or None), else (kind, emb): the table of the model's own
+    grid, or of `grid` = (gh, gw) fetched as `get_embed(shape=(gh, gw))`, and what it covers (classify_rope_embed).  The
+    contract mirrors timm's `Eva` / `RotaryEmbeddingCat` and is written from memory of timm 1.x, unverified against an installed
+    timm: `rope` is a module whose `get_embed(shape=None)` returns sin || cos on the last axis, 2 * head_dim wide."""
+    rope = getattr(m, "rope", None)
+    if rope is None:
+        return None
+    get = getattr(rope, "get_embed", None)
+    if not callable(get):
+        raise NotImplementedError(f"RAJNIViTWrapper: model.rope ({type(rope).__name__}) has no get_embed(): rotary positions are "
+                                  "taken from a module whose get_embed(shape=None) returns sin || cos tables")
+    with torch.no_grad():
+        emb = get() if grid is None else get(shape=tuple(grid))
+    return classify_rope_embed(emb, heads, head_dim, depth), emb
+
+
+def rope_layout(blocks) -> bool:
+    """True for rotate_half pairs (j, j + D/2), False for timm rot()'s (2i, 2i + 1): `blocks[i].attn.rotate_half`, False where
+    the attribute is missing; all blocks must agree"""
+    kinds = [bool(getattr(blk.attn, "rotate_half", False)) for blk in blocks]
+    if any(k != kinds[0] for k in kinds):
+        raise NotImplementedError(f"RAJNIViTWrapper: block {kinds.index(not kinds[0])}: attn.rotate_half differs between blocks "
+                                  "(one pairing of the rotary table per model)")
+    return kinds[0]
+
+
 def _num_prefix_without_class_token(m: nn.Module) -> int:
     """R of a model whose `cls_token` is None (timm class_token=False): the prefix tokens are its registers alone.  Accepted
     only when the model is consistent - no distillation pair, a well-formed `reg_token`, a declared `num_prefix_tokens` equal
@@ -200,7 +258,7 @@ def _num_prefix_without_class_token(m: nn.Module) -> int:
     if getattr(m, "dist_token", None) is not None or getattr(m, "head_dist", None) is not None:
         raise NotImplementedError(f"{why} but a distillation token or head_dist: distillation reads the class row")
     reg = getattr(m, "reg_token", None)
-    Cdim = m.pos_embed.shape[-1]
+    Cdim = model_embed_dim(m)
     R = 0
     if reg is not None:
         if reg.dim() != 3 or reg.shape[0] != 1 or reg.shape[1] < 1 or reg.shape[2] != Cdim:
@@ -213,7 +271,7 @@ def _num_prefix_without_class_token(m: nn.Module) -> int:
     if R > nat.MAX_PREFIX:
         raise NotImplementedError(f"{why} and {R} prefix tokens; at most {nat.MAX_PREFIX} are supported")
     n_patches = getattr(m.patch_embed, "num_patches", None)
-    if isinstance(n_patches, int) and m.pos_embed.shape[-2] not in (n_patches, n_patches + R):
+    if isinstance(n_patches, int) and m.pos_embed is not None and m.pos_embed.shape[-2] not in (n_patches, n_patches + R):
         raise NotImplementedError(f"{why}: pos_embed has {m.pos_embed.shape[-2]} rows; with {R} register tokens and {n_patches} "
                                   f"patches it must have {n_patches} (no_embed_class) or {n_patches + R}")
     pool = getattr(m, "global_pool", "token")
@@ -384,7 +442,7 @@ def attn_pool_module(m: nn.Module) -> Optional[nn.Module]:
         raise NotImplementedError(f"RAJNIViTWrapper: attn_pool beside global_pool={pool_kind!r} is not supported (an attention "
                                   "pool is the head of global_pool='map')")
     why = "RAJNIViTWrapper: attn_pool is not timm's AttentionPoolLatent as global_pool='map' builds it"
-    Cdim = m.pos_embed.shape[-1]
+    Cdim = model_embed_dim(m)
     latent = getattr(ap, "latent", None)
     lin = {name: getattr(ap, name, None) for name in ("q", "kv", "proj")}
     if not isinstance(latent, torch.Tensor) or any(not isinstance(v, nn.Linear) for v in lin.values()):
@@ -576,6 +634,28 @@ class RAJNIViTWrapper(nn.Module):
                 cache[key] = ops.resample_pos_embed(W["pos"], src, (gh, gw), pr)
         return cache[key], int(pr > 0)
 
+    def _rope_for_grid(self, W, gh: int, gw: int, device):
+        """(cos, sin) fp32 device tensors [..., gh * gw, D] of the model's rotary table, converted once per grid and cached
+        beside the packed weights like the resampled position embedding (8 entries; a plan keeps the pair it points to alive itself,
+        PlanInput.rot, as it keeps its position rows).  The model's own table at its own grid;
+        under dynamic_img_size the table of the input's grid, fetched as get_embed(shape=(gh, gw))."""
+        d = W["desc"]
+        cache = W.setdefault("rope_cache", {})
+        key = (gh, gw, device)
+        if key not in cache:
+            kind, emb = rope_tables(self.m, d["H"], d["D"], d["depth"], (gh, gw) if self._dynamic_img_size else None)
+            if kind != d["rope"]:
+                raise NotImplementedError(f"RAJNIViTWrapper: model.rope.get_embed(shape=({gh}, {gw})) returns a {kind} table but "
+                                          f"the model's own is {d['rope']}")
+            if emb.shape[-2] != gh * gw:
+                raise ValueError(f"model.rope's table has {emb.shape[-2]} rows but the input yields {gh * gw} patches; "
+                                 "set_dynamic_img_size(True) fetches the table of the input's grid")
+            sin, cos = emb.detach().to(device=device, dtype=torch.float32).chunk(2, dim=-1)
+            if len(cache) >= 8:
+                cache.pop(next(iter(cache)))
+            cache[key] = (cos.contiguous(), sin.contiguous())
+        return cache[key]
+
     def set_weight_format(self, fmt: str):
         """"model" (default), "fp8" or "fp8_mfma".
         "fp8": keep qkv/proj/fc1/fc2 weights as fp8 e4m3 with one fp32 scale per output row (BASELINE config 5,
@@ -601,6 +681,10 @@ class RAJNIViTWrapper(nn.Module):
         if fmt == "fp8_mfma" and self._norm_feature_or_none():
             raise NotImplementedError(f'set_weight_format("fp8_mfma"): not supported on a model with {self._norm_feature_or_none()}: '
                                       'the e4m3-output norm kernels are LayerNorm only ("fp8" weights work)')
+        if fmt == "fp8_mfma" and getattr(self.m, "rope", None) is not None:
+            raise NotImplementedError('set_weight_format("fp8_mfma"): not supported on a model with rotary position embeddings '
+                                      '(model.rope): the e4m3 attention and its bounds were fitted to unrotated q and k ("fp8" '
+                                      'weights work)')
         if fmt == "fp8_mfma" and self._mlp_act_or_none() == "quick_gelu":
             raise NotImplementedError('set_weight_format("fp8_mfma"): the model\'s MLPs use QuickGELU; the fp8 x fp8 FC1 epilogue '
                                       'and its hidden-activation bound are exact GELU only ("fp8" weights work)')
@@ -703,7 +787,7 @@ class RAJNIViTWrapper(nn.Module):
         what is wrong with a norm it does not recognise)"""
         pe_norm = getattr(self.m.patch_embed, "norm", None)
         try:
-            dim = self.m.pos_embed.shape[-1]
+            dim = model_embed_dim(self.m)
             if classify_norm(self.blocks[0].norm1, dim) == "rms":
                 return "RMSNorm"
         except (NotImplementedError, AttributeError):
@@ -736,7 +820,7 @@ class RAJNIViTWrapper(nn.Module):
             raise ValueError("a model without a class token with set_last_block_cls_only(True): there is no class row to form")
         if not has_cls and self._weight_format == "fp8_mfma":
             raise NotImplementedError('weight format "fp8_mfma" on a model without a class token is not supported; "fp8" weights work')
-        Cdim = m.cls_token.shape[-1] if has_cls else m.pos_embed.shape[-1]
+        Cdim = model_embed_dim(m)
         heads = blk0.attn.num_heads
         try:      # (before anything reads its eps: an unrecognised norm is refused as that)
             classify_norm(blk0.norm1, Cdim)
@@ -826,7 +910,7 @@ class RAJNIViTWrapper(nn.Module):
         if desc["head_rows"] == 2 and self._cls_only_last:
             raise ValueError("a distillation model with set_last_block_cls_only(True): that opt-in forms the class row only")
         n_patches = getattr(m.patch_embed, "num_patches", None)
-        if has_cls and num_prefix > 1 and isinstance(n_patches, int) and m.pos_embed.shape[-2] not in (n_patches, n_patches + num_prefix):
+        if has_cls and num_prefix > 1 and isinstance(n_patches, int) and m.pos_embed is not None and m.pos_embed.shape[-2] not in (n_patches, n_patches + num_prefix):
             raise NotImplementedError(f"RAJNIViTWrapper: pos_embed has {m.pos_embed.shape[-2]} rows; with {num_prefix} prefix tokens "
                                       f"and {n_patches} patches it must have {n_patches} (no_embed_class) or {n_patches + num_prefix}")
         fc_norm = getattr(m, "fc_norm", None)
@@ -856,6 +940,19 @@ class RAJNIViTWrapper(nn.Module):
                        or desc["mlp_act"] != "gelu")
         # ... and plans that need no norm record keep the entry point they had
         desc["norm_record"] = feature is not None
+        # rotary positions (rajni_vit_rope): what the model's own table covers and how it pairs the elements; None without
+        rope = rope_tables(m, heads, desc["D"], desc["depth"])
+        desc["rope"] = rope[0] if rope else None
+        if rope:
+            desc["rope_half"] = rope_layout(self.blocks)
+            for i, blk in enumerate(self.blocks):
+                npt = getattr(blk.attn, "num_prefix_tokens", num_prefix)
+                if npt != num_prefix:
+                    raise NotImplementedError(f"RAJNIViTWrapper: block {i}: attn.num_prefix_tokens = {npt} but the model has "
+                                              f"{num_prefix} prefix tokens: the rotation skips exactly the prefix rows")
+            if self._weight_format == "fp8_mfma":      # (the table was attached after the setter)
+                raise NotImplementedError('weight format "fp8_mfma" on a model with rotary position embeddings (model.rope) is '
+                                          'not supported; "fp8" weights work')
         return desc
 
     def _all_params(self):
@@ -928,7 +1025,9 @@ class RAJNIViTWrapper(nn.Module):
             (m.reg_token if desc["num_prefix"] > (1 if desc["class_token"] else 0) else None)
         W["reg"] = (reg_src.detach().to(device=device, dtype=dtype).reshape(-1, desc["C"]).contiguous()
                     if reg_src is not None else None)
-        W["pos"] = m.pos_embed.detach().to(device=device, dtype=dtype).reshape(-1, desc["C"]).contiguous()
+        # (pos_embed None - rotary positions alone: _build_plan hands the patch GEMM a zero table of the input's grid)
+        W["pos"] = (m.pos_embed.detach().to(device=device, dtype=dtype).reshape(-1, desc["C"]).contiguous()
+                    if m.pos_embed is not None else None)
         rms = desc["norm_kind"] == "rms"      # no bias vector is packed or passed: the RMS kernels read none
         nb = lambda mod: None if rms else pv(getattr(mod, "bias", None))
         W["norm_w"], W["norm_b"] = (pv(m.norm.weight), nb(m.norm)) if desc["norm"] else (None, None)
@@ -1073,9 +1172,19 @@ class RAJNIViTWrapper(nn.Module):
             raise ValueError(f"image size {S} is not a multiple of the patch size {d['patch']}")
         gh, gw = Hh // d["patch"], Wd // d["patch"]
         n0 = gh * gw + P
-        pos_rows = W["pos"].shape[0]
         pos = W["pos"]
-        if self._dynamic_img_size:
+        pos_rows = pos.shape[0] if pos is not None else 0
+        if pos is None:
+            # no absolute embedding: a zero table of the grid's patch rows (cached like the resampled embeddings), which the
+            # patch GEMM adds as it adds any other - no kernel knows the difference
+            cache = W.setdefault("pos_cache", {})
+            zkey = ("zero", gh * gw, device, dtype)
+            if zkey not in cache:
+                if len(cache) >= 8:
+                    cache.pop(next(iter(cache)))
+                cache[zkey] = torch.zeros((gh * gw, d["C"]), dtype=dtype, device=device)
+            pos, pos_has_cls = cache[zkey], 0
+        elif self._dynamic_img_size:
             if getattr(self.m, "dynamic_img_pad", False) or getattr(self.m.patch_embed, "dynamic_img_pad", False):
                 raise NotImplementedError("RAJNIViTWrapper: dynamic_img_pad (padding images to a multiple of the patch size) is "
                                           "not supported")
@@ -1172,12 +1281,20 @@ class RAJNIViTWrapper(nn.Module):
             if d["embed_norm"]:
                 nrm.embed_norm_w, nrm.embed_norm_b = nat.ptr(W["embed_norm_w"]), nat.ptr(W["embed_norm_b"])
                 nrm.embed_norm_eps = d["embed_norm_eps"]
-        symbol, records = _native_call(_SIZES, pre, img, qry, apr, nrm)
+        rop = rot = None
+        if d["rope"]:             # the rope record beside the plan (rajni_vit_rope); None: no rotation, the entry points as ever
+            rot = cos, sin = self._rope_for_grid(W, gh, gw, device)
+            rop = nat.VitRope()
+            rop.cos, rop.sin, rop.rows = cos.data_ptr(), sin.data_ptr(), gh * gw
+            rop.head_stride = gh * gw * d["D"] if d["rope"] != "shared" else 0
+            rop.block_stride = d["H"] * gh * gw * d["D"] if d["rope"] == "per_block" else 0
+            rop.layout = nat.ROPE_HALF if d["rope_half"] else nat.ROPE_INTERLEAVED
+        symbol, records = _native_call(_SIZES, pre, img, qry, apr, nrm, rop)
         nbytes = getattr(nat.lib(), symbol)(C.byref(plan), *records)
         if nbytes == 0 and symbol not in _SIZES[:2]:
-            # the image, query, pool or norm record is refused: say why (the forward's own refusal; nothing is launched)
+            # the image, query, pool, norm or rope record is refused: say why (the forward's own refusal; nothing is launched)
             dry = nat.VitExt(pool=nat.POOL_MAP) if apr is not None else None
-            forward, records = _native_call(_FORWARDS, dry, pre, None, img, qry, apr, nrm)
+            forward, records = _native_call(_FORWARDS, dry, pre, None, img, qry, apr, nrm, rop)
             nat.check(getattr(nat.lib(), forward)(C.byref(plan), *records, 16, 16, None), forward)
             raise nat.NativeError(f"{symbol} refused the plan")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
@@ -1210,7 +1327,7 @@ class RAJNIViTWrapper(nn.Module):
             cap_arr = (C.c_int * len(caps))(*caps)
             layers = (cap_arr, int(lnorm), int(lfill == "last"), (len(caps), B, n0, d["C"]))
         self._plan = PlanEntry(key, plan, PlanRefs(blocks, tc, ws, W, ext, qk, pre), bufs, counts, full_mode, out_shape, layers,
-                               PlanInput(img, pos, gh, gw, qry, apr, nrm))
+                               PlanInput(img, pos, gh, gw, qry, apr, nrm, rop, rot))
         if len(self._plans) >= 4:     # workspaces are large: keep only a few batch shapes alive
             self._plans.pop(next(iter(self._plans)))
         self._plans[key] = self._plan
@@ -1352,7 +1469,9 @@ class RAJNIViTWrapper(nn.Module):
     def _run(self, x: torch.Tensor, mode: str):
         nat.require_device(x, "input images")
         self._check_input_shape(x)
-        anchor = self.m.cls_token if model_has_class_token(self.m) else self.m.pos_embed   # a parameter every model has
+        anchor = self.m.cls_token if model_has_class_token(self.m) else self.m.pos_embed   # a parameter every model has ...
+        if anchor is None:                                                                  # ... but one with rotary positions alone
+            anchor = self.m.patch_embed.proj.weight
         dtype = anchor.dtype
         if self._resid_bf16 and dtype in (torch.bfloat16, torch.float16) and self._resid_dtype != dtype:
             raise ValueError(f"a {self._resid_dtype} residual stream needs a {self._resid_dtype} model (the model is {dtype}); "
@@ -1374,7 +1493,7 @@ class RAJNIViTWrapper(nn.Module):
                     lay = nat.VitLayers()
                     lay.n, lay.blocks, lay.norm, lay.fill, lay.out, lay.slab_stride = len(cap_arr), cap_arr, lnorm, lfill, slabs.data_ptr(), 0
                 symbol, records = _native_call(_FORWARDS, entry.refs.ext, entry.refs.pre, lay, entry.input.img, entry.input.qry,
-                                               entry.input.apr, entry.input.nrm)
+                                               entry.input.apr, entry.input.nrm, entry.input.rop)
                 nat.check(getattr(nat.lib(), symbol)(C.byref(entry.plan), *records, x.data_ptr(), out.data_ptr(),
                                                      nat.stream_ptr(x.device)), symbol)
                 return out if lay is None else (out, slabs)
