@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "rajni_amd", "lib")
 OUT = os.path.join(OUT_DIR, "librajni_hip.so")
-SOURCES = ["capi.hip", "gemm.hip", "rowops.hip", "score_select.hip", "attention.hip", "attention_pool.hip", "variants.hip", "rope.hip", "image.hip", "forward.hip"]
+SOURCES = ["capi.hip", "gemm.hip", "rowops.hip", "score_select.hip", "attention.hip", "attention_pool.hip", "variants.hip", "rope.hip", "hidden_norm.hip", "image.hip", "forward.hip"]
 
 
 def needs_build():
@@ -17,7 +17,7 @@ def needs_build():
         return True
     t = os.path.getmtime(OUT)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h)
-                                                               for h in ("rajni_hip.h", "rajni_hip_debug.h", "rajni_hip_layers.h", "rajni_hip_image.h", "rajni_hip_query.h", "rajni_hip_attnpool.h", "rajni_hip_norm.h", "rajni_hip_rope.h")]
+                                                               for h in ("rajni_hip.h", "rajni_hip_debug.h", "rajni_hip_layers.h", "rajni_hip_image.h", "rajni_hip_query.h", "rajni_hip_attnpool.h", "rajni_hip_norm.h", "rajni_hip_rope.h", "rajni_hip_mlpnorm.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -11,6 +11,7 @@
 #include "../../include/rajni_hip_attnpool.h"
 #include "../../include/rajni_hip_norm.h"
 #include "../../include/rajni_hip_rope.h"
+#include "../../include/rajni_hip_mlpnorm.h"
 
 typedef unsigned short bf16_t;  // raw bf16 bits in memory
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -276,6 +277,10 @@ int launch_embed_norm(int kind, void* x, const float* w, const float* b, const v
 // src [B, N] (NULL: the row index) names for each patch token; head_stride 0 = one table for all heads
 int launch_rope_qk(void* qkv, const int32_t* src, const float* cost, const float* sint, long head_stride, int B, int N, int num_prefix,
                    int H, int D, int layout, int dtype, hipStream_t s);
+// hidden_norm.hip (rajni_hip_mlpnorm.h): the first n columns of every row of x [rows, ld] normalised in place - the norm between
+// FC1's epilogue and FC2; columns [n, ld) keep their zeros
+int launch_hidden_norm(int kind, void* x, long ld, const float* w, const float* b, long rows, int n, float eps, int dtype, int x_f32,
+                       hipStream_t s);
 // image.hip: position-embedding rows [prefix + sh * sw, C] -> [prefix + dh * dw, C], bicubic with antialiasing (timm's
 // resample_abs_pos_embed); prefix rows copied
 int launch_resample_pos_embed(const void* src, int sh, int sw, void* dst, int dh, int dw, int C, int prefix, int dtype, hipStream_t s);

@@ -2,7 +2,7 @@
 // that enqueues every kernel on the caller's stream.  Token counts are data independent,
 // so all shapes are known up front: no allocation, no host sync, no device->host traffic inside.
 //
-// A call is a plan and up to eight optional records.  make_spec resolves them once into a Spec, and everything below takes that
+// A call is a plan and up to nine optional records.  make_spec resolves them once into a Spec, and everything below takes that
 // Spec: check_all (every refusal, before the first launch), carve (the workspace), the block loop and the tails.
 //
 // Per block:  LN1 -> QKV GEMM (all N tokens) -> an attention form -> the tail (launch_tail):
@@ -36,7 +36,8 @@
 // norm launch is the RMS form of the same kernel; with an embedding norm the patch GEMM adds a zeroed position table and
 // launch_embed_norm follows it (rajni_hip_norm.h).  rope - every block rotates q and k in place behind q/k-norm, in front of
 // everything that reads w.qkv, by the table row of each token's place in the image; behind a scheduled block that place comes
-// from the composed selections in w.rsrc (rajni_hip_rope.h).
+// from the composed selections in w.rsrc (rajni_hip_rope.h).  mln - every block's tail normalises the first mln->n columns of
+// w.hid in place between FC1 and FC2 (rajni_hip_mlpnorm.h).
 #include "common.h"
 
 #include <vector>
@@ -72,6 +73,7 @@ struct Spec {
   int kind;                         // every norm of the forward but q/k-norm: RAJNI_NORM_LAYERNORM without the record
   bool rms, embed_norm;             // kind == RAJNI_NORM_RMS; the record carries a patch_embed.norm
   const rajni_vit_rope* rop;        // all zero arrives here as NULL
+  const rajni_vit_mlp_norm* mln;    // all zero arrives here as NULL
   hipStream_t s;
   bool nocls;                       // no class row: the prefix tokens are the registers alone
   int qmode;                        // the importance query of the scoring blocks
@@ -91,21 +93,23 @@ enum { ENTRY_FORWARD = 0, ENTRY_SIZE = 1 };
 
 Spec make_spec(int family, const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre,
                const rajni_vit_layers* lay, const rajni_vit_image* img, const rajni_vit_query* qry, const rajni_vit_attn_pool* ap,
-               hipStream_t s, const rajni_vit_norm* nrm = nullptr, const rajni_vit_rope* rop = nullptr) {
+               hipStream_t s, const rajni_vit_norm* nrm = nullptr, const rajni_vit_rope* rop = nullptr,
+               const rajni_vit_mlp_norm* mln = nullptr) {
   // a NULL trailing record makes a call the next-narrower entry point's, by name too (the size of a pool record is the query
   // size function's plus the pool rows, and there is no size function for a layers record)
-  static const char* const names[2][7] = {
+  static const char* const names[2][8] = {
       {"rajni_vit_forward_ext_prefix", "rajni_vit_forward_layers", "rajni_vit_forward_image", "rajni_vit_forward_query",
-       "rajni_vit_forward_pool", "rajni_vit_forward_norm", "rajni_vit_forward_rope"},
+       "rajni_vit_forward_pool", "rajni_vit_forward_norm", "rajni_vit_forward_rope", "rajni_vit_forward_mlpnorm"},
       {"rajni_vit_workspace_bytes_prefix", "rajni_vit_workspace_bytes_prefix", "rajni_vit_workspace_bytes_image",
        "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_norm",
-       "rajni_vit_workspace_bytes_rope"}};
+       "rajni_vit_workspace_bytes_rope", "rajni_vit_workspace_bytes_mlpnorm"}};
   if (qry && qry->class_token == 1 && qry->query == RAJNI_QUERY_CLS) qry = nullptr;
   if (nrm && nrm->kind == RAJNI_NORM_LAYERNORM && !nrm->embed_norm_w) nrm = nullptr;   // what NULL means
   if (rop && !rop->cos && !rop->sin && !rop->head_stride && !rop->block_stride && !rop->rows && !rop->layout) rop = nullptr;
+  if (mln && !mln->w && !mln->b && mln->eps == 0.f && !mln->n) mln = nullptr;
   Spec c{};
-  c.rop = rop;
-  c.who = names[family][rop ? 6 : nrm ? 5 : (ap && family == ENTRY_FORWARD) ? 4 : qry ? 3 : img ? 2 : lay ? 1 : 0];
+  c.rop = rop; c.mln = mln;
+  c.who = names[family][mln ? 7 : rop ? 6 : nrm ? 5 : (ap && family == ENTRY_FORWARD) ? 4 : qry ? 3 : img ? 2 : lay ? 1 : 0];
   c.p = plan; c.ext = ext; c.pre = pre; c.lay = lay; c.img = img; c.qry = qry; c.ap = ap; c.nrm = nrm; c.s = s;
   c.kind = nrm ? nrm->kind : RAJNI_NORM_LAYERNORM;
   c.rms = c.kind == RAJNI_NORM_RMS;
@@ -378,9 +382,11 @@ inline bool attn_emits_e4m3(const rajni_vit_plan& p, const rajni_block& blk, int
 }
 
 // everything of a block behind its attention: proj + residual -> LN2 -> fc1 + GELU -> fc2 + residual
-struct Tail { rajni_linear_args proj, fc1, fc2; };
+struct Tail { rajni_linear_args proj, fc1, fc2; const float *mln_w, *mln_b; };   // mln_w: this block's norm between fc1 and fc2, or null
 Tail tail_args(const Spec& f, const rajni_block& blk, const AttnRows& r, const void* x, void* y) {
-  return Tail{proj_args(f, blk, r, x, y), fc1_args(f, blk, r.M), fc2_args(f, blk, r.M, y)};
+  const long i = &blk - f.p->blocks;
+  return Tail{proj_args(f, blk, r, x, y), fc1_args(f, blk, r.M), fc2_args(f, blk, r.M, y), f.mln ? f.mln->w[i] : nullptr,
+              (f.mln && f.mln->b && !f.rms) ? f.mln->b[i] : nullptr};
 }
 // would rajni_linear take all three?  (the dry run: every refusal, no launch; 256 CUs - no refusal depends on the count)
 bool tail_ok(const Tail& t) {
@@ -395,6 +401,10 @@ int launch_tail(const Spec& f, const rajni_block& blk, const Tail& t) {
   if (rc != RAJNI_OK) return rc;
   rc = launch_linear(t.fc1, f.s);
   if (rc != RAJNI_OK) return rc;
+  if (t.mln_w) {   // the rows FC1 has just written, their first mln->n columns; the zero padding behind them stays
+    rc = launch_hidden_norm(f.kind, f.w.hid, f.p->hidden, t.mln_w, t.mln_b, t.fc1.M, f.mln->n, f.mln->eps, f.p->dtype, 0, f.s);
+    if (rc != RAJNI_OK) return rc;
+  }
   return launch_linear(t.fc2, f.s);
 }
 
@@ -546,6 +556,30 @@ int check_rope(const Spec& c) {
                 "%s: RoPE (a rope record) is unsupported with plan.act_fp8 - the e4m3 attention and its bounds were fitted to "
                 "unrotated q and k", who);
   RAJNI_REQUIRE_PLACED("rajni_vit_forward_rope: rope", {"cos", r.cos, 16}, {"sin", r.sin, 16});
+  return RAJNI_OK;
+}
+
+// the mlp-norm record against the plan (rajni_hip_mlpnorm.h): host-side tests, every refusal names the combination
+int check_mlp_norm(const Spec& c) {
+  const char* who = c.who;          // (an mlp-norm record is the widest there is: the mlpnorm entry point of the call's family)
+  const rajni_vit_plan& p = *c.p;
+  const rajni_vit_mlp_norm& m = *c.mln;
+  RAJNI_REQUIRE(m.n > 0 && m.n <= p.hidden, RAJNI_ERR_INVALID,
+                "%s: mlp_norm.n must be the MLP width, 1..plan.hidden = %d (%d): plan.hidden is the zero-padded width", who, p.hidden,
+                m.n);
+  RAJNI_REQUIRE(m.n <= RAJNI_HIDDEN_NORM_MAX, RAJNI_ERR_UNSUPPORTED,
+                "%s: mlp_norm.n = %d is over rajni_hidden_norm's cap of %d columns", who, m.n, RAJNI_HIDDEN_NORM_MAX);
+  RAJNI_REQUIRE(m.w, RAJNI_ERR_INVALID, "%s: null pointer (mlp_norm.w) with a non-zero mlp_norm record", who);
+  RAJNI_REQUIRE(!p.act_fp8, RAJNI_ERR_UNSUPPORTED,
+                "%s: a norm inside the MLP (an mlp_norm record) is unsupported with plan.act_fp8 - FC1's e4m3 epilogue scales the "
+                "hidden rows for FC2 before the norm could run", who);
+  RAJNI_REQUIRE(p.depth > 0 && p.blocks, RAJNI_ERR_INVALID, "%s: bad plan", who);
+  for (int i = 0; i < p.depth; ++i) {
+    RAJNI_REQUIRE(m.w[i], RAJNI_ERR_INVALID, "%s: null pointer (mlp_norm.w[%d]) with a non-zero mlp_norm record", who, i);
+    char blk[64];
+    snprintf(blk, sizeof(blk), "rajni_vit_forward_mlpnorm: mlp_norm block %d", i);
+    RAJNI_REQUIRE_PLACED(blk, {"w", m.w[i], 16}, {"b", m.b ? m.b[i] : nullptr, 16});
+  }
   return RAJNI_OK;
 }
 
@@ -703,7 +737,7 @@ int launch_source_idx_before(const Spec& c, int upto, int32_t* src, int Nf) {
 
 // Every refusal of the forward, before the first launch.  The order is part of the contract - callers match the first message:
 // the prefix record under the entry point's name; null pointers; the query record (whether there is a class row decides every
-// count); the pool record; the norm record; the image record (every count below is against its grid); the rope record; the layers
+// count); the pool record; the norm record; the image record (every count below is against its grid); the rope record; the mlp-norm record; the layers
 // record; then the plan, the
 // placement of what it points to, the ext record, the distilled head, the schedule, and last the workspace, carved here.
 int check_all(Spec& c, const void* images, const void* logits) {
@@ -716,6 +750,7 @@ int check_all(Spec& c, const void* images, const void* logits) {
   if (c.nrm && (rc = check_norm(c)) != RAJNI_OK) return rc;
   if (c.img && (rc = check_image(c)) != RAJNI_OK) return rc;
   if (c.rop && (rc = check_rope(c)) != RAJNI_OK) return rc;
+  if (c.mln && (rc = check_mlp_norm(c)) != RAJNI_OK) return rc;
   if (c.lay && (rc = check_layers(c)) != RAJNI_OK) return rc;
   if (c.dense_last && (rc = check_dense_last(c)) != RAJNI_OK) return rc;
   if ((rc = check_plan(c)) != RAJNI_OK) return rc;
@@ -739,6 +774,7 @@ size_t workspace_bytes(const Spec& c) {
   if (c.ap && (!pool_hidden_ok(*c.ap) || c.p->B <= 0 || c.p->C <= 0)) return 0;
   if (c.nrm && check_norm(c) != RAJNI_OK) return 0;
   if (c.rop && check_rope(c) != RAJNI_OK) return 0;
+  if (c.mln && check_mlp_norm(c) != RAJNI_OK) return 0;
   return carve(c).total;
 }
 
@@ -1029,6 +1065,13 @@ extern "C" int rajni_vit_forward_rope(const rajni_vit_plan* plan, const rajni_vi
                                       const void* images, void* logits, rajni_stream_t stream) {
   return vit_forward(make_spec(ENTRY_FORWARD, plan, ext, prefix, layers, image, query, pool, (hipStream_t)stream, norm, rope), images, logits);
 }
+extern "C" int rajni_vit_forward_mlpnorm(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
+                                         const rajni_vit_layers* layers, const rajni_vit_image* image, const rajni_vit_query* query,
+                                         const rajni_vit_attn_pool* pool, const rajni_vit_norm* norm, const rajni_vit_rope* rope,
+                                         const rajni_vit_mlp_norm* mlp_norm, const void* images, void* logits, rajni_stream_t stream) {
+  return vit_forward(make_spec(ENTRY_FORWARD, plan, ext, prefix, layers, image, query, pool, (hipStream_t)stream, norm, rope, mlp_norm),
+                     images, logits);
+}
 extern "C" size_t rajni_vit_workspace_bytes(const rajni_vit_plan* plan) {
   return workspace_bytes(make_spec(ENTRY_SIZE, plan, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
 }
@@ -1056,6 +1099,13 @@ extern "C" size_t rajni_vit_workspace_bytes_rope(const rajni_vit_plan* plan, con
                                                  const rajni_vit_query* query, const rajni_vit_attn_pool* pool, const rajni_vit_norm* norm,
                                                  const rajni_vit_rope* rope) {
   return workspace_bytes(make_spec(ENTRY_SIZE, plan, nullptr, prefix, nullptr, image, query, pool, nullptr, norm, rope));
+}
+
+extern "C" size_t rajni_vit_workspace_bytes_mlpnorm(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix,
+                                                    const rajni_vit_image* image, const rajni_vit_query* query,
+                                                    const rajni_vit_attn_pool* pool, const rajni_vit_norm* norm,
+                                                    const rajni_vit_rope* rope, const rajni_vit_mlp_norm* mlp_norm) {
+  return workspace_bytes(make_spec(ENTRY_SIZE, plan, nullptr, prefix, nullptr, image, query, pool, nullptr, norm, rope, mlp_norm));
 }
 
 extern "C" void rajni_debug_set_last_block_all_rows(int on) { g_last_block_all_rows = on; }

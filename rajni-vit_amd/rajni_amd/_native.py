@@ -282,6 +282,26 @@ _ROPE_SIGS = {
                                        C.POINTER(VitRope), c_void_p, c_void_p, c_void_p]),
 }
 ROPE_SYMBOLS = tuple(_ROPE_SIGS.keys())
+# include/rajni_hip_mlpnorm.h, additive in the same way: a norm inside the MLP, between the activation (or the gate) and fc2
+HIDDEN_NORM_MAX = 4096   # RAJNI_HIDDEN_NORM_MAX: the widest row rajni_hidden_norm takes
+
+
+class VitMlpNorm(C.Structure):
+    """rajni_vit_mlp_norm (include/rajni_hip_mlpnorm.h): per-block fp32 weight / bias pointers [n], the eps and the model's MLP
+    width n (plan.hidden is the zero-padded one)"""
+    _fields_ = [("w", C.POINTER(c_void_p)), ("b", C.POINTER(c_void_p)), ("eps", C.c_float), ("n", c_int)]
+
+
+_MLPNORM_SIGS = {
+    "rajni_hidden_norm": (c_int, [c_int, c_void_p, C.c_long, c_void_p, c_void_p, c_int, c_int, C.c_float, c_int, c_int, c_void_p]),
+    "rajni_vit_workspace_bytes_mlpnorm": (c_size_t, [C.POINTER(VitPlan), C.POINTER(VitPrefix), C.POINTER(VitImage),
+                                                     C.POINTER(VitQuery), C.POINTER(VitAttnPool), C.POINTER(VitNorm),
+                                                     C.POINTER(VitRope), C.POINTER(VitMlpNorm)]),
+    "rajni_vit_forward_mlpnorm": (c_int, [C.POINTER(VitPlan), C.POINTER(VitExt), C.POINTER(VitPrefix), C.POINTER(VitLayers),
+                                          C.POINTER(VitImage), C.POINTER(VitQuery), C.POINTER(VitAttnPool), C.POINTER(VitNorm),
+                                          C.POINTER(VitRope), C.POINTER(VitMlpNorm), c_void_p, c_void_p, c_void_p]),
+}
+MLPNORM_SYMBOLS = tuple(_MLPNORM_SIGS.keys())
 RESAMPLE_MAX_GRID = 128     # RAJNI_RESAMPLE_MAX_GRID: grid cells per axis, source and destination
 ABI_VERSION = 8     # include/rajni_hip.h; bumped whenever a struct or an entry point changes
 _lib: Optional[C.CDLL] = None
@@ -298,7 +318,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
             "(hipcc --offload-arch=gfx950). rajni_amd has no CPU or PyTorch fallback by design.")
     lib = C.CDLL(path)
     for name, (res, args) in (list(_SIGS.items()) + list(_LAYERS_SIGS.items()) + list(_IMAGE_SIGS.items()) + list(_QUERY_SIGS.items())
-                              + list(_ATTNPOOL_SIGS.items()) + list(_NORM_SIGS.items()) + list(_ROPE_SIGS.items())):
+                              + list(_ATTNPOOL_SIGS.items()) + list(_NORM_SIGS.items()) + list(_ROPE_SIGS.items())
+                              + list(_MLPNORM_SIGS.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

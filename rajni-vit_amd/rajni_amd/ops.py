@@ -396,6 +396,27 @@ def rope_qk(qkv: torch.Tensor, num_heads: int, cos: torch.Tensor, sin: torch.Ten
     return qkv
 
 
+def hidden_norm(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], eps: float, n: Optional[int] = None,
+                rms: bool = False) -> torch.Tensor:
+    """The norm inside an MLP (include/rajni_hip_mlpnorm.h), IN PLACE on x [rows, ld] (bf16 / fp16 / fp32): columns [0, n) of
+    every row become LayerNorm (`rms`: RMSNorm, b not read) of those n columns with fp32 w / b [n] (b None = 0); the divisor of
+    the statistics is n.  `n` defaults to w's length; columns [n, ld) are the zero padding of the hidden buffer and must hold
+    zeros - they hold zeros afterwards.  ld % 8 == 0, n <= HIDDEN_NORM_MAX.  Returns x."""
+    nat.require_device(x, "x")
+    if x.dim() != 2:
+        raise ValueError(f"hidden_norm: x must be [rows, ld], got {tuple(x.shape)}")
+    x = _placed(x, "x", in_place=True)
+    rows, ld = x.shape
+    n = int(w.numel()) if n is None else int(n)
+    if w.dtype != torch.float32 or w.dim() != 1 or w.numel() != n or (b is not None and (b.dtype != torch.float32 or b.shape != w.shape)):
+        raise ValueError(f"hidden_norm: w and b must be fp32 [{n}]")
+    w, b = _placed(w, "w"), _placed(b, "b")
+    with nat.device_guard(x.device):
+        nat.check(nat.lib().rajni_hidden_norm(nat.NORM_RMS if rms else nat.NORM_LAYERNORM, x.data_ptr(), ld, w.data_ptr(), nat.ptr(b),
+                                              rows, n, float(eps), _dt(x), 0, nat.stream_ptr(x.device)), "rajni_hidden_norm")
+    return x
+
+
 def layernorm_stream(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], eps: float,
                      model_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """timm's `x = norm_pre(x)`: LayerNorm over the last axis written back IN PLACE into the residual stream x (fp32, or the

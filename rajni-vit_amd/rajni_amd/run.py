@@ -79,7 +79,7 @@ def create_base(args):
         model = timm.create_model(args.model, pretrained=args.pretrained)
         source = "timm"
     except ImportError:
-        tables = (ts.CONFIGS, ts.SWIGLU_CONFIGS, ts.NOCLASS_CONFIGS, ts.MAP_CONFIGS, ts.NORM_CONFIGS, ts.ROPE_CONFIGS)
+        tables = ts.ALL_CONFIG_TABLES
         if not any(args.model in t for t in tables):
             raise SystemExit(f"timm is not installed and '{args.model}' is not a built-in config "
                              f"{[n for t in tables for n in sorted(t)]}")

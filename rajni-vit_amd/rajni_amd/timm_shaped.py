@@ -85,6 +85,10 @@ class ViTConfig:
     rope = "none"
     rope_half = False
     abs_pos = True
+    # ... and what EvaViTConfig makes fields
+    mlp_norm = False
+    eva_block = False
+    qkv_split = False
 
     def __post_init__(self):
         if self.rope not in ("none", "axial", "mixed"):
@@ -145,6 +149,18 @@ class RopeViTConfig(NormViTConfig):
                                           # axis; "mixed": learned per-block, per-head frequencies over both axes (RoPE-Mixed)
     rope_half: bool = False               # False: the pairs are (2i, 2i + 1) (timm rot()); True: (i, i + D / 2) (rotate_half)
     abs_pos: bool = True                  # False: no learned absolute position embedding at all (pos_embed is None)
+
+
+@dataclass(frozen=True)
+class EvaViTConfig(RopeViTConfig):
+    """RopeViTConfig plus the rest of timm's `Eva` model (the EVA02 image towers).  A subclass for NormViTConfig's reason.
+    (Keyword only in practice.)"""
+    mlp_norm: bool = False                # a norm of the trunk's kind over the hidden width, between the activation (or the
+                                          # gate) and fc2: timm Mlp / SwiGLU `norm_layer`, EVA02's sub-LayerNorm (scale_mlp)
+    eva_block: bool = False               # timm EvaBlock / EvaAttention spellings: LayerScale as the parameters `gamma_1` /
+                                          # `gamma_2` (None without layer_scale) with no ls1 / ls2 modules; a bias-free `qkv`
+                                          # beside the parameters `q_bias` / `v_bias` (k has no bias); `attn.norm` = Identity
+    qkv_split: bool = False               # `q_proj` / `k_proj` (no bias) / `v_proj` apart and `attn.qkv` None (qkv_fused=False)
 
 
 # The model names BASELINE.json's configs use.
@@ -365,9 +381,39 @@ ROPE_CONFIGS: Dict[str, ViTConfig] = {
 }
 
 
+# timm's `Eva` models, in a table of their own for the same reason.
+_EVA = dict(patch_size=14, rope="axial", eva_block=True)
+EVA_CONFIGS: Dict[str, ViTConfig] = {
+    # ---- the EVA02 towers at 224 px.  timm is not importable where this was written: the four entries are WRITTEN FROM MEMORY
+    # of timm 1.x AND ARE UNVERIFIED (whether q / k / v are fused, the heads' presence and the pooling may each be off): Ti and S
+    # with the packed SwiGLU and no norm inside it, B and L with the split SwiGLU and its sub-LayerNorm over 2048 / 2730 ----
+    "eva02_tiny_patch14_224": EvaViTConfig(embed_dim=192, depth=12, num_heads=3, mlp_ratio=512 / 192, mlp="swiglu_packed", **_EVA),
+    "eva02_small_patch14_224": EvaViTConfig(embed_dim=384, depth=12, num_heads=6, mlp_ratio=1024 / 384, mlp="swiglu_packed", **_EVA),
+    "eva02_base_patch14_224": EvaViTConfig(embed_dim=768, depth=12, num_heads=12, mlp_ratio=2048 / 768, mlp="swiglu",
+                                           mlp_norm=True, qkv_split=True, **_EVA),
+    "eva02_large_patch14_224": EvaViTConfig(embed_dim=1024, depth=24, num_heads=16, mlp_ratio=2730 / 1024, mlp="swiglu",
+                                            mlp_norm=True, qkv_split=True, **_EVA),
+    # micro models (not timm names).  The Eva block with LayerScale, the split SwiGLU and its norm over 344 columns (whole
+    # 16-byte chunks, 384 zero-padded); 342 columns (a partial last chunk) with q / k / v apart; the RMS kind without a class
+    # token; a plain GELU MLP with mlp.norm on the ordinary block and no rope; head dim 40
+    "vit_micro_eva_patch16_64": EvaViTConfig(**_MICRO, mlp_ratio=2.6875, layer_scale=1e-6, mlp="swiglu", mlp_norm=True,
+                                             rope="axial", eva_block=True),
+    "vit_micro_eva_h342_patch16_64": EvaViTConfig(**_MICRO, mlp_ratio=342 / 128, mlp="swiglu", mlp_norm=True, rope="axial",
+                                                  eva_block=True, qkv_split=True),
+    "vit_micro_eva_rms_gap_patch16_64": EvaViTConfig(**_MICRO, mlp_ratio=2.6875, layer_scale=1e-6, mlp="swiglu", mlp_norm=True,
+                                                     rope="axial", eva_block=True, norm="rms", global_pool="avg",
+                                                     class_token=False),
+    "vit_micro_mlpnorm_patch16_64": EvaViTConfig(**_MICRO, mlp_ratio=2.6875, mlp_norm=True),
+    "vit_micro_eva_d40_patch14_56": EvaViTConfig(img_size=56, patch_size=14, embed_dim=320, depth=4, num_heads=8, num_classes=10,
+                                                 mlp_ratio=2.0, mlp="swiglu", mlp_norm=True, rope="axial", eva_block=True),
+}
+ALL_CONFIG_TABLES = (CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS, MAP_CONFIGS, NORM_CONFIGS, ROPE_CONFIGS, EVA_CONFIGS)
+
+
 def config_of(name: str) -> ViTConfig:
-    """the built-in config of that name, from CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS, MAP_CONFIGS, NORM_CONFIGS or ROPE_CONFIGS"""
-    tables = (CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS, MAP_CONFIGS, NORM_CONFIGS, ROPE_CONFIGS)
+    """the built-in config of that name, from CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS, MAP_CONFIGS, NORM_CONFIGS, ROPE_CONFIGS or
+    EVA_CONFIGS"""
+    tables = ALL_CONFIG_TABLES
     for table in tables:
         if name in table:
             return table[name]
@@ -461,14 +507,23 @@ class RotaryEmbedding(nn.Module):
 
 class Attention(nn.Module):
     def __init__(self, dim: int, num_heads: int, qk_norm: bool = False, ln_eps: float = 1e-6, bias: bool = True,
-                 rotate_half: bool = False, num_prefix_tokens: int = 1):
+                 rotate_half: bool = False, num_prefix_tokens: int = 1, eva: bool = False, qkv_split: bool = False):
         super().__init__()
         self.rotate_half = rotate_half                  # the pairing of a rotary table handed to forward (timm Eva's attribute)
         self.num_prefix_tokens = num_prefix_tokens      # rows in front that carry no position
         self.num_heads = num_heads
         self.head_dim = dim // num_heads
         self.scale = self.head_dim ** -0.5
-        self.qkv = nn.Linear(dim, dim * 3, bias=bias)
+        if qkv_split:      # timm EvaAttention(qkv_fused=False): three projections, k without a bias
+            self.qkv = None
+            self.q_proj, self.k_proj, self.v_proj = nn.Linear(dim, dim, bias=bias), nn.Linear(dim, dim, bias=False), nn.Linear(dim, dim, bias=bias)
+        else:
+            self.qkv = nn.Linear(dim, dim * 3, bias=bias and not eva)
+        if eva:            # timm EvaAttention: q and v biases as parameters beside a bias-free qkv (k's is a buffer of zeros)
+            fused_bias = bias and not qkv_split
+            self.q_bias = nn.Parameter(torch.zeros(dim)) if fused_bias else None
+            self.v_bias = nn.Parameter(torch.zeros(dim)) if fused_bias else None
+            self.norm = nn.Identity()      # (scale_norm=False: the inner attention norm of no released EVA02 checkpoint)
         self.q_norm = nn.LayerNorm(self.head_dim, eps=ln_eps) if qk_norm else nn.Identity()
         self.k_norm = nn.LayerNorm(self.head_dim, eps=ln_eps) if qk_norm else nn.Identity()
         self.attn_drop = nn.Dropout(0.0)
@@ -477,15 +532,22 @@ class Attention(nn.Module):
 
     def forward(self, x, rope=None):
         B, N, C = x.shape
-        qkv = self.qkv(x).reshape(B, N, 3, self.num_heads, self.head_dim).permute(2, 0, 3, 1, 4)
-        q, k, v = qkv.unbind(0)
+        if self.qkv is None:
+            qkv = torch.stack([self.q_proj(x), self.k_proj(x), self.v_proj(x)], 2)
+        elif getattr(self, "q_bias", None) is not None:
+            qkv = F.linear(x, self.qkv.weight, torch.cat([self.q_bias, torch.zeros_like(self.q_bias), self.v_bias]))
+        else:
+            qkv = self.qkv(x)
+        q, k, v = qkv.reshape(B, N, 3, self.num_heads, self.head_dim).permute(2, 0, 3, 1, 4).unbind(0)
         q, k = self.q_norm(q), self.k_norm(k)
         if rope is not None:      # timm EvaAttention: behind q/k-norm, the prefix rows pass through
             P = self.num_prefix_tokens
             q = torch.cat([q[:, :, :P], apply_rot_embed_cat(q[:, :, P:], rope, self.rotate_half)], 2)
             k = torch.cat([k[:, :, :P], apply_rot_embed_cat(k[:, :, P:], rope, self.rotate_half)], 2)
-        x = F.scaled_dot_product_attention(q, k, v)
-        return self.proj_drop(self.proj(x.transpose(1, 2).reshape(B, N, C)))
+        x = F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(B, N, C)
+        if hasattr(self, "norm"):
+            x = self.norm(x)
+        return self.proj_drop(self.proj(x))
 
 
 class LayerScale(nn.Module):
@@ -561,10 +623,14 @@ class SwiGLU(nn.Module):
 
 def make_mlp(cfg: "ViTConfig") -> nn.Module:
     if cfg.mlp == "swiglu_packed":
-        return GluMlp(cfg.embed_dim, cfg.hidden_dim, bias=cfg.bias)
-    if cfg.mlp == "swiglu":
-        return SwiGLU(cfg.embed_dim, cfg.hidden_dim, bias=cfg.bias)
-    return Mlp(cfg.embed_dim, cfg.hidden_dim, cfg.act, bias=cfg.bias)
+        mlp = GluMlp(cfg.embed_dim, cfg.hidden_dim, bias=cfg.bias)
+    elif cfg.mlp == "swiglu":
+        mlp = SwiGLU(cfg.embed_dim, cfg.hidden_dim, bias=cfg.bias)
+    else:
+        mlp = Mlp(cfg.embed_dim, cfg.hidden_dim, cfg.act, bias=cfg.bias)
+    if cfg.mlp_norm:      # timm `norm_layer`: over the hidden width, between the activation (or the gate) and fc2
+        mlp.norm = make_norm(cfg, cfg.hidden_dim)
+    return mlp
 
 
 class AttentionPoolLatent(nn.Module):
@@ -610,15 +676,27 @@ class Block(nn.Module):
         C = cfg.embed_dim
         self.norm1 = make_norm(cfg, C)
         self.attn = Attention(C, cfg.num_heads, cfg.qk_norm, cfg.ln_eps, cfg.bias, rotate_half=cfg.rope_half,
-                              num_prefix_tokens=cfg.num_prefix_tokens)
-        self.ls1 = LayerScale(C, cfg.layer_scale) if cfg.layer_scale else nn.Identity()
+                              num_prefix_tokens=cfg.num_prefix_tokens, eva=cfg.eva_block, qkv_split=cfg.qkv_split)
+        gamma = lambda: nn.Parameter(cfg.layer_scale * torch.ones(C)) if cfg.layer_scale else None
+        if cfg.eva_block:      # timm EvaBlock: the LayerScale vectors are parameters of the block, None without init_values
+            self.gamma_1 = gamma()
+        else:
+            self.ls1 = LayerScale(C, cfg.layer_scale) if cfg.layer_scale else nn.Identity()
         self.drop_path1 = nn.Identity()
         self.norm2 = make_norm(cfg, C)
         self.mlp = make_mlp(cfg)
-        self.ls2 = LayerScale(C, cfg.layer_scale) if cfg.layer_scale else nn.Identity()
+        if cfg.eva_block:
+            self.gamma_2 = gamma()
+        else:
+            self.ls2 = LayerScale(C, cfg.layer_scale) if cfg.layer_scale else nn.Identity()
         self.drop_path2 = nn.Identity()
 
     def forward(self, x, rope=None):
+        if not hasattr(self, "ls1"):      # timm EvaBlock.forward
+            a = self.attn(self.norm1(x)) if rope is None else self.attn(self.norm1(x), rope=rope)
+            x = x + self.drop_path1(a if self.gamma_1 is None else self.gamma_1 * a)
+            h = self.mlp(self.norm2(x))
+            return x + self.drop_path2(h if self.gamma_2 is None else self.gamma_2 * h)
         x = x + self.drop_path1(self.ls1(self.attn(self.norm1(x)) if rope is None else self.attn(self.norm1(x), rope=rope)))
         x = x + self.drop_path2(self.ls2(self.mlp(self.norm2(x))))
         return x
@@ -810,6 +888,23 @@ def synth_state_dict(cfg: ViTConfig, seed: int = 0, std: float = 0.02,
         ln("patch_embed.norm", C)
     if cfg.rope == "mixed":      # after every other draw: per-block, per-head frequencies, radians per patch on each axis
         sd["rope.freqs"] = nrm(cfg.depth, cfg.num_heads, cfg.head_dim // 2, 2, s=1.0)
+    if cfg.mlp_norm:             # after every other draw: the norm inside every MLP
+        for i in range(cfg.depth):
+            ln(f"blocks.{i}.mlp.norm", Hd)
+    # Eva's spellings draw nothing: the tensors above under the names the modules have.  The packed qkv's rows are q, k, v in
+    # that order; k has no bias in either spelling, and the values drawn for it are dropped
+    for i in range(cfg.depth if (cfg.eva_block or cfg.qkv_split) else 0):
+        p = f"blocks.{i}."
+        bias = sd.pop(p + "attn.qkv.bias", None)
+        if cfg.qkv_split:
+            wq, wk, wv = np.split(sd.pop(p + "attn.qkv.weight"), 3)
+            sd[p + "attn.q_proj.weight"], sd[p + "attn.k_proj.weight"], sd[p + "attn.v_proj.weight"] = wq.copy(), wk.copy(), wv.copy()
+            if bias is not None:
+                sd[p + "attn.q_proj.bias"], sd[p + "attn.v_proj.bias"] = bias[:C].copy(), bias[2 * C:].copy()
+        elif bias is not None:
+            sd[p + "attn.q_bias"], sd[p + "attn.v_bias"] = bias[:C].copy(), bias[2 * C:].copy()
+        if cfg.eva_block and cfg.layer_scale:
+            sd[p + "gamma_1"], sd[p + "gamma_2"] = sd.pop(p + "ls1.gamma"), sd.pop(p + "ls2.gamma")
     return sd
 
 

@@ -39,13 +39,69 @@ def qk_norm_modules(attn: nn.Module, where: str = "RAJNIAttention"):
     return q, k
 
 
+def qkv_form(attn: nn.Module, where: str = "RAJNIAttention") -> str:
+    """How an attention module spells its q / k / v projection, recognised by what is there: "fused" - `qkv`, an nn.Linear with
+    or without a bias; "fused_qv_bias" - a bias-free `qkv` beside the [C] parameters `q_bias` and `v_bias` (timm EvaAttention: k
+    has no bias); "split" - `q_proj` / `k_proj` / `v_proj`, three nn.Linear of one shape, with `qkv` absent or None.  A
+    half-formed spelling raises NotImplementedError, and so does an inner attention norm (`attn.norm` other than Identity / None:
+    Eva's scale_norm, which no released EVA02 checkpoint has)."""
+    norm = getattr(attn, "norm", None)
+    if norm is not None and not isinstance(norm, nn.Identity):
+        raise NotImplementedError(f"{where}: attn.norm ({type(norm).__name__}), a norm between attention and proj, is not supported")
+    qkv = getattr(attn, "qkv", None)
+    split = [getattr(attn, n, None) for n in ("q_proj", "k_proj", "v_proj")]
+    qb, vb = getattr(attn, "q_bias", None), getattr(attn, "v_bias", None)
+    if qkv is None:
+        if not all(isinstance(m, nn.Linear) for m in split) or len({tuple(m.weight.shape) for m in split}) != 1 \
+                or split[0].in_features != split[0].out_features:
+            raise NotImplementedError(f"{where}: attn.qkv is absent, so q_proj, k_proj and v_proj must be three nn.Linear (C -> C)")
+        if qb is not None or vb is not None:
+            raise NotImplementedError(f"{where}: attn.q_bias / attn.v_bias beside q_proj / k_proj / v_proj: the biases of a split "
+                                      "projection are the three linears' own")
+        return "split"
+    if not isinstance(qkv, nn.Linear):
+        raise NotImplementedError(f"{where}: attn.qkv must be nn.Linear, got {type(qkv).__name__}")
+    if any(m is not None for m in split):
+        raise NotImplementedError(f"{where}: attn.qkv together with q_proj / k_proj / v_proj: one spelling of the projection per model")
+    if qb is None and vb is None:
+        return "fused"
+    if qb is None or vb is None:
+        raise NotImplementedError(f"{where}: attn.q_bias and attn.v_bias come together (timm EvaAttention); the module has only "
+                                  f"{'v_bias' if qb is None else 'q_bias'}")
+    Cdim = qkv.in_features
+    if qkv.bias is not None or tuple(qb.shape) != (Cdim,) or tuple(vb.shape) != (Cdim,):
+        raise NotImplementedError(f"{where}: attn.q_bias / attn.v_bias must be [{Cdim}] beside a bias-free attn.qkv")
+    return "fused_qv_bias"
+
+
+def packed_qkv(attn: nn.Module, where: str = "RAJNIAttention"):
+    """(weight [3C, C], bias [3C] or None) of any spelling qkv_form knows, rows in the order q, k, v: the `qkv` weight itself; the
+    bias cat(q_bias, 0, v_bias); or cat(q_proj, k_proj, v_proj) with the three biases concatenated, a missing one as zeros (no
+    bias at all when none of the three has one).  Detached tensors on the module's device, values untouched."""
+    form = qkv_form(attn, where)
+    if form == "fused":
+        return attn.qkv.weight.detach(), None if attn.qkv.bias is None else attn.qkv.bias.detach()
+    if form == "fused_qv_bias":
+        q, v = attn.q_bias.detach(), attn.v_bias.detach()
+        return attn.qkv.weight.detach(), torch.cat([q, torch.zeros_like(q), v])
+    lins = (attn.q_proj, attn.k_proj, attn.v_proj)
+    w = torch.cat([m.weight.detach() for m in lins])
+    if all(m.bias is None for m in lins):
+        return w, None
+    return w, torch.cat([m.bias.detach() if m.bias is not None else torch.zeros_like(m.weight[:, 0]).detach() for m in lins])
+
+
 class RAJNIAttention(nn.Module):
     def __init__(self, attn: nn.Module, keep_ratio: float, update: bool):
         super().__init__()
         # attribute contract of a timm Attention (attention.py:8-12)
         self.num_heads = attn.num_heads
         self.scale = attn.scale
-        self.qkv = attn.qkv
+        # the q / k / v projection in the spelling the model has (qkv_form): the attributes stay, for the same reason
+        self.qkv = getattr(attn, "qkv", None)
+        for name in ("q_proj", "k_proj", "v_proj", "q_bias", "v_bias", "norm"):
+            if getattr(attn, name, None) is not None:
+                setattr(self, name, getattr(attn, name))
         self.proj = attn.proj
         self.proj_drop = attn.proj_drop
         # timm qk_norm=True: LayerNorm over the head dim of q and k (ops.qk_norm); the modules stay attributes, so the
@@ -69,15 +125,16 @@ class RAJNIAttention(nn.Module):
 
     # ---- weights in the layout the kernels want (rebuilt when parameters change) -------------
     def _weights(self, device, dtype):
-        params = [self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias]
+        qkv_w, qkv_b = packed_qkv(self)
+        params = [p for p in self.parameters(recurse=True)]
         qk = qk_norm_modules(self)
         if qk:
             params += [qk[0].weight, qk[0].bias, qk[1].weight, qk[1].bias]
         key = (str(device), dtype) + tuple((p.data_ptr(), p._version) for p in params if p is not None)
         if self._packed_key != key:
             self._packed = dict(
-                qkv_w=ops.pack_weight(self.qkv.weight, dtype, device),
-                qkv_b=ops.pack_vec(self.qkv.bias, dtype, device),
+                qkv_w=ops.pack_weight(qkv_w, dtype, device),
+                qkv_b=ops.pack_vec(qkv_b, dtype, device),
                 proj_w=ops.pack_weight(self.proj.weight, dtype, device),
                 proj_b=ops.pack_vec(self.proj.bias, dtype, device))
             if qk:

@@ -41,7 +41,7 @@ import torch.nn as nn
 
 from .. import _native as nat
 from .. import ops
-from .attention import RAJNIAttention, qk_norm_modules
+from .attention import RAJNIAttention, qk_norm_modules, qkv_form, packed_qkv
 
 
 class PlanRefs(NamedTuple):
@@ -66,6 +66,7 @@ class PlanInput(NamedTuple):
     nrm: object = None   # rajni_vit_norm
     rop: object = None   # rajni_vit_rope
     rot: object = None   # the (cos, sin) tensors that record points to: a plan owns what it points to, whatever the cache evicts
+    mln: object = None   # (rajni_vit_mlp_norm, the two pointer arrays it points to)
 
 
 class PlanEntry(NamedTuple):
@@ -82,15 +83,16 @@ class PlanEntry(NamedTuple):
 
 
 # The native entry points, narrowest first: each takes the records of the one in front of it and one more, and a call goes
-# through the one that takes the widest record it has - a rope record: _rope, else a norm record: _norm, else a pool record: _pool, else a query record: _query, else an image
+# through the one that takes the widest record it has - an mlp-norm record: _mlpnorm, else a rope record: _rope, else a norm record: _norm, else a pool record: _pool, else a query record: _query, else an image
 # record: _image, else layers: _layers, else prefix: _ext_prefix, else ext: _ext, else the plain one.  (The symbol is part of
 # the interface: nat.check puts it into the error message.)
 _FORWARDS = ("rajni_vit_forward", "rajni_vit_forward_ext", "rajni_vit_forward_ext_prefix", "rajni_vit_forward_layers",
              "rajni_vit_forward_image", "rajni_vit_forward_query", "rajni_vit_forward_pool",
-             "rajni_vit_forward_norm", "rajni_vit_forward_rope")                            # (ext, pre, lay, img, qry, apr, nrm, rop)
+             "rajni_vit_forward_norm", "rajni_vit_forward_rope", "rajni_vit_forward_mlpnorm")   # (ext, pre, lay, img, qry, apr, nrm, rop, mln)
 _SIZES = ("rajni_vit_workspace_bytes", "rajni_vit_workspace_bytes_prefix", "rajni_vit_workspace_bytes_image",
           "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_pool",
-          "rajni_vit_workspace_bytes_norm", "rajni_vit_workspace_bytes_rope")               # (pre, img, qry, apr, nrm, rop)
+          "rajni_vit_workspace_bytes_norm", "rajni_vit_workspace_bytes_rope",
+          "rajni_vit_workspace_bytes_mlpnorm")                                              # (pre, img, qry, apr, nrm, rop, mln)
 NORM_MAX_C = 2048      # the row kernels hold a row in one wave's registers: C <= 64 lanes * 4 chunks * 8 elements
 
 
@@ -388,8 +390,8 @@ def gated_mlp_form(mlp: nn.Module) -> Optional[str]:
     """None for a plain MLP (fc1 -> act -> fc2); "packed" for timm's GluMlp layout - ONE fc1 whose output is twice fc2's
     input, chunked into (x1, x2) - and "split" for timm's SwiGLU layout (fc1_g and fc1_x).  Recognised by structure, not by
     class name.  Raises NotImplementedError for a gated MLP the native forward does not compute: a gate other than SiLU
-    (GELU-gated GEGLU and the like), or an active `norm` between the gate and fc2.  (A plain Mlp whose act is SiLU is not
-    gated: classify_mlp_act refuses it as before.)"""
+    (GELU-gated GEGLU and the like).  (A plain Mlp whose act is SiLU is not gated: classify_mlp_act refuses it as before.  A
+    `norm` between the gate and fc2 is mlp_norm_module's.)"""
     fc1, fc2 = getattr(mlp, "fc1", None), getattr(mlp, "fc2", None)
     fc1_g, fc1_x = getattr(mlp, "fc1_g", None), getattr(mlp, "fc1_x", None)
     if isinstance(fc1_g, nn.Linear) and isinstance(fc1_x, nn.Linear) and isinstance(fc2, nn.Linear):
@@ -405,10 +407,36 @@ def gated_mlp_form(mlp: nn.Module) -> Optional[str]:
     if not _is_silu(act):
         raise NotImplementedError(f"{name}: a gated MLP is supported with the SiLU gate only (SwiGLU), t * sigmoid(t); its act "
                                   f"{type(act).__name__} computes something else")
-    norm = getattr(mlp, "norm", None)
-    if norm is not None and not isinstance(norm, nn.Identity):
-        raise NotImplementedError(f"{name}: mlp.norm ({type(norm).__name__}) between the gate and fc2 is not supported")
     return form
+
+
+def mlp_norm_module(mlp: nn.Module) -> Optional[nn.Module]:
+    """the norm between an MLP's activation (or gate) and fc2 - timm `Mlp.norm` / `SwiGLU.norm` / `GluMlp.norm`, EVA02's
+    sub-LayerNorm - or None where there is none (no attribute, None or nn.Identity)"""
+    norm = getattr(mlp, "norm", None)
+    return None if norm is None or isinstance(norm, nn.Identity) else norm
+
+
+def block_layer_scales(blk: nn.Module, where: str):
+    """(gamma of the attention branch, gamma of the MLP branch), each a [C] tensor or None, in either spelling: timm Block's
+    `ls1` / `ls2` (Identity, or a LayerScale with `.gamma`) or timm EvaBlock's `gamma_1` / `gamma_2` (a parameter or None), the
+    second taken where the first is absent.  A block with both spellings is refused."""
+    out = []
+    for ls_name, g_name in (("ls1", "gamma_1"), ("ls2", "gamma_2")):
+        has_ls, has_g = hasattr(blk, ls_name), hasattr(blk, g_name)
+        if has_ls and has_g:
+            raise NotImplementedError(f"{where}: both {ls_name} and {g_name}: one spelling of LayerScale per block")
+        if has_g:
+            g = getattr(blk, g_name)
+            if g is not None and not (isinstance(g, torch.Tensor) and g.dim() == 1):
+                raise NotImplementedError(f"{where}: {g_name} must be a [C] parameter or None")
+            out.append(g)
+            continue
+        ls = getattr(blk, ls_name, None)
+        if ls is not None and not isinstance(ls, nn.Identity) and not hasattr(ls, "gamma"):
+            raise NotImplementedError(f"{ls_name} must be Identity or a LayerScale with .gamma")
+        out.append(ls.gamma if (ls is not None and hasattr(ls, "gamma")) else None)
+    return out[0], out[1]
 
 
 def gated_fc1(mlp: nn.Module, form: str):
@@ -685,6 +713,10 @@ class RAJNIViTWrapper(nn.Module):
             raise NotImplementedError('set_weight_format("fp8_mfma"): not supported on a model with rotary position embeddings '
                                       '(model.rope): the e4m3 attention and its bounds were fitted to unrotated q and k ("fp8" '
                                       'weights work)')
+        if fmt == "fp8_mfma" and any(mlp_norm_module(blk.mlp) is not None for blk in self.blocks):
+            raise NotImplementedError('set_weight_format("fp8_mfma"): not supported on a model with a norm inside the MLP (mlp.norm): '
+                                      'the fp8 x fp8 FC1 epilogue scales the hidden rows for FC2 before the norm could run ("fp8" '
+                                      'weights work)')
         if fmt == "fp8_mfma" and self._mlp_act_or_none() == "quick_gelu":
             raise NotImplementedError('set_weight_format("fp8_mfma"): the model\'s MLPs use QuickGELU; the fp8 x fp8 FC1 epilogue '
                                       'and its hidden-activation bound are exact GELU only ("fp8" weights work)')
@@ -721,6 +753,10 @@ class RAJNIViTWrapper(nn.Module):
                     w = w[:hid]               # rows / columns past the model's MLP width are zero padding
                 elif ours == "fc2":
                     w = w[:, :hid]
+                elif ours == "qkv" and qkv_form(self.blocks[i].attn) == "split":      # keyed like the base model here too
+                    for name, part in zip(("q_proj", "k_proj", "v_proj"), w.chunk(3)):
+                        out[f"blocks.{i}.attn.{name}.weight"] = part
+                    continue
                 out[f"blocks.{i}.{theirs}.weight"] = w
         return out
 
@@ -872,9 +908,30 @@ class RAJNIViTWrapper(nn.Module):
                 raise NotImplementedError(f"block {i}: {e}") from None
             if desc.setdefault("mlp_act", kind) != kind:
                 raise NotImplementedError(f"block {i}: mlp.act differs between blocks ({kind} after {desc['mlp_act']})")
-            mlp_norm = getattr(blk.mlp, "norm", None)
-            if mlp_norm is not None and not isinstance(mlp_norm, nn.Identity):
-                raise NotImplementedError(f"block {i}: mlp.norm is not supported")
+            # the norm inside the MLP (rajni_vit_mlp_norm): in every block or in none, of the model's one kind, with one eps
+            mlp_norm = mlp_norm_module(blk.mlp)
+            if i == 0:
+                desc["mlp_norm"] = mlp_norm is not None
+            if (mlp_norm is not None) != desc["mlp_norm"]:
+                which = f"mlp.norm ({type(mlp_norm).__name__})" if mlp_norm is not None else "no mlp.norm"
+                raise NotImplementedError(f"block {i}: {type(blk.mlp).__name__}: {which} where block 0 has "
+                                          f"{'one' if desc['mlp_norm'] else 'none'}: a norm inside the MLP in every block or in none")
+            if mlp_norm is not None:
+                try:
+                    kind = classify_norm(mlp_norm, desc["hidden"])
+                except NotImplementedError as e:
+                    raise NotImplementedError(f"RAJNIViTWrapper: blocks.{i}.mlp.norm: {e}") from None
+                if kind != desc["norm_kind"]:
+                    raise NotImplementedError(f"RAJNIViTWrapper: blocks.{i}.mlp.norm is {kind} but blocks.0.norm1 is "
+                                              f"{desc['norm_kind']}: mixed norm kinds in one model are not supported")
+                if float(mlp_norm.eps) != desc.setdefault("mlp_norm_eps", float(mlp_norm.eps)):
+                    raise NotImplementedError(f"RAJNIViTWrapper: blocks.{i}.mlp.norm has eps {float(mlp_norm.eps)} but blocks.0.mlp.norm "
+                                              f"has {desc['mlp_norm_eps']}: the norms inside the MLPs share one eps")
+            try:      # the spellings of the block: LayerScale and the q / k / v projection
+                block_layer_scales(blk, f"block {i}")
+                qkv_form(blk.attn, f"block {i}")
+            except NotImplementedError as e:
+                raise NotImplementedError(f"RAJNIViTWrapper: {e}") from None
             qk = qk_norm_modules(blk.attn, f"block {i}")
             if i == 0:
                 desc["qk_norm"] = qk is not None
@@ -885,6 +942,12 @@ class RAJNIViTWrapper(nn.Module):
                 raise NotImplementedError(f"block {i}: attn.q_norm must be nn.LayerNorm over the head dim {desc['D']}")
             if blk.attn.num_heads != heads or float(blk.attn.scale) != desc["scale"]:
                 raise NotImplementedError(f"block {i}: heads/scale differ between blocks")
+        if desc["mlp_norm"] and desc["hidden"] > nat.HIDDEN_NORM_MAX:
+            raise NotImplementedError(f"RAJNIViTWrapper: mlp.norm over an MLP width of {desc['hidden']}: the row kernel holds a row "
+                                      f"in one wave's registers and takes up to {nat.HIDDEN_NORM_MAX} columns")
+        if desc["mlp_norm"] and self._weight_format == "fp8_mfma":      # (the norm was attached after the setter)
+            raise NotImplementedError('weight format "fp8_mfma" on a model with a norm inside the MLP (mlp.norm) is not supported; '
+                                      '"fp8" weights work')
         # timm's head: norm -> pool -> fc_norm -> head, `norm` and `fc_norm` each an affine LayerNorm or Identity
         desc["pool"] = self._pool_kind()
         # the attention pool of global_pool='map' (None for every other head): its heads, its MLP's width and activation
@@ -1073,17 +1136,13 @@ class RAJNIViTWrapper(nn.Module):
         blocks = []
         for blk in self.blocks:
             a = blk.attn
-            ls1 = getattr(blk, "ls1", None)
-            ls2 = getattr(blk, "ls2", None)
-            g1 = pv(ls1.gamma) if (ls1 is not None and hasattr(ls1, "gamma")) else None
-            g2 = pv(ls2.gamma) if (ls2 is not None and hasattr(ls2, "gamma")) else None
-            for ls, nm in ((ls1, "ls1"), (ls2, "ls2")):
-                if ls is not None and not isinstance(ls, nn.Identity) and not hasattr(ls, "gamma"):
-                    raise NotImplementedError(f"{nm} must be Identity or a LayerScale with .gamma")
+            g1, g2 = (pv(g) for g in block_layer_scales(blk, "RAJNIViTWrapper"))
             for dp in (getattr(blk, "drop_path1", None), getattr(blk, "drop_path2", None)):
                 if dp is not None and not isinstance(dp, nn.Identity) and self.training:
                     raise NotImplementedError("drop_path in training mode: this is the inference path")
-            (qkv_w, qkv_s), (proj_w, proj_s) = pq(a.qkv.weight), pq(a.proj.weight)
+            # (q_proj / k_proj / v_proj, or a bias-free qkv beside q_bias / v_bias: packed here, once, into the one [3C, C] weight)
+            qkv_weight, qkv_bias = packed_qkv(a)
+            (qkv_w, qkv_s), (proj_w, proj_s) = pq(qkv_weight), pq(a.proj.weight)
             # An MLP width that is not whole 64-wide K steps (so400m: 4304) is zero-padded: fc1 gets zero rows (it
             # has them anyway, up to the next 256) with zero bias, GELU(0) = 0 (QuickGELU(0) = 0 alike) lands in the padding columns of the
             # hidden buffer, and fc2's zero-padded input columns ignore them - exact, no kernel involved.
@@ -1114,11 +1173,14 @@ class RAJNIViTWrapper(nn.Module):
                     fc1_b = torch.cat([fc1_b, zeros(hpad - hid)])
             blocks.append(dict(
                 norm1_w=pv(blk.norm1.weight), norm1_b=nb(blk.norm1),
-                qkv_w=qkv_w, qkv_s=qkv_s, qkv_b=pv(a.qkv.bias) if a.qkv.bias is not None else zeros(3 * desc["C"]),
+                qkv_w=qkv_w, qkv_s=qkv_s, qkv_b=pv(qkv_bias) if qkv_bias is not None else zeros(3 * desc["C"]),
                 proj_w=proj_w, proj_s=proj_s, proj_b=pv(a.proj.bias) if a.proj.bias is not None else zeros(desc["C"]),
                 ls1=g1, norm2_w=pv(blk.norm2.weight), norm2_b=nb(blk.norm2),
                 fc1_w=fc1_w, fc1_s=fc1_s, fc1_b=fc1_b,
                 fc2_w=fc2_w, fc2_s=fc2_s, fc2_b=pv(blk.mlp.fc2.bias), ls2=g2))
+            if desc["mlp_norm"]:      # rajni_vit_mlp_norm: [hidden] fp32, the true width (no bias vector for the RMS kind)
+                mn = mlp_norm_module(blk.mlp)
+                blocks[-1].update(mlp_norm_w=pv(mn.weight), mlp_norm_b=nb(mn))
             if desc["qk_norm"]:
                 q, k = qk_norm_modules(a)
                 blocks[-1].update(q_norm_w=pv(q.weight), q_norm_b=pv(q.bias), k_norm_w=pv(k.weight), k_norm_b=pv(k.bias))
@@ -1289,12 +1351,20 @@ class RAJNIViTWrapper(nn.Module):
             rop.head_stride = gh * gw * d["D"] if d["rope"] != "shared" else 0
             rop.block_stride = d["H"] * gh * gw * d["D"] if d["rope"] == "per_block" else 0
             rop.layout = nat.ROPE_HALF if d["rope_half"] else nat.ROPE_INTERLEAVED
-        symbol, records = _native_call(_SIZES, pre, img, qry, apr, nrm, rop)
+        mln = None
+        if d["mlp_norm"]:         # the mlp-norm record beside the plan (rajni_vit_mlp_norm); None: the entry points as ever
+            rec = nat.VitMlpNorm()
+            mw = (C.c_void_p * d["depth"])(*[bw["mlp_norm_w"].data_ptr() for bw in W["blocks"]])
+            mb = (C.c_void_p * d["depth"])(*[nat.ptr(bw["mlp_norm_b"]) for bw in W["blocks"]])
+            rec.w, rec.b, rec.eps, rec.n = mw, mb, d["mlp_norm_eps"], d["hidden"]
+            mln = (rec, mw, mb)
+        mrec = mln[0] if mln else None
+        symbol, records = _native_call(_SIZES, pre, img, qry, apr, nrm, rop, mrec)
         nbytes = getattr(nat.lib(), symbol)(C.byref(plan), *records)
         if nbytes == 0 and symbol not in _SIZES[:2]:
-            # the image, query, pool, norm or rope record is refused: say why (the forward's own refusal; nothing is launched)
+            # the image, query, pool, norm, rope or mlp-norm record is refused: say why (the forward's own refusal; nothing is launched)
             dry = nat.VitExt(pool=nat.POOL_MAP) if apr is not None else None
-            forward, records = _native_call(_FORWARDS, dry, pre, None, img, qry, apr, nrm, rop)
+            forward, records = _native_call(_FORWARDS, dry, pre, None, img, qry, apr, nrm, rop, mrec)
             nat.check(getattr(nat.lib(), forward)(C.byref(plan), *records, 16, 16, None), forward)
             raise nat.NativeError(f"{symbol} refused the plan")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
@@ -1327,7 +1397,7 @@ class RAJNIViTWrapper(nn.Module):
             cap_arr = (C.c_int * len(caps))(*caps)
             layers = (cap_arr, int(lnorm), int(lfill == "last"), (len(caps), B, n0, d["C"]))
         self._plan = PlanEntry(key, plan, PlanRefs(blocks, tc, ws, W, ext, qk, pre), bufs, counts, full_mode, out_shape, layers,
-                               PlanInput(img, pos, gh, gw, qry, apr, nrm, rop, rot))
+                               PlanInput(img, pos, gh, gw, qry, apr, nrm, rop, rot, mln))
         if len(self._plans) >= 4:     # workspaces are large: keep only a few batch shapes alive
             self._plans.pop(next(iter(self._plans)))
         self._plans[key] = self._plan
@@ -1493,7 +1563,8 @@ class RAJNIViTWrapper(nn.Module):
                     lay = nat.VitLayers()
                     lay.n, lay.blocks, lay.norm, lay.fill, lay.out, lay.slab_stride = len(cap_arr), cap_arr, lnorm, lfill, slabs.data_ptr(), 0
                 symbol, records = _native_call(_FORWARDS, entry.refs.ext, entry.refs.pre, lay, entry.input.img, entry.input.qry,
-                                               entry.input.apr, entry.input.nrm, entry.input.rop)
+                                               entry.input.apr, entry.input.nrm, entry.input.rop,
+                                               entry.input.mln[0] if entry.input.mln else None)
                 nat.check(getattr(nat.lib(), symbol)(C.byref(entry.plan), *records, x.data_ptr(), out.data_ptr(),
                                                      nat.stream_ptr(x.device)), symbol)
                 return out if lay is None else (out, slabs)
