@@ -17,7 +17,7 @@ def needs_build():
         return True
     t = os.path.getmtime(OUT)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h)
-                                                               for h in ("rajni_hip.h", "rajni_hip_debug.h", "rajni_hip_layers.h", "rajni_hip_image.h", "rajni_hip_query.h", "rajni_hip_attnpool.h", "rajni_hip_norm.h", "rajni_hip_rope.h", "rajni_hip_mlpnorm.h")]
+                                                               for h in ("rajni_hip.h", "rajni_hip_debug.h", "rajni_hip_layers.h", "rajni_hip_image.h", "rajni_hip_query.h", "rajni_hip_attnpool.h", "rajni_hip_norm.h", "rajni_hip_rope.h", "rajni_hip_mlpnorm.h", "rajni_hip_relpos.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -37,6 +37,46 @@ struct AttnArgs {
   float oinv, oscale;
   float* row_scale;
 };
+// the argument of the instantiations with a relative position bias (rajni_hip_relpos.h): AttnArgs itself keeps its size, so no
+// kernel that takes it changes (tools/isa_identity.py)
+struct AttnArgsRB : AttnArgs { RelBias rb; };
+__device__ __forceinline__ const RelBias* rb_of(const AttnArgs&) { return nullptr; }
+__device__ __forceinline__ const RelBias* rb_of(const AttnArgsRB& a) { return &a.rb; }
+
+// ---- relative position bias (rajni_hip_relpos.h).  A token's code is y * (2 gw - 1) + x of its patch, or -1 for a prefix row
+// (and for a padding row past np); the table index of a (query, key) pair of patches is code_q - code_k + center.  A patch
+// position past the grid is clamped to the last patch, so no index leaves the table.
+// The bias joins S in the units of q . k: S' = S + bias * (1 / scale), so that scale * S' is the biased logit and the softmax code
+// behind it is the code without a bias, untouched (a zero bias adds +0: the same bits).  Roundings: 1 / scale (host, exact for a
+// power of two), the product, the add.
+constexpr float RB_LOG2E = 1.4426950408889634f;
+__device__ __forceinline__ int rb_code(const RelBias& rb, const int* posb, int t, int np) {
+  if (t >= np) return -1;
+  const int p0 = (posb ? posb[t] : t) - rb.P;
+  if (p0 < 0) return -1;
+  const int p = p0 < rb.npatch ? p0 : rb.npatch - 1;
+  const int y = p / rb.gw;
+  return y * (2 * rb.gw - 1) + (p - y * rb.gw);
+}
+// what a lane (= one query) needs for its row of the bias: its own code and the three prefix values of its head
+struct RbRow {
+  const float* tab; int base; bool qpre; float sp_k, sp_q, inv;
+  __device__ __forceinline__ RbRow() : tab(nullptr), base(0), qpre(false), sp_k(0.f), sp_q(0.f), inv(0.f) {}
+  __device__ __forceinline__ RbRow(const RelBias& rb, int head, int cq) {
+    tab = rb.table + (size_t)head * rb.T;
+    qpre = cq < 0;
+    base = cq + rb.center;
+    inv = rb.inv_scale;
+    sp_k = (qpre ? rb.pqk[head] : rb.pk[head]) * inv;   // the key is a prefix row
+    sp_q = rb.pq[head] * inv;                           // the query is one, the key a patch
+  }
+  // the bias against a key of code ck, over scale
+  __device__ __forceinline__ float operator()(int ck) const {
+    const bool kpre = ck < 0;
+    const float v = tab[(kpre || qpre) ? 0 : base - ck] * inv;
+    return kpre ? sp_k : qpre ? sp_q : v;
+  }
+};
 __device__ __forceinline__ unsigned attn_pack4_e4m3(float a, float b, float c, float d) {   // saturating RNE (gemm_f8.h)
   a = __builtin_amdgcn_fmed3f(a, -448.f, 448.f); b = __builtin_amdgcn_fmed3f(b, -448.f, 448.f);
   c = __builtin_amdgcn_fmed3f(c, -448.f, 448.f); d = __builtin_amdgcn_fmed3f(d, -448.f, 448.f);
@@ -64,11 +104,20 @@ __device__ __forceinline__ bf16x8 tr_pair(const char* sv, int row, int col) {
 }
 
 // A: the 16-bit operand format of every kernel below (bf16_t or f16_t: the MFMA form and the rounding of P and O)
-template <typename A = bf16_t>
-__global__ void __launch_bounds__(AT_THREADS) attn_bf16_d64(const AttnArgs a) {
+// RB: a relative position bias is added to S (before the block maximum: the running maximum sees biased logits)
+// (Args = AttnArgsRB; a template parameter, so that the instantiations without a bias are the code they were)
+template <typename A = bf16_t, typename Args = AttnArgs>
+__global__ void __launch_bounds__(AT_THREADS) attn_bf16_d64(const Args a) {
+  constexpr bool RB = !__is_same(Args, AttnArgs);
+  const RelBias* const rbp = rb_of(a);
   __shared__ __attribute__((aligned(16))) char smem[AT_LDS];
   char* sk = smem;
   char* sv = smem + KV_CHUNK * 128;
+  int* scode = nullptr;             // RB: the codes of the chunk's 128 keys
+  if constexpr (RB) {
+    __shared__ __attribute__((aligned(16))) int scode_[KV_CHUNK];
+    scode = scode_;
+  }
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int l31 = lane & 31, h = lane >> 5, g = lane >> 4, l15 = lane & 15;
   const int head = blockIdx.y, b = blockIdx.z;
@@ -78,12 +127,16 @@ __global__ void __launch_bounds__(AT_THREADS) attn_bf16_d64(const AttnArgs a) {
 
   const int qbase = blockIdx.x * AT_QROWS + wave * 32;
   const bool active = qbase < (a.nq < np ? a.nq : np);
+  const int* posb = nullptr;
+  if constexpr (RB) posb = rbp->pos ? rbp->pos + (long)b * np : nullptr;
+  int cq = 0;
 
   // ---- Q fragments straight from HBM (B operand: lane holds Q[q = l31][d = 16s + 8h .. +7])
   bf16x8 qf[4];
   {
     int q = qbase + l31;
     if (q > np - 1) q = np - 1;
+    if constexpr (RB) cq = rb_code(*rbp, posb, q, np);
     const int srow = idx ? idx[q] : q;
     const bf16_t* qp = img + (long)srow * C3 + head * 64 + 8 * h;
 #pragma unroll
@@ -96,6 +149,8 @@ __global__ void __launch_bounds__(AT_THREADS) attn_bf16_d64(const AttnArgs a) {
   float m_run = -INFINITY, l_run = 0.f;
 
   const int st_c = tid & 7, st_r = tid >> 3;  // staging: 8 threads per 128-byte row, 32 rows per pass
+  RbRow row;
+  if constexpr (RB) row = RbRow(*rbp, head, cq);
 
   for (int c0 = 0; c0 < np; c0 += KV_CHUNK) {
     // ---- stage K and V rows c0 .. c0+127 (gathered through keep_idx), zero-fill past np
@@ -120,6 +175,9 @@ __global__ void __launch_bounds__(AT_THREADS) attn_bf16_d64(const AttnArgs a) {
       *reinterpret_cast<uint4*>(sk + k_off(row, st_c)) = kreg[i];
       *reinterpret_cast<uint4*>(sv + v_off(row, st_c)) = vreg[i];
     }
+    if constexpr (RB) {
+      if (tid < KV_CHUNK) scode[tid] = rb_code(*rbp, posb, c0 + tid, np);
+    }
     __syncthreads();
 
     if (active) {
@@ -134,6 +192,16 @@ __global__ void __launch_bounds__(AT_THREADS) attn_bf16_d64(const AttnArgs a) {
         for (int ks = 0; ks < 4; ++ks) {
           const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sk + k_off(krow, 2 * ks + h));
           s = mfma_32x32x16<A>(kf, qf[ks], s);
+        }
+        if constexpr (RB) {   // S + bias / scale: everything below runs on the biased S as it does on S
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int4 c4 = *reinterpret_cast<const int4*>(scode + kb * 32 + 8 * j + 4 * h);
+            s[4 * j + 0] += row(c4.x);
+            s[4 * j + 1] += row(c4.y);
+            s[4 * j + 2] += row(c4.z);
+            s[4 * j + 3] += row(c4.w);
+          }
         }
         const int nvalid = np - c0 - kb * 32;  // keys of this sub-block that exist
         if (nvalid < 32) {
@@ -235,10 +303,11 @@ constexpr bool stage_o(int nsub) { return (RAJNI_ATTN_STAGE_MASK >> (nsub - 1)) 
 // layout a lane owns 8 bytes of 8 different rows per instruction: 32 partial cache lines each, which backed
 // up the vector-memory queue - the NEXT item's prefetch then stalled at issue (tools/attn_stamps.py:
 // prefetch issue 2.5k + stores 1.7k of 11k cycles per item).
-template <typename A, int NSUB, bool O8 = false>
+// RB: scode holds the codes of all NSUB * 32 staged rows (rb_code), and the bias is added to S before the row maximum
+template <typename A, int NSUB, bool O8 = false, bool RB = false>
 __device__ __forceinline__ void attn_tile_compute(const char* sk, const char* sv, const bf16x8 (&qf)[4],
                                                   const AttnArgs& a, int b, int head, int qbase, int lane,
-                                                  char* so = nullptr) {
+                                                  char* so = nullptr, const int* scode = nullptr, const RelBias* rbp = nullptr) {
   const int l31 = lane & 31, h = lane >> 5, g = lane >> 4, l15 = lane & 15;
   const int np = a.np, C = a.H * 64;
   // ---- S^T = K Q^T for every 32-key block
@@ -258,6 +327,19 @@ __device__ __forceinline__ void attn_tile_compute(const char* sk, const char* sv
   asm volatile("" :: "v"(s[0][0]), "v"(s[NSUB - 1][15]));
   const unsigned long long tsS = __builtin_amdgcn_s_memtime();
 #endif
+  if constexpr (RB) {   // S + bias / scale: everything below runs on the biased S as it does on S
+    const RbRow row(*rbp, head, scode[qbase + l31 < np ? qbase + l31 : np - 1]);
+#pragma unroll
+    for (int kb = 0; kb < NSUB; ++kb)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int4 c4 = *reinterpret_cast<const int4*>(scode + kb * 32 + 8 * j + 4 * h);
+        s[kb][4 * j + 0] += row(c4.x);
+        s[kb][4 * j + 1] += row(c4.y);
+        s[kb][4 * j + 2] += row(c4.z);
+        s[kb][4 * j + 3] += row(c4.w);
+      }
+  }
   // mask the keys past np (only in the last block)
   {
     const int nvalid = np - (NSUB - 1) * 32;
@@ -390,12 +472,15 @@ __device__ __forceinline__ void attn_tile_compute(const char* sk, const char* sv
   }
 }
 
-template <int NSUB, typename A = bf16_t>
-__global__ void __launch_bounds__(ATF_THREADS, 2) attn_bf16_d64_full(const AttnArgs a) {
+// RB: ROWS * 4 more bytes of LDS behind V hold the rows' codes
+template <int NSUB, typename A = bf16_t, typename Args = AttnArgs>
+__global__ void __launch_bounds__(ATF_THREADS, 2) attn_bf16_d64_full(const Args a) {
+  constexpr bool RB = !__is_same(Args, AttnArgs);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int ROWS = NSUB * 32;
   char* sk = smem;
   char* sv = smem + ROWS * 128;
+  int* scode = reinterpret_cast<int*>(smem + ROWS * 256);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int l31 = lane & 31, h = lane >> 5, g = lane >> 4, l15 = lane & 15;
   const int head = blockIdx.x, b = blockIdx.y;
@@ -433,10 +518,15 @@ __global__ void __launch_bounds__(ATF_THREADS, 2) attn_bf16_d64_full(const AttnA
         *reinterpret_cast<uint4*>(sv + v_off(t, st_c)) = vr;
       }
     }
+    if constexpr (RB) {
+      const RelBias& rb = *rb_of(a);
+      if (tid < ROWS) scode[tid] = rb_code(rb, rb.pos ? rb.pos + (long)b * np : nullptr, tid, np);
+    }
   }
   __syncthreads();
   if (!active) return;
-  attn_tile_compute<A, NSUB>(sk, sv, qf, a, b, head, qbase, lane);
+  if constexpr (RB) attn_tile_compute<A, NSUB, false, true>(sk, sv, qf, a, b, head, qbase, lane, nullptr, scode, rb_of(a));
+  else attn_tile_compute<A, NSUB>(sk, sv, qf, a, b, head, qbase, lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -609,10 +699,22 @@ struct AttnArgsF32 {
   float c;
   int nq;           // as in AttnArgs (the launch's grid.x covers nq rows)
 };
+struct AttnArgsF32RB : AttnArgsF32 { RelBias rb; };
+__device__ __forceinline__ const RelBias* rb_of(const AttnArgsF32&) { return nullptr; }
+__device__ __forceinline__ const RelBias* rb_of(const AttnArgsF32RB& a) { return &a.rb; }
 
-__global__ void __launch_bounds__(256) attn_f32_d64(const AttnArgsF32 a) {
+// Args = AttnArgsF32RB: a relative position bias on the logit
+template <typename Args = AttnArgsF32>
+__global__ void __launch_bounds__(256) attn_f32_d64(const Args a) {
+  constexpr bool RB = !__is_same(Args, AttnArgsF32);
+  const RelBias* const rbp = rb_of(a);
   __shared__ __attribute__((aligned(16))) float sk[64 * 64];
   __shared__ __attribute__((aligned(16))) float sv[64 * 64];
+  int* scode = nullptr;             // RB: the codes of the chunk's 64 keys
+  if constexpr (RB) {
+    __shared__ int scode_[64];
+    scode = scode_;
+  }
   const int tid = threadIdx.x;
   const int qrow = tid >> 2, pt = tid & 3;           // 64 query rows x 4 lanes
   const int head = blockIdx.y, b = blockIdx.z;
@@ -622,6 +724,12 @@ __global__ void __launch_bounds__(256) attn_f32_d64(const AttnArgsF32 a) {
   int q = blockIdx.x * 64 + qrow;
   const bool valid = q < np;
   if (!valid) q = np - 1;
+  const int* posb = nullptr;
+  RbRow row;
+  if constexpr (RB) {
+    posb = rbp->pos ? rbp->pos + (long)b * np : nullptr;
+    row = RbRow(*rbp, head, rb_code(*rbp, posb, q, np));
+  }
   float qv[16], o[16];
   {
     const int srow = idx ? idx[q] : q;
@@ -653,6 +761,9 @@ __global__ void __launch_bounds__(256) attn_f32_d64(const AttnArgsF32 a) {
       reinterpret_cast<float4*>(sk)[e] = kq;
       reinterpret_cast<float4*>(sv)[e] = vq;
     }
+    if constexpr (RB) {
+      if (tid < 64) scode[tid] = rb_code(*rbp, posb, c0 + tid, np);
+    }
     __syncthreads();
     const int nk = np - c0 < 64 ? np - c0 : 64;
     for (int j = 0; j < nk; ++j) {
@@ -662,6 +773,7 @@ __global__ void __launch_bounds__(256) attn_f32_d64(const AttnArgsF32 a) {
       for (int e = 0; e < 16; ++e) d = fmaf(qv[e], kr[e], d);
       d += __shfl_xor(d, 1, 64);
       d += __shfl_xor(d, 2, 64);
+      if constexpr (RB) d += row(scode[j]);
       const float sc = d * a.c;
       const float m_new = fmaxf(m_run, sc);
       const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
@@ -1142,7 +1254,7 @@ int launch_attention(const void* qkv, const int32_t* keep_idx, void* out, int B,
     f.n_src = n_src; f.np = np; f.H = H; f.c = scale * 1.4426950408889634f; f.nq = nq;
     ProfScope prof(KC_ATTENTION, s, 4.0 * B * H * (double)nq * np * D, 4.0 * B * kv_q_o * H * D);
     const dim3 grid((nq + 63) / 64, H, B);
-    if (D == 64) hipLaunchKernelGGL(attn_f32_d64, grid, dim3(256), 0, s, f);
+    if (D == 64) hipLaunchKernelGGL(attn_f32_d64<AttnArgsF32>, grid, dim3(256), 0, s, f);
     else if (D < 64) hipLaunchKernelGGL(attn_f32_dgen<16>, grid, dim3(256), 0, s, f, D);
     else hipLaunchKernelGGL(attn_f32_dgen<32>, grid, dim3(256), 0, s, f, D);
     RAJNI_CHECK_LAUNCH("attn_f32");
@@ -1160,6 +1272,93 @@ int launch_attention(const void* qkv, const int32_t* keep_idx, void* out, int B,
   const int rc = dtype == RAJNI_F16 ? launch_attention16<f16_t>(a, B, np, H, D, s) : launch_attention16<bf16_t>(a, B, np, H, D, s);
   if (rc != RAJNI_OK) return rc;
   RAJNI_CHECK_LAUNCH("attn_bf16_d64");
+  return RAJNI_OK;
+}
+
+// ---- attention with a relative position bias (rajni_hip_relpos.h): head dim 64.  np <= 256: the one-shot kernel with the
+// rows' codes behind V in LDS (the persistent kernel's prefetch pipeline carries no codes: a bias launch never takes it, so
+// rajni_debug_force_attention modes 0 and 2 launch the same kernel here); larger np, or mode 1: the chunked kernel; fp32: attn_f32_d64<AttnArgsF32RB>.
+namespace {
+template <int NSUB, typename A>
+int launch_full_rb(const AttnArgsRB& a, int B, hipStream_t s) {
+  constexpr int lds = NSUB * 32 * 256 + NSUB * 32 * 4;
+  if (lds > 64 * 1024) {
+    static bool attr_by_device[RAJNI_MAX_DEVICES] = {};
+    bool& attr = attr_by_device[rajni_current_device()];
+    if (!attr) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bf16_d64_full<NSUB, A, AttnArgsRB>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      if (e != hipSuccess) { rajni_set_error("hipFuncSetAttribute(attn relpos): %s", hipGetErrorString(e)); return RAJNI_ERR_LAUNCH; }
+      attr = true;
+    }
+  }
+  hipLaunchKernelGGL((attn_bf16_d64_full<NSUB, A, AttnArgsRB>), dim3(a.H, B), dim3(ATF_THREADS), lds, s, a);
+  return RAJNI_OK;
+}
+template <typename A>
+int launch_attention16_rb(const AttnArgsRB& a, int B, int np, hipStream_t s) {
+  const int nsub = (np + 31) / 32;
+  if (nsub <= 8 && g_force_attn != 1) {
+    switch (nsub) {
+      case 1: return launch_full_rb<1, A>(a, B, s);
+      case 2: return launch_full_rb<2, A>(a, B, s);
+      case 3: return launch_full_rb<3, A>(a, B, s);
+      case 4: return launch_full_rb<4, A>(a, B, s);
+      case 5: return launch_full_rb<5, A>(a, B, s);
+      case 6: return launch_full_rb<6, A>(a, B, s);
+      case 7: return launch_full_rb<7, A>(a, B, s);
+      default: return launch_full_rb<8, A>(a, B, s);
+    }
+  }
+  hipLaunchKernelGGL((attn_bf16_d64<A, AttnArgsRB>), dim3((a.nq + AT_QROWS - 1) / AT_QROWS, a.H, B), dim3(AT_THREADS), 0, s, a);
+  return RAJNI_OK;
+}
+}  // namespace
+
+int launch_attention_relpos(const void* qkv, const int32_t* keep_idx, void* out, int B, int n_src, int np, int nq, int H, int D,
+                            float scale, int dtype, const float* table, const float* pq, const float* pk, const float* pqk,
+                            int gh, int gw, int num_prefix, const int32_t* pos, hipStream_t s) {
+  const char* who = "rajni_attention_relpos";
+  RAJNI_REQUIRE(H <= RAJNI_MAX_GRID_YZ && B <= RAJNI_MAX_GRID_YZ, RAJNI_ERR_UNSUPPORTED,
+                "%s: B=%d H=%d - one launch takes at most %d images and %d heads (grid y / z)", who, B, H, RAJNI_MAX_GRID_YZ,
+                RAJNI_MAX_GRID_YZ);
+  RAJNI_REQUIRE(D == 64, RAJNI_ERR_UNSUPPORTED, "%s: a relative position bias with head dim %d - head dim 64 only", who, D);
+  RAJNI_REQUIRE(gh >= 1 && gw >= 1, RAJNI_ERR_INVALID, "%s: bad grid %d x %d", who, gh, gw);
+  RAJNI_REQUIRE(gh <= RAJNI_RELPOS_MAX_GRID && gw <= RAJNI_RELPOS_MAX_GRID, RAJNI_ERR_UNSUPPORTED,
+                "%s: grid %d x %d - a relative position bias takes at most %d x %d patches", who, gh, gw, RAJNI_RELPOS_MAX_GRID,
+                RAJNI_RELPOS_MAX_GRID);
+  RAJNI_REQUIRE(num_prefix >= 0 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID, "%s: num_prefix must be 0..%d (%d)", who,
+                RAJNI_MAX_PREFIX, num_prefix);
+  RAJNI_REQUIRE(qkv && out && table && pq && pk && pqk, RAJNI_ERR_INVALID, "%s: null pointer", who);
+  RAJNI_REQUIRE(scale > 0.f && scale < INFINITY, RAJNI_ERR_INVALID, "%s: scale must be positive and finite (the bias is divided by it)", who);
+  RAJNI_REQUIRE(B > 0 && H > 0 && np > 0 && n_src >= np, RAJNI_ERR_INVALID, "%s: bad shape B=%d H=%d np=%d n_src=%d", who, B, H, np,
+                n_src);
+  RAJNI_REQUIRE(keep_idx != nullptr || np == n_src, RAJNI_ERR_INVALID, "%s: identity selection needs np == n_src", who);
+  RAJNI_REQUIRE(nq >= 1 && nq <= np, RAJNI_ERR_INVALID, "%s: query-row limit nq=%d outside 1..np=%d", who, nq, np);
+  RAJNI_REQUIRE(dtype == RAJNI_BF16 || dtype == RAJNI_F16 || dtype == RAJNI_F32, RAJNI_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+  RelBias rb{};
+  rb.table = table; rb.pq = pq; rb.pk = pk; rb.pqk = pqk; rb.pos = pos;
+  rb.gw = gw; rb.npatch = gh * gw; rb.P = num_prefix;
+  rb.inv_scale = 1.0f / scale;
+  rb.T = (2 * gh - 1) * (2 * gw - 1); rb.center = (gh - 1) * (2 * gw - 1) + (gw - 1);
+  const double kv_q_o = 2.0 * np + 2.0 * nq, es = dtype == RAJNI_F32 ? 4.0 : 2.0;
+  ProfScope prof(KC_ATTENTION, s, 4.0 * B * H * (double)nq * np * D, es * B * kv_q_o * H * D);
+  if (dtype == RAJNI_F32) {
+    AttnArgsF32RB f{};
+    f.qkv = (const float*)qkv; f.idx = keep_idx; f.out = (float*)out;
+    f.n_src = n_src; f.np = np; f.H = H; f.c = scale * RB_LOG2E; f.nq = nq; f.rb = rb;
+    hipLaunchKernelGGL(attn_f32_d64<AttnArgsF32RB>, dim3((nq + 63) / 64, H, B), dim3(256), 0, s, f);
+    RAJNI_CHECK_LAUNCH("attn_f32_d64_rb");
+    return RAJNI_OK;
+  }
+  AttnArgsRB a{};
+  a.qkv = (const bf16_t*)qkv; a.idx = keep_idx; a.out = (bf16_t*)out;
+  a.n_src = n_src; a.np = np; a.H = H; a.nq = nq;
+  a.c = scale * RB_LOG2E;
+  a.rb = rb;
+  const int rc = dtype == RAJNI_F16 ? launch_attention16_rb<f16_t>(a, B, np, s) : launch_attention16_rb<bf16_t>(a, B, np, s);
+  if (rc != RAJNI_OK) return rc;
+  RAJNI_CHECK_LAUNCH("attn_bf16_d64 (relpos)");
   return RAJNI_OK;
 }
 

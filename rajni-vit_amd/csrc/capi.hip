@@ -218,6 +218,47 @@ int rajni_attention(const void* qkv, const int32_t* keep_idx, void* out, int B, 
   return launch_attention(qkv, keep_idx, out, B, n_src, np, np, H, D, scale, dtype, (hipStream_t)stream);
 }
 
+// rajni_attention with a relative position bias (include/rajni_hip_relpos.h)
+int rajni_attention_relpos(const void* qkv, const int32_t* keep_idx, void* out, int B, int n_src, int np, int H, int D, float scale,
+                           int dtype, const float* table, const float* prefix_q, const float* prefix_k, const float* prefix_qk,
+                           int gh, int gw, int num_prefix, const int32_t* pos, rajni_stream_t stream) {
+  NEED_DTYPE("rajni_attention_relpos");
+  RAJNI_REQUIRE_PLACED("rajni_attention_relpos", {"qkv", qkv, 16}, {"keep_idx", keep_idx, 4}, {"out", out, 16}, {"table", table, 4},
+                       {"prefix_q", prefix_q, 4}, {"prefix_k", prefix_k, 4}, {"prefix_qk", prefix_qk, 4}, {"pos", pos, 4});
+  return launch_attention_relpos(qkv, keep_idx, out, B, n_src, np, np, H, D, scale, dtype, table, prefix_q, prefix_k, prefix_qk, gh, gw,
+                                 num_prefix, pos, (hipStream_t)stream);
+}
+
+// rajni_score_select_ws with the class row's relative position bias (include/rajni_hip_relpos.h)
+int rajni_score_select_relpos(const void* qkv, int B, int N, int H, int D, float eps, int num_prefix, int keep, void* scores_out,
+                              int32_t* keep_idx, void* next_scores, int dtype, void* workspace, size_t workspace_bytes,
+                              const float* prefix_q, const float* prefix_qk, rajni_stream_t stream) {
+  const char* who = "rajni_score_select_relpos";
+  NEED_DTYPE("rajni_score_select_relpos");
+  RAJNI_REQUIRE(B <= RAJNI_MAX_GRID_YZ || rajni_score_select_workspace_bytes(B, N, H, D, dtype) == 0, RAJNI_ERR_UNSUPPORTED,
+                "%s: B=%d - one launch of the tiled path takes at most %d images (grid: token tiles x images)", who, B, RAJNI_MAX_GRID_YZ);
+  RAJNI_REQUIRE_PLACED(who, {"qkv", qkv, 16}, {"scores_out", scores_out, rajni_elem_bytes(dtype)}, {"keep_idx", keep_idx, 4},
+                       {"next_scores", next_scores, rajni_elem_bytes(dtype)}, {"workspace", workspace, 256}, {"prefix_q", prefix_q, 4},
+                       {"prefix_qk", prefix_qk, 4});
+  RAJNI_REQUIRE(qkv != nullptr && prefix_q != nullptr && prefix_qk != nullptr, RAJNI_ERR_INVALID, "%s: null pointer", who);
+  RAJNI_REQUIRE(num_prefix >= 1 && num_prefix <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID, "%s: num_prefix must be 1..%d (%d)", who,
+                RAJNI_MAX_PREFIX, num_prefix);
+  RAJNI_REQUIRE(B > 0 && N >= num_prefix + 1, RAJNI_ERR_INVALID,
+                "%s: need B > 0 and at least one patch token (B=%d N=%d num_prefix=%d)", who, B, N, num_prefix);
+  RAJNI_REQUIRE(keep >= 0 && keep <= N - num_prefix, RAJNI_ERR_INVALID, "%s: keep must be 0 (scores only) or 1..%d (%d)", who,
+                N - num_prefix, keep);
+  RAJNI_REQUIRE(keep == 0 || keep_idx != nullptr, RAJNI_ERR_INVALID, "%s: keep_idx is null with keep=%d", who, keep);
+  RAJNI_REQUIRE(keep > 0 || scores_out != nullptr, RAJNI_ERR_INVALID, "%s: scores_out is null with keep=0", who);
+  const size_t need = rajni_score_select_workspace_bytes(B, N, H, D, dtype);
+  RAJNI_REQUIRE(need == 0 || workspace != nullptr, RAJNI_ERR_INVALID,
+                "%s: workspace is null but N=%d H=%d D=%d needs %zu B (rajni_score_select_workspace_bytes)", who, N, H, D, need);
+  RAJNI_REQUIRE(workspace_bytes >= need, RAJNI_ERR_INVALID, "%s: workspace_bytes=%zu but N=%d H=%d D=%d needs %zu B", who,
+                workspace_bytes, N, H, D, need);
+  return launch_score_select(qkv, nullptr, B, N, H, D, eps, keep, scores_out, keep_idx, next_scores, dtype, (hipStream_t)stream,
+                             num_prefix, need ? workspace : nullptr, need ? workspace_bytes : 0, RAJNI_QUERY_CLS, prefix_q, prefix_qk,
+                             num_prefix);
+}
+
 // rajni_attention limited to the query rows [0, nq) (include/rajni_hip_debug.h)
 extern "C" int rajni_debug_attention_rows(const void* qkv, const int32_t* keep_idx, void* out, int B, int n_src, int np, int nq,
                                           int H, int D, float scale, int dtype, rajni_stream_t stream) {

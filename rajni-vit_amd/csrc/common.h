@@ -12,6 +12,7 @@
 #include "../../include/rajni_hip_norm.h"
 #include "../../include/rajni_hip_rope.h"
 #include "../../include/rajni_hip_mlpnorm.h"
+#include "../../include/rajni_hip_relpos.h"
 
 typedef unsigned short bf16_t;  // raw bf16 bits in memory
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -227,6 +228,17 @@ int launch_layernorm_fp8(const void* x, long xs, const float* w, const float* b,
                          float* hscale, float wnorm, float bmax, int rows, int C, float eps, int x_f32, hipStream_t s);
 int launch_attention(const void* qkv, const int32_t* keep_idx, void* out, int B, int n_src, int np, int nq,
                      int H, int D, float scale, int dtype, hipStream_t s);   // nq: query rows [0, nq) only (np = all)
+// a relative position bias on the logits (rajni_hip_relpos.h): one block's table [H][T] and values [H], the positions of the
+// packed rows (null: the row index) and the grid.  A kernel argument of the head-dim-64 and fp32 attention kernels; all zero: none
+struct RelBias {
+  const float* table; const float* pq; const float* pk; const float* pqk;
+  const int32_t* pos;     // [B, np]
+  int gw, npatch, P, center, T;   // grid width, gh * gw, prefix rows, index of (dy, dx) = (0, 0), entries per head
+  float inv_scale;                // 1 / scale: the bias joins q . k in front of the scale
+};
+int launch_attention_relpos(const void* qkv, const int32_t* keep_idx, void* out, int B, int n_src, int np, int nq, int H, int D,
+                            float scale, int dtype, const float* table, const float* pq, const float* pk, const float* pqk,
+                            int gh, int gw, int num_prefix, const int32_t* pos, hipStream_t s);
 int launch_attention_fp8(const void* qkv, const int32_t* keep_idx, void* out_q, float out_scale, float* row_scale,
                          int B, int n_src, int np, int H, int D, float scale, hipStream_t s);
 int launch_attention_cls(const void* qkv, void* out, int B, int N, int H, int D, float scale, int dtype,
@@ -240,7 +252,8 @@ int launch_attention_pool(const void* kv, const float* q, void* out, int B, int 
 int launch_score_select(const void* qkv, const void* scores_in, int B, int N, int H, int D,
                         float eps, int keep, void* scores_out, int32_t* keep_idx,
                         void* next_scores, int dtype, hipStream_t s, int num_prefix = 1, void* ws = nullptr,
-                        size_t ws_bytes = 0, int query = RAJNI_QUERY_CLS);   // RAJNI_QUERY_MEAN: ws sized by rajni_score_select_query_workspace_bytes
+                        size_t ws_bytes = 0, int query = RAJNI_QUERY_CLS, const float* rb_pq = nullptr,
+                        const float* rb_pqk = nullptr, int rb_prefix = 0);   // RAJNI_QUERY_MEAN: ws sized by rajni_score_select_query_workspace_bytes
 int launch_gather_rows(const void* src, const int32_t* idx, void* dst, int B, int n_src, int n_dst,
                        int row_bytes, hipStream_t s);
 // RAJNI_POOL_DENSE: the selections composed into src [B, Nf] (levels[0] = the last scheduled block's; host arrays), and the

@@ -37,7 +37,9 @@
 // launch_embed_norm follows it (rajni_hip_norm.h).  rope - every block rotates q and k in place behind q/k-norm, in front of
 // everything that reads w.qkv, by the table row of each token's place in the image; behind a scheduled block that place comes
 // from the composed selections in w.rsrc (rajni_hip_rope.h).  mln - every block's tail normalises the first mln->n columns of
-// w.hid in place between FC1 and FC2 (rajni_hip_mlpnorm.h).
+// w.hid in place between FC1 and FC2 (rajni_hip_mlpnorm.h).  relpos - every attention launch adds block i's relative position
+// bias to its logits and every scoring launch the class row's; the place of each packed row in the image comes from the composed
+// selections in w.bsrc, this block's included (rajni_hip_relpos.h).
 #include "common.h"
 
 #include <vector>
@@ -57,6 +59,7 @@ struct Workspace {
   // rows, phid [B, pool.hidden] - all fp32 whatever the plan's dtype: the B-row part of the tail runs in fp32
   char *po, *py, *pn, *phid;
   int32_t* rsrc;           // a rope record: [B, n0] = where each token of the stream sat in the unpruned sequence (w.qkv is live there)
+  int32_t* bsrc;           // a relpos record: [B, n0] = where each packed row of the attention (behind the block's own selection) sat
   size_t total, cols_bytes;
 };
 
@@ -74,6 +77,7 @@ struct Spec {
   bool rms, embed_norm;             // kind == RAJNI_NORM_RMS; the record carries a patch_embed.norm
   const rajni_vit_rope* rop;        // all zero arrives here as NULL
   const rajni_vit_mlp_norm* mln;    // all zero arrives here as NULL
+  const rajni_vit_relpos* rel;      // all zero arrives here as NULL
   hipStream_t s;
   bool nocls;                       // no class row: the prefix tokens are the registers alone
   int qmode;                        // the importance query of the scoring blocks
@@ -94,22 +98,24 @@ enum { ENTRY_FORWARD = 0, ENTRY_SIZE = 1 };
 Spec make_spec(int family, const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* pre,
                const rajni_vit_layers* lay, const rajni_vit_image* img, const rajni_vit_query* qry, const rajni_vit_attn_pool* ap,
                hipStream_t s, const rajni_vit_norm* nrm = nullptr, const rajni_vit_rope* rop = nullptr,
-               const rajni_vit_mlp_norm* mln = nullptr) {
+               const rajni_vit_mlp_norm* mln = nullptr, const rajni_vit_relpos* rel = nullptr) {
   // a NULL trailing record makes a call the next-narrower entry point's, by name too (the size of a pool record is the query
   // size function's plus the pool rows, and there is no size function for a layers record)
-  static const char* const names[2][8] = {
+  static const char* const names[2][9] = {
       {"rajni_vit_forward_ext_prefix", "rajni_vit_forward_layers", "rajni_vit_forward_image", "rajni_vit_forward_query",
-       "rajni_vit_forward_pool", "rajni_vit_forward_norm", "rajni_vit_forward_rope", "rajni_vit_forward_mlpnorm"},
+       "rajni_vit_forward_pool", "rajni_vit_forward_norm", "rajni_vit_forward_rope", "rajni_vit_forward_mlpnorm",
+       "rajni_vit_forward_relpos"},
       {"rajni_vit_workspace_bytes_prefix", "rajni_vit_workspace_bytes_prefix", "rajni_vit_workspace_bytes_image",
        "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_norm",
-       "rajni_vit_workspace_bytes_rope", "rajni_vit_workspace_bytes_mlpnorm"}};
+       "rajni_vit_workspace_bytes_rope", "rajni_vit_workspace_bytes_mlpnorm", "rajni_vit_workspace_bytes_relpos"}};
   if (qry && qry->class_token == 1 && qry->query == RAJNI_QUERY_CLS) qry = nullptr;
   if (nrm && nrm->kind == RAJNI_NORM_LAYERNORM && !nrm->embed_norm_w) nrm = nullptr;   // what NULL means
   if (rop && !rop->cos && !rop->sin && !rop->head_stride && !rop->block_stride && !rop->rows && !rop->layout) rop = nullptr;
   if (mln && !mln->w && !mln->b && mln->eps == 0.f && !mln->n) mln = nullptr;
+  if (rel && !rel->table && !rel->prefix_q && !rel->prefix_k && !rel->prefix_qk && !rel->block_stride && !rel->gh && !rel->gw) rel = nullptr;
   Spec c{};
-  c.rop = rop; c.mln = mln;
-  c.who = names[family][mln ? 7 : rop ? 6 : nrm ? 5 : (ap && family == ENTRY_FORWARD) ? 4 : qry ? 3 : img ? 2 : lay ? 1 : 0];
+  c.rop = rop; c.mln = mln; c.rel = rel;
+  c.who = names[family][rel ? 8 : mln ? 7 : rop ? 6 : nrm ? 5 : (ap && family == ENTRY_FORWARD) ? 4 : qry ? 3 : img ? 2 : lay ? 1 : 0];
   c.p = plan; c.ext = ext; c.pre = pre; c.lay = lay; c.img = img; c.qry = qry; c.ap = ap; c.nrm = nrm; c.s = s;
   c.kind = nrm ? nrm->kind : RAJNI_NORM_LAYERNORM;
   c.rms = c.kind == RAJNI_NORM_RMS;
@@ -162,6 +168,7 @@ Workspace carve(const Spec& c) {
   const size_t prow = c.ap ? (size_t)p.B * p.C * sizeof(float) : 0;            // the pool rows likewise
   const size_t opo = take(prow), opy = take(prow), opn = take(prow), oph = take(c.ap ? (size_t)p.B * c.ap->hidden * sizeof(float) : 0);
   const size_t orsrc = take(c.rop ? rows * sizeof(int32_t) : 0);               // and the rope record's source map
+  const size_t obsrc = take(c.rel ? rows * sizeof(int32_t) : 0);               // and the relpos record's
   char* base = (char*)p.workspace;
   w.xa = base + oxa; w.xb = base + oxb; w.xn = base + oxn; w.qkv = base + oqkv; w.att = base + oatt;
   w.hid = base + ohid; w.clsn = base + ocls; w.scf = base + oscf; w.cols = base + ocols;
@@ -170,6 +177,7 @@ Workspace carve(const Spec& c) {
   w.xs = reinterpret_cast<float*>(base + oxs); w.hs = reinterpret_cast<float*>(base + ohs);
   w.po = base + opo; w.py = base + opy; w.pn = base + opn; w.phid = base + oph;
   w.rsrc = c.rop ? reinterpret_cast<int32_t*>(base + orsrc) : nullptr;
+  w.bsrc = c.rel ? reinterpret_cast<int32_t*>(base + obsrc) : nullptr;
   w.total = off;
   return w;
 }
@@ -583,6 +591,47 @@ int check_mlp_norm(const Spec& c) {
   return RAJNI_OK;
 }
 
+// the relpos record against the plan, the grid and the other records (rajni_hip_relpos.h): host-side tests, every refusal names
+// the combination
+int check_relpos(const Spec& c) {
+  const char* who = c.who;          // (a relpos record is the widest there is: the relpos entry point of the call's family)
+  const rajni_vit_plan& p = *c.p;
+  const rajni_vit_relpos& r = *c.rel;
+  RAJNI_REQUIRE(r.table && r.prefix_q && r.prefix_k && r.prefix_qk, RAJNI_ERR_INVALID,
+                "%s: null pointer (relpos.%s) with a non-zero relpos record", who,
+                !r.table ? "table" : !r.prefix_q ? "prefix_q" : !r.prefix_k ? "prefix_k" : "prefix_qk");
+  RAJNI_REQUIRE(p.patch_size > 0 && p.H > 0 && p.D > 0, RAJNI_ERR_INVALID, "%s: bad plan", who);
+  RAJNI_REQUIRE(r.gh >= 1 && r.gw >= 1, RAJNI_ERR_INVALID, "%s: relpos.gh and relpos.gw must be positive (%d x %d)", who, r.gh, r.gw);
+  RAJNI_REQUIRE(r.gh <= RAJNI_RELPOS_MAX_GRID && r.gw <= RAJNI_RELPOS_MAX_GRID, RAJNI_ERR_UNSUPPORTED,
+                "%s: a relative position bias on a %d x %d grid - the cap is %d x %d patches", who, r.gh, r.gw, RAJNI_RELPOS_MAX_GRID,
+                RAJNI_RELPOS_MAX_GRID);
+  RAJNI_REQUIRE(r.gh == c.height / p.patch_size && r.gw == c.width / p.patch_size, RAJNI_ERR_INVALID,
+                "%s: relpos.gh x relpos.gw must equal the forward's patch grid, %d x %d (%d x %d)", who, c.height / p.patch_size,
+                c.width / p.patch_size, r.gh, r.gw);
+  const long long per_block = (long long)p.H * (2 * r.gh - 1) * (2 * r.gw - 1);
+  RAJNI_REQUIRE(r.block_stride == 0 || r.block_stride == per_block, RAJNI_ERR_INVALID,
+                "%s: relpos.block_stride must be 0 (one table for all blocks) or H * (2 gh - 1) * (2 gw - 1) = %lld (%lld)", who,
+                per_block, r.block_stride);
+  RAJNI_REQUIRE(p.D == 64, RAJNI_ERR_UNSUPPORTED,
+                "%s: a relative position bias (a relpos record) with head dim %d - the bias kernels are head dim 64 only", who, p.D);
+  RAJNI_REQUIRE(!p.act_fp8, RAJNI_ERR_UNSUPPORTED,
+                "%s: a relative position bias (a relpos record) is unsupported with plan.act_fp8 - the e4m3 attention and its "
+                "bounds were fitted to logits without a bias", who);
+  RAJNI_REQUIRE(!c.nocls && c.qmode == RAJNI_QUERY_CLS, RAJNI_ERR_UNSUPPORTED,
+                "%s: a relative position bias (a relpos record) with %s - importance is scored on the class row's biased logits, "
+                "and a mean query has no position", who, c.nocls ? "query.class_token = 0" : "the mean importance query (RAJNI_QUERY_MEAN)");
+  RAJNI_REQUIRE(!c.rop, RAJNI_ERR_UNSUPPORTED,
+                "%s: a relative position bias (a relpos record) together with RoPE (a rope record) - no model has both", who);
+  RAJNI_REQUIRE(!p.cls_only_last_block, RAJNI_ERR_UNSUPPORTED,
+                "%s: a relative position bias (a relpos record) with plan.cls_only_last_block - the CLS-query kernel of that "
+                "opt-in takes no bias", who);
+  RAJNI_REQUIRE(p.attn_scale > 0.f && p.attn_scale < INFINITY, RAJNI_ERR_INVALID,
+                "%s: plan.attn_scale must be positive and finite with a relpos record (the bias is divided by it)", who);
+  RAJNI_REQUIRE_PLACED("rajni_vit_forward_relpos: relpos", {"table", r.table, 4}, {"prefix_q", r.prefix_q, 4}, {"prefix_k", r.prefix_k, 4},
+                       {"prefix_qk", r.prefix_qk, 4});
+  return RAJNI_OK;
+}
+
 // the token walk (model.py:43,50): a scheduled block leaves its kept patch tokens and the P prefix tokens ...
 inline int tokens_after(const rajni_block& blk, int N, int P) { return blk.keep > 0 ? blk.keep + P : N; }
 // ... so this many enter block i
@@ -751,6 +800,7 @@ int check_all(Spec& c, const void* images, const void* logits) {
   if (c.img && (rc = check_image(c)) != RAJNI_OK) return rc;
   if (c.rop && (rc = check_rope(c)) != RAJNI_OK) return rc;
   if (c.mln && (rc = check_mlp_norm(c)) != RAJNI_OK) return rc;
+  if (c.rel && (rc = check_relpos(c)) != RAJNI_OK) return rc;
   if (c.lay && (rc = check_layers(c)) != RAJNI_OK) return rc;
   if (c.dense_last && (rc = check_dense_last(c)) != RAJNI_OK) return rc;
   if ((rc = check_plan(c)) != RAJNI_OK) return rc;
@@ -775,6 +825,7 @@ size_t workspace_bytes(const Spec& c) {
   if (c.nrm && check_norm(c) != RAJNI_OK) return 0;
   if (c.rop && check_rope(c) != RAJNI_OK) return 0;
   if (c.mln && check_mlp_norm(c) != RAJNI_OK) return 0;
+  if (c.rel && check_relpos(c) != RAJNI_OK) return 0;
   return carve(c).total;
 }
 
@@ -833,6 +884,18 @@ int vit_forward(Spec f, const void* images, void* logits) {
   // the rope record: w.rsrc names the place of every token of `cur` in the unpruned sequence once a scheduled block has run
   // (before that the place is the row index and the kernel gets no map); stale whenever a selection has changed the token set
   bool rope_mapped = false, rope_stale = false;
+  // the relpos record: w.bsrc names the place of every packed row of the attention once a scheduled block has selected (its own
+  // selection included); it stays good through the unscheduled blocks behind it, whose token set is the same
+  const rajni_vit_relpos* rel = f.rel;
+  bool rel_mapped = false;
+  const int rel_gh = rel ? rel->gh : 0, rel_gw = rel ? rel->gw : 0;
+  const float *rb_t = nullptr, *rb_q = nullptr, *rb_k = nullptr, *rb_qk = nullptr;   // block i's table and values
+  // a block's attention over np rows gathered by idx from n_src, query rows [0, nq): with block i's bias where there is a record
+  auto attend = [&](const int32_t* idx, void* out, int n_src, int np, int nq) {
+    if (!rel) return launch_attention(w.qkv, idx, out, B, n_src, np, nq, p.H, p.D, p.attn_scale, dt, s);
+    return launch_attention_relpos(w.qkv, idx, out, B, n_src, np, nq, p.H, p.D, p.attn_scale, dt, rb_t, rb_q, rb_k, rb_qk, rel_gh, rel_gw, P,
+                                   rel_mapped ? w.bsrc : nullptr, s);
+  };
 
   for (int i = 0; i < p.depth; ++i) {
     const rajni_block& blk = p.blocks[i];
@@ -857,6 +920,12 @@ int vit_forward(Spec f, const void* images, void* logits) {
       if (rc != RAJNI_OK) return rc;
     }
 
+    if (rel) {
+      const size_t vo = rel->block_stride ? (size_t)i * p.H : 0;
+      rb_t = rel->table + (size_t)i * rel->block_stride;
+      rb_q = rel->prefix_q + vo; rb_k = rel->prefix_k + vo; rb_qk = rel->prefix_qk + vo;
+    }
+
     // ---- the two CLS forms of the last block: only x[:, 0] reaches the head (model.py:65-66), so the tail runs on the B CLS
     //      rows - the residual row of image b is its CLS row, row b * N of `cur` - and leaves the stream [B, 1, C] in `oth`
     const long cls_ld = (long)N * C;
@@ -876,7 +945,7 @@ int vit_forward(Spec f, const void* images, void* logits) {
       // the two residual rows through idx01 and the stream leaves [B, 2, C] in `oth`
       const Tail t = tail_args(f, blk, AttnRows{2 * B, C, nullptr, C, w.idx01, 2, N}, cur, oth);
       if (tail_ok(t)) {
-        rc = launch_attention(w.qkv, nullptr, w.xn, B, N, N, 2, p.H, p.D, p.attn_scale, dt, s);
+        rc = attend(nullptr, w.xn, N, N, 2);
         if (rc != RAJNI_OK) return rc;
         rc = launch_gather_rows(w.xn, w.idx01, w.att, B, N, 2, C * rajni_elem_bytes(dt), s);
         if (rc != RAJNI_OK) return rc;
@@ -889,7 +958,7 @@ int vit_forward(Spec f, const void* images, void* logits) {
       // the all-rows kernels on the rows the head reads: the first query tile, proj on its CLS rows in place (stride N * C)
       const Tail t = tail_args(f, blk, AttnRows{B, cls_ld, nullptr, cls_ld, nullptr, 0, 0}, cur, oth);
       if (tail_ok(t)) {   // (a refused shape or stride: all rows below, as if this branch were not here)
-        rc = launch_attention(w.qkv, nullptr, w.att, B, N, N, 1, p.H, p.D, p.attn_scale, dt, s);
+        rc = attend(nullptr, w.att, N, N, 1);
         if (rc != RAJNI_OK) return rc;
         rc = launch_tail(f, blk, t);
         if (rc != RAJNI_OK) return rc;
@@ -906,7 +975,8 @@ int vit_forward(Spec f, const void* images, void* logits) {
         const void* full = carried;
         if (recompute) {
           void* dst = blk.scores ? blk.scores : (void*)w.scf;
-          rc = launch_score_select(w.qkv, nullptr, B, N, p.H, p.D, 1e-6f, 0, dst, nullptr, nullptr, dt, s, f.nocls ? P : 1, w.sst, w.sst_bytes, f.qmode);
+          rc = launch_score_select(w.qkv, nullptr, B, N, p.H, p.D, 1e-6f, 0, dst, nullptr, nullptr, dt, s, f.nocls ? P : 1, w.sst, w.sst_bytes, f.qmode,
+                                   rb_q, rb_qk, rel ? P : 0);
           if (rc != RAJNI_OK) return rc;
           full = dst;
         }
@@ -922,7 +992,7 @@ int vit_forward(Spec f, const void* images, void* logits) {
       } else {
         if (recompute)
           rc = launch_score_select(w.qkv, nullptr, B, N, p.H, p.D, 1e-6f, blk.keep, blk.scores,
-                                   blk.keep_idx, blk.next_scores, dt, s, P, w.sst, w.sst_bytes, f.qmode);
+                                   blk.keep_idx, blk.next_scores, dt, s, P, w.sst, w.sst_bytes, f.qmode, rb_q, rb_qk, rel ? P : 0);
         else
           rc = launch_score_select(nullptr, carried, B, N, 0, 0, 0.f, blk.keep, nullptr,
                                    blk.keep_idx, blk.next_scores, dt, s, P);
@@ -930,6 +1000,11 @@ int vit_forward(Spec f, const void* images, void* logits) {
         idx = blk.keep_idx;
       }
       carried = blk.next_scores;  // attention.py:58,60
+      if (rel) {   // the places of the Np rows this block's attention runs on
+        rc = launch_source_idx_before(f, i + 1, w.bsrc, Np);
+        if (rc != RAJNI_OK) return rc;
+        rel_mapped = true;
+      }
     } else {
       carried = nullptr;          // model.py:63
     }
@@ -937,7 +1012,7 @@ int vit_forward(Spec f, const void* images, void* logits) {
     // ---- attention on the kept tokens, gather fused (attention.py:42-54)
     const bool att8 = attn_emits_e4m3(p, blk, Np);
     if (att8) rc = launch_attention_fp8(w.qkv, idx, w.att, blk.attn_out_scale, w.xs, B, N, Np, p.H, p.D, p.attn_scale, s);
-    else rc = launch_attention(w.qkv, idx, w.att, B, N, Np, Np, p.H, p.D, p.attn_scale, dt, s);
+    else rc = attend(idx, w.att, N, Np, Np);
     if (rc != RAJNI_OK) return rc;
     // a pruned block gathers its residual rows from `cur` into `oth`; an unpruned one runs proj in place (each element is
     // read and written by the same lane: in place is safe)
@@ -1071,6 +1146,21 @@ extern "C" int rajni_vit_forward_mlpnorm(const rajni_vit_plan* plan, const rajni
                                          const rajni_vit_mlp_norm* mlp_norm, const void* images, void* logits, rajni_stream_t stream) {
   return vit_forward(make_spec(ENTRY_FORWARD, plan, ext, prefix, layers, image, query, pool, (hipStream_t)stream, norm, rope, mlp_norm),
                      images, logits);
+}
+extern "C" int rajni_vit_forward_relpos(const rajni_vit_plan* plan, const rajni_vit_ext* ext, const rajni_vit_prefix* prefix,
+                                        const rajni_vit_layers* layers, const rajni_vit_image* image, const rajni_vit_query* query,
+                                        const rajni_vit_attn_pool* pool, const rajni_vit_norm* norm, const rajni_vit_rope* rope,
+                                        const rajni_vit_mlp_norm* mlp_norm, const rajni_vit_relpos* relpos, const void* images,
+                                        void* logits, rajni_stream_t stream) {
+  return vit_forward(make_spec(ENTRY_FORWARD, plan, ext, prefix, layers, image, query, pool, (hipStream_t)stream, norm, rope, mlp_norm, relpos),
+                     images, logits);
+}
+extern "C" size_t rajni_vit_workspace_bytes_relpos(const rajni_vit_plan* plan, const rajni_vit_prefix* prefix,
+                                                   const rajni_vit_image* image, const rajni_vit_query* query,
+                                                   const rajni_vit_attn_pool* pool, const rajni_vit_norm* norm,
+                                                   const rajni_vit_rope* rope, const rajni_vit_mlp_norm* mlp_norm,
+                                                   const rajni_vit_relpos* relpos) {
+  return workspace_bytes(make_spec(ENTRY_SIZE, plan, nullptr, prefix, nullptr, image, query, pool, nullptr, norm, rope, mlp_norm, relpos));
 }
 extern "C" size_t rajni_vit_workspace_bytes(const rajni_vit_plan* plan) {
   return workspace_bytes(make_spec(ENTRY_SIZE, plan, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));

@@ -31,6 +31,9 @@ constexpr int SS_PART = 512;
 #define RAJNI_SS_VUM 6
 #endif
 
+// the class row's relative position bias (rajni_hip_relpos.h): [H] fp32 each - pq on the patch keys, pqk on the P prefix keys
+// (rows 0 .. P - 1)
+struct ScoreBias { const float* pq; const float* pqk; int P; };
 struct ScoreArgs {          // T = activation dtype (bf16_t, f16_t or float)
   const void* qkv;          // T [B,N,3C] or null (select-only)
   const void* scores_in;    // T [B,N] (select-only)
@@ -43,6 +46,16 @@ struct ScoreArgs {          // T = activation dtype (bf16_t, f16_t or float)
   void* next_scores;        // T [B,P+keep] or null
   unsigned long long* stamps;   // diagnostic builds (-DRAJNI_SS_STAMPS): 16 x u64 s_memtime per workgroup, or null
 };
+// the argument of the instantiations with the bias: ScoreArgs itself keeps its size, so no kernel that takes it changes
+struct ScoreArgsRB : ScoreArgs { ScoreBias rb; };
+__device__ __forceinline__ const ScoreBias* rb_of(const ScoreArgs&) { return nullptr; }
+__device__ __forceinline__ const ScoreBias* rb_of(const ScoreArgsRB& a) { return &a.rb; }
+// the class row's logit of head h against key row n, with its bias (fp32 add, before the softmax)
+template <bool RB>
+__device__ __forceinline__ float ss_logit(const ScoreBias* rb, float scaled_dot, int h, int n) {
+  if constexpr (RB) return scaled_dot + (n < rb->P ? rb->pqk[h] : rb->pq[h]);
+  else return scaled_dot;
+}
 #ifdef RAJNI_SS_STAMPS
 #define SS_STAMP(i) do { if (a.stamps != nullptr && threadIdx.x == 0) a.stamps[blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
@@ -215,8 +228,11 @@ __device__ __forceinline__ void select_tail(const ScoreArgs& a, int b, float* sc
 // otherwise (N = 577 with 16 heads: 185 KiB would be needed) vbar reuses the logits' region after the statistics.
 // QMEAN: the importance query is the mean of the N query rows (RAJNI_QUERY_MEAN) instead of row 0; everything behind the
 // fill of `qcls` is the same code.
-template <bool COMPUTE, typename T, bool MERGED, bool QMEAN = false>
-__global__ void __launch_bounds__(SS_THREADS) score_select_kernel(const ScoreArgs a) {
+// Args = ScoreArgsRB: the class row's logits get their relative position bias (never with QMEAN: the mean query has no
+// position).  A template parameter, so that the instantiations without a bias are the code they were (tools/isa_identity.py).
+template <bool COMPUTE, typename T, bool MERGED, bool QMEAN = false, typename Args = ScoreArgs>
+__global__ void __launch_bounds__(SS_THREADS) score_select_kernel(const Args a) {
+  constexpr bool RB = !__is_same(Args, ScoreArgs);
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int b = blockIdx.x;
@@ -305,7 +321,7 @@ __global__ void __launch_bounds__(SS_THREADS) score_select_kernel(const ScoreArg
       dot = fmaf(kf[4], q1.x, dot); dot = fmaf(kf[5], q1.y, dot); dot = fmaf(kf[6], q1.z, dot);
       dot = fmaf(kf[7], q1.w, dot);
       dot = group_sum(dot, LP);
-      if ((c & (LP - 1)) == 0) region[(c / LP) * N + n] = dot * inv_sqrt_d;
+      if ((c & (LP - 1)) == 0) region[(c / LP) * N + n] = ss_logit<RB>(rb_of(a), dot * inv_sqrt_d, c / LP, n);
     };
     auto k_pass = [&]() {
       if (!pow2) {
@@ -319,7 +335,7 @@ __global__ void __launch_bounds__(SS_THREADS) score_select_kernel(const ScoreArg
 #pragma unroll
             for (int j = 0; j < 8; ++j) dot = fmaf(kf[j], qcls[h * D + c * 8 + j], dot);
           }
-          region[h * N + n] = dot * inv_sqrt_d;
+          region[h * N + n] = ss_logit<RB>(rb_of(a), dot * inv_sqrt_d, h, n);
         }
       } else {
         int n = tid / CP, c = tid - n * CP;
@@ -616,8 +632,9 @@ __global__ void __launch_bounds__(SQ_THREADS) score_qmean_kernel(const T* __rest
   }
 }
 
-template <typename T>
-__global__ void __launch_bounds__(ST_THREADS) score_tile_kernel(const ScoreArgs a, const TiledArgs t) {
+template <typename T, typename Args = ScoreArgs>
+__global__ void __launch_bounds__(ST_THREADS) score_tile_kernel(const Args a, const TiledArgs t) {
+  constexpr bool RB = !__is_same(Args, ScoreArgs);
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int tile = blockIdx.x, b = blockIdx.y;
@@ -659,7 +676,7 @@ __global__ void __launch_bounds__(ST_THREADS) score_tile_kernel(const ScoreArgs 
 #pragma unroll
         for (int j = 0; j < 8; ++j) dot = fmaf(kf[j], qcls[h * D + c * 8 + j], dot);
       }
-      lt[h * ST_TILE + n] = dot * inv_sqrt_d;
+      lt[h * ST_TILE + n] = ss_logit<RB>(rb_of(a), dot * inv_sqrt_d, h, t0 + n);
     }
   } else {
     const int dn = ST_THREADS / CP, dc = ST_THREADS - dn * CP;   // item index += ST_THREADS
@@ -684,7 +701,7 @@ __global__ void __launch_bounds__(ST_THREADS) score_tile_kernel(const ScoreArgs 
           dot = fmaf(kf[u][4], q1.x, dot); dot = fmaf(kf[u][5], q1.y, dot); dot = fmaf(kf[u][6], q1.z, dot);
           dot = fmaf(kf[u][7], q1.w, dot);
           dot = group_sum(dot, LP);     // the LP lanes of a head row are one aligned group with one token: all in or all out
-          if ((cc[u] & (LP - 1)) == 0) lt[(cc[u] / LP) * ST_TILE + nn[u]] = dot * inv_sqrt_d;
+          if ((cc[u] & (LP - 1)) == 0) lt[(cc[u] / LP) * ST_TILE + nn[u]] = ss_logit<RB>(rb_of(a), dot * inv_sqrt_d, cc[u] / LP, t0 + nn[u]);
         }
     }
   }
@@ -915,7 +932,7 @@ extern "C" size_t rajni_score_select_query_workspace_bytes(int B, int N, int H, 
 
 namespace {
 // the tiled path: (the mean query's launch,) tile kernel + finish kernel, nothing else on the stream
-int launch_score_tiled(ScoreArgs a, int B, int dtype, void* ws, size_t ws_bytes, hipStream_t s, bool qmean) {
+int launch_score_tiled(ScoreArgs a, int B, int dtype, void* ws, size_t ws_bytes, hipStream_t s, bool qmean, const ScoreBias& rb) {
   const int N = a.N, H = a.H, D = a.D;
   RAJNI_REQUIRE(B <= RAJNI_MAX_GRID_YZ, RAJNI_ERR_UNSUPPORTED,
                 "score/select: B=%d - one launch of the tiled path takes at most %d images (grid: token tiles x images)", B,
@@ -961,7 +978,16 @@ int launch_score_tiled(ScoreArgs a, int B, int dtype, void* ws, size_t ws_bytes,
     else hipLaunchKernelGGL(score_qmean_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)a.qkv, t.qbar, N, C);
     RAJNI_CHECK_LAUNCH("score_qmean_kernel");
   }
-  hipLaunchKernelGGL(tile, dim3(l.tiles, B), dim3(ST_THREADS), tl, s, a, t);
+  if (rb.pq != nullptr) {
+    typedef void (*kern_rb_t)(const ScoreArgsRB, const TiledArgs);
+    const kern_rb_t tile_rb = dtype == RAJNI_F16 ? &score_tile_kernel<f16_t, ScoreArgsRB>
+                              : dtype == RAJNI_F32 ? &score_tile_kernel<float, ScoreArgsRB> : &score_tile_kernel<bf16_t, ScoreArgsRB>;
+    ScoreArgsRB ar{};
+    static_cast<ScoreArgs&>(ar) = a; ar.rb = rb;
+    hipLaunchKernelGGL(tile_rb, dim3(l.tiles, B), dim3(ST_THREADS), tl, s, ar, t);
+  } else {
+    hipLaunchKernelGGL(tile, dim3(l.tiles, B), dim3(ST_THREADS), tl, s, a, t);
+  }
   RAJNI_CHECK_LAUNCH("score_tile_kernel");
   hipLaunchKernelGGL(fin, dim3(B), dim3(SS_THREADS), fl, s, a, t);
   RAJNI_CHECK_LAUNCH("score_finish_kernel");
@@ -972,7 +998,8 @@ int launch_score_tiled(ScoreArgs a, int B, int dtype, void* ws, size_t ws_bytes,
 // qkv != null: compute scores (and select when keep > 0); qkv == null: select from scores_in.
 int launch_score_select(const void* qkv, const void* scores_in, int B, int N, int H, int D,
                         float eps, int keep, void* scores_out, int32_t* keep_idx,
-                        void* next_scores, int dtype, hipStream_t s, int P, void* ws, size_t ws_bytes, int query) {
+                        void* next_scores, int dtype, hipStream_t s, int P, void* ws, size_t ws_bytes, int query,
+                        const float* rb_pq, const float* rb_pqk, int rb_prefix) {
   RAJNI_REQUIRE(dtype == RAJNI_BF16 || dtype == RAJNI_F32 || dtype == RAJNI_F16, RAJNI_ERR_INVALID, "score/select: bad dtype %d", dtype);
   // (P = 0, a sequence without a class row, reaches here from rajni_hip_query.h alone: the other entry points refuse it themselves)
   RAJNI_REQUIRE(P >= 0 && P <= RAJNI_MAX_PREFIX, RAJNI_ERR_INVALID, "score/select: num_prefix must be 0..%d (%d)", RAJNI_MAX_PREFIX, P);
@@ -986,6 +1013,12 @@ int launch_score_select(const void* qkv, const void* scores_in, int B, int N, in
   a.N = N; a.keep = keep; a.eps = eps; a.P = P;
   a.scores_out = scores_out; a.keep_idx = keep_idx; a.next_scores = next_scores;
   a.stamps = rajni_g_stamps;
+  // the class row's relative position bias: both value arrays or neither, a computed score, the class query
+  RAJNI_REQUIRE((rb_pq != nullptr) == (rb_pqk != nullptr), RAJNI_ERR_INVALID, "score/select: prefix_q and prefix_qk come together");
+  RAJNI_REQUIRE(!rb_pq || (qkv != nullptr && query == RAJNI_QUERY_CLS && rb_prefix >= 1 && rb_prefix <= RAJNI_MAX_PREFIX && rb_prefix < N),
+                RAJNI_ERR_UNSUPPORTED, "score/select: a relative position bias needs computed scores, the class query and 1..%d prefix "
+                "rows (the mean importance query has no position)", RAJNI_MAX_PREFIX);
+  const ScoreBias rb{rb_pq, rb_pqk, rb_prefix};
   size_t lds;
   bool merged = false;
   const bool qmean = qkv != nullptr && query == RAJNI_QUERY_MEAN;
@@ -995,7 +1028,7 @@ int launch_score_select(const void* qkv, const void* scores_in, int B, int N, in
     RAJNI_REQUIRE(H > 0, RAJNI_ERR_INVALID, "importance: H must be positive");
     a.qkv = qkv; a.H = H; a.D = D;
     // a shape one workgroup holds takes the kernel it always took; scratch serves the others (and any shape under the test hook)
-    if (ws != nullptr && (ss_needs_tiles(N, H, D, qmean) || g_ss_force_tiled != 0)) return launch_score_tiled(a, B, dtype, ws, ws_bytes, s, qmean);
+    if (ws != nullptr && (ss_needs_tiles(N, H, D, qmean) || g_ss_force_tiled != 0)) return launch_score_tiled(a, B, dtype, ws, ws_bytes, s, qmean, rb);
     merged = ss_lds_bytes(N, H, D, P, true, qmean) <= 160 * 1024 && g_ss_force_two_pass == 0;   // else vbar reuses the logits' region
     lds = ss_lds_bytes(N, H, D, P, merged, qmean);
   } else {
@@ -1011,6 +1044,11 @@ int launch_score_select(const void* qkv, const void* scores_in, int B, int N, in
                 qkv != nullptr ? "; rajni_score_select_ws scores such shapes through caller-provided scratch" : "");
   const bool f32 = dtype == RAJNI_F32;
   typedef void (*kern_t)(const ScoreArgs);
+  typedef void (*kern_rb_t)(const ScoreArgsRB);
+  const kern_rb_t kern_rb = !rb_pq ? nullptr
+      : dtype == RAJNI_F16 ? (merged ? &score_select_kernel<true, f16_t, true, false, ScoreArgsRB> : &score_select_kernel<true, f16_t, false, false, ScoreArgsRB>)
+      : f32 ? (merged ? &score_select_kernel<true, float, true, false, ScoreArgsRB> : &score_select_kernel<true, float, false, false, ScoreArgsRB>)
+            : (merged ? &score_select_kernel<true, bf16_t, true, false, ScoreArgsRB> : &score_select_kernel<true, bf16_t, false, false, ScoreArgsRB>);
   const kern_t kern = qmean
       ? (dtype == RAJNI_F16 ? (merged ? &score_select_kernel<true, f16_t, true, true> : &score_select_kernel<true, f16_t, false, true>)
          : f32 ? (merged ? &score_select_kernel<true, float, true, true> : &score_select_kernel<true, float, false, true>)
@@ -1022,7 +1060,8 @@ int launch_score_select(const void* qkv, const void* scores_in, int B, int N, in
                                     : (f32 ? &score_select_kernel<true, float, false> : &score_select_kernel<true, bf16_t, false>))
                           : (f32 ? &score_select_kernel<false, float, false> : &score_select_kernel<false, bf16_t, false>);
   if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute(kern_rb ? reinterpret_cast<const void*>(kern_rb) : reinterpret_cast<const void*>(kern),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) {
       rajni_set_error("hipFuncSetAttribute(score_select, %zu): %s", lds, hipGetErrorString(e));
       return RAJNI_ERR_LAUNCH;
@@ -1031,7 +1070,13 @@ int launch_score_select(const void* qkv, const void* scores_in, int B, int N, in
   const double es = f32 ? 4.0 : 2.0;
   const double bytes = qkv ? ((qmean ? 3.0 : 2.0) * N * H * D + (qmean ? 0 : H * D)) * es * B + 4.0 * N * B : 6.0 * N * B;
   ProfScope prof(qkv ? (keep > 0 ? KC_SCORE_SELECT : KC_IMPORTANCE) : KC_SELECT, s, 0.0, bytes);
-  hipLaunchKernelGGL(kern, dim3(B), dim3(SS_THREADS), lds, s, a);
+  if (kern_rb) {
+    ScoreArgsRB ar{};
+    static_cast<ScoreArgs&>(ar) = a; ar.rb = rb;
+    hipLaunchKernelGGL(kern_rb, dim3(B), dim3(SS_THREADS), lds, s, ar);
+  } else {
+    hipLaunchKernelGGL(kern, dim3(B), dim3(SS_THREADS), lds, s, a);
+  }
   RAJNI_CHECK_LAUNCH("score_select_kernel");
   return RAJNI_OK;
 }

@@ -302,6 +302,31 @@ _MLPNORM_SIGS = {
                                           C.POINTER(VitRope), C.POINTER(VitMlpNorm), c_void_p, c_void_p, c_void_p]),
 }
 MLPNORM_SYMBOLS = tuple(_MLPNORM_SIGS.keys())
+# include/rajni_hip_relpos.h, additive in the same way: a relative position bias on the attention logits (BEiT, vit_relpos)
+RELPOS_MAX_GRID = 32     # RAJNI_RELPOS_MAX_GRID: patches per grid side
+
+
+class VitRelPos(C.Structure):
+    """rajni_vit_relpos (include/rajni_hip_relpos.h): fp32 table [blocks or 1][H][(2 gh - 1)(2 gw - 1)], the three prefix
+    values [blocks or 1][H] each, the table's block stride (0: shared) and the patch grid"""
+    _fields_ = [("table", c_void_p), ("prefix_q", c_void_p), ("prefix_k", c_void_p), ("prefix_qk", c_void_p),
+                ("block_stride", C.c_longlong), ("gh", c_int), ("gw", c_int)]
+
+
+_RELPOS_SIGS = {
+    "rajni_attention_relpos": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "rajni_score_select_relpos": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "rajni_vit_workspace_bytes_relpos": (c_size_t, [C.POINTER(VitPlan), C.POINTER(VitPrefix), C.POINTER(VitImage),
+                                                    C.POINTER(VitQuery), C.POINTER(VitAttnPool), C.POINTER(VitNorm),
+                                                    C.POINTER(VitRope), C.POINTER(VitMlpNorm), C.POINTER(VitRelPos)]),
+    "rajni_vit_forward_relpos": (c_int, [C.POINTER(VitPlan), C.POINTER(VitExt), C.POINTER(VitPrefix), C.POINTER(VitLayers),
+                                         C.POINTER(VitImage), C.POINTER(VitQuery), C.POINTER(VitAttnPool), C.POINTER(VitNorm),
+                                         C.POINTER(VitRope), C.POINTER(VitMlpNorm), C.POINTER(VitRelPos), c_void_p, c_void_p,
+                                         c_void_p]),
+}
+RELPOS_SYMBOLS = tuple(_RELPOS_SIGS.keys())
 RESAMPLE_MAX_GRID = 128     # RAJNI_RESAMPLE_MAX_GRID: grid cells per axis, source and destination
 ABI_VERSION = 8     # include/rajni_hip.h; bumped whenever a struct or an entry point changes
 _lib: Optional[C.CDLL] = None
@@ -319,7 +344,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib = C.CDLL(path)
     for name, (res, args) in (list(_SIGS.items()) + list(_LAYERS_SIGS.items()) + list(_IMAGE_SIGS.items()) + list(_QUERY_SIGS.items())
                               + list(_ATTNPOOL_SIGS.items()) + list(_NORM_SIGS.items()) + list(_ROPE_SIGS.items())
-                              + list(_MLPNORM_SIGS.items())):
+                              + list(_MLPNORM_SIGS.items()) + list(_RELPOS_SIGS.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

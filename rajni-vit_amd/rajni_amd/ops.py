@@ -5,7 +5,7 @@ torch's current stream; all compute is in librajni_hip.so.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -173,19 +173,58 @@ def select_topk(scores: torch.Tensor, keep: int, num_prefix: int = 1) -> Tuple[t
     return idx, nxt
 
 
+class RelPos(NamedTuple):
+    """One block's relative position bias for the stand-alone entries (include/rajni_hip_relpos.h), fp32 on the device:
+    table [H, (2 gh - 1) * (2 gw - 1)], prefix_q / prefix_k / prefix_qk [H], grid = (gh, gw)."""
+    table: torch.Tensor
+    prefix_q: torch.Tensor
+    prefix_k: torch.Tensor
+    prefix_qk: torch.Tensor
+    grid: Tuple[int, int]
+
+
+def _rel_pos_placed(rel_pos: "RelPos", num_heads: int) -> "RelPos":
+    gh, gw = (int(g) for g in rel_pos.grid)
+    T = (2 * gh - 1) * (2 * gw - 1)
+    if tuple(rel_pos.table.shape) != (num_heads, T):
+        raise ValueError(f"rel_pos.table must be [H, (2 gh - 1) * (2 gw - 1)] = [{num_heads}, {T}], got {tuple(rel_pos.table.shape)}")
+    vals = []
+    for name in ("prefix_q", "prefix_k", "prefix_qk"):
+        v = getattr(rel_pos, name)
+        if tuple(v.shape) != (num_heads,):
+            raise ValueError(f"rel_pos.{name} must be [H] = [{num_heads}], got {tuple(v.shape)}")
+        vals.append(_placed(v.float(), "rel_pos." + name, 4))
+    return RelPos(_placed(rel_pos.table.float(), "rel_pos.table", 4), *vals, (gh, gw))
+
+
 def score_select(qkv: torch.Tensor, num_heads: int, keep: int, eps: float = 1e-6, want_scores: bool = True,
-                 num_prefix: int = 1, query: str = "cls"):
+                 num_prefix: int = 1, query: str = "cls", rel_pos: Optional[RelPos] = None):
     """qkv [B, N, 3C] -> (scores [B, N] or None, keep_idx int32 [B, P+keep], next_scores [B, P+keep]), P = `num_prefix`
     as in select_topk (the scores themselves do not depend on P).  `query`: "cls" (row 0) or "mean" (the mean query row);
-    P = 0 (a sequence without a class row) goes through rajni_score_select_query with either."""
+    P = 0 (a sequence without a class row) goes through rajni_score_select_query with either.
+    `rel_pos`: the class row's logits get prefix_q[h] on the patch keys and prefix_qk[h] on the P prefix keys before its softmax
+    (rajni_score_select_relpos; keep = 0 gives the scores alone); the class query and P >= 1 only."""
     nat.require_device(qkv, "qkv")
     qkv = _placed(qkv, "qkv")
     B, N, threeC = qkv.shape
     D = threeC // 3 // num_heads
     P = int(num_prefix)
     scores = torch.empty((B, N), dtype=qkv.dtype, device=qkv.device) if want_scores else None
-    idx = torch.empty((B, keep + P), dtype=torch.int32, device=qkv.device)
-    nxt = torch.empty((B, keep + P), dtype=qkv.dtype, device=qkv.device)
+    idx = torch.empty((B, keep + P), dtype=torch.int32, device=qkv.device) if keep > 0 or rel_pos is None else None
+    nxt = torch.empty((B, keep + P), dtype=qkv.dtype, device=qkv.device) if keep > 0 or rel_pos is None else None
+    if rel_pos is not None:
+        if query != "cls" or P == 0:
+            raise NotImplementedError("score_select: a relative position bias needs the class query and a class row "
+                                      "(the mean importance query has no position)")
+        rp = _rel_pos_placed(rel_pos, num_heads)
+        ws = _score_scratch(qkv, B, N, num_heads, D)
+        with nat.device_guard(qkv.device):
+            nat.check(nat.lib().rajni_score_select_relpos(qkv.data_ptr(), B, N, num_heads, D, eps, P, keep, nat.ptr(scores),
+                                                          nat.ptr(idx), nat.ptr(nxt), _dt(qkv), nat.ptr(ws),
+                                                          ws.numel() if ws is not None else 0, rp.prefix_q.data_ptr(),
+                                                          rp.prefix_qk.data_ptr(), nat.stream_ptr(qkv.device)),
+                      "rajni_score_select_relpos")
+        return scores, idx, nxt
     if query != "cls" or P == 0:
         _score_select_query(qkv, B, N, num_heads, D, eps, P, keep, query, scores, idx, nxt)
         return scores, idx, nxt
@@ -220,8 +259,11 @@ def gather_rows(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def attention(qkv: torch.Tensor, keep_idx: Optional[torch.Tensor], num_heads: int, scale: float) -> torch.Tensor:
-    """qkv [B, N, 3C]; keep_idx [B, Np] int32 or None -> [B, Np, C]"""
+def attention(qkv: torch.Tensor, keep_idx: Optional[torch.Tensor], num_heads: int, scale: float,
+              rel_pos: Optional[RelPos] = None, pos: Optional[torch.Tensor] = None, num_prefix: int = 1) -> torch.Tensor:
+    """qkv [B, N, 3C]; keep_idx [B, Np] int32 or None -> [B, Np, C].
+    `rel_pos`: the bias of include/rajni_hip_relpos.h on the logits (rajni_attention_relpos); `pos` [B, Np] int32 is then the place
+    each packed row had in the unpruned sequence (None: the packed row index), the first `num_prefix` places being prefix rows."""
     nat.require_device(qkv, "qkv")
     qkv = _placed(qkv, "qkv")
     B, N, threeC = qkv.shape
@@ -233,6 +275,21 @@ def attention(qkv: torch.Tensor, keep_idx: Optional[torch.Tensor], num_heads: in
     else:
         Np = N
     out = torch.empty((B, Np, Cc), dtype=qkv.dtype, device=qkv.device)
+    if rel_pos is not None:
+        rp = _rel_pos_placed(rel_pos, num_heads)
+        if pos is not None:
+            if tuple(pos.shape) != (B, Np):
+                raise ValueError(f"pos must be [B, Np] = [{B}, {Np}], got {tuple(pos.shape)}")
+            pos = _placed(pos.to(torch.int32), "pos", 4)
+        with nat.device_guard(qkv.device):
+            nat.check(nat.lib().rajni_attention_relpos(qkv.data_ptr(), nat.ptr(keep_idx), out.data_ptr(), B, N, Np, num_heads, D,
+                                                       float(scale), _dt(qkv), rp.table.data_ptr(), rp.prefix_q.data_ptr(),
+                                                       rp.prefix_k.data_ptr(), rp.prefix_qk.data_ptr(), rp.grid[0], rp.grid[1],
+                                                       int(num_prefix), nat.ptr(pos), nat.stream_ptr(qkv.device)),
+                      "rajni_attention_relpos")
+        return out
+    if pos is not None:
+        raise ValueError("attention: pos without rel_pos")
     with nat.device_guard(qkv.device):
         nat.check(nat.lib().rajni_attention(qkv.data_ptr(), nat.ptr(keep_idx), out.data_ptr(), B, N, Np, num_heads, D,
                                             float(scale), _dt(qkv), nat.stream_ptr(qkv.device)), "rajni_attention")

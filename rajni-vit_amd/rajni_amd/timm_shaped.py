@@ -89,8 +89,17 @@ class ViTConfig:
     mlp_norm = False
     eva_block = False
     qkv_split = False
+    # ... and what RelPosViTConfig makes fields
+    rel_pos = "none"
+    img_width = None
 
     def __post_init__(self):
+        if self.rel_pos not in ("none", "beit", "beit_shared", "relpos", "srelpos"):
+            raise ValueError(f"ViTConfig: rel_pos must be 'none', 'beit', 'beit_shared', 'relpos' or 'srelpos', got {self.rel_pos!r}")
+        if self.rel_pos != "none" and (self.rope != "none" or not self.class_token or self.distilled):
+            raise ValueError("ViTConfig: rel_pos needs a class token and goes with neither rope nor distilled")
+        if self.img_width is not None and (self.rel_pos == "none" or self.abs_pos):
+            raise ValueError("ViTConfig: img_width (a rectangular grid) is for rel_pos models without an absolute embedding")
         if self.rope not in ("none", "axial", "mixed"):
             raise ValueError(f"ViTConfig: rope must be 'none', 'axial' or 'mixed', got {self.rope!r}")
         if self.rope != "none" and self.head_dim % 4:
@@ -115,8 +124,13 @@ class ViTConfig:
         return self.global_pool == "avg" if self.fc_norm is None else bool(self.fc_norm)
 
     @property
+    def grid(self):
+        """(gh, gw) of the model's own input: img_size is its height, and its width too unless img_width says otherwise"""
+        return self.img_size // self.patch_size, (self.img_width or self.img_size) // self.patch_size
+
+    @property
     def num_patches(self) -> int:
-        return (self.img_size // self.patch_size) ** 2
+        return self.grid[0] * self.grid[1]
 
     @property
     def head_dim(self) -> int:
@@ -161,6 +175,19 @@ class EvaViTConfig(RopeViTConfig):
                                           # `gamma_2` (None without layer_scale) with no ls1 / ls2 modules; a bias-free `qkv`
                                           # beside the parameters `q_bias` / `v_bias` (k has no bias); `attn.norm` = Identity
     qkv_split: bool = False               # `q_proj` / `k_proj` (no bias) / `v_proj` apart and `attn.qkv` None (qkv_fused=False)
+
+
+@dataclass(frozen=True)
+class RelPosViTConfig(EvaViTConfig):
+    """EvaViTConfig plus a learned relative position bias on the attention logits (BEiT / BEiTv2, timm's vit_relpos_* and
+    vit_srelpos_* line).  A subclass for NormViTConfig's reason.  (Keyword only in practice.)"""
+    rel_pos: str = "none"                 # "beit": every block's attention owns `relative_position_bias_table`
+                                          # [(2 gh - 1)(2 gw - 1) + 3, H] (three rows for the class token's pairs),
+                                          # `relative_position_index` and `_get_rel_pos_bias()`; "beit_shared": one model-level
+                                          # `rel_pos_bias` module (BEiT use_shared_rel_pos_bias); "relpos": every attention owns a
+                                          # `rel_pos` module with `get_bias()` and zero rows / columns for the prefix tokens
+                                          # (timm RelPosBias); "srelpos": one model-level `shared_rel_pos` of that kind
+    img_width: Optional[int] = None       # the input's width where it differs from img_size (its height): a rectangular grid
 
 
 # The model names BASELINE.json's configs use.
@@ -407,12 +434,30 @@ EVA_CONFIGS: Dict[str, ViTConfig] = {
     "vit_micro_eva_d40_patch14_56": EvaViTConfig(img_size=56, patch_size=14, embed_dim=320, depth=4, num_heads=8, num_classes=10,
                                                  mlp_ratio=2.0, mlp="swiglu", mlp_norm=True, rope="axial", eva_block=True),
 }
-ALL_CONFIG_TABLES = (CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS, MAP_CONFIGS, NORM_CONFIGS, ROPE_CONFIGS, EVA_CONFIGS)
+# Models with a relative position bias, in a table of their own for the same reason.
+_BEIT = dict(eva_block=True, abs_pos=False, global_pool="avg", rel_pos="beit")
+RELPOS_CONFIGS: Dict[str, ViTConfig] = {
+    # ---- the real checkpoints' dimensions.  timm is not importable where this was written: the entries are WRITTEN FROM MEMORY of
+    # timm 1.x AND ARE UNVERIFIED (the LayerScale init values and the pooling may be off) ----
+    "beit_base_patch16_224": RelPosViTConfig(embed_dim=768, depth=12, num_heads=12, layer_scale=0.1, **_BEIT),
+    "beit_large_patch16_224": RelPosViTConfig(embed_dim=1024, depth=24, num_heads=16, layer_scale=1e-5, **_BEIT),
+    "beitv2_base_patch16_224": RelPosViTConfig(embed_dim=768, depth=12, num_heads=12, layer_scale=1e-5, **_BEIT),
+    "vit_relpos_base_patch16_clsgap_224": RelPosViTConfig(embed_dim=768, depth=12, num_heads=12, abs_pos=False, global_pool="avg",
+                                                          fc_norm=False, rel_pos="relpos"),
+    # ---- micro models (not timm names).  BEiT's layout - q / v bias, gamma_1 / gamma_2, no absolute embedding, mean pool with
+    # fc_norm - with a table per block; its shared-bias twin; a rel_pos model with a class-token head; a 48 x 96 input (3 x 6
+    # grid: the only one on which exchanging dy and dx shows) ----
+    "beit_micro_patch16_64": RelPosViTConfig(**_MICRO, layer_scale=0.1, **_BEIT),
+    "beit_micro_shared_patch16_64": RelPosViTConfig(**_MICRO, layer_scale=0.1, **{**_BEIT, "rel_pos": "beit_shared"}),
+    "vit_micro_relpos_patch16_64": RelPosViTConfig(**_MICRO, abs_pos=False, rel_pos="relpos"),
+    "beit_micro_patch16_48x96": RelPosViTConfig(**{**_MICRO, "img_size": 48}, img_width=96, layer_scale=0.1, **_BEIT),
+}
+ALL_CONFIG_TABLES = (CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS, MAP_CONFIGS, NORM_CONFIGS, ROPE_CONFIGS, EVA_CONFIGS, RELPOS_CONFIGS)
 
 
 def config_of(name: str) -> ViTConfig:
-    """the built-in config of that name, from CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS, MAP_CONFIGS, NORM_CONFIGS, ROPE_CONFIGS or
-    EVA_CONFIGS"""
+    """the built-in config of that name, from CONFIGS, SWIGLU_CONFIGS, NOCLASS_CONFIGS, MAP_CONFIGS, NORM_CONFIGS, ROPE_CONFIGS,
+    EVA_CONFIGS or RELPOS_CONFIGS"""
     tables = ALL_CONFIG_TABLES
     for table in tables:
         if name in table:
@@ -442,9 +487,11 @@ def make_norm(cfg: "ViTConfig", dim: int) -> nn.Module:
 class PatchEmbed(nn.Module):
     def __init__(self, cfg: ViTConfig):
         super().__init__()
-        self.img_size = (cfg.img_size, cfg.img_size)
+        self.img_size = (cfg.img_size, cfg.img_width or cfg.img_size)
         self.patch_size = (cfg.patch_size, cfg.patch_size)
         self.num_patches = cfg.num_patches
+        if cfg.rel_pos != "none":      # timm PatchEmbed.grid_size (the other configs' modules stay as they were)
+            self.grid_size = cfg.grid
         self.proj = nn.Conv2d(cfg.in_chans, cfg.embed_dim, cfg.patch_size, cfg.patch_size)
         self.norm = make_norm(cfg, cfg.embed_dim) if cfg.embed_norm else nn.Identity()
 
@@ -505,10 +552,80 @@ class RotaryEmbedding(nn.Module):
         return torch.cat([ang.sin(), ang.cos()], -1).to(dev)
 
 
+def relative_position_index(gh: int, gw: int, class_token: bool) -> torch.Tensor:
+    """timm gen_relative_position_index: [n, n] (n = gh * gw, + 1 with class_token) indices into a table whose row
+    (dy + gh - 1) * (2 gw - 1) + (dx + gw - 1) holds the pair (query - key) = (dy, dx); with class_token three more rows: the class
+    query against a patch key, a patch query against the class key, class against class"""
+    ys, xs = torch.meshgrid(torch.arange(gh), torch.arange(gw), indexing="ij")
+    c = torch.stack([ys.reshape(-1), xs.reshape(-1)])                     # [2, n]
+    rel = c[:, :, None] - c[:, None, :]                                   # [2, n, n]: query - key
+    idx = (rel[0] + gh - 1) * (2 * gw - 1) + (rel[1] + gw - 1)
+    if not class_token:
+        return idx
+    T = (2 * gh - 1) * (2 * gw - 1)
+    out = torch.zeros(gh * gw + 1, gh * gw + 1, dtype=idx.dtype)
+    out[1:, 1:] = idx
+    out[0, 0:] = T
+    out[0:, 0] = T + 1
+    out[0, 0] = T + 2
+    return out
+
+
+class RelativePositionBias(nn.Module):
+    """BEiT's shared bias (timm `RelativePositionBias`, the model's `rel_pos_bias`): forward() returns [H, N, N], N = gh * gw + 1.
+    Written from memory of timm 1.x, unverified against an installed timm."""
+
+    def __init__(self, window_size, num_heads: int):
+        super().__init__()
+        gh, gw = window_size
+        self.window_size = (gh, gw)
+        self.window_area = gh * gw
+        self.relative_position_bias_table = nn.Parameter(torch.zeros((2 * gh - 1) * (2 * gw - 1) + 3, num_heads))
+        self.register_buffer("relative_position_index", relative_position_index(gh, gw, True), persistent=False)
+
+    def forward(self):
+        n = self.window_area + 1
+        return self.relative_position_bias_table[self.relative_position_index.view(-1)].view(n, n, -1).permute(2, 0, 1).contiguous()
+
+
+class RelPosBias(nn.Module):
+    """timm `RelPosBias` (the `rel_pos` of a vit_relpos attention, the `shared_rel_pos` of a vit_srelpos model): a table over the
+    patch pairs alone, get_bias() returns [1, H, N, N] with zero rows and columns for the prefix tokens.  From memory of timm 1.x."""
+
+    def __init__(self, window_size, num_heads: int, prefix_tokens: int = 0):
+        super().__init__()
+        gh, gw = window_size
+        self.window_size = (gh, gw)
+        self.window_area = gh * gw
+        self.prefix_tokens = prefix_tokens
+        self.relative_position_bias_table = nn.Parameter(torch.zeros((2 * gh - 1) * (2 * gw - 1), num_heads))
+        self.register_buffer("relative_position_index", relative_position_index(gh, gw, False), persistent=False)
+
+    def get_bias(self):
+        n = self.window_area
+        b = self.relative_position_bias_table[self.relative_position_index.view(-1)].view(n, n, -1).permute(2, 0, 1)
+        return F.pad(b, [self.prefix_tokens, 0, self.prefix_tokens, 0]).unsqueeze(0).contiguous()
+
+    def forward(self, attn, shared_rel_pos=None):
+        return attn + self.get_bias()
+
+
 class Attention(nn.Module):
     def __init__(self, dim: int, num_heads: int, qk_norm: bool = False, ln_eps: float = 1e-6, bias: bool = True,
-                 rotate_half: bool = False, num_prefix_tokens: int = 1, eva: bool = False, qkv_split: bool = False):
+                 rotate_half: bool = False, num_prefix_tokens: int = 1, eva: bool = False, qkv_split: bool = False,
+                 rel_pos: str = "none", grid=None):
         super().__init__()
+        if rel_pos == "beit":       # timm Beit Attention: the table, its index and _get_rel_pos_bias()
+            gh, gw = grid
+            self.window_size = (gh, gw)
+            self.relative_position_bias_table = nn.Parameter(torch.zeros((2 * gh - 1) * (2 * gw - 1) + 3, num_heads))
+            self.register_buffer("relative_position_index", relative_position_index(gh, gw, True), persistent=False)
+        elif rel_pos == "beit_shared":   # timm: the attributes exist and are None when the model owns the bias
+            self.window_size, self.relative_position_bias_table, self.relative_position_index = None, None, None
+        elif rel_pos == "relpos":   # timm RelPosAttention
+            self.rel_pos = RelPosBias(grid, num_heads, prefix_tokens=num_prefix_tokens)
+        elif rel_pos == "srelpos":
+            self.rel_pos = None
         self.rotate_half = rotate_half                  # the pairing of a rotary table handed to forward (timm Eva's attribute)
         self.num_prefix_tokens = num_prefix_tokens      # rows in front that carry no position
         self.num_heads = num_heads
@@ -530,7 +647,13 @@ class Attention(nn.Module):
         self.proj = nn.Linear(dim, dim, bias=bias)
         self.proj_drop = nn.Dropout(0.0)
 
-    def forward(self, x, rope=None):
+    def _get_rel_pos_bias(self):
+        """timm Beit Attention._get_rel_pos_bias: [1, H, N, N]"""
+        n = self.window_size[0] * self.window_size[1] + 1
+        b = self.relative_position_bias_table[self.relative_position_index.view(-1)].view(n, n, -1)
+        return b.permute(2, 0, 1).contiguous().unsqueeze(0)
+
+    def forward(self, x, rope=None, shared_rel_pos_bias=None):
         B, N, C = x.shape
         if self.qkv is None:
             qkv = torch.stack([self.q_proj(x), self.k_proj(x), self.v_proj(x)], 2)
@@ -544,7 +667,18 @@ class Attention(nn.Module):
             P = self.num_prefix_tokens
             q = torch.cat([q[:, :, :P], apply_rot_embed_cat(q[:, :, P:], rope, self.rotate_half)], 2)
             k = torch.cat([k[:, :, :P], apply_rot_embed_cat(k[:, :, P:], rope, self.rotate_half)], 2)
-        x = F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(B, N, C)
+        bias = None      # a learned relative position bias: the attention's own, the model's shared one, or (timm adds both) their sum
+        if getattr(self, "relative_position_bias_table", None) is not None:
+            bias = self._get_rel_pos_bias()
+        elif getattr(self, "rel_pos", None) is not None:
+            bias = self.rel_pos.get_bias()
+        if shared_rel_pos_bias is not None:
+            bias = shared_rel_pos_bias if bias is None else bias + shared_rel_pos_bias
+        if bias is None:
+            x = F.scaled_dot_product_attention(q, k, v)
+        else:
+            x = F.scaled_dot_product_attention(q, k, v, attn_mask=bias.to(q.dtype))
+        x = x.transpose(1, 2).reshape(B, N, C)
         if hasattr(self, "norm"):
             x = self.norm(x)
         return self.proj_drop(self.proj(x))
@@ -676,7 +810,8 @@ class Block(nn.Module):
         C = cfg.embed_dim
         self.norm1 = make_norm(cfg, C)
         self.attn = Attention(C, cfg.num_heads, cfg.qk_norm, cfg.ln_eps, cfg.bias, rotate_half=cfg.rope_half,
-                              num_prefix_tokens=cfg.num_prefix_tokens, eva=cfg.eva_block, qkv_split=cfg.qkv_split)
+                              num_prefix_tokens=cfg.num_prefix_tokens, eva=cfg.eva_block, qkv_split=cfg.qkv_split,
+                              **(dict(rel_pos=cfg.rel_pos, grid=cfg.grid) if cfg.rel_pos != "none" else {}))
         gamma = lambda: nn.Parameter(cfg.layer_scale * torch.ones(C)) if cfg.layer_scale else None
         if cfg.eva_block:      # timm EvaBlock: the LayerScale vectors are parameters of the block, None without init_values
             self.gamma_1 = gamma()
@@ -691,7 +826,17 @@ class Block(nn.Module):
             self.ls2 = LayerScale(C, cfg.layer_scale) if cfg.layer_scale else nn.Identity()
         self.drop_path2 = nn.Identity()
 
-    def forward(self, x, rope=None):
+    def forward(self, x, rope=None, shared_rel_pos_bias=None):
+        if shared_rel_pos_bias is not None or getattr(self.attn, "rel_pos", None) is not None or \
+                getattr(self.attn, "relative_position_bias_table", None) is not None:
+            # timm Beit Block / RelPosBlock: the model's shared bias (or None) goes to the attention beside x
+            a = self.attn(self.norm1(x), shared_rel_pos_bias=shared_rel_pos_bias)
+            g1, g2 = (getattr(self, "gamma_1", None), getattr(self, "gamma_2", None)) if not hasattr(self, "ls1") else (None, None)
+            a = self.ls1(a) if hasattr(self, "ls1") else (a if g1 is None else g1 * a)
+            x = x + self.drop_path1(a)
+            h = self.mlp(self.norm2(x))
+            h = self.ls2(h) if hasattr(self, "ls2") else (h if g2 is None else g2 * h)
+            return x + self.drop_path2(h)
         if not hasattr(self, "ls1"):      # timm EvaBlock.forward
             a = self.attn(self.norm1(x)) if rope is None else self.attn(self.norm1(x), rope=rope)
             x = x + self.drop_path1(a if self.gamma_1 is None else self.gamma_1 * a)
@@ -724,6 +869,14 @@ class VisionTransformer(nn.Module):
         g = cfg.img_size // cfg.patch_size
         self.rope = (RotaryEmbedding(cfg.head_dim, (g, g), cfg.rope, cfg.rope_half, cfg.num_heads, cfg.depth)
                      if cfg.rope != "none" else None)
+        if cfg.rel_pos == "beit_shared":      # timm Beit(use_shared_rel_pos_bias=True)
+            self.rel_pos_bias = RelativePositionBias(cfg.grid, cfg.num_heads)
+        elif cfg.rel_pos == "beit":
+            self.rel_pos_bias = None
+        elif cfg.rel_pos == "srelpos":        # timm VisionTransformerRelPos(shared_rel_pos=True)
+            self.shared_rel_pos = RelPosBias(cfg.grid, cfg.num_heads, prefix_tokens=cfg.num_prefix_tokens)
+        elif cfg.rel_pos == "relpos":
+            self.shared_rel_pos = None
         self.pos_drop = nn.Dropout(0.0)
         if cfg.global_pool not in ("token", "avg", "map"):
             raise ValueError(f"global_pool must be 'token', 'avg' or 'map', got {cfg.global_pool!r}")
@@ -761,7 +914,13 @@ class VisionTransformer(nn.Module):
     def forward_features(self, x):
         x = self._pos_embed(self.patch_embed(x))
         x = self.norm_pre(x)
-        if self.rope is None:
+        if self.cfg.rel_pos != "none":      # timm Beit / VisionTransformerRelPos.forward_features
+            shared = self.rel_pos_bias() if getattr(self, "rel_pos_bias", None) is not None else None
+            if getattr(self, "shared_rel_pos", None) is not None:
+                shared = self.shared_rel_pos.get_bias()
+            for blk in self.blocks:
+                x = blk(x, shared_rel_pos_bias=shared)
+        elif self.rope is None:
             x = self.blocks(x)
         else:      # timm Eva.forward_features: the table (a per-block slice of a mixed one) goes to every block
             emb = self.rope.get_embed()
@@ -891,6 +1050,17 @@ def synth_state_dict(cfg: ViTConfig, seed: int = 0, std: float = 0.02,
     if cfg.mlp_norm:             # after every other draw: the norm inside every MLP
         for i in range(cfg.depth):
             ln(f"blocks.{i}.mlp.norm", Hd)
+    if cfg.rel_pos != "none":    # after every other draw: the bias tables.  A FIXTURE CHOICE: standard deviation 1, not timm's
+        gh, gw = cfg.grid        # trunc_normal(.02), which would not move a logit - trained tables are of order one
+        rows = (2 * gh - 1) * (2 * gw - 1) + (3 if cfg.rel_pos.startswith("beit") else 0)
+        name = "relative_position_bias_table"
+        if cfg.rel_pos == "beit_shared":
+            sd["rel_pos_bias." + name] = nrm(rows, cfg.num_heads, s=1.0)
+        elif cfg.rel_pos == "srelpos":
+            sd["shared_rel_pos." + name] = nrm(rows, cfg.num_heads, s=1.0)
+        else:
+            for i in range(cfg.depth):
+                sd[f"blocks.{i}.attn." + ("rel_pos." if cfg.rel_pos == "relpos" else "") + name] = nrm(rows, cfg.num_heads, s=1.0)
     # Eva's spellings draw nothing: the tensors above under the names the modules have.  The packed qkv's rows are q, k, v in
     # that order; k has no bias in either spelling, and the values drawn for it are dropped
     for i in range(cfg.depth if (cfg.eva_block or cfg.qkv_split) else 0):

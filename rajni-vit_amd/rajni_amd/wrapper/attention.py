@@ -112,6 +112,30 @@ class RAJNIAttention(nn.Module):
         # the pairing of a model's rotary table (timm Eva's attribute; RAJNIViTWrapper reads it from every block).  This module's
         # own forward takes no table: the rotation of a RoPE model runs in the whole-forward plan only
         self.rotate_half = bool(getattr(attn, "rotate_half", False))
+        # a learned relative position bias (BEiT's table and _get_rel_pos_bias(), timm RelPosAttention's rel_pos module): the
+        # attributes stay, for the same reason, and RAJNIViTWrapper reads the bias through them.  This module's own forward takes
+        # no table either - the bias runs in the whole-forward plan only - and refuses to run without it
+        for name in ("relative_position_bias_table", "rel_pos", "window_size"):
+            if getattr(attn, name, None) is not None:
+                setattr(self, name, getattr(attn, name))
+        if getattr(attn, "relative_position_bias_table", None) is not None:
+            # BEiT: the table and its index buffer become this module's own, and _get_rel_pos_bias below is timm's gather - held,
+            # here and now, to what the wrapped attention's own method returns (a bias is recognised by what it computes)
+            index, get = getattr(attn, "relative_position_index", None), getattr(attn, "_get_rel_pos_bias", None)
+            if not callable(get):
+                self._get_rel_pos_bias = None      # RAJNIViTWrapper refuses the model, as it does without this wrapper
+            elif not isinstance(index, torch.Tensor) or index.dim() != 2:
+                raise NotImplementedError("RAJNIAttention: attn.relative_position_bias_table without an [n, n] "
+                                          "attn.relative_position_index: the bias cannot be read, and the model is not run without it")
+            else:
+                self.register_buffer("relative_position_index", index,
+                                     persistent="relative_position_index" not in getattr(attn, "_non_persistent_buffers_set", ()))
+                with torch.no_grad():
+                    theirs = get()
+                theirs = theirs[0] if theirs.dim() == 4 else theirs
+                if theirs.shape != self._get_rel_pos_bias().shape[1:] or not torch.equal(theirs, self._get_rel_pos_bias()[0]):
+                    raise NotImplementedError("RAJNIAttention: attn._get_rel_pos_bias() does not return "
+                                              "relative_position_bias_table[relative_position_index] as timm's BEiT attention does")
         self.keep_ratio = keep_ratio
         self.update = update
         # prefix tokens at the front of x (CLS + timm register tokens): always kept, never ranked.  RAJNIViTWrapper sets it
@@ -122,6 +146,13 @@ class RAJNIAttention(nn.Module):
         self.importance_query = "cls"
         self._packed = None
         self._packed_key = None
+
+    @torch.no_grad()
+    def _get_rel_pos_bias(self):
+        """timm Beit Attention._get_rel_pos_bias: [1, H, n, n]"""
+        n = self.relative_position_index.shape[0]
+        b = self.relative_position_bias_table[self.relative_position_index.reshape(-1)].view(n, n, -1)
+        return b.permute(2, 0, 1).contiguous().unsqueeze(0)
 
     # ---- weights in the layout the kernels want (rebuilt when parameters change) -------------
     def _weights(self, device, dtype):
@@ -148,6 +179,9 @@ class RAJNIAttention(nn.Module):
     def forward(self, x: torch.Tensor, prev_scores: Optional[torch.Tensor] = None):
         """x: [B, N, C] (already normed).  Returns out [B, Np, C], keep_idx [B, Np] int64,
         next_scores [B, Np]; Np = num_prefix_tokens + keep."""
+        if getattr(self, "relative_position_bias_table", None) is not None or getattr(self, "rel_pos", None) is not None:
+            raise NotImplementedError("RAJNIAttention: this attention has a relative position bias, which the module's own forward "
+                                      "does not apply: run the model through RAJNIViTWrapper's forward")
         nat.require_device(x, "x")
         B, N, Cc = x.shape
         w = self._weights(x.device, x.dtype)

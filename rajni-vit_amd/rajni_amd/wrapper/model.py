@@ -67,6 +67,7 @@ class PlanInput(NamedTuple):
     rop: object = None   # rajni_vit_rope
     rot: object = None   # the (cos, sin) tensors that record points to: a plan owns what it points to, whatever the cache evicts
     mln: object = None   # (rajni_vit_mlp_norm, the two pointer arrays it points to)
+    rel: object = None   # rajni_vit_relpos (its tensors live in the packed weights, which PlanRefs.W keeps alive)
 
 
 class PlanEntry(NamedTuple):
@@ -88,11 +89,12 @@ class PlanEntry(NamedTuple):
 # the interface: nat.check puts it into the error message.)
 _FORWARDS = ("rajni_vit_forward", "rajni_vit_forward_ext", "rajni_vit_forward_ext_prefix", "rajni_vit_forward_layers",
              "rajni_vit_forward_image", "rajni_vit_forward_query", "rajni_vit_forward_pool",
-             "rajni_vit_forward_norm", "rajni_vit_forward_rope", "rajni_vit_forward_mlpnorm")   # (ext, pre, lay, img, qry, apr, nrm, rop, mln)
+             "rajni_vit_forward_norm", "rajni_vit_forward_rope", "rajni_vit_forward_mlpnorm",
+             "rajni_vit_forward_relpos")                                   # (ext, pre, lay, img, qry, apr, nrm, rop, mln, rel)
 _SIZES = ("rajni_vit_workspace_bytes", "rajni_vit_workspace_bytes_prefix", "rajni_vit_workspace_bytes_image",
           "rajni_vit_workspace_bytes_query", "rajni_vit_workspace_bytes_pool",
           "rajni_vit_workspace_bytes_norm", "rajni_vit_workspace_bytes_rope",
-          "rajni_vit_workspace_bytes_mlpnorm")                                              # (pre, img, qry, apr, nrm, rop, mln)
+          "rajni_vit_workspace_bytes_mlpnorm", "rajni_vit_workspace_bytes_relpos")          # (pre, img, qry, apr, nrm, rop, mln, rel)
 NORM_MAX_C = 2048      # the row kernels hold a row in one wave's registers: C <= 64 lanes * 4 chunks * 8 elements
 
 
@@ -239,6 +241,131 @@ def rope_tables(m: nn.Module, heads: int, head_dim: int, depth: int, grid=None):
     with torch.no_grad():
         emb = get() if grid is None else get(shape=tuple(grid))
     return classify_rope_embed(emb, heads, head_dim, depth), emb
+
+
+# ---- a learned relative position bias on the attention logits (include/rajni_hip_relpos.h) --------------------------------
+# The module contract, WRITTEN FROM MEMORY OF timm 1.x AND UNVERIFIED against an installed timm (as the rotary contract is):
+#   BEiT              blocks[i].attn.relative_position_bias_table (a tensor) and blocks[i].attn._get_rel_pos_bias()
+#   vit_relpos        blocks[i].attn.rel_pos (a module) and its get_bias()
+#   shared            base_model.rel_pos_bias (a module, called: rel_pos_bias()) or base_model.shared_rel_pos.get_bias()
+# each returning the dense bias [H, n0, n0] (a leading batch axis of 1 is accepted) that timm adds to the scaled logits.  A bias
+# is recognised by what it computes: the dense tensor is decomposed (decompose_rel_pos_bias) and refused if it is not a function
+# of the patch offset with constant prefix rows and columns.
+REL_POS_ATTRS = ("relative_position_bias_table", "rel_pos")            # on an attention
+REL_POS_MODEL_ATTRS = ("rel_pos_bias", "shared_rel_pos")               # on the model
+
+
+def _attn_bias_source(attn: nn.Module, where: str):
+    """the callable that returns an attention's own dense bias, or None; an attribute outside the contract is refused"""
+    table, rp = getattr(attn, "relative_position_bias_table", None), getattr(attn, "rel_pos", None)
+    if table is not None and rp is not None:
+        raise NotImplementedError(f"{where}: attn.relative_position_bias_table together with attn.rel_pos: one bias per attention")
+    if table is not None:
+        get = getattr(attn, "_get_rel_pos_bias", None)
+        if not callable(get):
+            raise NotImplementedError(f"{where}: attn.relative_position_bias_table without a callable attn._get_rel_pos_bias(): the "
+                                      "bias cannot be read, and the model is not run without it")
+        return get
+    if rp is not None:
+        get = getattr(rp, "get_bias", None)
+        if not callable(get):
+            raise NotImplementedError(f"{where}: attn.rel_pos ({type(rp).__name__}) has no get_bias(): the bias cannot be read, and "
+                                      "the model is not run without it")
+        return get
+    return None
+
+
+def rel_pos_sources(m: nn.Module, blocks):
+    """(per-block callables or None, the shared callable or None).  Blocks that disagree on having a bias are refused."""
+    per = [_attn_bias_source(blk.attn, f"RAJNIViTWrapper: block {i}") for i, blk in enumerate(blocks)]
+    have = [g is not None for g in per]
+    if any(have) and not all(have):
+        raise NotImplementedError(f"RAJNIViTWrapper: block {have.index(True)} has a relative position bias and block "
+                                  f"{have.index(False)} has none: every block or no block")
+    shared = None
+    rpb, srp = getattr(m, "rel_pos_bias", None), getattr(m, "shared_rel_pos", None)
+    if rpb is not None and srp is not None:
+        raise NotImplementedError("RAJNIViTWrapper: base_model.rel_pos_bias together with base_model.shared_rel_pos")
+    if rpb is not None:
+        if not callable(rpb):
+            raise NotImplementedError(f"RAJNIViTWrapper: base_model.rel_pos_bias ({type(rpb).__name__}) is not callable: the shared "
+                                      "bias cannot be read, and the model is not run without it")
+        shared = rpb
+    elif srp is not None:
+        shared = getattr(srp, "get_bias", None)
+        if not callable(shared):
+            raise NotImplementedError(f"RAJNIViTWrapper: base_model.shared_rel_pos ({type(srp).__name__}) has no get_bias(): the "
+                                      "shared bias cannot be read, and the model is not run without it")
+    return (per if all(have) and per else None), shared
+
+
+def model_has_rel_pos(m: nn.Module, blocks) -> bool:
+    """any attribute of the contract is present and not None (cheap: the setters ask before a forward has described the model)"""
+    return any(getattr(m, a, None) is not None for a in REL_POS_MODEL_ATTRS) or \
+        any(getattr(blk.attn, a, None) is not None for blk in blocks for a in REL_POS_ATTRS)
+
+
+def dense_rel_pos_bias(get, heads: int, where: str) -> torch.Tensor:
+    """the dense bias a source returns, as fp32 [H, n0, n0] on the host"""
+    try:
+        with torch.no_grad():
+            b = get()
+    except Exception as e:      # (a getter that wants arguments, a module without a forward ...: outside the contract)
+        raise NotImplementedError(f"{where}: reading the bias failed ({type(e).__name__}: {e}): the model is not run without it") from None
+    if not isinstance(b, torch.Tensor):
+        raise NotImplementedError(f"{where}: the relative position bias is a {type(b).__name__}, not a tensor")
+    if b.dim() == 4 and b.shape[0] == 1:
+        b = b[0]
+    if b.dim() != 3 or b.shape[0] != heads or b.shape[1] != b.shape[2]:
+        raise NotImplementedError(f"{where}: the relative position bias must be [H, n0, n0] (or [1, H, n0, n0]) with H = {heads}, "
+                                  f"got {tuple(b.shape)}")
+    return b.detach().to(device="cpu", dtype=torch.float32)
+
+
+def decompose_rel_pos_bias(dense: torch.Tensor, gh: int, gw: int, P: int, where: str = "relative position bias"):
+    """dense [H, n0, n0] fp32, n0 = P + gh * gw -> (table [H, (2 gh - 1)(2 gw - 1)], prefix_q [H], prefix_k [H], prefix_qk [H]) of
+    include/rajni_hip_relpos.h, exactly: bit for bit the patch-patch part must depend on (dy, dx) = (query - key) alone and the
+    prefix rows and columns must be constant per head in each of the three categories.  A bias that fails is refused, naming the
+    first element that breaks the structure."""
+    H, n0 = dense.shape[0], dense.shape[1]
+    n = gh * gw
+    if n0 != P + n:
+        raise NotImplementedError(f"{where}: the bias covers {n0} tokens but the model has {P} prefix tokens and a {gh} x {gw} grid")
+    ys, xs = torch.meshgrid(torch.arange(gh), torch.arange(gw), indexing="ij")
+    ys, xs = ys.reshape(-1), xs.reshape(-1)
+    idx = (ys[:, None] - ys[None, :] + gh - 1) * (2 * gw - 1) + (xs[:, None] - xs[None, :] + gw - 1)      # [n, n]
+    patch = dense[:, P:, P:]
+    table = torch.zeros(H, (2 * gh - 1) * (2 * gw - 1), dtype=torch.float32)
+    table[:, idx.reshape(-1)] = patch.reshape(H, -1)        # every offset occurs: each entry is written (by some pair)
+
+    def first_bad(got, want, q0, k0, what):
+        bad = (got.view(torch.int32) != want.view(torch.int32)).nonzero()
+        if bad.numel():
+            h, q, k = (int(v) for v in bad[0])
+            raise NotImplementedError(f"{where}: not a function of the relative offset: element [head {h}, query {q + q0}, key "
+                                      f"{k + k0}] = {float(got[h, q, k])!r} but {what} holds {float(want[h, q, k])!r}")
+    first_bad(patch.contiguous(), table[:, idx].contiguous(), P, P, "another pair of the same offset (dy, dx)")
+    pq, pk, pqk = (torch.zeros(H, dtype=torch.float32) for _ in range(3))
+    if P:
+        pq, pk, pqk = dense[:, 0, P].clone(), dense[:, P, 0].clone(), dense[:, 0, 0].clone()
+        first_bad(dense[:, :P, P:].contiguous(), pq[:, None, None].expand(H, P, n).contiguous(), 0, P, "the first prefix-query / patch-key pair")
+        first_bad(dense[:, P:, :P].contiguous(), pk[:, None, None].expand(H, n, P).contiguous(), P, 0, "the first patch-query / prefix-key pair")
+        first_bad(dense[:, :P, :P].contiguous(), pqk[:, None, None].expand(H, P, P).contiguous(), 0, 0, "the first prefix / prefix pair")
+    return table, pq, pk, pqk
+
+
+def rel_pos_grid(m: nn.Module, blocks, n_patches: int):
+    """(gh, gw) of the model's own input: patch_embed.grid_size or an attention's window_size where it is a pair of that many
+    patches, else the integer square root"""
+    for gs in (getattr(m.patch_embed, "grid_size", None), getattr(blocks[0].attn, "window_size", None),
+               getattr(getattr(blocks[0].attn, "rel_pos", None), "window_size", None)):
+        if isinstance(gs, (tuple, list)) and len(gs) == 2 and all(isinstance(v, int) and v > 0 for v in gs) and gs[0] * gs[1] == n_patches:
+            return int(gs[0]), int(gs[1])
+    r = math.isqrt(n_patches)
+    if r * r != n_patches:
+        raise NotImplementedError(f"RAJNIViTWrapper: cannot tell the grid of a relative position bias over {n_patches} patches: "
+                                  "patch_embed.grid_size does not give it and it is not square")
+    return r, r
 
 
 def rope_layout(blocks) -> bool:
@@ -613,6 +740,9 @@ class RAJNIViTWrapper(nn.Module):
         ops.query_code(query)
         if query == "cls" and not model_has_class_token(self.m):
             raise ValueError('set_importance_query("cls"): the model has no class token; "mean" is its only importance query')
+        if query == "mean" and model_has_rel_pos(self.m, self.blocks):
+            raise NotImplementedError('set_importance_query("mean"): not supported on a model with a relative position bias - '
+                                      "importance is scored on the class row's biased logits, and a mean query has no position")
         if query != self.importance_query:
             self._drop_plans()
         self._query = query
@@ -626,6 +756,10 @@ class RAJNIViTWrapper(nn.Module):
         embedding is resampled to the input's token grid as timm's resample_abs_pos_embed does (bicubic, antialias; one native
         launch per new grid, cached), prefix rows passed through.  Off (the default unless the base model says otherwise) the
         wrapper takes square inputs at the embedding's own grid, plus the reference's `pos_embed[:, :N]` slice."""
+        if on and model_has_rel_pos(self.m, self.blocks):
+            raise NotImplementedError("set_dynamic_img_size(True): not supported on a model with a relative position bias - timm "
+                                      "resizes the bias table when the checkpoint is loaded, not per input; the model's own grid "
+                                      "(rectangular or not) works")
         if bool(on) != self._dynamic_img_size:
             self._dynamic_img_size = bool(on)
             self._drop_plans()
@@ -713,6 +847,9 @@ class RAJNIViTWrapper(nn.Module):
             raise NotImplementedError('set_weight_format("fp8_mfma"): not supported on a model with rotary position embeddings '
                                       '(model.rope): the e4m3 attention and its bounds were fitted to unrotated q and k ("fp8" '
                                       'weights work)')
+        if fmt == "fp8_mfma" and model_has_rel_pos(self.m, self.blocks):
+            raise NotImplementedError('set_weight_format("fp8_mfma"): not supported on a model with a relative position bias: the '
+                                      'e4m3 attention and its bounds were fitted to logits without a bias ("fp8" weights work)')
         if fmt == "fp8_mfma" and any(mlp_norm_module(blk.mlp) is not None for blk in self.blocks):
             raise NotImplementedError('set_weight_format("fp8_mfma"): not supported on a model with a norm inside the MLP (mlp.norm): '
                                       'the fp8 x fp8 FC1 epilogue scales the hidden rows for FC2 before the norm could run ("fp8" '
@@ -777,6 +914,10 @@ class RAJNIViTWrapper(nn.Module):
         if on and self._pool_kind() == "map":
             raise ValueError("set_last_block_cls_only: the model pools with global_pool='map'; the CLS-only last block never "
                              "forms the rows the attention pool reads")
+        if on and model_has_rel_pos(self.m, self.blocks):
+            raise NotImplementedError("set_last_block_cls_only: not supported on a model with a relative position bias - the "
+                                      "CLS-query kernel of that opt-in takes no bias (the default forward already computes the "
+                                      "last block for the rows the head reads)")
         if bool(on) != self._cls_only_last:
             self._cls_only_last = bool(on)
             self._drop_plans()
@@ -1016,6 +1157,36 @@ class RAJNIViTWrapper(nn.Module):
             if self._weight_format == "fp8_mfma":      # (the table was attached after the setter)
                 raise NotImplementedError('weight format "fp8_mfma" on a model with rotary position embeddings (model.rope) is '
                                           'not supported; "fp8" weights work')
+        # a learned relative position bias (rajni_vit_relpos): None, "block" (every attention has its own, with or without a
+        # shared one beside it) or "shared" (the model's alone), and the grid it is stated on.  Everything outside the native
+        # contract is refused here, on the host, before any launch
+        per, shared = rel_pos_sources(m, self.blocks)
+        desc["rel_pos"] = "block" if per else "shared" if shared else None
+        if desc["rel_pos"]:
+            what = "a model with a relative position bias"
+            if desc["D"] != 64:
+                raise NotImplementedError(f"RAJNIViTWrapper: {what} and head dim {desc['D']}: the bias kernels are head dim 64 only")
+            if self._weight_format == "fp8_mfma":
+                raise NotImplementedError(f'weight format "fp8_mfma" on {what} is not supported; "fp8" weights work')
+            if not has_cls or self.importance_query != "cls":
+                raise NotImplementedError(f"RAJNIViTWrapper: {what} " + ("without a class token" if not has_cls else
+                                          'with the mean importance query (set_importance_query("mean"))') + ": importance is "
+                                          "scored on the class row's biased logits, and a mean query has no position")
+            if self._dynamic_img_size:
+                raise NotImplementedError(f"RAJNIViTWrapper: {what} with dynamic_img_size: timm resizes the bias table when the "
+                                          "checkpoint is loaded, not per input")
+            if rope:
+                raise NotImplementedError(f"RAJNIViTWrapper: {what} that also has rotary position embeddings (model.rope): RoPE "
+                                          "together with a bias is not supported")
+            if self._cls_only_last:
+                raise NotImplementedError(f"RAJNIViTWrapper: {what} with set_last_block_cls_only(True): the CLS-query kernel of "
+                                          "that opt-in takes no bias")
+            first = dense_rel_pos_bias(per[0] if per else shared, heads, "RAJNIViTWrapper: relative position bias")
+            gh, gw = rel_pos_grid(m, self.blocks, first.shape[1] - num_prefix)
+            if gh > nat.RELPOS_MAX_GRID or gw > nat.RELPOS_MAX_GRID:
+                raise NotImplementedError(f"RAJNIViTWrapper: a relative position bias on a {gh} x {gw} grid: the cap is "
+                                          f"{nat.RELPOS_MAX_GRID} x {nat.RELPOS_MAX_GRID} patches")
+            desc["rel_pos_grid"] = (gh, gw)
         return desc
 
     def _all_params(self):
@@ -1195,6 +1366,23 @@ class RAJNIViTWrapper(nn.Module):
                 vd = ops.dequantize_fp8(qkv_w, qkv_s)[2 * C:3 * C]
                 blocks[-1]["attn_out_scale"] = ops.attention_out_scale(blocks[-1]["norm1_w"], blocks[-1]["norm1_b"], vd,
                                                                        blocks[-1]["qkv_b"][2 * C:3 * C])
+        if desc["rel_pos"]:
+            # rajni_vit_relpos: every block's dense bias - its own plus the shared one (timm adds both) - decomposed into the
+            # table and the three prefix values, fp32.  Packed here, once; the tables are parameters of the model, so a change
+            # re-packs them with everything else (the fingerprint above)
+            per, shared = rel_pos_sources(m, self.blocks)
+            gh, gw = desc["rel_pos_grid"]
+            sh = dense_rel_pos_bias(shared, desc["H"], "RAJNIViTWrapper: the shared relative position bias") if shared else None
+            parts = []
+            for i in range(desc["depth"] if per else 1):
+                where = f"RAJNIViTWrapper: block {i}: relative position bias" if per else "RAJNIViTWrapper: the shared relative position bias"
+                dense = dense_rel_pos_bias(per[i], desc["H"], where) if per else sh
+                if per and sh is not None:
+                    dense = dense + sh
+                parts.append(decompose_rel_pos_bias(dense, gh, gw, desc["num_prefix"], where))
+            stack = lambda j: torch.stack([p_[j] for p_ in parts]).to(device=device, dtype=torch.float32).contiguous()
+            W["rel_pos"] = dict(table=stack(0), prefix_q=stack(1), prefix_k=stack(2), prefix_qk=stack(3),
+                                block_stride=desc["H"] * (2 * gh - 1) * (2 * gw - 1) if per else 0)
         W["blocks"] = blocks
         self._weights, self._weights_key = W, key
         self._weights_sig, self._weights_cfg = sig, cfg_key
@@ -1359,12 +1547,22 @@ class RAJNIViTWrapper(nn.Module):
             rec.w, rec.b, rec.eps, rec.n = mw, mb, d["mlp_norm_eps"], d["hidden"]
             mln = (rec, mw, mb)
         mrec = mln[0] if mln else None
-        symbol, records = _native_call(_SIZES, pre, img, qry, apr, nrm, rop, mrec)
+        rel = None
+        if d["rel_pos"]:          # the relpos record beside the plan (rajni_vit_relpos); None: no bias, the entry points as ever
+            if (gh, gw) != d["rel_pos_grid"]:
+                raise ValueError(f"the model's relative position bias is stated on a {d['rel_pos_grid'][0]} x {d['rel_pos_grid'][1]} "
+                                 f"grid but the input yields {gh} x {gw} patches (the table is resized when a checkpoint is "
+                                 "loaded, not per input)")
+            rp = W["rel_pos"]
+            rel = nat.VitRelPos()
+            rel.table, rel.prefix_q, rel.prefix_k, rel.prefix_qk = (rp[k].data_ptr() for k in ("table", "prefix_q", "prefix_k", "prefix_qk"))
+            rel.block_stride, rel.gh, rel.gw = rp["block_stride"], gh, gw
+        symbol, records = _native_call(_SIZES, pre, img, qry, apr, nrm, rop, mrec, rel)
         nbytes = getattr(nat.lib(), symbol)(C.byref(plan), *records)
         if nbytes == 0 and symbol not in _SIZES[:2]:
             # the image, query, pool, norm, rope or mlp-norm record is refused: say why (the forward's own refusal; nothing is launched)
             dry = nat.VitExt(pool=nat.POOL_MAP) if apr is not None else None
-            forward, records = _native_call(_FORWARDS, dry, pre, None, img, qry, apr, nrm, rop, mrec)
+            forward, records = _native_call(_FORWARDS, dry, pre, None, img, qry, apr, nrm, rop, mrec, rel)
             nat.check(getattr(nat.lib(), forward)(C.byref(plan), *records, 16, 16, None), forward)
             raise nat.NativeError(f"{symbol} refused the plan")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
@@ -1397,7 +1595,7 @@ class RAJNIViTWrapper(nn.Module):
             cap_arr = (C.c_int * len(caps))(*caps)
             layers = (cap_arr, int(lnorm), int(lfill == "last"), (len(caps), B, n0, d["C"]))
         self._plan = PlanEntry(key, plan, PlanRefs(blocks, tc, ws, W, ext, qk, pre), bufs, counts, full_mode, out_shape, layers,
-                               PlanInput(img, pos, gh, gw, qry, apr, nrm, rop, rot, mln))
+                               PlanInput(img, pos, gh, gw, qry, apr, nrm, rop, rot, mln, rel))
         if len(self._plans) >= 4:     # workspaces are large: keep only a few batch shapes alive
             self._plans.pop(next(iter(self._plans)))
         self._plans[key] = self._plan
@@ -1532,6 +1730,8 @@ class RAJNIViTWrapper(nn.Module):
         return self._dynamic_img_size
 
     def _check_input_shape(self, x: torch.Tensor):
+        if x.dim() == 4 and x.shape[-1] != x.shape[-2] and not self._dynamic_img_size and model_has_rel_pos(self.m, self.blocks):
+            return      # a rectangular fixed grid: _build_plan holds the input to the grid the model's bias is stated on
         if x.dim() != 4 or (x.shape[-1] != x.shape[-2] and not self._dynamic_img_size):
             raise ValueError(f"expected images [B, C, S, S], got {tuple(x.shape)}"
                              + ("" if x.dim() != 4 else "; set_dynamic_img_size(True) takes [B, C, H, W]"))
@@ -1564,7 +1764,7 @@ class RAJNIViTWrapper(nn.Module):
                     lay.n, lay.blocks, lay.norm, lay.fill, lay.out, lay.slab_stride = len(cap_arr), cap_arr, lnorm, lfill, slabs.data_ptr(), 0
                 symbol, records = _native_call(_FORWARDS, entry.refs.ext, entry.refs.pre, lay, entry.input.img, entry.input.qry,
                                                entry.input.apr, entry.input.nrm, entry.input.rop,
-                                               entry.input.mln[0] if entry.input.mln else None)
+                                               entry.input.mln[0] if entry.input.mln else None, entry.input.rel)
                 nat.check(getattr(nat.lib(), symbol)(C.byref(entry.plan), *records, x.data_ptr(), out.data_ptr(),
                                                      nat.stream_ptr(x.device)), symbol)
                 return out if lay is None else (out, slabs)

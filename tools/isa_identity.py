@@ -5,7 +5,11 @@ summary (registers, LDS, scratch) behind it.  Lines that carry only file-wide nu
 section ordinals) are normalised; nothing else is.  Prints one line per kernel of NEW; exit status 1 when a kernel of OLD
 differs or is missing.
 
-    python tools/isa_identity.py old.s new.s
+    python tools/isa_identity.py old.s new.s [--map REGEX REPL ...]
+
+--map: a kernel that gained a template parameter has a new mangled name.  Each REGEX -> REPL pair (re.sub, in order) turns a
+symbol of NEW into the symbol it had in OLD; such a kernel is compared under its old name (its own name inside its body is
+rewritten the same way) and printed as `identical` / `DIFFERS` with `<- old symbol` behind it.
 """
 import hashlib
 import re
@@ -45,22 +49,33 @@ def kernels(path):
 
 
 def main():
-    old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
-    bad = 0
+    args = sys.argv[1:]
+    maps = []
+    while "--map" in args:
+        i = args.index("--map")
+        maps.append((re.compile(args[i + 1]), args[i + 2]))
+        del args[i:i + 3]
+    old, new = kernels(args[0]), kernels(args[1])
+    bad = n_same = n_new = 0
+    seen = set()
     for k in sorted(new):
-        h = hashlib.sha256(new[k].encode()).hexdigest()[:16]
-        if k not in old:
-            state = "NEW"
-        elif old[k] == new[k]:
-            state = "identical"
+        ko = k
+        for rx, repl in maps:
+            ko = rx.sub(repl, ko)
+        body = new[k].replace(k, ko) if ko != k else new[k]
+        h = hashlib.sha256(body.encode()).hexdigest()[:16]
+        if ko not in old:
+            state, n_new = "NEW", n_new + 1
+        elif old[ko] == body:
+            state, n_same = "identical", n_same + 1
         else:
             state, bad = "DIFFERS", bad + 1
-        print(f"{state:9s} {h} {len(new[k].splitlines()):6d} lines  {k}")
-    for k in sorted(set(old) - set(new)):
+        seen.add(ko)
+        print(f"{state:9s} {h} {len(body.splitlines()):6d} lines  {k}" + (f"  <- {ko}" if ko != k and ko in old else ""))
+    for k in sorted(set(old) - seen):
         print(f"MISSING   {k}")
         bad += 1
-    n_same = sum(1 for k in old if k in new and old[k] == new[k])
-    print(f"# {len(old)} kernels in old, {len(new)} in new: {n_same} identical, {len(set(new) - set(old))} new, {bad} differing or missing")
+    print(f"# {len(old)} kernels in old, {len(new)} in new: {n_same} identical, {n_new} new, {bad} differing or missing")
     return 1 if bad else 0
 
 
